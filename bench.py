@@ -17,6 +17,11 @@ the ``cpu_baseline`` leg (rank 0, N = 1).
 Other lines (same schema, not the headline metric): ``--forward-only --batch 256`` (BASELINE configs[1]), ``--dlm``
 (per-lineout super-Gaussian order: W tables by the FP64 MFMA GEMM), ``--free-form``, ``--config4`` (BASELINE configs[3]:
 2-D angular form factor, 256 x 256 f_e, 512 angles x 1024 wavelengths).
+
+``--dump-outputs DIR`` writes what the last timed step computed -- the arrays the caller of the timed path receives -- as
+DIR/<name>.npy (float64, rank 0).  The parameters and the noise are seeded, so the inputs of two runs with the same arguments are
+the same and their outputs can be compared one for one (the synthetic 'measured' spectra are the build's own forward model at the
+seeded truth parameters, so two builds see them to within that model's rounding).
 """
 from __future__ import annotations
 
@@ -36,6 +41,25 @@ FP64_PEAK = 78.6e12    # flop/s, AMD public spec for FP64 vector (not in the loc
 FLOP_PER_SPECTRUM = 13.0e6  # forward + adjoint, shared W table
 FLOP_PER_SPECTRUM_FWD = 4.3e6  # forward only (4 MFLOP of points + 0.3 MFLOP of instrument function)
 N_SIMD = 1024               # 256 CUs x 4 SIMDs: a VALU instruction occupies its SIMD's issue port for 4 cycles
+DUMP_LIMIT = 60_000_000     # bytes of array data --dump-outputs writes at most (64 MB with the .npy headers)
+DUMP_SEED = 20251004        # the fixed row sample of outputs larger than DUMP_LIMIT
+TIMING_RING = 65536         # launches tsff_enable_timing can keep
+
+
+def dump_outputs(path, arrays):
+    """{name: CUDA tensor or array} -> path/<name>.npy in float64.  When the arrays hold more than DUMP_LIMIT bytes, each one
+    with more than one row keeps the same fixed, seeded sample of its rows (sorted), so that [B, ...] outputs stay aligned."""
+    host = {k: (v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)).astype(np.float64, copy=False)
+            for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT:
+        for k, a in host.items():
+            if a.ndim >= 2 and a.shape[0] > 1:
+                n = max(1, int(a.shape[0] * DUMP_LIMIT / total))
+                host[k] = a[np.sort(np.random.default_rng(DUMP_SEED).choice(a.shape[0], n, replace=False))]
+    os.makedirs(path, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a))
 
 
 def self_launch(args) -> int:
@@ -166,16 +190,18 @@ def config4_main(args):
     def step():
         return eng.form_factor_2d(0, Xd, fd, ud_ang, va_ang, out=P)
 
-    steps, warm = max(1, min(args.steps, 10)), max(1, min(args.warmup, 2))
+    steps, warm = args.steps, max(1, min(args.warmup, 2))
     for _ in range(warm):
         step()
     torch.cuda.synchronize()
-    eng.enable_timing(steps)
+    eng.enable_timing(min(steps, TIMING_RING))
     t0 = time.perf_counter()
     for _ in range(steps):
         step()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"form_factor": P})
     kt = eng.kernel_times_ms()
     kavg_s = float(np.mean(kt)) * 1e-3
     l1_peak = eng.l1_read_peak_tbps()
@@ -255,7 +281,13 @@ def main():
     ap.add_argument("--spin-ms", type=float, default=300.0, help="untimed clock warm-up in front of the timed region: the step repeated for this many ms (0: none, the protocol of rounds 1 and 2)")
     ap.add_argument("--dlm-blocks", type=int, default=-1, help="--dlm: column blocks of the pipelined step (TSFF_OPT_DLM_BLOCKS; 1 = one stream)")
     ap.add_argument("--plan", type=int, default=0, help="launch plan bit mask (experiments): 0 automatic, 1 never interleave the features, 2 two-sweep kernel instead of the one-sweep one")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64; at most 64 MB in all, "
+                         "a fixed seeded sample of the rows of larger outputs).  Default path: loss_terms [3] and grad [P, B x gpus]; "
+                         "--free-form: grad [P + nvx, B x gpus]; --forward-only: ThryE, ThryI [B, 1024]; --config4 / --arts: form_factor")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
     if args.config4 or args.arts:
@@ -390,13 +422,19 @@ def main():
         for _ in range(int(np.ceil(args.spin_ms * 1e-3 / (dtc / args.steps)))):
             step()
         fence()
-    eng.enable_timing(max(args.steps, 1))
+    eng.enable_timing(min(args.steps, TIMING_RING))
     ar_i[0] = 0
     t0 = time.perf_counter()
     for _ in range(args.steps):
         out = step()
     fence()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:   # (before the PCIe-inclusive leg below reuses the packed buffer)
+        if args.forward_only:
+            dumped = {"ThryE": out[0], "ThryI": out[1]}
+        else:   # [3 loss sums | rows (trainable leaves, then f_e values for --free-form) x lineouts of the global batch]
+            dumped = {"loss_terms": out[:3], "grad": out[3:].view(-1, B * world)}
+        dump_outputs(args.dump_outputs, dumped)
     ktimes = eng.kernel_times_ms()
     if os.environ.get("TSFF_BENCH_KTRACE"):   # kernel time against the launch index of the timed burst (the device clock ramps under load)
         print("kernel_ms_by_launch " + " ".join("%.4f" % v for v in ktimes), file=sys.stderr)

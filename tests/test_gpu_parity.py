@@ -2,6 +2,7 @@
 the CPU oracle on the same seeded inputs.  Floating point (float64): tolerance 1e-5 relative as
 BASELINE.json's north_star states; most checks are far tighter and say so."""
 import copy
+import os
 
 import numpy as np
 import pytest
@@ -14,6 +15,7 @@ from tsadar_amd import _lib as L
 pytestmark = pytest.mark.gpu
 
 RTOL = 1e-5  # north_star tolerance
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 @pytest.fixture(scope="module")
@@ -74,7 +76,7 @@ def test_forward_reference_golden(torch_mod):
     eng = _engine(cfg, util.P9, activate=True)
     tp = ThomsonParams(cfg["parameters"], num_params=1, batch=True, activate=True)
     E, _ = eng.forward(tp.to_matrix(), np.array([1]), np.array([1]), np.array([0]), np.array([0]))
-    golden = np.load("tests/golden/ref_ThryE-1d.npy")
+    golden = np.load(os.path.join(GOLDEN, "ref_ThryE-1d.npy"))
     np.testing.assert_allclose(E.cpu().numpy(), golden, rtol=RTOL, atol=0)
 
 
@@ -388,7 +390,7 @@ def test_committed_golden_fixture(torch_mod):
     from tsadar_amd import ThomsonParams, tree
     from tsadar_amd.loss_function import LossFunction
 
-    z = np.load("tests/golden/oracle_fit_b4.npz")
+    z = np.load(os.path.join(GOLDEN, "oracle_fit_b4.npz"))
     B = 4
     cfg = decks.deck_fit(active=("Te", "ne", "Ti", "Va", "lam", "amp1"))
     cfg["optimizer"]["batch_size"] = B
@@ -610,7 +612,7 @@ def test_two_rank_sharded_fit_step_on_gpu(torch_mod, tmp_path):
     one = np.load(tmp_path / "single.npy")
     np.testing.assert_array_equal(r0[1:], one[1:])
     assert abs(r0[0] - one[0]) <= 1e-14 * abs(one[0])
-    z = np.load("tests/golden/oracle_fit_b4.npz")
+    z = np.load(os.path.join(GOLDEN, "oracle_fit_b4.npz"))
     gref = z["grad"][:, [0, 1, 2, 4, 5, 3]].T.reshape(-1)
     assert abs(r0[0] - float(z["loss"])) < 1e-9 * abs(float(z["loss"]))
     assert np.max(np.abs(r0[1:] - gref)) < 1e-7 * np.max(np.abs(gref))
@@ -1233,7 +1235,7 @@ def test_angular_vg_loss_finite_difference(torch_mod):
     # sensitivity amplifies rounding by ~500x per iteration; (ii) the run ends at a stationary point of the ORACLE's loss
     # with a lower value -- i.e. it stopped because the model has a minimum there, not because of a wrong gradient.
     cfg["parameters"]["electron"]["fe"]["active"] = False
-    fix = np.load("tests/golden/angular_lbfgs_oracle.npz")
+    fix = np.load(os.path.join(GOLDEN, "angular_lbfgs_oracle.npz"))
     truth2 = orc.init_normed_params(cfg["parameters"], 1, True)
     truth2["Te"] = truth2["Te"] - 0.2
     truth2["ne"] = truth2["ne"] + 0.12
@@ -1876,7 +1878,7 @@ def test_committed_golden_fixture_2d(torch_mod):
     from tsadar_amd import ThomsonParams
     from tsadar_amd.diagnostic import ThomsonScatteringDiagnostic
 
-    z = np.load("tests/golden/oracle_2d.npz")
+    z = np.load(os.path.join(GOLDEN, "oracle_2d.npz"))
     cfg = decks.deck_fit()
     sa = dict(sa=z["ff_sa"], weights=np.ones((2, 3)) / 3)
     eng = _engine(cfg, sa)
@@ -2078,8 +2080,8 @@ def test_reference_angular_decks_against_oracle_fixture(torch_mod, tag):
     from tsadar_amd import ThomsonParams
     from tsadar_amd.diagnostic import ThomsonScatteringDiagnostic
 
-    z = np.load("tests/golden/oracle_arts.npz")
-    cfg = json.load(open(f"tests/golden/{tag}_deck.json"))
+    z = np.load(os.path.join(GOLDEN, "oracle_arts.npz"))
+    cfg = json.load(open(os.path.join(GOLDEN, f"{tag}_deck.json")))
     sa = _angular_sa(cfg)   # (spectype "angular" for the geometry lookup, then "angular_full": test_angular_1v.py:53-58)
     n0, n1 = cfg["other"]["CCDsize"]
     batch = dict(e_data=np.ones((n0, n1)), i_data=np.ones((n0, n1)), noise_e=np.array([0]), noise_i=np.array([0]),

@@ -1,12 +1,16 @@
 """The oracle against every fixture the reference's own tests hold for this path:
 the golden vector of tests/test_forward/test_1d.py and the two dispersion-relation known-answer
 tests.  CPU only."""
+import os
+
 import numpy as np
 from scipy.signal import find_peaks
 
 import decks
 import util
 from oracle import tsadar_oracle as orc
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def test_reference_golden_vector():
@@ -17,7 +21,7 @@ def test_reference_golden_vector():
                  e_amps=np.array([1]), i_amps=np.array([1]))
     normed = orc.init_normed_params(cfg["parameters"], 1, activate=True)
     E, I, lE, lI = orc.ts_diag(cfg, util.P9, normed, batch)
-    golden = np.load("tests/golden/ref_ThryE-1d.npy")
+    golden = np.load(os.path.join(GOLDEN, "ref_ThryE-1d.npy"))
     np.testing.assert_allclose(E, golden, rtol=1e-4, atol=0)  # the reference's own criterion
     assert np.max(np.abs(E - golden) / np.abs(golden)) < 1e-9
     assert E.max() == golden.max() == 1.0104138361652801  # amp 1 -> 1.010414 through the "logit"
