@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define TSFF_ABI_VERSION 8
+#define TSFF_ABI_VERSION 9
 /* error codes (every entry point returns 0 or one of these; text via tsff_last_error):
  * -1 bad argument, -2 unsupported configuration / option, -3 not a differentiable leaf, -5 HIP runtime error,
  * -22 stale or foreign token of saved projection records (tsff_form_factor_2d_grad),
@@ -152,6 +152,10 @@ typedef struct tsff_handle tsff_handle;
 int tsff_create(const tsff_config *cfg, tsff_handle **out);
 void tsff_destroy(tsff_handle *h);
 const char *tsff_last_error(const tsff_handle *h); /* h == NULL: last tsff_create failure */
+/* the kernels the most recent entry point on h enqueued, in launch order, ';'-separated, each spelled like its demangled
+ * device symbol without "void tsff::" (e.g. "k_fused_prep<1>;k_spectrum_fused<1, 0, false, true>;k_fused_finish<1>");
+ * valid until the next call on h.  Recorded on the host: no device synchronisation. */
+const char *tsff_last_launch(const tsff_handle *h);
 int tsff_abi_version(void);
 int tsff_set_stream(tsff_handle *h, void *hip_stream);
 /* options.  TSFF_OPT_DENOM_MODE: denominators of the l1/l2 functionals in tsff_loss_grad -- 0 (default):

@@ -140,6 +140,21 @@ def deck_fit(points_per_pixel=1, nvx=128, m=2.0, active=("Te", "ne", "Ti", "Va",
             "A": {"val": 1.0, "active": False},
             "fract": {"val": 0.4, "active": False},
         }
+    elif n_ion in (3, 4):
+        # every Z, A, Ti and fraction distinct (a kernel that drops or swaps a species changes ThryI), every fraction >= 0.1;
+        # "Z" in `active` makes every species' Z trainable, "Ti_same_3" ties ion-3's Ti to ion-1's (ts_params.py:557-558)
+        species = [(8.0, 40.0, 0.2, 0.4), (1.0, 1.0, 0.3, 0.3), (6.0, 12.0, 0.25, 0.2), (2.0, 4.0, 0.35, 0.1)][:n_ion]
+        if n_ion == 3:
+            species[0] = species[0][:3] + (0.5,)
+        for s, (Z, A, Ti, fract) in enumerate(species):
+            P[f"ion-{s + 1}"] = {
+                "Ti": _p(Ti, "Ti" in active, 0.01, 1.0, same=(s == 2 and "Ti_same_3" in active)),
+                "Z": _p(Z, "Z" in active, 0.5, 25.0),
+                "A": {"val": A, "active": False},
+                "fract": {"val": fract, "active": False},
+            }
+    elif n_ion != 1:
+        raise ValueError(f"n_ion must be 1..4, got {n_ion}")
     return finish(cfg)
 
 

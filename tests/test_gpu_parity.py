@@ -210,6 +210,37 @@ def test_gradient_two_sweep_kernel(torch_mod, n_ion):
     _grad_case(torch_mod, active, names, B=2, seed=4 + n_ion, n_ion=n_ion, tweak=tweak, plan=2)
 
 
+@pytest.mark.parametrize("ppp", [1, 5])
+def test_gradient_two_sweep_kernel_dlm_order(torch_mod, ppp):
+    """The two-sweep kernel (plan bit 1: k_spectrum<1, 1, 1, ...>) on the reference's shipped active set {Te, ne, m, amp1, amp2,
+    lam} at 1 and 5 points per pixel against the autodiff twin."""
+    from oracle import tsadar_oracle_torch as ot
+
+    B = 2
+    names = ["Te", "ne", "m", "amp1", "amp2", "lam"]
+    cfg = decks.deck_fit(points_per_pixel=ppp, active=tuple(names), m=2.7)
+    sa = util.sa_fit(B)
+    batch = util.synthetic_batch(cfg, sa, B, seed=45)
+    normed = util.random_lineouts(cfg, B, seed=47, ranges=dict(m=(2.05, 4.4)))
+    i_norm, e_norm = orc.loss_norms(cfg, batch)
+    eng = _engine(cfg, sa)
+    eng.set_launch_plan(2)
+    w = eng.loss_weights(B, i_norm, e_norm, cfg["data"]["ion_loss_scale"])
+    gm = eng.slots.active.astype(np.uint8)
+    terms, grad, E, I = eng.loss_grad(util.normed_to_matrix(normed, 1), batch, w, gm, want_spectra=True)
+    torch_mod.cuda.synchronize()
+    assert any(k.startswith("k_spectrum<1, 1, 1, ") for k in eng.last_launch()), eng.last_launch()
+    val, ref, Eo, Io = ot.value_and_grad(cfg, sa, normed, batch, i_norm, e_norm, names)
+    assert util.rel_err(E.cpu().numpy(), Eo) < 1e-8 and util.rel_err(I.cpu().numpy(), Io) < 1e-7
+    assert abs(float(np.dot(terms.cpu().numpy(), w)) - val) < 1e-9 * abs(val)
+    g = grad.cpu().numpy()
+    G = util.matrix_to_named(g, names)
+    scale = max(np.max(np.abs(v)) for v in ref.values())
+    for k in names:
+        assert np.max(np.abs(G[k] - ref[k])) <= 1e-7 * scale, (k, G[k], ref[k])
+    assert np.all(g[:, gm == 0] == 0.0)
+
+
 def test_gradient_one_sweep_two_ions(torch_mod):
     """a15 by the one-sweep kernel with n_ion = 2 and one gradient point (4 x 13 Jacobian-row accumulators per thread)."""
     names = ["Te", "ne", "Ti_1", "Ti_2", "Z_1", "Z_2", "lam", "Va", "ud", "amp1", "amp2", "amp3"]
@@ -1399,6 +1430,18 @@ def test_launch_plans_agree(torch_mod):
                                               (3, 1, ("Te", "ne", "m", "amp1", "amp2", "lam")), (4, 1, ("Te", "ne", "Ti", "lam", "amp3")),
                                               (6, 1, ("Te", "ne", "Ti", "Va", "lam", "amp1"))])
 def test_rows_kernel_points_per_pixel(torch_mod, ppp, n_ion, active):
+    _rows_kernel_case(ppp, n_ion, active)
+
+
+@pytest.mark.parametrize("nvx", [128, 320])
+def test_rows_kernel_reference_shipped_deck(torch_mod, nvx):
+    """The reference's shipped deck shape: 5 points per pixel, {Te, ne, m, amp1, amp2, lam} trainable (configs/1d/defaults.yaml:112,
+    tests/test_inverse/test_1d_random.py:33-39), nvx 128 and the production 320 (configs/1d/inputs.yaml:52): the rows kernel with
+    the DLM order's tangent tables against the autodiff twin, every gradient column."""
+    _rows_kernel_case(5, 1, ("Te", "ne", "m", "amp1", "amp2", "lam"), nvx=nvx)
+
+
+def _rows_kernel_case(ppp, n_ion, active, nvx=128):
     """k_spectrum_rows (points_per_pixel > 1: the one-sweep kernel with its Jacobian rows in a global scratch array) against
     the two-sweep kernel on the same deck -- spectra and loss sums the same bits, gradient to 1e-11 -- and against the C++
     oracle; 5 points per pixel is the reference's default deck shape (tests/configs/1d-defaults.yaml:100); the third case
@@ -1407,9 +1450,11 @@ def test_rows_kernel_points_per_pixel(torch_mod, ppp, n_ion, active):
     from oracle import c_oracle as co
 
     dlm = "m" in active
-    cfg = decks.deck_fit(points_per_pixel=ppp, active=active, n_ion=n_ion, m=2.6 if dlm else 2.0)
+    cfg = decks.deck_fit(points_per_pixel=ppp, nvx=nvx, active=active, n_ion=n_ion, m=2.6 if dlm else 2.0)
     B = 3
     sa, batch, normed, i_norm, e_norm = _loss_setup(cfg, B, seed=500 + ppp)
+    if dlm:   # per-lineout DLM orders inside the table's range
+        normed["m"] = util.random_lineouts(cfg, B, seed=520 + ppp, ranges=dict(m=(2.1, 4.3)))["m"]
     rng = np.random.default_rng(510 + ppp)
     batch["noise_e"] = 0.02 * rng.random((B, 1024))
     batch["noise_i"] = 0.02 * rng.random((B, 1024))
@@ -1446,7 +1491,18 @@ def test_rows_kernel_points_per_pixel(torch_mod, ppp, n_ion, active):
     np.testing.assert_allclose(out[0][0], out[2][0], rtol=1e-14)
     np.testing.assert_allclose(out[0][1], out[2][1], rtol=1e-10, atol=1e-12 * np.abs(out[0][1]).max())   # (sums of 10^4 terms in another order)
     assert np.abs(out[0][1]).max() > 0.0
-    if not dlm:
+    if dlm:   # the DLM order is differentiated: the autodiff twin, loss, spectra and every gradient column
+        from oracle import tsadar_oracle_torch as ot
+
+        names = [k for k in ("Te", "ne", "m", "amp1", "amp2", "lam", "Ti_1", "Va") if eng.slots.active[util.slot_of(k)]]
+        val, ref, Eo, Io = ot.value_and_grad(cfg, sa, normed, batch, i_norm, e_norm, names)
+        assert util.rel_err(out[0][2], Eo) < 1e-8 and util.rel_err(out[0][3], Io) < 1e-7
+        assert abs(float(np.dot(out[0][0], w)) - val) < 1e-9 * abs(val)
+        G = util.matrix_to_named(out[0][1], names)
+        scale = max(np.max(np.abs(v)) for v in ref.values())
+        for k in names:
+            assert np.max(np.abs(G[k] - ref[k])) <= 1e-7 * scale, (k, G[k], ref[k])
+    else:
         sums, gref, Eo, Io = co.loss_grad(cfg, sa, X, batch, w=w, gmask=gm)
         assert util.rel_err(out[0][2], Eo) < 1e-8 and util.rel_err(out[0][3], Io) < 1e-7
         np.testing.assert_allclose(out[0][0], sums.sum(axis=0), rtol=1e-9)
@@ -2125,6 +2181,40 @@ def test_loss_grad_packed_layout(torch_mod):
     eng.set_launch_plan(0)
     with pytest.raises(L.TsffError, match="packed-output"):
         eng.loss_grad_packed(X, batch, w, gm, act, Bg, Bg - 2)   # columns past the end of the global batch
+
+
+def test_loss_grad_packed_config4_rank_shard(torch_mod):
+    """configs[4]'s per-rank workload: 32 768 lineouts over 8 ranks, this rank's 4096 at b_offset = 3 x 4096 -- every lineout's
+    packed gradient columns against the C++ dual-number oracle, every other column exactly 0, the packed rows equal to tsff_loss_grad's
+    gradient bit for bit."""
+    from oracle import c_oracle as co
+    from tsadar_amd import synthetic as S
+
+    B, Bg, off = 4096, 32768, 3 * 4096
+    cfg = S.baseline_deck(batch_size=B)
+    sa = util.sa_fit(B)
+    eng = _engine(cfg, sa)
+    rng = np.random.default_rng(S.SEED + 3)
+    truth = S.draw_params(cfg, B, rng)
+    batch = S.make_batch(eng, truth, rng)
+    guess = S.draw_params(cfg, B, rng)
+    X = guess.to_matrix()
+    hb = {k: (v.cpu().numpy() if v is not None else None) for k, v in batch.items()}
+    w = eng.loss_weights(Bg, float(hb["i_data"].max()), float(hb["e_data"].max()), cfg["data"]["ion_loss_scale"])
+    gm = guess.grad_mask()
+    act = [s for s in range(eng.NP) if gm[s]]
+    terms, grad, _, _ = eng.loss_grad(X, batch, w, gm)
+    packed, _, _ = eng.loss_grad_packed(X, batch, w, gm, act, Bg, off)
+    p = packed.cpu().numpy()
+    rows = p[3:].reshape(len(act), Bg)
+    g = grad.cpu().numpy()
+    assert np.array_equal(p[:3], terms.cpu().numpy())
+    assert np.array_equal(rows[:, off:off + B], g[:, act].T)
+    assert np.all(rows[:, :off] == 0.0) and np.all(rows[:, off + B:] == 0.0)
+    sums, gref, _, _ = co.loss_grad(cfg, sa, X, hb, w=w, gmask=gm, want_spectra=False)
+    np.testing.assert_allclose(p[:3], sums.sum(axis=0), rtol=1e-9)
+    for r, s in enumerate(act):   # per column: relative to the column's largest entry, every lineout of the shard
+        assert np.max(np.abs(rows[r, off:off + B] - gref[:, s])) < 1e-6 * np.max(np.abs(gref[:, s])), s
 
 
 @pytest.mark.parametrize("kind", ["epw", "iaw"])

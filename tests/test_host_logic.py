@@ -47,6 +47,42 @@ def test_ravel_order_is_the_reference_pytree_order():
     np.testing.assert_array_equal(tp.ravel_grad(tp.X), flat)
 
 
+def test_four_species_slots_ravel_order_and_physical_values():
+    """4 ion species (TSFF_MAX_ION): the ion slots of ThomsonParams, the reference's ravel order (every species' Ti then Z,
+    species after species), fraction renormalisation and Ti tying against orc.init_normed_params / orc.physical_params."""
+    cfg = decks.deck_fit(active=("Te", "ne", "Ti", "Z", "lam", "amp1", "Ti_same_3"), n_ion=4)
+    B = 3
+    P = cfg["parameters"]
+    # unnormalised fractions (renormalisation must divide by their sum, 1.25)
+    for s, f in enumerate((0.5, 0.375, 0.25, 0.125)):
+        P[f"ion-{s + 1}"]["fract"]["val"] = f
+    tp = ThomsonParams(P, num_params=B, batch=True, activate=True)
+    normed = orc.init_normed_params(P, B, True)
+    rng = np.random.default_rng(3)
+    for k in ("Te", "ne", "Ti_1", "Ti_2", "Ti_4", "Z_1", "Z_2", "Z_3", "Z_4"):
+        normed[k] = normed[k] + 0.3 * rng.standard_normal(B)   # distinct values per lineout and species
+    tp.X[:] = util.normed_to_matrix(normed, 4)
+    np.testing.assert_array_equal(tp.X[:, L.P_ION0 + 4 * 3 + L.ION_Z], normed["Z_4"])
+    phys = orc.physical_params(P, normed, True)
+    Pm = tp.physical_matrix()
+    for k, v in phys.items():
+        np.testing.assert_allclose(Pm[:, util.slot_of(k)], v, rtol=1e-15, err_msg=k)
+    np.testing.assert_allclose([Pm[0, util.slot_of(f"fract_{s}")] for s in (1, 2, 3, 4)], [0.4, 0.3, 0.2, 0.1], rtol=1e-15)
+    np.testing.assert_array_equal(Pm[:, util.slot_of("Ti_3")], Pm[:, util.slot_of("Ti_1")])   # ion-3 tied to ion-1
+    assert not np.array_equal(Pm[:, util.slot_of("Ti_2")], Pm[:, util.slot_of("Ti_1")])
+    assert list(tp.slots.ti_same) == [0, 0, 1, 0]
+    names = [n for n, _ in tp.slots.active_leaves]
+    assert names == [("electron", "Te"), ("electron", "ne"), ("ion-1", "Ti"), ("ion-1", "Z"), ("ion-2", "Ti"), ("ion-2", "Z"),
+                     ("ion-3", "Ti"), ("ion-3", "Z"), ("ion-4", "Ti"), ("ion-4", "Z"), ("general", "lam"), ("general", "amp1")]
+    diff, static = tree.partition(tp, tree.get_filter_spec(P, tp))
+    flat, unravel = tree.ravel_pytree(diff)
+    assert flat.shape == (12 * B,)
+    for i, (sp, k) in enumerate(names[2:10]):
+        s = int(sp.split("-")[1])
+        np.testing.assert_array_equal(flat[(2 + i) * B:(3 + i) * B], tp.X[:, util.slot_of(f"{k}_{s}")], err_msg=f"{sp}.{k}")
+    np.testing.assert_array_equal(tp.ravel_grad(tp.X), flat)
+
+
 def test_dlm_table_and_maxwellian():
     np.testing.assert_allclose(D.dlm_table(128), orc.dlm_table(128), rtol=1e-14)
     for m in (2.0, 2.5158, 4.99):

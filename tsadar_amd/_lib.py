@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtsff.so")
 LIB_PATH = os.environ.get("TSFF_LIBRARY", LIB_PATH)  # A/B experiments: another in-tree build of the same ABI
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 MAX_ION = 4
 NBINS = 1024
 NXI1 = 1024
@@ -104,6 +104,7 @@ _SIGNATURES = {
     "tsff_create": (C.c_int, [C.POINTER(TsffConfig), C.POINTER(_vp)]),
     "tsff_destroy": (None, [_vp]),
     "tsff_last_error": (C.c_char_p, [_vp]),
+    "tsff_last_launch": (C.c_char_p, [_vp]),
     "tsff_set_stream": (C.c_int, [_vp, _vp]),
     "tsff_set_option": (C.c_int, [_vp, C.c_int32, C.c_int32]),
     "tsff_reserve": (C.c_int, [_vp, C.c_int32]),

@@ -36,6 +36,7 @@ struct tsff_handle {
   int fe_mode = 0;
   hipStream_t stream = nullptr;
   std::string err;
+  std::string launched;   // tsff_last_launch: the kernels the current entry point enqueued, ';'-separated
   // static device arrays
   tsff::DevBuf etab;
   tsff::DevBuf omgs[2], lam_bin[2], filt, cos_sa, sa_rad, w_sa, zp, zpf, xi1, xi2, taps[2], ptaps[2], mask[2], p_scale, p_shift, p_sig,
@@ -119,10 +120,13 @@ static int fail(tsff_handle* h, int code, const char* fmt, ...) {
 
 // every entry point runs with the handle's device current (a handle is bound to the device that was current at
 // tsff_create) and restores the caller's device on return
+// (and starts the launch record of tsff_last_launch: the string keeps its capacity, so recording allocates nothing once a call's
+// names have fitted)
 struct DevGuard {
   int prev = -1;
-  explicit DevGuard(const tsff_handle* h) {
+  explicit DevGuard(tsff_handle* h) {
     if (!h) return;
+    h->launched.clear();
     int cur = -1;
     if (hipGetDevice(&cur) == hipSuccess && cur != h->device && hipSetDevice(h->device) == hipSuccess) prev = cur;
   }
@@ -130,6 +134,39 @@ struct DevGuard {
   DevGuard(const DevGuard&) = delete;
   DevGuard& operator=(const DevGuard&) = delete;
 };
+
+// tsff_last_launch: every kernel launch goes through TSFF_LAUNCH / TSFF_LAUNCH0, which append the kernel's name spelled like its
+// demangled device symbol (template arguments included, e.g. "k_spectrum_fused<1, 0, false, true>") to h->launched
+static void note_arg(std::string& s, bool v) { s += v ? "true" : "false"; }
+static void note_arg(std::string& s, int v) {
+  char b[16];
+  snprintf(b, sizeof b, "%d", v);
+  s += b;
+}
+template <class... A>
+static void note_launch(tsff_handle* h, const char* kernel, A... targs) {
+  std::string& s = h->launched;
+  if (!s.empty()) s += ';';
+  s += kernel;
+  if constexpr (sizeof...(A) > 0) {
+    int i = 0;
+    s += '<';
+    ((s += i++ ? ", " : "", note_arg(s, targs)), ...);
+    s += '>';
+  }
+}
+#define TSFF_UNPAREN(...) __VA_ARGS__
+// TSFF_LAUNCH(h, k_name, (template arguments), grid, block, smem, stream, kernel arguments...)
+#define TSFF_LAUNCH(h, K, TARGS, ...)                              \
+  do {                                                             \
+    note_launch((h), #K, TSFF_UNPAREN TARGS);                      \
+    hipLaunchKernelGGL((K<TSFF_UNPAREN TARGS>), __VA_ARGS__);      \
+  } while (0)
+#define TSFF_LAUNCH0(h, K, ...)                                    \
+  do {                                                             \
+    note_launch((h), #K);                                          \
+    hipLaunchKernelGGL(K, __VA_ARGS__);                            \
+  } while (0)
 
 #define TSFF_HIP(h, call)                                                                         \
   do {                                                                                            \
@@ -240,7 +277,7 @@ static int launch_prepare(tsff_handle* h, const double* fe_dev, int mode, const 
   switch (h->n_ion) {
 #define TSFF_CASE(N)                                                                                              \
   case N:                                                                                                         \
-    hipLaunchKernelGGL((k_fe_prepare<N>), grid, block, h->smem_prepare, h->stream, h->S, fe_dev, mode, params, ht, W, \
+    TSFF_LAUNCH(h, k_fe_prepare, (N), grid, block, h->smem_prepare, h->stream, h->S, fe_dev, mode, params, ht, W, \
                        fe_out);                                                                                   \
     break;
     TSFF_CASE(1) TSFF_CASE(2) TSFF_CASE(3) TSFF_CASE(4)
@@ -284,7 +321,7 @@ static int launch_tables_block(tsff_handle* h, const double* params, const doubl
   switch (h->n_ion) {
 #define TSFF_CASE(N)                                                                                               \
   case N:                                                                                                          \
-    hipLaunchKernelGGL((k_fe_vectors<N>), grid, block, h->smem_vectors, st, h->S, fe_b, h->fe_mode, par_b, ht_b, htm_b, X_b, cst_b); \
+    TSFF_LAUNCH(h, k_fe_vectors, (N), grid, block, h->smem_vectors, st, h->S, fe_b, h->fe_mode, par_b, ht_b, htm_b, X_b, cst_b); \
     break;
     TSFF_CASE(1) TSFF_CASE(2) TSFF_CASE(3) TSFF_CASE(4)
 #undef TSFF_CASE
@@ -296,11 +333,11 @@ static int launch_tables_block(tsff_handle* h, const double* params, const doubl
   if (nc == 4 && !(h->plan & 32)) {   // 128 x 144 tiles: no partial last round (k_wgemm_w); plan bit 5: the 128 x 128 form
     dim3 wgrid(8 * ((nM + 7) / 8) * ((kNXi2 + kGNw - 1) / kGNw));
     TSFF_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_wgemm_w), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWgemmWSmem));
-    hipLaunchKernelGGL(k_wgemm_w, wgrid, block, kWgemmWSmem, st, h->S.lg, X_b, cst_b, h->S.xi2, nb, W_b, Wm_b, h->kw_lo, h->kw_hi);
+    TSFF_LAUNCH0(h, k_wgemm_w, wgrid, block, kWgemmWSmem, st, h->S.lg, X_b, cst_b, h->S.xi2, nb, W_b, Wm_b, h->kw_lo, h->kw_hi);
   } else if (nc == 4)
-    hipLaunchKernelGGL(k_wgemm<4>, ggrid, block, 0, st, h->S.lg, X_b, cst_b, h->S.xi2, nb, W_b, Wm_b, h->kw_lo, h->kw_hi);
+    TSFF_LAUNCH(h, k_wgemm, (4), ggrid, block, 0, st, h->S.lg, X_b, cst_b, h->S.xi2, nb, W_b, Wm_b, h->kw_lo, h->kw_hi);
   else
-    hipLaunchKernelGGL(k_wgemm<2>, ggrid, block, 0, st, h->S.lg, X_b, cst_b, h->S.xi2, nb, W_b, Wm_b, h->kw_lo, h->kw_hi);
+    TSFF_LAUNCH(h, k_wgemm, (2), ggrid, block, 0, st, h->S.lg, X_b, cst_b, h->S.xi2, nb, W_b, Wm_b, h->kw_lo, h->kw_hi);
   TSFF_HIP(h, hipGetLastError());
   return 0;
 }
@@ -356,8 +393,8 @@ static void launch_fused(tsff_handle* h, const KCall& K, dim3 grid, size_t smem,
     const double* lrec = h->lrec.as<double>();
     // the lineout scalars of every item, one thread each (k_fused_prep), then the one-sweep kernel itself
     switch (h->n_ion) {
-      case 1: hipLaunchKernelGGL((k_fused_prep<1>), dim3((grid.x + 63) / 64), dim3(64), 0, h->stream, h->S, K.params, K.B, f0, nload, h->lrec.as<double>(), h->finrec.as<double>()); break;
-      case 2: hipLaunchKernelGGL((k_fused_prep<2>), dim3((grid.x + 63) / 64), dim3(64), 0, h->stream, h->S, K.params, K.B, f0, nload, h->lrec.as<double>(), h->finrec.as<double>()); break;
+      case 1: TSFF_LAUNCH(h, k_fused_prep, (1), dim3((grid.x + 63) / 64), dim3(64), 0, h->stream, h->S, K.params, K.B, f0, nload, h->lrec.as<double>(), h->finrec.as<double>()); break;
+      case 2: TSFF_LAUNCH(h, k_fused_prep, (2), dim3((grid.x + 63) / 64), dim3(64), 0, h->stream, h->S, K.params, K.B, f0, nload, h->lrec.as<double>(), h->finrec.as<double>()); break;
     }
     // one launch over the whole batch, or -- the pipelined DLM plan -- one per column block, each behind the event of its tables
     const int nblk = h->pipe_nblk > 1 ? h->pipe_nblk : 1;
@@ -370,7 +407,7 @@ static void launch_fused(tsff_handle* h, const KCall& K, dim3 grid, size_t smem,
         (void)hipStreamWaitEvent(h->stream, h->blk_ev[i], 0);
       }
       switch (h->n_ion) {
-#define TSFF_LF(N, Z, E) hipLaunchKernelGGL((k_spectrum_fused<N, GM, Z, E>), g, block, smem, h->stream, h->S, Kb, f0, flags, lrec)
+#define TSFF_LF(N, Z, E) TSFF_LAUNCH(h, k_spectrum_fused, (N, GM, Z, E), g, block, smem, h->stream, h->S, Kb, f0, flags, lrec)
 #define TSFF_CASE(N)                                     \
   case N:                                                \
     if (zh && ex) TSFF_LF(N, true, true);                \
@@ -394,7 +431,7 @@ static void launch_rows(tsff_handle* h, const KCall& K, dim3 grid, size_t smem, 
   if constexpr (GM <= 1) {
     const dim3 block(kHalf);
     switch (h->n_ion) {
-#define TSFF_LR(N, Z, E) hipLaunchKernelGGL((k_spectrum_rows<N, GM, Z, E, FWD>), grid, block, smem, h->stream, h->S, K, f0, flags, gmask, grad, scratch, tickets)
+#define TSFF_LR(N, Z, E) TSFF_LAUNCH(h, k_spectrum_rows, (N, GM, Z, E, FWD), grid, block, smem, h->stream, h->S, K, f0, flags, gmask, grad, scratch, tickets)
 #define TSFF_CASE(N)                          \
   case N:                                     \
     if (zh && ex) TSFF_LR(N, true, true);     \
@@ -529,7 +566,7 @@ static int launch_spectrum(tsff_handle* h, KCall& K, const uint8_t* gmask = null
         if (h->timing) TSFF_HIP(h, hipEventRecord(h->ev0[slot], h->stream));
         const dim3 pgrid((unsigned)((nitems + 63) / 64)), grid((unsigned)nitems);
         double* lrec = h->lrec.as<double>();
-#define TSFF_LFW(N, Z, E, P) hipLaunchKernelGGL((k_forward_pairs<N, Z, E, P>), grid, dim3(kHalf * (3 - P)), smem_f, h->stream, h->S, K, f0, flags, lrec)
+#define TSFF_LFW(N, Z, E, P) TSFF_LAUNCH(h, k_forward_pairs, (N, Z, E, P), grid, dim3(kHalf * (3 - P)), smem_f, h->stream, h->S, K, f0, flags, lrec)
 #define TSFF_CASE(N)                                                                                                                 \
   case N:                                                                                                                            \
     if (wide) {                                                                                                                      \
@@ -538,7 +575,7 @@ static int launch_spectrum(tsff_handle* h, KCall& K, const uint8_t* gmask = null
       else if (ex_f) TSFF_LFW(N, false, 2, 1);                                                                                       \
       else TSFF_LFW(N, false, 0, 1);                                                                                                 \
     } else {                                                                                                                         \
-      hipLaunchKernelGGL((k_fused_prep<N>), pgrid, dim3(64), 0, h->stream, h->S, K.params, K.B, f0, nload, lrec, h->finrec.as<double>()); \
+      TSFF_LAUNCH(h, k_fused_prep, (N), pgrid, dim3(64), 0, h->stream, h->S, K.params, K.B, f0, nload, lrec, h->finrec.as<double>()); \
       if (three && ex_f) TSFF_LFW(N, true, 2, 2);                                                                                    \
       else if (zh_f && ex_f) TSFF_LFW(N, true, 1, 2);                                                                                \
       else if (zh_f) TSFF_LFW(N, true, 0, 2);                                                                                        \
@@ -604,13 +641,13 @@ static int launch_spectrum(tsff_handle* h, KCall& K, const uint8_t* gmask = null
 #define TSFF_CASE(N)                                                                                          \
   case N:                                                                                                     \
     if (tpf256 && !zh)                                                                                        \
-      hipLaunchKernelGGL((k_spectrum<N, MODE, GM, kHalf, false>), grid, block, smem, h->stream, h->S, K, f0, nfeat, flags, \
+      TSFF_LAUNCH(h, k_spectrum, (N, MODE, GM, kHalf, false), grid, block, smem, h->stream, h->S, K, f0, nfeat, flags, \
                          gmask, grad);                                                                        \
     else if (tpf256)                                                                                          \
-      hipLaunchKernelGGL((k_spectrum<N, MODE, GM, kHalf>), grid, block, smem, h->stream, h->S, K, f0, nfeat, flags, gmask, \
+      TSFF_LAUNCH(h, k_spectrum, (N, MODE, GM, kHalf, true), grid, block, smem, h->stream, h->S, K, f0, nfeat, flags, gmask, \
                          grad);                                                                               \
     else                                                                                                      \
-      hipLaunchKernelGGL((k_spectrum<N, MODE, GM, 2 * kHalf>), grid, block, smem, h->stream, h->S, K, f0, nfeat, flags,    \
+      TSFF_LAUNCH(h, k_spectrum, (N, MODE, GM, 2 * kHalf, true), grid, block, smem, h->stream, h->S, K, f0, nfeat, flags,    \
                          gmask, grad);                                                                        \
     break;
       TSFF_CASE(1) TSFF_CASE(2) TSFF_CASE(3) TSFF_CASE(4)
@@ -638,6 +675,8 @@ extern "C" {
 int tsff_abi_version(void) { return TSFF_ABI_VERSION; }
 
 const char* tsff_last_error(const tsff_handle* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
+
+const char* tsff_last_launch(const tsff_handle* h) { return h ? h->launched.c_str() : ""; }
 
 int tsff_create(const tsff_config* c, tsff_handle** out) {
   if (!c || !out) return fail(nullptr, -1, "null argument");
@@ -667,6 +706,7 @@ int tsff_create(const tsff_config* c, tsff_handle** out) {
     return fail(nullptr, -4, "no HIP device: libtsff has no CPU fallback");
 
   tsff_handle* h = new tsff_handle();
+  h->launched.reserve(1024);
   auto bail = [&](int rc) { g_create_error = h->err; delete h; return rc; };
 #define TSFF_HIPC(call)                                                                        \
   do {                                                                                         \
@@ -960,8 +1000,8 @@ static int fp64_peak(tsff_handle* h, bool mfma, double* tflops) {
   float best = 1e30f;
   for (int r = 0; r < reps + 1; ++r) {
     TSFF_HIP(h, hipEventRecord(e0, h->stream));
-    if (mfma) hipLaunchKernelGGL(k_mfma_peak, dim3(blocks), dim3(kThreads), 0, h->stream, out.as<double>(), iters / 4, 0.999999, 1e-7);
-    else hipLaunchKernelGGL(k_fma_peak, dim3(blocks), dim3(kThreads), 0, h->stream, out.as<double>(), iters, 0.999999, 1e-7);
+    if (mfma) TSFF_LAUNCH0(h, k_mfma_peak, dim3(blocks), dim3(kThreads), 0, h->stream, out.as<double>(), iters / 4, 0.999999, 1e-7);
+    else TSFF_LAUNCH0(h, k_fma_peak, dim3(blocks), dim3(kThreads), 0, h->stream, out.as<double>(), iters, 0.999999, 1e-7);
     TSFF_HIP(h, hipEventRecord(e1, h->stream));
     TSFF_HIP(h, hipEventSynchronize(e1));
     float ms = 0.f;
@@ -990,7 +1030,7 @@ int tsff_l1_read_peak(tsff_handle* h, double* tbps) {
   float best = 1e30f;
   for (int r = 0; r < reps + 1; ++r) {
     TSFF_HIP(h, hipEventRecord(e0, h->stream));
-    hipLaunchKernelGGL(k_l1_peak, dim3(blocks), dim3(kThreads), 0, h->stream, src.as<double2>(), out.as<double>(), iters);
+    TSFF_LAUNCH0(h, k_l1_peak, dim3(blocks), dim3(kThreads), 0, h->stream, src.as<double2>(), out.as<double>(), iters);
     TSFF_HIP(h, hipEventRecord(e1, h->stream));
     TSFF_HIP(h, hipEventSynchronize(e1));
     float ms = 0.f;
@@ -1028,7 +1068,7 @@ int tsff_form_factor(tsff_handle* h, int32_t feature, const double* phys, const 
   switch (h->n_ion) {
 #define TSFF_CASE(N)                                                                                                 \
   case N:                                                                                                            \
-    hipLaunchKernelGGL((k_form_factor<N>), grid, block, h->smem_spectrum, h->stream, h->S, K, (int)feature,          \
+    TSFF_LAUNCH(h, k_form_factor, (N), grid, block, h->smem_spectrum, h->stream, h->S, K, (int)feature,          \
                        h->S.omgs[feature], h->S.npts, P);                                                            \
     break;
     TSFF_CASE(1) TSFF_CASE(2) TSFF_CASE(3) TSFF_CASE(4)
@@ -1073,17 +1113,17 @@ int tsff_form_factor_grad(tsff_handle* h, int32_t feature, const double* phys, c
     if (grad_fe) {                                                                                                   \
       TSFF_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_form_factor_adj<N, 2>),                        \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit));                  \
-      hipLaunchKernelGGL((k_form_factor_adj<N, 2>), grid, block, smem, h->stream, h->S, K, (int)feature,             \
+      TSFF_LAUNCH(h, k_form_factor_adj, (N, 2), grid, block, smem, h->stream, h->S, K, (int)feature,             \
                          h->S.omgs[feature], h->S.npts, Pbar, h->lbparts.as<double>());                              \
     } else {                                                                                                         \
       TSFF_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_form_factor_adj<N, 0>),                        \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit));                  \
-      hipLaunchKernelGGL((k_form_factor_adj<N, 0>), grid, block, smem, h->stream, h->S, K, (int)feature,             \
+      TSFF_LAUNCH(h, k_form_factor_adj, (N, 0), grid, block, smem, h->stream, h->S, K, (int)feature,             \
                          h->S.omgs[feature], h->S.npts, Pbar, h->lbparts.as<double>());                              \
     }                                                                                                                \
-    hipLaunchKernelGGL(k_lbacc_reduce, dim3(B * h->S.G), dim3(kThreads), 0, h->stream, h->lbparts.as<double>(), nworker, NLB, \
+    TSFF_LAUNCH0(h, k_lbacc_reduce, dim3(B * h->S.G), dim3(kThreads), 0, h->stream, h->lbparts.as<double>(), nworker, NLB, \
                        h->lbacc.as<double>());                                                                       \
-    hipLaunchKernelGGL((k_ff2d_lines_adj<N>), dim3((B + 63) / 64), dim3(64), 0, h->stream, h->S, phys, (int)feature, (int)B, \
+    TSFF_LAUNCH(h, k_ff2d_lines_adj, (N), dim3((B + 63) / 64), dim3(64), 0, h->stream, h->S, phys, (int)feature, (int)B, \
                        h->lbacc.as<double>(), grad_phys, 1);                                                         \
     break;
     TSFF_CASE(1) TSFF_CASE(2) TSFF_CASE(3) TSFF_CASE(4)
@@ -1093,15 +1133,15 @@ int tsff_form_factor_grad(tsff_handle* h, int32_t feature, const double* phys, c
   if (grad_fe) {
     if (nchunk > 1) {
       const long nw = (long)B * kNXi2, nh = (long)2 * B * nvx;
-      hipLaunchKernelGGL(k_sum_chunks, dim3((unsigned)std::min<long>((nw + kThreads - 1) / kThreads, 1024)), dim3(kThreads), 0, h->stream,
+      TSFF_LAUNCH0(h, k_sum_chunks, dim3((unsigned)std::min<long>((nw + kThreads - 1) / kThreads, 1024)), dim3(kThreads), 0, h->stream,
                          K.Wb_out, nw, (int)nchunk);
-      hipLaunchKernelGGL(k_sum_chunks, dim3((unsigned)std::min<long>((nh + kThreads - 1) / kThreads, 1024)), dim3(kThreads), 0, h->stream,
+      TSFF_LAUNCH0(h, k_sum_chunks, dim3((unsigned)std::min<long>((nh + kThreads - 1) / kThreads, 1024)), dim3(kThreads), 0, h->stream,
                          K.Hy_out, nh, (int)nchunk);
     }
     dim3 ggrid(kNXi1 / kGN, (2 * B + kGM - 1) / kGM);
-    hipLaunchKernelGGL(k_wgemm_t, ggrid, dim3(kThreads), 0, h->stream, h->S.lg, K.Wb_out, h->S.xi2, (int)B, h->Yt.as<double>());
+    TSFF_LAUNCH0(h, k_wgemm_t, ggrid, dim3(kThreads), 0, h->stream, h->S.lg, K.Wb_out, h->S.xi2, (int)B, h->Yt.as<double>());
     TSFF_HIP(h, hipGetLastError());
-    hipLaunchKernelGGL(k_fe_adjoint, dim3(B), dim3(kThreads), h->smem_adjoint, h->stream, h->S, K.ht, h->Yt.as<double>(),
+    TSFF_LAUNCH0(h, k_fe_adjoint, dim3(B), dim3(kThreads), h->smem_adjoint, h->stream, h->S, K.ht, h->Yt.as<double>(),
                        K.Wb_out, K.Hy_out, K.Hs_out, grad_fe);
     TSFF_HIP(h, hipGetLastError());
   }
@@ -1174,7 +1214,7 @@ static int form_factor_2d_impl(tsff_handle* h, int32_t feature, const double* ph
     const int ntab = shared_fe ? 1 : B;
     tstride = pad2d_doubles((int)nv);
     TSFF_HIP(h, h->fpad.ensure(tstride * ntab * sizeof(double)));
-    hipLaunchKernelGGL(k_pad2d, dim3(ntab), dim3(kThreads), 0, h->stream, fe2d, (int)nv, h->fpad.as<double>());
+    TSFF_LAUNCH0(h, k_pad2d, dim3(ntab), dim3(kThreads), 0, h->stream, fe2d, (int)nv, h->fpad.as<double>());
     TSFF_HIP(h, hipGetLastError());
     tables = h->fpad.as<double>() + pad2d_margin((int)nv);   // (the padded table behind its leading margin; per-lineout tables tstride apart)
   }
@@ -1200,24 +1240,24 @@ static int form_factor_2d_impl(tsff_handle* h, int32_t feature, const double* ph
       if (lds) {                                                                                                   \
         TSFF_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_form_factor_2d<N, true, kGL, true>),       \
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit));              \
-        hipLaunchKernelGGL((k_form_factor_2d<N, true, kGL, true>), grid, block, smem, h->stream, h->S, phys, table, (int)nv, \
+        TSFF_LAUNCH(h, k_form_factor_2d, (N, true, kGL, true), grid, block, smem, h->stream, h->S, phys, table, (int)nv, \
                            ud_angle_deg * kPi / 180.0, va_angle_deg * kPi / 180.0, (int)feature, lo, hi, P, proj); \
       } else {                                                                                                     \
         TSFF_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_form_factor_2d<N, false, kGG, true>),      \
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit));              \
-        hipLaunchKernelGGL((k_form_factor_2d<N, false, kGG, true>), grid, block, smem, h->stream, h->S, phys, table, (int)nv, \
+        TSFF_LAUNCH(h, k_form_factor_2d, (N, false, kGG, true), grid, block, smem, h->stream, h->S, phys, table, (int)nv, \
                            ud_angle_deg * kPi / 180.0, va_angle_deg * kPi / 180.0, (int)feature, lo, hi, P, proj); \
       }                                                                                                            \
     } else                                                                                                         \
     if (lds) {                                                                                                     \
       TSFF_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_form_factor_2d<N, true, kGL>),                    \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit));                \
-      hipLaunchKernelGGL((k_form_factor_2d<N, true, kGL>), grid, block, smem, h->stream, h->S, phys, table, (int)nv,    \
+      TSFF_LAUNCH(h, k_form_factor_2d, (N, true, kGL, false), grid, block, smem, h->stream, h->S, phys, table, (int)nv,\
                          ud_angle_deg * kPi / 180.0, va_angle_deg * kPi / 180.0, (int)feature, lo, hi, P);    \
     } else {                                                                                                       \
       TSFF_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_form_factor_2d<N, false, kGG>),                   \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit));                \
-      hipLaunchKernelGGL((k_form_factor_2d<N, false, kGG>), grid, block, smem, h->stream, h->S, phys, table, (int)nv,   \
+      TSFF_LAUNCH(h, k_form_factor_2d, (N, false, kGG, false), grid, block, smem, h->stream, h->S, phys, table, (int)nv,\
                          ud_angle_deg * kPi / 180.0, va_angle_deg * kPi / 180.0, (int)feature, lo, hi, P);    \
     }                                                                                                              \
     break;
@@ -1270,7 +1310,7 @@ int tsff_form_factor_2d_grad(tsff_handle* h, int32_t feature, const double* phys
   const double* table = fe2d;  // (one table shared by all lineouts: the 2-D path is never batched in the reference)
   if (!lds) {
     TSFF_HIP(h, h->fpad.ensure(pad2d_doubles((int)nv) * sizeof(double)));
-    hipLaunchKernelGGL(k_pad2d, dim3(1), dim3(kThreads), 0, h->stream, fe2d, (int)nv, h->fpad.as<double>());
+    TSFF_LAUNCH0(h, k_pad2d, dim3(1), dim3(kThreads), 0, h->stream, fe2d, (int)nv, h->fpad.as<double>());
     table = h->fpad.as<double>() + pad2d_margin((int)nv);
   }
   const long want = (long)h->ncu2d() * (lds ? 1 : 8);
@@ -1287,17 +1327,17 @@ int tsff_form_factor_2d_grad(tsff_handle* h, int32_t feature, const double* phys
     if (lds) {                                                                                                      \
       TSFF_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_form_factor_2d_adj<N, true, kGL>),            \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit));                 \
-      hipLaunchKernelGGL((k_form_factor_2d_adj<N, true, kGL>), grid, block, smem, h->stream, h->S, phys, table, (int)nv, ud, va, \
+      TSFF_LAUNCH(h, k_form_factor_2d_adj, (N, true, kGL), grid, block, smem, h->stream, h->S, phys, table, (int)nv, ud, va, \
                          (int)feature, pb, pe, Pbar, h->lbparts.as<double>(), f1bar, proj);                          \
     } else {                                                                                                        \
       TSFF_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_form_factor_2d_adj<N, false, kGG>),           \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit));                 \
-      hipLaunchKernelGGL((k_form_factor_2d_adj<N, false, kGG>), grid, block, smem, h->stream, h->S, phys, table, (int)nv, ud, va, \
+      TSFF_LAUNCH(h, k_form_factor_2d_adj, (N, false, kGG), grid, block, smem, h->stream, h->S, phys, table, (int)nv, ud, va, \
                          (int)feature, pb, pe, Pbar, h->lbparts.as<double>(), f1bar, proj);                          \
     }                                                                                                               \
-    hipLaunchKernelGGL(k_lbacc_reduce, dim3(B * h->S.G), dim3(kThreads), 0, h->stream, h->lbparts.as<double>(), nworker, NLB, \
+    TSFF_LAUNCH0(h, k_lbacc_reduce, dim3(B * h->S.G), dim3(kThreads), 0, h->stream, h->lbparts.as<double>(), nworker, NLB, \
                        h->lbacc.as<double>());                                                                      \
-    hipLaunchKernelGGL((k_ff2d_lines_adj<N>), dim3((B + 63) / 64), dim3(64), 0, h->stream, h->S, phys, (int)feature, (int)B, \
+    TSFF_LAUNCH(h, k_ff2d_lines_adj, (N), dim3((B + 63) / 64), dim3(64), 0, h->stream, h->S, phys, (int)feature, (int)B, \
                        h->lbacc.as<double>(), grad_phys, 0);                                                        \
     break;
     TSFF_CASE(1) TSFF_CASE(2) TSFF_CASE(3) TSFF_CASE(4)
@@ -1322,12 +1362,12 @@ static int table_adjoint_2d(tsff_handle* h, int nv, long npoint, double* grad_fe
   TSFF_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_ff2d_table_adj), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit));
   const size_t slab = (size_t)tmax * tmax;
   TSFF_HIP(h, h->fbar_parts.ensure((size_t)per_tile * ntiles * slab * sizeof(double)));
-  hipLaunchKernelGGL(k_ff2d_table_adj, dim3(per_tile, ntiles), dim3(4 * kThreads), smem, h->stream, nv, h->f1bar.as<double>(), npoint,
+  TSFF_LAUNCH0(h, k_ff2d_table_adj, dim3(per_tile, ntiles), dim3(4 * kThreads), smem, h->stream, nv, h->f1bar.as<double>(), npoint,
                      h->fbar_parts.as<double>(), slab);
   for (int t = 0; t < ntiles; ++t)   // one launch per tile, in order: the overlapping halos of neighbouring tiles add up without atomics
-    hipLaunchKernelGGL(k_ff2d_sum_tiles, dim3((unsigned)((slab + kThreads - 1) / kThreads)), dim3(kThreads), 0, h->stream, nv,
+    TSFF_LAUNCH0(h, k_ff2d_sum_tiles, dim3((unsigned)((slab + kThreads - 1) / kThreads)), dim3(kThreads), 0, h->stream, nv,
                        h->fbar_parts.as<double>(), (int)per_tile, slab, h->fbar_pad.as<double>(), t);
-  hipLaunchKernelGGL(k_ff2d_fold_ghosts, dim3(1), dim3(kThreads), 0, h->stream, nv, h->fbar_pad.as<double>(), grad_fe2d);
+  TSFF_LAUNCH0(h, k_ff2d_fold_ghosts, dim3(1), dim3(kThreads), 0, h->stream, nv, h->fbar_pad.as<double>(), grad_fe2d);
   TSFF_HIP(h, hipGetLastError());
   return 0;
 }
@@ -1362,12 +1402,12 @@ int tsff_ats_spectrum(tsff_handle* h, const double* P, const double* e_amps, dou
   double* M = h->ats_M.as<double>();
   double* A = h->ats_A.as<double>();
   double* Bm = h->ats_B.as<double>();
-  hipLaunchKernelGGL(k_ats_weights, grid, block, 0, h->stream, P, h->ats_w.as<double>(), h->S.filt, h->S.G, npts,
+  TSFF_LAUNCH0(h, k_ats_weights, grid, block, 0, h->stream, P, h->ats_w.as<double>(), h->S.filt, h->S.G, npts,
                      h->S.n_angles, npx, M);
-  hipLaunchKernelGGL(k_ats_conv, grid, block, 0, h->stream, M, h->ats_ta.as<double>(), h->ats_nta, h->ats_offa, 1, npx, npts, A);
-  hipLaunchKernelGGL(k_ats_conv, grid, block, 0, h->stream, A, h->ats_tl.as<double>(), h->ats_ntl, h->ats_offl, 0, npx, npts, Bm);
-  hipLaunchKernelGGL(k_ats_rownorm, dim3(npx), block, 0, h->stream, M, Bm, npts);
-  hipLaunchKernelGGL(k_ats_resunit, dim3(h->ats_row_end - h->ats_row_start), block, 0, h->stream, Bm, h->ats_lam.as<double>(),
+  TSFF_LAUNCH0(h, k_ats_conv, grid, block, 0, h->stream, M, h->ats_ta.as<double>(), h->ats_nta, h->ats_offa, 1, npx, npts, A);
+  TSFF_LAUNCH0(h, k_ats_conv, grid, block, 0, h->stream, A, h->ats_tl.as<double>(), h->ats_ntl, h->ats_offl, 0, npx, npts, Bm);
+  TSFF_LAUNCH0(h, k_ats_rownorm, dim3(npx), block, 0, h->stream, M, Bm, npts);
+  TSFF_LAUNCH0(h, k_ats_resunit, dim3(h->ats_row_end - h->ats_row_start), block, 0, h->stream, Bm, h->ats_lam.as<double>(),
                      npts, h->ats_lam_step, h->ats_ang_step, h->ats_row_start, e_amps, lam, amp1, amp2, ThryE);
   TSFF_HIP(h, hipGetLastError());
   return 0;
@@ -1393,20 +1433,20 @@ int tsff_ats_adjoint(tsff_handle* h, const double* P, const double* e_amps, doub
   double* stats = h->ats_stats.as<double>();
   double* ampb = stats + (size_t)npx * 4;
   // forward up to the unscaled convolved image
-  hipLaunchKernelGGL(k_ats_weights, grid, block, 0, h->stream, P, h->ats_w.as<double>(), h->S.filt, h->S.G, npts,
+  TSFF_LAUNCH0(h, k_ats_weights, grid, block, 0, h->stream, P, h->ats_w.as<double>(), h->S.filt, h->S.G, npts,
                      h->S.n_angles, npx, M);
-  hipLaunchKernelGGL(k_ats_conv, grid, block, 0, h->stream, M, h->ats_ta.as<double>(), h->ats_nta, h->ats_offa, 1, npx, npts, A);
-  hipLaunchKernelGGL(k_ats_conv, grid, block, 0, h->stream, A, h->ats_tl.as<double>(), h->ats_ntl, h->ats_offl, 0, npx, npts, Bm);
-  hipLaunchKernelGGL(k_ats_rowstats, dim3(npx), block, 0, h->stream, M, Bm, npts, stats);
+  TSFF_LAUNCH0(h, k_ats_conv, grid, block, 0, h->stream, M, h->ats_ta.as<double>(), h->ats_nta, h->ats_offa, 1, npx, npts, A);
+  TSFF_LAUNCH0(h, k_ats_conv, grid, block, 0, h->stream, A, h->ats_tl.as<double>(), h->ats_ntl, h->ats_offl, 0, npx, npts, Bm);
+  TSFF_LAUNCH0(h, k_ats_rowstats, dim3(npx), block, 0, h->stream, M, Bm, npts, stats);
   // reverse
   TSFF_HIP(h, hipMemsetAsync(Cb, 0, img, h->stream));
-  hipLaunchKernelGGL(k_ats_resunit_adj, dim3(rows), block, 0, h->stream, Bm, stats, h->ats_lam.as<double>(), npts, h->ats_lam_step,
+  TSFF_LAUNCH0(h, k_ats_resunit_adj, dim3(rows), block, 0, h->stream, Bm, stats, h->ats_lam.as<double>(), npts, h->ats_lam_step,
                      h->ats_ang_step, h->ats_row_start, e_amps, lam, amp1, amp2, Ebar, Cb, ampb);
-  hipLaunchKernelGGL(k_ats_rownorm_adj, dim3(npx), block, 0, h->stream, Bm, stats, npts, Cb, Db);              // Cb -> Bmbar, Db = Mbar one-hots
-  hipLaunchKernelGGL(k_ats_conv_adj, grid, block, 0, h->stream, Cb, h->ats_tl.as<double>(), h->ats_ntl, h->ats_offl, 0, npx, npts, 0, A);   // A = Abar
-  hipLaunchKernelGGL(k_ats_conv_adj, grid, block, 0, h->stream, A, h->ats_ta.as<double>(), h->ats_nta, h->ats_offa, 1, npx, npts, 1, Db);  // Db += conv^T
+  TSFF_LAUNCH0(h, k_ats_rownorm_adj, dim3(npx), block, 0, h->stream, Bm, stats, npts, Cb, Db);              // Cb -> Bmbar, Db = Mbar one-hots
+  TSFF_LAUNCH0(h, k_ats_conv_adj, grid, block, 0, h->stream, Cb, h->ats_tl.as<double>(), h->ats_ntl, h->ats_offl, 0, npx, npts, 0, A);   // A = Abar
+  TSFF_LAUNCH0(h, k_ats_conv_adj, grid, block, 0, h->stream, A, h->ats_ta.as<double>(), h->ats_nta, h->ats_offa, 1, npx, npts, 1, Db);  // Db += conv^T
   dim3 wgrid((h->S.n_angles + kThreads - 1) / kThreads, npts);
-  hipLaunchKernelGGL(k_ats_weights_adj, wgrid, block, 0, h->stream, Db, h->ats_w.as<double>(), h->S.filt, h->S.G, npts, h->S.n_angles,
+  TSFF_LAUNCH0(h, k_ats_weights_adj, wgrid, block, 0, h->stream, Db, h->ats_w.as<double>(), h->S.filt, h->S.G, npts, h->S.n_angles,
                      npx, Pbar);
   TSFF_HIP(h, hipGetLastError());
   // amp adjoints: sum over the rows (host: a few hundred numbers)
@@ -1510,16 +1550,16 @@ static int loss_grad_impl(tsff_handle* h, const double* params, const double* fe
     if (rc) return rc;
     if (parts) {
       const long nw = (long)B * kNXi2, nh = (long)2 * B * nvx;
-      hipLaunchKernelGGL(k_add_parts, dim3((unsigned)std::min<long>((nw + kThreads - 1) / kThreads, 1024)), dim3(kThreads), 0, h->stream,
+      TSFF_LAUNCH0(h, k_add_parts, dim3((unsigned)std::min<long>((nw + kThreads - 1) / kThreads, 1024)), dim3(kThreads), 0, h->stream,
                          K.Wb_out, K.Wb_out + nw, nw);
-      hipLaunchKernelGGL(k_add_parts, dim3((unsigned)std::min<long>((nh + kThreads - 1) / kThreads, 1024)), dim3(kThreads), 0, h->stream,
+      TSFF_LAUNCH0(h, k_add_parts, dim3((unsigned)std::min<long>((nh + kThreads - 1) / kThreads, 1024)), dim3(kThreads), 0, h->stream,
                          K.Hy_out, K.Hy_out + nh, nh);
       TSFF_HIP(h, hipGetLastError());
     }
     dim3 ggrid(kNXi1 / kGN, (2 * B + kGM - 1) / kGM);
-    hipLaunchKernelGGL(k_wgemm_t, ggrid, dim3(kThreads), 0, h->stream, h->S.lg, K.Wb_out, h->S.xi2, (int)B, h->Yt.as<double>());
+    TSFF_LAUNCH0(h, k_wgemm_t, ggrid, dim3(kThreads), 0, h->stream, h->S.lg, K.Wb_out, h->S.xi2, (int)B, h->Yt.as<double>());
     TSFF_HIP(h, hipGetLastError());
-    hipLaunchKernelGGL(k_fe_adjoint, dim3(B), dim3(kThreads), h->smem_adjoint, h->stream, h->S, K.ht, h->Yt.as<double>(),
+    TSFF_LAUNCH0(h, k_fe_adjoint, dim3(B), dim3(kThreads), h->smem_adjoint, h->stream, h->S, K.ht, h->Yt.as<double>(),
                        K.Wb_out, K.Hy_out, K.Hs_out, grad_fe);
     TSFF_HIP(h, hipGetLastError());
   } else {
@@ -1535,7 +1575,7 @@ static int loss_grad_impl(tsff_handle* h, const double* params, const double* fe
     switch (h->n_ion) {
 #define TSFF_CASE(N)                                                                                                          \
   case N:                                                                                                                     \
-    hipLaunchKernelGGL((k_fused_finish<N>), fgrid, dim3(kThreads), 0, h->stream, h->S, h->finrec.as<double>(), K.lbrec, K.lpart, (int)B, f0, nload, \
+    TSFF_LAUNCH(h, k_fused_finish, (N), fgrid, dim3(kThreads), 0, h->stream, h->S, h->finrec.as<double>(), K.lbrec, K.lpart, (int)B, f0, nload, \
                        with_m ? 1 : 0, h->gmask.as<uint8_t>(), grad, po ? nullptr : loss_terms, po ? h->act.as<int>() : nullptr,      \
                        po ? (int)po->n_act : 0, po ? (long)po->B_global : 0L, po ? (long)po->b_off : 0L, po ? po->packed : nullptr); \
     break;
@@ -1544,11 +1584,11 @@ static int loss_grad_impl(tsff_handle* h, const double* params, const double* fe
     }
   } else if (po) {
     const long n = (long)po->n_act * po->B_global;
-    hipLaunchKernelGGL(k_loss_reduce_packed, dim3((unsigned)std::max<long>(1, std::min<long>((n + kThreads - 1) / kThreads, 1024))), dim3(kThreads),
+    TSFF_LAUNCH0(h, k_loss_reduce_packed, dim3((unsigned)std::max<long>(1, std::min<long>((n + kThreads - 1) / kThreads, 1024))), dim3(kThreads),
                        0, h->stream, K.lpart, (int)B, parts ? K.gpart : nullptr, grad, h->S.NP, h->act.as<int>(), (int)po->n_act,
                        (long)po->B_global, (long)po->b_off, po->packed);
   } else {
-    hipLaunchKernelGGL(k_loss_reduce, dim3(parts ? (unsigned)std::min<long>((ng + kThreads - 1) / kThreads, 256) : 1), dim3(kThreads), 0,
+    TSFF_LAUNCH0(h, k_loss_reduce, dim3(parts ? (unsigned)std::min<long>((ng + kThreads - 1) / kThreads, 256) : 1), dim3(kThreads), 0,
                        h->stream, K.lpart, (int)B, loss_terms, parts ? K.gpart : nullptr, ng, grad);
   }
   TSFF_HIP(h, hipGetLastError());
@@ -1601,7 +1641,7 @@ int tsff_pack_fe_rows(tsff_handle* h, const double* loss_terms, const double* gr
     TSFF_HIP(h, hipMemcpy(h->act.p, h->act_host.data(), n_active * sizeof(int32_t), hipMemcpyHostToDevice));
   }
   const long tiles = ((B_global + 31) / 32) * ((n_active + h->S.nvx + 31) / 32);
-  hipLaunchKernelGGL(k_pack_fe_rows, dim3((unsigned)std::max<long>(1, std::min<long>(tiles, 2048))), dim3(kThreads), 0, h->stream, loss_terms, grad,
+  TSFF_LAUNCH0(h, k_pack_fe_rows, dim3((unsigned)std::max<long>(1, std::min<long>(tiles, 2048))), dim3(kThreads), 0, h->stream, loss_terms, grad,
                      h->S.NP, grad_fe, h->S.nvx, (int)B, h->act.as<int>(), (int)n_active, (long)B_global, (long)b_offset, packed);
   TSFF_HIP(h, hipGetLastError());
   return 0;

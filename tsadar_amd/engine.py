@@ -651,6 +651,12 @@ class Engine:
         bit 1: always the two-sweep kernel; bit 2: never three forward-only workgroups per CU."""
         L.check(self.lib, self.h, self.lib.tsff_set_option(self.h, L.OPT_LAUNCH_PLAN, int(plan)))
 
+    def last_launch(self) -> list:
+        """Names of the kernels the most recent library call on this engine enqueued, in launch order (tsff_last_launch),
+        spelled like their demangled device symbols, e.g. ["k_fused_prep<1>", "k_spectrum_fused<1, 0, false, true>", ...]."""
+        s = self.lib.tsff_last_launch(self.h).decode()
+        return s.split(";") if s else []
+
     def set_dlm_blocks(self, n: int):
         """TSFF_OPT_DLM_BLOCKS: column blocks of the pipelined DLM step (per-lineout tables of block i + 1 on a second stream while
         the one-sweep kernel works on block i).  0 / 1: off (default: measured slower on gfx950), n: n blocks.  Same bits."""
