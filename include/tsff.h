@@ -22,6 +22,7 @@
  *       generate_spectra.py:193-216, irf.py:5-47, thomson_diagnostic.py:78-107           tsff_ats_setup / tsff_ats_spectrum
  *   jax reverse mode through the above (equinox.filter_value_and_grad, loss_function.py:108)
  *       tsff_loss_grad(_fe), tsff_form_factor_grad, tsff_form_factor_2d_grad, tsff_ats_adjoint
+ *   LossFunction.h_loss_wrt_params (equinox.filter_hessian) inverse/loss_function.py:170-188  tsff_loss_hess
  *
  * Conventions
  *   - every array pointer in a *call* is a DEVICE pointer (hipMalloc'ed or a torch CUDA tensor);
@@ -43,7 +44,7 @@
 extern "C" {
 #endif
 
-#define TSFF_ABI_VERSION 9
+#define TSFF_ABI_VERSION 10
 /* error codes (every entry point returns 0 or one of these; text via tsff_last_error):
  * -1 bad argument, -2 unsupported configuration / option, -3 not a differentiable leaf, -5 HIP runtime error,
  * -22 stale or foreign token of saved projection records (tsff_form_factor_2d_grad),
@@ -309,6 +310,25 @@ int tsff_loss_grad_packed(tsff_handle *h, const double *params, const double *fe
                           const double *noise_i, int32_t B, const double *weights, const uint8_t *grad_mask,
                           const int32_t *active_slots, int32_t n_active, int64_t B_global, int64_t b_offset,
                           double *packed, double *ThryE, double *ThryI);
+
+/* Exact per-lineout Hessian of the fit loss: LossFunction._loss_for_hess_fn_ / h_loss_wrt_params
+ * (inverse/loss_function.py:170-188, equinox.filter_hessian) for every lineout b, with respect to the normalised leaves
+ * of the slots active_slots (HOST [n_active], ravel order).  The loss uses the denominators |data| + 1e-10 of
+ * loss_function.py:183 for l1 / l2, WHATEVER TSFF_OPT_DENOM_MODE says, sum reduce and the deck's loss_method.
+ *   weights (HOST [3]): as tsff_loss_grad (w_iaw, w_blue, w_red; w_blue = w_red = 1/2 halves e_error when both EPW ranges
+ *   are fitted, loss_function.py:262-264);
+ *   loss_terms (device [3]): un-weighted masked sums S_iaw, S_blue, S_red over the B lineouts;
+ *   grad (device [B][n_active]) and hess (device [B][n_active][n_active], symmetric): of sum_k weights[k] S_k.
+ * active_slots takes exactly the slots tsff_loss_grad takes in grad_mask: a slot out of range or repeated returns -1,
+ * TSFF_P_M without fe_mode == TSFF_FE_DLM -2, an ion's A slot -3; -2 as well when the tables of the path exceed the LDS
+ * of a workgroup (large nvx).  With TSFF_P_M active the second m-derivatives of the DLM tables are built per lineout
+ * (base.py:277-294: linear in m inside a cell, divided by its own sum).  Second-order forward mode (hyper-dual numbers)
+ * per (lineout, pair of active leaves): a fixed set of launches whatever n_active. */
+int tsff_loss_hess(tsff_handle *h, const double *params, const double *fe, const double *e_data, const double *i_data,
+                   const double *e_amps, const double *i_amps, const double *noise_e, const double *noise_i, int32_t B,
+                   const double *weights, const int32_t *active_slots, int32_t n_active, double *loss_terms,
+                   double *grad, double *hess);
+
 
 /* The same plus the gradient w.r.t. the tabulated distribution function itself: grad_fe [B][nvx] (device) =
  * d loss / d fe[b][i], for fe_mode == TSFF_FE_PER_LINEOUT.  This is what equinox.filter_value_and_grad returns for the

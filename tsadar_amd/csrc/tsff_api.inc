@@ -90,6 +90,8 @@ struct tsff_handle {
   std::vector<uint8_t> gmask_host;  // last gradient mask uploaded (re-sent only when it changes)
   tsff::DevBuf act, gradws;         // tsff_loss_grad_packed: active slots on the device, per-lineout gradient workspace
   std::vector<int32_t> act_host;
+  tsff::DevBuf hws, hout;          // tsff_loss_hess: hyper-dual spectra of the persistent workgroups, per-task sums
+  tsff::DevBuf htmm, Xmm, cstmm, Wmm, Wmm_unused;   // tsff_loss_hess with the DLM order m: second m-derivative tables
   size_t smem_adjoint = 0;
   tsff::DevBuf ats_w, ats_ta, ats_tl, ats_lam, ats_M, ats_A, ats_B, ats_C, ats_D, ats_stats;
   int ats_npx = 0, ats_nta = 0, ats_offa = 0, ats_ntl = 0, ats_offl = 0, ats_lam_step = 1, ats_ang_step = 1,
@@ -1643,6 +1645,98 @@ int tsff_pack_fe_rows(tsff_handle* h, const double* loss_terms, const double* gr
   const long tiles = ((B_global + 31) / 32) * ((n_active + h->S.nvx + 31) / 32);
   TSFF_LAUNCH0(h, k_pack_fe_rows, dim3((unsigned)std::max<long>(1, std::min<long>(tiles, 2048))), dim3(kThreads), 0, h->stream, loss_terms, grad,
                      h->S.NP, grad_fe, h->S.nvx, (int)B, h->act.as<int>(), (int)n_active, (long)B_global, (long)b_offset, packed);
+  TSFF_HIP(h, hipGetLastError());
+  return 0;
+}
+
+// exact per-lineout Hessian (k_hessian.inc): persistent k_hess_pairs over (lineout, pair of active leaves), k_hess_finish,
+// k_loss_reduce -- the same launches whatever the number of active leaves
+constexpr int kHessMaxWG = 1024;   // persistent workgroups of k_hess_pairs (bounds the scratch: 4 npts doubles each)
+int tsff_loss_hess(tsff_handle* h, const double* params, const double* fe, const double* e_data, const double* i_data,
+                   const double* e_amps, const double* i_amps, const double* noise_e, const double* noise_i, int32_t B,
+                   const double* weights, const int32_t* active_slots, int32_t n_active, double* loss_terms, double* grad,
+                   double* hess) {
+  DevGuard dg__(h);
+  if (!h) return -1;
+  if (!weights || !active_slots || !loss_terms || !grad || !hess || n_active < 1 || n_active > h->S.NP)
+    return fail(h, -1, "bad argument");
+  HessArgs A{};
+  A.n = n_active;
+  A.npair = n_active * (n_active + 1) / 2;
+  for (int k = 0; k < n_active; ++k) {
+    const int s = active_slots[k];
+    if (s < 0 || s >= h->S.NP) return fail(h, -1, "active slot %d out of range", s);
+    for (int q = 0; q < k; ++q)
+      if (active_slots[q] == s) return fail(h, -1, "active slot %d repeated", s);
+    A.slot[k] = s;
+  }
+  for (int k = 0; k < n_active; ++k) {
+    const int s = active_slots[k];
+    if (s == TSFF_P_M && h->fe_mode != TSFF_FE_DLM)
+      return fail(h, -2, "gradient w.r.t. the DLM order m needs fe_mode == TSFF_FE_DLM");
+    for (int i = 0; i < h->n_ion; ++i)
+      if (s == TSFF_P_ION0 + 4 * i + TSFF_ION_A) return fail(h, -3, "A is not a differentiable leaf (ts_params.py:296)");
+    if (s == TSFF_P_M) A.with_m = 1;
+  }
+  if ((long)B * A.npair > 0x7fffffffL) return fail(h, -1, "too many (lineout, pair) tasks");
+  A.tasks = B * A.npair;
+  KCall K{};
+  int rc = fill_call(h, K, params, fe, e_amps, i_amps, noise_e, noise_i, B, nullptr, nullptr);
+  if (rc) return rc;
+  if (h->S.load[0] && !e_data) return fail(h, -1, "e_data missing");
+  if (h->S.load[1] && !i_data) return fail(h, -1, "i_data missing");
+  K.data[0] = e_data; K.data[1] = i_data;
+  const size_t smem = sizeof(double) * hess_smem_doubles(h->S, A.with_m != 0);
+  if (smem > kLdsLimit)
+    return fail(h, -2, "tsff_loss_hess: LDS budget exceeded (%zu B with nvx = %d%s): reduce nvx", smem, h->S.nvx,
+                A.with_m ? " and the DLM order as a leaf" : "");
+  if (A.with_m) {   // second m-derivative tables: k_hess_mtab, then the shipped W-table GEMM on its rows
+    const size_t nvx = h->S.nvx;
+    TSFF_HIP(h, h->htmm.ensure((size_t)B * nvx * sizeof(double2)));
+    TSFF_HIP(h, h->Xmm.ensure((size_t)B * 4 * kNXi1 * sizeof(double)));
+    TSFF_HIP(h, h->cstmm.ensure((size_t)B * 2 * sizeof(double)));
+    TSFF_HIP(h, h->Wmm.ensure((size_t)B * kNXi2 * sizeof(double)));
+    TSFF_HIP(h, h->Wmm_unused.ensure((size_t)B * kNXi2 * sizeof(double)));
+    const size_t smem_t = sizeof(double2) * 6 * nvx + sizeof(double) * (nvx + 2 * kNXi1 + 8);
+    switch (h->n_ion) {
+#define TSFF_CASE(N)                                                                                                     \
+  case N:                                                                                                                \
+    TSFF_LAUNCH(h, k_hess_mtab, (N), dim3(B), dim3(kThreads), smem_t, h->stream, h->S, params, K.ht, K.htm, h->htmm.as<double2>(), \
+                h->Xmm.as<double>(), h->cstmm.as<double>());                                                             \
+    break;
+      TSFF_CASE(1) TSFF_CASE(2) TSFF_CASE(3) TSFF_CASE(4)
+#undef TSFF_CASE
+    }
+    TSFF_HIP(h, hipGetLastError());
+    const int nM = (B + kGM / 4 - 1) / (kGM / 4);
+    dim3 wgrid(8 * ((nM + 7) / 8) * ((kNXi2 + kGNw - 1) / kGNw));
+    TSFF_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_wgemm_w), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWgemmWSmem));
+    TSFF_LAUNCH0(h, k_wgemm_w, wgrid, dim3(kThreads), kWgemmWSmem, h->stream, h->S.lg, h->Xmm.as<double>(), h->cstmm.as<double>(),
+                 h->S.xi2, (int)B, h->Wmm.as<double>(), h->Wmm_unused.as<double>(), h->kw_lo, h->kw_hi);
+    TSFF_HIP(h, hipGetLastError());
+    A.htmm = h->htmm.as<double2>();
+    A.Wmm = h->Wmm.as<double>();
+  }
+  const int nwg = std::min(A.tasks, kHessMaxWG);
+  TSFF_HIP(h, h->hws.ensure((size_t)nwg * 4 * h->S.npts * sizeof(double)));
+  TSFF_HIP(h, h->hout.ensure((size_t)A.tasks * 12 * sizeof(double)));
+  switch (h->n_ion) {
+#define TSFF_CASE(N)                                                                                                        \
+  case N:                                                                                                                   \
+    TSFF_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_hess_pairs<N>), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                    (int)smem));                                                                            \
+    TSFF_LAUNCH(h, k_hess_pairs, (N), dim3(nwg), dim3(kThreads), smem, h->stream, h->S, K, A, h->hws.as<double>(),         \
+                h->hout.as<double>());                                                                                      \
+    break;
+    TSFF_CASE(1) TSFF_CASE(2) TSFF_CASE(3) TSFF_CASE(4)
+#undef TSFF_CASE
+  }
+  TSFF_HIP(h, hipGetLastError());
+  TSFF_LAUNCH0(h, k_hess_finish, dim3((B + kThreads - 1) / kThreads), dim3(kThreads), 0, h->stream, h->hout.as<double>(), A, (int)B,
+               weights[0], weights[1], weights[2], K.lpart, grad, hess);
+  TSFF_HIP(h, hipGetLastError());
+  TSFF_LAUNCH0(h, k_loss_reduce, dim3(1), dim3(kThreads), 0, h->stream, K.lpart, (int)B, loss_terms, (const double*)nullptr, 0L,
+               (double*)nullptr);
   TSFF_HIP(h, hipGetLastError());
   return 0;
 }

@@ -8,6 +8,7 @@
 //                                          chain rule to the normalised leaves
 //   k_loss_reduce  a14                   : deterministic reduction of the masked loss sums
 //   k_form_factor  a4-a10                : raw FormFactor.__call__ output (known-answer tests)
+//   k_hess_pairs   a16                   : exact per-lineout Hessian of the fit loss (hyper-dual forward mode, k_hessian.inc)
 #include "tsff_device.h"
 
 namespace tsff {
@@ -90,6 +91,7 @@ constexpr int kFusedMaxIon = 2;  // k_spectrum_fused is instantiated for n_ion <
 #include "k_form_factor_2d.inc"
 #include "k_ats.inc"
 #include "k_peak.inc"
+#include "k_hessian.inc"
 
 }  // namespace tsff
 

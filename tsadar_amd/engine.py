@@ -571,6 +571,33 @@ class Engine:
         L.check(self.lib, self.h, rc)
         return terms, grad, E, I
 
+    def loss_hess(self, params, batch, weights, active_slots, fe=None):
+        """Exact per-lineout Hessian of ``_loss_for_hess_fn_`` (denominators |data| + 1e-10 for l1 / l2, sum reduce) w.r.t. the
+        normalised leaves of ``active_slots`` (ravel order): -> (loss_terms[3], grad[B, P], hess[B, P, P]) as CUDA tensors of
+        sum_k weights[k] S_k; nothing is synchronised (tsff_loss_hess)."""
+        torch = self.torch
+        X = self.dev(params).reshape(-1, self.NP)
+        B = X.shape[0]
+        act = np.ascontiguousarray(active_slots, dtype=np.int32)
+        P = int(act.size)
+        ea = self._vec(batch["e_amps"], B) if self.load_ele else None
+        ia = self._vec(batch["i_amps"], B) if self.load_ion else None
+        ed = self._mat(batch["e_data"], B) if self.load_ele else None
+        idt = self._mat(batch["i_data"], B) if self.load_ion else None
+        ne_, ni_ = self._mat(batch.get("noise_e"), B), self._mat(batch.get("noise_i"), B)
+        fe_d = self.dev(fe)
+        terms = torch.empty(3, dtype=torch.float64, device=self.device)
+        grad = torch.empty((B, P), dtype=torch.float64, device=self.device)
+        hess = torch.empty((B, P, P), dtype=torch.float64, device=self.device)
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        self._sync_stream()
+        rc = self.lib.tsff_loss_hess(self.h, self._ptr(X), self._ptr(fe_d), self._ptr(ed), self._ptr(idt), self._ptr(ea),
+                                     self._ptr(ia), self._ptr(ne_), self._ptr(ni_), B, w.ctypes.data_as(L.c_double_p),
+                                     act.ctypes.data_as(C.POINTER(C.c_int32)), P, self._ptr(terms), self._ptr(grad),
+                                     self._ptr(hess))
+        L.check(self.lib, self.h, rc)
+        return terms, grad, hess
+
     def pack_fe_rows(self, terms, grad, gfe, active_slots, B_global=None, b_offset=0, out=None):
         """The packed buffer ``[3 | (P + nvx) x B_global]`` of a free-form f_e step from the outputs of ``loss_grad(want_fe_grad=True)``
         (tsff_pack_fe_rows: one transposing kernel, this rank's columns filled, the others zero)."""

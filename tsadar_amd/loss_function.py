@@ -395,7 +395,7 @@ class LossFunction:
         sqdev = {"ele": sqe.cpu().numpy(), "ion": sqi.cpu().numpy()}
         return total, sqdev, E.cpu().numpy(), I.cpu().numpy(), weights()
 
-    def h_loss_wrt_params(self, weights: ThomsonParams, batch: Dict, step: float = 1e-7):
+    def h_loss_wrt_params(self, weights: ThomsonParams, batch: Dict, step: float = 1e-7, method: str = "central"):
         """Hessian of the reference's ``_loss_for_hess_fn_`` (loss_function.py:173-188: denominators |data| + 1e-10,
         sum reduce, i_error + e_error) w.r.t. the trainable normalised leaves, in the nested layout
         ``get_sigmas`` reads (postprocess.py:188-251): ``hess[species][key][species2][key2]`` is a [B, B] matrix whose
@@ -406,29 +406,51 @@ class LossFunction:
         The step is small on purpose: JAX's second derivative of the piecewise-linear table lookups (Z', W) is
         zero inside a table cell, and a step of 1e-7 (normalised units) keeps nearly every sample inside its
         cell, so the difference quotient reproduces that convention (2e-6 relative against double-backward
-        autodiff of the oracle; with 1e-4 the curvature of the tables leaks in and entries change sign)."""
+        autodiff of the oracle; with 1e-4 the curvature of the tables leaks in and entries change sign).
+
+        ``method="exact"``: the exact Hessian in one device call (Engine.loss_hess, tsff_loss_hess: second-order forward
+        mode through the whole chain, the reference's table convention; ``step`` is unused).  Not built for angular decks
+        or for a free-form f_e among the trainable leaves.  With ``distributed=True`` both
+        methods compute this rank's lineouts: lineouts do not couple."""
+        if method not in ("central", "exact"):
+            raise ValueError(f"h_loss_wrt_params: unknown method {method!r} (central or exact)")
+        if method == "exact":
+            if getattr(self, "angular", False):
+                raise NotImplementedError("h_loss_wrt_params(method='exact') is not built for angular_full decks")
+            if getattr(weights, "fval", None) is not None and (weights.slots.fval_active or weights.slots.fval2d_active):
+                raise NotImplementedError("h_loss_wrt_params(method='exact'): the Hessian over the free-form f_e values "
+                                          "(nvx table leaves) is not built")
         eng = self.ts_diag.engine(weights.activate)
         X = weights.to_matrix()
         B = X.shape[0]
-        db = self._device_batch(eng, batch, B)
+        db = None if (method == "exact" and B == 0) else self._device_batch(eng, batch, B)
         c = 0.5 if (eng.fit_blue and eng.fit_red) else 1.0
         w = np.array([1.0 if eng.fit_iaw else 0.0, c if eng.fit_blue else 0.0, c if eng.fit_red else 0.0])
         leaves = weights.slots.active_leaves
         act = [s for _, s in leaves]
-        gm = weights.grad_mask()
-        H = np.zeros((B, len(act), len(act)))
-        eng.set_denominator_mode(2)
-        try:
-            for k, s in enumerate(act):
-                Xp, Xm = X.copy(), X.copy()
-                Xp[:, s] += step
-                Xm[:, s] -= step
-                gp = eng.loss_grad(Xp, db, w, gm)[1][:, act].cpu().numpy()
-                gn = eng.loss_grad(Xm, db, w, gm)[1][:, act].cpu().numpy()
-                H[:, :, k] = (gp - gn) / (2 * step)
-        finally:
-            eng.set_denominator_mode(0)
-        H = 0.5 * (H + np.transpose(H, (0, 2, 1)))
+        if method == "exact":
+            if B == 0:   # (an empty shard of a distributed fit: no lineouts, the layout below with [0, 0] blocks)
+                H = np.zeros((0, len(act), len(act)))
+            else:
+                from . import distribution as Dist
+
+                fe = Dist.arbitrary_1v(weights.fval) if weights.fval is not None else None
+                H = eng.loss_hess(X, db, w, act, fe=fe)[2].cpu().numpy()
+        else:
+            gm = weights.grad_mask()
+            H = np.zeros((B, len(act), len(act)))
+            eng.set_denominator_mode(2)
+            try:
+                for k, s in enumerate(act):
+                    Xp, Xm = X.copy(), X.copy()
+                    Xp[:, s] += step
+                    Xm[:, s] -= step
+                    gp = eng.loss_grad(Xp, db, w, gm)[1][:, act].cpu().numpy()
+                    gn = eng.loss_grad(Xm, db, w, gm)[1][:, act].cpu().numpy()
+                    H[:, :, k] = (gp - gn) / (2 * step)
+            finally:
+                eng.set_denominator_mode(0)
+            H = 0.5 * (H + np.transpose(H, (0, 2, 1)))
         hess = {}
         for a, ((sp1, k1), _) in enumerate(leaves):
             for b_, ((sp2, k2), _) in enumerate(leaves):
