@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 namespace tsff {
@@ -176,6 +177,58 @@ static void note_launch(tsff_handle* h, const char* kernel, A... targs) {
     if (e__ != hipSuccess) return fail((h), -5, "%s failed: %s", #call, hipGetErrorString(e__)); \
   } while (0)
 
+// kernels with more dynamic LDS than the default limit: the attribute is raised on exactly the instantiation that is launched
+// (TSFF_LAUNCH_LDS(h, k_name, (template arguments), attribute bytes, grid, block, smem, stream, kernel arguments...))
+#define TSFF_LDS_ATTR(h, KFN, BYTES) \
+  TSFF_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(KFN), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(BYTES)))
+#define TSFF_LAUNCH_LDS(h, K, TARGS, BYTES, ...)      \
+  do {                                                \
+    TSFF_LDS_ATTR(h, (K<TSFF_UNPAREN TARGS>), BYTES); \
+    TSFF_LAUNCH(h, K, TARGS, __VA_ARGS__);            \
+  } while (0)
+#define TSFF_LAUNCH0_LDS(h, K, BYTES, ...) \
+  do {                                     \
+    TSFF_LDS_ATTR(h, K, BYTES);            \
+    TSFF_LAUNCH0(h, K, __VA_ARGS__);       \
+  } while (0)
+
+// runtime value -> template argument: f(std::integral_constant<int, n>) for n in [1, MAX] (nothing otherwise), f(bool_constant)
+template <int MAX, class F>
+static auto with_ion(int n, F&& f) {
+  using R = decltype(f(std::integral_constant<int, 1>{}));
+  if constexpr (MAX > 1)
+    if (n < MAX) return with_ion<MAX - 1>(n, f);
+  if (n == MAX) return f(std::integral_constant<int, MAX>{});
+  return R();
+}
+template <class F>
+static auto with_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+
+// timing ring: one event pair per main-kernel launch (tsff_enable_timing), recorded on the handle's stream
+static size_t timing_slot(const tsff_handle* h) { return h->ev0.empty() ? 0 : h->ev_count % h->ev0.size(); }
+static int timing_begin(tsff_handle* h) {
+  if (h->timing) TSFF_HIP(h, hipEventRecord(h->ev0[timing_slot(h)], h->stream));
+  return 0;
+}
+static int timing_end(tsff_handle* h) {
+  if (h->timing) {
+    TSFF_HIP(h, hipEventRecord(h->ev1[timing_slot(h)], h->stream));
+    h->ev_count++;
+  }
+  return 0;
+}
+
+// the active slots of the packed outputs on the device; re-sent only when the list changes
+static int upload_slots(tsff_handle* h, const int32_t* act, int n) {
+  if (h->act_host.size() == (size_t)n && std::memcmp(h->act_host.data(), act, n * sizeof(int32_t)) == 0) return 0;
+  h->act_host.assign(act, act + n);
+  TSFF_HIP(h, h->act.ensure(kNP_MAX * sizeof(int32_t)));
+  // (pageable source that the next call may reassign: a synchronous copy of <= NP indices, once per change of the slot list)
+  TSFF_HIP(h, hipStreamSynchronize(h->stream));
+  TSFF_HIP(h, hipMemcpy(h->act.p, h->act_host.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
+  return 0;
+}
+
 template <class T>
 static hipError_t upload(DevBuf& b, const T* src, size_t n) {
   hipError_t e = b.ensure(n * sizeof(T) ? n * sizeof(T) : 8);
@@ -245,12 +298,14 @@ static hipError_t set_smem_attrs(size_t spec, size_t prep, size_t vec, size_t ad
   return hipSuccess;
 }
 
+constexpr size_t kRowsScratchMax = (size_t)16 << 30;   // the row scratch of k_spectrum_rows (larger: the two-sweep kernel)
+
 static int ensure_workspace(tsff_handle* h, int B, bool with_rows = false) {
   if (with_rows && h->S.ppp > 1 && h->S.G == 1 && h->n_ion <= 2) {
     // the row scratch of k_spectrum_rows (points_per_pixel > 1; the widest layout: DLM tangent component included), so that a
     // handle reserved through tsff_reserve allocates nothing in tsff_loss_grad (graph capture)
     const size_t need = (size_t)B * ((h->S.load[0] ? 1 : 0) + (h->S.load[1] ? 1 : 0)) * (9 + 3 * (size_t)h->n_ion) * h->S.npts * sizeof(double);
-    if (need <= ((size_t)16 << 30)) TSFF_HIP(h, h->rows.ensure(need));
+    if (need <= kRowsScratchMax) TSFF_HIP(h, h->rows.ensure(need));
   }
   if (B <= h->reserved_B) return 0;
   const int slots = h->fe_mode == TSFF_FE_SHARED ? 1 : B;
@@ -276,15 +331,9 @@ static int launch_prepare(tsff_handle* h, const double* fe_dev, int mode, const 
                           double2* ht, double* W, double* fe_out) {
   const int qsplit = slots >= 64 ? 1 : (slots >= 8 ? 4 : 16);
   dim3 grid(slots, qsplit), block(kThreads);
-  switch (h->n_ion) {
-#define TSFF_CASE(N)                                                                                              \
-  case N:                                                                                                         \
-    TSFF_LAUNCH(h, k_fe_prepare, (N), grid, block, h->smem_prepare, h->stream, h->S, fe_dev, mode, params, ht, W, \
-                       fe_out);                                                                                   \
-    break;
-    TSFF_CASE(1) TSFF_CASE(2) TSFF_CASE(3) TSFF_CASE(4)
-#undef TSFF_CASE
-  }
+  with_ion<TSFF_MAX_ION>(h->n_ion, [&](auto N) {
+    TSFF_LAUNCH(h, k_fe_prepare, (N.value), grid, block, h->smem_prepare, h->stream, h->S, fe_dev, mode, params, ht, W, fe_out);
+  });
   TSFF_HIP(h, hipGetLastError());
   return 0;
 }
@@ -320,22 +369,16 @@ static int launch_tables_block(tsff_handle* h, const double* params, const doubl
   double* X_b = h->X.as<double>() + (size_t)b0 * 4 * kNXi1; double* cst_b = h->cst.as<double>() + (size_t)b0 * 2;
   double* W_b = h->W.as<double>() + (size_t)b0 * kNXi2; double* Wm_b = h->Wm.as<double>() + (size_t)b0 * kNXi2;
   dim3 grid(nb), block(kThreads);
-  switch (h->n_ion) {
-#define TSFF_CASE(N)                                                                                               \
-  case N:                                                                                                          \
-    TSFF_LAUNCH(h, k_fe_vectors, (N), grid, block, h->smem_vectors, st, h->S, fe_b, h->fe_mode, par_b, ht_b, htm_b, X_b, cst_b); \
-    break;
-    TSFF_CASE(1) TSFF_CASE(2) TSFF_CASE(3) TSFF_CASE(4)
-#undef TSFF_CASE
-  }
+  with_ion<TSFF_MAX_ION>(h->n_ion, [&](auto N) {
+    TSFF_LAUNCH(h, k_fe_vectors, (N.value), grid, block, h->smem_vectors, st, h->S, fe_b, h->fe_mode, par_b, ht_b, htm_b, X_b, cst_b);
+  });
   TSFF_HIP(h, hipGetLastError());
   const int nc = h->fe_mode == TSFF_FE_DLM ? 4 : 2;  // explicit f_e tables carry no tangent vectors
   const int nM = (nb + kGM / nc - 1) / (kGM / nc), nQ = (kNXi2 + kGN - 1) / kGN;
   dim3 ggrid(8 * ((nM + 7) / 8) * nQ);
   if (nc == 4 && !(h->plan & 32)) {   // 128 x 144 tiles: no partial last round (k_wgemm_w); plan bit 5: the 128 x 128 form
     dim3 wgrid(8 * ((nM + 7) / 8) * ((kNXi2 + kGNw - 1) / kGNw));
-    TSFF_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_wgemm_w), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWgemmWSmem));
-    TSFF_LAUNCH0(h, k_wgemm_w, wgrid, block, kWgemmWSmem, st, h->S.lg, X_b, cst_b, h->S.xi2, nb, W_b, Wm_b, h->kw_lo, h->kw_hi);
+    TSFF_LAUNCH0_LDS(h, k_wgemm_w, kWgemmWSmem, wgrid, block, kWgemmWSmem, st, h->S.lg, X_b, cst_b, h->S.xi2, nb, W_b, Wm_b, h->kw_lo, h->kw_hi);
   } else if (nc == 4)
     TSFF_LAUNCH(h, k_wgemm, (4), ggrid, block, 0, st, h->S.lg, X_b, cst_b, h->S.xi2, nb, W_b, Wm_b, h->kw_lo, h->kw_hi);
   else
@@ -387,67 +430,6 @@ static int prepare_tables(tsff_handle* h, const double* params, const double* fe
   return 0;
 }
 
-// k_spectrum_fused for n_ion <= kFusedMaxIon (GM: 0 plasma parameters, 1 + the DLM order)
-template <int GM>
-static void launch_fused(tsff_handle* h, const KCall& K, dim3 grid, size_t smem, int f0, int flags, bool zh, bool ex, int nload) {
-  if constexpr (GM <= 1) {
-    const dim3 block(kHalf);
-    const double* lrec = h->lrec.as<double>();
-    // the lineout scalars of every item, one thread each (k_fused_prep), then the one-sweep kernel itself
-    switch (h->n_ion) {
-      case 1: TSFF_LAUNCH(h, k_fused_prep, (1), dim3((grid.x + 63) / 64), dim3(64), 0, h->stream, h->S, K.params, K.B, f0, nload, h->lrec.as<double>(), h->finrec.as<double>()); break;
-      case 2: TSFF_LAUNCH(h, k_fused_prep, (2), dim3((grid.x + 63) / 64), dim3(64), 0, h->stream, h->S, K.params, K.B, f0, nload, h->lrec.as<double>(), h->finrec.as<double>()); break;
-    }
-    // one launch over the whole batch, or -- the pipelined DLM plan -- one per column block, each behind the event of its tables
-    const int nblk = h->pipe_nblk > 1 ? h->pipe_nblk : 1;
-    for (int i = 0; i < nblk; ++i) {
-      KCall Kb = K;
-      dim3 g = grid;
-      if (nblk > 1) {
-        Kb.b0 = i * h->pipe_nb; Kb.B = std::min(h->pipe_nb, K.B - Kb.b0);
-        g = dim3((unsigned)(Kb.B * nload));
-        (void)hipStreamWaitEvent(h->stream, h->blk_ev[i], 0);
-      }
-      switch (h->n_ion) {
-#define TSFF_LF(N, Z, E) TSFF_LAUNCH(h, k_spectrum_fused, (N, GM, Z, E), g, block, smem, h->stream, h->S, Kb, f0, flags, lrec)
-#define TSFF_CASE(N)                                     \
-  case N:                                                \
-    if (zh && ex) TSFF_LF(N, true, true);                \
-    else if (zh) TSFF_LF(N, true, false);                \
-    else if (ex) TSFF_LF(N, false, true);                \
-    else TSFF_LF(N, false, false);                       \
-    break;
-        TSFF_CASE(1) TSFF_CASE(2)
-#undef TSFF_CASE
-#undef TSFF_LF
-      }
-    }
-    h->pipe_nblk = 0;
-  }
-}
-
-// k_spectrum_rows (points_per_pixel > 1) for n_ion <= kFusedMaxIon
-template <int GM, bool FWD = false>
-static void launch_rows(tsff_handle* h, const KCall& K, dim3 grid, size_t smem, int f0, int flags, bool zh, bool ex, const uint8_t* gmask,
-                        double* grad, double* scratch, unsigned* tickets) {
-  if constexpr (GM <= 1) {
-    const dim3 block(kHalf);
-    switch (h->n_ion) {
-#define TSFF_LR(N, Z, E) TSFF_LAUNCH(h, k_spectrum_rows, (N, GM, Z, E, FWD), grid, block, smem, h->stream, h->S, K, f0, flags, gmask, grad, scratch, tickets)
-#define TSFF_CASE(N)                          \
-  case N:                                     \
-    if (zh && ex) TSFF_LR(N, true, true);     \
-    else if (zh) TSFF_LR(N, true, false);     \
-    else if (ex) TSFF_LR(N, false, true);     \
-    else TSFF_LR(N, false, false);            \
-    break;
-      TSFF_CASE(1) TSFF_CASE(2)
-#undef TSFF_CASE
-#undef TSFF_LR
-    }
-  }
-}
-
 // Launch plan of k_spectrum.  Two loaded features:
 //   interleaved (default when two one-feature workgroups fit the LDS of a CU): ONE launch of 2B 256-thread workgroups,
 //     workgroup 2b + f evaluates feature f of lineout b; two workgroups per CU overlap each other's barriers, table
@@ -455,210 +437,241 @@ static void launch_rows(tsff_handle* h, const KCall& K, dim3 grid, size_t smem, 
 //   fused: both features in one 512-thread workgroup (one workgroup per CU) -- used when the LDS footprint does not
 //     allow two workgroups per CU (table-adjoint mode with large velocity grids, points_per_pixel > 1);
 //   split: one 512-thread launch per feature, the second accumulating into grad (LDS budget exceeded: points_per_pixel 5).
-// MODE 1 runs the one-sweep kernel k_spectrum_fused instead wherever its restrictions hold (see `fused` below).
+// MODE 1 runs the one-sweep kernel k_spectrum_fused instead wherever its restrictions hold (see plan_spectrum).
 // One loaded feature: 256-thread workgroups when two fit a CU, else 512.  The k_s cache is used when it still fits.
 // TSFF_OPT_LAUNCH_PLAN (bit mask): bit 0 never interleave (both features in one workgroup / split as the budget allows),
 // bit 1 never use the one-sweep kernel.
-template <int MODE, int GM = 0>
-static int launch_spectrum(tsff_handle* h, KCall& K, const uint8_t* gmask = nullptr, double* grad = nullptr,
-                           bool* used_gpart = nullptr, bool* used_lbrec = nullptr) {
-  const int nload = (h->S.load[0] ? 1 : 0) + (h->S.load[1] ? 1 : 0);
-  // (tpf: threads per feature of the instantiation the size is for -- 256-thread-per-feature workgroups with
-  //  points_per_pixel 1 keep the per-bin adjoint in the memory of the spectrum, alias_xy)
-  // (zh: Z' table held for xi >= 0 only, 13 KB less LDS for about 1 % more instructions -- used only when the full
-  //  table would cost the two-workgroups-per-CU plan)
-  // (forward-only calls need 139 VGPRs: THREE one-feature workgroups fit a CU's registers, and its LDS too with the half
-  //  Z' table and without the k_s cache -- 3 wavefronts per SIMD hide the lookups' latency better than 2: TSFF_OPT_LAUNCH_PLAN bit 2 off)
-  //  (only when there are more workgroups than two per CU: a grid that fits at two per CU gains nothing and pays for the half table)
-  // the one-sweep kernel (k_spectrum_fused.inc) wherever its restrictions hold: loss + gradient, one gradient point, one point
-  // per pixel, 256-thread one-feature workgroups, no table adjoints; with the base-point exchange (EX: 15 KB more LDS, n_angles
-  // <= 16) when two such workgroups still fit a CU (the half Z' table makes room)
-  // points_per_pixel > 1: the one-sweep kernel with its rows in a global scratch array (k_spectrum_rows.inc) -- one launch of
-  // 256-thread one-feature workgroups, two per CU (the full Z' table if that still fits, else the half table); the scratch is
-  // capped at kRowsScratchMax (larger batches fall back to the two-sweep kernel)
-  if constexpr (MODE == 1 && GM <= 1) {
-    if (h->S.G == 1 && h->S.ppp > 1 && h->n_ion <= kFusedMaxIon && !(h->plan & 2) && !h->S.raw[0] && !h->S.raw[1] && nload >= 1) {
+enum class SpectrumForm { rows, pairs, one_sweep, two_sweep };
+
+struct SpectrumPlan {
+  SpectrumForm form = SpectrumForm::two_sweep;
+  // zh: the half Z' table; ex: the base-point exchange; ks: the k_s cache; three: three workgroups per CU; wide: two workgroups
+  // per item (pair sweep); split: one workgroup per (lineout, feature, round); interleaved: both features' workgroups in one launch
+  bool zh = false, ex = false, ks = false, three = false, wide = false, split = false, interleaved = false;
+  int nfeat = 1, tpf = kHalf;   // features per workgroup, threads per feature
+  size_t smem = 0;
+  dim3 grid, block;
+  size_t rows = 0, tickets = 0, gpart = 0, lbrec = 0, lrec = 0, finrec = 0;   // bytes of the buffers the form needs (0: none)
+};
+
+template <int V> using IntC = std::integral_constant<int, V>;
+
+// the launch plan of one launch_spectrum call: decisions only, nothing allocated or launched
+template <int MODE, int GM>
+static SpectrumPlan plan_spectrum(const tsff_handle& h, int B, int nload) {
+  const KStatic& S = h.S;
+  const size_t nitems = (size_t)B * nload;   // one-feature workgroups
+  const size_t finrec = nitems * (2 * (size_t)S.NP + 1 + 9 + 4 * (size_t)h.n_ion) * sizeof(double);
+  // points_per_pixel > 1, loss + gradient: the one-sweep kernel with its rows in a global scratch array (k_spectrum_rows.inc) -- one
+  // launch of 256-thread one-feature workgroups, two per CU (the full Z' table if that still fits, else the half table); the scratch
+  // is capped at kRowsScratchMax (larger batches fall back to the two-sweep kernel).  Forward only: the forward form of the rounds
+  // kernel (FWD) -- two 256-thread workgroups per CU and, for small batches, the rounds of a lineout on separate workgroups --
+  // instead of k_spectrum MODE 0's one 512-thread workgroup per CU
+  if constexpr ((MODE == 1 && GM <= 1) || (MODE == 0 && GM == 0)) {
+    if (S.G == 1 && S.ppp > 1 && h.n_ion <= kFusedMaxIon && !(h.plan & 2) && !S.raw[0] && !S.raw[1] && nload >= 1) {
+      constexpr bool FWD = MODE == 0;
+      SpectrumPlan p;
+      p.form = SpectrumForm::rows;
       // (the exchange's 15 KB live in the sweep's part of the LDS: free whenever the chain's buffers are the larger part)
-      const bool ex_r = h->S.n_angles <= 16 && !(h->plan & 8) && 2 * sizeof(double) * rows_smem_doubles(h->S, GM, true, true) <= kLdsLimit;
-      const bool zh_r = 2 * sizeof(double) * rows_smem_doubles(h->S, GM, false, ex_r) > kLdsLimit;
-      const size_t smem_r = sizeof(double) * rows_smem_doubles(h->S, GM, zh_r, ex_r);
-      const bool il = nload == 2;
-      const size_t nwg = (size_t)K.B * nload;
-      const size_t need = nwg * rows_components(h->n_ion, GM) * (size_t)h->S.npts * sizeof(double);
-      constexpr size_t kRowsScratchMax = (size_t)16 << 30;
-      if (2 * smem_r <= kLdsLimit && need <= kRowsScratchMax) {
-        if (int rcj = join_pipe(h)) return rcj;
-        TSFF_HIP(h, h->rows.ensure(need));
+      p.ex = S.n_angles <= 16 && !(h.plan & 8) && 2 * sizeof(double) * rows_smem_doubles(S, GM, true, true) <= kLdsLimit;
+      p.zh = 2 * sizeof(double) * rows_smem_doubles(S, GM, false, p.ex) > kLdsLimit;
+      p.smem = sizeof(double) * rows_smem_doubles(S, GM, p.zh, p.ex);
+      p.interleaved = nload == 2;
+      p.rows = nitems * (FWD ? 1 : rows_components(h.n_ion, GM)) * (size_t)S.npts * sizeof(double);   // (forward: the value only)
+      if (2 * p.smem <= kLdsLimit && (FWD || p.rows <= kRowsScratchMax)) {
         // small batches: one workgroup per (lineout, feature, ROUND), the last one of a (lineout, feature) runs the chain
-        const bool split = nwg * 2 <= (size_t)h->ncu2d() && !(h->plan & 1);
-        if (split && h->tickets.bytes < nwg * sizeof(unsigned)) {
-          TSFF_HIP(h, h->tickets.ensure(std::max<size_t>(nwg, 1024) * sizeof(unsigned)));
-          TSFF_HIP(h, hipMemsetAsync(h->tickets.p, 0, h->tickets.bytes, h->stream));
-        }
-        if (il) {
-          TSFF_HIP(h, h->gpart.ensure((size_t)2 * K.B * h->S.NP * sizeof(double)));
-          K.gpart = h->gpart.as<double>();
-          if (used_gpart) *used_gpart = true;
-        }
-        const size_t slot = h->ev0.empty() ? 0 : h->ev_count % h->ev0.size();
-        if (h->timing) TSFF_HIP(h, hipEventRecord(h->ev0[slot], h->stream));
-        launch_rows<GM>(h, K, split ? dim3((unsigned)nwg, (unsigned)h->S.ppp) : dim3((unsigned)nwg), smem_r, h->S.load[0] ? 0 : 1, (il ? 4 : 0) | (split ? 16 : 0), zh_r, ex_r, gmask, grad,
-                        h->rows.as<double>(), split ? h->tickets.as<unsigned>() : nullptr);
-        TSFF_HIP(h, hipGetLastError());
-        if (h->timing) { TSFF_HIP(h, hipEventRecord(h->ev1[slot], h->stream)); h->ev_count++; }
-        return 0;
-      }
-    }
-  }
-  // forward only at several points per pixel: the forward form of the rounds kernel (k_spectrum_rows<..., FWD>): two 256-thread
-  // workgroups per CU and, for small batches, the rounds of a lineout on separate workgroups -- instead of k_spectrum MODE 0's one
-  // 512-thread workgroup per CU
-  if constexpr (MODE == 0 && GM == 0) {
-    if (h->S.G == 1 && h->S.ppp > 1 && h->n_ion <= kFusedMaxIon && !(h->plan & 2) && !h->S.raw[0] && !h->S.raw[1] && nload >= 1) {
-      const bool ex_r = h->S.n_angles <= 16 && !(h->plan & 8) && 2 * sizeof(double) * rows_smem_doubles(h->S, 0, true, true) <= kLdsLimit;
-      const bool zh_r = 2 * sizeof(double) * rows_smem_doubles(h->S, 0, false, ex_r) > kLdsLimit;
-      const size_t smem_r = sizeof(double) * rows_smem_doubles(h->S, 0, zh_r, ex_r);
-      const bool il = nload == 2;
-      const size_t nwg = (size_t)K.B * nload;
-      const size_t need = nwg * (size_t)h->S.npts * sizeof(double);   // (one component: the forward value)
-      if (2 * smem_r <= kLdsLimit) {
-        TSFF_HIP(h, h->rows.ensure(need));
-        const bool split = nwg * 2 <= (size_t)h->ncu2d() && !(h->plan & 1);
-        if (split && h->tickets.bytes < nwg * sizeof(unsigned)) {
-          TSFF_HIP(h, h->tickets.ensure(std::max<size_t>(nwg, 1024) * sizeof(unsigned)));
-          TSFF_HIP(h, hipMemsetAsync(h->tickets.p, 0, h->tickets.bytes, h->stream));
-        }
-        const size_t slot = h->ev0.empty() ? 0 : h->ev_count % h->ev0.size();
-        if (h->timing) TSFF_HIP(h, hipEventRecord(h->ev0[slot], h->stream));
-        launch_rows<0, true>(h, K, split ? dim3((unsigned)nwg, (unsigned)h->S.ppp) : dim3((unsigned)nwg), smem_r, h->S.load[0] ? 0 : 1, (il ? 4 : 0) | (split ? 16 : 0), zh_r, ex_r,
-                             nullptr, nullptr, h->rows.as<double>(), split ? h->tickets.as<unsigned>() : nullptr);
-        TSFF_HIP(h, hipGetLastError());
-        if (h->timing) { TSFF_HIP(h, hipEventRecord(h->ev1[slot], h->stream)); h->ev_count++; }
-        return 0;
+        p.split = nitems * 2 <= (size_t)h.ncu2d() && !(h.plan & 1);
+        p.tickets = p.split ? nitems * sizeof(unsigned) : 0;
+        if (!FWD && p.interleaved) p.gpart = (size_t)2 * B * S.NP * sizeof(double);
+        p.grid = p.split ? dim3((unsigned)nitems, (unsigned)S.ppp) : dim3((unsigned)nitems);
+        p.block = dim3(kHalf);
+        return p;
       }
     }
   }
   // forward only (tsff_forward), one gradient point, one point per pixel: the pair-sweep kernel (k_forward.inc) -- two workgroups
   // per item while the whole batch fits one dispatch round of two items per CU (configs[1]), else one; plan bit 8 (256): never
   if constexpr (MODE == 0 && GM == 0) {
-    if (h->S.G == 1 && h->S.ppp == 1 && h->n_ion <= kFusedMaxIon && !(h->plan & 256) && nload >= 1) {
-      const bool exok = h->S.n_angles <= 16 && !(h->plan & 8);
-      const bool il = nload == 2;
-      const size_t nitems = (size_t)K.B * nload;
+    if (S.G == 1 && S.ppp == 1 && h.n_ion <= kFusedMaxIon && !(h.plan & 256) && nload >= 1) {
+      SpectrumPlan p;
+      p.form = SpectrumForm::pairs;
+      p.ex = S.n_angles <= 16 && !(h.plan & 8);
+      p.interleaved = nload == 2;
       // 512 threads per item (one pair per thread, lane-shuffle exchange) while the batch fits one round of two items per CU
-      const bool wide = nitems <= 2 * (size_t)h->ncu2d() && !(h->plan & 1);
+      p.wide = nitems <= 2 * (size_t)h.ncu2d() && !(h.plan & 1);
       // LDS of the forward workgroup (smem_fwd_doubles): two per CU with the lane exchange through LDS (the full Z' table and the
       // k_s cache as they fit), or -- batches of more than two items per CU -- THREE per CU with the half Z' table, no k_s cache and
       // the exchange by lane shuffles (plan bit 2 (4): never)
-      const int exm2 = exok ? 1 : 0;
-      const bool zh2 = 2 * sizeof(double) * smem_fwd_doubles(h->S, false, false, exm2) > kLdsLimit;
-      const bool ks2 = 2 * sizeof(double) * smem_fwd_doubles(h->S, true, zh2, exm2) <= kLdsLimit;
-      const size_t smem2 = sizeof(double) * smem_fwd_doubles(h->S, ks2, zh2, exm2);
-      const size_t smem3 = sizeof(double) * smem_fwd_doubles(h->S, false, true, exok ? 2 : 0);
-      const bool three = !wide && !(h->plan & 4) && nitems > 2 * (size_t)h->ncu2d() && 3 * smem3 <= kLdsLimit;
-      const bool ex_f = exok, zh_f = three ? true : zh2, ks_f = three ? false : ks2;
-      const size_t smem_f = three ? smem3 : (wide ? sizeof(double) * smem_fwd_doubles(h->S, ks2, zh2, exok ? 2 : 0) : smem2);
-      if (2 * smem_f <= kLdsLimit) {
-        if (!wide) {
-          TSFF_HIP(h, h->lrec.ensure(nitems * kLineRec * sizeof(double)));
-          TSFF_HIP(h, h->finrec.ensure(nitems * (2 * (size_t)h->S.NP + 1 + 9 + 4 * (size_t)h->n_ion) * sizeof(double)));
-        }
-        const int f0 = h->S.load[0] ? 0 : 1, flags = (ks_f ? 2 : 0) | (il ? 4 : 0) | (wide ? 8 : 0);
-        const size_t slot = h->ev0.empty() ? 0 : h->ev_count % h->ev0.size();
-        if (h->timing) TSFF_HIP(h, hipEventRecord(h->ev0[slot], h->stream));
-        const dim3 pgrid((unsigned)((nitems + 63) / 64)), grid((unsigned)nitems);
-        double* lrec = h->lrec.as<double>();
-#define TSFF_LFW(N, Z, E, P) TSFF_LAUNCH(h, k_forward_pairs, (N, Z, E, P), grid, dim3(kHalf * (3 - P)), smem_f, h->stream, h->S, K, f0, flags, lrec)
-#define TSFF_CASE(N)                                                                                                                 \
-  case N:                                                                                                                            \
-    if (wide) {                                                                                                                      \
-      if (zh_f && ex_f) TSFF_LFW(N, true, 2, 1);                                                                                     \
-      else if (zh_f) TSFF_LFW(N, true, 0, 1);                                                                                        \
-      else if (ex_f) TSFF_LFW(N, false, 2, 1);                                                                                       \
-      else TSFF_LFW(N, false, 0, 1);                                                                                                 \
-    } else {                                                                                                                         \
-      TSFF_LAUNCH(h, k_fused_prep, (N), pgrid, dim3(64), 0, h->stream, h->S, K.params, K.B, f0, nload, lrec, h->finrec.as<double>()); \
-      if (three && ex_f) TSFF_LFW(N, true, 2, 2);                                                                                    \
-      else if (zh_f && ex_f) TSFF_LFW(N, true, 1, 2);                                                                                \
-      else if (zh_f) TSFF_LFW(N, true, 0, 2);                                                                                        \
-      else if (ex_f) TSFF_LFW(N, false, 1, 2);                                                                                       \
-      else TSFF_LFW(N, false, 0, 2);                                                                                                 \
-    }                                                                                                                                \
-    break;
-        switch (h->n_ion) { TSFF_CASE(1) TSFF_CASE(2) }
-#undef TSFF_CASE
-#undef TSFF_LFW
-        TSFF_HIP(h, hipGetLastError());
-        if (h->timing) { TSFF_HIP(h, hipEventRecord(h->ev1[slot], h->stream)); h->ev_count++; }
-        return 0;
+      const int exm2 = p.ex ? 1 : 0;
+      const bool zh2 = 2 * sizeof(double) * smem_fwd_doubles(S, false, false, exm2) > kLdsLimit;
+      const bool ks2 = 2 * sizeof(double) * smem_fwd_doubles(S, true, zh2, exm2) <= kLdsLimit;
+      const size_t smem3 = sizeof(double) * smem_fwd_doubles(S, false, true, p.ex ? 2 : 0);
+      p.three = !p.wide && !(h.plan & 4) && nitems > 2 * (size_t)h.ncu2d() && 3 * smem3 <= kLdsLimit;
+      p.zh = p.three || zh2;
+      p.ks = !p.three && ks2;
+      p.smem = p.three ? smem3 : sizeof(double) * smem_fwd_doubles(S, ks2, zh2, p.ex ? (p.wide ? 2 : 1) : 0);
+      if (2 * p.smem <= kLdsLimit) {
+        if (!p.wide) { p.lrec = nitems * kLineRec * sizeof(double); p.finrec = finrec; }
+        p.grid = dim3((unsigned)nitems);
+        p.block = dim3(p.wide ? 2 * kHalf : kHalf);
+        return p;
       }
     }
   }
-  const bool fused_ok = MODE == 1 && GM <= 1 && h->S.G == 1 && h->S.ppp == 1 && h->n_ion <= kFusedMaxIon && !(h->plan & 2);
-  const bool ex = fused_ok && h->S.n_angles <= 16 && !(h->plan & 8) &&
-                  2 * sizeof(double) * smem_doubles(h->S, 1, GM, false, true, true, true) <= kLdsLimit;
-  const bool three_fit = MODE == 0 && !(h->plan & 4) && (long)K.B * nload > 2L * h->ncu2d() &&
-                         3 * sizeof(double) * smem_doubles(h->S, 1, GM, false, alias_xy(h->S, 256), true) <= kLdsLimit;
-  const bool zh = three_fit || 2 * sizeof(double) * smem_doubles(h->S, 1, GM, false, alias_xy(h->S, 256), false, ex) > kLdsLimit;
-  auto bytes = [&](int nf, bool ks, int tpf) { return sizeof(double) * smem_doubles(h->S, nf, GM, ks, alias_xy(h->S, tpf), zh, ex && nf == 1 && tpf == 256); };
-  const bool two_per_cu = 2 * bytes(1, false, 256) <= kLdsLimit;      // two one-feature workgroups per CU
-  const bool interleaved = nload == 2 && two_per_cu && !(h->plan & 1);
-  int nfeat = nload;
-  if (interleaved || bytes(nfeat, false, 256) > kLdsLimit) nfeat = 1;
-  const bool small_wg = nfeat == 1 && two_per_cu;                // 256-thread one-feature workgroups
-  const int tpf = (nfeat == 2 || small_wg) ? 256 : 512;
-  const size_t budget = small_wg ? kLdsLimit / (three_fit ? 3 : 2) : kLdsLimit;
-  const bool use_ks = bytes(nfeat, true, tpf) <= budget;
-  size_t smem = bytes(nfeat, use_ks, tpf);
-  if ((h->plan & 64) && smem <= kLdsLimit / 2) smem = kLdsLimit / 2 + 1024;   // (experiments: one workgroup per CU)
-  if (smem > kLdsLimit) return fail(h, TSFF_ERR_LDS, "LDS budget exceeded (%zu B): reduce npts or the IRF cutoff", smem);
-  const bool fused_launch = fused_ok && nfeat == 1 && small_wg && (interleaved ? 1 : nload / nfeat) == 1;
-  if (!fused_launch)
-    if (int rcj = join_pipe(h)) return rcj;
-  if (fused_launch) {   // the one-sweep kernel leaves per-wavefront records; k_fused_finish turns them into the gradient
-    TSFF_HIP(h, h->lbrec.ensure((size_t)K.B * nload * (kHalf / 64) * kLBRec * sizeof(double)));
-    TSFF_HIP(h, h->lrec.ensure((size_t)K.B * nload * kLineRec * sizeof(double)));
-    TSFF_HIP(h, h->finrec.ensure((size_t)K.B * nload * (2 * (size_t)h->S.NP + 1 + 9 + 4 * (size_t)h->n_ion) * sizeof(double)));
-    K.lbrec = h->lbrec.as<double>();
-    if (used_lbrec) *used_lbrec = true;
-  } else if (interleaved && MODE == 1) {
-    TSFF_HIP(h, h->gpart.ensure((size_t)2 * K.B * h->S.NP * sizeof(double)));
+  SpectrumPlan p;
+  // the one-sweep kernel (k_spectrum_fused.inc) wherever its restrictions hold: loss + gradient, one gradient point, one point
+  // per pixel, 256-thread one-feature workgroups, no table adjoints; with the base-point exchange (EX: 15 KB more LDS, n_angles
+  // <= 16) when two such workgroups still fit a CU (the half Z' table makes room)
+  const bool fused_ok = MODE == 1 && GM <= 1 && S.G == 1 && S.ppp == 1 && h.n_ion <= kFusedMaxIon && !(h.plan & 2);
+  p.ex = fused_ok && S.n_angles <= 16 && !(h.plan & 8) && 2 * sizeof(double) * smem_doubles(S, 1, GM, false, true, true, true) <= kLdsLimit;
+  // forward-only calls need 139 VGPRs: THREE one-feature workgroups fit a CU's registers, and its LDS too with the half Z' table
+  // and without the k_s cache -- 3 wavefronts per SIMD hide the lookups' latency better than 2 (plan bit 2 (4): never); only when
+  // there are more workgroups than two per CU (a grid that fits at two per CU gains nothing and pays for the half table)
+  p.three = MODE == 0 && !(h.plan & 4) && (long)nitems > 2L * h.ncu2d() &&
+            3 * sizeof(double) * smem_doubles(S, 1, GM, false, alias_xy(S, 256), true) <= kLdsLimit;
+  // zh: Z' table held for xi >= 0 only, 13 KB less LDS for about 1 % more instructions -- used only when the full table would
+  // cost the two-workgroups-per-CU plan
+  p.zh = p.three || 2 * sizeof(double) * smem_doubles(S, 1, GM, false, alias_xy(S, 256), false, p.ex) > kLdsLimit;
+  // (tpf: threads per feature of the instantiation the size is for -- 256-thread-per-feature workgroups with points_per_pixel 1
+  //  keep the per-bin adjoint in the memory of the spectrum, alias_xy)
+  auto bytes = [&](int nf, bool ks, int tpf) {
+    return sizeof(double) * smem_doubles(S, nf, GM, ks, alias_xy(S, tpf), p.zh, p.ex && nf == 1 && tpf == 256);
+  };
+  const bool two_per_cu = 2 * bytes(1, false, 256) <= kLdsLimit;   // two one-feature workgroups per CU
+  p.interleaved = nload == 2 && two_per_cu && !(h.plan & 1);
+  p.nfeat = nload;
+  if (p.interleaved || bytes(p.nfeat, false, 256) > kLdsLimit) p.nfeat = 1;
+  const bool small_wg = p.nfeat == 1 && two_per_cu;   // 256-thread one-feature workgroups
+  p.tpf = (p.nfeat == 2 || small_wg) ? kHalf : 2 * kHalf;
+  const size_t budget = small_wg ? kLdsLimit / (p.three ? 3 : 2) : kLdsLimit;
+  p.ks = bytes(p.nfeat, true, p.tpf) <= budget;
+  p.smem = bytes(p.nfeat, p.ks, p.tpf);
+  if ((h.plan & 64) && p.smem <= kLdsLimit / 2) p.smem = kLdsLimit / 2 + 1024;   // (experiments: one workgroup per CU)
+  // (the one-sweep kernel: also no second accumulating launch)
+  const int nlaunch = p.interleaved ? 1 : nload / p.nfeat;
+  if (fused_ok && small_wg && nlaunch == 1) {   // it leaves per-wavefront records; k_fused_finish turns them into the gradient
+    p.form = SpectrumForm::one_sweep;
+    p.lbrec = nitems * (kHalf / 64) * kLBRec * sizeof(double);
+    p.lrec = nitems * kLineRec * sizeof(double);
+    p.finrec = finrec;
+  } else if (p.interleaved && MODE == 1) {
+    p.gpart = (size_t)2 * B * S.NP * sizeof(double);
+  }
+  p.grid = dim3(p.interleaved ? 2 * B : B);
+  p.block = dim3(small_wg ? kHalf : 2 * kHalf);
+  return p;
+}
+
+// the one-sweep kernel k_spectrum_fused (GM: 0 plasma parameters, 1 + the DLM order): the lineout scalars of every item, one
+// thread each (k_fused_prep), then one launch over the whole batch, or -- the pipelined DLM plan -- one per column block, each
+// behind the event of its tables
+template <int GM>
+static void launch_fused(tsff_handle* h, const KCall& K, const SpectrumPlan& p, int f0, int flags, int nload) {
+  with_ion<kFusedMaxIon>(h->n_ion, [&](auto N) {
+    const double* lrec = h->lrec.as<double>();
+    TSFF_LAUNCH(h, k_fused_prep, (N.value), dim3((p.grid.x + 63) / 64), dim3(64), 0, h->stream, h->S, K.params, K.B, f0, nload,
+                h->lrec.as<double>(), h->finrec.as<double>());
+    const int nblk = h->pipe_nblk > 1 ? h->pipe_nblk : 1;
+    for (int i = 0; i < nblk; ++i) {
+      KCall Kb = K;
+      dim3 g = p.grid;
+      if (nblk > 1) {
+        Kb.b0 = i * h->pipe_nb; Kb.B = std::min(h->pipe_nb, K.B - Kb.b0);
+        g = dim3((unsigned)(Kb.B * nload));
+        (void)hipStreamWaitEvent(h->stream, h->blk_ev[i], 0);
+      }
+      with_bool(p.zh, [&](auto ZH) {
+        with_bool(p.ex, [&](auto EX) {
+          TSFF_LAUNCH(h, k_spectrum_fused, (N.value, GM, ZH.value, EX.value), g, p.block, p.smem, h->stream, h->S, Kb, f0, flags, lrec);
+        });
+      });
+    }
+  });
+  h->pipe_nblk = 0;
+}
+
+// plan_spectrum, then the buffers of the plan, the timing ring and the launches
+template <int MODE, int GM = 0>
+static int launch_spectrum(tsff_handle* h, KCall& K, const uint8_t* gmask = nullptr, double* grad = nullptr,
+                           bool* used_gpart = nullptr, bool* used_lbrec = nullptr) {
+  const int nload = (h->S.load[0] ? 1 : 0) + (h->S.load[1] ? 1 : 0);
+  const SpectrumPlan p = plan_spectrum<MODE, GM>(*h, K.B, nload);
+  if (p.smem > kLdsLimit) return fail(h, TSFF_ERR_LDS, "LDS budget exceeded (%zu B): reduce npts or the IRF cutoff", p.smem);
+  // the one-sweep kernel takes the tables block by block; every other form waits for all of them (a no-op for forward calls:
+  // only the loss + gradient builds its tables on the second stream)
+  if (p.form != SpectrumForm::one_sweep)
+    if (int rc = join_pipe(h)) return rc;
+  if (p.rows) TSFF_HIP(h, h->rows.ensure(p.rows));
+  if (p.tickets && h->tickets.bytes < p.tickets) {
+    TSFF_HIP(h, h->tickets.ensure(std::max<size_t>(p.tickets, 1024 * sizeof(unsigned))));
+    TSFF_HIP(h, hipMemsetAsync(h->tickets.p, 0, h->tickets.bytes, h->stream));
+  }
+  if (p.gpart) {
+    TSFF_HIP(h, h->gpart.ensure(p.gpart));
     K.gpart = h->gpart.as<double>();
     if (used_gpart) *used_gpart = true;
   }
-  const size_t slot = h->ev0.empty() ? 0 : h->ev_count % h->ev0.size();
-  if (h->timing) TSFF_HIP(h, hipEventRecord(h->ev0[slot], h->stream));
-  const int nlaunch = interleaved ? 1 : nload / nfeat;
+  if (p.lbrec) TSFF_HIP(h, h->lbrec.ensure(p.lbrec));
+  if (p.lrec) TSFF_HIP(h, h->lrec.ensure(p.lrec));
+  if (p.finrec) TSFF_HIP(h, h->finrec.ensure(p.finrec));
+  if (p.form == SpectrumForm::one_sweep) {
+    K.lbrec = h->lbrec.as<double>();
+    if (used_lbrec) *used_lbrec = true;
+  }
+  if (int rc = timing_begin(h)) return rc;
+  const int nlaunch = p.interleaved ? 1 : nload / p.nfeat;
   for (int l = 0; l < nlaunch; ++l) {
     const int f0 = nlaunch == 2 ? l : (h->S.load[0] ? 0 : 1);
-    const int flags = (l > 0 ? 1 : 0) | (use_ks ? 2 : 0) | (interleaved ? 4 : 0);
-    const bool tpf256 = nfeat == 2 || small_wg;  // threads per feature: 256 (two-feature or small workgroup) or 512
-    dim3 grid(interleaved ? 2 * K.B : K.B), block(nfeat == 2 || !small_wg ? 2 * kHalf : kHalf);
-    // (one-sweep kernel: also no second accumulating launch)
-    const bool fused = fused_launch;
-    if (fused) {
-      launch_fused<GM>(h, K, grid, smem, f0, flags, zh, ex, nload);
-    } else
-    switch (h->n_ion) {
-#define TSFF_CASE(N)                                                                                          \
-  case N:                                                                                                     \
-    if (tpf256 && !zh)                                                                                        \
-      TSFF_LAUNCH(h, k_spectrum, (N, MODE, GM, kHalf, false), grid, block, smem, h->stream, h->S, K, f0, nfeat, flags, \
-                         gmask, grad);                                                                        \
-    else if (tpf256)                                                                                          \
-      TSFF_LAUNCH(h, k_spectrum, (N, MODE, GM, kHalf, true), grid, block, smem, h->stream, h->S, K, f0, nfeat, flags, gmask, \
-                         grad);                                                                               \
-    else                                                                                                      \
-      TSFF_LAUNCH(h, k_spectrum, (N, MODE, GM, 2 * kHalf, true), grid, block, smem, h->stream, h->S, K, f0, nfeat, flags,    \
-                         gmask, grad);                                                                        \
-    break;
-      TSFF_CASE(1) TSFF_CASE(2) TSFF_CASE(3) TSFF_CASE(4)
-#undef TSFF_CASE
+    const int flags = (l > 0 ? 1 : 0) | (p.ks ? 2 : 0) | (p.interleaved ? 4 : 0) | (p.wide ? 8 : 0) | (p.split ? 16 : 0);
+    switch (p.form) {
+      case SpectrumForm::rows:
+        if constexpr ((MODE == 1 && GM <= 1) || (MODE == 0 && GM == 0))
+          with_ion<kFusedMaxIon>(h->n_ion, [&](auto N) {
+            with_bool(p.zh, [&](auto ZH) {
+              with_bool(p.ex, [&](auto EX) {
+                TSFF_LAUNCH(h, k_spectrum_rows, (N.value, GM, ZH.value, EX.value, MODE == 0), p.grid, p.block, p.smem, h->stream, h->S,
+                            K, f0, flags, gmask, grad, h->rows.as<double>(), p.split ? h->tickets.as<unsigned>() : nullptr);
+              });
+            });
+          });
+        break;
+      case SpectrumForm::pairs:
+        if constexpr (MODE == 0 && GM == 0)
+          with_ion<kFusedMaxIon>(h->n_ion, [&](auto N) {
+            double* lrec = h->lrec.as<double>();
+            auto pairs = [&](auto ZH, auto EXM, auto NPAIR) {
+              TSFF_LAUNCH(h, k_forward_pairs, (N.value, ZH.value, EXM.value, NPAIR.value), p.grid, p.block, p.smem, h->stream, h->S, K,
+                          f0, flags, lrec);
+            };
+            // the nine shipped (ZH, EXM, NPAIR) forms; EXM: 0 no exchange, 1 through LDS, 2 by lane shuffles
+            if (p.wide) {
+              with_bool(p.zh, [&](auto ZH) { p.ex ? pairs(ZH, IntC<2>(), IntC<1>()) : pairs(ZH, IntC<0>(), IntC<1>()); });
+            } else {
+              TSFF_LAUNCH(h, k_fused_prep, (N.value), dim3((p.grid.x + 63) / 64), dim3(64), 0, h->stream, h->S, K.params, K.B, f0, nload,
+                          lrec, h->finrec.as<double>());
+              if (p.three && p.ex) pairs(std::true_type(), IntC<2>(), IntC<2>());
+              else with_bool(p.zh, [&](auto ZH) { p.ex ? pairs(ZH, IntC<1>(), IntC<2>()) : pairs(ZH, IntC<0>(), IntC<2>()); });
+            }
+          });
+        break;
+      case SpectrumForm::one_sweep:
+        if constexpr (MODE == 1 && GM <= 1) launch_fused<GM>(h, K, p, f0, flags, nload);
+        break;
+      case SpectrumForm::two_sweep:
+        with_ion<TSFF_MAX_ION>(h->n_ion, [&](auto N) {
+          auto spectrum = [&](auto TPF, auto ZH) {
+            TSFF_LAUNCH(h, k_spectrum, (N.value, MODE, GM, TPF.value, ZH.value), p.grid, p.block, p.smem, h->stream, h->S, K, f0,
+                        p.nfeat, flags, gmask, grad);
+          };
+          // (512 threads per feature ships with the half Z' table only)
+          if (p.tpf == kHalf) with_bool(p.zh, [&](auto ZH) { spectrum(IntC<kHalf>(), ZH); });
+          else spectrum(IntC<2 * kHalf>(), std::true_type());
+        });
+        break;
     }
     TSFF_HIP(h, hipGetLastError());
   }
-  if (h->timing) { TSFF_HIP(h, hipEventRecord(h->ev1[slot], h->stream)); h->ev_count++; }
-  return 0;
+  return timing_end(h);
 }
 
 // blockIdx.y extent of the form-factor kernels: with few lineouts the angles are spread over workgroups (ARTS: one
@@ -883,14 +896,9 @@ int tsff_create(const tsff_config* c, tsff_handle** out) {
   h->smem_prepare = sizeof(double) * (2 * (size_t)S.nvx + 3 * kNXi1 + 8) + sizeof(double2) * S.nvx;
   h->smem_vectors = sizeof(double2) * 6 * (size_t)S.nvx + sizeof(double) * (2 * (size_t)S.nvx + 4 * kNXi1 + 8);
   h->smem_adjoint = sizeof(double2) * 3 * (size_t)S.nvx + sizeof(double) * (2 * (size_t)S.nvx + 4 * kNXi1 + 8);
-  hipError_t ea = hipSuccess;
-  switch (c->n_ion) {
-    case 1: ea = set_smem_attrs<1>(h->smem_spectrum, h->smem_prepare, h->smem_vectors, h->smem_adjoint); break;
-    case 2: ea = set_smem_attrs<2>(h->smem_spectrum, h->smem_prepare, h->smem_vectors, h->smem_adjoint); break;
-    case 3: ea = set_smem_attrs<3>(h->smem_spectrum, h->smem_prepare, h->smem_vectors, h->smem_adjoint); break;
-    case 4: ea = set_smem_attrs<4>(h->smem_spectrum, h->smem_prepare, h->smem_vectors, h->smem_adjoint); break;
-  }
-  TSFF_HIPC(ea);
+  TSFF_HIPC(with_ion<TSFF_MAX_ION>(c->n_ion, [&](auto N) {
+    return set_smem_attrs<N.value>(h->smem_spectrum, h->smem_prepare, h->smem_vectors, h->smem_adjoint);
+  }));
   // shared distribution function: build its tables once
   TSFF_HIPC(h->ht.ensure((size_t)S.nvx * sizeof(double2)));
   TSFF_HIPC(h->W.ensure((size_t)kNXi2 * sizeof(double)));
@@ -1067,15 +1075,10 @@ int tsff_form_factor(tsff_handle* h, int32_t feature, const double* phys, const 
   rc = prepare_tables(h, phys, fe, B, K);
   if (rc) return rc;
   dim3 grid(B, angle_chunks(h, B)), block(kThreads);
-  switch (h->n_ion) {
-#define TSFF_CASE(N)                                                                                                 \
-  case N:                                                                                                            \
-    TSFF_LAUNCH(h, k_form_factor, (N), grid, block, h->smem_spectrum, h->stream, h->S, K, (int)feature,          \
-                       h->S.omgs[feature], h->S.npts, P);                                                            \
-    break;
-    TSFF_CASE(1) TSFF_CASE(2) TSFF_CASE(3) TSFF_CASE(4)
-#undef TSFF_CASE
-  }
+  with_ion<TSFF_MAX_ION>(h->n_ion, [&](auto N) {
+    TSFF_LAUNCH(h, k_form_factor, (N.value), grid, block, h->smem_spectrum, h->stream, h->S, K, (int)feature, h->S.omgs[feature],
+                h->S.npts, P);
+  });
   TSFF_HIP(h, hipGetLastError());
   return 0;
 }
@@ -1109,28 +1112,18 @@ int tsff_form_factor_grad(tsff_handle* h, int32_t feature, const double* phys, c
   const size_t smem = sizeof(double) * smem_doubles(h->S, 1, grad_fe ? 2 : 0, false);
   if (smem > kLdsLimit) return fail(h, TSFF_ERR_LDS, "LDS budget exceeded (%zu B)", smem);
   dim3 grid(B, nchunk), block(kThreads);
-  switch (h->n_ion) {
-#define TSFF_CASE(N)                                                                                                 \
-  case N:                                                                                                            \
-    if (grad_fe) {                                                                                                   \
-      TSFF_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_form_factor_adj<N, 2>),                        \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit));                  \
-      TSFF_LAUNCH(h, k_form_factor_adj, (N, 2), grid, block, smem, h->stream, h->S, K, (int)feature,             \
-                         h->S.omgs[feature], h->S.npts, Pbar, h->lbparts.as<double>());                              \
-    } else {                                                                                                         \
-      TSFF_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_form_factor_adj<N, 0>),                        \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit));                  \
-      TSFF_LAUNCH(h, k_form_factor_adj, (N, 0), grid, block, smem, h->stream, h->S, K, (int)feature,             \
-                         h->S.omgs[feature], h->S.npts, Pbar, h->lbparts.as<double>());                              \
-    }                                                                                                                \
-    TSFF_LAUNCH0(h, k_lbacc_reduce, dim3(B * h->S.G), dim3(kThreads), 0, h->stream, h->lbparts.as<double>(), nworker, NLB, \
-                       h->lbacc.as<double>());                                                                       \
-    TSFF_LAUNCH(h, k_ff2d_lines_adj, (N), dim3((B + 63) / 64), dim3(64), 0, h->stream, h->S, phys, (int)feature, (int)B, \
-                       h->lbacc.as<double>(), grad_phys, 1);                                                         \
-    break;
-    TSFF_CASE(1) TSFF_CASE(2) TSFF_CASE(3) TSFF_CASE(4)
-#undef TSFF_CASE
-  }
+  rc = with_ion<TSFF_MAX_ION>(h->n_ion, [&](auto N) {
+    return with_bool(grad_fe != nullptr, [&](auto FE) {
+      TSFF_LAUNCH_LDS(h, k_form_factor_adj, (N.value, FE.value ? 2 : 0), kLdsLimit, grid, block, smem, h->stream, h->S, K, (int)feature,
+                      h->S.omgs[feature], h->S.npts, Pbar, h->lbparts.as<double>());
+      TSFF_LAUNCH0(h, k_lbacc_reduce, dim3(B * h->S.G), dim3(kThreads), 0, h->stream, h->lbparts.as<double>(), nworker, NLB,
+                   h->lbacc.as<double>());
+      TSFF_LAUNCH(h, k_ff2d_lines_adj, (N.value), dim3((B + 63) / 64), dim3(64), 0, h->stream, h->S, phys, (int)feature, (int)B,
+                  h->lbacc.as<double>(), grad_phys, 1);
+      return 0;
+    });
+  });
+  if (rc) return rc;
   TSFF_HIP(h, hipGetLastError());
   if (grad_fe) {
     if (nchunk > 1) {
@@ -1233,41 +1226,20 @@ static int form_factor_2d_impl(tsff_handle* h, int32_t feature, const double* ph
     const long hi = shared_fe ? pend : std::min(pend, (long)(b + 1) * per_lineout);
     const double* table = tables + (shared_fe ? 0 : (size_t)b * tstride);
     dim3 grid((unsigned)std::min((hi - lo + kG2 - 1) / kG2, want)), block(kG2 * kThreads);
-    const size_t tslot = h->ev0.empty() ? 0 : h->ev_count % h->ev0.size();
-    if (h->timing) TSFF_HIP(h, hipEventRecord(h->ev0[tslot], h->stream));
-    switch (h->n_ion) {
-#define TSFF_CASE(N)                                                                                               \
-  case N:                                                                                                          \
-    if (save) {                                                                                                    \
-      if (lds) {                                                                                                   \
-        TSFF_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_form_factor_2d<N, true, kGL, true>),       \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit));              \
-        TSFF_LAUNCH(h, k_form_factor_2d, (N, true, kGL, true), grid, block, smem, h->stream, h->S, phys, table, (int)nv, \
-                           ud_angle_deg * kPi / 180.0, va_angle_deg * kPi / 180.0, (int)feature, lo, hi, P, proj); \
-      } else {                                                                                                     \
-        TSFF_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_form_factor_2d<N, false, kGG, true>),      \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit));              \
-        TSFF_LAUNCH(h, k_form_factor_2d, (N, false, kGG, true), grid, block, smem, h->stream, h->S, phys, table, (int)nv, \
-                           ud_angle_deg * kPi / 180.0, va_angle_deg * kPi / 180.0, (int)feature, lo, hi, P, proj); \
-      }                                                                                                            \
-    } else                                                                                                         \
-    if (lds) {                                                                                                     \
-      TSFF_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_form_factor_2d<N, true, kGL>),                    \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit));                \
-      TSFF_LAUNCH(h, k_form_factor_2d, (N, true, kGL, false), grid, block, smem, h->stream, h->S, phys, table, (int)nv,\
-                         ud_angle_deg * kPi / 180.0, va_angle_deg * kPi / 180.0, (int)feature, lo, hi, P);    \
-    } else {                                                                                                       \
-      TSFF_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_form_factor_2d<N, false, kGG>),                   \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit));                \
-      TSFF_LAUNCH(h, k_form_factor_2d, (N, false, kGG, false), grid, block, smem, h->stream, h->S, phys, table, (int)nv,\
-                         ud_angle_deg * kPi / 180.0, va_angle_deg * kPi / 180.0, (int)feature, lo, hi, P);    \
-    }                                                                                                              \
-    break;
-      TSFF_CASE(1) TSFF_CASE(2) TSFF_CASE(3) TSFF_CASE(4)
-#undef TSFF_CASE
-    }
+    if (int rc = timing_begin(h)) return rc;
+    int rc = with_ion<TSFF_MAX_ION>(h->n_ion, [&](auto N) {
+      return with_bool(lds, [&](auto LDS) {
+        return with_bool(save, [&](auto SAVE) {
+          TSFF_LAUNCH_LDS(h, k_form_factor_2d, (N.value, LDS.value, LDS.value ? kGL : kGG, SAVE.value), kLdsLimit, grid, block, smem,
+                          h->stream, h->S, phys, table, (int)nv, ud_angle_deg * kPi / 180.0, va_angle_deg * kPi / 180.0, (int)feature,
+                          lo, hi, P, proj);
+          return 0;
+        });
+      });
+    });
+    if (rc) return rc;
     TSFF_HIP(h, hipGetLastError());
-    if (h->timing) { TSFF_HIP(h, hipEventRecord(h->ev1[tslot], h->stream)); h->ev_count++; }
+    if ((rc = timing_end(h))) return rc;
   }
   return 0;
 }
@@ -1323,31 +1295,21 @@ int tsff_form_factor_2d_grad(tsff_handle* h, int32_t feature, const double* phys
   const int nworker = (int)grid.x * kG2;
   TSFF_HIP(h, h->lbparts.ensure((size_t)B * h->S.G * nworker * NLB * sizeof(double)));
   TSFF_HIP(h, hipMemsetAsync(h->lbparts.p, 0, (size_t)B * h->S.G * nworker * NLB * sizeof(double), h->stream));
-  switch (h->n_ion) {
-#define TSFF_CASE(N)                                                                                                \
-  case N:                                                                                                           \
-    if (lds) {                                                                                                      \
-      TSFF_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_form_factor_2d_adj<N, true, kGL>),            \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit));                 \
-      TSFF_LAUNCH(h, k_form_factor_2d_adj, (N, true, kGL), grid, block, smem, h->stream, h->S, phys, table, (int)nv, ud, va, \
-                         (int)feature, pb, pe, Pbar, h->lbparts.as<double>(), f1bar, proj);                          \
-    } else {                                                                                                        \
-      TSFF_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_form_factor_2d_adj<N, false, kGG>),           \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit));                 \
-      TSFF_LAUNCH(h, k_form_factor_2d_adj, (N, false, kGG), grid, block, smem, h->stream, h->S, phys, table, (int)nv, ud, va, \
-                         (int)feature, pb, pe, Pbar, h->lbparts.as<double>(), f1bar, proj);                          \
-    }                                                                                                               \
-    TSFF_LAUNCH0(h, k_lbacc_reduce, dim3(B * h->S.G), dim3(kThreads), 0, h->stream, h->lbparts.as<double>(), nworker, NLB, \
-                       h->lbacc.as<double>());                                                                      \
-    TSFF_LAUNCH(h, k_ff2d_lines_adj, (N), dim3((B + 63) / 64), dim3(64), 0, h->stream, h->S, phys, (int)feature, (int)B, \
-                       h->lbacc.as<double>(), grad_phys, 0);                                                        \
-    break;
-    TSFF_CASE(1) TSFF_CASE(2) TSFF_CASE(3) TSFF_CASE(4)
-#undef TSFF_CASE
-  }
+  int rc = with_ion<TSFF_MAX_ION>(h->n_ion, [&](auto N) {
+    return with_bool(lds, [&](auto LDS) {
+      TSFF_LAUNCH_LDS(h, k_form_factor_2d_adj, (N.value, LDS.value, LDS.value ? kGL : kGG), kLdsLimit, grid, block, smem, h->stream, h->S,
+                      phys, table, (int)nv, ud, va, (int)feature, pb, pe, Pbar, h->lbparts.as<double>(), f1bar, proj);
+      TSFF_LAUNCH0(h, k_lbacc_reduce, dim3(B * h->S.G), dim3(kThreads), 0, h->stream, h->lbparts.as<double>(), nworker, NLB,
+                   h->lbacc.as<double>());
+      TSFF_LAUNCH(h, k_ff2d_lines_adj, (N.value), dim3((B + 63) / 64), dim3(64), 0, h->stream, h->S, phys, (int)feature, (int)B,
+                  h->lbacc.as<double>(), grad_phys, 0);
+      return 0;
+    });
+  });
+  if (rc) return rc;
   TSFF_HIP(h, hipGetLastError());
   if (grad_fe2d) {
-    int rc = table_adjoint_2d(h, nv, ntotal, grad_fe2d);
+    rc = table_adjoint_2d(h, nv, ntotal, grad_fe2d);
     if (rc) return rc;
   }
   return 0;
@@ -1361,11 +1323,10 @@ static int table_adjoint_2d(tsff_handle* h, int nv, long npoint, double* grad_fe
   const int tmax = std::min(ncell, kTile2) + 3;
   const size_t smem = sizeof(double) * (size_t)tmax * (tmax | 1);
   const unsigned per_tile = (unsigned)std::max<long>(1, std::min<long>((npoint + 3) / 4, h->ncu2d() / ntiles));
-  TSFF_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_ff2d_table_adj), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit));
   const size_t slab = (size_t)tmax * tmax;
   TSFF_HIP(h, h->fbar_parts.ensure((size_t)per_tile * ntiles * slab * sizeof(double)));
-  TSFF_LAUNCH0(h, k_ff2d_table_adj, dim3(per_tile, ntiles), dim3(4 * kThreads), smem, h->stream, nv, h->f1bar.as<double>(), npoint,
-                     h->fbar_parts.as<double>(), slab);
+  TSFF_LAUNCH0_LDS(h, k_ff2d_table_adj, kLdsLimit, dim3(per_tile, ntiles), dim3(4 * kThreads), smem, h->stream, nv, h->f1bar.as<double>(),
+                   npoint, h->fbar_parts.as<double>(), slab);
   for (int t = 0; t < ntiles; ++t)   // one launch per tile, in order: the overlapping halos of neighbouring tiles add up without atomics
     TSFF_LAUNCH0(h, k_ff2d_sum_tiles, dim3((unsigned)((slab + kThreads - 1) / kThreads)), dim3(kThreads), 0, h->stream, nv,
                        h->fbar_parts.as<double>(), (int)per_tile, slab, h->fbar_pad.as<double>(), t);
@@ -1512,13 +1473,7 @@ static int loss_grad_impl(tsff_handle* h, const double* params, const double* fe
       if (po->act[k] < 0 || po->act[k] >= h->S.NP) return fail(h, -1, "active slot %d out of range", (int)po->act[k]);
     TSFF_HIP(h, h->gradws.ensure((size_t)B * h->S.NP * sizeof(double)));
     grad = h->gradws.as<double>();
-    if (h->act_host.size() != (size_t)po->n_act || std::memcmp(h->act_host.data(), po->act, po->n_act * sizeof(int32_t)) != 0) {
-      h->act_host.assign(po->act, po->act + po->n_act);
-      TSFF_HIP(h, h->act.ensure(kNP_MAX * sizeof(int32_t)));
-      // (pageable source that the next call may reassign: a synchronous copy of <= NP indices, once per change of the slot list)
-      TSFF_HIP(h, hipStreamSynchronize(h->stream));
-      TSFF_HIP(h, hipMemcpy(h->act.p, h->act_host.data(), po->n_act * sizeof(int32_t), hipMemcpyHostToDevice));
-    }
+    if ((rc = upload_slots(h, po->act, po->n_act))) return rc;
     loss_terms = po->packed;
   }
   if (!weights || !grad_mask || !loss_terms || !grad) return fail(h, -1, "bad argument");
@@ -1574,16 +1529,11 @@ static int loss_grad_impl(tsff_handle* h, const double* params, const double* fe
     const int nload = (h->S.load[0] ? 1 : 0) + (h->S.load[1] ? 1 : 0), f0 = h->S.load[0] ? 0 : 1;
     const int per_wg = kThreads / nload;
     const dim3 fgrid((unsigned)((B + per_wg - 1) / per_wg) + 1);   // (+ 1: the last workgroup reduces the loss sums)
-    switch (h->n_ion) {
-#define TSFF_CASE(N)                                                                                                          \
-  case N:                                                                                                                     \
-    TSFF_LAUNCH(h, k_fused_finish, (N), fgrid, dim3(kThreads), 0, h->stream, h->S, h->finrec.as<double>(), K.lbrec, K.lpart, (int)B, f0, nload, \
-                       with_m ? 1 : 0, h->gmask.as<uint8_t>(), grad, po ? nullptr : loss_terms, po ? h->act.as<int>() : nullptr,      \
-                       po ? (int)po->n_act : 0, po ? (long)po->B_global : 0L, po ? (long)po->b_off : 0L, po ? po->packed : nullptr); \
-    break;
-      TSFF_CASE(1) TSFF_CASE(2)
-#undef TSFF_CASE
-    }
+    with_ion<kFusedMaxIon>(h->n_ion, [&](auto N) {
+      TSFF_LAUNCH(h, k_fused_finish, (N.value), fgrid, dim3(kThreads), 0, h->stream, h->S, h->finrec.as<double>(), K.lbrec, K.lpart, (int)B,
+                  f0, nload, with_m ? 1 : 0, h->gmask.as<uint8_t>(), grad, po ? nullptr : loss_terms, po ? h->act.as<int>() : nullptr,
+                  po ? (int)po->n_act : 0, po ? (long)po->B_global : 0L, po ? (long)po->b_off : 0L, po ? po->packed : nullptr);
+    });
   } else if (po) {
     const long n = (long)po->n_act * po->B_global;
     TSFF_LAUNCH0(h, k_loss_reduce_packed, dim3((unsigned)std::max<long>(1, std::min<long>((n + kThreads - 1) / kThreads, 1024))), dim3(kThreads),
@@ -1636,12 +1586,7 @@ int tsff_pack_fe_rows(tsff_handle* h, const double* loss_terms, const double* gr
     return fail(h, -1, "bad argument");
   for (int k = 0; k < n_active; ++k)
     if (active_slots[k] < 0 || active_slots[k] >= h->S.NP) return fail(h, -1, "active slot %d out of range", (int)active_slots[k]);
-  if (h->act_host.size() != (size_t)n_active || std::memcmp(h->act_host.data(), active_slots, n_active * sizeof(int32_t)) != 0) {
-    h->act_host.assign(active_slots, active_slots + n_active);
-    TSFF_HIP(h, h->act.ensure(kNP_MAX * sizeof(int32_t)));
-    TSFF_HIP(h, hipStreamSynchronize(h->stream));
-    TSFF_HIP(h, hipMemcpy(h->act.p, h->act_host.data(), n_active * sizeof(int32_t), hipMemcpyHostToDevice));
-  }
+  if (int rc = upload_slots(h, active_slots, n_active)) return rc;
   const long tiles = ((B_global + 31) / 32) * ((n_active + h->S.nvx + 31) / 32);
   TSFF_LAUNCH0(h, k_pack_fe_rows, dim3((unsigned)std::max<long>(1, std::min<long>(tiles, 2048))), dim3(kThreads), 0, h->stream, loss_terms, grad,
                      h->S.NP, grad_fe, h->S.nvx, (int)B, h->act.as<int>(), (int)n_active, (long)B_global, (long)b_offset, packed);
@@ -1698,21 +1643,15 @@ int tsff_loss_hess(tsff_handle* h, const double* params, const double* fe, const
     TSFF_HIP(h, h->Wmm.ensure((size_t)B * kNXi2 * sizeof(double)));
     TSFF_HIP(h, h->Wmm_unused.ensure((size_t)B * kNXi2 * sizeof(double)));
     const size_t smem_t = sizeof(double2) * 6 * nvx + sizeof(double) * (nvx + 2 * kNXi1 + 8);
-    switch (h->n_ion) {
-#define TSFF_CASE(N)                                                                                                     \
-  case N:                                                                                                                \
-    TSFF_LAUNCH(h, k_hess_mtab, (N), dim3(B), dim3(kThreads), smem_t, h->stream, h->S, params, K.ht, K.htm, h->htmm.as<double2>(), \
-                h->Xmm.as<double>(), h->cstmm.as<double>());                                                             \
-    break;
-      TSFF_CASE(1) TSFF_CASE(2) TSFF_CASE(3) TSFF_CASE(4)
-#undef TSFF_CASE
-    }
+    with_ion<TSFF_MAX_ION>(h->n_ion, [&](auto N) {
+      TSFF_LAUNCH(h, k_hess_mtab, (N.value), dim3(B), dim3(kThreads), smem_t, h->stream, h->S, params, K.ht, K.htm, h->htmm.as<double2>(),
+                  h->Xmm.as<double>(), h->cstmm.as<double>());
+    });
     TSFF_HIP(h, hipGetLastError());
     const int nM = (B + kGM / 4 - 1) / (kGM / 4);
     dim3 wgrid(8 * ((nM + 7) / 8) * ((kNXi2 + kGNw - 1) / kGNw));
-    TSFF_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_wgemm_w), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWgemmWSmem));
-    TSFF_LAUNCH0(h, k_wgemm_w, wgrid, dim3(kThreads), kWgemmWSmem, h->stream, h->S.lg, h->Xmm.as<double>(), h->cstmm.as<double>(),
-                 h->S.xi2, (int)B, h->Wmm.as<double>(), h->Wmm_unused.as<double>(), h->kw_lo, h->kw_hi);
+    TSFF_LAUNCH0_LDS(h, k_wgemm_w, kWgemmWSmem, wgrid, dim3(kThreads), kWgemmWSmem, h->stream, h->S.lg, h->Xmm.as<double>(),
+                     h->cstmm.as<double>(), h->S.xi2, (int)B, h->Wmm.as<double>(), h->Wmm_unused.as<double>(), h->kw_lo, h->kw_hi);
     TSFF_HIP(h, hipGetLastError());
     A.htmm = h->htmm.as<double2>();
     A.Wmm = h->Wmm.as<double>();
@@ -1720,17 +1659,12 @@ int tsff_loss_hess(tsff_handle* h, const double* params, const double* fe, const
   const int nwg = std::min(A.tasks, kHessMaxWG);
   TSFF_HIP(h, h->hws.ensure((size_t)nwg * 4 * h->S.npts * sizeof(double)));
   TSFF_HIP(h, h->hout.ensure((size_t)A.tasks * 12 * sizeof(double)));
-  switch (h->n_ion) {
-#define TSFF_CASE(N)                                                                                                        \
-  case N:                                                                                                                   \
-    TSFF_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_hess_pairs<N>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                    (int)smem));                                                                            \
-    TSFF_LAUNCH(h, k_hess_pairs, (N), dim3(nwg), dim3(kThreads), smem, h->stream, h->S, K, A, h->hws.as<double>(),         \
-                h->hout.as<double>());                                                                                      \
-    break;
-    TSFF_CASE(1) TSFF_CASE(2) TSFF_CASE(3) TSFF_CASE(4)
-#undef TSFF_CASE
-  }
+  rc = with_ion<TSFF_MAX_ION>(h->n_ion, [&](auto N) {
+    TSFF_LAUNCH_LDS(h, k_hess_pairs, (N.value), smem, dim3(nwg), dim3(kThreads), smem, h->stream, h->S, K, A, h->hws.as<double>(),
+                    h->hout.as<double>());
+    return 0;
+  });
+  if (rc) return rc;
   TSFF_HIP(h, hipGetLastError());
   TSFF_LAUNCH0(h, k_hess_finish, dim3((B + kThreads - 1) / kThreads), dim3(kThreads), 0, h->stream, h->hout.as<double>(), A, (int)B,
                weights[0], weights[1], weights[2], K.lpart, grad, hess);
