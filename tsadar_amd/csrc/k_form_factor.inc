@@ -118,10 +118,7 @@ __global__ __launch_bounds__(kThreads) void k_form_factor_adj(KStatic S, KCall K
     }
     lines_adjoint_finalize<NI>(L, LB);   // deferred wavefront-uniform factors of point_reverse
     double lb[NLB];
-    lb[0] = LB.wpe2; lb[1] = LB.wL; lb[2] = LB.kL; lb[3] = LB.ivTe; lb[4] = LB.a_e; lb[5] = LB.pref; lb[6] = LB.Ud; lb[7] = LB.Vd;
-#pragma unroll
-    for (int s = 0; s < NI; ++s) { lb[8 + 3 * s] = LB.ixi[s]; lb[9 + 3 * s] = LB.a_i[s]; lb[10 + 3 * s] = LB.cs[s]; }
-    lb[NLB - 1] = LB.m;
+    lines_adj_store<NI>(LB, lb);
     // one partial per wavefront and angle chunk, plain stores; k_lbacc_reduce adds them in a fixed order
     const int nworker = (int)gridDim.y * (kThreads / 64), worker = (int)blockIdx.y * (kThreads / 64) + (tid >> 6);
 #pragma unroll

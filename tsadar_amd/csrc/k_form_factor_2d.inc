@@ -1778,11 +1778,7 @@ __global__ void k_ff2d_lines_adj(KStatic S, const double* __restrict__ phys, int
     LineS<NI> L, LB;
     make_lines<NI>(p, S.lam_shift[f], g, S.G, L);
     zero_lines<NI>(LB);
-    const double* o = LBacc + ((size_t)b * S.G + g) * NLB;
-    LB.wpe2 = o[0]; LB.wL = o[1]; LB.kL = o[2]; LB.ivTe = o[3]; LB.a_e = o[4]; LB.pref = o[5]; LB.Ud = o[6]; LB.Vd = o[7];
-#pragma unroll
-    for (int s = 0; s < NI; ++s) { LB.ixi[s] = o[8 + 3 * s]; LB.a_i[s] = o[9 + 3 * s]; LB.cs[s] = o[10 + 3 * s]; }
-    if (with_m) LB.m = o[NLB - 1];
+    lines_adj_load<NI>(LBacc + ((size_t)b * S.G + g) * NLB, with_m, LB);
     make_lines_adjoint<NI>(p, S.lam_shift[f], g, S.G, L, LB, pb);
   }
 #pragma unroll

@@ -90,13 +90,7 @@ __global__ __launch_bounds__(kHalf * (3 - NPAIR), 2) void k_forward_pairs(KStati
       phys_from_lds<NI>(m.phys, p);
       make_lines_uniform<NI>(p, S.lam_shift[f], 0, 1, L);
     } else {   // the lineout scalars as k_fused_prep left them (wavefront-uniform address)
-      const double* __restrict__ lr = lrec + (size_t)item * kLineRec;
-      L.wpe2 = uni(lr[0]); L.wL = uni(lr[1]); L.kL = uni(lr[2]); L.ivTe = uni(lr[3]); L.a_e = uni(lr[4]); L.pref = uni(lr[5]);
-      L.Ud = uni(lr[6]); L.Vd = uni(lr[7]); L.i2wL = uni(lr[8]); L.m = 0.0;
-#pragma unroll
-      for (int s = 0; s < NI; ++s) {
-        L.ixi[s] = uni(lr[9 + 4 * s]); L.a_i[s] = uni(lr[10 + 4 * s]); L.cs[s] = uni(lr[11 + 4 * s]); L.hai[s] = uni(lr[12 + 4 * s]);
-      }
+      lines_load<NI>(lrec + (size_t)item * kLineRec, 1, [](double v) { return uni(v); }, L);
     }
     if (use_ks) {
 #pragma unroll
@@ -234,9 +228,7 @@ __global__ __launch_bounds__(kHalf * (3 - NPAIR), 2) void k_forward_pairs(KStati
   const double p_lam = uni(p_lam_v), p_amp1 = uni(p_amp1_v), p_amp2 = uni(p_amp2_v), p_amp3 = uni(p_amp3_v);
 #pragma unroll
   for (int r = 0; r < BPT; ++r) {
-    double A;
-    if (f == TSFF_FEATURE_ELE) A = amps * (lpre[r] < p_lam ? p_amp1 : p_amp2);  // irf.py:126-130
-    else A = raw ? 1.0 : amps * p_amp3;                                          // irf.py:76
+    const double A = bin_amplitude(f, raw, amps, lpre[r], p_lam, p_amp1, p_amp2, p_amp3);
     K.thry[f][row4 + r] = thry_value(A, ybin[r], invM, K.noise[f] != nullptr, npre[r]);   // thomson_diagnostic.py:139-140
   }
 }

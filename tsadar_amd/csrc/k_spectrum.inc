@@ -345,25 +345,6 @@ __device__ __forceinline__ void half_argmax(double& v, int& idx, double* scratch
   }
 }
 
-// T_p = A_p ybin_p / M (+ noise_p) (irf.py:76,126-130; thomson_diagnostic.py:139-140) with its roundings written out -- product,
-// product, sum, never a fused multiply-add -- so that a spectrum is the same bits from every kernel whatever shape the
-// surrounding code gives the compiler (test_launch_plans_agree)
-__device__ __forceinline__ double thry_value(double A, double y, double invM, bool has_noise, double noise) {
-#pragma clang fp contract(off)
-  const double t = (A * y) * invM;
-  return has_noise ? t + noise : t;
-}
-
-// loss functional e(d, t) and de/dt (loss_function.py:386-418); the 1/uncert of l1/l2 is folded
-// into the weights by the host (constant denominators) or applied here (theory denominator).
-__device__ __forceinline__ void loss_point(int method, double d, double t, double& e, double& det) {
-  const double r = d - t;
-  if (method == TSFF_LOSS_L2) { e = r * r; det = -2.0 * r; }
-  else if (method == TSFF_LOSS_L1) { e = fabs(r); det = r > 0.0 ? -1.0 : (r < 0.0 ? 1.0 : 0.0); }
-  else if (method == TSFF_LOSS_LOGCOSH) { e = log(cosh(r)); det = -tanh(r); }
-  else { e = t - d * log(t); det = 1.0 - d / t; }
-}
-
 // ------------------------------------------------------------------------------------------
 // k_spectrum: one workgroup per lineout; threads [0,256) evaluate the first loaded feature, threads
 // [256,512) the second (EPW, IAW), sharing the LDS copies of the Z', W and ln f_e tables.  A deck with
@@ -550,9 +531,7 @@ __global__ __launch_bounds__(2 * kHalf, TSFF_OCC) void k_spectrum(KStatic S, KCa
 #pragma unroll
   for (int r = 0; r < BPT; ++r) {
     const int pb = PB(r);
-    double A;
-    if (f == TSFF_FEATURE_ELE) A = amps * (lamb[pb] < p_lam ? p_amp1 : p_amp2);  // irf.py:126-130
-    else A = raw ? 1.0 : amps * p_amp3;                                          // irf.py:76
+    const double A = bin_amplitude(f, raw, amps, f == TSFF_FEATURE_ELE ? lamb[pb] : 0.0, p_lam, p_amp1, p_amp2, p_amp3);
     Ap[r] = A;
     const double t = thry_value(A, ybin[r], invM, K.noise[f] != nullptr,
                                 K.noise[f] ? K.noise[f][(size_t)b * TSFF_NBINS + pb] : 0.0);   // thomson_diagnostic.py:139-140
@@ -561,24 +540,16 @@ __global__ __launch_bounds__(2 * kHalf, TSFF_OCC) void k_spectrum(KStatic S, KCa
     if (MODE >= 1) {
       const double d = K.data[f][(size_t)b * TSFF_NBINS + pb];
       const uint8_t mk = S.mask[f][pb];
-      double e, det;
-      loss_point(S.loss_method, d, t, e, det);
       if (MODE == 2) {
+        double e, det;
+        loss_point(S.loss_method, d, t, e, det);
         if (S.loss_method == TSFF_LOSS_L2 || S.loss_method == TSFF_LOSS_L1) e /= t;  // loss_function.py:320-321
         double sq = 0.0;
         if (mk & 1) { s0 += e; sq += e; }
         if (mk & 2) { s1 += e; sq += e; }
         if (K.sqdev[f]) K.sqdev[f][(size_t)b * TSFF_NBINS + pb] = sq;
       } else {
-        if (K.denom_mode == 2 && (S.loss_method == TSFF_LOSS_L2 || S.loss_method == TSFF_LOSS_L1)) {
-          const double iden = 1.0 / (fabs(d) + 1e-10);  // loss_function.py:183 (_loss_for_hess_fn_)
-          e *= iden;
-          det *= iden;
-        }
-        double w = 0.0;
-        if (mk & 1) { s0 += e; w += (f == TSFF_FEATURE_ELE ? K.wts[1] : K.wts[0]); }
-        if (mk & 2) { s1 += e; w += K.wts[2]; }
-        Tb[r] = w != 0.0 ? det * w : 0.0;  // (samples outside every fit range may hold anything, NaN included)
+        Tb[r] = bin_loss(S, K, f, d, t, mk, s0, s1);
       }
     }
   }
@@ -597,10 +568,7 @@ __global__ __launch_bounds__(2 * kHalf, TSFF_OCC) void k_spectrum(KStatic S, KCa
 #pragma unroll
   for (int r = 0; r < BPT; ++r) {
     const int pb = PB(r);
-    const double u = Tb[r] * ybin[r] * invM;  // dL/dA_p
-    sn += u * Ap[r];
-    if (f == TSFF_FEATURE_ELE) { if (lamb[pb] < p_lam) a1b += u * amps; else a2b += u * amps; }
-    else a1b += u * amps;
+    norm_adjoint_bin(f, Tb[r], ybin[r], invM, Ap[r], amps, f == TSFF_FEATURE_ELE ? lamb[pb] : 0.0, p_lam, sn, a1b, a2b);
   }
   sn = half_sum<NW>(sn, m.red, half, hw, lane);
   a1b = half_sum<NW>(a1b, m.red, half, hw, lane);
@@ -744,10 +712,7 @@ __global__ __launch_bounds__(2 * kHalf, TSFF_OCC) void k_spectrum(KStatic S, KCa
     {
       lines_adjoint_finalize<NI>(L, LB);   // deferred wavefront-uniform factors of point_reverse
       double lb[NLB];
-      lb[0] = LB.wpe2; lb[1] = LB.wL; lb[2] = LB.kL; lb[3] = LB.ivTe; lb[4] = LB.a_e; lb[5] = LB.pref; lb[6] = LB.Ud; lb[7] = LB.Vd;
-#pragma unroll
-      for (int s = 0; s < NI; ++s) { lb[8 + 3 * s] = LB.ixi[s]; lb[9 + 3 * s] = LB.a_i[s]; lb[10 + 3 * s] = LB.cs[s]; }
-      lb[NLB - 1] = LB.m;
+      lines_adj_store<NI>(LB, lb);
       __syncthreads();
 #pragma unroll
       for (int k = 0; k < NLB; ++k) {
@@ -763,10 +728,7 @@ __global__ __launch_bounds__(2 * kHalf, TSFF_OCC) void k_spectrum(KStatic S, KCa
           if (NW == 8) v += (r[4 * NLB + k] + r[5 * NLB + k]) + (r[6 * NLB + k] + r[7 * NLB + k]);
           lb[k] = v;
         }
-        LB.wpe2 = lb[0]; LB.wL = lb[1]; LB.kL = lb[2]; LB.ivTe = lb[3]; LB.a_e = lb[4]; LB.pref = lb[5]; LB.Ud = lb[6]; LB.Vd = lb[7];
-#pragma unroll
-        for (int s = 0; s < NI; ++s) { LB.ixi[s] = lb[8 + 3 * s]; LB.a_i[s] = lb[9 + 3 * s]; LB.cs[s] = lb[10 + 3 * s]; }
-        LB.m = lb[NLB - 1];
+        lines_adj_load<NI>(lb, true, LB);
         Phys<NI> p;
         phys_from_lds<NI>(m.phys, p);
         double pbar[NPk];
@@ -797,10 +759,7 @@ __global__ __launch_bounds__(2 * kHalf, TSFF_OCC) void k_spectrum(KStatic S, KCa
     }
   }
   // amplitudes (irf.py:76,126-130)
-  if (ht == 0) {
-    if (f == TSFF_FEATURE_ELE) { gsum[half * NPk + TSFF_P_AMP1] += a1b; gsum[half * NPk + TSFF_P_AMP2] += a2b; }
-    else gsum[half * NPk + TSFF_P_AMP3] += a1b;
-  }
+  if (ht == 0) amp_adjoint(f, a1b, a2b, gsum + half * NPk);
   __syncthreads();
   // ---- feature sum and the chain rule to the normalised leaves (Ti tying, fraction renormalisation,
   //      activation; ts_params.py:329-350, 543-563) ----
@@ -809,29 +768,12 @@ __global__ __launch_bounds__(2 * kHalf, TSFF_OCC) void k_spectrum(KStatic S, KCa
       for (int s = 0; s < NPk; ++s) gsum[s] += gsum[NPk + s];
     Phys<NI> p;
     phys_from_lds<NI>(m.phys, p);
-#pragma unroll
-    for (int s = 1; s < NI; ++s)
-      if (S.ti_same[s]) {
-        gsum[TSFF_P_ION0 + TSFF_ION_TI] += gsum[TSFF_P_ION0 + 4 * s + TSFF_ION_TI];
-        gsum[TSFF_P_ION0 + 4 * s + TSFF_ION_TI] = 0.0;
-      }
-    double dot = 0.0;
-#pragma unroll
-    for (int s = 0; s < NI; ++s) dot += gsum[TSFF_P_ION0 + 4 * s + TSFF_ION_FRACT] * p.fr[s];
-#pragma unroll
-    for (int s = 0; s < NI; ++s) {
-      const int o = TSFF_P_ION0 + 4 * s + TSFF_ION_FRACT;
-      gsum[o] = (gsum[o] - dot) / p.fsum;
-      gsum[TSFF_P_ION0 + 4 * s + TSFF_ION_A] = 0.0;
-    }
-    if (GM != 1) gsum[TSFF_P_M] = 0.0;
+    tie_renorm_adjoint<NI>(S, p, GM == 1, gsum);
   }
   __syncthreads();
   if (tid < NPk) {
     const double xv = xpar[tid];
-    double v = gsum[tid] * S.p_scale[tid];
-    if (S.p_sig[tid]) { const double sg = sigmoid(xv); v *= sg * (1.0 - sg); }
-    v = gmask[tid] ? v : 0.0;
+    const double v = activation_adjoint(gsum[tid], S.p_scale[tid], S.p_sig[tid], [&] { return sigmoid(xv); }, gmask[tid]);
     if (interleaved) K.gpart[((size_t)f * K.B + b) * NPk + tid] = v;  // summed over the two features by k_loss_reduce
     else grad[(size_t)b * NPk + tid] = accumulate ? grad[(size_t)b * NPk + tid] + v : v;
   }

@@ -263,13 +263,7 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_fused(KStatic S, KCall K,
     // fraction renormalisation, three square roots and eight divisions were 3 us of ONE wavefront-uniform dependency chain at the
     // head of every workgroup, repeated by all its 256 threads.  Wavefront-uniform address: scalar loads, straight into SGPRs.
     {
-      const double* __restrict__ lr = lrec + gitem * kLineRec;
-      L.wpe2 = uni(lr[0]); L.wL = uni(lr[1]); L.kL = uni(lr[2]); L.ivTe = uni(lr[3]); L.a_e = uni(lr[4]); L.pref = uni(lr[5]);
-      L.Ud = uni(lr[6]); L.Vd = uni(lr[7]); L.i2wL = uni(lr[8]); L.m = 0.0;
-#pragma unroll
-      for (int s = 0; s < NI; ++s) {
-        L.ixi[s] = uni(lr[9 + 4 * s]); L.a_i[s] = uni(lr[10 + 4 * s]); L.cs[s] = uni(lr[11 + 4 * s]); L.hai[s] = uni(lr[12 + 4 * s]);
-      }
+      lines_load<NI>(lrec + gitem * kLineRec, 1, [](double v) { return uni(v); }, L);
     }
     if (use_ks) {
       // k_s(lambda) of this lineout (angle independent, form_factor.py:218), by every wavefront for the samples its own lanes read:
@@ -458,37 +452,17 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_fused(KStatic S, KCall K,
 #pragma unroll
   for (int r = 0; r < BPT; ++r) {
     const int pb = 4 * ht + r;
-    double A;
-    if (f == TSFF_FEATURE_ELE) A = amps * (lpre[r] < p_lam ? p_amp1 : p_amp2);  // irf.py:126-130
-    else A = raw ? 1.0 : amps * p_amp3;                                          // irf.py:76
+    const double A = bin_amplitude(f, raw, amps, lpre[r], p_lam, p_amp1, p_amp2, p_amp3);
     Ap[r] = A;
     const double t = thry_value(A, ybin[r], invM, K.noise[f] != nullptr, npre[r]);   // thomson_diagnostic.py:139-140
     if (K.thry[f]) K.thry[f][(size_t)b * TSFF_NBINS + pb] = t;
-    const double d = dpre[r];
-    const uint8_t mk = mpre[r];
-    double e, det;
-    loss_point(S.loss_method, d, t, e, det);
-    if (K.denom_mode == 2 && (S.loss_method == TSFF_LOSS_L2 || S.loss_method == TSFF_LOSS_L1)) {
-      const double iden = 1.0 / (fabs(d) + 1e-10);  // loss_function.py:183 (_loss_for_hess_fn_)
-      e *= iden;
-      det *= iden;
-    }
-    double w = 0.0;
-    if (mk & 1) { s0 += e; w += (f == TSFF_FEATURE_ELE ? K.wts[1] : K.wts[0]); }
-    if (mk & 2) { s1 += e; w += K.wts[2]; }
-    Tb[r] = w != 0.0 ? det * w : 0.0;  // (samples outside every fit range may hold anything, NaN included)
+    Tb[r] = bin_loss(S, K, f, dpre[r], t, mpre[r], s0, s1);
   }
 
   // ================= adjoint of normalisation + binning: T_p = A_p ybin_p / M (+ noise), M attained at pstar =================
   double sn = 0.0, a1b = 0.0, a2b = 0.0;
 #pragma unroll
-  for (int r = 0; r < BPT; ++r) {
-    const int pb = 4 * ht + r;
-    const double u = Tb[r] * ybin[r] * invM;  // dL/dA_p
-    sn += u * Ap[r];
-    if (f == TSFF_FEATURE_ELE) { if (lpre[r] < p_lam) a1b += u * amps; else a2b += u * amps; }
-    else a1b += u * amps;
-  }
+  for (int r = 0; r < BPT; ++r) norm_adjoint_bin(f, Tb[r], ybin[r], invM, Ap[r], amps, lpre[r], p_lam, sn, a1b, a2b);
   // The five block sums (two loss sums, three sums of the normalisation's adjoint) are NOT waited for here: every wavefront leaves
   // its partial sums in LDS and goes on; they are read behind the barrier that follows the adjoint convolution anyway.  What needed
   // them at this point -- the correction -sn / M of ybar at the arg-max bin -- is linear in ybar and is applied to the convolved
@@ -563,10 +537,7 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_fused(KStatic S, KCall K,
   // k_loss_reduce -- in round 2 they were 1.8 us of one lane's latency plus two barriers at the end of every workgroup.
   {
     double lb[kLBRec];
-    lb[0] = LB.wpe2; lb[1] = LB.wL; lb[2] = LB.kL; lb[3] = LB.ivTe; lb[4] = LB.a_e; lb[5] = LB.pref; lb[6] = LB.Ud; lb[7] = LB.Vd;
-#pragma unroll
-    for (int s = 0; s < NI; ++s) { lb[8 + 3 * s] = LB.ixi[s]; lb[9 + 3 * s] = LB.a_i[s]; lb[10 + 3 * s] = LB.cs[s]; }
-    lb[NLB - 1] = LB.m;
+    lines_adj_store<NI>(LB, lb);
 #pragma unroll
     for (int k = 0; k < NLB; ++k) lb[k] = wave_sum(lb[k]);
     lb[NLB] = a1b; lb[NLB + 1] = a2b;   // (block sums: the same in every wavefront's record; the finish kernel reads wavefront 0's)
@@ -582,7 +553,7 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_fused(KStatic S, KCall K,
 
 // k_fused_prep: the lineout scalars of every (lineout, feature) item of a k_spectrum_fused launch -- one thread per item, the
 // very code of the spectrum kernels (load_phys, make_lines: the same bits), plus the four physical parameters the instrument chain
-// reads.  lrec[item][kLineRec]: wpe2, wL, kL, 1/vTe, a_e, pref, Ud, Vd, 2/wL | per ion 1/xi_i, a_i, c_s, -a_i/2 | lam, amp1, amp2, amp3.
+// reads.  lrec[item][kLineRec]: the line record (lines_store) | lam, amp1, amp2, amp3.
 // finrec[k][item] (component-major, read by k_fused_finish with one item per lane): the physical parameters and the sum of the
 // un-normalised fractions (NP + 1), sigmoid(x) of the slots that have one (NP), and the lineout scalars once more (9 + 4 n_ion).
 template <int NI>
@@ -603,32 +574,16 @@ __global__ __launch_bounds__(64) void k_fused_prep(KStatic S, const double* __re
   make_lines<NI>(p, S.lam_shift[f], 0, 1, L);
   {
     double ph[NPk + 1];
-    ph[TSFF_P_TE] = p.Te; ph[TSFF_P_NE] = p.ne; ph[TSFF_P_M] = p.m; ph[TSFF_P_LAM] = p.lam; ph[TSFF_P_AMP1] = p.amp1; ph[TSFF_P_AMP2] = p.amp2;
-    ph[TSFF_P_AMP3] = p.amp3; ph[TSFF_P_NE_GRADIENT] = p.neg; ph[TSFF_P_TE_GRADIENT] = p.teg; ph[TSFF_P_UD] = p.ud; ph[TSFF_P_VA] = p.Va;
-#pragma unroll
-    for (int s = 0; s < NI; ++s) {
-      const int o = TSFF_P_ION0 + 4 * s;
-      ph[o + TSFF_ION_TI] = p.Ti[s]; ph[o + TSFF_ION_Z] = p.Z[s]; ph[o + TSFF_ION_A] = p.A[s]; ph[o + TSFF_ION_FRACT] = p.fr[s];
-    }
-    ph[NPk] = p.fsum;
+    phys_to_array<NI>(p, ph);
     double* __restrict__ q = finrec + item;
 #pragma unroll
     for (int k = 0; k <= NPk; ++k) q[(size_t)k * nitems] = ph[k];
 #pragma unroll
     for (int k = 0; k < NPk; ++k) q[(size_t)(NPk + 1 + k) * nitems] = sgv[k];
-    q += (size_t)(2 * NPk + 1) * nitems;
-    q[0] = L.wpe2; q[nitems] = L.wL; q[2 * nitems] = L.kL; q[3 * nitems] = L.ivTe; q[4 * nitems] = L.a_e; q[5 * nitems] = L.pref;
-    q[6 * nitems] = L.Ud; q[7 * nitems] = L.Vd; q[8 * nitems] = L.i2wL;
-#pragma unroll
-    for (int s = 0; s < NI; ++s) {
-      q[(size_t)(9 + 4 * s) * nitems] = L.ixi[s]; q[(size_t)(10 + 4 * s) * nitems] = L.a_i[s]; q[(size_t)(11 + 4 * s) * nitems] = L.cs[s];
-      q[(size_t)(12 + 4 * s) * nitems] = L.hai[s];
-    }
+    lines_store<NI>(L, q + (size_t)(2 * NPk + 1) * nitems, nitems);
   }
   double* __restrict__ r = lrec + (size_t)item * kLineRec;
-  r[0] = L.wpe2; r[1] = L.wL; r[2] = L.kL; r[3] = L.ivTe; r[4] = L.a_e; r[5] = L.pref; r[6] = L.Ud; r[7] = L.Vd; r[8] = L.i2wL;
-#pragma unroll
-  for (int s = 0; s < NI; ++s) { r[9 + 4 * s] = L.ixi[s]; r[10 + 4 * s] = L.a_i[s]; r[11 + 4 * s] = L.cs[s]; r[12 + 4 * s] = L.hai[s]; }
+  lines_store<NI>(L, r, 1);
   r[9 + 4 * NI] = p.lam; r[10 + 4 * NI] = p.amp1; r[11 + 4 * NI] = p.amp2; r[12 + 4 * NI] = p.amp3;
 }
 
@@ -698,13 +653,7 @@ __global__ __launch_bounds__(kThreads) void k_fused_finish(KStatic S, const doub
     phys_from_lds<NI>(ph, p);
     q += (size_t)(2 * NPk + 1) * nitems;
     LineS<NI> L;
-    L.wpe2 = q[0]; L.wL = q[nitems]; L.kL = q[2 * nitems]; L.ivTe = q[3 * nitems]; L.a_e = q[4 * nitems]; L.pref = q[5 * nitems];
-    L.Ud = q[6 * nitems]; L.Vd = q[7 * nitems]; L.i2wL = q[8 * nitems]; L.m = 0.0;
-#pragma unroll
-    for (int s = 0; s < NI; ++s) {
-      L.ixi[s] = q[(size_t)(9 + 4 * s) * nitems]; L.a_i[s] = q[(size_t)(10 + 4 * s) * nitems]; L.cs[s] = q[(size_t)(11 + 4 * s) * nitems];
-      L.hai[s] = q[(size_t)(12 + 4 * s) * nitems];
-    }
+    lines_load<NI>(q, nitems, [](double v) { return v; }, L);
     double lb[NLB];
 #pragma unroll
     for (int k = 0; k < NLB; ++k) {
@@ -714,41 +663,15 @@ __global__ __launch_bounds__(kThreads) void k_fused_finish(KStatic S, const doub
     const double a1b = lbrec[(size_t)NLB * NW * nitems + item], a2b = lbrec[(size_t)(NLB + 1) * NW * nitems + item];
     LineS<NI> LB;
     zero_lines<NI>(LB);
-    LB.wpe2 = lb[0]; LB.wL = lb[1]; LB.kL = lb[2]; LB.ivTe = lb[3]; LB.a_e = lb[4]; LB.pref = lb[5]; LB.Ud = lb[6]; LB.Vd = lb[7];
-#pragma unroll
-    for (int s = 0; s < NI; ++s) { LB.ixi[s] = lb[8 + 3 * s]; LB.a_i[s] = lb[9 + 3 * s]; LB.cs[s] = lb[10 + 3 * s]; }
-    LB.m = lb[NLB - 1];
+    lines_adj_load<NI>(lb, true, LB);
     double g[NPk];
 #pragma unroll
     for (int s = 0; s < NPk; ++s) g[s] = 0.0;
     make_lines_adjoint<NI>(p, S.lam_shift[f], 0, 1, L, LB, g);
-    // amplitudes (irf.py:76,126-130)
-    if (f == TSFF_FEATURE_ELE) { g[TSFF_P_AMP1] += a1b; g[TSFF_P_AMP2] += a2b; }
-    else g[TSFF_P_AMP3] += a1b;
-    // Ti tying, fraction renormalisation (ts_params.py:543-563)
+    amp_adjoint(f, a1b, a2b, g);
+    tie_renorm_adjoint<NI>(S, p, gm == 1, g);
 #pragma unroll
-    for (int s = 1; s < NI; ++s)
-      if (S.ti_same[s]) {
-        g[TSFF_P_ION0 + TSFF_ION_TI] += g[TSFF_P_ION0 + 4 * s + TSFF_ION_TI];
-        g[TSFF_P_ION0 + 4 * s + TSFF_ION_TI] = 0.0;
-      }
-    double dot = 0.0;
-#pragma unroll
-    for (int s = 0; s < NI; ++s) dot += g[TSFF_P_ION0 + 4 * s + TSFF_ION_FRACT] * p.fr[s];
-#pragma unroll
-    for (int s = 0; s < NI; ++s) {
-      const int o = TSFF_P_ION0 + 4 * s + TSFF_ION_FRACT;
-      g[o] = (g[o] - dot) / p.fsum;
-      g[TSFF_P_ION0 + 4 * s + TSFF_ION_A] = 0.0;
-    }
-    if (gm != 1) g[TSFF_P_M] = 0.0;
-    // activation (ts_params.py:329-350) and the gradient mask
-#pragma unroll
-    for (int s = 0; s < NPk; ++s) {
-      double v = g[s] * S.p_scale[s];
-      if (S.p_sig[s]) { const double sg = sgv[s]; v *= sg * (1.0 - sg); }
-      gv[s] = gmask[s] ? v : 0.0;
-    }
+    for (int s = 0; s < NPk; ++s) gv[s] = activation_adjoint(g[s], S.p_scale[s], S.p_sig[s], [&] { return sgv[s]; }, gmask[s]);
   }
   if (nload == 2) {   // electron-feature part + ion-feature part (k_loss_reduce's order), in the even lane
 #pragma unroll

@@ -323,9 +323,7 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_rows(KStatic S, KCall K, 
 #pragma unroll
     for (int r = 0; r < BPT; ++r) {
       const int pb = PB(r);
-      double A;
-      if (f == TSFF_FEATURE_ELE) A = amps * (lamb[pb] < p_lam ? p_amp1 : p_amp2);  // irf.py:126-130
-      else A = amps * p_amp3;                                                      // irf.py:76
+      const double A = bin_amplitude(f, false, amps, f == TSFF_FEATURE_ELE ? lamb[pb] : 0.0, p_lam, p_amp1, p_amp2, p_amp3);
       K.thry[f][(size_t)b * TSFF_NBINS + pb] = thry_value(A, ybin[r], invM, K.noise[f] != nullptr,
                                                           K.noise[f] ? K.noise[f][(size_t)b * TSFF_NBINS + pb] : 0.0);   // thomson_diagnostic.py:139-140
     }
@@ -336,26 +334,12 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_rows(KStatic S, KCall K, 
 #pragma unroll
   for (int r = 0; r < BPT; ++r) {
     const int pb = PB(r);
-    double A;
-    if (f == TSFF_FEATURE_ELE) A = amps * (lamb[pb] < p_lam ? p_amp1 : p_amp2);  // irf.py:126-130
-    else A = amps * p_amp3;                                                      // irf.py:76
+    const double A = bin_amplitude(f, false, amps, f == TSFF_FEATURE_ELE ? lamb[pb] : 0.0, p_lam, p_amp1, p_amp2, p_amp3);
     Ap[r] = A;
     const double t = thry_value(A, ybin[r], invM, K.noise[f] != nullptr,
                                 K.noise[f] ? K.noise[f][(size_t)b * TSFF_NBINS + pb] : 0.0);   // thomson_diagnostic.py:139-140
     if (K.thry[f]) K.thry[f][(size_t)b * TSFF_NBINS + pb] = t;
-    const double d = K.data[f][(size_t)b * TSFF_NBINS + pb];
-    const uint8_t mk = S.mask[f][pb];
-    double e, det;
-    loss_point(S.loss_method, d, t, e, det);
-    if (K.denom_mode == 2 && (S.loss_method == TSFF_LOSS_L2 || S.loss_method == TSFF_LOSS_L1)) {
-      const double iden = 1.0 / (fabs(d) + 1e-10);  // loss_function.py:183 (_loss_for_hess_fn_)
-      e *= iden;
-      det *= iden;
-    }
-    double w = 0.0;
-    if (mk & 1) { s0 += e; w += (f == TSFF_FEATURE_ELE ? K.wts[1] : K.wts[0]); }
-    if (mk & 2) { s1 += e; w += K.wts[2]; }
-    Tb[r] = w != 0.0 ? det * w : 0.0;  // (samples outside every fit range may hold anything, NaN included)
+    Tb[r] = bin_loss(S, K, f, K.data[f][(size_t)b * TSFF_NBINS + pb], t, S.mask[f][pb], s0, s1);
   }
 
   // ================= adjoint of normalisation + binning: T_p = A_p ybin_p / M (+ noise), M attained at pstar =================
@@ -363,10 +347,7 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_rows(KStatic S, KCall K, 
 #pragma unroll
   for (int r = 0; r < BPT; ++r) {
     const int pb = PB(r);
-    const double u = Tb[r] * ybin[r] * invM;  // dL/dA_p
-    sn += u * Ap[r];
-    if (f == TSFF_FEATURE_ELE) { if (lamb[pb] < p_lam) a1b += u * amps; else a2b += u * amps; }
-    else a1b += u * amps;
+    norm_adjoint_bin(f, Tb[r], ybin[r], invM, Ap[r], amps, f == TSFF_FEATURE_ELE ? lamb[pb] : 0.0, p_lam, sn, a1b, a2b);
   }
   {   // the two loss sums and the three sums of the normalisation's adjoint in one reduction (half_sums)
     double v5[5] = {s0, s1, sn, a1b, a2b};
@@ -479,45 +460,21 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_rows(KStatic S, KCall K, 
     for (int k = 0; k < NLB; ++k) lb[k] = (r[k] + r[NLB + k]) + (r[2 * NLB + k] + r[3 * NLB + k]);
     LineS<NI> LB;
     zero_lines<NI>(LB);
-    LB.wpe2 = lb[0]; LB.wL = lb[1]; LB.kL = lb[2]; LB.ivTe = lb[3]; LB.a_e = lb[4]; LB.pref = lb[5]; LB.Ud = lb[6]; LB.Vd = lb[7];
-#pragma unroll
-    for (int s = 0; s < NI; ++s) { LB.ixi[s] = lb[8 + 3 * s]; LB.a_i[s] = lb[9 + 3 * s]; LB.cs[s] = lb[10 + 3 * s]; }
-    LB.m = lb[NLB - 1];
+    lines_adj_load<NI>(lb, true, LB);
     Phys<NI> p;
     phys_from_lds<NI>(m.phys, p);
     double g[NPk];   // (registers: the LDS read-modify-writes this section used to make were a serial chain of round trips)
 #pragma unroll
     for (int s = 0; s < NPk; ++s) g[s] = 0.0;
     make_lines_adjoint<NI>(p, lam_shift, 0, 1, L, LB, g);
-    // amplitudes (irf.py:76,126-130)
-    if (f == TSFF_FEATURE_ELE) { g[TSFF_P_AMP1] += a1b; g[TSFF_P_AMP2] += a2b; }
-    else g[TSFF_P_AMP3] += a1b;
-    // Ti tying, fraction renormalisation (ts_params.py:543-563)
-#pragma unroll
-    for (int s = 1; s < NI; ++s)
-      if (S.ti_same[s]) {
-        g[TSFF_P_ION0 + TSFF_ION_TI] += g[TSFF_P_ION0 + 4 * s + TSFF_ION_TI];
-        g[TSFF_P_ION0 + 4 * s + TSFF_ION_TI] = 0.0;
-      }
-    double dot = 0.0;
-#pragma unroll
-    for (int s = 0; s < NI; ++s) dot += g[TSFF_P_ION0 + 4 * s + TSFF_ION_FRACT] * p.fr[s];
-#pragma unroll
-    for (int s = 0; s < NI; ++s) {
-      const int o = TSFF_P_ION0 + 4 * s + TSFF_ION_FRACT;
-      g[o] = (g[o] - dot) / p.fsum;
-      g[TSFF_P_ION0 + 4 * s + TSFF_ION_A] = 0.0;
-    }
-    if (GM != 1) g[TSFF_P_M] = 0.0;
+    amp_adjoint(f, a1b, a2b, g);
+    tie_renorm_adjoint<NI>(S, p, GM == 1, g);
 #pragma unroll
     for (int s = 0; s < NPk; ++s) gsum[s] = g[s];
   }
   __syncthreads();
-  // activation (ts_params.py:329-350) and the gradient mask
   if (tid < NPk) {
-    double v = gsum[tid] * fin_scale;
-    if (fin_sig) { const double sg = sigmoid(fin_x); v *= sg * (1.0 - sg); }
-    v = fin_mask ? v : 0.0;
+    const double v = activation_adjoint(gsum[tid], fin_scale, fin_sig, [&] { return sigmoid(fin_x); }, fin_mask);
     if (interleaved) K.gpart[((size_t)f * K.B + b) * NPk + tid] = v;  // summed over the two features by k_loss_reduce
     else grad[(size_t)b * NPk + tid] = v;
   }

@@ -816,6 +816,63 @@ __device__ __forceinline__ void zero_lines(LineS<NI>& L) {
   for (int s = 0; s < NI; ++s) L.ixi[s] = L.a_i[s] = L.cs[s] = L.hai[s] = 0.0;
 }
 
+// the inverse of phys_from_lds
+template <int NI>
+__device__ __forceinline__ void phys_to_array(const Phys<NI>& p, double* ph) {
+  ph[TSFF_P_TE] = p.Te; ph[TSFF_P_NE] = p.ne; ph[TSFF_P_M] = p.m; ph[TSFF_P_LAM] = p.lam; ph[TSFF_P_AMP1] = p.amp1; ph[TSFF_P_AMP2] = p.amp2;
+  ph[TSFF_P_AMP3] = p.amp3; ph[TSFF_P_NE_GRADIENT] = p.neg; ph[TSFF_P_TE_GRADIENT] = p.teg; ph[TSFF_P_UD] = p.ud; ph[TSFF_P_VA] = p.Va;
+#pragma unroll
+  for (int s = 0; s < NI; ++s) {
+    const int o = TSFF_P_ION0 + 4 * s;
+    ph[o + TSFF_ION_TI] = p.Ti[s]; ph[o + TSFF_ION_Z] = p.Z[s]; ph[o + TSFF_ION_A] = p.A[s]; ph[o + TSFF_ION_FRACT] = p.fr[s];
+  }
+  ph[TSFF_NP(NI)] = p.fsum;
+}
+
+// the adjoint-carrying fields of LineS as lb[9 + 3 NI]: wpe2, wL, kL, ivTe, a_e, pref, Ud, Vd | ixi, a_i, cs per species | m.
+// The layout of the kernels' wavefront reductions and of the LBacc records that k_ff2d_lines_adj reads (there without m unless
+// with_m).  The load sets those fields only.
+template <int NI>
+__device__ __forceinline__ void lines_adj_store(const LineS<NI>& LB, double* lb) {
+  lb[0] = LB.wpe2; lb[1] = LB.wL; lb[2] = LB.kL; lb[3] = LB.ivTe; lb[4] = LB.a_e; lb[5] = LB.pref; lb[6] = LB.Ud; lb[7] = LB.Vd;
+#pragma unroll
+  for (int s = 0; s < NI; ++s) { lb[8 + 3 * s] = LB.ixi[s]; lb[9 + 3 * s] = LB.a_i[s]; lb[10 + 3 * s] = LB.cs[s]; }
+  lb[8 + 3 * NI] = LB.m;
+}
+
+template <int NI>
+__device__ __forceinline__ void lines_adj_load(const double* lb, bool with_m, LineS<NI>& LB) {
+  LB.wpe2 = lb[0]; LB.wL = lb[1]; LB.kL = lb[2]; LB.ivTe = lb[3]; LB.a_e = lb[4]; LB.pref = lb[5]; LB.Ud = lb[6]; LB.Vd = lb[7];
+#pragma unroll
+  for (int s = 0; s < NI; ++s) { LB.ixi[s] = lb[8 + 3 * s]; LB.a_i[s] = lb[9 + 3 * s]; LB.cs[s] = lb[10 + 3 * s]; }
+  if (with_m) LB.m = lb[8 + 3 * NI];
+}
+
+// the line record of a lineout, 9 + 4 NI values q[k stride]: wpe2, wL, kL, 1/vTe, a_e, pref, Ud, Vd, 2/wL | per ion 1/xi_i, a_i,
+// c_s, -a_i/2 (k_fused_prep writes it; stride 1 for the item-major lrec, the item count for the component-major finrec).  The load
+// passes every value through cvt (uni for wavefront-uniform scalar loads) and sets m = 0.
+template <int NI>
+__device__ __forceinline__ void lines_store(const LineS<NI>& L, double* q, size_t stride) {
+  q[0] = L.wpe2; q[stride] = L.wL; q[2 * stride] = L.kL; q[3 * stride] = L.ivTe; q[4 * stride] = L.a_e; q[5 * stride] = L.pref;
+  q[6 * stride] = L.Ud; q[7 * stride] = L.Vd; q[8 * stride] = L.i2wL;
+#pragma unroll
+  for (int s = 0; s < NI; ++s) {
+    q[(9 + 4 * s) * stride] = L.ixi[s]; q[(10 + 4 * s) * stride] = L.a_i[s]; q[(11 + 4 * s) * stride] = L.cs[s];
+    q[(12 + 4 * s) * stride] = L.hai[s];
+  }
+}
+
+template <int NI, class CVT>
+__device__ __forceinline__ void lines_load(const double* q, size_t stride, CVT cvt, LineS<NI>& L) {
+  L.wpe2 = cvt(q[0]); L.wL = cvt(q[stride]); L.kL = cvt(q[2 * stride]); L.ivTe = cvt(q[3 * stride]); L.a_e = cvt(q[4 * stride]);
+  L.pref = cvt(q[5 * stride]); L.Ud = cvt(q[6 * stride]); L.Vd = cvt(q[7 * stride]); L.i2wL = cvt(q[8 * stride]); L.m = 0.0;
+#pragma unroll
+  for (int s = 0; s < NI; ++s) {
+    L.ixi[s] = cvt(q[(9 + 4 * s) * stride]); L.a_i[s] = cvt(q[(10 + 4 * s) * stride]); L.cs[s] = cvt(q[(11 + 4 * s) * stride]);
+    L.hai[s] = cvt(q[(12 + 4 * s) * stride]);
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // parameter transform  (ts_params.py:329-350, 543-603)
 // ------------------------------------------------------------------------------------------

@@ -8,6 +8,7 @@
 //                                          chain rule to the normalised leaves
 //   k_loss_reduce  a14                   : deterministic reduction of the masked loss sums
 //   k_form_factor  a4-a10                : raw FormFactor.__call__ output (known-answer tests)
+//   k_chain.inc    a12, a14, a15         : the chain's rules around the sweeps (amplitudes, loss, their adjoint, gradient tail), once
 //   k_hess_pairs   a16                   : exact per-lineout Hessian of the fit loss (hyper-dual forward mode, k_hessian.inc)
 #include "tsff_device.h"
 
@@ -79,6 +80,7 @@ struct KCall {
   int b0, Btot;
 };
 
+#include "k_chain.inc"
 #include "k_tables.inc"
 #include "k_spectrum.inc"
 constexpr int kLineRec = 24;     // doubles per item of k_fused_prep's record: 9 + 4 n_ion lineout scalars + lam, amp1, amp2, amp3
