@@ -31,6 +31,9 @@
  *   - the caller owns every buffer; the library never frees caller memory;
  *   - calls are asynchronous on the handle's stream (tsff_set_stream); the caller synchronises;
  *   - return value 0 = success, negative = error, text via tsff_last_error();
+ *   - a refused call (negative return) of tsff_forward, tsff_loss_grad(_packed, _fe), tsff_loss_hess, tsff_array_loss and
+ *     tsff_form_factor(_grad) has enqueued nothing: their arguments, LDS budgets and buffers are checked before the first
+ *     launch, and tsff_last_launch reports an empty list (other entry points may have enqueued work before a failure);
  *   - a handle is bound to the device that was current at tsff_create; handles are not thread-safe,
  *     the library is re-entrant across handles.
  *   - no CPU fallback exists: without a HIP device every entry point fails.
@@ -158,6 +161,13 @@ const char *tsff_last_error(const tsff_handle *h); /* h == NULL: last tsff_creat
  * valid until the next call on h.  Recorded on the host: no device synchronisation. */
 const char *tsff_last_launch(const tsff_handle *h);
 int tsff_abi_version(void);
+/* Bind the handle to a stream; later calls enqueue on it.  The handle's scratch is shared by its calls, so when the stream
+ * changes after a call, the new stream first waits on an event recorded on the old one: a call on the new stream never
+ * overtakes the handle's work still running on the old one (the caller's own buffers are the caller's to order).  Setting the
+ * stream the handle already has is a no-op.  The stream a handle is bound to must stay valid while it is bound: to retire a
+ * stream, first bind the handle to another one (or to the null stream), then destroy it.  If either stream is capturing a
+ * graph, the new stream does not wait: ordering it behind earlier work is then the caller's job (see the graph-capture contract
+ * at tsff_reserve). */
 int tsff_set_stream(tsff_handle *h, void *hip_stream);
 /* options.  TSFF_OPT_DENOM_MODE: denominators of the l1/l2 functionals in tsff_loss_grad -- 0 (default):
  * constants folded into `weights` (LossFunction.__loss__, loss_function.py:364-373); 2: |data| + 1e-10 per sample
@@ -181,7 +191,12 @@ int tsff_set_stream(tsff_handle *h, void *hip_stream);
  * and vector instructions share one datapath: DESIGN.md section 4.2), which is why it is off. */
 enum { TSFF_OPT_DENOM_MODE = 1, TSFF_OPT_LAUNCH_PLAN = 2, TSFF_OPT_DLM_BLOCKS = 3 };
 int tsff_set_option(tsff_handle *h, int32_t key, int32_t value);
-/* make sure the workspace holds B lineouts (calls grow it lazily; not inside graph capture) */
+/* make sure the workspace holds B lineouts (calls grow it lazily).
+ * Graph capture: tsff_forward and tsff_loss_grad(_packed) can be captured on the handle's stream after (1) tsff_reserve(h, B) with B at least the captured batch, (2) one eager call with the grad mask and slot list to
+ * be captured, (3) a synchronisation of the stream.  A call on a capturing stream that would have to allocate, upload a changed
+ * mask or slot list, or synchronise is refused with -2 and enqueues nothing; so is a loss + gradient call that would run the
+ * pipelined DLM plan (TSFF_OPT_DLM_BLOCKS > 1 forks onto a second stream: set the option to 0 before capturing).  The captured kernels take the device pointers and
+ * the host scalars (weights, B, offsets) of the call: replays read new parameters from the same buffers. */
 int tsff_reserve(tsff_handle *h, int32_t B);
 
 /* wavelength axes (HOST pointers): the binned axes lamAxisE/lamAxisI [1024] in nm that the

@@ -1,0 +1,682 @@
+"""The library run the way include/tsff.h and INTEGRATION.md say it may be run: many handles on many streams, from two host
+threads, configs[4]'s eight ranks on one device, one handle moved between streams, handles with different velocity grids in one
+process, refused calls, and graph capture.
+
+The reference of every concurrent result is the same call made serially (one stream, a synchronisation after each call): equal
+bit for bit, except the table adjoints (d loss / d fe, d loss / d fe2d: gathered with LDS atomics), which are reproducible to
+1e-13 of their largest entry (test_adjoints_are_run_to_run_reproducible).  The serial results of the first round are checked
+against the oracles at the bounds of test_kernel_matrix.py, and every call's tsff_last_launch equals its serial twin's.
+"""
+import os
+import subprocess
+import sys
+import threading
+
+import numpy as np
+import pytest
+
+import decks
+import util
+from oracle import tsadar_oracle as orc
+from test_kernel_matrix import (_cheap_batch, _deck, _fe2d, _ff2d_check_adjoint, _ff2d_check_forward, _free_form_fe, _phys,
+                                _spectrum_check, _spectrum_inputs)
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TABLE_ADJOINTS = ("gfe", "gf2d")   # LDS-atomic gathers: 1e-13 of the largest entry instead of bit equality
+
+
+def _torch():
+    import torch
+
+    assert torch.cuda.is_available(), "gpu tests need a HIP device"
+    return torch
+
+
+def _engine(cfg, sa, **kw):
+    from tsadar_amd.engine import Engine
+
+    return Engine(cfg, sa, **kw)
+
+
+def _host(out):
+    return {k: v.cpu().numpy() for k, v in out.items() if v is not None}
+
+
+def _same(name, got, ref, what):
+    for k in ref:
+        if k in TABLE_ADJOINTS:
+            err = np.max(np.abs(got[k] - ref[k]))
+            assert err <= 1e-13 * np.max(np.abs(ref[k])), (name, what, k, err)
+        else:
+            assert np.array_equal(got[k], ref[k]), (name, what, k, np.max(np.abs(got[k] - ref[k])))
+
+
+def _twin_weighted_grad(cfg, sa, normed, batch, w, names, fe_batch=None):
+    """d (sum_k w[k] S_k) / d leaves of the given lineouts by reverse-mode autodiff of the torch twin: the per-lineout gradient
+    of the library's loss (weights fixed by the whole batch), whatever subset of lineouts is evaluated."""
+    import torch
+    from oracle import tsadar_oracle_torch as ot
+
+    nt = {k: ot._t(v).clone() for k, v in normed.items()}
+    for k in names:
+        nt[k].requires_grad_(True)
+    fb = None if fe_batch is None else torch.tensor(fe_batch, dtype=torch.float64, requires_grad=True)
+    S, _, E, I = ot.masked_sums(cfg, sa, nt, batch, True, fb)
+    val = (torch.as_tensor(np.asarray(w, dtype=np.float64)) * S).sum()
+    leaves = [nt[k] for k in names] + ([fb] if fb is not None else [])
+    grads = torch.autograd.grad(val, leaves, allow_unused=True)
+    out = {k: g.numpy() for k, g in zip(names, grads)}
+    return S.detach().numpy(), out, (grads[-1].numpy() if fb is not None else None), E.detach().numpy(), I.detach().numpy()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# workloads: one engine each, every form that owns scratch or hands work between workgroups
+# ---------------------------------------------------------------------------------------------------------------------
+
+class Work:
+    """One engine and its calls: ``call(r)`` enqueues round r on the current stream and returns its device outputs and the
+    launch list of each library call; ``check(r, out)`` compares round r's serial outputs with the oracles through
+    test_kernel_matrix's checks (test_hessian_exact's twin for the Hessian)."""
+
+    def __init__(self, name, d, B, entry, plan=0, kernels=()):
+        from test_hessian_exact import _leaves, _weights
+        from tsadar_amd import _lib as L
+
+        torch = _torch()
+        self.name, self.d, self.B, self.entry, self.kernels = name, d, B, entry, kernels
+        n = self.n_ion = d.get("n_ion", 1)
+        self.cfg = _deck(d)
+        nang = d.get("nang", 10)
+        self.sa = dict(sa=np.linspace(53.6, 66.1, nang), weights=np.ones((B, nang)) / nang)
+        self.eng = _engine(self.cfg, self.sa, fe_mode=L.FE_PER_LINEOUT if d.get("fe") else None)
+        self.eng.set_launch_plan(plan)
+        dev = self.eng.device
+        self.normed, self.X, self.Xd, self.extra = [], [], [], []
+        for r in range(3):
+            if entry == "ff2d":   # physical parameters, the 2-D table and a seed of the adjoint
+                nm, X = _phys(self.cfg, self.sa, B, n, 61 + n + 100 * r)
+                G = int(self.eng._cfg_struct.num_grad_points)
+                shape = (B, G, self.eng.npts, int(self.eng._cfg_struct.n_angles))
+                ex = dict(fe2=torch.as_tensor(_fe2d(48)[1], device=dev),
+                          Pbar=torch.as_tensor(np.random.default_rng(40 + r).standard_normal(shape), device=dev))
+                self.batch = _cheap_batch(B)
+            else:
+                self.batch, nm, X, fe = _spectrum_inputs(self.eng, self.cfg, self.sa, d, B, n, round_=r)
+                ex = dict(fe=torch.as_tensor(fe, device=dev)) if fe is not None else {}
+            self.normed.append(nm)
+            self.X.append(X)
+            self.Xd.append(torch.as_tensor(X, device=dev))
+            self.extra.append(ex)
+        i_norm, e_norm = orc.loss_norms(self.cfg, self.batch)
+        self.w = self.eng.loss_weights(B, i_norm, e_norm, self.cfg["data"]["ion_loss_scale"])
+        self.gm = self.eng.slots.active.astype(np.uint8)
+        _, self.names, self.act = _leaves(self.cfg)
+        if entry == "hess":   # (the twin's Hessian loss: w = 1, 1/2, 1/2)
+            self.w = _weights(self.cfg)
+        self.db = {k: (torch.as_tensor(np.asarray(v, dtype=np.float64), device=dev).contiguous() if v is not None else None)
+                   for k, v in self.batch.items()}
+        torch.cuda.synchronize()
+
+    def call(self, r):
+        e, X, ex = self.eng, self.Xd[r], self.extra[r]
+        if self.entry == "lg":
+            t, g, E, I = e.loss_grad(X, self.db, self.w, self.gm, want_spectra=True)
+            return dict(terms=t, grad=g, E=E, I=I), [e.last_launch()]
+        if self.entry == "lgfe":
+            t, g, E, I, gfe = e.loss_grad(X, self.db, self.w, self.gm, fe=ex["fe"], want_spectra=True, want_fe_grad=True)
+            return dict(terms=t, grad=g, E=E, I=I, gfe=gfe), [e.last_launch()]
+        if self.entry == "fwd":
+            E, I = e.forward(X, self.db["e_amps"], self.db["i_amps"], self.db["noise_e"], self.db["noise_i"])
+            return dict(E=E, I=I), [e.last_launch()]
+        if self.entry == "hess":
+            t, g, H = e.loss_hess(X, self.db, self.w, self.act)
+            return dict(terms=t, grad=g, hess=H), [e.last_launch()]
+        if self.entry == "ff2d":
+            P = e.form_factor_2d(1, X, ex["fe2"], 25.0, -40.0, save=True)
+            l1 = e.last_launch()
+            gp, gf = e.form_factor_2d_grad(1, X, ex["fe2"], ex["Pbar"], 25.0, -40.0, use_saved=True)
+            return dict(P=P, gp=gp, gf2d=gf), [l1, e.last_launch()]
+        raise ValueError(self.entry)
+
+    def check(self, r, out):
+        """round r's serial outputs (host arrays) against the oracles"""
+        cfg, B, n = self.cfg, self.B, self.n_ion
+        if self.entry == "ff2d":   # the forward against the oracle, both adjoints by central differences of the forward
+            _ff2d_check_forward(cfg, self.sa, B, n, self.normed[r], 1, 48, 25.0, -40.0, out["P"])
+            _ff2d_check_adjoint(self.eng, self.X[r], _fe2d(48)[1], self.extra[r]["Pbar"], 1, 25.0, -40.0, n, out["gp"], out["gf2d"])
+            return
+        if self.entry == "hess":
+            from test_hessian_exact import HESS_TOL, _twin_hessian
+
+            for b in range(B):
+                one = lambda t: {k: (v[b:b + 1] if isinstance(v, np.ndarray) and v.ndim >= 1 else v) for k, v in t.items()}
+                Ho = _twin_hessian(cfg, dict(sa=self.sa["sa"], weights=self.sa["weights"][:1]), one(self.normed[r]), one(self.batch),
+                                   self.names)
+                H = out["hess"][b]
+                assert np.array_equal(H, H.T)
+                assert np.max(np.abs(H - Ho)) <= HESS_TOL * np.max(np.abs(Ho)), b
+            return
+        fe = self.extra[r]["fe"].cpu().numpy() if "fe" in self.extra[r] else None
+        _spectrum_check(cfg, self.sa, self.d, B, self.entry, n, self.eng, self.batch, self.normed[r], self.X[r], fe, self.w, self.gm, out)
+
+
+WORKS = [
+    # (name, deck, B, entry, plan, kernels the call must launch: a name, or the prefix of one)
+    ("headline", {}, 4096, "lg", 0, ("k_fused_prep<1>", "k_spectrum_fused<1, 0, false, true>", "k_fused_finish<1>")),
+    ("rows_split", {"ppp": 5, "m": True, "nvx": 320}, 16, "lg", 0, ("k_fe_vectors<1>", "k_spectrum_rows<1, 1, ")),
+    ("rows", {"ppp": 5, "nvx": 320}, 256, "lg", 0, ("k_spectrum_rows<1, 0, ",)),
+    ("dlm", {"m": True}, 8, "lg", 0, ("k_fe_vectors<1>", "k_wgemm_w", "k_spectrum_fused<1, 1, ")),
+    ("two_sweep", {}, 64, "lg", 2, ("k_spectrum<1, 1, 0, ",)),
+    ("free_fe", {"fe": True}, 4, "lgfe", 0, ("k_fe_vectors<1>", "k_spectrum<1, 1, 2, ", "k_wgemm_t")),
+    ("forward", {}, 600, "fwd", 0, ("k_fused_prep<1>", "k_forward_pairs<1, true, 2, 2>")),
+    ("hess", {}, 4, "hess", 0, ("k_hess_pairs<1>", "k_hess_finish")),
+    ("three_ion", {"n_ion": 3}, 4, "lg", 0, ("k_spectrum<3, 1, 0, 256, false>",)),
+    ("ff2d", {}, 2, "ff2d", 0, ("k_form_factor_2d<1, true, 4, true>",)),
+]
+
+
+@pytest.fixture(scope="module")
+def works():
+    _torch()
+    return [Work(*w) for w in WORKS]
+
+
+@pytest.fixture(scope="module")
+def serial(works):
+    """every round of every workload, one stream, synchronised after each call; round 0 against the oracles"""
+    torch = _torch()
+    ref = {}
+    for w in works:
+        for r in range(3):
+            out, launches = w.call(r)
+            torch.cuda.synchronize()
+            ref[w.name, r] = (_host(out), launches)
+        if w.name == "rows_split":
+            _assert_split_form(w.B)
+        for k in w.kernels:
+            assert any(x == k or (k.endswith(" ") and x.startswith(k)) for l in ref[w.name, 0][1] for x in l), (w.name, k, ref[w.name, 0][1])
+        w.check(0, ref[w.name, 0][0])
+    return ref
+
+
+def _assert_split_form(B, nload=2):
+    """The 5-points-per-pixel rows kernel spreads the rounds of a (lineout, feature) over workgroups that meet through per-handle
+    arrival tickets when 2 x B x features <= CUs and plan bit 0 is clear (plan_spectrum in tsff_api.inc): make sure the batch
+    of the case keeps it on this device, so that the ticket path cannot drop out of the test unnoticed"""
+    torch = _torch()
+    ncu = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+    assert 2 * B * nload <= ncu, (B, ncu)
+
+
+def _round_robin(ws, stream_of):
+    torch = _torch()
+    got = {}
+    for r in range(3):
+        for w in ws:
+            with torch.cuda.stream(stream_of(w)):
+                got[w.name, r] = w.call(r)
+    return got
+
+
+def _compare(got, serial):
+    torch = _torch()
+    torch.cuda.synchronize()
+    for (name, r), (out, launches) in got.items():
+        ref, ref_launches = serial[name, r]
+        assert launches == ref_launches, (name, r, launches, ref_launches)
+        _same(name, _host(out), ref, f"round {r}")
+
+
+def test_many_handles_many_streams_one_thread(works, serial):
+    torch = _torch()
+    streams = {w.name: torch.cuda.Stream() for w in works}
+    got = _round_robin(works, lambda w: streams[w.name])
+    _compare(got, serial)
+
+
+def test_two_host_threads(works, serial):
+    torch = _torch()
+    halves = [works[0::2], works[1::2]]
+    results, errors = [{}, {}], []
+
+    def run(i):
+        try:
+            s = torch.cuda.Stream()
+            results[i].update(_round_robin(halves[i], lambda w: s))
+        except BaseException as e:   # (re-raised in the main thread)
+            errors.append(e)
+
+    th = [threading.Thread(target=run, args=(i,)) for i in range(2)]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join()
+    if errors:
+        raise errors[0]
+    _compare({**results[0], **results[1]}, serial)
+
+
+def _config4_deck(B_global):
+    from tsadar_amd import synthetic as S
+
+    return S.baseline_deck(points_per_pixel=5, nvx=320, active=("Te", "ne", "m", "amp1", "amp2", "lam"), batch_size=B_global)
+
+
+def test_config4_eight_ranks_on_one_device():
+    """configs[4]'s eight ranks (B = 512 of 4096 each, b_offset = 512 r) as eight handles on eight streams, concurrently"""
+    torch = _torch()
+    from tsadar_amd import _lib as L
+    from tsadar_amd import synthetic as S
+
+    R, B, Bg = 8, 512, 4096
+    cfg = _config4_deck(Bg)
+    rng = np.random.default_rng(S.SEED + 8)
+    sa = util.sa_fit(Bg)
+    engs = [_engine(cfg, dict(sa=sa["sa"], weights=sa["weights"][:B])) for _ in range(R)]
+    guess = S.draw_params(cfg, Bg, rng, dlm=True)
+    batch = _cheap_batch(Bg)
+    X = guess.to_matrix()
+    # the DLM order takes four values (a different one lineout to lineout): the C++ oracle below, whose f_e is shared, runs once per value
+    m_norm = X[rng.choice(Bg, 4, replace=False), L.P_M]
+    X[:, L.P_M] = m_norm[rng.integers(0, 4, Bg)]
+    gm = guess.grad_mask()
+    act = [s for s in range(engs[0].NP) if gm[s]]
+    w = engs[0].loss_weights(Bg, float(batch["i_data"].max()), float(batch["e_data"].max()), cfg["data"]["ion_loss_scale"])
+    dev = engs[0].device
+    shard = lambda a, r: a[r * B:(r + 1) * B]
+    Xd = [torch.as_tensor(shard(X, r), device=dev) for r in range(R)]
+    db = [{k: (torch.as_tensor(shard(v, r), device=dev).contiguous() if v is not None else None) for k, v in batch.items()} for r in range(R)]
+
+    def call(r):
+        out = torch.empty(3 + len(act) * Bg, dtype=torch.float64, device=dev)
+        engs[r].loss_grad_packed(Xd[r], db[r], w, gm, act, Bg, r * B, out=out)
+        return out
+
+    ref, ref_launch = [], []
+    for r in range(R):
+        ref.append(call(r).cpu().numpy())
+        torch.cuda.synchronize()
+        ref_launch.append(engs[r].last_launch())
+        assert any(k.startswith("k_spectrum_rows<1, 1, ") for k in ref_launch[r]), ref_launch[r]
+    streams = [torch.cuda.Stream() for _ in range(R)]
+    outs = []
+    for r in range(R):
+        with torch.cuda.stream(streams[r]):
+            outs.append(call(r))
+        assert engs[r].last_launch() == ref_launch[r], (r, engs[r].last_launch(), ref_launch[r])
+    torch.cuda.synchronize()
+    total = np.zeros_like(ref[0])
+    for r in range(R):
+        p = outs[r].cpu().numpy()
+        assert np.array_equal(p, ref[r]), r
+        rows = p[3:].reshape(len(act), Bg)
+        assert np.all(rows[:, :r * B] == 0.0) and np.all(rows[:, (r + 1) * B:] == 0.0), r
+        total += p
+    # the sum of the eight buffers: the loss sums and every column but the DLM order's against the C++ dual-number oracle, every
+    # lineout, one run per value of the order with that order's f_e (test_loss_grad_packed_config4_rank_shard's bounds) ...
+    from oracle import c_oracle as co
+
+    sm = engs[0].slots
+    rows = total[3:].reshape(len(act), Bg)
+    gm_plain = np.array(gm)
+    gm_plain[L.P_M] = 0
+    sums = np.zeros(3)
+    for x in m_norm:
+        idx = np.nonzero(X[:, L.P_M] == x)[0]
+        m_phys = (1.0 / (1.0 + np.exp(-x)) if sm.sigmoid[L.P_M] else x) * sm.scale[L.P_M] + sm.shift[L.P_M]
+        sg = {k: (v[idx] if isinstance(v, np.ndarray) and v.ndim >= 1 else v) for k, v in batch.items()}
+        su, gref, _, _ = co.loss_grad(cfg, dict(sa=sa["sa"], weights=sa["weights"][idx]), X[idx], sg, w=w, gmask=gm_plain,
+                                      fe=orc.dlm_fe(m_phys, 320), want_spectra=False)
+        sums += su.sum(axis=0)
+        for k, s in enumerate(act):
+            if s != L.P_M:
+                assert np.max(np.abs(rows[k, idx] - gref[:, s])) < 1e-6 * np.max(np.abs(gref[:, s])), (s, m_phys)
+    np.testing.assert_allclose(total[:3], sums, rtol=1e-9)
+    # ... and every leaf, the DLM order included, against reverse-mode autodiff of the torch twin on a seeded sample from every shard
+    sample = np.sort(np.concatenate([r * B + np.random.default_rng(70 + r).choice(B, 8, replace=False) for r in range(R)]))
+    names = {util.slot_of(k): k for k in ("Te", "ne", "m", "lam", "amp1", "amp2")}
+    nm = {k: X[sample, util.slot_of(k)] for k in orc.init_normed_params(cfg["parameters"], len(sample), True)}
+    sb = {k: (v[sample] if isinstance(v, np.ndarray) and v.ndim >= 1 else v) for k, v in batch.items()}
+    Ssub, ref_g, _, _, _ = _twin_weighted_grad(cfg, dict(sa=sa["sa"], weights=sa["weights"][sample]), nm, sb, w,
+                                               [names[s] for s in act])
+    for k, s in enumerate(act):   # per column: relative to the column's largest entry
+        g = ref_g[names[s]]
+        assert np.max(np.abs(rows[k, sample] - g)) < 1e-6 * np.max(np.abs(g)), names[s]
+
+
+def _hip():
+    """the HIP runtime torch loaded (stream creation and destruction for the stream-lifetime case)"""
+    import ctypes as C
+
+    _torch()
+    with open("/proc/self/maps") as f:   # (the copy already mapped into this process: a second runtime would not share its streams)
+        paths = sorted({ln.split()[-1] for ln in f if "libamdhip64.so" in ln})
+    assert paths, "libamdhip64 is not loaded"
+    hip = C.CDLL(paths[0])
+    hip.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
+    hip.hipStreamDestroy.argtypes = [C.c_void_p]
+    hip.hipStreamSynchronize.argtypes = [C.c_void_p]
+    return hip
+
+
+def test_set_stream_orders_the_new_stream_behind_the_old(works, serial):
+    """tsff_set_stream itself, without the Engine (whose own wait_stream would hide it): a call on s1 queued behind a long
+    device-side sleep, then tsff_set_stream(s2) and a call on s2 with other parameters, no synchronisation in between.  When s2
+    has drained, s1 must have too (s2 waited for the handle's work on s1), and both results equal their serial twins.  Then a
+    stream is retired the way tsff.h says (the handle bound to another one first, then the stream destroyed): the handle keeps
+    working."""
+    import ctypes as C
+
+    torch = _torch()
+    from tsadar_amd import _lib as L
+
+    w = {x.name: x for x in works}["headline"]
+    eng, lib, h, B = w.eng, w.eng.lib, w.eng.h, w.B
+    p = eng._ptr
+    wa, ga = np.ascontiguousarray(w.w, dtype=np.float64), np.ascontiguousarray(w.gm, dtype=np.uint8)
+    outs = [(torch.empty(3, dtype=torch.float64, device=eng.device), torch.empty((B, eng.NP), dtype=torch.float64, device=eng.device))
+            for _ in range(3)]
+
+    def raw(r, out):
+        d = w.db
+        rc = lib.tsff_loss_grad(h, p(w.Xd[r]), None, p(d["e_data"]), p(d["i_data"]), p(d["e_amps"]), p(d["i_amps"]), p(d["noise_e"]),
+                                p(d["noise_i"]), B, wa.ctypes.data_as(L.c_double_p), ga.ctypes.data_as(L.c_uint8_p), p(out[0]), p(out[1]),
+                                None, None)
+        L.check(lib, h, rc)
+
+    def same(r, out):
+        ref = serial["headline", r][0]
+        assert np.array_equal(out[0].cpu().numpy(), ref["terms"]) and np.array_equal(out[1].cpu().numpy(), ref["grad"]), r
+
+    s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+    torch.cuda.synchronize()
+    L.check(lib, h, lib.tsff_set_stream(h, C.c_void_p(s1.cuda_stream)))
+    with torch.cuda.stream(s1):
+        torch.cuda._sleep(100_000_000)   # (tens of milliseconds or more: far longer than the call that follows on s2)
+    raw(0, outs[0])
+    L.check(lib, h, lib.tsff_set_stream(h, C.c_void_p(s2.cuda_stream)))
+    raw(1, outs[1])
+    s2.synchronize()
+    s1_done = s1.query()
+    torch.cuda.synchronize()
+    assert s1_done, "the call on s2 did not wait for the handle's work on s1"
+    same(0, outs[0])
+    same(1, outs[1])
+    # a stream of the caller's own, retired as tsff.h prescribes: the handle moved to another stream first, then the stream destroyed
+    hip = _hip()
+    s3 = C.c_void_p()
+    assert hip.hipStreamCreate(C.byref(s3)) == 0
+    L.check(lib, h, lib.tsff_set_stream(h, s3))
+    raw(2, outs[2])
+    L.check(lib, h, lib.tsff_set_stream(h, C.c_void_p(s2.cuda_stream)))
+    assert hip.hipStreamSynchronize(s3) == 0
+    assert hip.hipStreamDestroy(s3) == 0
+    raw(1, outs[1])
+    torch.cuda.synchronize()
+    same(2, outs[2])
+    same(1, outs[1])
+    L.check(lib, h, lib.tsff_set_stream(h, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    eng._last_stream = None
+
+
+def test_one_handle_switched_between_streams(works, serial):
+    """a call on s1 followed, with no synchronisation, by a call on s2 with other parameters and the same batch (same scratch)"""
+    torch = _torch()
+    s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+    by = {w.name: w for w in works}
+    got = {}
+    for name in ("headline", "dlm", "rows_split", "rows"):
+        w = by[name]
+        with torch.cuda.stream(s1):
+            got[name, 0] = w.call(0)
+        with torch.cuda.stream(s2):
+            got[name, 1] = w.call(1)
+    _compare(got, serial)
+
+
+def test_vg_loss_under_two_streams():
+    """LossFunction.vg_loss (Engine.upload's staging, the packed buffer, the download) alternating between two streams"""
+    torch = _torch()
+    from tsadar_amd import ThomsonParams, tree
+    from tsadar_amd.loss_function import LossFunction
+
+    B = 4
+    cfg = decks.deck_fit()
+    sa = util.sa_fit(B)
+    batch = util.synthetic_batch(cfg, sa, B, seed=17)
+    loss_fn = LossFunction(cfg, sa, batch)
+    xs = []
+    for r in range(3):
+        tp = ThomsonParams(cfg["parameters"], B, batch=True, activate=True)
+        tp.X[:, util.slot_of("Te")] += 0.1 * (r + 1)
+        diff, static = tree.partition(tp, tree.get_filter_spec(cfg["parameters"], tp))
+        x0, loss_fn.unravel_weights = tree.ravel_pytree(diff)
+        xs.append((x0, static))
+    ref = [loss_fn.vg_loss(x, st, batch) for x, st in xs]
+    torch.cuda.synchronize()
+    s = [torch.cuda.Stream(), torch.cuda.Stream()]
+    for r, (x, st) in enumerate(xs + xs[::-1]):
+        with torch.cuda.stream(s[r % 2]):
+            v, g = loss_fn.vg_loss(x, st, batch)
+        k = r if r < 3 else 5 - r
+        assert v == ref[k][0] and np.array_equal(g, ref[k][1]), r
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# handles with different velocity grids in one process
+# ---------------------------------------------------------------------------------------------------------------------
+
+def _grid_engines():
+    """A (DLM, nvx 320, m trainable) and A2 (free-form f_e, nvx 320)"""
+    from tsadar_amd import _lib as L
+
+    sa = util.sa_fit(4)
+    return _engine(_deck({"m": True, "nvx": 320}), sa), _engine(_deck({"fe": True, "nvx": 320}), sa, fe_mode=L.FE_PER_LINEOUT)
+
+
+def _grid_calls(eng, eng2):
+    """A's loss + gradient; A2's form factor, chi table and loss + gradient with d loss / d fe -- as host arrays"""
+    torch = _torch()
+    out = {}
+    B = 4
+    cfg = eng.cfg
+    sa = util.sa_fit(B)
+    batch = util.synthetic_batch(cfg, sa, B, seed=23)
+    nm = util.random_lineouts(cfg, B, seed=24, ranges=dict(m=(2.1, 4.2)))
+    i_norm, e_norm = orc.loss_norms(cfg, batch)
+    w = eng.loss_weights(B, i_norm, e_norm)
+    t, g, E, I = eng.loss_grad(util.normed_to_matrix(nm, 1), batch, w, eng.slots.active.astype(np.uint8), want_spectra=True)
+    out.update(dlm_terms=t, dlm_grad=g, dlm_E=E, dlm_I=I)
+    cfg2 = eng2.cfg
+    fe = _free_form_fe(B, 320, 25)
+    phys = orc.physical_params(cfg2["parameters"], util.random_lineouts(cfg2, B, seed=26), True)
+    out["ff"] = eng2.form_factor(1, util.normed_to_matrix(phys, 1), fe)
+    out["chi"] = eng2.chi_table(fe)
+    t, g, E, I, gfe = eng2.loss_grad(util.normed_to_matrix(nm, 1), batch, w, eng2.slots.active.astype(np.uint8), fe=fe,
+                                     want_spectra=True, want_fe_grad=True)
+    out.update(fe_terms=t, fe_grad=g, fe_E=E, fe_I=I, gfe=gfe)
+    torch.cuda.synchronize()
+    return {k: v.cpu().numpy() for k, v in out.items()}
+
+
+def _grid_child(path):   # (run in a fresh process: no handle with another velocity grid is ever created there)
+    np.savez(path, **_grid_calls(*_grid_engines()))
+
+
+def test_handles_with_different_velocity_grids(tmp_path):
+    """A created, then handles with nvx 64 (they used to set the process-wide LDS attribute of k_fe_vectors, k_fe_prepare,
+    k_form_factor and k_fe_adjoint to their own, smaller sizes), then A's calls: equal to A's calls in a process where the small
+    handles never existed"""
+    torch = _torch()
+    from tsadar_amd import _lib as L
+
+    path = str(tmp_path / "alone.npz")
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([ROOT, os.path.join(ROOT, "tests")]))
+    subprocess.run([sys.executable, "-c", f"import test_concurrency as t; t._grid_child({path!r})"], cwd=ROOT, env=env,
+                   check=True, timeout=600)
+    alone = dict(np.load(path))
+    eng_a, eng_a2 = _grid_engines()
+    sa = util.sa_fit(4)
+    small = [_engine(_deck({"m": True, "nvx": 64}), sa), _engine(_deck({"fe": True, "nvx": 64}), sa, fe_mode=L.FE_PER_LINEOUT)]
+    torch.cuda.synchronize()
+    again = _grid_calls(eng_a, eng_a2)
+    assert len(small) == 2
+    assert sorted(again) == sorted(alone)
+    for k in alone:
+        if k == "gfe":
+            assert np.max(np.abs(again[k] - alone[k])) <= 1e-13 * np.max(np.abs(alone[k])), k
+        else:
+            assert np.array_equal(again[k], alone[k]), k
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# refused calls enqueue nothing
+# ---------------------------------------------------------------------------------------------------------------------
+
+def _raw(eng, fn, X, B, db, w, gm, amps=True, fe=None, out=None):
+    """a library entry point called directly (the Engine cannot pass a missing amplitude or spectrum buffer)"""
+    import ctypes as C
+    from tsadar_amd import _lib as L
+
+    p = eng._ptr
+    wa, ga = np.ascontiguousarray(w, dtype=np.float64), np.ascontiguousarray(gm, dtype=np.uint8)
+    ea, ia = (db["e_amps"], db["i_amps"]) if amps else (None, None)
+    eng._sync_stream()
+    if fn == "forward":
+        return eng.lib.tsff_forward(eng.h, p(X), p(fe), p(ea), p(ia), None, None, B, None, p(out))
+    return eng.lib.tsff_loss_grad(eng.h, p(X), p(fe), p(db["e_data"]), p(db["i_data"]), p(ea), p(ia), None, None, B,
+                                  wa.ctypes.data_as(L.c_double_p), ga.ctypes.data_as(L.c_uint8_p), p(out[0]), p(out[1]), None, None)
+
+
+@pytest.mark.parametrize("blocks", [0, 2])
+@pytest.mark.parametrize("kind", ["dlm", "per_lineout"])
+def test_refused_calls_enqueue_nothing(kind, blocks):
+    torch = _torch()
+    from tsadar_amd import _lib as L
+    from tsadar_amd._lib import TsffError
+
+    B = 1024
+    d = {"m": True} if kind == "dlm" else {"fe": True}
+    w = Work(kind, d, B, "lg")
+    eng = w.eng
+    eng.set_dlm_blocks(blocks)
+    X, db, gm, act = w.Xd[0], w.db, w.gm, list(w.act)
+    fe = w.extra[0].get("fe")
+    NP = eng.NP
+    a_slot = np.array(gm)
+    a_slot[L.P_ION0 + L.ION_A] = 1
+    with_m = np.array(gm)
+    with_m[L.P_M] = 1
+
+    def valid(e):
+        if kind == "dlm":
+            t, g, E, I = e.loss_grad(X, db, w.w, gm, want_spectra=True)
+            return _host(dict(terms=t, grad=g, E=E, I=I))
+        t, g, E, I, gfe = e.loss_grad(X, db, w.w, gm, fe=fe, want_spectra=True, want_fe_grad=True)
+        return _host(dict(terms=t, grad=g, E=E, I=I, gfe=gfe))
+
+    fresh = Work(kind, d, B, "lg").eng
+    fresh.set_dlm_blocks(blocks)
+    ref = valid(fresh)
+    torch.cuda.synchronize()
+    terms = torch.empty(3, dtype=torch.float64, device=eng.device)
+    grad = torch.empty((B, NP), dtype=torch.float64, device=eng.device)
+    E = torch.empty((B, 1024), dtype=torch.float64, device=eng.device)
+    lg = (lambda m: eng.loss_grad(X, db, w.w, m, want_spectra=True)) if kind == "dlm" else \
+        (lambda m: eng.loss_grad(X, db, w.w, m, fe=fe, want_spectra=True, want_fe_grad=True))
+    packed = lambda m, a, Bg=B: eng.loss_grad_packed(X, db, w.w, m, a, Bg, 0, out=torch.empty(3 + len(a) * Bg, dtype=torch.float64,
+                                                                                               device=eng.device))
+    refusals = [
+        ("packed: lineouts beyond B_global", lambda: packed(gm, act, B - 1)),
+        ("packed: slot out of range", lambda: packed(gm, act + [NP])),
+        ("A slot", lambda: lg(a_slot)),
+        ("packed: A slot", lambda: packed(a_slot, act)),
+        ("hess: repeated slot", lambda: eng.loss_hess(X, db, w.w, act + act[:1])),
+        ("hess: A slot", lambda: eng.loss_hess(X, db, w.w, act + [L.P_ION0 + L.ION_A])),
+        ("missing data", lambda: lg_missing()),
+        ("missing amplitudes", lambda: raw_check(_raw(eng, "lg", X, B, db, w.w, gm, amps=False, fe=fe, out=(terms, grad)))),
+        ("forward: ThryE missing", lambda: raw_check(_raw(eng, "forward", X, B, db, w.w, gm, fe=fe, out=E))),
+    ]
+    if kind == "per_lineout":
+        refusals += [("m without DLM", lambda: lg(with_m)),
+                     ("hess: m without DLM", lambda: eng.loss_hess(X, db, w.w, act + [L.P_M], fe=fe))]
+
+    def lg_missing():
+        nd = dict(db, e_data=None)
+        if kind == "dlm":
+            return eng.loss_grad(X, nd, w.w, gm)
+        return eng.loss_grad(X, nd, w.w, gm, fe=fe, want_fe_grad=True)
+
+    def raw_check(rc):
+        if rc != 0:
+            raise TsffError(f"libtsff error {rc}: {eng.lib.tsff_last_error(eng.h).decode()}")
+
+    for what, call in refusals:
+        with pytest.raises(TsffError):
+            call()
+        assert eng.last_launch() == [], (what, eng.last_launch())
+        got = valid(eng)
+        torch.cuda.synchronize()
+        _same(kind, got, ref, f"after '{what}'")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# graph capture
+# ---------------------------------------------------------------------------------------------------------------------
+
+CAPTURE = [("headline", {}, 512), ("rows_split", {"ppp": 5, "m": True, "nvx": 320}, 16), ("dlm", {"m": True}, 256)]
+
+
+@pytest.mark.parametrize("name,d,B", CAPTURE, ids=[c[0] for c in CAPTURE])
+def test_graph_capture(name, d, B):
+    """tsff.h's contract: reserve, one eager call with the mask and slots to be captured, synchronise, capture; every replay
+    equal to an eager call with the parameters copied into the static input.  Captured at the warm-up's batch and at a larger
+    one (tsff_reserve alone covers every allocation); a capture with another mask is refused with TsffError."""
+    torch = _torch()
+    from tsadar_amd._lib import TsffError
+
+    s = torch.cuda.Stream()
+
+    def packed(X, n, out, gm=None):
+        db = {k: (v[:n] if v is not None else None) for k, v in w.db.items()}   # (leading rows: contiguous views)
+        eng.loss_grad_packed(X[:n], db, w.w, w.gm if gm is None else gm, w.act, n, 0, out=out)
+        return out
+
+    def new_out(n):
+        return torch.empty(3 + len(w.act) * n, dtype=torch.float64, device=eng.device)
+
+    if name == "rows_split":
+        _assert_split_form(B)
+    for Bw in (B, B // 2):   # warm-up batch (a fresh handle each); the capture is at B
+        w = Work(name, d, B, "lg")
+        eng = w.eng
+        with torch.cuda.stream(s):
+            eng.reserve(B)
+            static = w.Xd[0][:B].clone()
+            out = new_out(B)
+            packed(static, Bw, new_out(Bw))
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=s):
+            packed(static, B, out)
+        captured = eng.last_launch()
+        for r in (1, 2, 0):
+            static.copy_(w.Xd[r][:B])
+            g.replay()
+            torch.cuda.synchronize()
+            got = out.cpu().numpy()
+            with torch.cuda.stream(s):
+                ref = packed(w.Xd[r], B, new_out(B))
+            torch.cuda.synchronize()
+            assert eng.last_launch() == captured, (captured, eng.last_launch())
+            assert np.array_equal(got, ref.cpu().numpy()), (name, Bw, r)
+        del g
+    other = np.array(w.gm)
+    other[np.nonzero(other)[0][0]] = 0
+    g3 = torch.cuda.CUDAGraph()
+    with pytest.raises(TsffError, match="graph capture"):
+        with torch.cuda.graph(g3, stream=s):
+            packed(static, B, out, gm=other)
+    assert eng.last_launch() == []

@@ -355,60 +355,75 @@ def _trained(eng, n_ion):
     return [k for k in names if eng.slots.active[util.slot_of(k)]]
 
 
-def _spectrum_case(eng, cfg, sa, d, B, entry, kernels, n_ion):
-    from oracle import c_oracle as co
-    from oracle import tsadar_oracle_torch as ot
-
+def _spectrum_inputs(eng, cfg, sa, d, B, n_ion, round_=0):
+    """the batch, normalised leaves (round_ > 0: another seeded draw), parameter matrix and free-form f_e of a spectrum case"""
     batch = util.synthetic_batch(cfg, sa, B, seed=3 + B) if B <= 8 else _cheap_batch(B)
-    normed = util.random_lineouts(cfg, B, seed=11 + n_ion, ranges=dict(m=(2.1, 4.2)) if d.get("m") else None)
+    normed = util.random_lineouts(cfg, B, seed=11 + n_ion + 100 * round_, ranges=dict(m=(2.1, 4.2)) if d.get("m") else None)
     X = util.normed_to_matrix(normed, n_ion)
-    fe = _free_form_fe(B, eng.nvx, 5) if d.get("fe") else None
-    rows = np.arange(B) if B <= 8 else np.array([0, B // 2, B - 1])   # lineouts compared with the oracle
-    nb, sb = _sub(normed, rows), _sub(batch, rows)
-    sar = dict(sa=sa["sa"], weights=sa["weights"][rows])
-    tolE, tolI = 1e-8, 1e-7
-    if n_ion >= 3:
-        _sensitivity_guard(cfg, sar, nb, sb, tolI)
+    fe = _free_form_fe(B, eng.nvx, 5 + round_) if d.get("fe") else None
+    return batch, normed, X, fe
+
+
+def _spectrum_case(eng, cfg, sa, d, B, entry, kernels, n_ion):
+    batch, normed, X, fe = _spectrum_inputs(eng, cfg, sa, d, B, n_ion)
+    i_norm, e_norm = orc.loss_norms(cfg, batch)
+    w = eng.loss_weights(B, i_norm, e_norm, cfg["data"]["ion_loss_scale"])
+    gm = eng.slots.active.astype(np.uint8)
     if entry in ("fwd", "al"):
         if entry == "fwd":
             E, I = eng.forward(X, batch["e_amps"], batch["i_amps"], batch["noise_e"], batch["noise_i"], fe=fe)
         else:
             _, _, _, E, I = eng.array_loss(X, batch, fe=fe)
-        _sync()
-        _assert_launched(eng, kernels)
+        out = dict(E=E, I=I)
+    elif entry == "lgfe":
+        terms, grad, E, I, gfe = eng.loss_grad(X, batch, w, gm, fe=fe, want_spectra=True, want_fe_grad=True)
+        out = dict(terms=terms, grad=grad, E=E, I=I, gfe=gfe)
+    else:
+        terms, grad, E, I = eng.loss_grad(X, batch, w, gm, want_spectra=True)
+        out = dict(terms=terms, grad=grad, E=E, I=I)
+    _sync()
+    _assert_launched(eng, kernels)
+    _spectrum_check(cfg, sa, d, B, entry, n_ion, eng, batch, normed, X, fe, w, gm, {k: v.cpu().numpy() for k, v in out.items()})
+
+
+def _spectrum_check(cfg, sa, d, B, entry, n_ion, eng, batch, normed, X, fe, w, gm, out):
+    """the outputs of a spectrum case (host arrays E, I and, for the loss entries, terms, grad, gfe) against the oracles"""
+    from oracle import c_oracle as co
+    from oracle import tsadar_oracle_torch as ot
+
+    rows = np.arange(B) if B <= 8 else np.array([0, B // 2, B - 1])   # lineouts compared with the oracle
+    nb, sb = _sub(normed, rows), _sub(batch, rows)
+    sar = dict(sa=sa["sa"], weights=sa["weights"][rows])
+    tolE, tolI = 1e-8, 1e-7
+    E, I = out["E"], out["I"]
+    if n_ion >= 3:
+        _sensitivity_guard(cfg, sar, nb, sb, tolI)
+    if entry in ("fwd", "al"):
         Eo, Io, _, _ = orc.ts_diag(cfg, sar, nb, sb, fe_batch=None if fe is None else fe[rows])
-        assert util.rel_err(E.cpu().numpy()[rows], Eo) < tolE
-        assert util.rel_err(I.cpu().numpy()[rows], Io) < tolI
+        assert util.rel_err(E[rows], Eo) < tolE
+        assert util.rel_err(I[rows], Io) < tolI
         return
     i_norm, e_norm = orc.loss_norms(cfg, batch)
-    w = eng.loss_weights(B, i_norm, e_norm, cfg["data"]["ion_loss_scale"])
-    gm = eng.slots.active.astype(np.uint8)
+    terms, g = out["terms"], out["grad"]
     if entry == "lgfe":
-        terms, grad, E, I, gfe = eng.loss_grad(X, batch, w, gm, fe=fe, want_spectra=True, want_fe_grad=True)
-        _sync()
-        _assert_launched(eng, kernels)
         names = _trained(eng, n_ion)
-        assert np.all(grad.cpu().numpy()[:, gm == 0] == 0.0)
+        assert np.all(g[:, gm == 0] == 0.0)
         val, ref, ref_fe, Eo, Io = ot.value_and_grad_fe(cfg, sa, normed, batch, i_norm, e_norm, names, fe)
-        assert util.rel_err(E.cpu().numpy(), Eo) < tolE and util.rel_err(I.cpu().numpy(), Io) < tolI
-        assert abs(float(np.dot(terms.cpu().numpy(), w)) - val) < 1e-9 * abs(val)
-        G = util.matrix_to_named(grad.cpu().numpy(), names)
+        assert util.rel_err(E, Eo) < tolE and util.rel_err(I, Io) < tolI
+        assert abs(float(np.dot(terms, w)) - val) < 1e-9 * abs(val)
+        G = util.matrix_to_named(g, names)
         scale = max(np.max(np.abs(v)) for v in ref.values())
         for k in names:
             assert np.max(np.abs(G[k] - ref[k])) / scale < 1e-7, k
-        a, r = gfe.cpu().numpy() * fe, ref_fe * fe   # as d loss / d ln fe: the tails of fe span 20 decades
+        a, r = out["gfe"] * fe, ref_fe * fe   # as d loss / d ln fe: the tails of fe span 20 decades
         assert np.max(np.abs(a - r)) / np.max(np.abs(r)) < 1e-7
         return
-    terms, grad, E, I = eng.loss_grad(X, batch, w, gm, want_spectra=True)
-    _sync()
-    _assert_launched(eng, kernels)
-    g = grad.cpu().numpy()
     assert np.all(g[:, gm == 0] == 0.0)
     if d.get("m"):   # the DLM order is differentiated: the autodiff twin
         names = _trained(eng, n_ion)
         val, ref, Eo, Io = ot.value_and_grad(cfg, sa, normed, batch, i_norm, e_norm, names)
-        assert util.rel_err(E.cpu().numpy(), Eo) < tolE and util.rel_err(I.cpu().numpy(), Io) < tolI
-        assert abs(float(np.dot(terms.cpu().numpy(), w)) - val) < 1e-9 * abs(val)
+        assert util.rel_err(E, Eo) < tolE and util.rel_err(I, Io) < tolI
+        assert abs(float(np.dot(terms, w)) - val) < 1e-9 * abs(val)
         G = util.matrix_to_named(g, names)
         scale = max(np.max(np.abs(v)) for v in ref.values())
         for k in names:
@@ -416,9 +431,9 @@ def _spectrum_case(eng, cfg, sa, d, B, entry, kernels, n_ion):
         return
     # plasma parameters: the C++ dual-number oracle, every compared lineout, per column
     sums, gref, Eo, Io = co.loss_grad(cfg, sar, X[rows], sb, w=w, gmask=gm)
-    assert util.rel_err(E.cpu().numpy()[rows], Eo) < tolE and util.rel_err(I.cpu().numpy()[rows], Io) < tolI
+    assert util.rel_err(E[rows], Eo) < tolE and util.rel_err(I[rows], Io) < tolI
     if len(rows) == B:
-        np.testing.assert_allclose(terms.cpu().numpy(), sums.sum(axis=0), rtol=1e-9)
+        np.testing.assert_allclose(terms, sums.sum(axis=0), rtol=1e-9)
     for s in np.nonzero(gm)[0]:
         assert np.max(np.abs(g[rows, s] - gref[:, s])) <= 1e-6 * np.max(np.abs(gref[:, s])), s
 
@@ -527,15 +542,11 @@ def _ff2d_case(eng, cfg, sa, B, entry, kernels, n_ion):
     vx, fe2 = _fe2d(nv)
     ud_ang, va_ang = 25.0, -40.0
     if not entry.startswith("ff2d_adj"):
-        idx = np.array([0, 333, 700, 1023])
-        for feature, rng in ((0, cfg["other"]["lamrangE"]), (1, cfg["other"]["lamrangI"])):
+        for feature in (0, 1):
             P = eng.form_factor_2d(feature, X, fe2, ud_ang, va_ang, save=entry.startswith("ff2d_save")).cpu().numpy()
             _sync()
             _assert_launched(eng, kernels)
-            for b in range(B):
-                p = orc.lineout_params(phys, b, n_ion)
-                Po, _ = orc.form_factor_2d(rng, cfg["other"]["npts"], 0.0, sa["sa"], 1, p, vx, fe2, ud_ang, va_ang, lam_index=idx)
-                assert np.max(np.abs(P[b][:, idx, :] - Po) / np.abs(Po)) < 1e-7, (feature, b)
+            _ff2d_check_forward(cfg, sa, B, n_ion, phys, feature, nv, ud_ang, va_ang, P)
         return
     # the adjoint: directional derivatives of <Pbar, P> by central differences of the HIP 2-D forward
     feature = 1
@@ -545,8 +556,26 @@ def _ff2d_case(eng, cfg, sa, B, entry, kernels, n_ion):
     gp, gf = eng.form_factor_2d_grad(feature, X, fe2, Pbar, ud_ang, va_ang, want_table=True)
     _sync()
     _assert_launched(eng, kernels)
-    gp = gp.cpu().numpy()
+    _ff2d_check_adjoint(eng, X, fe2, Pbar, feature, ud_ang, va_ang, n_ion, gp.cpu().numpy(), gf.cpu().numpy())
+
+
+def _ff2d_check_forward(cfg, sa, B, n_ion, phys, feature, nv, ud_ang, va_ang, P):
+    """P [B, G, npts, n_angles] of tsff_form_factor_2d (host) against the oracle at four wavelengths"""
+    rng = (cfg["other"]["lamrangE"], cfg["other"]["lamrangI"])[feature]
+    vx, fe2 = _fe2d(nv)
+    idx = np.array([0, 333, 700, 1023])
+    for b in range(B):
+        p = orc.lineout_params(phys, b, n_ion)
+        Po, _ = orc.form_factor_2d(rng, cfg["other"]["npts"], 0.0, sa["sa"], 1, p, vx, fe2, ud_ang, va_ang, lam_index=idx)
+        assert np.max(np.abs(P[b][:, idx, :] - Po) / np.abs(Po)) < 1e-7, (feature, b)
+
+
+def _ff2d_check_adjoint(eng, X, fe2, Pbar, feature, ud_ang, va_ang, n_ion, gp, gf):
+    """grad_phys / grad_fe2d (host) of tsff_form_factor_2d_grad for the seed Pbar: directional derivatives of <Pbar, P> by central
+    differences of the HIP 2-D forward"""
+    nv = fe2.shape[0]
     J = lambda Xv, f: float((eng.form_factor_2d(feature, Xv, f, ud_ang, va_ang) * Pbar).sum())
+    P0 = eng.form_factor_2d(feature, X, fe2, ud_ang, va_ang)
     jabs = float((P0 * Pbar).abs().sum())
     for name in _fd_names(n_ion):
         s = util.slot_of(name)
@@ -559,7 +588,7 @@ def _ff2d_case(eng, cfg, sa, B, entry, kernels, n_ion):
         err = _best_fd(J, gp[:, s].sum(), shifted, [r * scale for r in (1e-4, 1e-5, 1e-6, 1e-7)], jabs)
         assert err < 1e-4, (name, err)
     dfe = fe2 * np.cos(np.arange(nv))[None]
-    an = float(np.sum(gf.cpu().numpy() * dfe))
+    an = float(np.sum(gf * dfe))
     assert _best_fd(J, an, lambda h: (X, fe2 + h * dfe), (1e-4, 1e-5, 1e-6), jabs) < 1e-4
 
 

@@ -36,6 +36,10 @@ struct tsff_handle {
   int n_ion = 1;
   int fe_mode = 0;
   hipStream_t stream = nullptr;
+  // tsff_set_stream: ev_switch orders the next stream behind the work earlier calls left on the previous one; `enqueued`: a call
+  // has run since the last switch; `capturing`: the current call's stream is being captured into a graph (set by DevGuard)
+  hipEvent_t ev_switch = nullptr;
+  bool enqueued = false, capturing = false;
   std::string err;
   std::string launched;   // tsff_last_launch: the kernels the current entry point enqueued, ';'-separated
   // static device arrays
@@ -125,15 +129,28 @@ static int fail(tsff_handle* h, int code, const char* fmt, ...) {
 // tsff_create) and restores the caller's device on return
 // (and starts the launch record of tsff_last_launch: the string keeps its capacity, so recording allocates nothing once a call's
 // names have fitted)
+// An entry point's guard also notes whether its stream is being captured into a graph, and on the way out joins the DLM tables
+// still in flight on the second stream (join_pipe), whichever return path the call took -- nothing is left unordered behind the
+// handle's stream.  call = false (tsff_set_stream, tsff_destroy): the device only.
+static int join_pipe(tsff_handle* h);
 struct DevGuard {
   int prev = -1;
-  explicit DevGuard(tsff_handle* h) {
+  tsff_handle* call = nullptr;
+  explicit DevGuard(tsff_handle* h, bool is_call = true) {
     if (!h) return;
-    h->launched.clear();
     int cur = -1;
     if (hipGetDevice(&cur) == hipSuccess && cur != h->device && hipSetDevice(h->device) == hipSuccess) prev = cur;
+    if (!is_call) return;
+    call = h;
+    h->launched.clear();
+    h->enqueued = true;
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    h->capturing = hipStreamIsCapturing(h->stream, &st) == hipSuccess && st != hipStreamCaptureStatusNone;
   }
-  ~DevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+  ~DevGuard() {
+    if (call) (void)join_pipe(call);
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
   DevGuard(const DevGuard&) = delete;
   DevGuard& operator=(const DevGuard&) = delete;
 };
@@ -177,10 +194,25 @@ static void note_launch(tsff_handle* h, const char* kernel, A... targs) {
     if (e__ != hipSuccess) return fail((h), -5, "%s failed: %s", #call, hipGetErrorString(e__)); \
   } while (0)
 
+// a per-handle device buffer that must hold N bytes: grown (hipFree + hipMalloc) only outside graph capture -- a call on a
+// capturing stream that would have to grow one is refused with -2 before it enqueues anything (see tsff_reserve)
+#define TSFF_ENSURE(h, BUF, N)                                                                                            \
+  do {                                                                                                                    \
+    const size_t n__ = (N);                                                                                               \
+    if (n__ > (BUF).bytes) {                                                                                              \
+      if ((h)->capturing) return fail((h), -2, "graph capture: %s needs %zu bytes (tsff_reserve the batch first)", #BUF, n__); \
+      TSFF_HIP(h, (BUF).ensure(n__));                                                                                     \
+    }                                                                                                                     \
+  } while (0)
+
 // kernels with more dynamic LDS than the default limit: the attribute is raised on exactly the instantiation that is launched
-// (TSFF_LAUNCH_LDS(h, k_name, (template arguments), attribute bytes, grid, block, smem, stream, kernel arguments...))
-#define TSFF_LDS_ATTR(h, KFN, BYTES) \
-  TSFF_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(KFN), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(BYTES)))
+// (TSFF_LAUNCH_LDS(h, k_name, (template arguments), attribute bytes, grid, block, smem, stream, kernel arguments...)); inside
+// graph capture it is left as the eager call the capture contract requires set it
+#define TSFF_LDS_ATTR(h, KFN, BYTES)                                                                                                \
+  do {                                                                                                                              \
+    if (!(h)->capturing)                                                                                                            \
+      TSFF_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(KFN), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(BYTES))); \
+  } while (0)
 #define TSFF_LAUNCH_LDS(h, K, TARGS, BYTES, ...)      \
   do {                                                \
     TSFF_LDS_ATTR(h, (K<TSFF_UNPAREN TARGS>), BYTES); \
@@ -221,8 +253,10 @@ static int timing_end(tsff_handle* h) {
 // the active slots of the packed outputs on the device; re-sent only when the list changes
 static int upload_slots(tsff_handle* h, const int32_t* act, int n) {
   if (h->act_host.size() == (size_t)n && std::memcmp(h->act_host.data(), act, n * sizeof(int32_t)) == 0) return 0;
+  if (h->capturing)
+    return fail(h, -2, "graph capture: the active slot list differs from the last eager call's (a change is uploaded synchronously)");
   h->act_host.assign(act, act + n);
-  TSFF_HIP(h, h->act.ensure(kNP_MAX * sizeof(int32_t)));
+  TSFF_ENSURE(h, h->act, kNP_MAX * sizeof(int32_t));
   // (pageable source that the next call may reassign: a synchronous copy of <= NP indices, once per change of the slot list)
   TSFF_HIP(h, hipStreamSynchronize(h->stream));
   TSFF_HIP(h, hipMemcpy(h->act.p, h->act_host.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -239,7 +273,7 @@ static hipError_t upload(DevBuf& b, const T* src, size_t n) {
 
 
 template <int NI>
-static hipError_t set_smem_attrs(size_t spec, size_t prep, size_t vec, size_t adj) {
+static hipError_t set_smem_attrs() {
   hipError_t e;
 #define TSFF_ATTR(k, n)                                                                                      \
   e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(n)); \
@@ -290,10 +324,12 @@ static hipError_t set_smem_attrs(size_t spec, size_t prep, size_t vec, size_t ad
     TSFF_ATTR((k_spectrum_rows<NI, 0, true, true, true>), kLdsLimit)
     TSFF_ATTR((k_spectrum_rows<NI, 0, false, true, true>), kLdsLimit)
   }
-  TSFF_ATTR((k_form_factor<NI>), spec)
-  TSFF_ATTR((k_fe_prepare<NI>), prep)
-  TSFF_ATTR((k_fe_vectors<NI>), vec)
-  TSFF_ATTR(k_fe_adjoint, adj)
+  // (the attribute is process-wide, not per handle: the families sized by the velocity grid get the CU's whole LDS too, so that
+  // creating a handle with a smaller grid never lowers the limit another handle's launches rely on)
+  TSFF_ATTR((k_form_factor<NI>), kLdsLimit)
+  TSFF_ATTR((k_fe_prepare<NI>), kLdsLimit)
+  TSFF_ATTR((k_fe_vectors<NI>), kLdsLimit)
+  TSFF_ATTR(k_fe_adjoint, kLdsLimit)
 #undef TSFF_ATTR
   return hipSuccess;
 }
@@ -305,22 +341,38 @@ static int ensure_workspace(tsff_handle* h, int B, bool with_rows = false) {
     // the row scratch of k_spectrum_rows (points_per_pixel > 1; the widest layout: DLM tangent component included), so that a
     // handle reserved through tsff_reserve allocates nothing in tsff_loss_grad (graph capture)
     const size_t need = (size_t)B * ((h->S.load[0] ? 1 : 0) + (h->S.load[1] ? 1 : 0)) * (9 + 3 * (size_t)h->n_ion) * h->S.npts * sizeof(double);
-    if (need <= kRowsScratchMax) TSFF_HIP(h, h->rows.ensure(need));
+    if (need <= kRowsScratchMax) TSFF_ENSURE(h, h->rows, need);
   }
   if (B <= h->reserved_B) return 0;
+  if (h->capturing) return fail(h, -2, "graph capture: the workspace holds %d lineouts, the call has %d (tsff_reserve the batch first)", h->reserved_B, B);
   const int slots = h->fe_mode == TSFF_FE_SHARED ? 1 : B;
-  TSFF_HIP(h, h->lpart.ensure((size_t)B * 3 * sizeof(double)));
+  TSFF_ENSURE(h, h->lpart, (size_t)B * 3 * sizeof(double));
   // the kernels overwrite the slots of the loaded features; the slots of a feature that is not loaded stay zero
   TSFF_HIP(h, hipMemsetAsync(h->lpart.p, 0, (size_t)B * 3 * sizeof(double), h->stream));
+  // the records of the one-sweep and pair-sweep kernels, the per-feature gradient parts of the interleaved plans, the packed
+  // call's gradient workspace and slot list, and the arrival counters of the rows kernel's split form (zeroed once: the last
+  // arrival resets its counter) at their largest over the plans plan_spectrum can pick for B lineouts -- so that a call on a
+  // reserved handle allocates nothing (graph capture)
+  const size_t nitems = (size_t)B * ((h->S.load[0] ? 1 : 0) + (h->S.load[1] ? 1 : 0));
+  TSFF_ENSURE(h, h->lbrec, nitems * (kHalf / 64) * kLBRec * sizeof(double));
+  TSFF_ENSURE(h, h->lrec, nitems * kLineRec * sizeof(double));
+  TSFF_ENSURE(h, h->finrec, nitems * (2 * (size_t)h->S.NP + 1 + 9 + 4 * (size_t)h->n_ion) * sizeof(double));
+  TSFF_ENSURE(h, h->gpart, (size_t)2 * B * h->S.NP * sizeof(double));
+  TSFF_ENSURE(h, h->gradws, (size_t)B * h->S.NP * sizeof(double));
+  TSFF_ENSURE(h, h->act, kNP_MAX * sizeof(int32_t));
+  if (h->tickets.bytes < 1024 * sizeof(unsigned)) {
+    TSFF_ENSURE(h, h->tickets, 1024 * sizeof(unsigned));
+    TSFF_HIP(h, hipMemsetAsync(h->tickets.p, 0, h->tickets.bytes, h->stream));
+  }
   if (h->fe_mode != TSFF_FE_SHARED) {
     // growing the table buffers would drop the shared slot; non-shared modes rebuild them per call
-    TSFF_HIP(h, h->ht.ensure((size_t)slots * h->S.nvx * sizeof(double2)));
-    TSFF_HIP(h, h->W.ensure((size_t)slots * kNXi2 * sizeof(double)));
-    TSFF_HIP(h, h->fe_tmp.ensure((size_t)slots * h->S.nvx * sizeof(double)));
-    TSFF_HIP(h, h->htm.ensure((size_t)slots * h->S.nvx * sizeof(double2)));
-    TSFF_HIP(h, h->Wm.ensure((size_t)slots * kNXi2 * sizeof(double)));
-    TSFF_HIP(h, h->X.ensure((size_t)slots * 4 * kNXi1 * sizeof(double)));
-    TSFF_HIP(h, h->cst.ensure((size_t)slots * 2 * sizeof(double)));
+    TSFF_ENSURE(h, h->ht, (size_t)slots * h->S.nvx * sizeof(double2));
+    TSFF_ENSURE(h, h->W, (size_t)slots * kNXi2 * sizeof(double));
+    TSFF_ENSURE(h, h->fe_tmp, (size_t)slots * h->S.nvx * sizeof(double));
+    TSFF_ENSURE(h, h->htm, (size_t)slots * h->S.nvx * sizeof(double2));
+    TSFF_ENSURE(h, h->Wm, (size_t)slots * kNXi2 * sizeof(double));
+    TSFF_ENSURE(h, h->X, (size_t)slots * 4 * kNXi1 * sizeof(double));
+    TSFF_ENSURE(h, h->cst, (size_t)slots * 2 * sizeof(double));
   }
   h->reserved_B = B;
   return 0;
@@ -590,6 +642,21 @@ static void launch_fused(tsff_handle* h, const KCall& K, const SpectrumPlan& p, 
   h->pipe_nblk = 0;
 }
 
+// the scratch buffers of the plan launch_spectrum<MODE, GM> will pick for B lineouts, sized (and its LDS budget checked) before a
+// call enqueues anything, so that a refusal leaves nothing behind
+template <int MODE, int GM>
+static int size_plan(tsff_handle* h, int B) {
+  const int nload = (h->S.load[0] ? 1 : 0) + (h->S.load[1] ? 1 : 0);
+  const SpectrumPlan p = plan_spectrum<MODE, GM>(*h, B, nload);
+  if (p.smem > kLdsLimit) return fail(h, TSFF_ERR_LDS, "LDS budget exceeded (%zu B): reduce npts or the IRF cutoff", p.smem);
+  if (p.rows) TSFF_ENSURE(h, h->rows, p.rows);
+  if (p.gpart) TSFF_ENSURE(h, h->gpart, p.gpart);
+  if (p.lbrec) TSFF_ENSURE(h, h->lbrec, p.lbrec);
+  if (p.lrec) TSFF_ENSURE(h, h->lrec, p.lrec);
+  if (p.finrec) TSFF_ENSURE(h, h->finrec, p.finrec);
+  return 0;
+}
+
 // plan_spectrum, then the buffers of the plan, the timing ring and the launches
 template <int MODE, int GM = 0>
 static int launch_spectrum(tsff_handle* h, KCall& K, const uint8_t* gmask = nullptr, double* grad = nullptr,
@@ -601,19 +668,19 @@ static int launch_spectrum(tsff_handle* h, KCall& K, const uint8_t* gmask = null
   // only the loss + gradient builds its tables on the second stream)
   if (p.form != SpectrumForm::one_sweep)
     if (int rc = join_pipe(h)) return rc;
-  if (p.rows) TSFF_HIP(h, h->rows.ensure(p.rows));
+  if (p.rows) TSFF_ENSURE(h, h->rows, p.rows);
   if (p.tickets && h->tickets.bytes < p.tickets) {
-    TSFF_HIP(h, h->tickets.ensure(std::max<size_t>(p.tickets, 1024 * sizeof(unsigned))));
+    TSFF_ENSURE(h, h->tickets, std::max<size_t>(p.tickets, 1024 * sizeof(unsigned)));
     TSFF_HIP(h, hipMemsetAsync(h->tickets.p, 0, h->tickets.bytes, h->stream));
   }
   if (p.gpart) {
-    TSFF_HIP(h, h->gpart.ensure(p.gpart));
+    TSFF_ENSURE(h, h->gpart, p.gpart);
     K.gpart = h->gpart.as<double>();
     if (used_gpart) *used_gpart = true;
   }
-  if (p.lbrec) TSFF_HIP(h, h->lbrec.ensure(p.lbrec));
-  if (p.lrec) TSFF_HIP(h, h->lrec.ensure(p.lrec));
-  if (p.finrec) TSFF_HIP(h, h->finrec.ensure(p.finrec));
+  if (p.lbrec) TSFF_ENSURE(h, h->lbrec, p.lbrec);
+  if (p.lrec) TSFF_ENSURE(h, h->lrec, p.lrec);
+  if (p.finrec) TSFF_ENSURE(h, h->finrec, p.finrec);
   if (p.form == SpectrumForm::one_sweep) {
     K.lbrec = h->lbrec.as<double>();
     if (used_lbrec) *used_lbrec = true;
@@ -897,7 +964,7 @@ int tsff_create(const tsff_config* c, tsff_handle** out) {
   h->smem_vectors = sizeof(double2) * 6 * (size_t)S.nvx + sizeof(double) * (2 * (size_t)S.nvx + 4 * kNXi1 + 8);
   h->smem_adjoint = sizeof(double2) * 3 * (size_t)S.nvx + sizeof(double) * (2 * (size_t)S.nvx + 4 * kNXi1 + 8);
   TSFF_HIPC(with_ion<TSFF_MAX_ION>(c->n_ion, [&](auto N) {
-    return set_smem_attrs<N.value>(h->smem_spectrum, h->smem_prepare, h->smem_vectors, h->smem_adjoint);
+    return set_smem_attrs<N.value>();
   }));
   // shared distribution function: build its tables once
   TSFF_HIPC(h->ht.ensure((size_t)S.nvx * sizeof(double2)));
@@ -909,6 +976,8 @@ int tsff_create(const tsff_config* c, tsff_handle** out) {
     if (rc) return bail(rc);
     TSFF_HIPC(hipStreamSynchronize(h->stream));
   }
+  // (tsff_set_stream; it only orders streams of this device: a device-scope release, no system-wide cache write-back per call)
+  TSFF_HIPC(hipEventCreateWithFlags(&h->ev_switch, hipEventDisableTiming | hipEventReleaseToDevice));
 #undef TSFF_HIPC
   *out = h;
   return 0;
@@ -916,7 +985,8 @@ int tsff_create(const tsff_config* c, tsff_handle** out) {
 
 void tsff_destroy(tsff_handle* h) {
   if (!h) return;
-  DevGuard dg__(h);
+  DevGuard dg__(h, false);
+  if (h->ev_switch) (void)hipEventDestroy(h->ev_switch);
   for (auto e : h->ev0) (void)hipEventDestroy(e);
   for (auto e : h->ev1) (void)hipEventDestroy(e);
   for (auto e : h->blk_ev) (void)hipEventDestroy(e);
@@ -927,7 +997,25 @@ void tsff_destroy(tsff_handle* h) {
 
 int tsff_set_stream(tsff_handle* h, void* s) {
   if (!h) return -1;
-  h->stream = reinterpret_cast<hipStream_t>(s);
+  const hipStream_t ns = reinterpret_cast<hipStream_t>(s);
+  if (ns == h->stream) return 0;
+  // the handle's scratch (tables, records, row scratch, partial sums) is shared by its calls: work a call left on the old stream
+  // must finish before the new stream's first call rewrites it -- the new stream waits on an event recorded on the old one, once
+  // per switch (recording one at the end of every call instead, which would let the old stream die first, costs the one-stream
+  // hot path 0.6 %).  So the old stream must still exist (tsff.h); a stream that is capturing a graph does not take part (ordering
+  // is then the caller's)
+  if (h->enqueued) {
+    DevGuard dg__(h, false);
+    hipStreamCaptureStatus a = hipStreamCaptureStatusNone, b = hipStreamCaptureStatusNone;
+    TSFF_HIP(h, hipStreamIsCapturing(h->stream, &a));
+    TSFF_HIP(h, hipStreamIsCapturing(ns, &b));
+    if (a == hipStreamCaptureStatusNone && b == hipStreamCaptureStatusNone) {
+      TSFF_HIP(h, hipEventRecord(h->ev_switch, h->stream));
+      TSFF_HIP(h, hipStreamWaitEvent(ns, h->ev_switch, 0));
+    }
+    h->enqueued = false;
+  }
+  h->stream = ns;
   return 0;
 }
 
@@ -1067,11 +1155,12 @@ int tsff_chi_table(tsff_handle* h, const double* fe, int32_t n, double* W) {
 int tsff_form_factor(tsff_handle* h, int32_t feature, const double* phys, const double* fe, int32_t B, double* P) {
   DevGuard dg__(h);
   if (!h || !phys || !P || B < 1 || feature < 0 || feature > 1) return fail(h, -1, "bad argument");
+  if (h->fe_mode == TSFF_FE_DLM) return fail(h, -3, "tsff_form_factor takes explicit distribution functions (fe_mode SHARED or PER_LINEOUT)");
+  if (h->fe_mode == TSFF_FE_PER_LINEOUT && !fe) return fail(h, -2, "fe_mode PER_LINEOUT needs fe[B][nvx]");
   int rc = ensure_workspace(h, B);
   if (rc) return rc;
   KCall K{};
   K.params = phys; K.B = B;
-  if (h->fe_mode == TSFF_FE_DLM) return fail(h, -3, "tsff_form_factor takes explicit distribution functions (fe_mode SHARED or PER_LINEOUT)");
   rc = prepare_tables(h, phys, fe, B, K);
   if (rc) return rc;
   dim3 grid(B, angle_chunks(h, B)), block(kThreads);
@@ -1087,30 +1176,33 @@ int tsff_form_factor_grad(tsff_handle* h, int32_t feature, const double* phys, c
                           double* grad_phys, double* grad_fe) {
   DevGuard dg__(h);
   if (!h || !phys || !Pbar || !grad_phys || B < 1 || feature < 0 || feature > 1) return fail(h, -1, "bad argument");
+  if (h->fe_mode == TSFF_FE_DLM) return fail(h, -3, "tsff_form_factor_grad takes explicit distribution functions (fe_mode SHARED or PER_LINEOUT)");
+  if (grad_fe && h->fe_mode != TSFF_FE_PER_LINEOUT) return fail(h, -2, "gradient w.r.t. f_e needs fe_mode == TSFF_FE_PER_LINEOUT");
+  if (h->fe_mode == TSFF_FE_PER_LINEOUT && !fe) return fail(h, -2, "fe_mode PER_LINEOUT needs fe[B][nvx]");
+  const size_t smem = sizeof(double) * smem_doubles(h->S, 1, grad_fe ? 2 : 0, false);
+  if (smem > kLdsLimit) return fail(h, TSFF_ERR_LDS, "LDS budget exceeded (%zu B)", smem);
   int rc = ensure_workspace(h, B);
   if (rc) return rc;
   KCall K{};
   K.params = phys; K.B = B;
-  if (h->fe_mode == TSFF_FE_DLM) return fail(h, -3, "tsff_form_factor_grad takes explicit distribution functions (fe_mode SHARED or PER_LINEOUT)");
-  if (grad_fe && h->fe_mode != TSFF_FE_PER_LINEOUT) return fail(h, -2, "gradient w.r.t. f_e needs fe_mode == TSFF_FE_PER_LINEOUT");
-  rc = prepare_tables(h, phys, fe, B, K);
-  if (rc) return rc;
   const int NLB = 9 + 3 * h->n_ion, nvx = h->S.nvx;
   const unsigned nchunk = angle_chunks(h, B);
   const int nworker = (int)nchunk * (kThreads / 64);   // one partial per wavefront and angle chunk (every slot is written)
-  TSFF_HIP(h, h->lbacc.ensure((size_t)B * h->S.G * NLB * sizeof(double)));
-  TSFF_HIP(h, h->lbparts.ensure((size_t)B * h->S.G * nworker * NLB * sizeof(double)));
+  TSFF_ENSURE(h, h->lbacc, (size_t)B * h->S.G * NLB * sizeof(double));
+  TSFF_ENSURE(h, h->lbparts, (size_t)B * h->S.G * nworker * NLB * sizeof(double));
   if (grad_fe) {   // per-chunk blocks [chunk][B][.], summed in order by k_sum_chunks
-    TSFF_HIP(h, h->Wb.ensure((size_t)nchunk * B * kNXi2 * sizeof(double)));
-    TSFF_HIP(h, h->Hys.ensure((size_t)nchunk * B * 2 * nvx * sizeof(double)));
-    TSFF_HIP(h, h->Yt.ensure((size_t)B * 2 * kNXi1 * sizeof(double)));
+    TSFF_ENSURE(h, h->Wb, (size_t)nchunk * B * kNXi2 * sizeof(double));
+    TSFF_ENSURE(h, h->Hys, (size_t)nchunk * B * 2 * nvx * sizeof(double));
+    TSFF_ENSURE(h, h->Yt, (size_t)B * 2 * kNXi1 * sizeof(double));
+  }
+  rc = prepare_tables(h, phys, fe, B, K);
+  if (rc) return rc;
+  if (grad_fe) {
     K.Wb_out = h->Wb.as<double>();
     K.Hy_out = h->Hys.as<double>();
     K.Hs_out = K.Hy_out + (size_t)B * nvx;
     K.htm = nullptr; K.Wm = nullptr;
   }
-  const size_t smem = sizeof(double) * smem_doubles(h->S, 1, grad_fe ? 2 : 0, false);
-  if (smem > kLdsLimit) return fail(h, TSFF_ERR_LDS, "LDS budget exceeded (%zu B)", smem);
   dim3 grid(B, nchunk), block(kThreads);
   rc = with_ion<TSFF_MAX_ION>(h->n_ion, [&](auto N) {
     return with_bool(grad_fe != nullptr, [&](auto FE) {
@@ -1208,7 +1300,7 @@ static int form_factor_2d_impl(tsff_handle* h, int32_t feature, const double* ph
   if (!lds) {  // tables that do not fit LDS are read through L1/L2 from a padded copy (ghost cells by k_pad2d)
     const int ntab = shared_fe ? 1 : B;
     tstride = pad2d_doubles((int)nv);
-    TSFF_HIP(h, h->fpad.ensure(tstride * ntab * sizeof(double)));
+    TSFF_ENSURE(h, h->fpad, tstride * ntab * sizeof(double));
     TSFF_LAUNCH0(h, k_pad2d, dim3(ntab), dim3(kThreads), 0, h->stream, fe2d, (int)nv, h->fpad.as<double>());
     TSFF_HIP(h, hipGetLastError());
     tables = h->fpad.as<double>() + pad2d_margin((int)nv);   // (the padded table behind its leading margin; per-lineout tables tstride apart)
@@ -1216,7 +1308,7 @@ static int form_factor_2d_impl(tsff_handle* h, int32_t feature, const double* ph
   double* proj = nullptr;
   h->proj_begin = h->proj_end = -1; h->proj_token = 0;
   if (save) {   // projection records of the points [pbegin, pend) for the adjoint that follows (tsff_form_factor_2d_grad)
-    TSFF_HIP(h, h->proj.ensure((size_t)(pend - pbegin) * proj2d_doubles(nv) * sizeof(double)));
+    TSFF_ENSURE(h, h->proj, (size_t)(pend - pbegin) * proj2d_doubles(nv) * sizeof(double));
     proj = h->proj.as<double>();
     h->proj_begin = pbegin; h->proj_end = pend; h->proj_nv = nv; h->proj_feature = feature;
     h->proj_phys = phys; h->proj_fe = fe2d; h->proj_ud = ud_angle_deg; h->proj_va = va_angle_deg; h->proj_B = B;
@@ -1275,15 +1367,15 @@ int tsff_form_factor_2d_grad(tsff_handle* h, int32_t feature, const double* phys
   const int kG2 = lds ? kGL : kGG;
   const size_t smem = sizeof(double) * (kG2 * gsz(nv) + (lds ? (size_t)(nv + 2) * pitch2d(nv, true) : 0));
   if (smem > kLdsLimit) return fail(h, -2, "nv = %d needs %zu B of LDS scratch", (int)nv, smem);
-  TSFF_HIP(h, h->lbacc.ensure((size_t)B * h->S.G * NLB * sizeof(double)));
+  TSFF_ENSURE(h, h->lbacc, (size_t)B * h->S.G * NLB * sizeof(double));
   double* f1bar = nullptr;
   if (grad_fe2d) {
-    TSFF_HIP(h, h->f1bar.ensure((size_t)ntotal * (nv + 2) * sizeof(double)));
+    TSFF_ENSURE(h, h->f1bar, (size_t)ntotal * (nv + 2) * sizeof(double));
     f1bar = h->f1bar.as<double>();
   }
   const double* table = fe2d;  // (one table shared by all lineouts: the 2-D path is never batched in the reference)
   if (!lds) {
-    TSFF_HIP(h, h->fpad.ensure(pad2d_doubles((int)nv) * sizeof(double)));
+    TSFF_ENSURE(h, h->fpad, pad2d_doubles((int)nv) * sizeof(double));
     TSFF_LAUNCH0(h, k_pad2d, dim3(1), dim3(kThreads), 0, h->stream, fe2d, (int)nv, h->fpad.as<double>());
     table = h->fpad.as<double>() + pad2d_margin((int)nv);
   }
@@ -1293,7 +1385,7 @@ int tsff_form_factor_2d_grad(tsff_handle* h, int32_t feature, const double* phys
   // one partial slot per point group and (lineout, gradient point); a group only writes the slots of the (b, g) it meets,
   // the others stay zero
   const int nworker = (int)grid.x * kG2;
-  TSFF_HIP(h, h->lbparts.ensure((size_t)B * h->S.G * nworker * NLB * sizeof(double)));
+  TSFF_ENSURE(h, h->lbparts, (size_t)B * h->S.G * nworker * NLB * sizeof(double));
   TSFF_HIP(h, hipMemsetAsync(h->lbparts.p, 0, (size_t)B * h->S.G * nworker * NLB * sizeof(double), h->stream));
   int rc = with_ion<TSFF_MAX_ION>(h->n_ion, [&](auto N) {
     return with_bool(lds, [&](auto LDS) {
@@ -1317,14 +1409,14 @@ int tsff_form_factor_2d_grad(tsff_handle* h, int32_t feature, const double* phys
 
 static int table_adjoint_2d(tsff_handle* h, int nv, long npoint, double* grad_fe2d) {
   const size_t padn = (size_t)(nv + 2) * (nv + 2);
-  TSFF_HIP(h, h->fbar_pad.ensure(padn * sizeof(double)));
+  TSFF_ENSURE(h, h->fbar_pad, padn * sizeof(double));
   TSFF_HIP(h, hipMemsetAsync(h->fbar_pad.p, 0, padn * sizeof(double), h->stream));
   const int ncell = nv - 1, ntx = (ncell + kTile2 - 1) / kTile2, ntiles = ntx * ntx;
   const int tmax = std::min(ncell, kTile2) + 3;
   const size_t smem = sizeof(double) * (size_t)tmax * (tmax | 1);
   const unsigned per_tile = (unsigned)std::max<long>(1, std::min<long>((npoint + 3) / 4, h->ncu2d() / ntiles));
   const size_t slab = (size_t)tmax * tmax;
-  TSFF_HIP(h, h->fbar_parts.ensure((size_t)per_tile * ntiles * slab * sizeof(double)));
+  TSFF_ENSURE(h, h->fbar_parts, (size_t)per_tile * ntiles * slab * sizeof(double));
   TSFF_LAUNCH0_LDS(h, k_ff2d_table_adj, kLdsLimit, dim3(per_tile, ntiles), dim3(4 * kThreads), smem, h->stream, nv, h->f1bar.as<double>(),
                    npoint, h->fbar_parts.as<double>(), slab);
   for (int t = 0; t < ntiles; ++t)   // one launch per tile, in order: the overlapping halos of neighbouring tiles add up without atomics
@@ -1347,9 +1439,9 @@ int tsff_ats_setup(tsff_handle* h, const tsff_ats_config* c) {
   TSFF_HIP(h, upload(h->ats_tl, c->taps_lam, c->n_taps_lam));
   TSFF_HIP(h, upload(h->ats_lam, c->lam_axis, h->S.npts));
   const size_t img = (size_t)c->n_px * h->S.npts * sizeof(double);
-  TSFF_HIP(h, h->ats_M.ensure(img));
-  TSFF_HIP(h, h->ats_A.ensure(img));
-  TSFF_HIP(h, h->ats_B.ensure(img));
+  TSFF_ENSURE(h, h->ats_M, img);
+  TSFF_ENSURE(h, h->ats_A, img);
+  TSFF_ENSURE(h, h->ats_B, img);
   h->ats_npx = c->n_px; h->ats_nta = c->n_taps_ang; h->ats_offa = c->tap_off_ang; h->ats_ntl = c->n_taps_lam;
   h->ats_offl = c->tap_off_lam; h->ats_lam_step = c->lam_step; h->ats_ang_step = c->ang_step;
   h->ats_row_start = c->row_start; h->ats_row_end = c->row_end;
@@ -1384,9 +1476,9 @@ int tsff_ats_adjoint(tsff_handle* h, const double* P, const double* e_amps, doub
   const int npts = h->S.npts, npx = h->ats_npx, rows = h->ats_row_end - h->ats_row_start;
   if (npts / h->ats_lam_step > TSFF_NBINS) return fail(h, -2, "more than %d wavelength resolution units per row", TSFF_NBINS);
   const size_t img = (size_t)npx * npts * sizeof(double);
-  TSFF_HIP(h, h->ats_C.ensure(img));
-  TSFF_HIP(h, h->ats_D.ensure(img));
-  TSFF_HIP(h, h->ats_stats.ensure((size_t)npx * 4 * sizeof(double) + (size_t)rows * 2 * sizeof(double)));
+  TSFF_ENSURE(h, h->ats_C, img);
+  TSFF_ENSURE(h, h->ats_D, img);
+  TSFF_ENSURE(h, h->ats_stats, (size_t)npx * 4 * sizeof(double) + (size_t)rows * 2 * sizeof(double));
   dim3 block(kThreads), grid((npts + kThreads - 1) / kThreads, npx);
   double* M = h->ats_M.as<double>();
   double* A = h->ats_A.as<double>();
@@ -1441,11 +1533,17 @@ static int fill_call(tsff_handle* h, KCall& K, const double* params, const doubl
 int tsff_forward(tsff_handle* h, const double* params, const double* fe, const double* e_amps, const double* i_amps,
                  const double* noise_e, const double* noise_i, int32_t B, double* ThryE, double* ThryI) {
   DevGuard dg__(h);
+  if (!h) return -1;
+  if (h->S.load[0] && !ThryE) return fail(h, -1, "ThryE missing");
+  if (h->S.load[1] && !ThryI) return fail(h, -1, "ThryI missing");
+  if (h->fe_mode == TSFF_FE_PER_LINEOUT && !fe) return fail(h, -2, "fe_mode PER_LINEOUT needs fe[B][nvx]");
+  if (params && B >= 1 && (!h->S.load[0] || e_amps) && (!h->S.load[1] || i_amps)) {   // (otherwise refused by fill_call)
+    if (int rc = size_plan<0, 0>(h, B)) return rc;
+    if (int rc = ensure_workspace(h, B)) return rc;
+  }
   KCall K{};
   int rc = fill_call(h, K, params, fe, e_amps, i_amps, noise_e, noise_i, B, ThryE, ThryI);
   if (rc) return rc;
-  if (h->S.load[0] && !ThryE) return fail(h, -1, "ThryE missing");
-  if (h->S.load[1] && !ThryI) return fail(h, -1, "ThryI missing");
   return launch_spectrum<0>(h, K);
 }
 
@@ -1460,23 +1558,17 @@ static int loss_grad_impl(tsff_handle* h, const double* params, const double* fe
                           const double* e_amps, const double* i_amps, const double* noise_e, const double* noise_i, int32_t B,
                           const double* weights, const uint8_t* grad_mask, double* loss_terms, double* grad, double* grad_fe,
                           bool want_fe, double* ThryE, double* ThryI, const PackedOut* po = nullptr) {
-  KCall K{};
-  // (the DLM order as a leaf, no table adjoints: the one-sweep kernel can take the per-lineout tables block by block)
-  const bool pipe = grad_mask && h && h->fe_mode == TSFF_FE_DLM && !want_fe && grad_mask[TSFF_P_M] != 0;
-  int rc = fill_call(h, K, params, fe, e_amps, i_amps, noise_e, noise_i, B, ThryE, ThryI, pipe);
-  if (rc) return rc;
+  if (!h) return -1;
+  // every argument is checked before anything is enqueued: a refused call leaves nothing behind (fill_call launches the tables)
   if (po) {
     if (!po->act || !po->packed || po->n_act < 1 || po->n_act > h->S.NP || po->b_off < 0 || po->b_off + B > po->B_global)
       return fail(h, -1, "bad packed-output argument (slots %d, lineouts [%lld, %lld) of %lld)", (int)po->n_act, (long long)po->b_off,
                   (long long)(po->b_off + B), (long long)po->B_global);
     for (int k = 0; k < po->n_act; ++k)
       if (po->act[k] < 0 || po->act[k] >= h->S.NP) return fail(h, -1, "active slot %d out of range", (int)po->act[k]);
-    TSFF_HIP(h, h->gradws.ensure((size_t)B * h->S.NP * sizeof(double)));
-    grad = h->gradws.as<double>();
-    if ((rc = upload_slots(h, po->act, po->n_act))) return rc;
     loss_terms = po->packed;
   }
-  if (!weights || !grad_mask || !loss_terms || !grad) return fail(h, -1, "bad argument");
+  if (!weights || !grad_mask || !loss_terms || (!po && !grad)) return fail(h, -1, "bad argument");
   if (h->S.load[0] && !e_data) return fail(h, -1, "e_data missing");
   if (h->S.load[1] && !i_data) return fail(h, -1, "i_data missing");
   const bool with_m = grad_mask[TSFF_P_M] != 0;
@@ -1485,20 +1577,43 @@ static int loss_grad_impl(tsff_handle* h, const double* params, const double* fe
     return fail(h, -2, "gradient w.r.t. f_e needs fe_mode == TSFF_FE_PER_LINEOUT and an output buffer");
   for (int s = 0; s < h->n_ion; ++s)
     if (grad_mask[TSFF_P_ION0 + 4 * s + TSFF_ION_A]) return fail(h, -3, "A is not a differentiable leaf (ts_params.py:296)");
+  if (!params || B < 1) return fail(h, -1, "bad argument");
+  if (h->S.load[0] && !e_amps) return fail(h, -1, "e_amps missing");
+  if (h->S.load[1] && !i_amps) return fail(h, -1, "i_amps missing");
+  if (h->fe_mode == TSFF_FE_PER_LINEOUT && !fe) return fail(h, -2, "fe_mode PER_LINEOUT needs fe[B][nvx]");
+  int rc = 0;
+  // a changed mask / slot list is uploaded synchronously (pageable source, once per change) -- refused inside graph capture
+  if (h->gmask_host.size() != (size_t)h->S.NP || std::memcmp(h->gmask_host.data(), grad_mask, h->S.NP) != 0) {
+    if (h->capturing) return fail(h, -2, "graph capture: the gradient mask differs from the last eager call's (a change is uploaded synchronously)");
+    h->gmask_host.assign(grad_mask, grad_mask + h->S.NP);
+    TSFF_HIP(h, hipStreamSynchronize(h->stream));
+    TSFF_HIP(h, hipMemcpy(h->gmask.p, h->gmask_host.data(), h->S.NP, hipMemcpyHostToDevice));
+  }
+  if (po && (rc = upload_slots(h, po->act, po->n_act))) return rc;
+  // (the pipelined DLM plan forks onto the handle's second stream: not inside a capture, which this library keeps to one stream)
+  if (h->capturing && h->fe_mode == TSFF_FE_DLM && !want_fe && with_m && h->dlm_blocks > 1)
+    return fail(h, -2, "graph capture: TSFF_OPT_DLM_BLOCKS > 1 would fork onto a second stream (set it to 0 before capturing)");
+  rc = want_fe ? size_plan<1, 2>(h, B) : with_m ? size_plan<1, 1>(h, B) : size_plan<1, 0>(h, B);
+  if (rc) return rc;
+  if ((rc = ensure_workspace(h, B))) return rc;
+  if (want_fe) {
+    TSFF_ENSURE(h, h->Wb, (size_t)2 * B * kNXi2 * sizeof(double));    // (x 2: per-feature parts of the interleaved plan)
+    TSFF_ENSURE(h, h->Hys, (size_t)2 * B * 2 * h->S.nvx * sizeof(double));
+    TSFF_ENSURE(h, h->Yt, (size_t)B * 2 * kNXi1 * sizeof(double));
+  }
+  if (po) TSFF_ENSURE(h, h->gradws, (size_t)B * h->S.NP * sizeof(double));
+  KCall K{};
+  // (the DLM order as a leaf, no table adjoints: the one-sweep kernel can take the per-lineout tables block by block)
+  const bool pipe = h->fe_mode == TSFF_FE_DLM && !want_fe && with_m;
+  rc = fill_call(h, K, params, fe, e_amps, i_amps, noise_e, noise_i, B, ThryE, ThryI, pipe);
+  if (rc) return rc;
+  if (po) grad = h->gradws.as<double>();
   K.data[0] = e_data; K.data[1] = i_data;
   K.wts[0] = weights[0]; K.wts[1] = weights[1]; K.wts[2] = weights[2];
   K.denom_mode = h->denom_mode;
-  if (h->gmask_host.size() != (size_t)h->S.NP || std::memcmp(h->gmask_host.data(), grad_mask, h->S.NP) != 0) {
-    h->gmask_host.assign(grad_mask, grad_mask + h->S.NP);
-    TSFF_HIP(h, hipStreamSynchronize(h->stream));   // (as for the slot list below: pageable source, once per change of the mask)
-    TSFF_HIP(h, hipMemcpy(h->gmask.p, h->gmask_host.data(), h->S.NP, hipMemcpyHostToDevice));
-  }
   bool parts = false, lbrec = false;
   if (want_fe) {
     const int nvx = h->S.nvx;
-    TSFF_HIP(h, h->Wb.ensure((size_t)2 * B * kNXi2 * sizeof(double)));    // (x 2: per-feature parts of the interleaved plan)
-    TSFF_HIP(h, h->Hys.ensure((size_t)2 * B * 2 * nvx * sizeof(double)));
-    TSFF_HIP(h, h->Yt.ensure((size_t)B * 2 * kNXi1 * sizeof(double)));
     K.Wb_out = h->Wb.as<double>();
     K.Hy_out = h->Hys.as<double>();
     K.Hs_out = K.Hy_out + (size_t)B * nvx;
@@ -1625,23 +1740,33 @@ int tsff_loss_hess(tsff_handle* h, const double* params, const double* fe, const
   }
   if ((long)B * A.npair > 0x7fffffffL) return fail(h, -1, "too many (lineout, pair) tasks");
   A.tasks = B * A.npair;
-  KCall K{};
-  int rc = fill_call(h, K, params, fe, e_amps, i_amps, noise_e, noise_i, B, nullptr, nullptr);
-  if (rc) return rc;
   if (h->S.load[0] && !e_data) return fail(h, -1, "e_data missing");
   if (h->S.load[1] && !i_data) return fail(h, -1, "i_data missing");
-  K.data[0] = e_data; K.data[1] = i_data;
   const size_t smem = sizeof(double) * hess_smem_doubles(h->S, A.with_m != 0);
   if (smem > kLdsLimit)
     return fail(h, -2, "tsff_loss_hess: LDS budget exceeded (%zu B with nvx = %d%s): reduce nvx", smem, h->S.nvx,
                 A.with_m ? " and the DLM order as a leaf" : "");
+  if (h->fe_mode == TSFF_FE_PER_LINEOUT && !fe) return fail(h, -2, "fe_mode PER_LINEOUT needs fe[B][nvx]");
+  // every buffer of the call before the first launch (fill_call enqueues the tables)
+  const int nwg = std::min(A.tasks, kHessMaxWG);
+  if (A.with_m) {
+    const size_t nvx = h->S.nvx;
+    TSFF_ENSURE(h, h->htmm, (size_t)B * nvx * sizeof(double2));
+    TSFF_ENSURE(h, h->Xmm, (size_t)B * 4 * kNXi1 * sizeof(double));
+    TSFF_ENSURE(h, h->cstmm, (size_t)B * 2 * sizeof(double));
+    TSFF_ENSURE(h, h->Wmm, (size_t)B * kNXi2 * sizeof(double));
+    TSFF_ENSURE(h, h->Wmm_unused, (size_t)B * kNXi2 * sizeof(double));
+  }
+  TSFF_ENSURE(h, h->hws, (size_t)nwg * 4 * h->S.npts * sizeof(double));
+  TSFF_ENSURE(h, h->hout, (size_t)A.tasks * 12 * sizeof(double));
+  if (params && B >= 1 && (!h->S.load[0] || e_amps) && (!h->S.load[1] || i_amps))   // (otherwise refused by fill_call)
+    if (int rc = ensure_workspace(h, B)) return rc;
+  KCall K{};
+  int rc = fill_call(h, K, params, fe, e_amps, i_amps, noise_e, noise_i, B, nullptr, nullptr);
+  if (rc) return rc;
+  K.data[0] = e_data; K.data[1] = i_data;
   if (A.with_m) {   // second m-derivative tables: k_hess_mtab, then the shipped W-table GEMM on its rows
     const size_t nvx = h->S.nvx;
-    TSFF_HIP(h, h->htmm.ensure((size_t)B * nvx * sizeof(double2)));
-    TSFF_HIP(h, h->Xmm.ensure((size_t)B * 4 * kNXi1 * sizeof(double)));
-    TSFF_HIP(h, h->cstmm.ensure((size_t)B * 2 * sizeof(double)));
-    TSFF_HIP(h, h->Wmm.ensure((size_t)B * kNXi2 * sizeof(double)));
-    TSFF_HIP(h, h->Wmm_unused.ensure((size_t)B * kNXi2 * sizeof(double)));
     const size_t smem_t = sizeof(double2) * 6 * nvx + sizeof(double) * (nvx + 2 * kNXi1 + 8);
     with_ion<TSFF_MAX_ION>(h->n_ion, [&](auto N) {
       TSFF_LAUNCH(h, k_hess_mtab, (N.value), dim3(B), dim3(kThreads), smem_t, h->stream, h->S, params, K.ht, K.htm, h->htmm.as<double2>(),
@@ -1656,11 +1781,8 @@ int tsff_loss_hess(tsff_handle* h, const double* params, const double* fe, const
     A.htmm = h->htmm.as<double2>();
     A.Wmm = h->Wmm.as<double>();
   }
-  const int nwg = std::min(A.tasks, kHessMaxWG);
-  TSFF_HIP(h, h->hws.ensure((size_t)nwg * 4 * h->S.npts * sizeof(double)));
-  TSFF_HIP(h, h->hout.ensure((size_t)A.tasks * 12 * sizeof(double)));
   rc = with_ion<TSFF_MAX_ION>(h->n_ion, [&](auto N) {
-    TSFF_LAUNCH_LDS(h, k_hess_pairs, (N.value), smem, dim3(nwg), dim3(kThreads), smem, h->stream, h->S, K, A, h->hws.as<double>(),
+    TSFF_LAUNCH_LDS(h, k_hess_pairs, (N.value), kLdsLimit, dim3(nwg), dim3(kThreads), smem, h->stream, h->S, K, A, h->hws.as<double>(),
                     h->hout.as<double>());
     return 0;
   });
@@ -1679,12 +1801,16 @@ int tsff_array_loss(tsff_handle* h, const double* params, const double* fe, cons
                     const double* e_amps, const double* i_amps, const double* noise_e, const double* noise_i, int32_t B,
                     double* sums, double* sqdev_e, double* sqdev_i, double* ThryE, double* ThryI) {
   DevGuard dg__(h);
-  KCall K{};
-  int rc = fill_call(h, K, params, fe, e_amps, i_amps, noise_e, noise_i, B, ThryE, ThryI);
-  if (rc) return rc;
+  if (!h) return -1;
   if (!sums) return fail(h, -1, "bad argument");
   if (h->S.load[0] && !e_data) return fail(h, -1, "e_data missing");
   if (h->S.load[1] && !i_data) return fail(h, -1, "i_data missing");
+  if (h->fe_mode == TSFF_FE_PER_LINEOUT && !fe) return fail(h, -2, "fe_mode PER_LINEOUT needs fe[B][nvx]");
+  if (params && B >= 1 && (!h->S.load[0] || e_amps) && (!h->S.load[1] || i_amps))   // (otherwise refused by fill_call)
+    if (int rc = size_plan<2, 0>(h, B)) return rc;
+  KCall K{};
+  int rc = fill_call(h, K, params, fe, e_amps, i_amps, noise_e, noise_i, B, ThryE, ThryI);
+  if (rc) return rc;
   K.data[0] = e_data; K.data[1] = i_data;
   K.sqdev[0] = sqdev_e; K.sqdev[1] = sqdev_i;
   K.lpart = sums;

@@ -229,6 +229,7 @@ class Engine:
 
         self._keep = keep
         self._staging = {}
+        self._last_stream = None
         self._cfg_struct = c
         h = C.c_void_p()
         cutoff = irf_cutoff_sigmas
@@ -298,6 +299,7 @@ class Engine:
             buf[2].synchronize()   # (the earlier H2D copy out of this pinned buffer)
         pin, dev, ev = buf
         pin.numpy()[...] = a
+        self._follow_stream()   # (the device tensor may still be read by the previous call on another stream)
         dev.copy_(pin, non_blocking=True)
         ev.record(torch.cuda.current_stream(self.device))
         return dev
@@ -314,9 +316,27 @@ class Engine:
         torch.cuda.current_stream(self.device).synchronize()
         return pin.numpy().copy()
 
+    def _follow_stream(self):
+        """torch's current stream, made to wait for the stream of this engine's previous call when it is another one: the
+        staging tensors of ``upload`` and the packed buffers are reused call after call (the library orders its own scratch
+        the same way, tsff_set_stream).  Not inside graph capture: the capture contract (tsff.h) keeps one stream."""
+        torch = self.torch
+        s = torch.cuda.current_stream(self.device)
+        last = self._last_stream
+        if last is not None and last != s and not torch.cuda.is_current_stream_capturing():
+            s.wait_stream(last)
+        self._last_stream = s
+        return s
+
     def _sync_stream(self):
-        s = self.torch.cuda.current_stream(self.device)
+        s = self._follow_stream()
         L.check(self.lib, self.h, self.lib.tsff_set_stream(self.h, C.c_void_p(s.cuda_stream)))
+
+    def reserve(self, B: int):
+        """tsff_reserve: size the workspace for calls of up to B lineouts now, so that they allocate nothing -- the first step
+        of the graph-capture contract of tsff.h (reserve, one eager call with the same mask and slots, synchronise, capture)."""
+        self._sync_stream()
+        L.check(self.lib, self.h, self.lib.tsff_reserve(self.h, int(B)))
 
     def _vec(self, a, B):
         """amplitude-like input -> [B] device vector."""
