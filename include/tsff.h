@@ -23,6 +23,7 @@
  *   jax reverse mode through the above (equinox.filter_value_and_grad, loss_function.py:108)
  *       tsff_loss_grad(_fe), tsff_form_factor_grad, tsff_form_factor_2d_grad, tsff_ats_adjoint
  *   LossFunction.h_loss_wrt_params (equinox.filter_hessian) inverse/loss_function.py:170-188  tsff_loss_hess
+ *   _1d_adam_loop_ (optax.adam + eqx.apply_updates + best tracking)  inverse/loops.py:59-95        tsff_adam_fit
  *
  * Conventions
  *   - every array pointer in a *call* is a DEVICE pointer (hipMalloc'ed or a torch CUDA tensor);
@@ -31,8 +32,8 @@
  *   - the caller owns every buffer; the library never frees caller memory;
  *   - calls are asynchronous on the handle's stream (tsff_set_stream); the caller synchronises;
  *   - return value 0 = success, negative = error, text via tsff_last_error();
- *   - a refused call (negative return) of tsff_forward, tsff_loss_grad(_packed, _fe), tsff_loss_hess, tsff_array_loss and
- *     tsff_form_factor(_grad) has enqueued nothing: their arguments, LDS budgets and buffers are checked before the first
+ *   - a refused call (negative return) of tsff_forward, tsff_loss_grad(_packed, _fe), tsff_loss_hess, tsff_array_loss,
+ *     tsff_adam_fit and tsff_form_factor(_grad) has enqueued nothing: their arguments, LDS budgets and buffers are checked before the first
  *     launch, and tsff_last_launch reports an empty list (other entry points may have enqueued work before a failure);
  *   - a handle is bound to the device that was current at tsff_create; handles are not thread-safe,
  *     the library is re-entrant across handles.
@@ -47,7 +48,7 @@
 extern "C" {
 #endif
 
-#define TSFF_ABI_VERSION 10
+#define TSFF_ABI_VERSION 11
 /* error codes (every entry point returns 0 or one of these; text via tsff_last_error):
  * -1 bad argument, -2 unsupported configuration / option, -3 not a differentiable leaf, -5 HIP runtime error,
  * -22 stale or foreign token of saved projection records (tsff_form_factor_2d_grad),
@@ -325,6 +326,33 @@ int tsff_loss_grad_packed(tsff_handle *h, const double *params, const double *fe
                           const double *noise_i, int32_t B, const double *weights, const uint8_t *grad_mask,
                           const int32_t *active_slots, int32_t n_active, int64_t B_global, int64_t b_offset,
                           double *packed, double *ThryE, double *ThryI);
+
+/* The reference's 1-D Adam loop (_1d_adam_loop_, inverse/loops.py:59-95) on the device: n_steps steps, each the packed
+ * loss + gradient of tsff_loss_grad_packed (B_global = B, b_offset = 0, no spectra) into a buffer owned by the handle followed by
+ * one Adam update of the active leaves, all enqueued on the handle's stream; the call returns once they are enqueued (no
+ * synchronisation and no allocation between the steps -- everything is sized and uploaded before the first launch).
+ *   params (device [B][NP], in/out): normalised leaves; the slots of active_slots are trained, the others stay as they are;
+ *   fe: as tsff_loss_grad -- with fe_mode PER_LINEOUT the given [B][nvx] table is a constant: this entry never trains f_e;
+ *   weights (HOST [3]): as tsff_loss_grad; the loss of a step is (w[0] S_iaw + w[1] S_blue) + w[2] S_red;
+ *   active_slots (HOST [n_active]): the trained slots in ravel order (as tsff_loss_grad_packed); the gradient mask is derived
+ *   from them.  A slot out of range or repeated returns -1, TSFF_P_M without fe_mode == TSFF_FE_DLM -2, an ion's A slot -3;
+ *   step0: the optimiser's step count before the first step (optax's `count`): a fit run in chunks of 10 + 10 + 10 steps with
+ *   step0 = 0, 10, 20 is bit for bit one call of 30 steps;
+ *   hyper (HOST [4]): lr, b1, b2, eps;
+ *   state (device [2][n_active][B], in/out): mu, nu of the active leaves; zeros start a fit;
+ *   loss_hist (device [n_steps] or NULL): the loss of each step, measured at the parameters BEFORE its update;
+ *   best (device [1 + B * NP], in/out): [best loss | best params]; start a fit with [1e16 | params].  A step whose loss is below
+ *   best[0] (never a NaN) makes it the best loss and copies the step's UPDATED iterate into the active slots of the best
+ *   params (loops.py:88-93 store diff_params after apply_updates: the iterate one step past the one whose loss was measured).
+ * The update is tsadar_amd.tree.Adam's, operation for operation in double and unfused (k_adam.inc):
+ *   mu = b1 mu + (1 - b1) g;  nu = b2 nu + ((1 - b2) g) g;  x += ((-lr) (mu / c1)) / (sqrt(nu / c2) + eps),
+ *   c1 = 1 - b1^count, c2 = 1 - b2^count (computed on the host with pow), count = step0 + step + 1,
+ * so it reproduces that host loop bit for bit (optax associates -lr * ((m / c1) / (...)) and (1 - b2) g^2: an ulp apart).
+ * n_steps == 0 returns 0 and enqueues nothing; n_steps < 0, a null params, state, best or hyper returns -1. */
+int tsff_adam_fit(tsff_handle *h, double *params, const double *fe, const double *e_data, const double *i_data,
+                  const double *e_amps, const double *i_amps, const double *noise_e, const double *noise_i, int32_t B,
+                  const double *weights, const int32_t *active_slots, int32_t n_active, int32_t n_steps, int32_t step0,
+                  const double *hyper, double *state, double *loss_hist, double *best);
 
 /* Exact per-lineout Hessian of the fit loss: LossFunction._loss_for_hess_fn_ / h_loss_wrt_params
  * (inverse/loss_function.py:170-188, equinox.filter_hessian) for every lineout b, with respect to the normalised leaves

@@ -94,6 +94,7 @@ struct tsff_handle {
   }
   std::vector<uint8_t> gmask_host;  // last gradient mask uploaded (re-sent only when it changes)
   tsff::DevBuf act, gradws;         // tsff_loss_grad_packed: active slots on the device, per-lineout gradient workspace
+  tsff::DevBuf adam_packed, adam_best;   // tsff_adam_fit: the packed buffer of its steps, the ping-pong pair of best losses
   std::vector<int32_t> act_host;
   tsff::DevBuf hws, hout;          // tsff_loss_hess: hyper-dual spectra of the persistent workgroups, per-task sums
   tsff::DevBuf htmm, Xmm, cstmm, Wmm, Wmm_unused;   // tsff_loss_hess with the DLM order m: second m-derivative tables
@@ -247,6 +248,16 @@ static int timing_end(tsff_handle* h) {
     TSFF_HIP(h, hipEventRecord(h->ev1[timing_slot(h)], h->stream));
     h->ev_count++;
   }
+  return 0;
+}
+
+// the gradient mask on the device; re-sent (synchronously: pageable source) only when it changes -- refused inside graph capture
+static int upload_mask(tsff_handle* h, const uint8_t* grad_mask) {
+  if (h->gmask_host.size() == (size_t)h->S.NP && std::memcmp(h->gmask_host.data(), grad_mask, h->S.NP) == 0) return 0;
+  if (h->capturing) return fail(h, -2, "graph capture: the gradient mask differs from the last eager call's (a change is uploaded synchronously)");
+  h->gmask_host.assign(grad_mask, grad_mask + h->S.NP);
+  TSFF_HIP(h, hipStreamSynchronize(h->stream));
+  TSFF_HIP(h, hipMemcpy(h->gmask.p, h->gmask_host.data(), h->S.NP, hipMemcpyHostToDevice));
   return 0;
 }
 
@@ -1583,12 +1594,7 @@ static int loss_grad_impl(tsff_handle* h, const double* params, const double* fe
   if (h->fe_mode == TSFF_FE_PER_LINEOUT && !fe) return fail(h, -2, "fe_mode PER_LINEOUT needs fe[B][nvx]");
   int rc = 0;
   // a changed mask / slot list is uploaded synchronously (pageable source, once per change) -- refused inside graph capture
-  if (h->gmask_host.size() != (size_t)h->S.NP || std::memcmp(h->gmask_host.data(), grad_mask, h->S.NP) != 0) {
-    if (h->capturing) return fail(h, -2, "graph capture: the gradient mask differs from the last eager call's (a change is uploaded synchronously)");
-    h->gmask_host.assign(grad_mask, grad_mask + h->S.NP);
-    TSFF_HIP(h, hipStreamSynchronize(h->stream));
-    TSFF_HIP(h, hipMemcpy(h->gmask.p, h->gmask_host.data(), h->S.NP, hipMemcpyHostToDevice));
-  }
+  if ((rc = upload_mask(h, grad_mask))) return rc;
   if (po && (rc = upload_slots(h, po->act, po->n_act))) return rc;
   // (the pipelined DLM plan forks onto the handle's second stream: not inside a capture, which this library keeps to one stream)
   if (h->capturing && h->fe_mode == TSFF_FE_DLM && !want_fe && with_m && h->dlm_blocks > 1)
@@ -1681,6 +1687,72 @@ int tsff_loss_grad_packed(tsff_handle* h, const double* params, const double* fe
   po.act = active_slots; po.n_act = n_active; po.B_global = B_global; po.b_off = b_offset; po.packed = packed;
   return loss_grad_impl(h, params, fe, e_data, i_data, e_amps, i_amps, noise_e, noise_i, B, weights, grad_mask, nullptr, nullptr,
                         nullptr, false, ThryE, ThryI, &po);
+}
+
+// the 1-D Adam fit on the device (k_adam.inc): n_steps x (loss_grad_impl in its packed form + k_adam_step), all enqueued on the
+// handle's stream.  Everything a step needs -- the plan's scratch, the workspace, the packed buffer, the mask and the slot list
+// -- is sized and uploaded before the first launch, so the loop itself allocates nothing and never synchronises (each step's
+// loss_grad_impl finds the same mask, slot list and batch size in place: its upload and growth paths return before doing anything).
+int tsff_adam_fit(tsff_handle* h, double* params, const double* fe, const double* e_data, const double* i_data, const double* e_amps,
+                  const double* i_amps, const double* noise_e, const double* noise_i, int32_t B, const double* weights,
+                  const int32_t* active_slots, int32_t n_active, int32_t n_steps, int32_t step0, const double* hyper, double* state,
+                  double* loss_hist, double* best) {
+  DevGuard dg__(h);
+  if (!h) return -1;
+  // every argument is checked before anything is enqueued (a refused call leaves nothing behind)
+  if (!params || B < 1 || !weights || !active_slots || !hyper || !state || !best || n_active < 1 || n_active > h->S.NP ||
+      n_steps < 0 || step0 < 0 || (int64_t)step0 + n_steps > 0x7fffffffLL)
+    return fail(h, -1, "bad argument");
+  uint8_t gm[kNP_MAX] = {};
+  for (int k = 0; k < n_active; ++k) {
+    const int s = active_slots[k];
+    if (s < 0 || s >= h->S.NP) return fail(h, -1, "active slot %d out of range", s);
+    if (gm[s]) return fail(h, -1, "active slot %d repeated", s);
+    gm[s] = 1;
+  }
+  if (gm[TSFF_P_M] && h->fe_mode != TSFF_FE_DLM) return fail(h, -2, "gradient w.r.t. the DLM order m needs fe_mode == TSFF_FE_DLM");
+  for (int i = 0; i < h->n_ion; ++i)
+    if (gm[TSFF_P_ION0 + 4 * i + TSFF_ION_A]) return fail(h, -3, "A is not a differentiable leaf (ts_params.py:296)");
+  if (h->S.load[0] && (!e_data || !e_amps)) return fail(h, -1, "e_data / e_amps missing");
+  if (h->S.load[1] && (!i_data || !i_amps)) return fail(h, -1, "i_data / i_amps missing");
+  if (h->fe_mode == TSFF_FE_PER_LINEOUT && !fe) return fail(h, -2, "fe_mode PER_LINEOUT needs fe[B][nvx]");
+  if (n_steps == 0) return 0;
+  const bool with_m = gm[TSFF_P_M] != 0;
+  if (h->capturing && h->fe_mode == TSFF_FE_DLM && with_m && h->dlm_blocks > 1)
+    return fail(h, -2, "graph capture: TSFF_OPT_DLM_BLOCKS > 1 would fork onto a second stream (set it to 0 before capturing)");
+  int rc = with_m ? size_plan<1, 1>(h, B) : size_plan<1, 0>(h, B);
+  if (rc) return rc;
+  if ((rc = ensure_workspace(h, B))) return rc;
+  TSFF_ENSURE(h, h->gradws, (size_t)B * h->S.NP * sizeof(double));
+  const long n = (long)n_active * B;
+  TSFF_ENSURE(h, h->adam_packed, (size_t)(3 + n) * sizeof(double));
+  TSFF_ENSURE(h, h->adam_best, 2 * sizeof(double));
+  if ((rc = upload_mask(h, gm))) return rc;
+  if ((rc = upload_slots(h, active_slots, n_active))) return rc;
+  // the optimiser's scalars exactly as tree.Adam computes them in Python (1 - b1, -lr, 1 - b1**count: glibc pow is Python's **)
+  const double lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3];
+  const double omb1 = 1.0 - b1, omb2 = 1.0 - b2, neg_lr = -lr;
+  double* packed = h->adam_packed.as<double>();
+  double* bl = h->adam_best.as<double>();   // bl[t & 1]: the best loss before step t, bl[(t + 1) & 1]: after it
+  double* mu = state;
+  double* nu = state + n;
+  PackedOut po;
+  po.act = active_slots; po.n_act = n_active; po.B_global = B; po.b_off = 0; po.packed = packed;
+  TSFF_HIP(h, hipMemcpyAsync(bl, best, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  const dim3 agrid((unsigned)std::min<long>((n + kThreads - 1) / kThreads, 1024));
+  for (int t = 0; t < n_steps; ++t) {
+    rc = loss_grad_impl(h, params, fe, e_data, i_data, e_amps, i_amps, noise_e, noise_i, B, weights, gm, nullptr, nullptr, nullptr,
+                        false, nullptr, nullptr, &po);
+    if (rc) return rc;
+    const double count = (double)step0 + t + 1;
+    const double c1 = 1.0 - std::pow(b1, count), c2 = 1.0 - std::pow(b2, count);
+    TSFF_LAUNCH0(h, k_adam_step, agrid, dim3(kThreads), 0, h->stream, (const double*)packed, weights[0], weights[1], weights[2],
+                 h->act.as<int>(), (int)n_active, (int)B, h->S.NP, params, mu, nu, b1, omb1, b2, omb2, neg_lr, c1, c2, eps,
+                 loss_hist ? loss_hist + t : nullptr, (const double*)(bl + (t & 1)), bl + ((t + 1) & 1),
+                 t == n_steps - 1 ? best : nullptr, best + 1);
+    TSFF_HIP(h, hipGetLastError());
+  }
+  return 0;
 }
 
 int tsff_loss_grad_fe(tsff_handle* h, const double* params, const double* fe, const double* e_data, const double* i_data,

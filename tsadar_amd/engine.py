@@ -668,6 +668,44 @@ class Engine:
         L.check(self.lib, self.h, rc)
         return out, E, I
 
+    def adam_fit(self, params, batch, weights, active_slots, n_steps, hyper, state=None, best=None, step0=0, loss_hist=True,
+                 fe=None):
+        """tsff_adam_fit: ``n_steps`` Adam steps of the active leaves on the device, enqueued at once; nothing is synchronised.
+        -> (params [B, NP], state [2, P, B] (mu, nu), loss_hist [n_steps] or None, best [1 + B * NP] = [best loss | best params])
+        as CUDA tensors.  ``params``, ``state`` and ``best`` are updated in place when they are float64 CUDA tensors already
+        (pass the returned ones to the next chunk, with ``step0`` the steps done so far); otherwise they are copied to new
+        ones.  ``state=None`` starts a fit (zeros), ``best=None`` starts the best tracking at [1e16 | params].
+        ``hyper`` = (lr, b1, b2, eps).  ``fe`` (fe_mode PER_LINEOUT): the tabulated f_e, a constant of the fit."""
+        torch = self.torch
+        X = self.dev(params).reshape(-1, self.NP)
+        B = X.shape[0]
+        act = np.ascontiguousarray(active_slots, dtype=np.int32)
+        P = int(act.size)
+        ea = self._vec(batch["e_amps"], B) if self.load_ele else None
+        ia = self._vec(batch["i_amps"], B) if self.load_ion else None
+        ed = self._mat(batch["e_data"], B) if self.load_ele else None
+        idt = self._mat(batch["i_data"], B) if self.load_ion else None
+        ne_, ni_ = self._mat(batch.get("noise_e"), B), self._mat(batch.get("noise_i"), B)
+        fe_d = self.dev(fe)
+        state = torch.zeros((2, P, B), dtype=torch.float64, device=self.device) if state is None else self.dev(state)
+        assert state.numel() == 2 * P * B, f"state must hold 2 x {P} x {B} values"
+        if best is None:
+            best = torch.cat([torch.full((1,), 1e16, dtype=torch.float64, device=self.device), X.reshape(-1)])
+        else:
+            best = self.dev(best)
+        assert best.numel() == 1 + B * self.NP, f"best must hold 1 + {B} x {self.NP} values"
+        hist = torch.empty(max(int(n_steps), 0), dtype=torch.float64, device=self.device) if loss_hist else None
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        hy = np.ascontiguousarray(hyper, dtype=np.float64)
+        assert hy.size == 4, "hyper = (lr, b1, b2, eps)"
+        self._sync_stream()
+        rc = self.lib.tsff_adam_fit(self.h, self._ptr(X), self._ptr(fe_d), self._ptr(ed), self._ptr(idt), self._ptr(ea), self._ptr(ia),
+                                    self._ptr(ne_), self._ptr(ni_), B, w.ctypes.data_as(L.c_double_p),
+                                    act.ctypes.data_as(C.POINTER(C.c_int32)), P, int(n_steps), int(step0),
+                                    hy.ctypes.data_as(L.c_double_p), self._ptr(state), self._ptr(hist), self._ptr(best))
+        L.check(self.lib, self.h, rc)
+        return X, state, hist, best
+
     def array_loss(self, params, batch, fe=None):
         torch = self.torch
         X = self.dev(params).reshape(-1, self.NP)
