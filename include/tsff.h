@@ -24,6 +24,7 @@
  *       tsff_loss_grad(_fe), tsff_form_factor_grad, tsff_form_factor_2d_grad, tsff_ats_adjoint
  *   LossFunction.h_loss_wrt_params (equinox.filter_hessian) inverse/loss_function.py:170-188  tsff_loss_hess
  *   _1d_adam_loop_ (optax.adam + eqx.apply_updates + best tracking)  inverse/loops.py:59-95        tsff_adam_fit
+ *   _1d_scipy_loop_ (scipy L-BFGS-B, bounds=None)                     inverse/loops.py:20-56        tsff_lbfgs_fit
  *
  * Conventions
  *   - every array pointer in a *call* is a DEVICE pointer (hipMalloc'ed or a torch CUDA tensor);
@@ -48,7 +49,7 @@
 extern "C" {
 #endif
 
-#define TSFF_ABI_VERSION 11
+#define TSFF_ABI_VERSION 12
 /* error codes (every entry point returns 0 or one of these; text via tsff_last_error):
  * -1 bad argument, -2 unsupported configuration / option, -3 not a differentiable leaf, -5 HIP runtime error,
  * -22 stale or foreign token of saved projection records (tsff_form_factor_2d_grad),
@@ -353,6 +354,33 @@ int tsff_adam_fit(tsff_handle *h, double *params, const double *fe, const double
                   const double *e_amps, const double *i_amps, const double *noise_e, const double *noise_i, int32_t B,
                   const double *weights, const int32_t *active_slots, int32_t n_active, int32_t n_steps, int32_t step0,
                   const double *hyper, double *state, double *loss_hist, double *best);
+
+/* The reference's default 1-D loop (_1d_scipy_loop_, inverse/loops.py:20-56: scipy L-BFGS-B on the activated leaves, bounds=None)
+ * on the device: n_evals x (the packed loss + gradient of tsff_loss_grad_packed with B_global = B, b_offset = 0 and no spectra,
+ * into a buffer owned by the handle, then 2 maxcor + 6 launches of k_lbfgs_step, one pass of the optimiser each), all enqueued
+ * on the handle's stream; the call returns once they are enqueued (no synchronisation and no allocation between the evaluations).  The optimiser is joint, unbounded L-BFGS-B on the
+ * flat vector of n = n_active x B unknowns in ravel order, as tsadar_amd/lbfgs.py restates it: the device reproduces that host
+ * restatement bit for bit (fixed-order inner products, k_lbfgs.inc) and scipy's iterates up to rounding.
+ *   params (device [B][NP], in/out): normalised leaves; k_lbfgs_step writes the next point to evaluate into the active slots;
+ *   once the status is terminal they hold the result (the last accepted iterate) and later evaluations change nothing;
+ *   fe, e_data .. noise_i, B, weights, active_slots, n_active: as tsff_adam_fit (the same refusals: a slot out of range or
+ *   repeated -1, TSFF_P_M without fe_mode == TSFF_FE_DLM -2, an ion's A slot -3); the loss of an evaluation is
+ *   (w[0] S_iaw + w[1] S_blue) + w[2] S_red;
+ *   opts (HOST [6]): maxcor (1..64), ftol, gtol, maxiter, maxfun, maxls -- scipy's options of the same names;
+ *   state (device [n_state], in/out): the optimiser (line search, x0, g0, d and the (s, y) ring); all zeros starts a fit at
+ *   params; n_state >= tsff_lbfgs_state_size(B, n_active, maxcor), else -1.  A fit run in chunks of 7 + 7 + 7 evaluations on
+ *   the same state is bit for bit one call of 21;
+ *   f_hist (device [n_evals] or NULL): the loss of each evaluation (NaN for an evaluation after the end);
+ *   info (device int32 [4] or NULL): status, nit, nfev, nskip after the last evaluation.  status: 0 running, 1 converged
+ *   (max|g| <= gtol), 2 converged (relative reduction of f <= ftol), 3 nit >= maxiter, 4 nfev > maxfun, 5 abnormal (the line
+ *   search failed with an empty memory); scipy's status is 0 for 1-2, 1 for 3-4, 2 for 5.
+ * n_evals == 0 returns 0 and enqueues nothing; n_evals < 0, a null params, weights, active_slots, opts or state, or a bad option
+ * returns -1. */
+int tsff_lbfgs_state_size(int32_t B, int32_t n_active, int32_t maxcor, int64_t *n_doubles);
+int tsff_lbfgs_fit(tsff_handle *h, double *params, const double *fe, const double *e_data, const double *i_data,
+                   const double *e_amps, const double *i_amps, const double *noise_e, const double *noise_i, int32_t B,
+                   const double *weights, const int32_t *active_slots, int32_t n_active, int32_t n_evals, const double *opts,
+                   double *state, int64_t n_state, double *f_hist, int32_t *info);
 
 /* Exact per-lineout Hessian of the fit loss: LossFunction._loss_for_hess_fn_ / h_loss_wrt_params
  * (inverse/loss_function.py:170-188, equinox.filter_hessian) for every lineout b, with respect to the normalised leaves

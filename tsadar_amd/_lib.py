@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtsff.so")
 LIB_PATH = os.environ.get("TSFF_LIBRARY", LIB_PATH)  # A/B experiments: another in-tree build of the same ABI
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 MAX_ION = 4
 NBINS = 1024
 NXI1 = 1024
@@ -129,6 +129,9 @@ _SIGNATURES = {
     "tsff_pack_fe_rows": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int64, C.c_int64, _vp]),
     "tsff_adam_fit": (C.c_int, [_vp] + [_vp] * 8 + [C.c_int32, c_double_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
                                 c_double_p, _vp, _vp, _vp]),
+    "tsff_lbfgs_state_size": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "tsff_lbfgs_fit": (C.c_int, [_vp] + [_vp] * 8 + [C.c_int32, c_double_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, c_double_p,
+                                 _vp, C.c_int64, _vp, _vp]),
     "tsff_loss_hess": (C.c_int, [_vp] + [_vp] * 8 + [C.c_int32, c_double_p, C.POINTER(C.c_int32), C.c_int32, _vp, _vp, _vp]),
     "tsff_array_loss": (C.c_int, [_vp] + [_vp] * 8 + [C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "tsff_enable_timing": (C.c_int, [_vp, C.c_int32]),

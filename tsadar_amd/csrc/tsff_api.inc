@@ -95,6 +95,7 @@ struct tsff_handle {
   std::vector<uint8_t> gmask_host;  // last gradient mask uploaded (re-sent only when it changes)
   tsff::DevBuf act, gradws;         // tsff_loss_grad_packed: active slots on the device, per-lineout gradient workspace
   tsff::DevBuf adam_packed, adam_best;   // tsff_adam_fit: the packed buffer of its steps, the ping-pong pair of best losses
+  tsff::DevBuf lbfgs_packed;             // tsff_lbfgs_fit: the packed buffer of its evaluations
   std::vector<int32_t> act_host;
   tsff::DevBuf hws, hout;          // tsff_loss_hess: hyper-dual spectra of the persistent workgroups, per-task sums
   tsff::DevBuf htmm, Xmm, cstmm, Wmm, Wmm_unused;   // tsff_loss_hess with the DLM order m: second m-derivative tables
@@ -1751,6 +1752,80 @@ int tsff_adam_fit(tsff_handle* h, double* params, const double* fe, const double
                  loss_hist ? loss_hist + t : nullptr, (const double*)(bl + (t & 1)), bl + ((t + 1) & 1),
                  t == n_steps - 1 ? best : nullptr, best + 1);
     TSFF_HIP(h, hipGetLastError());
+  }
+  return 0;
+}
+
+int tsff_lbfgs_state_size(int32_t B, int32_t n_active, int32_t maxcor, int64_t* n_doubles) {
+  if (B < 1 || n_active < 1 || maxcor < 1 || maxcor > kLbMaxCor || !n_doubles) return -1;
+  *n_doubles = lb_vec_offset(maxcor) + (int64_t)(4 + 2 * maxcor) * n_active * B;
+  return 0;
+}
+
+// the 1-D L-BFGS-B fit on the device (k_lbfgs.inc): n_evals x (loss_grad_impl in its packed form + lb_passes(maxcor) launches of
+// k_lbfgs_step on lb_blocks(n) workgroups), all enqueued on
+// the handle's stream, sized and uploaded before the first launch exactly as tsff_adam_fit is.
+int tsff_lbfgs_fit(tsff_handle* h, double* params, const double* fe, const double* e_data, const double* i_data, const double* e_amps,
+                   const double* i_amps, const double* noise_e, const double* noise_i, int32_t B, const double* weights,
+                   const int32_t* active_slots, int32_t n_active, int32_t n_evals, const double* opts, double* state, int64_t n_state,
+                   double* f_hist, int32_t* info) {
+  DevGuard dg__(h);
+  if (!h) return -1;
+  // every argument is checked before anything is enqueued (a refused call leaves nothing behind)
+  if (!params || B < 1 || !weights || !active_slots || !opts || !state || n_active < 1 || n_active > h->S.NP || n_evals < 0)
+    return fail(h, -1, "bad argument");
+  const double maxcor_d = opts[0], ftol = opts[1], gtol = opts[2], maxiter_d = opts[3], maxfun_d = opts[4], maxls_d = opts[5];
+  auto whole = [](double v, double lo, double hi) { return v >= lo && v <= hi && v == std::floor(v); };
+  if (!whole(maxcor_d, 1, kLbMaxCor) || !whole(maxiter_d, 0, 0x7fffffff) || !whole(maxfun_d, 0, 0x7fffffff) ||
+      !whole(maxls_d, 1, 0x7fffffff) || !(ftol >= 0.0) || !(gtol >= 0.0))
+    return fail(h, -1, "bad option (opts = maxcor in [1, %d], ftol >= 0, gtol >= 0, maxiter >= 0, maxfun >= 0, maxls >= 1)", kLbMaxCor);
+  uint8_t gm[kNP_MAX] = {};
+  for (int k = 0; k < n_active; ++k) {
+    const int s = active_slots[k];
+    if (s < 0 || s >= h->S.NP) return fail(h, -1, "active slot %d out of range", s);
+    if (gm[s]) return fail(h, -1, "active slot %d repeated", s);
+    gm[s] = 1;
+  }
+  if (gm[TSFF_P_M] && h->fe_mode != TSFF_FE_DLM) return fail(h, -2, "gradient w.r.t. the DLM order m needs fe_mode == TSFF_FE_DLM");
+  for (int i = 0; i < h->n_ion; ++i)
+    if (gm[TSFF_P_ION0 + 4 * i + TSFF_ION_A]) return fail(h, -3, "A is not a differentiable leaf (ts_params.py:296)");
+  if (h->S.load[0] && (!e_data || !e_amps)) return fail(h, -1, "e_data / e_amps missing");
+  if (h->S.load[1] && (!i_data || !i_amps)) return fail(h, -1, "i_data / i_amps missing");
+  if (h->fe_mode == TSFF_FE_PER_LINEOUT && !fe) return fail(h, -2, "fe_mode PER_LINEOUT needs fe[B][nvx]");
+  const int maxcor = (int)maxcor_d;
+  int64_t need = 0;
+  if (tsff_lbfgs_state_size(B, n_active, maxcor, &need) || n_state < need)
+    return fail(h, -1, "state holds %lld doubles, needs %lld", (long long)n_state, (long long)need);
+  if (n_evals == 0) return 0;
+  const bool with_m = gm[TSFF_P_M] != 0;
+  if (h->capturing && h->fe_mode == TSFF_FE_DLM && with_m && h->dlm_blocks > 1)
+    return fail(h, -2, "graph capture: TSFF_OPT_DLM_BLOCKS > 1 would fork onto a second stream (set it to 0 before capturing)");
+  int rc = with_m ? size_plan<1, 1>(h, B) : size_plan<1, 0>(h, B);
+  if (rc) return rc;
+  if ((rc = ensure_workspace(h, B))) return rc;
+  TSFF_ENSURE(h, h->gradws, (size_t)B * h->S.NP * sizeof(double));
+  const long n = (long)n_active * B;
+  TSFF_ENSURE(h, h->lbfgs_packed, (size_t)(3 + n) * sizeof(double));
+  if ((rc = upload_mask(h, gm))) return rc;
+  if ((rc = upload_slots(h, active_slots, n_active))) return rc;
+  // mainlb's tol = factr * epsmch with the wrapper's factr = ftol / eps (lbfgs.Lbfgs)
+  const double tol = (ftol / kLbEps) * kLbEps;
+  const int maxiter = (int)maxiter_d, maxfun = (int)maxfun_d, maxls = (int)maxls_d;
+  double* packed = h->lbfgs_packed.as<double>();
+  const dim3 grid((unsigned)lb_blocks(n));
+  const int passes = lb_passes(maxcor);
+  PackedOut po;
+  po.act = active_slots; po.n_act = n_active; po.B_global = B; po.b_off = 0; po.packed = packed;
+  for (int t = 0; t < n_evals; ++t) {
+    rc = loss_grad_impl(h, params, fe, e_data, i_data, e_amps, i_amps, noise_e, noise_i, B, weights, gm, nullptr, nullptr, nullptr,
+                        false, nullptr, nullptr, &po);
+    if (rc) return rc;
+    for (int k = 0; k < passes; ++k) {   // (a pass the evaluation does not need returns at once)
+      TSFF_LAUNCH0(h, k_lbfgs_step, grid, dim3(kLbThreads), 0, h->stream, (const double*)packed, weights[0], weights[1], weights[2],
+                   h->act.as<int>(), (int)n_active, (int)B, h->S.NP, params, state, maxcor, tol, gtol, maxiter, maxfun, maxls, k,
+                   f_hist ? f_hist + t : nullptr, info);
+      TSFF_HIP(h, hipGetLastError());
+    }
   }
   return 0;
 }

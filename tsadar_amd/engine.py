@@ -706,6 +706,63 @@ class Engine:
         L.check(self.lib, self.h, rc)
         return X, state, hist, best
 
+    def lbfgs_fit(self, params, batch, weights, active_slots, n_evals, opts=(10, 2.220446049250313e-09, 1e-5, 15000, 15000, 20),
+                  state=None, f_hist=True, info=None, fe=None):
+        """tsff_lbfgs_fit: ``n_evals`` evaluations of unbounded L-BFGS-B on the active leaves, enqueued at once; nothing is
+        synchronised.  -> (params [B, NP], state, f_hist [n_evals] or None, info int32 [4]) as CUDA tensors.  ``params``,
+        ``state`` and ``info`` are updated in place when they are CUDA tensors of the right type already (pass the returned
+        ones to the next chunk); otherwise they are copied to new ones.  ``state=None`` starts a fit (zeros) at ``params``.
+        ``opts`` = (maxcor, ftol, gtol, maxiter, maxfun, maxls).  ``fe`` (fe_mode PER_LINEOUT): a constant of the fit.
+        Read the outcome with :meth:`lbfgs_info`."""
+        torch = self.torch
+        X = self.dev(params).reshape(-1, self.NP)
+        B = X.shape[0]
+        act = np.ascontiguousarray(active_slots, dtype=np.int32)
+        P = int(act.size)
+        ea = self._vec(batch["e_amps"], B) if self.load_ele else None
+        ia = self._vec(batch["i_amps"], B) if self.load_ion else None
+        ed = self._mat(batch["e_data"], B) if self.load_ele else None
+        idt = self._mat(batch["i_data"], B) if self.load_ion else None
+        ne_, ni_ = self._mat(batch.get("noise_e"), B), self._mat(batch.get("noise_i"), B)
+        fe_d = self.dev(fe)
+        op = np.ascontiguousarray(opts, dtype=np.float64)
+        assert op.size == 6, "opts = (maxcor, ftol, gtol, maxiter, maxfun, maxls)"
+        if state is None:
+            need = C.c_int64(0)
+            if self.lib.tsff_lbfgs_state_size(B, P, int(op[0]), C.byref(need)) != 0:
+                raise L.TsffError(f"libtsff: no L-BFGS state for B = {B}, {P} leaves, maxcor = {op[0]}")
+            state = torch.zeros(need.value, dtype=torch.float64, device=self.device)
+        else:
+            state = self.dev(state)
+        if info is None or not (torch.is_tensor(info) and info.dtype == torch.int32 and info.is_cuda and info.numel() == 4):
+            info = torch.zeros(4, dtype=torch.int32, device=self.device)
+        hist = torch.empty(max(int(n_evals), 0), dtype=torch.float64, device=self.device) if f_hist else None
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        self._sync_stream()
+        rc = self.lib.tsff_lbfgs_fit(self.h, self._ptr(X), self._ptr(fe_d), self._ptr(ed), self._ptr(idt), self._ptr(ea), self._ptr(ia),
+                                     self._ptr(ne_), self._ptr(ni_), B, w.ctypes.data_as(L.c_double_p),
+                                     act.ctypes.data_as(C.POINTER(C.c_int32)), P, int(n_evals), op.ctypes.data_as(L.c_double_p),
+                                     self._ptr(state), int(state.numel()), self._ptr(hist), self._ptr(info))
+        L.check(self.lib, self.h, rc)
+        return X, state, hist, info
+
+    def lbfgs_info(self, info, state=None) -> dict:
+        """The outcome of :meth:`lbfgs_fit` (one synchronising copy, info and the loss together): status (tsadar_amd.lbfgs: RUNNING .. ABNORMAL), scipy's
+        termination class ``scipy_status`` (None while running), nit, nfev, nskip, and with ``state`` the loss ``f`` of the last
+        accepted iterate."""
+        from . import lbfgs
+
+        torch = self.torch
+        dv = info.to(torch.float64)   # (exact for int32) -- one copy of the counts and the loss
+        if state is not None:
+            dv = torch.cat([dv, state[lbfgs.HDR_F0:lbfgs.HDR_F0 + 1]])
+        host = self.download(dv)
+        v = [int(a) for a in host[:4]]
+        out = dict(status=v[0], scipy_status=lbfgs.SCIPY_STATUS.get(v[0]), nit=v[1], nfev=v[2], nskip=v[3])
+        if state is not None:
+            out["f"] = float(host[4])
+        return out
+
     def array_loss(self, params, batch, fe=None):
         torch = self.torch
         X = self.dev(params).reshape(-1, self.NP)
