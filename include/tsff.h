@@ -25,6 +25,7 @@
  *   LossFunction.h_loss_wrt_params (equinox.filter_hessian) inverse/loss_function.py:170-188  tsff_loss_hess
  *   _1d_adam_loop_ (optax.adam + eqx.apply_updates + best tracking)  inverse/loops.py:59-95        tsff_adam_fit
  *   _1d_scipy_loop_ (scipy L-BFGS-B, bounds=None)                     inverse/loops.py:20-56        tsff_lbfgs_fit
+ *   angular_optax (optax adam / rmsprop + early stop, ARTS decks)    inverse/loops.py:167-275      tsff_angular_fit
  *
  * Conventions
  *   - every array pointer in a *call* is a DEVICE pointer (hipMalloc'ed or a torch CUDA tensor);
@@ -34,7 +35,7 @@
  *   - calls are asynchronous on the handle's stream (tsff_set_stream); the caller synchronises;
  *   - return value 0 = success, negative = error, text via tsff_last_error();
  *   - a refused call (negative return) of tsff_forward, tsff_loss_grad(_packed, _fe), tsff_loss_hess, tsff_array_loss,
- *     tsff_adam_fit and tsff_form_factor(_grad) has enqueued nothing: their arguments, LDS budgets and buffers are checked before the first
+ *     tsff_adam_fit, tsff_angular_fit and tsff_form_factor(_grad) has enqueued nothing: their arguments, LDS budgets and buffers are checked before the first
  *     launch, and tsff_last_launch reports an empty list (other entry points may have enqueued work before a failure);
  *   - a handle is bound to the device that was current at tsff_create; handles are not thread-safe,
  *     the library is re-entrant across handles.
@@ -49,7 +50,7 @@
 extern "C" {
 #endif
 
-#define TSFF_ABI_VERSION 12
+#define TSFF_ABI_VERSION 13
 /* error codes (every entry point returns 0 or one of these; text via tsff_last_error):
  * -1 bad argument, -2 unsupported configuration / option, -3 not a differentiable leaf, -5 HIP runtime error,
  * -22 stale or foreign token of saved projection records (tsff_form_factor_2d_grad),
@@ -381,6 +382,53 @@ int tsff_lbfgs_fit(tsff_handle *h, double *params, const double *fe, const doubl
                    const double *e_amps, const double *i_amps, const double *noise_e, const double *noise_i, int32_t B,
                    const double *weights, const int32_t *active_slots, int32_t n_active, int32_t n_evals, const double *opts,
                    double *state, int64_t n_state, double *f_hist, int32_t *info);
+
+/* The reference's angular loop (angular_optax, inverse/loops.py:167-275) on the device for one ARTS image: n_epochs epochs of
+ *   leaves -> physical parameters (ThomsonParams.__call__) and f_e of the generator -> tsff_form_factor (1-D) or the saving
+ *   tsff_form_factor_2d -> tsff_ats_spectrum with lam, amp1, amp2 read on the device -> loss and its seed (k_ang_loss: the
+ *   masks and loss functionals of LossFunction._angular_value, noise_e added) -> tsff_ats_adjoint, amplitude adjoints kept on
+ *   the device -> tsff_form_factor_grad or tsff_form_factor_2d_grad (saved records; the table adjoint when the table is
+ *   trained) -> chain rule (k_ang_chain: amplitudes, Ti tying, activation, the DLM order by central differences with h = 1e-6,
+ *   the Arbitrary2V VJP) -> optimiser step and early stop (k_ang_opt),
+ * all enqueued on the handle's stream; the call returns once they are enqueued.  Every refusal is checked before the first
+ * launch; the handle's scratch is sized in the first epoch, later epochs allocate nothing and nothing synchronises.  Needs
+ * fe_mode == TSFF_FE_PER_LINEOUT and tsff_ats_setup.
+ *   spec (HOST): the deck and the optimiser, below;
+ *   leaves (device [NP + nv^2 for TSFF_ANG_ARB2V], in/out): the normalised leaves of the one plasma condition, then fval;
+ *   gen_data (device): TSFF_ANG_DLM [nv][31] DLM table | [31] m axis (tsadar_amd.distribution.dlm_table, M_AXIS);
+ *   TSFF_ANG_TABLE2D the constant table [nv][nv]; TSFF_ANG_ARB2V unused;
+ *   e_data, noise_e (device [rows][nJ]), wcol (device [nJ]: blue / red masks over rows x mask count, halved when both are
+ *   fitted), e_amps (device [rows]);
+ *   moments (device [2 n] Adam (mu | nu), [n] RMSProp, n = n_active + nv^2 for ARB2V, else n_active; in/out): the active
+ *   scalar slots in the order of active_slots, then the table;
+ *   best (device [1 + NP + nv^2 for ARB2V], in/out): [best loss | the leaves after the update of the best epoch]; start at 100;
+ *   ctl (device int32 [8], in/out, zeros to start): [0] status (0 running, 1 ended: later epochs change nothing), [1] the
+ *   epoch the fit ended after, [2] g_wait, [3] b_wait (the reference's counters), [4] 1 once a best exists;
+ *   loss_hist (device [n_epochs] or NULL): each epoch's loss (NaN after the end);
+ *   best_hist (device [n_epochs][NP] or NULL): the best scalar leaves after each epoch (save_state), untouched while none exists.
+ * Chunks: epoch0 = the epochs done so far (Adam's bias correction); a fit in chunks is bit for bit one call.
+ * Refusals: a null pointer, a slot out of range or repeated -1, TSFF_P_M outside DLM decks -2, an ion's A slot -3, an unknown
+ * generator, optimiser or loss method, nv outside 4 .. 256 for 2-D tables, too little LDS -2 (TSFF_ERR_LDS for the 1-D adjoint). */
+enum { TSFF_ANG_TABLE2D = 0, TSFF_ANG_DLM = 1, TSFF_ANG_ARB2V = 2 };
+enum { TSFF_ANG_ADAM = 0, TSFF_ANG_RMSPROP = 1 };
+typedef struct {
+  int32_t generator;            /* TSFF_ANG_* */
+  int32_t nv;                   /* velocity points per axis (DLM: the handle's nvx) */
+  int32_t learn_log;            /* TSFF_ANG_ARB2V: fval^2 is -log10 f */
+  int32_t n_active;             /* trained scalar slots */
+  const int32_t *active_slots;  /* HOST [n_active] */
+  int32_t loss_method;          /* TSFF_LOSS_* */
+  double un;                    /* e_norm^2 (l1, l2) */
+  double ud_angle, va_angle;    /* degrees (2-D) */
+  double dvx;                   /* vx[1] - vx[0] of the velocity grid */
+  int32_t method;               /* TSFF_ANG_ADAM or TSFF_ANG_RMSPROP */
+  double lr, b1, b2, eps;       /* Adam: optax's (b1, b2, eps); RMSProp: eps */
+  double decay;                 /* RMSProp */
+  int32_t n_epochs, epoch0;
+} tsff_angular_spec;
+int tsff_angular_fit(tsff_handle *h, const tsff_angular_spec *spec, double *leaves, const double *gen_data, const double *e_data,
+                     const double *noise_e, const double *wcol, const double *e_amps, double *moments, double *best, int32_t *ctl,
+                     double *loss_hist, double *best_hist);
 
 /* Exact per-lineout Hessian of the fit loss: LossFunction._loss_for_hess_fn_ / h_loss_wrt_params
  * (inverse/loss_function.py:170-188, equinox.filter_hessian) for every lineout b, with respect to the normalised leaves

@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtsff.so")
 LIB_PATH = os.environ.get("TSFF_LIBRARY", LIB_PATH)  # A/B experiments: another in-tree build of the same ABI
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 MAX_ION = 4
 NBINS = 1024
 NXI1 = 1024
@@ -29,6 +29,8 @@ OPT_DENOM_MODE = 1
 OPT_LAUNCH_PLAN = 2
 OPT_DLM_BLOCKS = 3
 ERR_LDS = -7  # TSFF_ERR_LDS: more LDS needed than a CU has
+ANG_TABLE2D, ANG_DLM, ANG_ARB2V = range(3)   # tsff_angular_fit's generators
+ANG_ADAM, ANG_RMSPROP = range(2)             # and optimisers
 
 
 def n_params(n_ion: int) -> int:
@@ -98,6 +100,29 @@ class TsffAtsConfig(C.Structure):
     ]
 
 
+class TsffAngularSpec(C.Structure):
+    _fields_ = [
+        ("generator", C.c_int32),
+        ("nv", C.c_int32),
+        ("learn_log", C.c_int32),
+        ("n_active", C.c_int32),
+        ("active_slots", C.POINTER(C.c_int32)),
+        ("loss_method", C.c_int32),
+        ("un", C.c_double),
+        ("ud_angle", C.c_double),
+        ("va_angle", C.c_double),
+        ("dvx", C.c_double),
+        ("method", C.c_int32),
+        ("lr", C.c_double),
+        ("b1", C.c_double),
+        ("b2", C.c_double),
+        ("eps", C.c_double),
+        ("decay", C.c_double),
+        ("n_epochs", C.c_int32),
+        ("epoch0", C.c_int32),
+    ]
+
+
 _vp = C.c_void_p
 _SIGNATURES = {
     "tsff_abi_version": (C.c_int, []),
@@ -132,6 +157,7 @@ _SIGNATURES = {
     "tsff_lbfgs_state_size": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "tsff_lbfgs_fit": (C.c_int, [_vp] + [_vp] * 8 + [C.c_int32, c_double_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, c_double_p,
                                  _vp, C.c_int64, _vp, _vp]),
+    "tsff_angular_fit": (C.c_int, [_vp, C.POINTER(TsffAngularSpec)] + [_vp] * 11),
     "tsff_loss_hess": (C.c_int, [_vp] + [_vp] * 8 + [C.c_int32, c_double_p, C.POINTER(C.c_int32), C.c_int32, _vp, _vp, _vp]),
     "tsff_array_loss": (C.c_int, [_vp] + [_vp] * 8 + [C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "tsff_enable_timing": (C.c_int, [_vp, C.c_int32]),

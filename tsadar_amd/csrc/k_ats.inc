@@ -60,12 +60,14 @@ __global__ __launch_bounds__(kThreads) void k_ats_rownorm(const double* __restri
   for (int j = threadIdx.x; j < npts; j += kThreads) Y[(size_t)r * npts + j] *= sc;
 }
 
-// resolution-unit reduction + amplitude scaling (thomson_diagnostic.py:93-106): one workgroup per output row
+// resolution-unit reduction + amplitude scaling (thomson_diagnostic.py:93-106): one workgroup per output row.  phys (optional):
+// lam, amp1 and amp2 are read from these physical parameters instead of the scalar arguments
 __global__ __launch_bounds__(kThreads) void k_ats_resunit(const double* __restrict__ Y, const double* __restrict__ lam_nm,
                                                           int npts, int lam_step, int ang_step, int row_start,
                                                           const double* __restrict__ e_amps, double lam, double amp1, double amp2,
-                                                          double* __restrict__ out) {
+                                                          const double* __restrict__ phys, double* __restrict__ out) {
   __shared__ double red[8];
+  if (phys) { lam = phys[TSFF_P_LAM]; amp1 = phys[TSFF_P_AMP1]; amp2 = phys[TSFF_P_AMP2]; }   // (tsff_angular_fit: on the device)
   const int R = blockIdx.x, nJ = npts / lam_step;
   const int r0 = (row_start + R) * ang_step;
   double mx = -1e300;
@@ -110,10 +112,11 @@ __global__ __launch_bounds__(kThreads) void k_ats_rowstats(const double* __restr
 __global__ __launch_bounds__(kThreads) void k_ats_resunit_adj(const double* __restrict__ Bm, const double* __restrict__ stats,
                                                               const double* __restrict__ lam_nm, int npts, int lam_step,
                                                               int ang_step, int row_start, const double* __restrict__ e_amps,
-                                                              double lam, double amp1, double amp2,
+                                                              double lam, double amp1, double amp2, const double* __restrict__ phys,
                                                               const double* __restrict__ Ebar, double* __restrict__ Cbar,
                                                               double* __restrict__ ampbar /*[rows][2]*/) {
   __shared__ double red[8];
+  if (phys) { lam = phys[TSFF_P_LAM]; amp1 = phys[TSFF_P_AMP1]; amp2 = phys[TSFF_P_AMP2]; }
   __shared__ double Dl[TSFF_NBINS];
   const int R = blockIdx.x, nJ = npts / lam_step;
   const int r0 = (row_start + R) * ang_step;

@@ -96,6 +96,7 @@ struct tsff_handle {
   tsff::DevBuf act, gradws;         // tsff_loss_grad_packed: active slots on the device, per-lineout gradient workspace
   tsff::DevBuf adam_packed, adam_best;   // tsff_adam_fit: the packed buffer of its steps, the ping-pong pair of best losses
   tsff::DevBuf lbfgs_packed;             // tsff_lbfgs_fit: the packed buffer of its evaluations
+  tsff::DevBuf ang_ws;                   // tsff_angular_fit: parameters, tables, image, seed and adjoints of one epoch
   std::vector<int32_t> act_host;
   tsff::DevBuf hws, hout;          // tsff_loss_hess: hyper-dual spectra of the persistent workgroups, per-task sums
   tsff::DevBuf htmm, Xmm, cstmm, Wmm, Wmm_unused;   // tsff_loss_hess with the DLM order m: second m-derivative tables
@@ -1164,8 +1165,7 @@ int tsff_chi_table(tsff_handle* h, const double* fe, int32_t n, double* W) {
   return 0;
 }
 
-int tsff_form_factor(tsff_handle* h, int32_t feature, const double* phys, const double* fe, int32_t B, double* P) {
-  DevGuard dg__(h);
+static int form_factor_impl(tsff_handle* h, int32_t feature, const double* phys, const double* fe, int32_t B, double* P) {
   if (!h || !phys || !P || B < 1 || feature < 0 || feature > 1) return fail(h, -1, "bad argument");
   if (h->fe_mode == TSFF_FE_DLM) return fail(h, -3, "tsff_form_factor takes explicit distribution functions (fe_mode SHARED or PER_LINEOUT)");
   if (h->fe_mode == TSFF_FE_PER_LINEOUT && !fe) return fail(h, -2, "fe_mode PER_LINEOUT needs fe[B][nvx]");
@@ -1184,14 +1184,23 @@ int tsff_form_factor(tsff_handle* h, int32_t feature, const double* phys, const 
   return 0;
 }
 
-int tsff_form_factor_grad(tsff_handle* h, int32_t feature, const double* phys, const double* fe, int32_t B, const double* Pbar,
-                          double* grad_phys, double* grad_fe) {
+int tsff_form_factor(tsff_handle* h, int32_t feature, const double* phys, const double* fe, int32_t B, double* P) {
   DevGuard dg__(h);
+  return form_factor_impl(h, feature, phys, fe, B, P);
+}
+
+// LDS of k_form_factor_adj (with the f_e adjoint or without)
+static size_t form_factor_grad_smem(const tsff_handle* h, bool grad_fe) {
+  return sizeof(double) * smem_doubles(h->S, 1, grad_fe ? 2 : 0, false);
+}
+
+static int form_factor_grad_impl(tsff_handle* h, int32_t feature, const double* phys, const double* fe, int32_t B, const double* Pbar,
+                                 double* grad_phys, double* grad_fe) {
   if (!h || !phys || !Pbar || !grad_phys || B < 1 || feature < 0 || feature > 1) return fail(h, -1, "bad argument");
   if (h->fe_mode == TSFF_FE_DLM) return fail(h, -3, "tsff_form_factor_grad takes explicit distribution functions (fe_mode SHARED or PER_LINEOUT)");
   if (grad_fe && h->fe_mode != TSFF_FE_PER_LINEOUT) return fail(h, -2, "gradient w.r.t. f_e needs fe_mode == TSFF_FE_PER_LINEOUT");
   if (h->fe_mode == TSFF_FE_PER_LINEOUT && !fe) return fail(h, -2, "fe_mode PER_LINEOUT needs fe[B][nvx]");
-  const size_t smem = sizeof(double) * smem_doubles(h->S, 1, grad_fe ? 2 : 0, false);
+  const size_t smem = form_factor_grad_smem(h, grad_fe != nullptr);
   if (smem > kLdsLimit) return fail(h, TSFF_ERR_LDS, "LDS budget exceeded (%zu B)", smem);
   int rc = ensure_workspace(h, B);
   if (rc) return rc;
@@ -1245,6 +1254,12 @@ int tsff_form_factor_grad(tsff_handle* h, int32_t feature, const double* phys, c
     TSFF_HIP(h, hipGetLastError());
   }
   return 0;
+}
+
+int tsff_form_factor_grad(tsff_handle* h, int32_t feature, const double* phys, const double* fe, int32_t B, const double* Pbar,
+                          double* grad_phys, double* grad_fe) {
+  DevGuard dg__(h);
+  return form_factor_grad_impl(h, feature, phys, fe, B, Pbar, grad_phys, grad_fe);
 }
 
 int tsff_form_factor_2d(tsff_handle* h, int32_t feature, const double* phys, const double* fe2d, int32_t nv,
@@ -1349,6 +1364,19 @@ static int form_factor_2d_impl(tsff_handle* h, int32_t feature, const double* ph
 }
 
 static int table_adjoint_2d(tsff_handle* h, int nv, long npoint, double* grad_fe2d);
+static int form_factor_2d_grad_impl(tsff_handle* h, int32_t feature, const double* phys, const double* fe2d, int32_t nv,
+                                    double ud_angle_deg, double va_angle_deg, int32_t B, int64_t point_begin, int64_t point_end,
+                                    const double* proj, const double* Pbar, double* grad_phys, double* grad_fe2d);
+
+// LDS of k_form_factor_2d_adj for a table of nv x nv (lds: the table fits LDS)
+static size_t form_factor_2d_grad_smem(int nv, bool* lds_out) {
+  auto gsz = [&](int n) { return (2 + (size_t)(n <= 64 ? 4 : (n <= 128 ? 2 : 1))) * n + 2 * (size_t)n + 16 + 96; };
+  constexpr int kGL = TSFF_2D_GROUPS_LDS, kGG = TSFF_2D_GROUPS_L2;
+  const bool lds = sizeof(double) * (kGL * gsz(nv) + (size_t)(nv + 2) * pitch2d(nv, true)) <= kLdsLimit;
+  if (lds_out) *lds_out = lds;
+  const int kG2 = lds ? kGL : kGG;
+  return sizeof(double) * (kG2 * gsz(nv) + (lds ? (size_t)(nv + 2) * pitch2d(nv, true) : 0));
+}
 
 int tsff_form_factor_2d_grad(tsff_handle* h, int32_t feature, const double* phys, const double* fe2d, int32_t nv,
                              double ud_angle_deg, double va_angle_deg, int32_t B, int64_t point_begin, int64_t point_end,
@@ -1357,11 +1385,9 @@ int tsff_form_factor_2d_grad(tsff_handle* h, int32_t feature, const double* phys
   DevGuard dg__(h);
   if (!h || !phys || !fe2d || !Pbar || !grad_phys || B < 1 || feature < 0 || feature > 1 || nv < 4 || nv > 2048)
     return fail(h, -1, "bad argument");
-  const int NLB = kNLB2 + 3 * h->n_ion;
   const long per_lineout = (long)h->S.G * h->S.npts * h->S.n_angles, nall = per_lineout * B;
   const long pb = point_begin, pe = point_end < 0 ? nall : point_end;
   if (pb < 0 || pe > nall || pb > pe) return fail(h, -1, "point range [%ld, %ld) outside [0, %ld]", pb, pe, nall);
-  const long ntotal = pe - pb;   // points of this call (a rank's share; the adjoints are sums over points)
   const double* proj = nullptr;
   if (use_saved) {
     if (saved_token != h->proj_token)
@@ -1373,11 +1399,19 @@ int tsff_form_factor_2d_grad(tsff_handle* h, int32_t feature, const double* phys
       return fail(h, -2, "use_saved: the projection records were made from other inputs (phys / fe2d buffers, drift or flow angle, B)");
     proj = h->proj.as<double>();
   }
-  auto gsz = [&](int n) { return (2 + (size_t)(n <= 64 ? 4 : (n <= 128 ? 2 : 1))) * n + 2 * (size_t)n + 16 + 96; };
+  return form_factor_2d_grad_impl(h, feature, phys, fe2d, nv, ud_angle_deg, va_angle_deg, B, pb, pe, proj, Pbar, grad_phys, grad_fe2d);
+}
+
+// proj: the projection records of the saving forward of exactly these points and inputs (checked by the caller), or nullptr
+static int form_factor_2d_grad_impl(tsff_handle* h, int32_t feature, const double* phys, const double* fe2d, int32_t nv,
+                                    double ud_angle_deg, double va_angle_deg, int32_t B, int64_t pb, int64_t pe,
+                                    const double* proj, const double* Pbar, double* grad_phys, double* grad_fe2d) {
+  const int NLB = kNLB2 + 3 * h->n_ion;
+  const long ntotal = pe - pb;   // points of this call (a rank's share; the adjoints are sums over points)
   constexpr int kGL = TSFF_2D_GROUPS_LDS, kGG = TSFF_2D_GROUPS_L2;
-  const bool lds = sizeof(double) * (kGL * gsz(nv) + (size_t)(nv + 2) * pitch2d(nv, true)) <= kLdsLimit;
+  bool lds = false;
+  const size_t smem = form_factor_2d_grad_smem(nv, &lds);
   const int kG2 = lds ? kGL : kGG;
-  const size_t smem = sizeof(double) * (kG2 * gsz(nv) + (lds ? (size_t)(nv + 2) * pitch2d(nv, true) : 0));
   if (smem > kLdsLimit) return fail(h, -2, "nv = %d needs %zu B of LDS scratch", (int)nv, smem);
   TSFF_ENSURE(h, h->lbacc, (size_t)B * h->S.G * NLB * sizeof(double));
   double* f1bar = nullptr;
@@ -1460,8 +1494,9 @@ int tsff_ats_setup(tsff_handle* h, const tsff_ats_config* c) {
   return 0;
 }
 
-int tsff_ats_spectrum(tsff_handle* h, const double* P, const double* e_amps, double lam, double amp1, double amp2, double* ThryE) {
-  DevGuard dg__(h);
+// phys (device, optional): lam, amp1 and amp2 read from these physical parameters on the device instead of the scalars
+static int ats_spectrum_impl(tsff_handle* h, const double* P, const double* e_amps, double lam, double amp1, double amp2,
+                             const double* phys, double* ThryE) {
   if (!h || !P || !ThryE || !e_amps) return fail(h, -1, "bad argument");
   if (h->ats_npx == 0) return fail(h, -2, "tsff_ats_setup has not been called");
   const int npts = h->S.npts, npx = h->ats_npx;
@@ -1475,15 +1510,20 @@ int tsff_ats_spectrum(tsff_handle* h, const double* P, const double* e_amps, dou
   TSFF_LAUNCH0(h, k_ats_conv, grid, block, 0, h->stream, A, h->ats_tl.as<double>(), h->ats_ntl, h->ats_offl, 0, npx, npts, Bm);
   TSFF_LAUNCH0(h, k_ats_rownorm, dim3(npx), block, 0, h->stream, M, Bm, npts);
   TSFF_LAUNCH0(h, k_ats_resunit, dim3(h->ats_row_end - h->ats_row_start), block, 0, h->stream, Bm, h->ats_lam.as<double>(),
-                     npts, h->ats_lam_step, h->ats_ang_step, h->ats_row_start, e_amps, lam, amp1, amp2, ThryE);
+                     npts, h->ats_lam_step, h->ats_ang_step, h->ats_row_start, e_amps, lam, amp1, amp2, phys, ThryE);
   TSFF_HIP(h, hipGetLastError());
   return 0;
 }
 
-int tsff_ats_adjoint(tsff_handle* h, const double* P, const double* e_amps, double lam, double amp1, double amp2,
-                     const double* Ebar, double* Pbar, double* amp_bar) {
+int tsff_ats_spectrum(tsff_handle* h, const double* P, const double* e_amps, double lam, double amp1, double amp2, double* ThryE) {
   DevGuard dg__(h);
-  if (!h || !P || !e_amps || !Ebar || !Pbar || !amp_bar) return fail(h, -1, "bad argument");
+  return ats_spectrum_impl(h, P, e_amps, lam, amp1, amp2, nullptr, ThryE);
+}
+
+// the reverse chain; the amplitude adjoints stay on the device, per output row: *ampb_out = [rows][2] (handle scratch)
+static int ats_adjoint_impl(tsff_handle* h, const double* P, const double* e_amps, double lam, double amp1, double amp2,
+                            const double* phys, const double* Ebar, double* Pbar, double** ampb_out) {
+  if (!h || !P || !e_amps || !Ebar || !Pbar) return fail(h, -1, "bad argument");
   if (h->ats_npx == 0) return fail(h, -2, "tsff_ats_setup has not been called");
   const int npts = h->S.npts, npx = h->ats_npx, rows = h->ats_row_end - h->ats_row_start;
   if (npts / h->ats_lam_step > TSFF_NBINS) return fail(h, -2, "more than %d wavelength resolution units per row", TSFF_NBINS);
@@ -1508,7 +1548,7 @@ int tsff_ats_adjoint(tsff_handle* h, const double* P, const double* e_amps, doub
   // reverse
   TSFF_HIP(h, hipMemsetAsync(Cb, 0, img, h->stream));
   TSFF_LAUNCH0(h, k_ats_resunit_adj, dim3(rows), block, 0, h->stream, Bm, stats, h->ats_lam.as<double>(), npts, h->ats_lam_step,
-                     h->ats_ang_step, h->ats_row_start, e_amps, lam, amp1, amp2, Ebar, Cb, ampb);
+                     h->ats_ang_step, h->ats_row_start, e_amps, lam, amp1, amp2, phys, Ebar, Cb, ampb);
   TSFF_LAUNCH0(h, k_ats_rownorm_adj, dim3(npx), block, 0, h->stream, Bm, stats, npts, Cb, Db);              // Cb -> Bmbar, Db = Mbar one-hots
   TSFF_LAUNCH0(h, k_ats_conv_adj, grid, block, 0, h->stream, Cb, h->ats_tl.as<double>(), h->ats_ntl, h->ats_offl, 0, npx, npts, 0, A);   // A = Abar
   TSFF_LAUNCH0(h, k_ats_conv_adj, grid, block, 0, h->stream, A, h->ats_ta.as<double>(), h->ats_nta, h->ats_offa, 1, npx, npts, 1, Db);  // Db += conv^T
@@ -1516,6 +1556,18 @@ int tsff_ats_adjoint(tsff_handle* h, const double* P, const double* e_amps, doub
   TSFF_LAUNCH0(h, k_ats_weights_adj, wgrid, block, 0, h->stream, Db, h->ats_w.as<double>(), h->S.filt, h->S.G, npts, h->S.n_angles,
                      npx, Pbar);
   TSFF_HIP(h, hipGetLastError());
+  *ampb_out = ampb;
+  return 0;
+}
+
+int tsff_ats_adjoint(tsff_handle* h, const double* P, const double* e_amps, double lam, double amp1, double amp2,
+                     const double* Ebar, double* Pbar, double* amp_bar) {
+  DevGuard dg__(h);
+  if (!amp_bar) return fail(h, -1, "bad argument");
+  double* ampb = nullptr;
+  int rc = ats_adjoint_impl(h, P, e_amps, lam, amp1, amp2, nullptr, Ebar, Pbar, &ampb);
+  if (rc) return rc;
+  const int rows = h->ats_row_end - h->ats_row_start;
   // amp adjoints: sum over the rows (host: a few hundred numbers)
   std::vector<double> hb((size_t)rows * 2);
   TSFF_HIP(h, hipMemcpyAsync(hb.data(), ampb, hb.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -1751,6 +1803,120 @@ int tsff_adam_fit(tsff_handle* h, double* params, const double* fe, const double
                  h->act.as<int>(), (int)n_active, (int)B, h->S.NP, params, mu, nu, b1, omb1, b2, omb2, neg_lr, c1, c2, eps,
                  loss_hist ? loss_hist + t : nullptr, (const double*)(bl + (t & 1)), bl + ((t + 1) & 1),
                  t == n_steps - 1 ? best : nullptr, best + 1);
+    TSFF_HIP(h, hipGetLastError());
+  }
+  return 0;
+}
+
+// the angular (ARTS) fit on the device (k_angular.inc): n_epochs x (leaves -> physical parameters and f_e, form factor, ATS
+// chain, loss and seed, ATS adjoint, form-factor adjoint, chain rule, optimiser + early stop), all enqueued on the handle's
+// stream.  Every refusal is checked before the first launch; the handle's scratch is sized by the first epoch, so the later
+// ones allocate nothing, and nothing synchronises.
+int tsff_angular_fit(tsff_handle* h, const tsff_angular_spec* sp, double* leaves, const double* gen_data, const double* e_data,
+                     const double* noise_e, const double* wcol, const double* e_amps, double* moments, double* best, int32_t* ctl,
+                     double* loss_hist, double* best_hist) {
+  DevGuard dg__(h);
+  if (!h) return -1;
+  if (!sp || !leaves || !e_data || !noise_e || !wcol || !e_amps || !moments || !best || !ctl || sp->n_epochs < 0 || sp->epoch0 < 0 ||
+      (int64_t)sp->epoch0 + sp->n_epochs > 0x7fffffffLL || sp->n_active < 0 || sp->n_active > h->S.NP ||
+      (sp->n_active > 0 && !sp->active_slots))
+    return fail(h, -1, "bad argument");
+  if (h->ats_npx == 0) return fail(h, -2, "tsff_ats_setup has not been called");
+  if (h->fe_mode != TSFF_FE_PER_LINEOUT) return fail(h, -2, "tsff_angular_fit needs fe_mode == TSFF_FE_PER_LINEOUT");
+  const int gen = sp->generator, nv = sp->nv;
+  if (gen != TSFF_ANG_TABLE2D && gen != TSFF_ANG_DLM && gen != TSFF_ANG_ARB2V) return fail(h, -2, "unknown generator %d", gen);
+  const bool two_d = gen != TSFF_ANG_DLM;
+  if (gen == TSFF_ANG_DLM && nv != h->S.nvx) return fail(h, -1, "DLM: nv must be the handle's nvx (%d)", h->S.nvx);
+  if (two_d && (nv < 4 || nv > 256)) return fail(h, -2, "2-D tables of nv = 4 .. 256 (the fit keeps the projection records)");
+  if (gen != TSFF_ANG_ARB2V && !gen_data) return fail(h, -1, "gen_data missing");
+  if (sp->method != TSFF_ANG_ADAM && sp->method != TSFF_ANG_RMSPROP) return fail(h, -2, "unknown optimiser %d", sp->method);
+  if (sp->loss_method < 0 || sp->loss_method > 3) return fail(h, -2, "unknown loss method %d", sp->loss_method);
+  uint8_t gm[kNP_MAX] = {};
+  for (int k = 0; k < sp->n_active; ++k) {
+    const int s = sp->active_slots[k];
+    if (s < 0 || s >= h->S.NP) return fail(h, -1, "active slot %d out of range", s);
+    if (gm[s]) return fail(h, -1, "active slot %d repeated", s);
+    gm[s] = 1;
+  }
+  if (gm[TSFF_P_M] && gen != TSFF_ANG_DLM) return fail(h, -2, "the DLM order m is a leaf of DLM decks only");
+  for (int i = 0; i < h->n_ion; ++i)
+    if (gm[TSFF_P_ION0 + 4 * i + TSFF_ION_A]) return fail(h, -3, "A is not a differentiable leaf (ts_params.py:296)");
+  const long n_table = gen == TSFF_ANG_ARB2V ? (long)nv * nv : 0;
+  const long n = sp->n_active + n_table;
+  if (n < 1) return fail(h, -1, "nothing to train");
+  const int npts = h->S.npts, NA = h->S.n_angles, G = h->S.G, NP = h->S.NP;
+  const int rows = h->ats_row_end - h->ats_row_start, nJ = npts / h->ats_lam_step;
+  if (nJ > TSFF_NBINS) return fail(h, -2, "more than %d wavelength resolution units per row", TSFF_NBINS);
+  const bool want_dm = gm[TSFF_P_M] != 0, train_table = n_table > 0;
+  // the LDS budgets of the form-factor kernels (their entry points would refuse in the first epoch)
+  if (two_d) {
+    constexpr int kGL = TSFF_2D_GROUPS_LDS, kGG = TSFF_2D_GROUPS_L2;
+    const bool lds = sizeof(double) * smem2d_doubles(nv, true, kGL) <= kLdsLimit;
+    if (sizeof(double) * smem2d_doubles(nv, lds, lds ? kGL : kGG) > kLdsLimit || form_factor_2d_grad_smem(nv, nullptr) > kLdsLimit)
+      return fail(h, -2, "nv = %d needs more LDS than a CU has", nv);
+  } else if (form_factor_grad_smem(h, want_dm) > kLdsLimit) {
+    return fail(h, TSFF_ERR_LDS, "LDS budget exceeded (%zu B)", form_factor_grad_smem(h, want_dm));
+  }
+  if (sp->n_epochs == 0) return 0;
+  // scratch: phys | fe | dfe (2 nv) | aux | P | ThryE | Ebar | Pbar | gphys | gfe | grad | loss
+  const size_t nP = (size_t)G * npts * NA, nimg = (size_t)rows * nJ;
+  const size_t nfe = two_d ? (size_t)nv * nv : (size_t)nv;
+  size_t off = 0;
+  auto take = [&](size_t k) { const size_t o = off; off += (k + 1) & ~(size_t)1; return o; };
+  const size_t o_phys = take(NP + 1), o_fe = take(nfe), o_dfe = take(2 * (size_t)nv), o_aux = take(4), o_P = take(nP),
+               o_E = take(nimg), o_Eb = take(nimg), o_Pb = take(nP), o_gp = take(NP), o_gfe = take(nfe), o_grad = take(n),
+               o_loss = take(1), o_part = take(kAngLossBlocks);
+  TSFF_ENSURE(h, h->ang_ws, off * sizeof(double));
+  int rc = 0;
+  if (sp->n_active > 0 && (rc = upload_slots(h, sp->active_slots, sp->n_active))) return rc;
+  double* ws = h->ang_ws.as<double>();
+  double *phys = ws + o_phys, *fe = ws + o_fe, *dfe = ws + o_dfe, *aux = ws + o_aux, *P = ws + o_P, *E = ws + o_E, *Eb = ws + o_Eb,
+         *Pb = ws + o_Pb, *gphys = ws + o_gp, *gfe = ws + o_gfe, *grad = ws + o_grad, *lossv = ws + o_loss,
+         *lpart = ws + o_part;
+  const double* table = gen == TSFF_ANG_TABLE2D ? gen_data : fe;
+  const double dv2 = sp->dvx * sp->dvx, cvjp = 1.0 / dv2, ln10 = std::log(10.0);
+  // the optimiser's scalars as tree.Adam / tree.RMSProp compute them in Python (1 - b1, -lr, 1 - b1**count with glibc pow)
+  const bool adam = sp->method == TSFF_ANG_ADAM;
+  const double b1 = sp->b1, b2 = adam ? sp->b2 : sp->decay, omb1 = 1.0 - b1, omb2 = 1.0 - b2, neg_lr = -sp->lr;
+  const int* act = sp->n_active > 0 ? h->act.as<int>() : nullptr;
+  const long nall = (long)nP;
+  const unsigned nloss = (unsigned)std::min<long>(kAngLossBlocks, ((long)nimg + kThreads - 1) / kThreads);   // (a fixed partition)
+  for (int t = 0; t < sp->n_epochs; ++t) {
+    const int epoch = sp->epoch0 + t;
+    rc = with_ion<TSFF_MAX_ION>(h->n_ion, [&](auto N) {
+      TSFF_LAUNCH(h, k_ang_leaves, (N.value), dim3(1), dim3(kThreads), 0, h->stream, h->S, (const double*)leaves, gen,
+                  (int)sp->learn_log, nv, gen_data, sp->dvx, dv2, (int)want_dm, phys, fe, dfe, aux);
+      return 0;
+    });
+    if (rc) return rc;
+    TSFF_HIP(h, hipGetLastError());
+    rc = two_d ? form_factor_2d_impl(h, 0, phys, table, nv, 1, sp->ud_angle, sp->va_angle, 1, 0, -1, P, true)
+               : form_factor_impl(h, 0, phys, fe, 1, P);
+    if (rc) return rc;
+    if ((rc = ats_spectrum_impl(h, P, e_amps, 0.0, 0.0, 0.0, phys, E))) return rc;
+    TSFF_LAUNCH0(h, k_ang_loss, dim3(nloss), dim3(kThreads), 0, h->stream, (const double*)E, noise_e, e_data, wcol, rows, nJ,
+                 (int)sp->loss_method, sp->un, Eb, lpart);
+    TSFF_LAUNCH0(h, k_ang_loss_sum, dim3(1), dim3(kThreads), 0, h->stream, (const double*)lpart, (int)nloss, lossv);
+    TSFF_HIP(h, hipGetLastError());
+    double* ampb = nullptr;
+    if ((rc = ats_adjoint_impl(h, P, e_amps, 0.0, 0.0, 0.0, phys, Eb, Pb, &ampb))) return rc;
+    rc = two_d ? form_factor_2d_grad_impl(h, 0, phys, table, nv, sp->ud_angle, sp->va_angle, 1, 0, nall, h->proj.as<double>(), Pb,
+                                          gphys, train_table ? gfe : nullptr)
+               : form_factor_grad_impl(h, 0, phys, fe, 1, Pb, gphys, want_dm ? gfe : nullptr);
+    if (rc) return rc;
+    rc = with_ion<TSFF_MAX_ION>(h->n_ion, [&](auto N) {
+      TSFF_LAUNCH(h, k_ang_chain, (N.value), dim3(1), dim3(kThreads), 0, h->stream, h->S, (const double*)leaves, (const double*)gphys,
+                  (const double*)ampb, rows, (const double*)gfe, want_dm ? (const double*)dfe : nullptr, nv, (int)train_table,
+                  (int)sp->learn_log, nv, (const double*)aux, cvjp, ln10, act, (int)sp->n_active, grad);
+      return 0;
+    });
+    if (rc) return rc;
+    TSFF_HIP(h, hipGetLastError());
+    const double count = (double)epoch + 1;
+    const double c1 = 1.0 - std::pow(b1, count), c2 = 1.0 - std::pow(b2, count);
+    TSFF_LAUNCH0(h, k_ang_opt, dim3(1), dim3(kThreads), 0, h->stream, (const double*)lossv, (const double*)grad, act, (int)sp->n_active,
+                 NP, n_table, leaves, moments, adam ? 0 : 1, b1, omb1, b2, omb2, neg_lr, c1, c2, sp->eps, ctl, best, epoch,
+                 loss_hist ? loss_hist + t : nullptr, best_hist ? best_hist + (size_t)t * NP : nullptr);
     TSFF_HIP(h, hipGetLastError());
   }
   return 0;

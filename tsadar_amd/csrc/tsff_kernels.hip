@@ -12,6 +12,7 @@
 //   k_hess_pairs   a16                   : exact per-lineout Hessian of the fit loss (hyper-dual forward mode, k_hessian.inc)
 //   k_adam_step    loops.py:59-95        : one Adam step + best tracking on the packed loss and gradient (tsff_adam_fit, k_adam.inc)
 //   k_lbfgs_step   loops.py:20-56        : one evaluation's step of unbounded L-BFGS-B on the packed loss and gradient (tsff_lbfgs_fit)
+//   k_ang_*        loops.py:167-275      : the angular fit's generator, loss and seed, chain rule and optimiser step (tsff_angular_fit)
 #include "tsff_device.h"
 
 namespace tsff {
@@ -98,6 +99,7 @@ constexpr int kFusedMaxIon = 2;  // k_spectrum_fused is instantiated for n_ion <
 #include "k_hessian.inc"
 #include "k_adam.inc"
 #include "k_lbfgs.inc"
+#include "k_angular.inc"
 
 }  // namespace tsff
 

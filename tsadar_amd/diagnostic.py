@@ -63,17 +63,7 @@ class ThomsonScatteringDiagnostic:
             raise NotImplementedError("angular spectra are computed for one plasma condition (no vmap in the reference)")
         if cfg["other"]["PhysParams"]["norm"] > 0:
             raise NotImplementedError("PhysParams.norm > 0 is not built for angular spectra")
-        e_data = np.asarray(batch["e_data"])
-        lam_step = round(eng.npts / e_data.shape[1])
-        n_px = np.asarray(sas["weights"]).shape[0]
-        ang_step = round(n_px / cfg["other"]["CCDsize"][0])
-        key = (lam_step, ang_step)
-        if getattr(eng, "_ats_key", None) != key:
-            wid = cfg["other"]["PhysParams"]["widIRF"]
-            eng.ats_setup(sas["weights"], sas["angAxis"], wid["spect_FWHM_ele"] / 2.3548, wid["ang_FWHM_ele"] / 2.3548,
-                          lam_step, ang_step, cfg["data"]["lineouts"]["start"],
-                          min(cfg["data"]["lineouts"]["end"], n_px // ang_step), self.irf_cutoff_sigmas)
-            eng._ats_key = key
+        lam_step = self._ats_prepare(eng, batch)
         phys = ts_params.physical_matrix()
         fe2 = fe1 = None
         if eng.fe_dim == 2:
@@ -92,13 +82,33 @@ class ThomsonScatteringDiagnostic:
         rows = eng._ats_shape[0]
         e_amps = np.broadcast_to(np.asarray(batch["e_amps"], dtype=np.float64).reshape(-1, 1), (rows, 1))
         E_dev = eng.ats_spectrum(P[0], e_amps, p[L.P_LAM], p[L.P_AMP1], p[L.P_AMP2])
-        lamE = np.mean(wavelength_axis_nm(cfg["other"]["lamrangE"], eng.npts).reshape(-1, lam_step), axis=1)
+        lamE = self._ats_lam_axis(eng, lam_step)
         # what the adjoint (LossFunction._vg_angular) needs again: the device-resident P and image, the table, the parameters
         self._angular_ctx = dict(P=P, phys=phys, fe2=fe2, fe1=fe1, e_amps=e_amps, E_dev=E_dev, lamE=lamE)
         if not to_host:   # (the fit loop keeps the image on the device: the loss and its seed are evaluated there)
             return None, None, lamE, []
         E = E_dev.cpu().numpy() + np.asarray(batch["noise_e"])
         return E, 0 + np.asarray(batch["noise_i"]), lamE, []
+
+    def _ats_prepare(self, eng: Engine, batch: Dict) -> int:
+        """tsff_ats_setup for the image geometry of ``batch`` (once per pair of resolution units) -> the wavelength step."""
+        cfg, sas = self.cfg, self.scattering_angles
+        e_data = np.asarray(batch["e_data"])
+        lam_step = round(eng.npts / e_data.shape[1])
+        n_px = np.asarray(sas["weights"]).shape[0]
+        ang_step = round(n_px / cfg["other"]["CCDsize"][0])
+        key = (lam_step, ang_step)
+        if getattr(eng, "_ats_key", None) != key:
+            wid = cfg["other"]["PhysParams"]["widIRF"]
+            eng.ats_setup(sas["weights"], sas["angAxis"], wid["spect_FWHM_ele"] / 2.3548, wid["ang_FWHM_ele"] / 2.3548,
+                          lam_step, ang_step, cfg["data"]["lineouts"]["start"],
+                          min(cfg["data"]["lineouts"]["end"], n_px // ang_step), self.irf_cutoff_sigmas)
+            eng._ats_key = key
+        return lam_step
+
+    def _ats_lam_axis(self, eng: Engine, lam_step: int) -> np.ndarray:
+        """The wavelength axis of the resolution units (the blue / red masks are taken on it)."""
+        return np.mean(wavelength_axis_nm(self.cfg["other"]["lamrangE"], eng.npts).reshape(-1, lam_step), axis=1)
 
     def spectrum_breakdown(self, ts_params, batch):
         raise NotImplementedError("spectrum_breakdown (post-processing plots) is outside the hot path")

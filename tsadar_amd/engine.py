@@ -706,6 +706,44 @@ class Engine:
         L.check(self.lib, self.h, rc)
         return X, state, hist, best
 
+    def angular_fit(self, leaves, spec: dict, data: dict, n_epochs, state=None, epoch0=0, loss_hist=True, best_hist=False):
+        """tsff_angular_fit: ``n_epochs`` epochs of the angular (ARTS) fit on the device, enqueued at once; nothing is synchronised
+        (call ats_setup first).  ``leaves`` [NP (+ nv^2 of a trained Arbitrary2V table)]: the normalised leaves.  ``spec``: the
+        fields of tsff_angular_spec (generator, nv, learn_log, active_slots, loss_method, un, ud_angle, va_angle, dvx, method,
+        lr, b1, b2, eps, decay).  ``data``: device tensors gen_data, e_data and noise_e [rows, nJ], wcol [nJ], e_amps [rows].
+        -> (leaves, state = (moments, best, ctl), loss_hist [n_epochs] or None, best_hist [n_epochs, NP] (NaN rows: no best yet)
+        or None) as CUDA tensors;
+        ``leaves`` and ``state`` are updated in place when they are CUDA tensors already (pass the returned ones to the next
+        chunk, with ``epoch0`` the epochs done so far).  ``state=None`` starts a fit: zero moments, best = [100 | leaves]
+        (angular_optax's best_loss = 100.0), ctl zeros."""
+        torch = self.torch
+        x = self.dev(leaves).reshape(-1)
+        act = np.ascontiguousarray(spec.get("active_slots", ()), dtype=np.int32)
+        n = int(act.size) + int(x.numel()) - self.NP
+        adam = spec["method"] == L.ANG_ADAM
+        if state is None:
+            best = torch.cat([torch.full((1,), 100.0, dtype=torch.float64, device=self.device), x])
+            state = (torch.zeros((2 if adam else 1) * n, dtype=torch.float64, device=self.device), best,
+                     torch.zeros(8, dtype=torch.int32, device=self.device))
+        mom, best, ctl = state
+        assert mom.numel() == (2 if adam else 1) * n and best.numel() == 1 + x.numel() and ctl.dtype == torch.int32
+        hist = torch.empty(max(int(n_epochs), 0), dtype=torch.float64, device=self.device) if loss_hist else None
+        bh = torch.full((max(int(n_epochs), 0), self.NP), float("nan"), dtype=torch.float64, device=self.device) if best_hist else None
+        c = L.TsffAngularSpec()
+        c.generator, c.nv, c.learn_log = int(spec["generator"]), int(spec["nv"]), int(bool(spec.get("learn_log", False)))
+        c.n_active, c.active_slots = int(act.size), act.ctypes.data_as(C.POINTER(C.c_int32))
+        c.loss_method, c.un = int(spec["loss_method"]), float(spec["un"])
+        c.ud_angle, c.va_angle, c.dvx = float(spec.get("ud_angle", 0.0)), float(spec.get("va_angle", 0.0)), float(spec["dvx"])
+        c.method = int(spec["method"])
+        c.lr, c.b1, c.b2, c.eps, c.decay = (float(spec.get(k, 0.0)) for k in ("lr", "b1", "b2", "eps", "decay"))
+        c.n_epochs, c.epoch0 = int(n_epochs), int(epoch0)
+        self._sync_stream()
+        rc = self.lib.tsff_angular_fit(self.h, C.byref(c), self._ptr(x), self._ptr(data.get("gen_data")), self._ptr(data["e_data"]),
+                                       self._ptr(data["noise_e"]), self._ptr(data["wcol"]), self._ptr(data["e_amps"]), self._ptr(mom),
+                                       self._ptr(best), self._ptr(ctl), self._ptr(hist), self._ptr(bh))
+        L.check(self.lib, self.h, rc)
+        return x, (mom, best, ctl), hist, bh
+
     def lbfgs_fit(self, params, batch, weights, active_slots, n_evals, opts=(10, 2.220446049250313e-09, 1e-5, 15000, 15000, 20),
                   state=None, f_hist=True, info=None, fe=None):
         """tsff_lbfgs_fit: ``n_evals`` evaluations of unbounded L-BFGS-B on the active leaves, enqueued at once; nothing is

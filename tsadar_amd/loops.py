@@ -1,5 +1,6 @@
-"""Drop-ins for the reference's 1-D loops, run on the device: ``_1d_adam_loop_`` (tsadar/inverse/loops.py:59-95) as
-``adam_loop`` and the default ``_1d_scipy_loop_`` (loops.py:20-56, scipy L-BFGS-B) as ``lbfgs_loop``.
+"""Drop-ins for the reference's fit loops, run on the device: ``_1d_adam_loop_`` (tsadar/inverse/loops.py:59-95) as
+``adam_loop``, the default ``_1d_scipy_loop_`` (loops.py:20-56, scipy L-BFGS-B) as ``lbfgs_loop`` and the angular (ARTS)
+``angular_optax`` (loops.py:167-275) as ``angular_loop``.
 
 The reference alternates ``LossFunction.vg_loss`` (spectra and gradient to the host) with ``optax.adam`` and
 ``eqx.apply_updates`` on the host, once per epoch.  ``adam_loop`` enqueues the whole fit at once through
@@ -142,3 +143,148 @@ def lbfgs_loop(config: Dict, loss_fn, previous_weights: Optional[ThomsonParams],
     out = ts_params.copy()
     out.X = eng.download(Xd).reshape(B, -1).copy()
     return res["f"], out
+
+
+ANGULAR_CHUNK = 16   # epochs per enqueued chunk of angular_loop (at most this many minus one run after the early stop)
+RMSPROP_DECAY, RMSPROP_EPS = 0.9, 1e-8   # optax.rmsprop's defaults
+
+
+def angular_loop(config: Dict, all_data: Dict, sa: Dict, chunk: Optional[int] = None, progress=None, states: Optional[Dict] = None,
+                 info: Optional[Dict] = None, distributed: bool = False):
+    """``angular_optax(config, all_data, sa)`` -> (best_weights, epoch_loss, loss_fn), run on the device by
+    ``Engine.angular_fit`` (tsff_angular_fit, k_angular.inc).
+
+    The same config mutations (``batch_size = 1``, lineout start / end over ``ang_res_unit``), the same ``batch1`` slice of
+    ``all_data``, ``LossFunction(config, sa, batch1)`` and ``ThomsonParams(..., num_params=1, batch=False, activate=True)``;
+    ``optimizer.method`` "adam" (tree.Adam) or "rmsprop" (tree.RMSProp, optax's defaults), ``num_epochs`` epochs at
+    ``learning_rate``.  The early stop is the reference's as written: best_loss starts at 100.0 and best_weights at ``{}``
+    (returned as is when no epoch improves); an epoch whose loss is below the best takes the updated iterate as the best; an
+    improvement below 1e-6 counts towards the stop (after more than 5), a larger one resets the counters; the branch "stop on
+    increase" never runs.  ``epoch_loss`` is the LAST epoch's loss.
+
+    ``chunk``: epochs per enqueued chunk (default 16); after each chunk the loop synchronises once, stops once the fit has
+    ended, and reports to ``progress`` -- a tqdm-like object (``set_description``) or a callable ``progress(epochs_done,
+    last_loss)``.  ``states``: with ``save_state``, receives ``best_weights.get_unnormed_params()`` at the reference's epochs
+    (every ``save_state_freq``-th epoch that does not end the fit; an epoch before any best exists, where the reference would
+    fail on ``{}``, is skipped); writing the file and logging stay with the caller.  ``info``: a dict that receives
+    ``loss_hist`` (the loss of every epoch run, NaN after the end: the reference's per-epoch "epoch loss" metric),
+    ``stopped_after`` (the epoch of the early stop, or None) and ``leaves`` (the final normalised leaves, then fval).
+
+    Not built (NotImplementedError, raised before any device work): methods other than adam and rmsprop, multiplexed decks
+    (``shotnum`` a list), ``distributed=True``, trainable SphericalHarmonics generators, 1-D decks other than DLM1V."""
+    from . import _lib as L
+    from . import distribution as Dist
+    from .loss_function import LossFunction
+
+    opt = config["optimizer"]
+    method = opt["method"]
+    if method not in ("adam", "rmsprop"):
+        raise NotImplementedError(f"angular_loop: method {method!r} -- only adam and rmsprop are built on the device")
+    if isinstance(config["data"].get("shotnum"), list):
+        raise NotImplementedError("angular_loop: multiplexed decks (shotnum a list) are not built")
+    if distributed:
+        raise NotImplementedError("angular_loop: distributed=True is not built")
+    fecfg = config["parameters"]["electron"]["fe"]
+    dim = int(fecfg.get("dim", 1))
+    if dim == 2 and "sph" in str(fecfg["type"]).casefold() and fecfg.get("active", False):
+        raise NotImplementedError("angular_loop: a trainable SphericalHarmonics generator is not built on the device (use the host "
+                                  "loop over LossFunction.vg_loss)")
+    if dim == 1 and str(fecfg.get("type", "dlm")).casefold() != "dlm":
+        raise NotImplementedError(f"angular_loop: 1-D f_e of type {fecfg.get('type')!r} -- only DLM1V is built")
+
+    # loops.py:197-227, as written
+    config["optimizer"]["batch_size"] = 1
+    lo = config["data"]["lineouts"]
+    lo["start"] = int(lo["start"] / config["other"]["ang_res_unit"])
+    lo["end"] = int(lo["end"] / config["other"]["ang_res_unit"])
+    a, b = lo["start"], lo["end"]
+    batch1 = {"e_data": all_data["e_data"][a:b, :], "e_amps": all_data["e_amps"][a:b, :], "i_data": all_data["i_data"],
+              "i_amps": all_data["i_amps"], "noise_e": all_data["noiseE"][a:b, :], "noise_i": all_data["noiseI"][a:b, :]}
+    loss_fn = LossFunction(config, sa, batch1)
+    ts_params = ThomsonParams(config["parameters"], num_params=1, batch=False, activate=True)
+    sm = ts_params.slots
+    if sm.gen2d_active or ts_params.fval is not None or (dim == 1 and not sm.has_m):
+        raise NotImplementedError("angular_loop: this distribution function is not built on the device")
+    diff, _ = tree.partition(ts_params, tree.get_filter_spec(config["parameters"], ts_params))
+    act = [s for _, s in diff.slots if s >= 0]
+    train_table = any(s == tree.FVAL2D_SLOT for _, s in diff.slots)
+
+    eng = loss_fn.ts_diag.engine(ts_params.activate)
+    torch = eng.torch
+    diag = loss_fn.ts_diag
+    lam_step = diag._ats_prepare(eng, batch1)
+    rows, nJ = eng._ats_shape
+    wcol = loss_fn._angular_wcol(diag._ats_lam_axis(eng, lam_step), rows)
+    nvx = int(fecfg["nvx"])
+    vx = Dist.velocity_grid(nvx)
+    gen = config["parameters"]["general"]
+    leaves = ts_params.X[0].copy()
+    spec = dict(nv=nvx, active_slots=act, loss_method=L.LOSS_METHODS[opt["loss_method"]], un=loss_fn.e_norm**2,
+                dvx=vx[1] - vx[0], lr=float(opt["learning_rate"]))
+    if method == "adam":
+        spec.update(method=L.ANG_ADAM, b1=ADAM_B1, b2=ADAM_B2, eps=ADAM_EPS)
+    else:
+        spec.update(method=L.ANG_RMSPROP, decay=RMSPROP_DECAY, eps=RMSPROP_EPS)
+    if dim == 1:
+        spec["generator"] = L.ANG_DLM
+        gen_data = np.concatenate([Dist.dlm_table(nvx).ravel(), Dist.M_AXIS])
+    else:
+        spec.update(ud_angle=gen["ud"]["angle"], va_angle=gen["Va"]["angle"])
+        if train_table:
+            spec.update(generator=L.ANG_ARB2V, learn_log=ts_params.learn_log)
+            leaves = np.concatenate([leaves, ts_params.fval2d.ravel()])
+            gen_data = None
+        else:   # a constant table (SphericalHarmonics or Arbitrary2V not trained), built once on the host
+            spec["generator"] = L.ANG_TABLE2D
+            gen_data = np.ascontiguousarray(ts_params()["electron"]["fe"], dtype=np.float64)
+    img = lambda v: eng.dev(np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (rows, nJ))))
+    data = dict(gen_data=eng.dev(gen_data), e_data=img(batch1["e_data"]), noise_e=img(np.atleast_1d(batch1["noise_e"])),
+                wcol=eng.dev(wcol), e_amps=eng.dev(np.broadcast_to(np.asarray(batch1["e_amps"], dtype=np.float64).reshape(-1, 1),
+                                                                   (rows, 1)).reshape(-1)))
+
+    n_epochs = int(opt["num_epochs"])
+    save = bool(opt.get("save_state", False))
+    step = max(1, int(chunk)) if chunk else ANGULAR_CHUNK
+    x, state, done = eng.dev(leaves), None, 0
+    hists, bhs, ended = [], [], False
+    while done < n_epochs and not ended:
+        k = min(step, n_epochs - done)
+        x, state, hist, bh = eng.angular_fit(x, spec, data, k, state=state, epoch0=done, best_hist=save)
+        hists.append(hist)
+        if save:
+            bhs.append(bh)
+        done += k
+        host = eng.download(torch.cat([state[2][:2].to(torch.float64), hist]))   # the chunk's one synchronisation
+        ended = host[0] != 0
+        if progress is not None:
+            last = float(host[2 + int(host[1]) - (done - k)] if ended else host[-1])   # (an ended fit ended in this chunk)
+            if hasattr(progress, "set_description"):
+                progress.set_description(f"Loss {last:.2e}")
+            else:
+                progress(done, last)
+    if n_epochs == 0:
+        if info is not None:
+            info.update(loss_hist=np.zeros(0), stopped_after=None, leaves=leaves)
+        return {}, 0.0, loss_fn
+    ctl = eng.download(state[2].to(torch.float64))
+    hist = eng.download(torch.cat(hists))
+    last_epoch = int(ctl[1]) if ctl[0] != 0 else n_epochs - 1
+    epoch_loss = float(hist[last_epoch])
+    if info is not None:
+        info.update(loss_hist=hist, stopped_after=int(ctl[1]) if ctl[0] != 0 else None, leaves=eng.download(x))
+    if save and states is not None:
+        bh = eng.download(torch.cat(bhs))
+        freq = int(opt["save_state_freq"])
+        for i in range(last_epoch if ctl[0] != 0 else n_epochs):
+            if i % freq == 0 and not np.isnan(bh[i, 0]):
+                snap = ts_params.copy()
+                snap.X[0] = bh[i]
+                states[i] = snap.get_unnormed_params()
+    if ctl[4] == 0:   # (no epoch improved on 100.0: the reference returns the dict it started with)
+        return {}, epoch_loss, loss_fn
+    best = eng.download(state[1])
+    best_weights = ts_params.copy()
+    best_weights.X[0] = best[1 : 1 + eng.NP]
+    if train_table:
+        best_weights.fval2d = best[1 + eng.NP :].reshape(ts_params.fval2d.shape).copy()
+    return best_weights, epoch_loss, loss_fn

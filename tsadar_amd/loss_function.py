@@ -174,6 +174,21 @@ class LossFunction:
             derr = 1.0 - d / E
         return e_error, E, derr * wcol[None, :]
 
+    def _angular_wcol(self, lamE, rows: int) -> np.ndarray:
+        """d value / d err[:, j] of the angular loss: the blue / red masks on the resolution-unit axis over rows x mask count
+        (the nanmean over the image), halved when both are fitted."""
+        ext, r = self.cfg["other"]["extraoptions"], self.cfg["data"]["fit_rng"]
+        wcol = np.zeros(lamE.size)
+        nterm = 0
+        for on, lo, hi in ((ext["fit_EPWb"], r["blue_min"], r["blue_max"]), (ext["fit_EPWr"], r["red_min"], r["red_max"])):
+            if on:
+                m = (lamE > lo) & (lamE < hi)
+                wcol[m] += 1.0 / (rows * max(int(m.sum()), 1))
+                nterm += 1
+        if nterm == 2:
+            wcol *= 0.5
+        return wcol
+
     def _angular_value_device(self, eng, ts_params: ThomsonParams, batch, want_E: bool):
         """_angular_value(want_bar=True) with the image, the data, the masks and the loss seed on the device (a handful of
         element-wise torch operations on [rows, n_lam]; one scalar comes back): -> (value, ThryE or None, Ebar device)."""
@@ -183,18 +198,7 @@ class LossFunction:
         src = (batch["e_data"], batch["noise_e"])   # (strong references: see _device_batch)
         old_src = getattr(self, "_ang_dev_src", None)
         if old_src is None or old_src[0] is not src[0] or old_src[1] is not src[1]:
-            lamE = ctx["lamE"]
-            ext, r = self.cfg["other"]["extraoptions"], self.cfg["data"]["fit_rng"]
-            rows = ctx["E_dev"].shape[0]
-            wcol = np.zeros(lamE.size)
-            nterm = 0
-            for on, lo, hi in ((ext["fit_EPWb"], r["blue_min"], r["blue_max"]), (ext["fit_EPWr"], r["red_min"], r["red_max"])):
-                if on:
-                    m = (lamE > lo) & (lamE < hi)
-                    wcol[m] += 1.0 / (rows * max(int(m.sum()), 1))
-                    nterm += 1
-            if nterm == 2:
-                wcol *= 0.5
+            wcol = self._angular_wcol(ctx["lamE"], ctx["E_dev"].shape[0])
             self._ang_dev = dict(d=eng.dev(np.ascontiguousarray(batch["e_data"], dtype=np.float64)), wcol=eng.dev(wcol)[None, :],
                                  noise=eng.dev(np.array(np.atleast_1d(np.asarray(batch["noise_e"], dtype=np.float64)))))
             self._ang_dev_src = src

@@ -121,3 +121,23 @@ class Adam:
         c1, c2 = 1 - self.b1**count, 1 - self.b2**count
         upd = tree_map(lambda m, v: -self.lr * (m / c1) / (np.sqrt(v / c2) + self.eps), mu, nu)
         return upd, (count, mu, nu)
+
+
+class RMSProp:
+    """optax.rmsprop(learning_rate) for DiffParams with optax's defaults (decay = 0.9, eps = 1e-8, initial_scale = 0,
+    eps_in_sqrt = True, centered = False, momentum = None): ``scale_by_rms`` then ``scale_by_learning_rate``,
+        nu  = decay * nu + (1 - decay) * g^2
+        upd = -lr * g / sqrt(nu + eps)
+    (optax/_src/alias.py rmsprop, optax/_src/transform.py scale_by_rms; optax multiplies by rsqrt(nu + eps) where this
+    divides by the square root, a difference of rounding).  The bit reference of the RMSProp step of tsff_angular_fit."""
+
+    def __init__(self, learning_rate: float, decay: float = 0.9, eps: float = 1e-8):
+        self.lr, self.decay, self.eps = learning_rate, decay, eps
+
+    def init(self, params: DiffParams):
+        return tree_map(np.zeros_like, params)
+
+    def update(self, grads: DiffParams, state, params=None):
+        nu = tree_map(lambda v, g: self.decay * v + (1 - self.decay) * g * g, state, grads)
+        upd = tree_map(lambda v, g: -self.lr * g / np.sqrt(v + self.eps), nu, grads)
+        return upd, nu
