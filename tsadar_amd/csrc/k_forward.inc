@@ -14,20 +14,21 @@
 //   (Tried and dropped, profiles/r03o: two 256-thread workgroups per item that hand their halves over through global memory with
 //    an agent-scope ticket, four per CU with the spectrum buffer overlaying the tables: the release / acquire across XCDs costs more
 //    than the halved sweep saves -- 59 us against 52 at B = 256.)
-// EXM: how a pair gets its right-neighbour base point: 0 evaluates it itself; 1 from the next lane through LDS (k_spectrum_fused's
-// exchange); 2 from the next lane by a lane shuffle (ds_bpermute), the unit-boundary points of the last lanes through LDS.
+// EXM: how a pair gets its right-neighbour base point: 0 evaluates it itself; 1 and 2 take it from the next lane, register to
+// register (next_lane_f64, k_spectrum_fused's exchange), the unit-boundary points of the last lanes through LDS.  (1 was the exchange
+// through per-lane LDS slots, 2 the one by ds_bpermute shuffles; both are this one form now.  The planner still names its
+// two-workgroups-per-CU choice 1 and its wide / three-per-CU choice 2: the kernel names are what the coverage contract of the
+// instantiations lists.)
 // Reference rows a4-a13 of SURVEY.md section 8 (form_factor.py:182-298, generate_spectra.py:139-220, irf.py:50-132,
 // thomson_diagnostic.py:109-142).  Restrictions (launch_spectrum falls back to k_spectrum): one gradient point, one point per pixel.
-// LDS of a forward-only workgroup, laid out for it alone (k_spectrum's carve() reserves the adjoint's reduction scratch and, for any
-// exchange, the per-lane slots of the LDS form): with the half Z' table, no k_s cache and the lane-shuffle exchange (EXM = 2: only the
-// 8 x 16 unit-boundary points live in LDS) a workgroup takes 52 KB -- THREE per CU, and the sweep's 120 VGPRs leave room for four
-// wavefronts per SIMD.
-__host__ __device__ inline size_t smem_fwd_doubles(const KStatic& S, bool with_ks, bool zh, int exm) {
+// LDS of a forward-only workgroup, laid out for it alone (k_spectrum's carve() reserves the adjoint's reduction scratch): with the
+// half Z' table and no k_s cache (of the exchange only the 8 x 16 unit-boundary points live in LDS) a workgroup takes 52 KB --
+// THREE per CU, and the sweep's 120 VGPRs leave room for four wavefronts per SIMD.
+__host__ __device__ inline size_t smem_fwd_doubles(const KStatic& S, bool with_ks, bool zh, size_t exd) {   // exd: doubles of the exchange
   size_t n = 2 * (size_t)((zh ? kNZh : kNXi2) + S.nvx) + kNXi2 + 4 * (size_t)S.nvx + xbuf_doubles(S);   // zp, ht, W, hc, x
   if (with_ks) n += (size_t)S.npts + 2;
   n += S.ntaps[0] + S.ntaps[1] + 16 + 2 * (size_t)S.n_angles + (kNP_MAX + 2) + 64 + kNExpTab;           // taps, angles, phys, red, exp table
-  if (exm == 1) n += kExDoubles;
-  if (exm == 2) n += kExComp * kExBound;
+  n += exd;
   return n;
 }
 __device__ __forceinline__ Smem carve_fwd(unsigned char* smem, const KStatic& S, bool with_ks, bool zh, int exm) {
@@ -112,8 +113,7 @@ __global__ __launch_bounds__(kHalf * (3 - NPAIR), 2) void k_forward_pairs(KStati
   }
   const double ex_wse = (NPAIR == 2 && ((lane >> 4) & 1)) ? w_hi[NPAIR - 1] : w_hi[0];
   __syncthreads();
-  double* exl = EXM == 1 ? m.ex : nullptr;
-  double* exb = EXM == 2 ? m.ex : (EX ? m.ex + kExComp * kHalf : nullptr);   // (EXM 2: the boundary points are all there is)
+  double* exb = m.ex;
   auto unit_of = [&](int P) { return NPAIR == 1 ? hw : 2 * hw + P; };   // 128-sample unit of this wavefront's pair P
   if (EX) {   // the unit-boundary base points of this wavefront's unit(s), all angles at once (lane = 16 P + a)
     const int Pb = (lane >> 4) & 1, ab = lane & 15;
@@ -143,32 +143,17 @@ __global__ __launch_bounds__(kHalf * (3 - NPAIR), 2) void k_forward_pairs(KStati
       Base b0;
       base_eval<NI>(ws[P][0], use_ks ? ksc[jb] : ks_eval(ws[P][0], L.wpe2), ct, L, T, b0);
       const Base b0f = b0;   // (the thread's FIRST base point of this angle: what its left neighbour asks for)
-      if (EXM == 1) {
-        exl[ht] = b0.wd; exl[kHalf + ht] = b0.ik; exl[2 * kHalf + ht] = b0.xe; exl[3 * kHalf + ht] = b0.F; exl[4 * kHalf + ht] = b0.dH;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-      }
 #pragma unroll
       for (int i = 0; i < kPair; ++i) {
         const int j = jb + i;
         const bool has_next = (j + 1) < npts;
         Base b1;
-        if (EXM == 1 && i == kPair - 1) {
-          __builtin_amdgcn_wave_barrier();
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-          const double* src = lane == 63 ? exb + 16 * unit_of(P) + a : exl + ht + 1;
-          const int cs = lane == 63 ? kExBound : kHalf;
-          b1.wd = src[0]; b1.ik = src[cs]; b1.xe = src[2 * cs]; b1.F = src[3 * cs]; b1.dH = src[4 * cs];
-          b1.ks = ks2;
-          b1.k2 = base_k2<NI>(ks2, ct, L);
-          __builtin_amdgcn_wave_barrier();
-        } else if (EXM == 2 && i == kPair - 1) {   // the next lane's first base point by a lane shuffle; the last lane takes the unit's boundary point
+        if (EX && i == kPair - 1) {   // the next lane's first base point, register to register; the last lane takes the unit's boundary point
+          // (next_lane_f64: all 64 lanes are here -- the branches and loops around it are wavefront-uniform.  The forward value reads
+          //  xi_e and F of this point alone: the compiler drops the other three shifts and their boundary reads)
           const double* src = exb + 16 * unit_of(P) + a;
-          const bool edge = lane == 63;
-          const double e0 = src[0], e1 = src[kExBound], e2 = src[2 * kExBound], e3 = src[3 * kExBound], e4 = src[4 * kExBound];
-          const double s0 = __shfl_down(b0f.wd, 1, 64), s1 = __shfl_down(b0f.ik, 1, 64), s2 = __shfl_down(b0f.xe, 1, 64),
-                       s3 = __shfl_down(b0f.F, 1, 64), s4 = __shfl_down(b0f.dH, 1, 64);
-          b1.wd = edge ? e0 : s0; b1.ik = edge ? e1 : s1; b1.xe = edge ? e2 : s2; b1.F = edge ? e3 : s3; b1.dH = edge ? e4 : s4;
+          b1.wd = next_lane_f64(b0f.wd, src[0]); b1.ik = next_lane_f64(b0f.ik, src[kExBound]); b1.xe = next_lane_f64(b0f.xe, src[2 * kExBound]);
+          b1.F = next_lane_f64(b0f.F, src[3 * kExBound]); b1.dH = next_lane_f64(b0f.dH, src[4 * kExBound]);
           b1.ks = ks2;
           b1.k2 = base_k2<NI>(ks2, ct, L);
         } else {

@@ -30,7 +30,7 @@ struct Smem {
   double* wsa;    // [n_angles]
   double* red;    // [8 * kNP_MAX + 64]
   double* etab;   // [kNExpTab] 2^(j/64) (fexp_t)
-  double* ex;     // [kExDoubles] base-point exchange of k_spectrum_fused, or nullptr
+  double* ex;     // [kExDoubles] unit-boundary points of the base-point exchange (k_spectrum_fused), or nullptr
 };
 
 // one spectrum / per-bin adjoint buffer: linear with a zero halo, or four phase arrays (sample j -> phase j & 3, slot
@@ -55,12 +55,17 @@ __host__ __device__ inline size_t ybuf_doubles(const KStatic& S) {
 __host__ __device__ inline bool wm_in_lds(int gm) { return gm == 2 || (gm == 1 && !TSFF_WM_GLOBAL); }
 // alias: the per-bin adjoint buffer shares the memory of the spectrum buffer (phase layout only, see alias_xy)
 __host__ __device__ inline bool alias_xy(const KStatic& S, int tpf) { return tpf == 256 && S.ppp == 1; }
-// base-point exchange of k_spectrum_fused (EX): per component (w - k V, 1/k, xi_e, F, dH/dxi) one slot per thread and 8 units x 16 angles
-// of unit-boundary base points
+// base-point exchange of k_spectrum_fused (EX): per component (w - k V, 1/k, xi_e, F, dH/dxi) 8 units x 16 angles of unit-boundary
+// base points; the exchange between lanes itself runs in registers (next_lane_f64).
+// kExLdsDoubles is the footprint of the earlier form, which k_spectrum_rows keeps (its header): one LDS slot per thread and component
+// in front of the boundary points, 10 KB more.  It is also what the launch planner still CHARGES the register form when it decides
+// on EX, the half Z' table and the k_s cache: the decisions, and with them the instantiation every shape runs (the coverage contract
+// of the instantiations pins decks to kernels at those thresholds), are what they were; the allocation is the real size.
 constexpr int kExComp = 5, kExBound = 8 * 16;
-constexpr int kExDoubles = kExComp * (kHalf + kExBound);
+constexpr int kExDoubles = kExComp * kExBound;
+constexpr int kExLdsDoubles = kExComp * (kHalf + kExBound);
 __host__ __device__ inline size_t smem_doubles(const KStatic& S, int nfeat, int gm, bool with_ks, bool alias = false, bool zh = true,
-                                               bool ex = false) {
+                                               size_t exd = 0) {   // exd: doubles of the base-point exchange (0: none)
   size_t n = 2 * (size_t)((zh ? kNZh : kNXi2) + S.nvx) + kNXi2 + 4 * (size_t)S.nvx;     // zp, ht, W, hc
   if (gm) n += 4 * (size_t)S.nvx;                                                           // hcm
   if (wm_in_lds(gm)) n += kNXi2;                                                            // Wm
@@ -68,7 +73,7 @@ __host__ __device__ inline size_t smem_doubles(const KStatic& S, int nfeat, int 
   if (!alias) n += (size_t)nfeat * ybuf_doubles(S);                                         // per-bin adjoint buffers
   if (with_ks) n += (size_t)nfeat * ((size_t)S.npts + 2);                                   // k_s cache
   n += S.ntaps[0] + S.ntaps[1] + 16 + 2 * (size_t)S.n_angles + 11 * kNP_MAX + 66 + kNExpTab;     // taps (+ padding of one feature's padded copy), angles, phys, scratch, exp table
-  if (ex) n += kExDoubles;
+  n += exd;
   return n;
 }
 

@@ -200,11 +200,11 @@ constexpr int kRedSums = 32;   // offset (doubles) of the five partial block sum
 #define TSFF_FUSED_FAR 1   // wavefronts whose every point has |xi_i| > 28 run the sweep with the asymptotic ion terms
 #endif
 // EX: the third base point of a pair -- the right neighbour of its second sample, which is the FIRST sample of the next
-// thread's pair -- is not evaluated again but taken from that thread: every lane leaves (w - k V, 1/k, xi_e, F, dH/dxi) of its first
-// base point in LDS and reads its neighbour lane's (same wavefront: lockstep, no barrier; k_s comes from the cache, k^2 is
-// two instructions).  The last lane of a wavefront has no neighbour lane: the base points right of each 128-sample unit are
-// evaluated once per (unit, angle) before the sweep.  2 instead of 3 base evaluations (k, xi_e, Hermite lookup, exp: ~52
-// instructions each) per pair and angle.  Needs kExDoubles of LDS and n_angles <= 16 (launch_fused decides).
+// thread's pair -- is not evaluated again but taken from that thread: every lane receives (w - k V, 1/k, xi_e, F, dH/dxi) of its
+// neighbour lane's first base point register to register (next_lane_f64: ten DPP moves, no LDS, no wait, no barrier; k_s comes from
+// the cache, k^2 is two instructions).  The last lane of a wavefront has no neighbour lane: the base points right of each
+// 128-sample unit are evaluated once per (unit, angle) before the sweep and kept in LDS.  2 instead of 3 base evaluations (k, xi_e,
+// Hermite lookup, exp: ~52 instructions each) per pair and angle.  Needs kExDoubles of LDS and n_angles <= 16 (launch_fused decides).
 // The prologue (round 3).  The workgroup timeline (scripts/trace_fused.py, profiles/r03a_trace_fused.txt) showed what bounds the
 // launch: a wavefront issues at most every second slot of its SIMD (scripts/ubench_dep.hip), two resident wavefronts per SIMD do
 // not slow each other down, so a CU finishes a pair of workgroups every (sweep + everything else) -- and everything else was
@@ -307,10 +307,8 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_fused(KStatic S, KCall K,
 #pragma unroll
   for (int q = 0; q < kStrip; ++q) { zero_lines<NI>(J[q]); xa[q] = 0.0; KA[q].p1a = KA[q].p2a = KA[q].p1b = KA[q].p2b = 0.0; }
   const double cw = -0.5 * L.i2wL * L.i2wL;
-  // EX: slots of the exchange -- component c of lane l at ex[c kHalf + l]; of the base point right of unit u (u = 2 hw + P) at
-  // angle a at exb[c kExBound + 16 u + a]
-  double* exl = m.ex;
-  double* exb = EX ? m.ex + kExComp * kHalf : nullptr;
+  // EX: the base point right of unit u (u = 2 hw + P) at angle a: component c at exb[c kExBound + 16 u + a]
+  double* exb = m.ex;
   if (EX) {   // the unit-boundary base points of this wavefront's two units, all angles at once (lane = 16 P + a)
     const int Pb = (lane >> 4) & 1, ab = lane & 15;
     if (lane < 32 && ab < NA) {
@@ -322,6 +320,7 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_fused(KStatic S, KCall K,
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   // (the sweep reads other lanes' boundary points)
   }
   auto sweep = [&](auto pair_tag, auto far_tag) {
     constexpr int P = decltype(pair_tag)::value;
@@ -330,34 +329,32 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_fused(KStatic S, KCall K,
     const int j2 = min(jb + kPair, npts - 1);
     const double ks2 = EX ? (use_ks ? ksc[j2] : ks_eval(ws[P][kPair], L.wpe2)) : 0.0;
     double ct_n = m.cosa[0], wa_n = m.wsa[0];   // (the angle's constants are read from LDS one iteration ahead of their use)
+    // (EX) the unit's boundary point, which lane 63 takes for its missing neighbour
+    const double* exu = EX ? exb + 16 * (2 * hw + P) : nullptr;
     for (int a = 0; a < NA; ++a) {
       const double ct = uni(ct_n), wa = uni(wa_n * L.pref);
       { const int an = min(a + 1, NA - 1); ct_n = m.cosa[an]; wa_n = m.wsa[an]; }
       Base b0;
       base_eval<NI>(ws[P][0], use_ks ? ksc[jb] : ks_eval(ws[P][0], L.wpe2), ct, L, T, b0);
-      if (EX) {
-        exl[ht] = b0.wd; exl[kHalf + ht] = b0.ik; exl[2 * kHalf + ht] = b0.xe; exl[3 * kHalf + ht] = b0.F; exl[4 * kHalf + ht] = b0.dH;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-      }
+      // (EX) the lane's FIRST base point of this angle is what its left neighbour asks for: b0 itself is the second one by then
+      const double f_wd = b0.wd, f_ik = b0.ik, f_xe = b0.xe, f_F = b0.F, f_dH = b0.dH;
 #pragma unroll
       for (int i = 0; i < kPair; ++i) {
         constexpr int q0 = kPair * P;
         const int q = q0 + i, j = jb + i;
         const bool has_next = (j + 1) < npts;
         Base b1;
-        if (EX && i == kPair - 1) {   // the neighbour lane's first base point (or the unit's boundary point for the last lane)
-          // (reading it back ahead of the first point, so that the point covers the round trip, was tried: five more doubles live
-          //  across the point and the allocator spills twenty registers)
-          __builtin_amdgcn_wave_barrier();
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-          const double* src = lane == 63 ? exb + 16 * (2 * hw + P) + a : exl + ht + 1;
-          const int cs = lane == 63 ? kExBound : kHalf;
-          b1.wd = src[0]; b1.ik = src[cs]; b1.xe = src[2 * cs]; b1.F = src[3 * cs]; b1.dH = src[4 * cs];
+        if (EX && i == kPair - 1) {   // the neighbour lane's first base point (the unit's boundary point for the last lane), register
+          // to register (next_lane_f64; all 64 lanes are here: the branches and loops around it are wavefront-uniform)
+          // (The boundary point is read HERE.  Read an iteration ahead, as ct_n / wa_n are, or at the top of the iteration, its five
+          //  doubles live across the pair's first point and the allocator spills 26 / 10 registers outside the loops where this form
+          //  spills none; measured, DESIGN.md section 4.1b.)
+          const double* src = exu + a;
+          b1.wd = next_lane_f64(f_wd, src[0]); b1.ik = next_lane_f64(f_ik, src[kExBound]); b1.xe = next_lane_f64(f_xe, src[2 * kExBound]);
+          b1.F = next_lane_f64(f_F, src[3 * kExBound]); b1.dH = next_lane_f64(f_dH, src[4 * kExBound]);
           b1.ks = ks2;
           b1.k2 = base_k2<NI>(ks2, ct, L);   // (base_eval's own expression: the same bits; k itself -- a separately rounded
                                              //  square root there, not k2 * ik -- only enters through wd, which is exchanged)
-          __builtin_amdgcn_wave_barrier();   // (the next angle's stores stay behind these loads)
         } else {
           base_eval<NI>(ws[P][i + 1], use_ks ? ksc[min(j + 1, npts - 1)] : ks_eval(ws[P][i + 1], L.wpe2), ct, L, T, b1);
         }

@@ -30,8 +30,8 @@ __host__ __device__ inline int rows_components(int n_ion, int gm) { return 8 + 3
 __host__ __device__ inline size_t rows_persist_doubles(const KStatic& S) {
   return (size_t)S.ntaps[0] + S.ntaps[1] + (kNP_MAX + 2) + 2 * (size_t)S.n_angles + (10 * kNP_MAX + 64) + kNExpTab + 1;   // (+1: alignment pad)
 }
-__host__ __device__ inline size_t rows_sweep_doubles(const KStatic& S, int gm, bool zh, bool ex) {
-  return 2 * (size_t)((zh ? kNZh : kNXi2) + S.nvx) + kNXi2 + 4 * (size_t)S.nvx + (gm ? 4 * (size_t)S.nvx : 0) + (ex ? kExDoubles : 0);
+__host__ __device__ inline size_t rows_sweep_doubles(const KStatic& S, int gm, bool zh, size_t exd) {
+  return 2 * (size_t)((zh ? kNZh : kNXi2) + S.nvx) + kNXi2 + 4 * (size_t)S.nvx + (gm ? 4 * (size_t)S.nvx : 0) + exd;
 }
 // spectrum buffer of the chain: the linear layout with one pad double after every 4 ppp samples (the forward convolution's
 // lanes are 4 ppp samples apart: the pad makes that stride odd)
@@ -39,12 +39,16 @@ __host__ __device__ inline size_t rows_xbuf_doubles(const KStatic& S) {
   const size_t n = xbuf_doubles(S);
   return ((n + n / (4 * (size_t)S.ppp) + 3) & ~(size_t)1);
 }
-__host__ __device__ inline size_t rows_smem_doubles(const KStatic& S, int gm, bool zh, bool ex) {
-  const size_t a = rows_sweep_doubles(S, gm, zh, ex), c = rows_xbuf_doubles(S) + ybuf_doubles(S);
+__host__ __device__ inline size_t rows_smem_doubles(const KStatic& S, int gm, bool zh, size_t exd) {   // exd: doubles of the exchange
+  const size_t a = rows_sweep_doubles(S, gm, zh, exd), c = rows_xbuf_doubles(S) + ybuf_doubles(S);
   return rows_persist_doubles(S) + (a > c ? a : c);
 }
 
-// EX: the base-point exchange between neighbouring lanes of k_spectrum_fused (its header), per round
+// EX: the base-point exchange between neighbouring lanes of k_spectrum_fused (its header), per round -- here still in its earlier form
+// through LDS (one slot per thread and component, kExLdsDoubles in all): the register form (next_lane_f64) was built and measured
+// for this kernel too and bought nothing that could be told from the noise of its bench line (bench.py --ppp 5 --batch 1024: four
+// VALU instructions more and five LDS instructions fewer per angle, and this sweep waits for its angle constants at the top of every
+// iteration anyway), so the kernel stays instruction for instruction what it was; DESIGN.md section 4.1b has the numbers
 // FWD (round 3): tsff_forward at several points per pixel -- the same rounds with the forward value alone (point_forward_sd: the bits
 // of the loss kernel's spectrum), ONE scratch component, the chain up to the store of ThryE / ThryI.  It replaces k_spectrum MODE 0's
 // one 512-thread workgroup per CU for such decks (the reference's default: 5 points per pixel) and inherits the small-batch form (the

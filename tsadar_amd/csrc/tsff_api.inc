@@ -537,10 +537,12 @@ static SpectrumPlan plan_spectrum(const tsff_handle& h, int B, int nload) {
       constexpr bool FWD = MODE == 0;
       SpectrumPlan p;
       p.form = SpectrumForm::rows;
-      // (the exchange's 15 KB live in the sweep's part of the LDS: free whenever the chain's buffers are the larger part)
-      p.ex = S.n_angles <= 16 && !(h.plan & 8) && 2 * sizeof(double) * rows_smem_doubles(S, GM, true, true) <= kLdsLimit;
-      p.zh = 2 * sizeof(double) * rows_smem_doubles(S, GM, false, p.ex) > kLdsLimit;
-      p.smem = sizeof(double) * rows_smem_doubles(S, GM, p.zh, p.ex);
+      // (the exchange's 15 KB -- this kernel keeps the form through LDS -- live in the sweep's part of the LDS: free whenever the
+      //  chain's buffers are the larger part)
+      const size_t exd = kExLdsDoubles;
+      p.ex = S.n_angles <= 16 && !(h.plan & 8) && 2 * sizeof(double) * rows_smem_doubles(S, GM, true, exd) <= kLdsLimit;
+      p.zh = 2 * sizeof(double) * rows_smem_doubles(S, GM, false, p.ex ? exd : 0) > kLdsLimit;
+      p.smem = sizeof(double) * rows_smem_doubles(S, GM, p.zh, p.ex ? exd : 0);
       p.interleaved = nload == 2;
       p.rows = nitems * (FWD ? 1 : rows_components(h.n_ion, GM)) * (size_t)S.npts * sizeof(double);   // (forward: the value only)
       if (2 * p.smem <= kLdsLimit && (FWD || p.rows <= kRowsScratchMax)) {
@@ -562,20 +564,20 @@ static SpectrumPlan plan_spectrum(const tsff_handle& h, int B, int nload) {
       p.form = SpectrumForm::pairs;
       p.ex = S.n_angles <= 16 && !(h.plan & 8);
       p.interleaved = nload == 2;
-      // 512 threads per item (one pair per thread, lane-shuffle exchange) while the batch fits one round of two items per CU
+      // 512 threads per item (one pair per thread) while the batch fits one round of two items per CU
       p.wide = nitems <= 2 * (size_t)h.ncu2d() && !(h.plan & 1);
-      // LDS of the forward workgroup (smem_fwd_doubles): two per CU with the lane exchange through LDS (the full Z' table and the
-      // k_s cache as they fit), or -- batches of more than two items per CU -- THREE per CU with the half Z' table, no k_s cache and
-      // the exchange by lane shuffles (plan bit 2 (4): never)
-      const int exm2 = p.ex ? 1 : 0;
-      const bool zh2 = 2 * sizeof(double) * smem_fwd_doubles(S, false, false, exm2) > kLdsLimit;
-      const bool ks2 = 2 * sizeof(double) * smem_fwd_doubles(S, true, zh2, exm2) <= kLdsLimit;
-      const size_t smem3 = sizeof(double) * smem_fwd_doubles(S, false, true, p.ex ? 2 : 0);
+      // LDS of the forward workgroup (smem_fwd_doubles): two per CU (the full Z' table and the k_s cache as they fit), or -- batches
+      // of more than two items per CU -- THREE per CU with the half Z' table and no k_s cache (plan bit 2 (4): never).  EXM 1 and 2
+      // cost the same LDS: the exchange itself is in registers, only the unit-boundary points live in LDS
+      const size_t exd = p.ex ? kExDoubles : 0, exd2 = p.ex ? kExLdsDoubles : 0;   // (two per CU: decided at kExLdsDoubles, k_spectrum.inc)
+      const bool zh2 = 2 * sizeof(double) * smem_fwd_doubles(S, false, false, exd2) > kLdsLimit;
+      const bool ks2 = 2 * sizeof(double) * smem_fwd_doubles(S, true, zh2, exd2) <= kLdsLimit;
+      const size_t smem3 = sizeof(double) * smem_fwd_doubles(S, false, true, exd);
       p.three = !p.wide && !(h.plan & 4) && nitems > 2 * (size_t)h.ncu2d() && 3 * smem3 <= kLdsLimit;
       p.zh = p.three || zh2;
       p.ks = !p.three && ks2;
-      p.smem = p.three ? smem3 : sizeof(double) * smem_fwd_doubles(S, ks2, zh2, p.ex ? (p.wide ? 2 : 1) : 0);
-      if (2 * p.smem <= kLdsLimit) {
+      p.smem = p.three ? smem3 : sizeof(double) * smem_fwd_doubles(S, ks2, zh2, exd);
+      if (p.three || 2 * sizeof(double) * smem_fwd_doubles(S, ks2, zh2, p.wide ? exd : exd2) <= kLdsLimit) {
         if (!p.wide) { p.lrec = nitems * kLineRec * sizeof(double); p.finrec = finrec; }
         p.grid = dim3((unsigned)nitems);
         p.block = dim3(p.wide ? 2 * kHalf : kHalf);
@@ -585,10 +587,10 @@ static SpectrumPlan plan_spectrum(const tsff_handle& h, int B, int nload) {
   }
   SpectrumPlan p;
   // the one-sweep kernel (k_spectrum_fused.inc) wherever its restrictions hold: loss + gradient, one gradient point, one point
-  // per pixel, 256-thread one-feature workgroups, no table adjoints; with the base-point exchange (EX: 15 KB more LDS, n_angles
-  // <= 16) when two such workgroups still fit a CU (the half Z' table makes room)
+  // per pixel, 256-thread one-feature workgroups, no table adjoints; with the base-point exchange (EX: lane to lane in registers,
+  // 5 KB of LDS for the unit-boundary points, n_angles <= 16) when two such workgroups still fit a CU (the half Z' table makes room)
   const bool fused_ok = MODE == 1 && GM <= 1 && S.G == 1 && S.ppp == 1 && h.n_ion <= kFusedMaxIon && !(h.plan & 2);
-  p.ex = fused_ok && S.n_angles <= 16 && !(h.plan & 8) && 2 * sizeof(double) * smem_doubles(S, 1, GM, false, true, true, true) <= kLdsLimit;
+  p.ex = fused_ok && S.n_angles <= 16 && !(h.plan & 8) && 2 * sizeof(double) * smem_doubles(S, 1, GM, false, true, true, kExLdsDoubles) <= kLdsLimit;
   // forward-only calls need 139 VGPRs: THREE one-feature workgroups fit a CU's registers, and its LDS too with the half Z' table
   // and without the k_s cache -- 3 wavefronts per SIMD hide the lookups' latency better than 2 (plan bit 2 (4): never); only when
   // there are more workgroups than two per CU (a grid that fits at two per CU gains nothing and pays for the half table)
@@ -596,11 +598,12 @@ static SpectrumPlan plan_spectrum(const tsff_handle& h, int B, int nload) {
             3 * sizeof(double) * smem_doubles(S, 1, GM, false, alias_xy(S, 256), true) <= kLdsLimit;
   // zh: Z' table held for xi >= 0 only, 13 KB less LDS for about 1 % more instructions -- used only when the full table would
   // cost the two-workgroups-per-CU plan
-  p.zh = p.three || 2 * sizeof(double) * smem_doubles(S, 1, GM, false, alias_xy(S, 256), false, p.ex) > kLdsLimit;
+  p.zh = p.three || 2 * sizeof(double) * smem_doubles(S, 1, GM, false, alias_xy(S, 256), false, p.ex ? kExLdsDoubles : 0) > kLdsLimit;
   // (tpf: threads per feature of the instantiation the size is for -- 256-thread-per-feature workgroups with points_per_pixel 1
   //  keep the per-bin adjoint in the memory of the spectrum, alias_xy)
-  auto bytes = [&](int nf, bool ks, int tpf) {
-    return sizeof(double) * smem_doubles(S, nf, GM, ks, alias_xy(S, tpf), p.zh, p.ex && nf == 1 && tpf == 256);
+  // (exc: what the exchange is charged -- kExLdsDoubles for the decisions, kExDoubles for the allocation; k_spectrum.inc)
+  auto bytes = [&](int nf, bool ks, int tpf, size_t exc = kExLdsDoubles) {
+    return sizeof(double) * smem_doubles(S, nf, GM, ks, alias_xy(S, tpf), p.zh, (p.ex && nf == 1 && tpf == 256) ? exc : 0);
   };
   const bool two_per_cu = 2 * bytes(1, false, 256) <= kLdsLimit;   // two one-feature workgroups per CU
   p.interleaved = nload == 2 && two_per_cu && !(h.plan & 1);
@@ -610,7 +613,7 @@ static SpectrumPlan plan_spectrum(const tsff_handle& h, int B, int nload) {
   p.tpf = (p.nfeat == 2 || small_wg) ? kHalf : 2 * kHalf;
   const size_t budget = small_wg ? kLdsLimit / (p.three ? 3 : 2) : kLdsLimit;
   p.ks = bytes(p.nfeat, true, p.tpf) <= budget;
-  p.smem = bytes(p.nfeat, p.ks, p.tpf);
+  p.smem = bytes(p.nfeat, p.ks, p.tpf, kExDoubles);
   if ((h.plan & 64) && p.smem <= kLdsLimit / 2) p.smem = kLdsLimit / 2 + 1024;   // (experiments: one workgroup per CU)
   // (the one-sweep kernel: also no second accumulating launch)
   const int nlaunch = p.interleaved ? 1 : nload / p.nfeat;
@@ -723,7 +726,8 @@ static int launch_spectrum(tsff_handle* h, KCall& K, const uint8_t* gmask = null
               TSFF_LAUNCH(h, k_forward_pairs, (N.value, ZH.value, EXM.value, NPAIR.value), p.grid, p.block, p.smem, h->stream, h->S, K,
                           f0, flags, lrec);
             };
-            // the nine shipped (ZH, EXM, NPAIR) forms; EXM: 0 no exchange, 1 through LDS, 2 by lane shuffles
+            // the nine shipped (ZH, EXM, NPAIR) forms; EXM: 0 no exchange, 1 and 2 the lane exchange (one form since it runs in
+            // registers; the planner's two-per-CU and wide / three-per-CU choices keep their numbers, k_forward.inc)
             if (p.wide) {
               with_bool(p.zh, [&](auto ZH) { p.ex ? pairs(ZH, IntC<2>(), IntC<1>()) : pairs(ZH, IntC<0>(), IntC<1>()); });
             } else {

@@ -87,6 +87,18 @@ __device__ __forceinline__ double uni(double x) {
   return __hiloint2double(hi, lo);
 }
 
+// Lane i receives v of lane i + 1, lane 63 receives `last`: the whole-wavefront DPP shift (v_mov_b32_dpp wave_shl:1, a GFX9
+// control gfx950 still has; no bound_ctrl, so the lane without a source keeps the `old` operand), two 32-bit moves per double.
+// It stays in the register file: no LDS address, no lgkmcnt wait, no fence.
+// ONLY where all 64 lanes of the wavefront are active: a DPP read from a disabled lane does not deliver.  Keep the call outside
+// any divergent branch (wavefront-uniform branches and loops are fine).
+__device__ __forceinline__ double next_lane_f64(double v, double last) {
+  constexpr int kWaveShl1 = 0x130;
+  const int lo = __builtin_amdgcn_update_dpp(__double2loint(last), __double2loint(v), kWaveShl1, 0xf, 0xf, false);
+  const int hi = __builtin_amdgcn_update_dpp(__double2hiint(last), __double2hiint(v), kWaveShl1, 0xf, 0xf, false);
+  return __hiloint2double(hi, lo);
+}
+
 // ------------------------------------------------------------------------------------------
 // wavefront / workgroup reductions (64-wide wavefronts, xor-shuffle butterflies)
 // ------------------------------------------------------------------------------------------
