@@ -37,6 +37,9 @@
  *   - a refused call (negative return) of tsff_forward, tsff_loss_grad(_packed, _fe), tsff_loss_hess, tsff_array_loss,
  *     tsff_adam_fit, tsff_angular_fit and tsff_form_factor(_grad) has enqueued nothing: their arguments, LDS budgets and buffers are checked before the first
  *     launch, and tsff_last_launch reports an empty list (other entry points may have enqueued work before a failure);
+ *   - a call that breaks several conditions is refused for the first of: the entry point's own arguments (-1), the active slot
+ *     list (-1), a leaf the configuration does not have (-2), the leaf A (-3), the batch arguments (-1, then -2),
+ *     what the entry point checks against the batch (the state size of tsff_lbfgs_fit, the LDS budget of tsff_loss_hess);
  *   - a handle is bound to the device that was current at tsff_create; handles are not thread-safe,
  *     the library is re-entrant across handles.
  *   - no CPU fallback exists: without a HIP device every entry point fails.

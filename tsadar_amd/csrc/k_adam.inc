@@ -18,6 +18,23 @@
 // previous best, read from best_prev; workgroup 0 publishes the new one to best_next, a different scalar (the caller alternates
 // the two by step parity), so no workgroup can read a value another one of the same launch writes.  Only the active slots of
 // best_x change; best_loss_out (the last step only) receives the final best loss.
+
+// The update of one element (also k_ang_opt's, k_angular.inc): the moments in place, the step returned.  The pragma is each
+// helper's own -- its scope is the compound statement it appears in, so a calling kernel's does not reach an inlined callee.
+__device__ __forceinline__ double adam_update(double g, double& m, double& v, double b1, double omb1, double b2, double omb2,
+                                              double neg_lr, double c1, double c2, double eps) {
+#pragma clang fp contract(off)
+  m = b1 * m + omb1 * g;
+  v = b2 * v + (omb2 * g) * g;
+  return (neg_lr * (m / c1)) / (sqrt(v / c2) + eps);
+}
+// tree.RMSProp.update, under the same contract: nu = decay * v + ((1 - decay) * g) * g, upd = ((-lr) * g) / sqrt(nu + eps)
+__device__ __forceinline__ double rmsprop_update(double g, double& v, double decay, double omd, double neg_lr, double eps) {
+#pragma clang fp contract(off)
+  v = decay * v + (omd * g) * g;
+  return (neg_lr * g) / sqrt(v + eps);
+}
+
 __global__ __launch_bounds__(kThreads) void k_adam_step(const double* __restrict__ packed, double w0, double w1, double w2,
                                                          const int* __restrict__ act, int n_act, int B, int NP,
                                                          double* __restrict__ params, double* __restrict__ mu, double* __restrict__ nu,
@@ -38,10 +55,8 @@ __global__ __launch_bounds__(kThreads) void k_adam_step(const double* __restrict
   const long n = (long)n_act * B;
   for (long i = (long)blockIdx.x * kThreads + threadIdx.x; i < n; i += (long)gridDim.x * kThreads) {
     const long k = i / B, b = i - k * B;
-    const double g = packed[3 + i];
-    const double m = b1 * mu[i] + omb1 * g;
-    const double v = b2 * nu[i] + (omb2 * g) * g;
-    const double upd = (neg_lr * (m / c1)) / (sqrt(v / c2) + eps);
+    double m = mu[i], v = nu[i];
+    const double upd = adam_update(packed[3 + i], m, v, b1, omb1, b2, omb2, neg_lr, c1, c2, eps);
     const long o = b * NP + act[k];
     const double x = params[o] + upd;
     mu[i] = m;

@@ -202,18 +202,9 @@ __global__ __launch_bounds__(kThreads) void k_ang_opt(const double* __restrict__
     for (long i = threadIdx.x; i < n; i += kThreads) {
       const long o = i < n_act ? (long)act[i] : NP + (i - n_act);
       const double g = grad[i];
-      double upd;
-      if (method == 0) {
-        const double m = b1 * mom[i] + omb1 * g;
-        const double v = b2 * mom[n + i] + (omb2 * g) * g;
-        upd = (neg_lr * (m / c1)) / (sqrt(v / c2) + eps);
-        mom[i] = m;
-        mom[n + i] = v;
-      } else {
-        const double v = b2 * mom[i] + (omb2 * g) * g;
-        upd = (neg_lr * g) / sqrt(v + eps);
-        mom[i] = v;
-      }
+      double upd;   // (the formulas and their bit contract: k_adam.inc)
+      if (method == 0) upd = adam_update(g, mom[i], mom[n + i], b1, omb1, b2, omb2, neg_lr, c1, c2, eps);
+      else upd = rmsprop_update(g, mom[i], b2, omb2, neg_lr, eps);
       const double x = leaves[o] + upd;
       leaves[o] = x;
     }

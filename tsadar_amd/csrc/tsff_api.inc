@@ -94,8 +94,10 @@ struct tsff_handle {
   }
   std::vector<uint8_t> gmask_host;  // last gradient mask uploaded (re-sent only when it changes)
   tsff::DevBuf act, gradws;         // tsff_loss_grad_packed: active slots on the device, per-lineout gradient workspace
-  tsff::DevBuf adam_packed, adam_best;   // tsff_adam_fit: the packed buffer of its steps, the ping-pong pair of best losses
-  tsff::DevBuf lbfgs_packed;             // tsff_lbfgs_fit: the packed buffer of its evaluations
+  // tsff_adam_fit / tsff_lbfgs_fit: the packed buffer of their steps.  One for both, as gradws and act are shared: a handle runs
+  // one call at a time (handles are not thread-safe, tsff.h) and a stream switch is ordered behind the previous stream by ev_switch
+  tsff::DevBuf fit_packed;
+  tsff::DevBuf adam_best;                // tsff_adam_fit: the ping-pong pair of best losses
   tsff::DevBuf ang_ws;                   // tsff_angular_fit: parameters, tables, image, seed and adjoints of one epoch
   std::vector<int32_t> act_host;
   tsff::DevBuf hws, hout;          // tsff_loss_hess: hyper-dual spectra of the persistent workgroups, per-task sums
@@ -462,7 +464,6 @@ static int prepare_tables(tsff_handle* h, const double* params, const double* fe
     K.W = h->W.as<double>();
     return 0;
   }
-  if (h->fe_mode == TSFF_FE_PER_LINEOUT && !fe) return fail(h, -2, "fe_mode PER_LINEOUT needs fe[B][nvx]");
   // per-lineout tables: vectors (A, s, dA/dm, ds/dm) per lineout, then W = c + Lg (A + xi2 s) for the whole batch
   // blocks of a multiple of 256 lineouts (the GEMM spreads groups of eight 32-lineout tiles over the XCDs); off unless asked for
   int nblk = 1;
@@ -658,14 +659,18 @@ static void launch_fused(tsff_handle* h, const KCall& K, const SpectrumPlan& p, 
   h->pipe_nblk = 0;
 }
 
-// the scratch buffers of the plan launch_spectrum<MODE, GM> will pick for B lineouts, sized (and its LDS budget checked) before a
-// call enqueues anything, so that a refusal leaves nothing behind
+// the plan launch_spectrum<MODE, GM> runs for B lineouts, its LDS budget checked and every scratch buffer of it sized (the
+// arrival counters zeroed when they grow) -- before a call enqueues anything, so that a refusal leaves nothing behind
 template <int MODE, int GM>
-static int size_plan(tsff_handle* h, int B) {
+static int size_plan(tsff_handle* h, int B, SpectrumPlan& p) {
   const int nload = (h->S.load[0] ? 1 : 0) + (h->S.load[1] ? 1 : 0);
-  const SpectrumPlan p = plan_spectrum<MODE, GM>(*h, B, nload);
+  p = plan_spectrum<MODE, GM>(*h, B, nload);
   if (p.smem > kLdsLimit) return fail(h, TSFF_ERR_LDS, "LDS budget exceeded (%zu B): reduce npts or the IRF cutoff", p.smem);
   if (p.rows) TSFF_ENSURE(h, h->rows, p.rows);
+  if (p.tickets && h->tickets.bytes < p.tickets) {
+    TSFF_ENSURE(h, h->tickets, std::max<size_t>(p.tickets, 1024 * sizeof(unsigned)));
+    TSFF_HIP(h, hipMemsetAsync(h->tickets.p, 0, h->tickets.bytes, h->stream));
+  }
   if (p.gpart) TSFF_ENSURE(h, h->gpart, p.gpart);
   if (p.lbrec) TSFF_ENSURE(h, h->lbrec, p.lbrec);
   if (p.lrec) TSFF_ENSURE(h, h->lrec, p.lrec);
@@ -673,34 +678,17 @@ static int size_plan(tsff_handle* h, int B) {
   return 0;
 }
 
-// plan_spectrum, then the buffers of the plan, the timing ring and the launches
+// the launches of a plan size_plan<MODE, GM> made for K.B lineouts: the KCall's pointers into the plan's buffers (K.gpart when
+// p.gpart, K.lbrec for the one-sweep form), the pipe, the timing ring, the kernels.  Allocates and refuses nothing.
 template <int MODE, int GM = 0>
-static int launch_spectrum(tsff_handle* h, KCall& K, const uint8_t* gmask = nullptr, double* grad = nullptr,
-                           bool* used_gpart = nullptr, bool* used_lbrec = nullptr) {
+static int launch_spectrum(tsff_handle* h, KCall& K, const SpectrumPlan& p, const uint8_t* gmask = nullptr, double* grad = nullptr) {
   const int nload = (h->S.load[0] ? 1 : 0) + (h->S.load[1] ? 1 : 0);
-  const SpectrumPlan p = plan_spectrum<MODE, GM>(*h, K.B, nload);
-  if (p.smem > kLdsLimit) return fail(h, TSFF_ERR_LDS, "LDS budget exceeded (%zu B): reduce npts or the IRF cutoff", p.smem);
   // the one-sweep kernel takes the tables block by block; every other form waits for all of them (a no-op for forward calls:
   // only the loss + gradient builds its tables on the second stream)
   if (p.form != SpectrumForm::one_sweep)
     if (int rc = join_pipe(h)) return rc;
-  if (p.rows) TSFF_ENSURE(h, h->rows, p.rows);
-  if (p.tickets && h->tickets.bytes < p.tickets) {
-    TSFF_ENSURE(h, h->tickets, std::max<size_t>(p.tickets, 1024 * sizeof(unsigned)));
-    TSFF_HIP(h, hipMemsetAsync(h->tickets.p, 0, h->tickets.bytes, h->stream));
-  }
-  if (p.gpart) {
-    TSFF_ENSURE(h, h->gpart, p.gpart);
-    K.gpart = h->gpart.as<double>();
-    if (used_gpart) *used_gpart = true;
-  }
-  if (p.lbrec) TSFF_ENSURE(h, h->lbrec, p.lbrec);
-  if (p.lrec) TSFF_ENSURE(h, h->lrec, p.lrec);
-  if (p.finrec) TSFF_ENSURE(h, h->finrec, p.finrec);
-  if (p.form == SpectrumForm::one_sweep) {
-    K.lbrec = h->lbrec.as<double>();
-    if (used_lbrec) *used_lbrec = true;
-  }
+  if (p.gpart) K.gpart = h->gpart.as<double>();
+  if (p.form == SpectrumForm::one_sweep) K.lbrec = h->lbrec.as<double>();
   if (int rc = timing_begin(h)) return rc;
   const int nlaunch = p.interleaved ? 1 : nload / p.nfeat;
   for (int l = 0; l < nlaunch; ++l) {
@@ -763,6 +751,50 @@ static int launch_spectrum(tsff_handle* h, KCall& K, const uint8_t* gmask = null
 static unsigned angle_chunks(const tsff_handle* h, int B) {
   const int want = 4 * h->ncu2d();
   return (unsigned)std::max(1, std::min(h->S.n_angles, want / std::max(B, 1)));
+}
+
+// The refusals every entry point shares, each written once.  An entry point checks in this order -- its own arguments (-1), the
+// slot list (-1), the leaves (-2, -3), the batch (-1, -2) -- then sizes, then launches (tsff.h).
+
+static int check_fe(tsff_handle* h, const double* fe) {
+  if (h->fe_mode == TSFF_FE_PER_LINEOUT && !fe) return fail(h, -2, "fe_mode PER_LINEOUT needs fe[B][nvx]");
+  return 0;
+}
+
+// the batch of a spectrum call: what the nine batch arguments of an entry point say ([0] the electron feature, [1] the ion one)
+struct Batch {
+  const double *params, *fe, *data[2], *amps[2], *noise[2];
+  int B;
+};
+
+static int check_batch(tsff_handle* h, const Batch& b, bool need_data) {
+  if (!b.params || b.B < 1) return fail(h, -1, "bad argument");
+  for (int f = 0; f < 2; ++f) {
+    if (h->S.load[f] && need_data && !b.data[f]) return fail(h, -1, "%c_data missing", "ei"[f]);
+    if (h->S.load[f] && !b.amps[f]) return fail(h, -1, "%c_amps missing", "ei"[f]);
+  }
+  return check_fe(h, b.fe);
+}
+
+// the leaves a gradient mask asks for; m_ok: the DLM order m can be one (fe_mode DLM; tsff_angular_fit: a DLM deck)
+static int check_mask(tsff_handle* h, const uint8_t* gm, bool m_ok) {
+  if (gm[TSFF_P_M] && !m_ok)
+    return fail(h, -2, "gradient w.r.t. the DLM order m needs fe_mode == TSFF_FE_DLM (tsff_angular_fit: a DLM deck)");
+  for (int i = 0; i < h->n_ion; ++i)
+    if (gm[TSFF_P_ION0 + 4 * i + TSFF_ION_A]) return fail(h, -3, "A is not a differentiable leaf (ts_params.py:296)");
+  return 0;
+}
+
+// a list of n active slots, each in range and named once, as the gradient mask gm[kNP_MAX] (zeroed here), then check_mask
+static int check_slots(tsff_handle* h, const int32_t* act, int n, uint8_t* gm, bool m_ok) {
+  std::memset(gm, 0, kNP_MAX);
+  for (int k = 0; k < n; ++k) {
+    const int s = act[k];
+    if (s < 0 || s >= h->S.NP) return fail(h, -1, "active slot %d out of range", s);
+    if (gm[s]) return fail(h, -1, "active slot %d repeated", s);
+    gm[s] = 1;
+  }
+  return check_mask(h, gm, m_ok);
 }
 
 }  // namespace tsff
@@ -1172,9 +1204,9 @@ int tsff_chi_table(tsff_handle* h, const double* fe, int32_t n, double* W) {
 static int form_factor_impl(tsff_handle* h, int32_t feature, const double* phys, const double* fe, int32_t B, double* P) {
   if (!h || !phys || !P || B < 1 || feature < 0 || feature > 1) return fail(h, -1, "bad argument");
   if (h->fe_mode == TSFF_FE_DLM) return fail(h, -3, "tsff_form_factor takes explicit distribution functions (fe_mode SHARED or PER_LINEOUT)");
-  if (h->fe_mode == TSFF_FE_PER_LINEOUT && !fe) return fail(h, -2, "fe_mode PER_LINEOUT needs fe[B][nvx]");
-  int rc = ensure_workspace(h, B);
+  int rc = check_fe(h, fe);
   if (rc) return rc;
+  if ((rc = ensure_workspace(h, B))) return rc;
   KCall K{};
   K.params = phys; K.B = B;
   rc = prepare_tables(h, phys, fe, B, K);
@@ -1203,7 +1235,7 @@ static int form_factor_grad_impl(tsff_handle* h, int32_t feature, const double* 
   if (!h || !phys || !Pbar || !grad_phys || B < 1 || feature < 0 || feature > 1) return fail(h, -1, "bad argument");
   if (h->fe_mode == TSFF_FE_DLM) return fail(h, -3, "tsff_form_factor_grad takes explicit distribution functions (fe_mode SHARED or PER_LINEOUT)");
   if (grad_fe && h->fe_mode != TSFF_FE_PER_LINEOUT) return fail(h, -2, "gradient w.r.t. f_e needs fe_mode == TSFF_FE_PER_LINEOUT");
-  if (h->fe_mode == TSFF_FE_PER_LINEOUT && !fe) return fail(h, -2, "fe_mode PER_LINEOUT needs fe[B][nvx]");
+  if (int rc = check_fe(h, fe)) return rc;
   const size_t smem = form_factor_grad_smem(h, grad_fe != nullptr);
   if (smem > kLdsLimit) return fail(h, TSFF_ERR_LDS, "LDS budget exceeded (%zu B)", smem);
   int rc = ensure_workspace(h, B);
@@ -1581,21 +1613,14 @@ int tsff_ats_adjoint(tsff_handle* h, const double* P, const double* e_amps, doub
   return 0;
 }
 
-static int fill_call(tsff_handle* h, KCall& K, const double* params, const double* fe, const double* e_amps,
-                     const double* i_amps, const double* noise_e, const double* noise_i, int B, double* ThryE,
-                     double* ThryI, bool pipe = false) {
-  if (!h) return -1;
-  if (!params || B < 1) return fail(h, -1, "bad argument");
-  if (h->S.load[0] && !e_amps) return fail(h, -1, "e_amps missing");
-  if (h->S.load[1] && !i_amps) return fail(h, -1, "i_amps missing");
-  int rc = ensure_workspace(h, B);
-  if (rc) return rc;
-  K.params = params; K.B = B; K.b0 = 0; K.Btot = B;
-  K.amps[0] = e_amps; K.amps[1] = i_amps;
-  K.noise[0] = noise_e; K.noise[1] = noise_i;
+// the KCall of a batch and its tables.  Launches only: the batch is checked (check_batch) and the workspace sized
+// (ensure_workspace) by then
+static int fill_call(tsff_handle* h, KCall& K, const Batch& b, double* ThryE, double* ThryI, bool pipe = false) {
+  K.params = b.params; K.B = b.B; K.b0 = 0; K.Btot = b.B;
+  for (int f = 0; f < 2; ++f) { K.data[f] = b.data[f]; K.amps[f] = b.amps[f]; K.noise[f] = b.noise[f]; }
   K.thry[0] = ThryE; K.thry[1] = ThryI;
   K.lpart = h->lpart.as<double>();
-  return prepare_tables(h, params, fe, B, K, pipe);
+  return prepare_tables(h, b.params, b.fe, b.B, K, pipe);
 }
 
 int tsff_forward(tsff_handle* h, const double* params, const double* fe, const double* e_amps, const double* i_amps,
@@ -1604,15 +1629,15 @@ int tsff_forward(tsff_handle* h, const double* params, const double* fe, const d
   if (!h) return -1;
   if (h->S.load[0] && !ThryE) return fail(h, -1, "ThryE missing");
   if (h->S.load[1] && !ThryI) return fail(h, -1, "ThryI missing");
-  if (h->fe_mode == TSFF_FE_PER_LINEOUT && !fe) return fail(h, -2, "fe_mode PER_LINEOUT needs fe[B][nvx]");
-  if (params && B >= 1 && (!h->S.load[0] || e_amps) && (!h->S.load[1] || i_amps)) {   // (otherwise refused by fill_call)
-    if (int rc = size_plan<0, 0>(h, B)) return rc;
-    if (int rc = ensure_workspace(h, B)) return rc;
-  }
-  KCall K{};
-  int rc = fill_call(h, K, params, fe, e_amps, i_amps, noise_e, noise_i, B, ThryE, ThryI);
+  const Batch b{params, fe, {nullptr, nullptr}, {e_amps, i_amps}, {noise_e, noise_i}, B};
+  SpectrumPlan plan;
+  int rc = check_batch(h, b, false);
+  if (!rc) rc = size_plan<0, 0>(h, B, plan);
+  if (!rc) rc = ensure_workspace(h, B);
   if (rc) return rc;
-  return launch_spectrum<0>(h, K);
+  KCall K{};
+  if ((rc = fill_call(h, K, b, ThryE, ThryI))) return rc;
+  return launch_spectrum<0>(h, K, plan);
 }
 
 struct PackedOut {   // tsff_loss_grad_packed
@@ -1622,66 +1647,80 @@ struct PackedOut {   // tsff_loss_grad_packed
   double* packed = nullptr;
 };
 
-static int loss_grad_impl(tsff_handle* h, const double* params, const double* fe, const double* e_data, const double* i_data,
-                          const double* e_amps, const double* i_amps, const double* noise_e, const double* noise_i, int32_t B,
-                          const double* weights, const uint8_t* grad_mask, double* loss_terms, double* grad, double* grad_fe,
-                          bool want_fe, double* ThryE, double* ThryI, const PackedOut* po = nullptr) {
-  if (!h) return -1;
-  // every argument is checked before anything is enqueued: a refused call leaves nothing behind (fill_call launches the tables)
+// One loss + gradient evaluation: what it reads and where its results go (the entry point's), then what loss_grad_prepare
+// decided.  loss_grad_prepare holds everything that can refuse, allocate, upload or synchronise; loss_grad_enqueue only
+// launches, so a fit loop prepares once and enqueues once per step.
+struct LossGradCall {
+  Batch b;
+  const double* weights;
+  const uint8_t* grad_mask;
+  double *loss_terms, *grad, *grad_fe;
+  bool want_fe;            // tsff_loss_grad_fe: the f_e gradient too
+  double *ThryE, *ThryI;
+  const PackedOut* po;     // the packed form (loss_terms and grad are then the handle's)
+  bool with_m = false;     // loss_grad_prepare: the DLM order is a leaf
+  SpectrumPlan plan;       // loss_grad_prepare: the sized plan
+};
+
+// every argument is checked before anything is enqueued: a refused call leaves nothing behind
+static int loss_grad_prepare(tsff_handle* h, LossGradCall& c) {
+  const PackedOut* po = c.po;
+  const int B = c.b.B;
   if (po) {
     if (!po->act || !po->packed || po->n_act < 1 || po->n_act > h->S.NP || po->b_off < 0 || po->b_off + B > po->B_global)
       return fail(h, -1, "bad packed-output argument (slots %d, lineouts [%lld, %lld) of %lld)", (int)po->n_act, (long long)po->b_off,
                   (long long)(po->b_off + B), (long long)po->B_global);
     for (int k = 0; k < po->n_act; ++k)
       if (po->act[k] < 0 || po->act[k] >= h->S.NP) return fail(h, -1, "active slot %d out of range", (int)po->act[k]);
-    loss_terms = po->packed;
+    c.loss_terms = po->packed;
   }
-  if (!weights || !grad_mask || !loss_terms || (!po && !grad)) return fail(h, -1, "bad argument");
-  if (h->S.load[0] && !e_data) return fail(h, -1, "e_data missing");
-  if (h->S.load[1] && !i_data) return fail(h, -1, "i_data missing");
-  const bool with_m = grad_mask[TSFF_P_M] != 0;
-  if (with_m && h->fe_mode != TSFF_FE_DLM) return fail(h, -2, "gradient w.r.t. the DLM order m needs fe_mode == TSFF_FE_DLM");
-  if (want_fe && (h->fe_mode != TSFF_FE_PER_LINEOUT || !grad_fe))
+  if (!c.weights || !c.grad_mask || !c.loss_terms || (!po && !c.grad)) return fail(h, -1, "bad argument");
+  if (c.want_fe && (h->fe_mode != TSFF_FE_PER_LINEOUT || !c.grad_fe))
     return fail(h, -2, "gradient w.r.t. f_e needs fe_mode == TSFF_FE_PER_LINEOUT and an output buffer");
-  for (int s = 0; s < h->n_ion; ++s)
-    if (grad_mask[TSFF_P_ION0 + 4 * s + TSFF_ION_A]) return fail(h, -3, "A is not a differentiable leaf (ts_params.py:296)");
-  if (!params || B < 1) return fail(h, -1, "bad argument");
-  if (h->S.load[0] && !e_amps) return fail(h, -1, "e_amps missing");
-  if (h->S.load[1] && !i_amps) return fail(h, -1, "i_amps missing");
-  if (h->fe_mode == TSFF_FE_PER_LINEOUT && !fe) return fail(h, -2, "fe_mode PER_LINEOUT needs fe[B][nvx]");
-  int rc = 0;
+  int rc = check_mask(h, c.grad_mask, h->fe_mode == TSFF_FE_DLM);
+  if (!rc) rc = check_batch(h, c.b, true);
+  if (rc) return rc;
+  c.with_m = c.grad_mask[TSFF_P_M] != 0;
   // a changed mask / slot list is uploaded synchronously (pageable source, once per change) -- refused inside graph capture
-  if ((rc = upload_mask(h, grad_mask))) return rc;
+  if ((rc = upload_mask(h, c.grad_mask))) return rc;
   if (po && (rc = upload_slots(h, po->act, po->n_act))) return rc;
   // (the pipelined DLM plan forks onto the handle's second stream: not inside a capture, which this library keeps to one stream)
-  if (h->capturing && h->fe_mode == TSFF_FE_DLM && !want_fe && with_m && h->dlm_blocks > 1)
+  if (h->capturing && h->fe_mode == TSFF_FE_DLM && !c.want_fe && c.with_m && h->dlm_blocks > 1)
     return fail(h, -2, "graph capture: TSFF_OPT_DLM_BLOCKS > 1 would fork onto a second stream (set it to 0 before capturing)");
-  rc = want_fe ? size_plan<1, 2>(h, B) : with_m ? size_plan<1, 1>(h, B) : size_plan<1, 0>(h, B);
+  rc = c.want_fe ? size_plan<1, 2>(h, B, c.plan) : c.with_m ? size_plan<1, 1>(h, B, c.plan) : size_plan<1, 0>(h, B, c.plan);
   if (rc) return rc;
   if ((rc = ensure_workspace(h, B))) return rc;
-  if (want_fe) {
+  if (c.want_fe) {
     TSFF_ENSURE(h, h->Wb, (size_t)2 * B * kNXi2 * sizeof(double));    // (x 2: per-feature parts of the interleaved plan)
     TSFF_ENSURE(h, h->Hys, (size_t)2 * B * 2 * h->S.nvx * sizeof(double));
     TSFF_ENSURE(h, h->Yt, (size_t)B * 2 * kNXi1 * sizeof(double));
   }
   if (po) TSFF_ENSURE(h, h->gradws, (size_t)B * h->S.NP * sizeof(double));
+  return 0;
+}
+
+// the launches of a prepared call: the tables, the spectrum kernels of the plan, the reduction.  What can fail here is a HIP
+// error (the timing ring's events and the second stream of the pipelined DLM plan included)
+static int loss_grad_enqueue(tsff_handle* h, const LossGradCall& c) {
+  const PackedOut* po = c.po;
+  const int B = c.b.B;
+  const bool with_m = c.with_m;
+  double* const grad = po ? h->gradws.as<double>() : c.grad;
   KCall K{};
   // (the DLM order as a leaf, no table adjoints: the one-sweep kernel can take the per-lineout tables block by block)
-  const bool pipe = h->fe_mode == TSFF_FE_DLM && !want_fe && with_m;
-  rc = fill_call(h, K, params, fe, e_amps, i_amps, noise_e, noise_i, B, ThryE, ThryI, pipe);
+  const bool pipe = h->fe_mode == TSFF_FE_DLM && !c.want_fe && with_m;
+  int rc = fill_call(h, K, c.b, c.ThryE, c.ThryI, pipe);
   if (rc) return rc;
-  if (po) grad = h->gradws.as<double>();
-  K.data[0] = e_data; K.data[1] = i_data;
-  K.wts[0] = weights[0]; K.wts[1] = weights[1]; K.wts[2] = weights[2];
+  K.wts[0] = c.weights[0]; K.wts[1] = c.weights[1]; K.wts[2] = c.weights[2];
   K.denom_mode = h->denom_mode;
-  bool parts = false, lbrec = false;
-  if (want_fe) {
+  const bool parts = c.plan.gpart != 0, lbrec = c.plan.form == SpectrumForm::one_sweep;
+  if (c.want_fe) {
     const int nvx = h->S.nvx;
     K.Wb_out = h->Wb.as<double>();
     K.Hy_out = h->Hys.as<double>();
     K.Hs_out = K.Hy_out + (size_t)B * nvx;
     K.htm = nullptr; K.Wm = nullptr;  // the LDS region of the tangent tables holds the table adjoints
-    rc = launch_spectrum<1, 2>(h, K, h->gmask.as<uint8_t>(), grad, &parts);
+    rc = launch_spectrum<1, 2>(h, K, c.plan, h->gmask.as<uint8_t>(), grad);
     if (rc) return rc;
     if (parts) {
       const long nw = (long)B * kNXi2, nh = (long)2 * B * nvx;
@@ -1695,11 +1734,11 @@ static int loss_grad_impl(tsff_handle* h, const double* params, const double* fe
     TSFF_LAUNCH0(h, k_wgemm_t, ggrid, dim3(kThreads), 0, h->stream, h->S.lg, K.Wb_out, h->S.xi2, (int)B, h->Yt.as<double>());
     TSFF_HIP(h, hipGetLastError());
     TSFF_LAUNCH0(h, k_fe_adjoint, dim3(B), dim3(kThreads), h->smem_adjoint, h->stream, h->S, K.ht, h->Yt.as<double>(),
-                       K.Wb_out, K.Hy_out, K.Hs_out, grad_fe);
+                       K.Wb_out, K.Hy_out, K.Hs_out, c.grad_fe);
     TSFF_HIP(h, hipGetLastError());
   } else {
-    rc = with_m ? launch_spectrum<1, 1>(h, K, h->gmask.as<uint8_t>(), grad, &parts, &lbrec)
-                : launch_spectrum<1>(h, K, h->gmask.as<uint8_t>(), grad, &parts, &lbrec);
+    rc = with_m ? launch_spectrum<1, 1>(h, K, c.plan, h->gmask.as<uint8_t>(), grad)
+                : launch_spectrum<1>(h, K, c.plan, h->gmask.as<uint8_t>(), grad);
     if (rc) return rc;
   }
   const long ng = (long)B * h->S.NP;
@@ -1709,7 +1748,7 @@ static int loss_grad_impl(tsff_handle* h, const double* params, const double* fe
     const dim3 fgrid((unsigned)((B + per_wg - 1) / per_wg) + 1);   // (+ 1: the last workgroup reduces the loss sums)
     with_ion<kFusedMaxIon>(h->n_ion, [&](auto N) {
       TSFF_LAUNCH(h, k_fused_finish, (N.value), fgrid, dim3(kThreads), 0, h->stream, h->S, h->finrec.as<double>(), K.lbrec, K.lpart, (int)B,
-                  f0, nload, with_m ? 1 : 0, h->gmask.as<uint8_t>(), grad, po ? nullptr : loss_terms, po ? h->act.as<int>() : nullptr,
+                  f0, nload, with_m ? 1 : 0, h->gmask.as<uint8_t>(), grad, po ? nullptr : c.loss_terms, po ? h->act.as<int>() : nullptr,
                   po ? (int)po->n_act : 0, po ? (long)po->B_global : 0L, po ? (long)po->b_off : 0L, po ? po->packed : nullptr);
     });
   } else if (po) {
@@ -1719,10 +1758,16 @@ static int loss_grad_impl(tsff_handle* h, const double* params, const double* fe
                        (long)po->B_global, (long)po->b_off, po->packed);
   } else {
     TSFF_LAUNCH0(h, k_loss_reduce, dim3(parts ? (unsigned)std::min<long>((ng + kThreads - 1) / kThreads, 256) : 1), dim3(kThreads), 0,
-                       h->stream, K.lpart, (int)B, loss_terms, parts ? K.gpart : nullptr, ng, grad);
+                       h->stream, K.lpart, (int)B, c.loss_terms, parts ? K.gpart : nullptr, ng, grad);
   }
   TSFF_HIP(h, hipGetLastError());
   return 0;
+}
+
+static int loss_grad(tsff_handle* h, LossGradCall c) {
+  if (!h) return -1;
+  if (int rc = loss_grad_prepare(h, c)) return rc;
+  return loss_grad_enqueue(h, c);
 }
 
 int tsff_loss_grad(tsff_handle* h, const double* params, const double* fe, const double* e_data, const double* i_data,
@@ -1730,8 +1775,17 @@ int tsff_loss_grad(tsff_handle* h, const double* params, const double* fe, const
                    const double* weights, const uint8_t* grad_mask, double* loss_terms, double* grad, double* ThryE,
                    double* ThryI) {
   DevGuard dg__(h);
-  return loss_grad_impl(h, params, fe, e_data, i_data, e_amps, i_amps, noise_e, noise_i, B, weights, grad_mask, loss_terms,
-                        grad, nullptr, false, ThryE, ThryI);
+  const Batch b{params, fe, {e_data, i_data}, {e_amps, i_amps}, {noise_e, noise_i}, B};
+  return loss_grad(h, {b, weights, grad_mask, loss_terms, grad, nullptr, false, ThryE, ThryI, nullptr});
+}
+
+int tsff_loss_grad_fe(tsff_handle* h, const double* params, const double* fe, const double* e_data, const double* i_data,
+                      const double* e_amps, const double* i_amps, const double* noise_e, const double* noise_i, int32_t B,
+                      const double* weights, const uint8_t* grad_mask, double* loss_terms, double* grad, double* grad_fe,
+                      double* ThryE, double* ThryI) {
+  DevGuard dg__(h);
+  const Batch b{params, fe, {e_data, i_data}, {e_amps, i_amps}, {noise_e, noise_i}, B};
+  return loss_grad(h, {b, weights, grad_mask, loss_terms, grad, grad_fe, true, ThryE, ThryI, nullptr});
 }
 
 int tsff_loss_grad_packed(tsff_handle* h, const double* params, const double* fe, const double* e_data, const double* i_data,
@@ -1739,71 +1793,60 @@ int tsff_loss_grad_packed(tsff_handle* h, const double* params, const double* fe
                           const double* weights, const uint8_t* grad_mask, const int32_t* active_slots, int32_t n_active,
                           int64_t B_global, int64_t b_offset, double* packed, double* ThryE, double* ThryI) {
   DevGuard dg__(h);
-  if (!h) return -1;
-  PackedOut po;
-  po.act = active_slots; po.n_act = n_active; po.B_global = B_global; po.b_off = b_offset; po.packed = packed;
-  return loss_grad_impl(h, params, fe, e_data, i_data, e_amps, i_amps, noise_e, noise_i, B, weights, grad_mask, nullptr, nullptr,
-                        nullptr, false, ThryE, ThryI, &po);
+  const Batch b{params, fe, {e_data, i_data}, {e_amps, i_amps}, {noise_e, noise_i}, B};
+  const PackedOut po{active_slots, n_active, B_global, b_offset, packed};
+  return loss_grad(h, {b, weights, grad_mask, nullptr, nullptr, nullptr, false, ThryE, ThryI, &po});
 }
 
-// the 1-D Adam fit on the device (k_adam.inc): n_steps x (loss_grad_impl in its packed form + k_adam_step), all enqueued on the
-// handle's stream.  Everything a step needs -- the plan's scratch, the workspace, the packed buffer, the mask and the slot list
-// -- is sized and uploaded before the first launch, so the loop itself allocates nothing and never synchronises (each step's
-// loss_grad_impl finds the same mask, slot list and batch size in place: its upload and growth paths return before doing anything).
+// The set-up tsff_adam_fit and tsff_lbfgs_fit share once their arguments are checked (F.gm: the mask check_slots made of the
+// slot list): the packed buffer of 3 + n_active * B doubles their steps write and read, and loss_grad_prepare in the packed
+// form.  The loop that follows calls loss_grad_enqueue and its own step kernel, nothing else: it allocates nothing, never
+// synchronises and refuses nothing after the first launch.
+struct PackedFit {
+  uint8_t gm[kNP_MAX];
+  PackedOut po;
+  LossGradCall c;
+};
+static int prepare_packed_fit(tsff_handle* h, PackedFit& F, const Batch& b, const double* weights, const int32_t* act, int n_act) {
+  TSFF_ENSURE(h, h->fit_packed, (size_t)(3 + (long)n_act * b.B) * sizeof(double));
+  F.po = {act, n_act, b.B, 0, h->fit_packed.as<double>()};
+  F.c = {b, weights, F.gm, nullptr, nullptr, nullptr, false, nullptr, nullptr, &F.po};
+  return loss_grad_prepare(h, F.c);
+}
+
+// the 1-D Adam fit on the device (k_adam.inc): prepare_packed_fit, then n_steps x (loss_grad_enqueue + k_adam_step), all
+// enqueued on the handle's stream
 int tsff_adam_fit(tsff_handle* h, double* params, const double* fe, const double* e_data, const double* i_data, const double* e_amps,
                   const double* i_amps, const double* noise_e, const double* noise_i, int32_t B, const double* weights,
                   const int32_t* active_slots, int32_t n_active, int32_t n_steps, int32_t step0, const double* hyper, double* state,
                   double* loss_hist, double* best) {
   DevGuard dg__(h);
   if (!h) return -1;
-  // every argument is checked before anything is enqueued (a refused call leaves nothing behind)
   if (!params || B < 1 || !weights || !active_slots || !hyper || !state || !best || n_active < 1 || n_active > h->S.NP ||
       n_steps < 0 || step0 < 0 || (int64_t)step0 + n_steps > 0x7fffffffLL)
     return fail(h, -1, "bad argument");
-  uint8_t gm[kNP_MAX] = {};
-  for (int k = 0; k < n_active; ++k) {
-    const int s = active_slots[k];
-    if (s < 0 || s >= h->S.NP) return fail(h, -1, "active slot %d out of range", s);
-    if (gm[s]) return fail(h, -1, "active slot %d repeated", s);
-    gm[s] = 1;
-  }
-  if (gm[TSFF_P_M] && h->fe_mode != TSFF_FE_DLM) return fail(h, -2, "gradient w.r.t. the DLM order m needs fe_mode == TSFF_FE_DLM");
-  for (int i = 0; i < h->n_ion; ++i)
-    if (gm[TSFF_P_ION0 + 4 * i + TSFF_ION_A]) return fail(h, -3, "A is not a differentiable leaf (ts_params.py:296)");
-  if (h->S.load[0] && (!e_data || !e_amps)) return fail(h, -1, "e_data / e_amps missing");
-  if (h->S.load[1] && (!i_data || !i_amps)) return fail(h, -1, "i_data / i_amps missing");
-  if (h->fe_mode == TSFF_FE_PER_LINEOUT && !fe) return fail(h, -2, "fe_mode PER_LINEOUT needs fe[B][nvx]");
-  if (n_steps == 0) return 0;
-  const bool with_m = gm[TSFF_P_M] != 0;
-  if (h->capturing && h->fe_mode == TSFF_FE_DLM && with_m && h->dlm_blocks > 1)
-    return fail(h, -2, "graph capture: TSFF_OPT_DLM_BLOCKS > 1 would fork onto a second stream (set it to 0 before capturing)");
-  int rc = with_m ? size_plan<1, 1>(h, B) : size_plan<1, 0>(h, B);
-  if (rc) return rc;
-  if ((rc = ensure_workspace(h, B))) return rc;
-  TSFF_ENSURE(h, h->gradws, (size_t)B * h->S.NP * sizeof(double));
-  const long n = (long)n_active * B;
-  TSFF_ENSURE(h, h->adam_packed, (size_t)(3 + n) * sizeof(double));
+  const Batch b{params, fe, {e_data, i_data}, {e_amps, i_amps}, {noise_e, noise_i}, B};
+  PackedFit F;
+  int rc = check_slots(h, active_slots, n_active, F.gm, h->fe_mode == TSFF_FE_DLM);
+  if (!rc) rc = check_batch(h, b, true);
+  if (rc || n_steps == 0) return rc;
+  if ((rc = prepare_packed_fit(h, F, b, weights, active_slots, n_active))) return rc;
   TSFF_ENSURE(h, h->adam_best, 2 * sizeof(double));
-  if ((rc = upload_mask(h, gm))) return rc;
-  if ((rc = upload_slots(h, active_slots, n_active))) return rc;
+  const long n = (long)n_active * B;
   // the optimiser's scalars exactly as tree.Adam computes them in Python (1 - b1, -lr, 1 - b1**count: glibc pow is Python's **)
   const double lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3];
   const double omb1 = 1.0 - b1, omb2 = 1.0 - b2, neg_lr = -lr;
-  double* packed = h->adam_packed.as<double>();
+  const double* packed = F.po.packed;
   double* bl = h->adam_best.as<double>();   // bl[t & 1]: the best loss before step t, bl[(t + 1) & 1]: after it
   double* mu = state;
   double* nu = state + n;
-  PackedOut po;
-  po.act = active_slots; po.n_act = n_active; po.B_global = B; po.b_off = 0; po.packed = packed;
   TSFF_HIP(h, hipMemcpyAsync(bl, best, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
   const dim3 agrid((unsigned)std::min<long>((n + kThreads - 1) / kThreads, 1024));
   for (int t = 0; t < n_steps; ++t) {
-    rc = loss_grad_impl(h, params, fe, e_data, i_data, e_amps, i_amps, noise_e, noise_i, B, weights, gm, nullptr, nullptr, nullptr,
-                        false, nullptr, nullptr, &po);
-    if (rc) return rc;
+    if ((rc = loss_grad_enqueue(h, F.c))) return rc;
     const double count = (double)step0 + t + 1;
     const double c1 = 1.0 - std::pow(b1, count), c2 = 1.0 - std::pow(b2, count);
-    TSFF_LAUNCH0(h, k_adam_step, agrid, dim3(kThreads), 0, h->stream, (const double*)packed, weights[0], weights[1], weights[2],
+    TSFF_LAUNCH0(h, k_adam_step, agrid, dim3(kThreads), 0, h->stream, packed, weights[0], weights[1], weights[2],
                  h->act.as<int>(), (int)n_active, (int)B, h->S.NP, params, mu, nu, b1, omb1, b2, omb2, neg_lr, c1, c2, eps,
                  loss_hist ? loss_hist + t : nullptr, (const double*)(bl + (t & 1)), bl + ((t + 1) & 1),
                  t == n_steps - 1 ? best : nullptr, best + 1);
@@ -1835,16 +1878,8 @@ int tsff_angular_fit(tsff_handle* h, const tsff_angular_spec* sp, double* leaves
   if (gen != TSFF_ANG_ARB2V && !gen_data) return fail(h, -1, "gen_data missing");
   if (sp->method != TSFF_ANG_ADAM && sp->method != TSFF_ANG_RMSPROP) return fail(h, -2, "unknown optimiser %d", sp->method);
   if (sp->loss_method < 0 || sp->loss_method > 3) return fail(h, -2, "unknown loss method %d", sp->loss_method);
-  uint8_t gm[kNP_MAX] = {};
-  for (int k = 0; k < sp->n_active; ++k) {
-    const int s = sp->active_slots[k];
-    if (s < 0 || s >= h->S.NP) return fail(h, -1, "active slot %d out of range", s);
-    if (gm[s]) return fail(h, -1, "active slot %d repeated", s);
-    gm[s] = 1;
-  }
-  if (gm[TSFF_P_M] && gen != TSFF_ANG_DLM) return fail(h, -2, "the DLM order m is a leaf of DLM decks only");
-  for (int i = 0; i < h->n_ion; ++i)
-    if (gm[TSFF_P_ION0 + 4 * i + TSFF_ION_A]) return fail(h, -3, "A is not a differentiable leaf (ts_params.py:296)");
+  uint8_t gm[kNP_MAX];
+  if (int rc = check_slots(h, sp->active_slots, sp->n_active, gm, gen == TSFF_ANG_DLM)) return rc;   // (m: a leaf of DLM decks only)
   const long n_table = gen == TSFF_ANG_ARB2V ? (long)nv * nv : 0;
   const long n = sp->n_active + n_table;
   if (n < 1) return fail(h, -1, "nothing to train");
@@ -1932,16 +1967,14 @@ int tsff_lbfgs_state_size(int32_t B, int32_t n_active, int32_t maxcor, int64_t* 
   return 0;
 }
 
-// the 1-D L-BFGS-B fit on the device (k_lbfgs.inc): n_evals x (loss_grad_impl in its packed form + lb_passes(maxcor) launches of
-// k_lbfgs_step on lb_blocks(n) workgroups), all enqueued on
-// the handle's stream, sized and uploaded before the first launch exactly as tsff_adam_fit is.
+// the 1-D L-BFGS-B fit on the device (k_lbfgs.inc): prepare_packed_fit, then n_evals x (loss_grad_enqueue + lb_passes(maxcor)
+// launches of k_lbfgs_step on lb_blocks(n) workgroups), all enqueued on the handle's stream
 int tsff_lbfgs_fit(tsff_handle* h, double* params, const double* fe, const double* e_data, const double* i_data, const double* e_amps,
                    const double* i_amps, const double* noise_e, const double* noise_i, int32_t B, const double* weights,
                    const int32_t* active_slots, int32_t n_active, int32_t n_evals, const double* opts, double* state, int64_t n_state,
                    double* f_hist, int32_t* info) {
   DevGuard dg__(h);
   if (!h) return -1;
-  // every argument is checked before anything is enqueued (a refused call leaves nothing behind)
   if (!params || B < 1 || !weights || !active_slots || !opts || !state || n_active < 1 || n_active > h->S.NP || n_evals < 0)
     return fail(h, -1, "bad argument");
   const double maxcor_d = opts[0], ftol = opts[1], gtol = opts[2], maxiter_d = opts[3], maxfun_d = opts[4], maxls_d = opts[5];
@@ -1949,64 +1982,34 @@ int tsff_lbfgs_fit(tsff_handle* h, double* params, const double* fe, const doubl
   if (!whole(maxcor_d, 1, kLbMaxCor) || !whole(maxiter_d, 0, 0x7fffffff) || !whole(maxfun_d, 0, 0x7fffffff) ||
       !whole(maxls_d, 1, 0x7fffffff) || !(ftol >= 0.0) || !(gtol >= 0.0))
     return fail(h, -1, "bad option (opts = maxcor in [1, %d], ftol >= 0, gtol >= 0, maxiter >= 0, maxfun >= 0, maxls >= 1)", kLbMaxCor);
-  uint8_t gm[kNP_MAX] = {};
-  for (int k = 0; k < n_active; ++k) {
-    const int s = active_slots[k];
-    if (s < 0 || s >= h->S.NP) return fail(h, -1, "active slot %d out of range", s);
-    if (gm[s]) return fail(h, -1, "active slot %d repeated", s);
-    gm[s] = 1;
-  }
-  if (gm[TSFF_P_M] && h->fe_mode != TSFF_FE_DLM) return fail(h, -2, "gradient w.r.t. the DLM order m needs fe_mode == TSFF_FE_DLM");
-  for (int i = 0; i < h->n_ion; ++i)
-    if (gm[TSFF_P_ION0 + 4 * i + TSFF_ION_A]) return fail(h, -3, "A is not a differentiable leaf (ts_params.py:296)");
-  if (h->S.load[0] && (!e_data || !e_amps)) return fail(h, -1, "e_data / e_amps missing");
-  if (h->S.load[1] && (!i_data || !i_amps)) return fail(h, -1, "i_data / i_amps missing");
-  if (h->fe_mode == TSFF_FE_PER_LINEOUT && !fe) return fail(h, -2, "fe_mode PER_LINEOUT needs fe[B][nvx]");
+  const Batch b{params, fe, {e_data, i_data}, {e_amps, i_amps}, {noise_e, noise_i}, B};
+  PackedFit F;
+  int rc = check_slots(h, active_slots, n_active, F.gm, h->fe_mode == TSFF_FE_DLM);
+  if (!rc) rc = check_batch(h, b, true);
+  if (rc) return rc;
   const int maxcor = (int)maxcor_d;
   int64_t need = 0;
   if (tsff_lbfgs_state_size(B, n_active, maxcor, &need) || n_state < need)
     return fail(h, -1, "state holds %lld doubles, needs %lld", (long long)n_state, (long long)need);
   if (n_evals == 0) return 0;
-  const bool with_m = gm[TSFF_P_M] != 0;
-  if (h->capturing && h->fe_mode == TSFF_FE_DLM && with_m && h->dlm_blocks > 1)
-    return fail(h, -2, "graph capture: TSFF_OPT_DLM_BLOCKS > 1 would fork onto a second stream (set it to 0 before capturing)");
-  int rc = with_m ? size_plan<1, 1>(h, B) : size_plan<1, 0>(h, B);
-  if (rc) return rc;
-  if ((rc = ensure_workspace(h, B))) return rc;
-  TSFF_ENSURE(h, h->gradws, (size_t)B * h->S.NP * sizeof(double));
+  if ((rc = prepare_packed_fit(h, F, b, weights, active_slots, n_active))) return rc;
   const long n = (long)n_active * B;
-  TSFF_ENSURE(h, h->lbfgs_packed, (size_t)(3 + n) * sizeof(double));
-  if ((rc = upload_mask(h, gm))) return rc;
-  if ((rc = upload_slots(h, active_slots, n_active))) return rc;
   // mainlb's tol = factr * epsmch with the wrapper's factr = ftol / eps (lbfgs.Lbfgs)
   const double tol = (ftol / kLbEps) * kLbEps;
   const int maxiter = (int)maxiter_d, maxfun = (int)maxfun_d, maxls = (int)maxls_d;
-  double* packed = h->lbfgs_packed.as<double>();
+  const double* packed = F.po.packed;
   const dim3 grid((unsigned)lb_blocks(n));
   const int passes = lb_passes(maxcor);
-  PackedOut po;
-  po.act = active_slots; po.n_act = n_active; po.B_global = B; po.b_off = 0; po.packed = packed;
   for (int t = 0; t < n_evals; ++t) {
-    rc = loss_grad_impl(h, params, fe, e_data, i_data, e_amps, i_amps, noise_e, noise_i, B, weights, gm, nullptr, nullptr, nullptr,
-                        false, nullptr, nullptr, &po);
-    if (rc) return rc;
+    if ((rc = loss_grad_enqueue(h, F.c))) return rc;
     for (int k = 0; k < passes; ++k) {   // (a pass the evaluation does not need returns at once)
-      TSFF_LAUNCH0(h, k_lbfgs_step, grid, dim3(kLbThreads), 0, h->stream, (const double*)packed, weights[0], weights[1], weights[2],
+      TSFF_LAUNCH0(h, k_lbfgs_step, grid, dim3(kLbThreads), 0, h->stream, packed, weights[0], weights[1], weights[2],
                    h->act.as<int>(), (int)n_active, (int)B, h->S.NP, params, state, maxcor, tol, gtol, maxiter, maxfun, maxls, k,
                    f_hist ? f_hist + t : nullptr, info);
       TSFF_HIP(h, hipGetLastError());
     }
   }
   return 0;
-}
-
-int tsff_loss_grad_fe(tsff_handle* h, const double* params, const double* fe, const double* e_data, const double* i_data,
-                      const double* e_amps, const double* i_amps, const double* noise_e, const double* noise_i, int32_t B,
-                      const double* weights, const uint8_t* grad_mask, double* loss_terms, double* grad, double* grad_fe,
-                      double* ThryE, double* ThryI) {
-  DevGuard dg__(h);
-  return loss_grad_impl(h, params, fe, e_data, i_data, e_amps, i_amps, noise_e, noise_i, B, weights, grad_mask, loss_terms,
-                        grad, grad_fe, true, ThryE, ThryI);
 }
 
 int tsff_pack_fe_rows(tsff_handle* h, const double* loss_terms, const double* grad, const double* grad_fe, int32_t B,
@@ -2037,33 +2040,21 @@ int tsff_loss_hess(tsff_handle* h, const double* params, const double* fe, const
   if (!h) return -1;
   if (!weights || !active_slots || !loss_terms || !grad || !hess || n_active < 1 || n_active > h->S.NP)
     return fail(h, -1, "bad argument");
+  uint8_t gm[kNP_MAX];
+  if (int rc = check_slots(h, active_slots, n_active, gm, h->fe_mode == TSFF_FE_DLM)) return rc;
   HessArgs A{};
   A.n = n_active;
   A.npair = n_active * (n_active + 1) / 2;
-  for (int k = 0; k < n_active; ++k) {
-    const int s = active_slots[k];
-    if (s < 0 || s >= h->S.NP) return fail(h, -1, "active slot %d out of range", s);
-    for (int q = 0; q < k; ++q)
-      if (active_slots[q] == s) return fail(h, -1, "active slot %d repeated", s);
-    A.slot[k] = s;
-  }
-  for (int k = 0; k < n_active; ++k) {
-    const int s = active_slots[k];
-    if (s == TSFF_P_M && h->fe_mode != TSFF_FE_DLM)
-      return fail(h, -2, "gradient w.r.t. the DLM order m needs fe_mode == TSFF_FE_DLM");
-    for (int i = 0; i < h->n_ion; ++i)
-      if (s == TSFF_P_ION0 + 4 * i + TSFF_ION_A) return fail(h, -3, "A is not a differentiable leaf (ts_params.py:296)");
-    if (s == TSFF_P_M) A.with_m = 1;
-  }
+  std::copy(active_slots, active_slots + n_active, A.slot);
+  A.with_m = gm[TSFF_P_M];
   if ((long)B * A.npair > 0x7fffffffL) return fail(h, -1, "too many (lineout, pair) tasks");
   A.tasks = B * A.npair;
-  if (h->S.load[0] && !e_data) return fail(h, -1, "e_data missing");
-  if (h->S.load[1] && !i_data) return fail(h, -1, "i_data missing");
+  const Batch b{params, fe, {e_data, i_data}, {e_amps, i_amps}, {noise_e, noise_i}, B};
+  if (int rc = check_batch(h, b, true)) return rc;
   const size_t smem = sizeof(double) * hess_smem_doubles(h->S, A.with_m != 0);
   if (smem > kLdsLimit)
     return fail(h, -2, "tsff_loss_hess: LDS budget exceeded (%zu B with nvx = %d%s): reduce nvx", smem, h->S.nvx,
                 A.with_m ? " and the DLM order as a leaf" : "");
-  if (h->fe_mode == TSFF_FE_PER_LINEOUT && !fe) return fail(h, -2, "fe_mode PER_LINEOUT needs fe[B][nvx]");
   // every buffer of the call before the first launch (fill_call enqueues the tables)
   const int nwg = std::min(A.tasks, kHessMaxWG);
   if (A.with_m) {
@@ -2076,12 +2067,10 @@ int tsff_loss_hess(tsff_handle* h, const double* params, const double* fe, const
   }
   TSFF_ENSURE(h, h->hws, (size_t)nwg * 4 * h->S.npts * sizeof(double));
   TSFF_ENSURE(h, h->hout, (size_t)A.tasks * 12 * sizeof(double));
-  if (params && B >= 1 && (!h->S.load[0] || e_amps) && (!h->S.load[1] || i_amps))   // (otherwise refused by fill_call)
-    if (int rc = ensure_workspace(h, B)) return rc;
-  KCall K{};
-  int rc = fill_call(h, K, params, fe, e_amps, i_amps, noise_e, noise_i, B, nullptr, nullptr);
+  int rc = ensure_workspace(h, B);
   if (rc) return rc;
-  K.data[0] = e_data; K.data[1] = i_data;
+  KCall K{};
+  if ((rc = fill_call(h, K, b, nullptr, nullptr))) return rc;
   if (A.with_m) {   // second m-derivative tables: k_hess_mtab, then the shipped W-table GEMM on its rows
     const size_t nvx = h->S.nvx;
     const size_t smem_t = sizeof(double2) * 6 * nvx + sizeof(double) * (nvx + 2 * kNXi1 + 8);
@@ -2120,19 +2109,18 @@ int tsff_array_loss(tsff_handle* h, const double* params, const double* fe, cons
   DevGuard dg__(h);
   if (!h) return -1;
   if (!sums) return fail(h, -1, "bad argument");
-  if (h->S.load[0] && !e_data) return fail(h, -1, "e_data missing");
-  if (h->S.load[1] && !i_data) return fail(h, -1, "i_data missing");
-  if (h->fe_mode == TSFF_FE_PER_LINEOUT && !fe) return fail(h, -2, "fe_mode PER_LINEOUT needs fe[B][nvx]");
-  if (params && B >= 1 && (!h->S.load[0] || e_amps) && (!h->S.load[1] || i_amps))   // (otherwise refused by fill_call)
-    if (int rc = size_plan<2, 0>(h, B)) return rc;
-  KCall K{};
-  int rc = fill_call(h, K, params, fe, e_amps, i_amps, noise_e, noise_i, B, ThryE, ThryI);
+  const Batch b{params, fe, {e_data, i_data}, {e_amps, i_amps}, {noise_e, noise_i}, B};
+  SpectrumPlan plan;
+  int rc = check_batch(h, b, true);
+  if (!rc) rc = size_plan<2, 0>(h, B, plan);
+  if (!rc) rc = ensure_workspace(h, B);
   if (rc) return rc;
-  K.data[0] = e_data; K.data[1] = i_data;
+  KCall K{};
+  if ((rc = fill_call(h, K, b, ThryE, ThryI))) return rc;
   K.sqdev[0] = sqdev_e; K.sqdev[1] = sqdev_i;
   K.lpart = sums;
   TSFF_HIP(h, hipMemsetAsync(sums, 0, (size_t)B * 3 * sizeof(double), h->stream));
-  return launch_spectrum<2>(h, K);
+  return launch_spectrum<2>(h, K, plan);
 }
 
 #ifdef TSFF_TRACE

@@ -360,6 +360,20 @@ class Engine:
         t = self.dev(a)
         return t.reshape(B, L.NBINS).contiguous()
 
+    def _batch_args(self, X, batch, fe=None, need_data=True):
+        """The batch arguments of an entry point: -> (tensors, args).  ``args``: the C ABI's ``params, fe, e_data, i_data, e_amps,
+        i_amps, noise_e, noise_i, B`` for the lineouts of ``X`` [B, NP] (a feature that is not loaded: null; ``need_data=False``:
+        null data); ``tensors``: the device tensors behind them -- hold on to it until the library call has returned."""
+        B = X.shape[0]
+        ed = self._mat(batch["e_data"], B) if need_data and self.load_ele else None
+        idt = self._mat(batch["i_data"], B) if need_data and self.load_ion else None
+        ea = self._vec(batch["e_amps"], B) if self.load_ele else None
+        ia = self._vec(batch["i_amps"], B) if self.load_ion else None
+        ne_, ni_ = self._mat(batch.get("noise_e"), B), self._mat(batch.get("noise_i"), B)
+        fe_d = self.dev(fe)
+        p = self._ptr
+        return (X, fe_d, ed, idt, ea, ia, ne_, ni_), (p(X), p(fe_d), p(ed), p(idt), p(ea), p(ia), p(ne_), p(ni_), B)
+
     # ---- entry points ---------------------------------------------------------------------------
     def chi_table(self, fe):
         torch = self.torch
@@ -523,16 +537,12 @@ class Engine:
         torch = self.torch
         X = self.dev(params).reshape(-1, self.NP)
         B = X.shape[0]
-        ea = self._vec(e_amps, B) if self.load_ele else None
-        ia = self._vec(i_amps, B) if self.load_ion else None
-        ne_, ni_ = self._mat(noise_e, B), self._mat(noise_i, B)
-        fe_d = self.dev(fe)
+        keep, ba = self._batch_args(X, dict(e_amps=e_amps, i_amps=i_amps, noise_e=noise_e, noise_i=noise_i), fe, need_data=False)
         # (the kernel writes every entry of a loaded feature; a feature that is not loaded comes back as zeros)
         E = (torch.empty if self.load_ele else torch.zeros)((B, L.NBINS), dtype=torch.float64, device=self.device)
         I = (torch.empty if self.load_ion else torch.zeros)((B, L.NBINS), dtype=torch.float64, device=self.device)
         self._sync_stream()
-        rc = self.lib.tsff_forward(self.h, self._ptr(X), self._ptr(fe_d), self._ptr(ea), self._ptr(ia), self._ptr(ne_),
-                                   self._ptr(ni_), B, self._ptr(E), self._ptr(I))
+        rc = self.lib.tsff_forward(self.h, *ba[:2], *ba[4:], self._ptr(E), self._ptr(I))   # (no data arguments)
         L.check(self.lib, self.h, rc)
         return E, I
 
@@ -561,12 +571,7 @@ class Engine:
         torch = self.torch
         X = self.dev(params).reshape(-1, self.NP)
         B = X.shape[0]
-        ea = self._vec(batch["e_amps"], B) if self.load_ele else None
-        ia = self._vec(batch["i_amps"], B) if self.load_ion else None
-        ed = self._mat(batch["e_data"], B) if self.load_ele else None
-        idt = self._mat(batch["i_data"], B) if self.load_ion else None
-        ne_, ni_ = self._mat(batch.get("noise_e"), B), self._mat(batch.get("noise_i"), B)
-        fe_d = self.dev(fe)
+        keep, ba = self._batch_args(X, batch, fe)
         if out is None:
             terms = torch.empty(3, dtype=torch.float64, device=self.device)
             grad = torch.empty((B, self.NP), dtype=torch.float64, device=self.device)
@@ -579,15 +584,12 @@ class Engine:
         self._sync_stream()
         if want_fe_grad:
             gfe = torch.empty((B, self.nvx), dtype=torch.float64, device=self.device)
-            rc = self.lib.tsff_loss_grad_fe(self.h, self._ptr(X), self._ptr(fe_d), self._ptr(ed), self._ptr(idt), self._ptr(ea),
-                                            self._ptr(ia), self._ptr(ne_), self._ptr(ni_), B, w.ctypes.data_as(L.c_double_p),
-                                            gm.ctypes.data_as(L.c_uint8_p), self._ptr(terms), self._ptr(grad), self._ptr(gfe),
-                                            self._ptr(E), self._ptr(I))
+            rc = self.lib.tsff_loss_grad_fe(self.h, *ba, w.ctypes.data_as(L.c_double_p), gm.ctypes.data_as(L.c_uint8_p),
+                                            self._ptr(terms), self._ptr(grad), self._ptr(gfe), self._ptr(E), self._ptr(I))
             L.check(self.lib, self.h, rc)
             return terms, grad, E, I, gfe
-        rc = self.lib.tsff_loss_grad(self.h, self._ptr(X), self._ptr(fe_d), self._ptr(ed), self._ptr(idt), self._ptr(ea),
-                                     self._ptr(ia), self._ptr(ne_), self._ptr(ni_), B, w.ctypes.data_as(L.c_double_p),
-                                     gm.ctypes.data_as(L.c_uint8_p), self._ptr(terms), self._ptr(grad), self._ptr(E), self._ptr(I))
+        rc = self.lib.tsff_loss_grad(self.h, *ba, w.ctypes.data_as(L.c_double_p), gm.ctypes.data_as(L.c_uint8_p),
+                                     self._ptr(terms), self._ptr(grad), self._ptr(E), self._ptr(I))
         L.check(self.lib, self.h, rc)
         return terms, grad, E, I
 
@@ -600,21 +602,14 @@ class Engine:
         B = X.shape[0]
         act = np.ascontiguousarray(active_slots, dtype=np.int32)
         P = int(act.size)
-        ea = self._vec(batch["e_amps"], B) if self.load_ele else None
-        ia = self._vec(batch["i_amps"], B) if self.load_ion else None
-        ed = self._mat(batch["e_data"], B) if self.load_ele else None
-        idt = self._mat(batch["i_data"], B) if self.load_ion else None
-        ne_, ni_ = self._mat(batch.get("noise_e"), B), self._mat(batch.get("noise_i"), B)
-        fe_d = self.dev(fe)
+        keep, ba = self._batch_args(X, batch, fe)
         terms = torch.empty(3, dtype=torch.float64, device=self.device)
         grad = torch.empty((B, P), dtype=torch.float64, device=self.device)
         hess = torch.empty((B, P, P), dtype=torch.float64, device=self.device)
         w = np.ascontiguousarray(weights, dtype=np.float64)
         self._sync_stream()
-        rc = self.lib.tsff_loss_hess(self.h, self._ptr(X), self._ptr(fe_d), self._ptr(ed), self._ptr(idt), self._ptr(ea),
-                                     self._ptr(ia), self._ptr(ne_), self._ptr(ni_), B, w.ctypes.data_as(L.c_double_p),
-                                     act.ctypes.data_as(C.POINTER(C.c_int32)), P, self._ptr(terms), self._ptr(grad),
-                                     self._ptr(hess))
+        rc = self.lib.tsff_loss_hess(self.h, *ba, w.ctypes.data_as(L.c_double_p), act.ctypes.data_as(C.POINTER(C.c_int32)), P,
+                                     self._ptr(terms), self._ptr(grad), self._ptr(hess))
         L.check(self.lib, self.h, rc)
         return terms, grad, hess
 
@@ -644,11 +639,7 @@ class Engine:
         B = X.shape[0]
         Bg = int(B_global) if B_global is not None else B
         act = np.ascontiguousarray(active_slots, dtype=np.int32)
-        ea = self._vec(batch["e_amps"], B) if self.load_ele else None
-        ia = self._vec(batch["i_amps"], B) if self.load_ion else None
-        ed = self._mat(batch["e_data"], B) if self.load_ele else None
-        idt = self._mat(batch["i_data"], B) if self.load_ion else None
-        ne_, ni_ = self._mat(batch.get("noise_e"), B), self._mat(batch.get("noise_i"), B)
+        keep, ba = self._batch_args(X, batch)   # (a null fe)
         if out is None:
             key = ("packed", act.size, Bg)
             out = self._staging.get(key)
@@ -661,8 +652,7 @@ class Engine:
         w = np.ascontiguousarray(weights, dtype=np.float64)
         gm = np.ascontiguousarray(grad_mask, dtype=np.uint8)
         self._sync_stream()
-        rc = self.lib.tsff_loss_grad_packed(self.h, self._ptr(X), None, self._ptr(ed), self._ptr(idt), self._ptr(ea), self._ptr(ia),
-                                            self._ptr(ne_), self._ptr(ni_), B, w.ctypes.data_as(L.c_double_p), gm.ctypes.data_as(L.c_uint8_p),
+        rc = self.lib.tsff_loss_grad_packed(self.h, *ba, w.ctypes.data_as(L.c_double_p), gm.ctypes.data_as(L.c_uint8_p),
                                             act.ctypes.data_as(C.POINTER(C.c_int32)), int(act.size), Bg, int(b_offset), self._ptr(out),
                                             self._ptr(E), self._ptr(I))
         L.check(self.lib, self.h, rc)
@@ -681,12 +671,7 @@ class Engine:
         B = X.shape[0]
         act = np.ascontiguousarray(active_slots, dtype=np.int32)
         P = int(act.size)
-        ea = self._vec(batch["e_amps"], B) if self.load_ele else None
-        ia = self._vec(batch["i_amps"], B) if self.load_ion else None
-        ed = self._mat(batch["e_data"], B) if self.load_ele else None
-        idt = self._mat(batch["i_data"], B) if self.load_ion else None
-        ne_, ni_ = self._mat(batch.get("noise_e"), B), self._mat(batch.get("noise_i"), B)
-        fe_d = self.dev(fe)
+        keep, ba = self._batch_args(X, batch, fe)
         state = torch.zeros((2, P, B), dtype=torch.float64, device=self.device) if state is None else self.dev(state)
         assert state.numel() == 2 * P * B, f"state must hold 2 x {P} x {B} values"
         if best is None:
@@ -699,8 +684,7 @@ class Engine:
         hy = np.ascontiguousarray(hyper, dtype=np.float64)
         assert hy.size == 4, "hyper = (lr, b1, b2, eps)"
         self._sync_stream()
-        rc = self.lib.tsff_adam_fit(self.h, self._ptr(X), self._ptr(fe_d), self._ptr(ed), self._ptr(idt), self._ptr(ea), self._ptr(ia),
-                                    self._ptr(ne_), self._ptr(ni_), B, w.ctypes.data_as(L.c_double_p),
+        rc = self.lib.tsff_adam_fit(self.h, *ba, w.ctypes.data_as(L.c_double_p),
                                     act.ctypes.data_as(C.POINTER(C.c_int32)), P, int(n_steps), int(step0),
                                     hy.ctypes.data_as(L.c_double_p), self._ptr(state), self._ptr(hist), self._ptr(best))
         L.check(self.lib, self.h, rc)
@@ -757,12 +741,7 @@ class Engine:
         B = X.shape[0]
         act = np.ascontiguousarray(active_slots, dtype=np.int32)
         P = int(act.size)
-        ea = self._vec(batch["e_amps"], B) if self.load_ele else None
-        ia = self._vec(batch["i_amps"], B) if self.load_ion else None
-        ed = self._mat(batch["e_data"], B) if self.load_ele else None
-        idt = self._mat(batch["i_data"], B) if self.load_ion else None
-        ne_, ni_ = self._mat(batch.get("noise_e"), B), self._mat(batch.get("noise_i"), B)
-        fe_d = self.dev(fe)
+        keep, ba = self._batch_args(X, batch, fe)
         op = np.ascontiguousarray(opts, dtype=np.float64)
         assert op.size == 6, "opts = (maxcor, ftol, gtol, maxiter, maxfun, maxls)"
         if state is None:
@@ -777,8 +756,7 @@ class Engine:
         hist = torch.empty(max(int(n_evals), 0), dtype=torch.float64, device=self.device) if f_hist else None
         w = np.ascontiguousarray(weights, dtype=np.float64)
         self._sync_stream()
-        rc = self.lib.tsff_lbfgs_fit(self.h, self._ptr(X), self._ptr(fe_d), self._ptr(ed), self._ptr(idt), self._ptr(ea), self._ptr(ia),
-                                     self._ptr(ne_), self._ptr(ni_), B, w.ctypes.data_as(L.c_double_p),
+        rc = self.lib.tsff_lbfgs_fit(self.h, *ba, w.ctypes.data_as(L.c_double_p),
                                      act.ctypes.data_as(C.POINTER(C.c_int32)), P, int(n_evals), op.ctypes.data_as(L.c_double_p),
                                      self._ptr(state), int(state.numel()), self._ptr(hist), self._ptr(info))
         L.check(self.lib, self.h, rc)
@@ -805,19 +783,12 @@ class Engine:
         torch = self.torch
         X = self.dev(params).reshape(-1, self.NP)
         B = X.shape[0]
-        ea = self._vec(batch["e_amps"], B) if self.load_ele else None
-        ia = self._vec(batch["i_amps"], B) if self.load_ion else None
-        ed = self._mat(batch["e_data"], B) if self.load_ele else None
-        idt = self._mat(batch["i_data"], B) if self.load_ion else None
-        ne_, ni_ = self._mat(batch.get("noise_e"), B), self._mat(batch.get("noise_i"), B)
-        fe_d = self.dev(fe)
+        keep, ba = self._batch_args(X, batch, fe)
         z = lambda: torch.zeros((B, L.NBINS), dtype=torch.float64, device=self.device)
         sums = torch.zeros((B, 3), dtype=torch.float64, device=self.device)
         sqe, sqi, E, I = z(), z(), z(), z()
         self._sync_stream()
-        rc = self.lib.tsff_array_loss(self.h, self._ptr(X), self._ptr(fe_d), self._ptr(ed), self._ptr(idt), self._ptr(ea),
-                                      self._ptr(ia), self._ptr(ne_), self._ptr(ni_), B, self._ptr(sums), self._ptr(sqe),
-                                      self._ptr(sqi), self._ptr(E), self._ptr(I))
+        rc = self.lib.tsff_array_loss(self.h, *ba, self._ptr(sums), self._ptr(sqe), self._ptr(sqi), self._ptr(E), self._ptr(I))
         L.check(self.lib, self.h, rc)
         return sums, sqe, sqi, E, I
 

@@ -20,6 +20,37 @@ from .params import ThomsonParams
 ADAM_B1, ADAM_B2, ADAM_EPS = 0.9, 0.999, 1e-8   # optax.adam's defaults (the reference passes the learning rate only)
 
 
+def _one_d_setup(name: str, config: Dict, loss_fn, previous_weights: Optional[ThomsonParams], batch: Dict):
+    """What ``adam_loop`` and ``lbfgs_loop`` share before their first enqueue: the refusals (NotImplementedError, before any
+    device work), the weights, their trained part and its slots, and the engine with the batch on the device.
+    -> (ts_params, diff, act, eng, X, B, w, db, fe); fe: the constant table of a free-form f_e that is not trained, else None."""
+    if getattr(loss_fn, "angular", False) or "angular" in config["other"]["extraoptions"]["spectype"]:
+        raise NotImplementedError(f"{name}: angular decks run through the reference's angular loop, not a 1-D loop")
+    if getattr(loss_fn, "distributed", False):
+        raise NotImplementedError(f"{name}: distributed=True is not built (each step would all-reduce its packed buffer)")
+    ts_params = previous_weights if previous_weights is not None else \
+        ThomsonParams(config["parameters"], config["optimizer"]["batch_size"], activate=True)
+    sm = ts_params.slots
+    if sm.fval_active or sm.gen2d_active or getattr(sm, "fval2d_active", False):
+        raise NotImplementedError(f"{name}: a trainable free-form distribution function (Arbitrary1V.fval) is not built on the "
+                                  "device: its chain rule runs on the host (use vg_loss with a host optimiser)")
+    diff, _ = tree.partition(ts_params, tree.get_filter_spec(config["parameters"], ts_params))
+    act = [s for _, s in diff.slots]
+    eng = loss_fn.ts_diag.engine(ts_params.activate)
+    X = ts_params.to_matrix()
+    B = X.shape[0]
+    w = eng.loss_weights(B, loss_fn.i_norm, loss_fn.e_norm, config["data"]["ion_loss_scale"])
+    return ts_params, diff, act, eng, X, B, w, loss_fn._device_batch(eng, batch, B), ts_params.fe_table()
+
+
+def _report(progress, done: int, loss: float, text: str) -> None:
+    """One report to ``progress``: a tqdm-like object (``set_description``) gets ``text``, a callable ``(done, loss)``."""
+    if hasattr(progress, "set_description"):
+        progress.set_description(text)
+    else:
+        progress(done, loss)
+
+
 def adam_loop(config: Dict, loss_fn, previous_weights: Optional[ThomsonParams], batch: Dict, chunk: Optional[int] = None,
               progress=None) -> Tuple[float, ThomsonParams]:
     """``_1d_adam_loop_(config, loss_fn, previous_weights, batch, tbatch)`` -> (best_loss, best_weights).
@@ -32,29 +63,8 @@ def adam_loop(config: Dict, loss_fn, previous_weights: Optional[ThomsonParams], 
     Not built (NotImplementedError): angular decks (the reference runs them through another loop), a trainable free-form f_e
     (Arbitrary1V.fval: its chain rule runs on the host) and ``distributed=True`` loss functions."""
     opt = config["optimizer"]
-    if getattr(loss_fn, "angular", False) or "angular" in config["other"]["extraoptions"]["spectype"]:
-        raise NotImplementedError("adam_loop: angular decks run through the reference's angular loop, not the 1-D Adam loop")
-    if getattr(loss_fn, "distributed", False):
-        raise NotImplementedError("adam_loop: distributed=True is not built (each step would all-reduce the 3 loss sums)")
-    ts_params = previous_weights if previous_weights is not None else \
-        ThomsonParams(config["parameters"], opt["batch_size"], activate=True)
-    sm = ts_params.slots
-    if sm.fval_active or sm.gen2d_active or getattr(sm, "fval2d_active", False):
-        raise NotImplementedError("adam_loop: a trainable free-form distribution function (Arbitrary1V.fval) is not built on the "
-                                  "device: its chain rule runs on the host (use vg_loss with tree.Adam)")
-    diff, _ = tree.partition(ts_params, tree.get_filter_spec(config["parameters"], ts_params))
-    act = [s for _, s in diff.slots]
+    ts_params, _, act, eng, X, B, w, db, fe = _one_d_setup("adam_loop", config, loss_fn, previous_weights, batch)
     n_epochs = int(opt["num_epochs"])
-    eng = loss_fn.ts_diag.engine(ts_params.activate)
-    X = ts_params.to_matrix()
-    B = X.shape[0]
-    w = eng.loss_weights(B, loss_fn.i_norm, loss_fn.e_norm, config["data"]["ion_loss_scale"])
-    db = loss_fn._device_batch(eng, batch, B)
-    fe = None
-    if ts_params.fval is not None:   # (a free-form f_e that is not trained: a constant table)
-        from . import distribution as Dist
-
-        fe = Dist.arbitrary_1v(ts_params.fval)
     hyper = (float(opt["learning_rate"]), ADAM_B1, ADAM_B2, ADAM_EPS)
     step = max(1, int(chunk)) if chunk else max(1, n_epochs)
     Xd, state, best = eng.dev(X), None, None
@@ -65,10 +75,7 @@ def adam_loop(config: Dict, loss_fn, previous_weights: Optional[ThomsonParams], 
         done += k
         if progress is not None:
             last = float(eng.download(hist[-1:])[0])   # the chunk's one synchronisation
-            if hasattr(progress, "set_description"):
-                progress.set_description(f"Epoch {done}, Prev Epoch Loss {last:.2e}")
-            else:
-                progress(done, last)
+            _report(progress, done, last, f"Epoch {done}, Prev Epoch Loss {last:.2e}")
     out = ts_params.copy()
     if best is None:   # (no epoch: the reference leaves best_weights unbound; here the starting point)
         return 1e16, out
@@ -96,33 +103,12 @@ def lbfgs_loop(config: Dict, loss_fn, previous_weights: Optional[ThomsonParams],
     Not built (NotImplementedError, raised before any device work): angular decks, ``distributed=True`` loss functions, a
     trainable free-form f_e (Arbitrary1V.fval), ``grad_method`` other than "AD" and any ``method`` other than l-bfgs-b."""
     opt = config["optimizer"]
-    if getattr(loss_fn, "angular", False) or "angular" in config["other"]["extraoptions"]["spectype"]:
-        raise NotImplementedError("lbfgs_loop: angular decks run through the reference's angular loop, not the 1-D scipy loop")
-    if getattr(loss_fn, "distributed", False):
-        raise NotImplementedError("lbfgs_loop: distributed=True is not built (each evaluation would all-reduce the packed buffer)")
     if str(opt.get("method", "l-bfgs-b")).lower() != "l-bfgs-b":
         raise NotImplementedError(f"lbfgs_loop: method {opt.get('method')!r} -- only l-bfgs-b is built on the device")
     if opt.get("grad_method", "AD") != "AD":
         raise NotImplementedError(f"lbfgs_loop: grad_method {opt.get('grad_method')!r} -- only the analytic gradient (AD) is built")
-    ts_params = previous_weights if previous_weights is not None else \
-        ThomsonParams(config["parameters"], opt["batch_size"], activate=True)
-    sm = ts_params.slots
-    if sm.fval_active or sm.gen2d_active or getattr(sm, "fval2d_active", False):
-        raise NotImplementedError("lbfgs_loop: a trainable free-form distribution function (Arbitrary1V.fval) is not built on the "
-                                  "device: its chain rule runs on the host (use vg_loss with scipy)")
-    diff, static = tree.partition(ts_params, tree.get_filter_spec(config["parameters"], ts_params))
+    ts_params, diff, act, eng, X, B, w, db, fe = _one_d_setup("lbfgs_loop", config, loss_fn, previous_weights, batch)
     _, loss_fn.unravel_weights = tree.ravel_pytree(diff)   # (as the reference leaves it)
-    act = [s for _, s in diff.slots]
-    eng = loss_fn.ts_diag.engine(ts_params.activate)
-    X = ts_params.to_matrix()
-    B = X.shape[0]
-    w = eng.loss_weights(B, loss_fn.i_norm, loss_fn.e_norm, config["data"]["ion_loss_scale"])
-    db = loss_fn._device_batch(eng, batch, B)
-    fe = None
-    if ts_params.fval is not None:   # (a free-form f_e that is not trained: a constant table)
-        from . import distribution as Dist
-
-        fe = Dist.arbitrary_1v(ts_params.fval)
     from .lbfgs import RUNNING
 
     opts = (10, 2.220446049250313e-09, 1e-5, int(opt["num_epochs"]), 15000, 20)
@@ -132,10 +118,7 @@ def lbfgs_loop(config: Dict, loss_fn, previous_weights: Optional[ThomsonParams],
         Xd, state, _, dinfo = eng.lbfgs_fit(Xd, db, w, act, step, opts, state=state, f_hist=False, info=dinfo, fe=fe)
         res = eng.lbfgs_info(dinfo, state)   # the chunk's one synchronisation
         if progress is not None:
-            if hasattr(progress, "set_description"):
-                progress.set_description(f"Iteration {res['nit']}, Loss {res['f']:.2e}")
-            else:
-                progress(res["nit"], res["f"])
+            _report(progress, res["nit"], res["f"], f"Iteration {res['nit']}, Loss {res['f']:.2e}")
         if res["status"] != RUNNING:
             break
     if info is not None:
@@ -258,10 +241,7 @@ def angular_loop(config: Dict, all_data: Dict, sa: Dict, chunk: Optional[int] = 
         ended = host[0] != 0
         if progress is not None:
             last = float(host[2 + int(host[1]) - (done - k)] if ended else host[-1])   # (an ended fit ended in this chunk)
-            if hasattr(progress, "set_description"):
-                progress.set_description(f"Loss {last:.2e}")
-            else:
-                progress(done, last)
+            _report(progress, done, last, f"Loss {last:.2e}")
     if n_epochs == 0:
         if info is not None:
             info.update(loss_hist=np.zeros(0), stopped_after=None, leaves=leaves)

@@ -105,10 +105,7 @@ class LossFunction:
         db = self._device_batch(eng, batch, B)
         X = eng.upload(X)  # pinned staging, asynchronous H2D
         if ts_params.fval is not None:  # free-form f_e: explicit tables in, d loss / d fe out
-            from . import distribution as Dist
-
-            fe = Dist.arbitrary_1v(ts_params.fval)
-            terms, grad, E, I, gfe = eng.loss_grad(X, db, w, ts_params.grad_mask(), fe=fe, want_spectra=want_spectra,
+            terms, grad, E, I, gfe = eng.loss_grad(X, db, w, ts_params.grad_mask(), fe=ts_params.fe_table(), want_spectra=want_spectra,
                                                    want_fe_grad=True)
             self._gfe = gfe
             return eng, w, terms, grad, E, I
@@ -436,10 +433,7 @@ class LossFunction:
             if B == 0:   # (an empty shard of a distributed fit: no lineouts, the layout below with [0, 0] blocks)
                 H = np.zeros((0, len(act), len(act)))
             else:
-                from . import distribution as Dist
-
-                fe = Dist.arbitrary_1v(weights.fval) if weights.fval is not None else None
-                H = eng.loss_hess(X, db, w, act, fe=fe)[2].cpu().numpy()
+                H = eng.loss_hess(X, db, w, act, fe=weights.fe_table())[2].cpu().numpy()
         else:
             gm = weights.grad_mask()
             H = np.zeros((B, len(act), len(act)))

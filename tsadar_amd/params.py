@@ -217,6 +217,15 @@ class ThomsonParams:
         P[:, fr] = P[:, fr] / np.sum(P[:, fr], axis=1, keepdims=True)
         return P
 
+    def fe_table(self):
+        """The f_e table [B][nvx] of a free-form 1-D f_e (Arbitrary1V) at its current values -- the constant table of every call
+        that does not train it; None for every other f_e."""
+        if self.fval is None:
+            return None
+        from . import distribution as D
+
+        return D.arbitrary_1v(self.fval)
+
     def get_unnormed_params(self) -> Dict:
         sm = self.slots
         P = self.physical_matrix()
@@ -225,9 +234,7 @@ class ThomsonParams:
         if sm.has_m:
             out["electron"]["m"] = sq(P[:, L.P_M])
         if self.fval is not None:  # Arbitrary1V.get_unnormed_params: {"f": self()}
-            from . import distribution as D
-
-            out["electron"]["f"] = sq(D.arbitrary_1v(self.fval))
+            out["electron"]["f"] = sq(self.fe_table())
         for k in GENERAL_KEYS:
             out["general"][k] = sq(P[:, _GENERAL_SLOT[k]])
         for i, sp in enumerate(sm.species):
@@ -253,7 +260,7 @@ class ThomsonParams:
             out["electron"]["fe"] = fe if self.batch else fe[0]
             out["electron"]["v"] = vx if self.batch else vx[0]
         if self.fval is not None:
-            fe = D.arbitrary_1v(self.fval)
+            fe = self.fe_table()
             out["electron"].pop("f", None)
             out["electron"]["fe"] = fe if self.batch else fe[0]
             out["electron"]["v"] = np.tile(D.velocity_grid(nvx)[None, :], (fe.shape[0], 1)) if self.batch else D.velocity_grid(nvx)
