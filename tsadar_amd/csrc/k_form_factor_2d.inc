@@ -41,9 +41,6 @@ __device__ __forceinline__ void cell_of(double u, int nv, int& c, double& t) {
   c = (int)cd;
   t = u - cd;   // free outside the grid: the edge-cell polynomial continued (extrap=True)
 }
-#ifndef TSFF_2D_SPLIT_READS
-#define TSFF_2D_SPLIT_READS 1   // LDS-resident tables: one ds_read_b64 per stencil entry (17.3 -> 12.7 ms at the ARTS size)
-#endif
 __device__ __forceinline__ double bicubic_sample(const double* __restrict__ Fp, int nv, int pitch, double u, double v) {
   int cx, cy;
   double tx, ty, wx[4], wy[4];
@@ -62,8 +59,8 @@ __device__ __forceinline__ double bicubic_sample(const double* __restrict__ Fp, 
 }
 // the same for a table in LDS with ONE ds_read_b64 per stencil entry: the compiler pairs neighbouring entries into
 // ds_read2_b64, which moves 128 B per clock and CU where ds_read_b64 moves 256 (MI355X_MICROARCH.md, LDS table: 8 cycles
-// per wavefront instruction against 2) -- and the sampler is bound by the LDS pipe.  volatile on an explicit LDS
-// (address space 3) pointer keeps the reads apart.
+// per wavefront instruction against 2) -- and the sampler is bound by the LDS pipe (17.3 -> 12.7 ms at the ARTS size).
+// volatile on an explicit LDS (address space 3) pointer keeps the reads apart.
 typedef const volatile double __attribute__((address_space(3))) lds_cvdouble;
 __device__ __forceinline__ double bicubic_sample_lds(const double* Fp, int nv, int pitch, double u, double v) {
   int cx, cy;
@@ -84,89 +81,15 @@ __device__ __forceinline__ double bicubic_sample_lds(const double* Fp, int nv, i
   for (int m = 0; m < 4; ++m) r += wx[m] * (wy[0] * V[4 * m] + wy[1] * V[4 * m + 1] + wy[2] * V[4 * m + 2] + wy[3] * V[4 * m + 3]);
   return r;
 }
-// two-stage form of the sampler for tables read through L1/L2: the 16 stencil values of the NEXT sample are requested
-// before the current one is contracted, so that a wavefront keeps loads in flight while it computes (203 -> 190 ms at
-// 256^2; with the table in LDS the same change loses 8 %: there the LDS pipe, not its latency, is the limit)
-__device__ __forceinline__ void bicubic_fetch(const double* __restrict__ Fp, int pitch, int cx, int cy, double V[16]) {
-  const double* __restrict__ q0 = Fp + (size_t)cx * pitch + cy;
-#pragma unroll
-  for (int m = 0; m < 4; ++m) {
-    const double* __restrict__ row = q0 + (size_t)m * pitch;
-    V[4 * m] = row[0]; V[4 * m + 1] = row[1]; V[4 * m + 2] = row[2]; V[4 * m + 3] = row[3];
-  }
-}
-__device__ __forceinline__ double bicubic_dot(const double V[16], double tx, double ty) {
-  double wx[4], wy[4];
-  catmull_rom(tx, wx);
-  catmull_rom(ty, wy);
-  double r = 0.0;
-#pragma unroll
-  for (int m = 0; m < 4; ++m) r += wx[m] * (wy[0] * V[4 * m] + wy[1] * V[4 * m + 1] + wy[2] * V[4 * m + 2] + wy[3] * V[4 * m + 3]);
-  return r;
-}
-// the same four chains in every ACTIVE lane (inside control flow that has already restricted exec)
-__device__ __forceinline__ void window_shift_all(double& a0, double& a1, double& a2, double& a3, double an, double& b0, double& b1,
-                                                 double& b2, double& b3, double bn, double& c0, double& c1, double& c2, double& c3,
-                                                 double cn, double& d0, double& d1, double& d2, double& d3, double dn) {
-  asm volatile(
-      "v_mov_b64 %[a0], %[a1]\n\tv_mov_b64 %[a1], %[a2]\n\tv_mov_b64 %[a2], %[a3]\n\tv_mov_b64 %[a3], %[an]\n\t"
-      "v_mov_b64 %[b0], %[b1]\n\tv_mov_b64 %[b1], %[b2]\n\tv_mov_b64 %[b2], %[b3]\n\tv_mov_b64 %[b3], %[bn]\n\t"
-      "v_mov_b64 %[c0], %[c1]\n\tv_mov_b64 %[c1], %[c2]\n\tv_mov_b64 %[c2], %[c3]\n\tv_mov_b64 %[c3], %[cn]\n\t"
-      "v_mov_b64 %[d0], %[d1]\n\tv_mov_b64 %[d1], %[d2]\n\tv_mov_b64 %[d2], %[d3]\n\tv_mov_b64 %[d3], %[dn]"
-      : [a0] "+v"(a0), [a1] "+v"(a1), [a2] "+v"(a2), [a3] "+v"(a3), [b0] "+v"(b0), [b1] "+v"(b1), [b2] "+v"(b2), [b3] "+v"(b3),
-        [c0] "+v"(c0), [c1] "+v"(c1), [c2] "+v"(c2), [c3] "+v"(c3), [d0] "+v"(d0), [d1] "+v"(d1), [d2] "+v"(d2), [d3] "+v"(d3)
-      : [an] "v"(an), [bn] "v"(bn), [cn] "v"(cn), [dn] "v"(dn));
-}
 // Rolling 4 x 4 window of table VALUES along a rotated line (tables read through L1/L2).  From one sample to the next the
 // cell index moves by at most one on each axis (|cos|, |sin| <= 1; the clamp of cell_of is monotone), so the next stencil shares
 // 9 to 16 of its entries with the current one: per step only the row and the column that may enter are requested (8 loads
-// where the plain sampler issues 16 -- the sampler at 256^2 sat at 0.59 of the vector-L1 read rate) and the window is shifted
-// by selects.  The requests for step k + 1 are issued before sample k is contracted.  SX / SY = direction of the cell walk on
-// each axis, the same for every sample of a point (wavefront-uniform), ix always ascending: the sum is taken in the same
-// order, over the same values and weights, as the plain sampler takes it -- bit-identical results.
-// Entering column first (rows of the CURRENT window), then the entering row at the columns of the NEXT window: no corner case.
-#ifndef TSFF_2D_ROLL
-#define TSFF_2D_ROLL 1
-#endif
-// four chains a0 <- a1 <- a2 <- a3 <- n in the lanes of the mask m (a ballot), and in the same lanes the walk's state one cell on:
-// cell index (as a double) cd += DIR, fraction t -= DIR, byte offset of the window off8 += d8 (wavefront-uniform, may be negative)
-template <int DIR>
-__device__ __forceinline__ void window_shift(unsigned long long m, double& a0, double& a1, double& a2, double& a3, double an, double& b0, double& b1,
-                                             double& b2, double& b3, double bn, double& c0, double& c1, double& c2, double& c3,
-                                             double cn, double& d0, double& d1, double& d2, double& d3, double dn, double& cd, double& t,
-                                             unsigned& off8, int d8) {
-  unsigned long long sv;
-  if (DIR > 0)
-    asm volatile(
-        "s_waitcnt vmcnt(0)\n\t"   // (the entering line may have been requested by hand: see TSFF_2D_MASKED_COLUMN)
-        "s_and_saveexec_b64 %[sv], %[m]\n\t"
-        "v_mov_b64 %[a0], %[a1]\n\tv_mov_b64 %[a1], %[a2]\n\tv_mov_b64 %[a2], %[a3]\n\tv_mov_b64 %[a3], %[an]\n\t"
-        "v_mov_b64 %[b0], %[b1]\n\tv_mov_b64 %[b1], %[b2]\n\tv_mov_b64 %[b2], %[b3]\n\tv_mov_b64 %[b3], %[bn]\n\t"
-        "v_mov_b64 %[c0], %[c1]\n\tv_mov_b64 %[c1], %[c2]\n\tv_mov_b64 %[c2], %[c3]\n\tv_mov_b64 %[c3], %[cn]\n\t"
-        "v_mov_b64 %[d0], %[d1]\n\tv_mov_b64 %[d1], %[d2]\n\tv_mov_b64 %[d2], %[d3]\n\tv_mov_b64 %[d3], %[dn]\n\t"
-        "v_add_f64 %[cd], %[cd], 1.0\n\tv_add_f64 %[t], %[t], -1.0\n\tv_add_u32 %[off], %[d8], %[off]\n\t"
-        "s_mov_b64 exec, %[sv]"
-        : [sv] "=&s"(sv), [a0] "+v"(a0), [a1] "+v"(a1), [a2] "+v"(a2), [a3] "+v"(a3), [b0] "+v"(b0), [b1] "+v"(b1), [b2] "+v"(b2),
-          [b3] "+v"(b3), [c0] "+v"(c0), [c1] "+v"(c1), [c2] "+v"(c2), [c3] "+v"(c3), [d0] "+v"(d0), [d1] "+v"(d1), [d2] "+v"(d2),
-          [d3] "+v"(d3), [cd] "+v"(cd), [t] "+v"(t), [off] "+v"(off8)
-        : [m] "s"(m), [an] "v"(an), [bn] "v"(bn), [cn] "v"(cn), [dn] "v"(dn), [d8] "s"(d8)
-        : "scc");   // (s_and_saveexec writes SCC)
-  else
-    asm volatile(
-        "s_waitcnt vmcnt(0)\n\t"   // (the entering line may have been requested by hand: see TSFF_2D_MASKED_COLUMN)
-        "s_and_saveexec_b64 %[sv], %[m]\n\t"
-        "v_mov_b64 %[a0], %[a1]\n\tv_mov_b64 %[a1], %[a2]\n\tv_mov_b64 %[a2], %[a3]\n\tv_mov_b64 %[a3], %[an]\n\t"
-        "v_mov_b64 %[b0], %[b1]\n\tv_mov_b64 %[b1], %[b2]\n\tv_mov_b64 %[b2], %[b3]\n\tv_mov_b64 %[b3], %[bn]\n\t"
-        "v_mov_b64 %[c0], %[c1]\n\tv_mov_b64 %[c1], %[c2]\n\tv_mov_b64 %[c2], %[c3]\n\tv_mov_b64 %[c3], %[cn]\n\t"
-        "v_mov_b64 %[d0], %[d1]\n\tv_mov_b64 %[d1], %[d2]\n\tv_mov_b64 %[d2], %[d3]\n\tv_mov_b64 %[d3], %[dn]\n\t"
-        "v_add_f64 %[cd], %[cd], -1.0\n\tv_add_f64 %[t], %[t], 1.0\n\tv_add_u32 %[off], %[d8], %[off]\n\t"
-        "s_mov_b64 exec, %[sv]"
-        : [sv] "=&s"(sv), [a0] "+v"(a0), [a1] "+v"(a1), [a2] "+v"(a2), [a3] "+v"(a3), [b0] "+v"(b0), [b1] "+v"(b1), [b2] "+v"(b2),
-          [b3] "+v"(b3), [c0] "+v"(c0), [c1] "+v"(c1), [c2] "+v"(c2), [c3] "+v"(c3), [d0] "+v"(d0), [d1] "+v"(d1), [d2] "+v"(d2),
-          [d3] "+v"(d3), [cd] "+v"(cd), [t] "+v"(t), [off] "+v"(off8)
-        : [m] "s"(m), [an] "v"(an), [bn] "v"(bn), [cn] "v"(cn), [dn] "v"(dn), [d8] "s"(d8)
-        : "scc");
-}
+// where the plain sampler issues 16 -- the sampler at 256^2 sat at 0.59 of the vector-L1 read rate; a sampler that requested all
+// 16 entries of the next sample ahead of the contraction took 190 ms at 256^2, DESIGN.md section 4.3) and the window is shifted in
+// place.  SX / SY = direction of the cell walk on each axis, the same for every sample of a point (wavefront-uniform), ix always
+// ascending: the sum is taken in the same order, over the same values and weights, as the plain sampler takes it -- bit-identical
+// results.  Entering column first (rows of the CURRENT window), then the entering row at the columns of the NEXT window: no
+// corner case.
 // TR: F is the TRANSPOSED padded table (entry (cx, cy) at F[cy * pitch + cx]).  The lanes of a wavefront are neighbouring lines,
 // (-sin, cos) apart in cell units: where |sin| > |cos| they spread along the FIRST table axis, 64 lanes touch 64 different rows
 // of the table and the 8 wavefronts of a CU overrun its 32 KB L1; read from the transposed copy they lie along its contiguous
@@ -185,156 +108,17 @@ __device__ __forceinline__ void window_shift(unsigned long long m, double& a0, d
 // entering line one step outside the table (never selected: the cell index stops at the edge) is read from the margin k_pad2d
 // leaves around the padded pair instead of being clamped.  The fractions are the same doubles as cell_of's (u - c is exact for
 // an integer c <= 254 next to u, and so is the +-1 of a shift), so the samples are the same bits.
-struct RollVG { double idv, dv, v0, y, ds1, ds2; };
-template <int SX, int SY, bool TR, bool VG = false>
-__device__ __forceinline__ double project_rolling_1(const double* __restrict__ F, int nv, int pitch, double cb, double sb,
-                                                  double ul, double vl, int ix0, int ix1, RollVG* vg = nullptr) {
-#pragma clang fp contract(off)
-  double xi_d = (double)ix0, tx, ty, W[4][4], acc = 0.0, ds1 = 0.0, ds2 = 0.0, cdx, cdy;
-  unsigned off8;
-  {
-    int cx, cy;
-    cell_of(__builtin_fma(xi_d, cb, ul), nv, cx, tx);
-    cell_of(__builtin_fma(xi_d, sb, vl), nv, cy, ty);
-    cdx = (double)cx; cdy = (double)cy;
-    const unsigned o = (unsigned)(TR ? cy * pitch + cx : cx * pitch + cy);
-    off8 = o * 8u;
-    const double* __restrict__ q0 = F + o;
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-      for (int n = 0; n < 4; ++n) W[m][n] = q0[(unsigned)(TR ? n * pitch + m : m * pitch + n)];
-  }
-  // byte strides of one cell step on each axis, the entering column / row relative to the window's origin, and the uniform bases
-  const int px8 = (TR ? 1 : pitch) * 8, py8 = (TR ? pitch : 1) * 8;
-  // (the eight bases as opaque SGPR pairs in the GLOBAL address space: left to itself the compiler folds the lane offset into the
-  //  first base and then adds the row pitch in 64-bit VGPR arithmetic for every further load)
-  typedef const __attribute__((address_space(1))) char* gptr_t;
-  auto sptr = [](const char* p) {
-    const unsigned long long v = reinterpret_cast<unsigned long long>(p);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return reinterpret_cast<gptr_t>(((unsigned long long)hi << 32) | lo);
-  };
-  const char* Fc = reinterpret_cast<const char*>(F);
-  gptr_t bc[4];   // entering column: rows cx + m of the CURRENT window
-  gptr_t br[4];   // entering row: columns ncy + n of the NEXT window
-#pragma unroll
-  for (int m = 0; m < 4; ++m) {   // (the four CONTIGUOUS entries from one base: they are fetched as two 16-byte loads)
-    bc[m] = TR ? sptr(Fc + (SY > 0 ? 4 : -1) * py8) + 8 * m : sptr(Fc + (SY > 0 ? 4 : -1) * py8 + m * px8);
-    br[m] = TR ? sptr(Fc + (SX > 0 ? 4 : -1) * px8 + m * py8) : sptr(Fc + (SX > 0 ? 4 : -1) * px8) + 8 * m;
-  }
-  const unsigned dyv = (unsigned)(SY * py8);   // (in a VGPR: the select below already takes its mask from the scalar side)
-  double cmax = (double)(nv - 2);
-  const int nstep = __builtin_amdgcn_readfirstlane(ix1 - ix0);   // (the part of the line is the same for the lanes of a wavefront)
-  for (int it = 0; it < nstep; ++it) {
-    const double xc = xi_d;
-    // the weights of the current sample first: (tx, ty) then become the fractions of the NEXT position against the current cell
-    double wx[4], wy[4], dx[4], dy[4];
-    catmull_rom(tx, wx);
-    catmull_rom(ty, wy);
-    if (VG) {   // derivatives of the weights: -(3 t^2 - 4 t + 1) / 2, (9 t^2 - 10 t) / 2, (-9 t^2 + 8 t + 1) / 2, (3 t^2 - 2 t) / 2
-      dx[0] = __builtin_fma(__builtin_fma(-1.5, tx, 2.0), tx, -0.5); dx[1] = __builtin_fma(4.5, tx, -5.0) * tx;
-      dx[2] = __builtin_fma(__builtin_fma(-4.5, tx, 4.0), tx, 0.5);  dx[3] = __builtin_fma(1.5, tx, -1.0) * tx;
-      dy[0] = __builtin_fma(__builtin_fma(-1.5, ty, 2.0), ty, -0.5); dy[1] = __builtin_fma(4.5, ty, -5.0) * ty;
-      dy[2] = __builtin_fma(__builtin_fma(-4.5, ty, 4.0), ty, 0.5);  dy[3] = __builtin_fma(1.5, ty, -1.0) * ty;
-    }
-    xi_d += 1.0;   // (after the last sample the requests go to position ix1 of the line: the addresses stay inside the table + margin)
-    tx = __builtin_fma(xi_d, cb, ul) - cdx;
-    ty = __builtin_fma(xi_d, sb, vl) - cdy;
-    // shift masks as plain 64-bit scalars (comparisons written out: as `bool`s the compiler parks them in VGPRs as 0 / 1 and
-    // compares again in front of every use)
-    unsigned long long mx, my, ex, ey;
-    if (SX > 0) { asm("v_cmp_le_f64 %0, 1.0, %1" : "=s"(mx) : "v"(tx)); asm("v_cmp_lt_f64 %0, %1, %2" : "=s"(ex) : "v"(cdx), "v"(cmax)); }
-    else { asm("v_cmp_gt_f64 %0, 0, %1" : "=s"(mx) : "v"(tx)); asm("v_cmp_lt_f64 %0, 0, %1" : "=s"(ex) : "v"(cdx)); }
-    if (SY > 0) { asm("v_cmp_le_f64 %0, 1.0, %1" : "=s"(my) : "v"(ty)); asm("v_cmp_lt_f64 %0, %1, %2" : "=s"(ey) : "v"(cdy), "v"(cmax)); }
-    else { asm("v_cmp_gt_f64 %0, 0, %1" : "=s"(my) : "v"(ty)); asm("v_cmp_lt_f64 %0, 0, %1" : "=s"(ey) : "v"(cdy)); }
-    mx &= ex; my &= ey;
-    unsigned offr;
-    asm("v_cndmask_b32 %0, 0, %1, %2" : "=v"(offr) : "v"(dyv), "s"(my));
-    offr += off8;
-    double NC[4], NR[4];
-#ifndef TSFF_2D_MASKED_COLUMN
-#define TSFF_2D_MASKED_COLUMN 1
-#endif
-#ifndef TSFF_2D_EXP
-#define TSFF_2D_EXP 0   // (measurement builds, WRONG results: 1 no column requests, 2 no requests at all -- what the VMEM side costs)
-#endif
-#if TSFF_2D_MASKED_COLUMN
-    // The entering COLUMN is requested by the lanes that will shift along that axis only (exec = my; it is the minor axis of the walk:
-    // |step| <= 0.71 cells, on average 0.37 of the lanes).  Its four entries lie a table row apart (in the orientation the point
-    // reads), so every request touches as many cache lines as the wavefront's lanes span rows -- the four of them cost 25 ms of a
-    // 124 ms image against 9 ms for the two contiguous row requests (profiles/r03m_ab_cfg4_exp.txt) -- and a lane that does not shift
-    // never looks at what it would have fetched.  Written out (the compiler cannot put a load under a scalar mask it did not make
-    // itself); the values are consumed by window_shift only, behind its s_waitcnt.
-    {
-      unsigned long long sv;
-      if (TR) {   // contiguous in the transposed copy: two 16-byte requests
-        typedef double dbl2 __attribute__((ext_vector_type(2)));
-        dbl2 c01, c23;
-        asm volatile("s_and_saveexec_b64 %[sv], %[m]\n\t"
-                     "global_load_dwordx4 %[c01], %[off], %[b0]\n\t"
-                     "global_load_dwordx4 %[c23], %[off], %[b0] offset:16\n\t"
-                     "s_mov_b64 exec, %[sv]"
-                     : [sv] "=&s"(sv), [c01] "=&v"(c01), [c23] "=&v"(c23)
-                     : [m] "s"(my), [off] "v"(off8), [b0] "s"(bc[0])
-                     : "scc", "memory");
-        NC[0] = c01[0]; NC[1] = c01[1]; NC[2] = c23[0]; NC[3] = c23[1];
-      } else {
-        asm volatile("s_and_saveexec_b64 %[sv], %[m]\n\t"
-                     "global_load_dwordx2 %[n0], %[off], %[b0]\n\t"
-                     "global_load_dwordx2 %[n1], %[off], %[b1]\n\t"
-                     "global_load_dwordx2 %[n2], %[off], %[b2]\n\t"
-                     "global_load_dwordx2 %[n3], %[off], %[b3]\n\t"
-                     "s_mov_b64 exec, %[sv]"
-                     : [sv] "=&s"(sv), [n0] "=&v"(NC[0]), [n1] "=&v"(NC[1]), [n2] "=&v"(NC[2]), [n3] "=&v"(NC[3])
-                     : [m] "s"(my), [off] "v"(off8), [b0] "s"(bc[0]), [b1] "s"(bc[1]), [b2] "s"(bc[2]), [b3] "s"(bc[3])
-                     : "scc", "memory");
-      }
-    }
-#else
-#pragma unroll
-    for (int m = 0; m < 4; ++m) NC[m] = TSFF_2D_EXP >= 1 ? tx : *reinterpret_cast<const __attribute__((address_space(1))) double*>(bc[m] + off8);
-#endif
-#pragma unroll
-    for (int n = 0; n < 4; ++n) NR[n] = TSFF_2D_EXP >= 2 ? ty : *reinterpret_cast<const __attribute__((address_space(1))) double*>(br[n] + offr);
-    __builtin_amdgcn_sched_barrier(0);   // keep the requests ahead of the arithmetic on the current sample
-    // (explicit FMA chains under contract(off): the forward's SAVE pass and the adjoint's projection pass inline this function into
-    //  different kernels and must produce the same bits -- left to the contraction heuristics they once differed in the last place,
-    //  which the table adjoint amplifies to 5e-11)
-    auto dot4 = [](const double (&w)[4], const double (&v)[4]) {
-      return __builtin_fma(w[3], v[3], __builtin_fma(w[2], v[2], __builtin_fma(w[1], v[1], w[0] * v[0])));
-    };
-    if (!VG) {
-      double rr[4];
-#pragma unroll
-      for (int m = 0; m < 4; ++m) rr[m] = dot4(wy, W[m]);
-      acc += dot4(wx, rr);
-    } else {
-      double rr[4], rd[4];
-#pragma unroll
-      for (int m = 0; m < 4; ++m) { rr[m] = dot4(wy, W[m]); rd[m] = dot4(dy, W[m]); }
-      const double val = dot4(wx, rr), sx = dot4(dx, rr), sy = dot4(wx, rd);
-      const double Sx = sx * vg->idv, Sy = sy * vg->idv, x = __builtin_fma(xc, vg->dv, vg->v0);
-      acc += val;
-      ds1 += __builtin_fma(Sy, vg->y, Sx * x);
-      ds2 += __builtin_fma(-Sx, vg->y, Sy * x);
-    }
-    // the shifts: 64-bit moves under the lanes' own condition (16 v_mov_b64 per axis where selects take 32 v_cndmask_b32; written
-    // out because the compiler turns the conditional form into copies of the whole window and sinks the requests behind a wait).
-    // Entering column first (it was read at the rows of the current window), then the entering row (read at the next columns).
-    if (SY > 0) window_shift<1>(my, W[0][0], W[0][1], W[0][2], W[0][3], NC[0], W[1][0], W[1][1], W[1][2], W[1][3], NC[1],
-                                W[2][0], W[2][1], W[2][2], W[2][3], NC[2], W[3][0], W[3][1], W[3][2], W[3][3], NC[3], cdy, ty, off8, py8);
-    else window_shift<-1>(my, W[0][3], W[0][2], W[0][1], W[0][0], NC[0], W[1][3], W[1][2], W[1][1], W[1][0], NC[1],
-                          W[2][3], W[2][2], W[2][1], W[2][0], NC[2], W[3][3], W[3][2], W[3][1], W[3][0], NC[3], cdy, ty, off8, -py8);
-    if (SX > 0) window_shift<1>(mx, W[0][0], W[1][0], W[2][0], W[3][0], NR[0], W[0][1], W[1][1], W[2][1], W[3][1], NR[1],
-                                W[0][2], W[1][2], W[2][2], W[3][2], NR[2], W[0][3], W[1][3], W[2][3], W[3][3], NR[3], cdx, tx, off8, px8);
-    else window_shift<-1>(mx, W[3][0], W[2][0], W[1][0], W[0][0], NR[0], W[3][1], W[2][1], W[1][1], W[0][1], NR[1],
-                          W[3][2], W[2][2], W[1][2], W[0][2], NR[2], W[3][3], W[2][3], W[1][3], W[0][3], NR[3], cdx, tx, off8, -px8);
-  }
-  if (VG) { vg->ds1 = ds1; vg->ds2 = ds2; }
-  return acc;
-}
-// ---- the two-deep form (TSFF_2D_DEPTH 2, default) ----
+//
+// The entering COLUMN is requested by the lanes that will shift along that axis only (exec = my; it is the minor axis of the walk:
+// |step| <= 0.71 cells, on average 0.37 of the lanes).  Its four entries lie a table row apart (in the orientation the point
+// reads), so every request touches as many cache lines as the wavefront's lanes span rows -- the four of them cost 25 ms of a
+// 124 ms image against 9 ms for the two contiguous row requests (profiles/r03m_ab_cfg4_exp.txt) -- and a lane that does not shift
+// never looks at what it would have fetched.  The requests are written out (the compiler cannot put a load under a scalar mask it
+// did not make itself); the values are consumed by window_shift_w only, behind its s_waitcnt.
+// The shifts are 64-bit moves under the lanes' own condition (16 v_mov_b64 per axis where selects take 32 v_cndmask_b32; written
+// out because the compiler turns the conditional form into copies of the whole window and sinks the requests behind a wait).
+//
+// The requests run TWO DEEP.
 // With the instruction count down the sampler stopped being issue-bound: 30 % of the wavefront cycles were spent at the wait in
 // front of the shifts (SQ_WAIT_INST_ANY), because the entering line is requested at the top of the iteration that consumes it and
 // two wavefronts per SIMD cannot cover an L2 round trip (more wavefronts overrun the 32 KB L1: 3 per SIMD 130 ms, 4: 137 ms).
@@ -404,15 +188,11 @@ __device__ __forceinline__ void window_shift_w(unsigned long long m, double& a0,
       : [m] "s"(m), [an] "v"(an), [bn] "v"(bn), [cn] "v"(cn), [dn] "v"(dn), [w] "n"(WAIT)
       : "scc");
 }
-#ifndef TSFF_2D_DEPTH
-#define TSFF_2D_DEPTH 2
-#endif
-
+struct RollVG { double idv, dv, v0, y, ds1, ds2; };
 template <int SX, int SY, bool TR, bool VG = false>
 __device__ __forceinline__ double project_rolling(const double* __restrict__ F, int nv, int pitch, double cb, double sb,
                                                   double ul, double vl, int ix0, int ix1, RollVG* vg = nullptr) {
 #pragma clang fp contract(off)
-  if (TSFF_2D_DEPTH != 2) return project_rolling_1<SX, SY, TR, VG>(F, nv, pitch, cb, sb, ul, vl, ix0, ix1, vg);
   double xi_d = (double)ix0, xs_d = xi_d, W[4][4], acc = 0.0, ds1 = 0.0, ds2 = 0.0, cdx, cdy, wx[4], wy[4], dx[4], dy[4];
   double t0x, t0y, t1x = 0.0, t1y = 0.0;
   unsigned off8;
@@ -469,15 +249,10 @@ __device__ __forceinline__ double project_rolling(const double* __restrict__ F, 
     unsigned offr;
     asm("v_cndmask_b32 %0, 0, %1, %2" : "=v"(offr) : "v"(dyv), "s"(my));
     offr += off8;
-    // (TSFF_2D_EXP, measurement builds with WRONG results: 1 no column requests, 2 no requests at all, 3 every request issued with an empty mask,
-    //  4 column requests with an empty mask)
-    const unsigned long long rmy = (TSFF_2D_EXP == 3 || TSFF_2D_EXP == 4) ? 0ull : my, rmx = TSFF_2D_EXP == 3 ? 0ull : mx;
-    if (TSFF_2D_EXP == 1 || TSFF_2D_EXP == 2) { NC[0] = NC[1] = NC[2] = NC[3] = tx; }
-    else if (TR) request4_contig(rmy, off8, bc[0], NC);
-    else request4_strided(rmy, off8, bc[0], bc[1], bc[2], bc[3], NC);
-    if (TSFF_2D_EXP == 2) { NR[0] = NR[1] = NR[2] = NR[3] = ty; }
-    else if (TR) request4_strided(rmx, offr, br[0], br[1], br[2], br[3], NR);
-    else request4_contig(rmx, offr, br[0], NR);
+    if (TR) request4_contig(my, off8, bc[0], NC);
+    else request4_strided(my, off8, bc[0], bc[1], bc[2], bc[3], NC);
+    if (TR) request4_strided(mx, offr, br[0], br[1], br[2], br[3], NR);
+    else request4_contig(mx, offr, br[0], NR);
     cursor_step<SY>(my, cdy, ty, off8, SY * py8);
     cursor_step<SX>(mx, cdx, tx, off8, SX * px8);
   };
@@ -657,7 +432,7 @@ __device__ __forceinline__ double bicubic_sample_vg(const double* __restrict__ F
   for (int m = 0; m < 4; ++m) {
     const double* __restrict__ row = q0 + (size_t)m * pitch;
     double r0, r1, r2, r3;
-    if (LDSV && TSFF_2D_SPLIT_READS) {   // (one ds_read_b64 per entry, see bicubic_sample_lds)
+    if (LDSV) {   // (one ds_read_b64 per entry, see bicubic_sample_lds)
       lds_cvdouble* rl = (lds_cvdouble*)Fp + ((cx + m) * pitch + cy);
       r0 = rl[0]; r1 = rl[1]; r2 = rl[2]; r3 = rl[3];
     } else {
@@ -772,7 +547,7 @@ __global__ __launch_bounds__(kG2 * kThreads, TSFF_2D_WAVES) void k_form_factor_2
           line_origin(cb, sb, y, v0, idv, ul, vl);
           if (SAVE) {
             double ds1 = 0.0, ds2 = 0.0;
-            if (!LDS && TSFF_2D_ROLL) {
+            if (!LDS) {
               RollVG vg{idv, dv, v0, y, 0.0, 0.0};
               acc = project_rolling_any<true>(F, nv, pitch, cb, sb, ul, vl, ix0, ix1, &vg);
               ds1 = vg.ds1; ds2 = vg.ds2;
@@ -789,33 +564,9 @@ __global__ __launch_bounds__(kG2 * kThreads, TSFF_2D_WAVES) void k_form_factor_2
             rec[(nparts + pt) * nv + iy] = ds2;
           } else if (LDS) {
             for (int ix = ix0; ix < ix1; ++ix, xi_d += 1.0)
-#if TSFF_2D_SPLIT_READS
               acc += bicubic_sample_lds(F, nv, pitch, __builtin_fma(xi_d, cb, ul), __builtin_fma(xi_d, sb, vl));
-#else
-              acc += bicubic_sample(F, nv, pitch, __builtin_fma(xi_d, cb, ul), __builtin_fma(xi_d, sb, vl));
-#endif
-          } else if (TSFF_2D_ROLL) {
-            acc = project_rolling_any<false>(F, nv, pitch, cb, sb, ul, vl, ix0, ix1);
           } else {
-            int cx, cy;
-            double tx, ty, V[16];
-            cell_of(__builtin_fma(xi_d, cb, ul), nv, cx, tx);
-            cell_of(__builtin_fma(xi_d, sb, vl), nv, cy, ty);
-            bicubic_fetch(F, pitch, cx, cy, V);
-            for (int ix = ix0; ix < ix1; ++ix) {
-              xi_d += 1.0;   // (the fetch after the last sample repeats a valid position: no branch in the loop)
-              const double xn = ix + 1 < ix1 ? xi_d : xi_d - 1.0;
-              int ncx, ncy;
-              double ntx, nty, N[16];
-              cell_of(__builtin_fma(xn, cb, ul), nv, ncx, ntx);
-              cell_of(__builtin_fma(xn, sb, vl), nv, ncy, nty);
-              bicubic_fetch(F, pitch, ncx, ncy, N);
-              __builtin_amdgcn_sched_barrier(0);   // keep the requests ahead of the arithmetic on the previous sample
-              acc += bicubic_dot(V, tx, ty);
-#pragma unroll
-              for (int k = 0; k < 16; ++k) V[k] = N[k];
-              tx = ntx; ty = nty;
-            }
+            acc = project_rolling_any<false>(F, nv, pitch, cb, sb, ul, vl, ix0, ix1);
           }
           part[pt * nv + iy] = acc;
         }
@@ -1019,7 +770,7 @@ __global__ __launch_bounds__(kG2 * kThreads) void k_form_factor_2d_adj(KStatic S
           const double y = __builtin_fma((double)iy, dv, v0);
           double acc = 0.0, ul, vl, xi_d = (double)ix0;
           line_origin(cb, sb, y, v0, idv, ul, vl);
-          if (!LDS && TSFF_2D_ROLL) {
+          if (!LDS) {
             RollVG vg{idv, dv, v0, y, 0.0, 0.0};
             acc = project_rolling_any<true>(F, nv, pitch, cb, sb, ul, vl, ix0, ix1, &vg);
             ds1 = vg.ds1; ds2 = vg.ds2;
@@ -1319,9 +1070,6 @@ __global__ __launch_bounds__(kThreads) void k_lbacc_reduce(const double* __restr
 // wide on each side and then decided per sample by the very floor() every tile evaluates, so that each sample lands in
 // exactly one tile).
 constexpr int kTile2 = 128;
-#ifndef TSFF_TADJ_ROLL
-#define TSFF_TADJ_ROLL 3   // 0: 16 atomics per sample; 1: rolling window written with ifs; 2: rolling window, shifts as in-place moves; 3: lockstep walk under exec masks (round 3)
-#endif
 // indices ix with lo <= c * ix + e < hi (lo_inf / hi_inf: that side is open), widened by two
 __device__ __forceinline__ void line_range(double c, double e, double lo, double hi, bool lo_inf, bool hi_inf, int& a, int& b) {
   if (fabs(c) < 1.0e-9) return;   // (almost) parallel to the tile edge: the per-sample test decides
@@ -1333,66 +1081,12 @@ __device__ __forceinline__ void line_range(double c, double e, double lo, double
   a = a > ia ? a : ia;
   b = b < ib ? b : ib;
 }
-// One line's scatter with the rolling window of SUMS (TSFF_TADJ_ROLL == 2).  The samples of a line that fall into the tile are one
-// run (the clamped cell indices are monotone along the line); inside it the window follows the cell: the row / column that leaves goes
-// to LDS (4 atomics), the others move up by 64-bit moves in place (window_shift_all -- the `if` form of the same shifts compiled to
-// copies of the whole window around every branch: 180-200 VALU instructions per sample, this form ~120).  The advance loops run at
-// most once per sample in exact arithmetic; written as loops they also absorb a double step caused by rounding.
-template <int SGY>
-__device__ __forceinline__ void scatter_line_rolling(double* __restrict__ T, int pitch, int nv, int cx0, int cx1, int cy0, int cy1,
-                                                     bool whole, bool fwd, int ix0, int ix1, double cb, double sb, double ul,
-                                                     double vl, double val) {
-  double a00 = 0.0, a01 = 0.0, a02 = 0.0, a03 = 0.0, a10 = 0.0, a11 = 0.0, a12 = 0.0, a13 = 0.0;
-  double a20 = 0.0, a21 = 0.0, a22 = 0.0, a23 = 0.0, a30 = 0.0, a31 = 0.0, a32 = 0.0, a33 = 0.0;
-  int wcx = 0, wcy = 0;
-  bool open = false;
-  for (int k = 0; k < ix1 - ix0; ++k) {
-    const int ix = fwd ? ix0 + k : ix1 - 1 - k;
-    int cx, cy;
-    double tx, ty;
-    cell_of(__builtin_fma((double)ix, cb, ul), nv, cx, tx);
-    cell_of(__builtin_fma((double)ix, sb, vl), nv, cy, ty);
-    if (!whole && (cx < cx0 || cx >= cx1 || cy < cy0 || cy >= cy1)) continue;
-    if (!open) { wcx = cx; wcy = cy; open = true; }
-    for (; wcx != cx; ++wcx) {   // row 0 leaves the window (the walk is taken in the direction of non-decreasing cx)
-      double* q0 = T + (wcx - cx0) * pitch + (wcy - cy0);
-      atomicAdd(q0, a00); atomicAdd(q0 + 1, a01); atomicAdd(q0 + 2, a02); atomicAdd(q0 + 3, a03);
-      window_shift_all(a00, a10, a20, a30, 0.0, a01, a11, a21, a31, 0.0, a02, a12, a22, a32, 0.0, a03, a13, a23, a33, 0.0);
-    }
-    for (; wcy != cy; wcy += SGY) {   // one column leaves: the first (cy growing) or the last (cy falling)
-      double* q0 = T + (wcx - cx0) * pitch + (wcy - cy0) + (SGY > 0 ? 0 : 3);
-      if (SGY > 0) {
-        atomicAdd(q0, a00); atomicAdd(q0 + pitch, a10); atomicAdd(q0 + 2 * pitch, a20); atomicAdd(q0 + 3 * pitch, a30);
-        window_shift_all(a00, a01, a02, a03, 0.0, a10, a11, a12, a13, 0.0, a20, a21, a22, a23, 0.0, a30, a31, a32, a33, 0.0);
-      } else {
-        atomicAdd(q0, a03); atomicAdd(q0 + pitch, a13); atomicAdd(q0 + 2 * pitch, a23); atomicAdd(q0 + 3 * pitch, a33);
-        window_shift_all(a03, a02, a01, a00, 0.0, a13, a12, a11, a10, 0.0, a23, a22, a21, a20, 0.0, a33, a32, a31, a30, 0.0);
-      }
-    }
-    double wx[4], wy[4];
-    catmull_rom(tx, wx);
-    catmull_rom(ty, wy);
-    const double w0 = val * wx[0], w1 = val * wx[1], w2 = val * wx[2], w3 = val * wx[3];
-    a00 += w0 * wy[0]; a01 += w0 * wy[1]; a02 += w0 * wy[2]; a03 += w0 * wy[3];
-    a10 += w1 * wy[0]; a11 += w1 * wy[1]; a12 += w1 * wy[2]; a13 += w1 * wy[3];
-    a20 += w2 * wy[0]; a21 += w2 * wy[1]; a22 += w2 * wy[2]; a23 += w2 * wy[3];
-    a30 += w3 * wy[0]; a31 += w3 * wy[1]; a32 += w3 * wy[2]; a33 += w3 * wy[3];
-  }
-  if (open) {
-    double* q0 = T + (wcx - cx0) * pitch + (wcy - cy0);
-    atomicAdd(q0, a00); atomicAdd(q0 + 1, a01); atomicAdd(q0 + 2, a02); atomicAdd(q0 + 3, a03);
-    q0 += pitch;
-    atomicAdd(q0, a10); atomicAdd(q0 + 1, a11); atomicAdd(q0 + 2, a12); atomicAdd(q0 + 3, a13);
-    q0 += pitch;
-    atomicAdd(q0, a20); atomicAdd(q0 + 1, a21); atomicAdd(q0 + 2, a22); atomicAdd(q0 + 3, a23);
-    q0 += pitch;
-    atomicAdd(q0, a30); atomicAdd(q0 + 1, a31); atomicAdd(q0 + 2, a32); atomicAdd(q0 + 3, a33);
-  }
-}
-// ---- TSFF_TADJ_ROLL == 3 (round 3): the scatter as a LOCKSTEP walk ----
-// The rolling window of sums above is written with per-lane control flow (`continue` outside the tile, loops that advance the window):
-// every wavefront executes the union of its lanes' paths, 140 instructions per sample at 0.63 lane utilisation, and the kernel is
-// bound by that, not by its LDS atomics (plain stores in their place: 298 -> 273 ms at 256^2).  Here all lanes of a wavefront take the
+// One line's scatter as a LOCKSTEP walk with a rolling window of SUMS.  The samples of a line that fall into the tile are one run
+// (the clamped cell indices are monotone along the line); inside it a 4 x 4 register window follows the cell and only the row /
+// column that leaves it goes to LDS (4 atomics per axis step instead of 16 per sample).  Written with per-lane control flow
+// (`continue` outside the tile, loops that advance the window) every wavefront executed the union of its lanes' paths, 140
+// instructions per sample at 0.63 lane utilisation, and the kernel was bound by that, not by its LDS atomics (plain stores in
+// their place: 298 -> 273 ms at 256^2; DESIGN.md section 4.3).  Here all lanes of a wavefront take the
 // same steps k = 0 .. n_max - 1 (n_max: the longest chord among them) and everything lane-dependent is an exec mask held in a scalar
 // register pair, as in project_rolling: `valid` (k inside the lane's chord), `inside` (the sample's cell inside the tile), `started`
 // (the window has seen an inside sample: before that it is all zero and only follows the cell), the two shift masks.  The cell is
@@ -1566,10 +1260,6 @@ __global__ __launch_bounds__(4 * kThreads) void k_ff2d_table_adj(int nv, const d
   for (int i = threadIdx.x; i < trow * pitch; i += blockDim.x) T[i] = 0.0;
   __syncthreads();
   const double dv = 12.0 / nv, v0 = -6.0 + 0.5 * dv, idv = 1.0 / dv;
-  const int grp = threadIdx.x >> 8, gt = threadIdx.x & (kThreads - 1);
-  const int nvp = nv <= 64 ? 64 : (nv <= 128 ? 128 : 256);
-  const int nparts = nv <= 256 ? kThreads / nvp : 1;
-#if TSFF_TADJ_ROLL == 3
   // One POINT per wavefront, its lines in rounds of 64 taken from the centre of the tile outwards.  The lines of a point are parallel; a
   // line's chord through the (rectangular) tile shrinks with its distance from the line through the tile's centre, so lines sorted by
   // that distance have nearly equal chords within a round -- the lockstep walk runs as long as the longest chord of its 64 lanes, and
@@ -1610,116 +1300,6 @@ __global__ __launch_bounds__(4 * kThreads) void k_ff2d_table_adj(int nv, const d
       }
     }
   }
-#else
-  for (long pid = (long)blockIdx.x * 4 + grp; pid < npoint; pid += (long)gridDim.x * 4) {
-    const double* fb = f1bar + (size_t)pid * (nv + 2);
-    const double cb = fb[nv], sb = fb[nv + 1];
-    for (int iy = nv <= 256 ? gt % nvp : gt; iy < nv; iy += kThreads) {
-      const int pt = nv <= 256 ? gt / nvp : 0;
-      int ix0 = (nv * pt) / nparts, ix1 = (nv * (pt + 1)) / nparts;
-      const double y = __builtin_fma((double)iy, dv, v0), val = fb[iy] * dv;
-      if (!whole) {
-        // cell coordinate of sample ix along each table axis: u = c * ix + e
-        line_range(cb, (cb * v0 - y * sb - v0) * idv, (double)cx0, (double)cx1, cx0 == 0, cx1 == ncell, ix0, ix1);
-        line_range(sb, (sb * v0 + y * cb - v0) * idv, (double)cy0, (double)cy1, cy0 == 0, cy1 == ncell, ix0, ix1);
-      }
-      double ul, vl;
-      line_origin(cb, sb, y, v0, idv, ul, vl);
-#if TSFF_TADJ_ROLL == 2
-      {
-        const bool fwd = cb >= 0.0;
-        if ((fwd ? sb : -sb) >= 0.0) scatter_line_rolling<1>(T, pitch, nv, cx0, cx1, cy0, cy1, whole, fwd, ix0, ix1, cb, sb, ul, vl, val);
-        else scatter_line_rolling<-1>(T, pitch, nv, cx0, cx1, cy0, cy1, whole, fwd, ix0, ix1, cb, sb, ul, vl, val);
-      }
-#elif TSFF_TADJ_ROLL
-      // Rolling 4 x 4 register window.  Along its line a thread's cell index moves by at most one per step on each axis,
-      // so consecutive stencils overlap in 9 to 16 entries: the contributions are summed in registers and only the row /
-      // column that leaves the window is sent to LDS (4 atomics per axis step instead of 16 per sample).  The walk is
-      // taken in the direction of non-decreasing cx (the sum does not care), cy then moves one way too (sgy, uniform).
-      const bool fwd = cb >= 0.0;
-      const int sgy = (fwd ? sb : -sb) >= 0.0 ? 1 : -1;
-      double acc[4][4];
-      int wcx = 0, wcy = 0;
-      bool open = false;
-      auto flush_all = [&]() {
-        double* q0 = T + (size_t)(wcx - cx0) * pitch + (wcy - cy0);
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-#pragma unroll
-          for (int n = 0; n < 4; ++n) atomicAdd(q0 + (size_t)m * pitch + n, acc[m][n]);
-      };
-      for (int k = 0; k < ix1 - ix0; ++k) {
-        const int ix = fwd ? ix0 + k : ix1 - 1 - k;
-        int cx, cy;
-        double tx, ty;
-        cell_of(__builtin_fma((double)ix, cb, ul), nv, cx, tx);
-        cell_of(__builtin_fma((double)ix, sb, vl), nv, cy, ty);
-        if (!whole && (cx < cx0 || cx >= cx1 || cy < cy0 || cy >= cy1)) continue;
-        const int dxs = cx - wcx, dys = (cy - wcy) * sgy;
-        if (!open || dxs < 0 || dxs > 1 || dys < 0 || dys > 1) {   // first sample, or a jump (tile clipping): restart
-          if (open) flush_all();
-#pragma unroll
-          for (int m = 0; m < 4; ++m)
-#pragma unroll
-            for (int n = 0; n < 4; ++n) acc[m][n] = 0.0;
-          wcx = cx; wcy = cy; open = true;
-        } else {
-          if (dxs == 1) {   // row 0 leaves the window
-            double* q0 = T + (size_t)(wcx - cx0) * pitch + (wcy - cy0);
-#pragma unroll
-            for (int n = 0; n < 4; ++n) atomicAdd(q0 + n, acc[0][n]);
-#pragma unroll
-            for (int n = 0; n < 4; ++n) { acc[0][n] = acc[1][n]; acc[1][n] = acc[2][n]; acc[2][n] = acc[3][n]; acc[3][n] = 0.0; }
-            wcx = cx;
-          }
-          if (dys == 1) {   // one column leaves: the first (cy growing) or the last (cy falling)
-            double* q0 = T + (size_t)(wcx - cx0) * pitch + (wcy - cy0) + (sgy > 0 ? 0 : 3);
-#pragma unroll
-            for (int m = 0; m < 4; ++m) atomicAdd(q0 + (size_t)m * pitch, sgy > 0 ? acc[m][0] : acc[m][3]);
-            if (sgy > 0) {
-#pragma unroll
-              for (int m = 0; m < 4; ++m) { acc[m][0] = acc[m][1]; acc[m][1] = acc[m][2]; acc[m][2] = acc[m][3]; acc[m][3] = 0.0; }
-            } else {
-#pragma unroll
-              for (int m = 0; m < 4; ++m) { acc[m][3] = acc[m][2]; acc[m][2] = acc[m][1]; acc[m][1] = acc[m][0]; acc[m][0] = 0.0; }
-            }
-            wcy = cy;
-          }
-        }
-        double wx[4], wy[4];
-        catmull_rom(tx, wx);
-        catmull_rom(ty, wy);
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-          const double wm = val * wx[m];
-#pragma unroll
-          for (int n = 0; n < 4; ++n) acc[m][n] += wm * wy[n];
-        }
-      }
-      if (open) flush_all();
-#else
-      for (int ix = ix0; ix < ix1; ++ix) {
-        int cx, cy;
-        double tx, ty;
-        cell_of(__builtin_fma((double)ix, cb, ul), nv, cx, tx);
-        cell_of(__builtin_fma((double)ix, sb, vl), nv, cy, ty);
-        if (!whole && (cx < cx0 || cx >= cx1 || cy < cy0 || cy >= cy1)) continue;
-        double wx[4], wy[4];
-        catmull_rom(tx, wx);
-        catmull_rom(ty, wy);
-        double* q0 = T + (size_t)(cx - cx0) * pitch + (cy - cy0);
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-          const double wm = val * wx[m];
-#pragma unroll
-          for (int n = 0; n < 4; ++n) atomicAdd(q0 + (size_t)m * pitch + n, wm * wy[n]);
-        }
-      }
-#endif
-      if (nv <= 256) break;
-    }
-  }
-#endif
   __syncthreads();
   // the workgroup's partial tile goes to its own slab (plain coalesced stores); k_ff2d_sum_tiles adds the slabs of a tile
   // (hundreds of workgroups adding into the same 17 000 addresses by global atomics is exactly what LDS was used to avoid)

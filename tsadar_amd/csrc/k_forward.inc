@@ -109,7 +109,7 @@ __global__ __launch_bounds__(kHalf * (3 - NPAIR), 2) void k_forward_pairs(KStati
   for (int p = 0; p < NPAIR; ++p) {
     const double w_lo = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(ws[p][0]), 0), __builtin_amdgcn_readlane(__double2loint(ws[p][0]), 0));
     w_hi[p] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(ws[p][kPair]), 63), __builtin_amdgcn_readlane(__double2loint(ws[p][kPair]), 63));
-    far[p] = TSFF_FUSED_FAR && far_range_w<NI>(w_lo, w_hi[p], L);
+    far[p] = far_range_w<NI>(w_lo, w_hi[p], L);
   }
   const double ex_wse = (NPAIR == 2 && ((lane >> 4) & 1)) ? w_hi[NPAIR - 1] : w_hi[0];
   __syncthreads();

@@ -45,10 +45,6 @@ __device__ __forceinline__ HD hd_exp(HD x) {
   const double e = exp(x.v);
   return hd_chain(x, e, e, e);
 }
-__device__ __forceinline__ HD hd_log(HD x) {
-  const double r = 1.0 / x.v;
-  return hd_chain(x, log(x.v), r, -r * r);
-}
 __device__ __forceinline__ HD hd_sigmoid(HD x) {
   const double s = sigmoid(x.v), d = s * (1.0 - s);
   return hd_chain(x, s, d, d * (1.0 - 2.0 * s));

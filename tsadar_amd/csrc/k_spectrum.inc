@@ -48,11 +48,7 @@ __host__ __device__ inline size_t ybuf_doubles(const KStatic& S) {
 // with_m: tangent tables of the DLM order; with_ks: k_s cache
 // gm (the kernel's GM): 0 no extra tables; 1 tangent tables of the DLM order -- the Hermite coefficients of d ln fe / dm in
 // LDS, dW/dm read from global memory (one lookup per point of the reverse sweep only; keeping its 13 KB out of LDS is what
-// lets two one-feature workgroups share a CU, TSFF_WM_GLOBAL); 2 the table ADJOINTS (LDS atomics: both regions in LDS)
-#ifndef TSFF_WM_GLOBAL
-#define TSFF_WM_GLOBAL 1
-#endif
-__host__ __device__ inline bool wm_in_lds(int gm) { return gm == 2 || (gm == 1 && !TSFF_WM_GLOBAL); }
+// lets two one-feature workgroups share a CU); 2 the table ADJOINTS (LDS atomics: both regions in LDS)
 // alias: the per-bin adjoint buffer shares the memory of the spectrum buffer (phase layout only, see alias_xy)
 __host__ __device__ inline bool alias_xy(const KStatic& S, int tpf) { return tpf == 256 && S.ppp == 1; }
 // base-point exchange of k_spectrum_fused (EX): per component (w - k V, 1/k, xi_e, F, dH/dxi) 8 units x 16 angles of unit-boundary
@@ -68,7 +64,7 @@ __host__ __device__ inline size_t smem_doubles(const KStatic& S, int nfeat, int 
                                                size_t exd = 0) {   // exd: doubles of the base-point exchange (0: none)
   size_t n = 2 * (size_t)((zh ? kNZh : kNXi2) + S.nvx) + kNXi2 + 4 * (size_t)S.nvx;     // zp, ht, W, hc
   if (gm) n += 4 * (size_t)S.nvx;                                                           // hcm
-  if (wm_in_lds(gm)) n += kNXi2;                                                            // Wm
+  if (gm == 2) n += kNXi2;                                                                  // Wm
   n += (size_t)nfeat * xbuf_doubles(S);                                                     // spectrum buffers
   if (!alias) n += (size_t)nfeat * ybuf_doubles(S);                                         // per-bin adjoint buffers
   if (with_ks) n += (size_t)nfeat * ((size_t)S.npts + 2);                                   // k_s cache
@@ -91,7 +87,7 @@ __device__ __forceinline__ Smem carve(unsigned char* smem, const KStatic& S, int
   m.hc = reinterpret_cast<double2*>(p); p += 4 * (size_t)S.nvx;
   m.hcm = nullptr; m.Wm = nullptr;
   if (gm) { m.hcm = reinterpret_cast<double2*>(p); p += 4 * (size_t)S.nvx; }
-  if (wm_in_lds(gm)) { m.Wm = p; p += kNXi2; }
+  if (gm == 2) { m.Wm = p; p += kNXi2; }
   m.ksc = nullptr;
   if (with_ks) { m.ksc = p; p += (size_t)nfeat * (S.npts + 2); }
   m.taps = p; p += S.ntaps[0] + S.ntaps[1] + 16;

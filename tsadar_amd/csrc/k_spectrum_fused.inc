@@ -196,9 +196,6 @@ __device__ __forceinline__ void conv4_phase(const double* __restrict__ xs, int L
 }
 
 constexpr int kRedSums = 32;   // offset (doubles) of the five partial block sums in the reduction scratch
-#ifndef TSFF_FUSED_FAR
-#define TSFF_FUSED_FAR 1   // wavefronts whose every point has |xi_i| > 28 run the sweep with the asymptotic ion terms
-#endif
 // EX: the third base point of a pair -- the right neighbour of its second sample, which is the FIRST sample of the next
 // thread's pair -- is not evaluated again but taken from that thread: every lane receives (w - k V, 1/k, xi_e, F, dH/dxi) of its
 // neighbour lane's first base point register to register (next_lane_f64: ten DPP moves, no LDS, no wait, no barrier; k_s comes from
@@ -288,7 +285,7 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_fused(KStatic S, KCall K,
     w_lo[p] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(ws[p][0]), 0), __builtin_amdgcn_readlane(__double2loint(ws[p][0]), 0));
     w_hi[p] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(ws[p][kPair]), 63), __builtin_amdgcn_readlane(__double2loint(ws[p][kPair]), 63));
   }
-  const bool far0 = TSFF_FUSED_FAR && far_range_w<NI>(w_lo[0], w_hi[0], L), far1 = TSFF_FUSED_FAR && far_range_w<NI>(w_lo[1], w_hi[1], L);
+  const bool far0 = far_range_w<NI>(w_lo[0], w_hi[0], L), far1 = far_range_w<NI>(w_lo[1], w_hi[1], L);
   // (EX) frequency of the unit-boundary base point this lane evaluates behind the barrier (lane = 16 P + a)
   const double ex_wse = ((lane >> 4) & 1) ? w_hi[1] : w_hi[0];
   __syncthreads();
@@ -372,18 +369,6 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_fused(KStatic S, KCall K,
   if (far0) sweep(std::integral_constant<int, 0>{}, std::true_type{}); else sweep(std::integral_constant<int, 0>{}, std::false_type{});
   if (far1) sweep(std::integral_constant<int, 1>{}, std::true_type{}); else sweep(std::integral_constant<int, 1>{}, std::false_type{});
   TSFF_STAMP_WAVE(9);
-#ifdef TSFF_SWEEP_ONLY   // (measurement build: the sweep alone -- what two sweeping wavefronts per SIMD achieve)
-  {
-    double acc = 0.0;
-#pragma unroll
-    for (int q = 0; q < kStrip; ++q) acc += xa[q] + J[q].wL + J[q].ivTe + J[q].a_e + J[q].Ud + J[q].Vd + J[q].ixi[0] + J[q].a_i[0] + J[q].cs[0] + KA[q].p1a + KA[q].p2a + KA[q].p1b + KA[q].p2b;
-    __syncthreads();
-    TSFF_STAMP(3);
-    if (acc == 1.2345e300) K.gpart[0] = acc;
-    TSFF_STAMP(8);
-    return;
-  }
-#endif
 #pragma unroll
   for (int q = 0; q < kStrip; ++q) {   // the k_L and omega_pe^2 columns of the rows from their angle sums (see KsAcc)
     const int j = JQ(q);

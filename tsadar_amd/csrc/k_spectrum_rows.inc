@@ -131,7 +131,6 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_rows(KStatic S, KCall K, 
 #pragma unroll
     for (int q = 0; q < kStrip; ++q) { zero_lines<NI>(J[q]); xa[q] = 0.0; KA[q].p1a = KA[q].p2a = KA[q].p1b = KA[q].p2b = 0.0; }
     auto far_unit = [&](int p) {
-      if (!TSFF_FUSED_FAR) return false;
       const int jw0 = rd * TSFF_NBINS + (p ? TSFF_NBINS / 2 : 0) + kPair * 64 * hw;
       return far_range<NI>(omgs, jw0, min(jw0 + kPair * 64, npts - 1), L);
     };
