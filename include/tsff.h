@@ -35,7 +35,8 @@
  *   - calls are asynchronous on the handle's stream (tsff_set_stream); the caller synchronises;
  *   - return value 0 = success, negative = error, text via tsff_last_error();
  *   - a refused call (negative return) of tsff_forward, tsff_loss_grad(_packed, _fe), tsff_loss_hess, tsff_array_loss,
- *     tsff_adam_fit, tsff_angular_fit and tsff_form_factor(_grad) has enqueued nothing: their arguments, LDS budgets and buffers are checked before the first
+ *     tsff_adam_fit, tsff_angular_fit, tsff_form_factor(_grad), tsff_form_factor_2d(_range, _save, _grad), tsff_ats_spectrum
+ *     and tsff_ats_adjoint has enqueued nothing: their arguments, LDS budgets and buffers are checked before the first
  *     launch, and tsff_last_launch reports an empty list (other entry points may have enqueued work before a failure);
  *   - a call that breaks several conditions is refused for the first of: the entry point's own arguments (-1), the active slot
  *     list (-1), a leaf the configuration does not have (-2), the leaf A (-3), the batch arguments (-1, then -2),
@@ -393,8 +394,8 @@ int tsff_lbfgs_fit(tsff_handle *h, double *params, const double *fe, const doubl
  *   the device -> tsff_form_factor_grad or tsff_form_factor_2d_grad (saved records; the table adjoint when the table is
  *   trained) -> chain rule (k_ang_chain: amplitudes, Ti tying, activation, the DLM order by central differences with h = 1e-6,
  *   the Arbitrary2V VJP) -> optimiser step and early stop (k_ang_opt),
- * all enqueued on the handle's stream; the call returns once they are enqueued.  Every refusal is checked before the first
- * launch; the handle's scratch is sized in the first epoch, later epochs allocate nothing and nothing synchronises.  Needs
+ * all enqueued on the handle's stream; the call returns once they are enqueued.  Every refusal is checked before anything is
+ * allocated, and the handle's scratch is sized before the first launch: no epoch allocates, and nothing synchronises.  Needs
  * fe_mode == TSFF_FE_PER_LINEOUT and tsff_ats_setup.
  *   spec (HOST): the deck and the optimiser, below;
  *   leaves (device [NP + nv^2 for TSFF_ANG_ARB2V], in/out): the normalised leaves of the one plasma condition, then fval;

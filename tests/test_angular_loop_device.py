@@ -305,6 +305,46 @@ def test_angular_loop_chunks_are_bit_identical(torch_mod):
         assert np.array_equal(best.X, runs[0][0].X) and epoch_loss == runs[0][1]
 
 
+def _stage_records(eng, cfg, two_d):
+    """The launch records of the entry points an epoch is made of, called one by one at the fit's shapes (one lineout, all its
+    points; the table adjoint / the f_e adjoint as the fit of these decks asks for them)."""
+    from tsadar_amd import ThomsonParams
+    from tsadar_amd import _lib as L
+
+    torch = eng.torch
+    tp = ThomsonParams(cfg["parameters"], 1, batch=False, activate=True)
+    phys = tp.physical_matrix()
+    p, gen, rows = phys[0], cfg["parameters"]["general"], eng._ats_shape[0]
+    fe = np.ascontiguousarray(tp()["electron"]["fe"], dtype=np.float64)
+    if two_d:
+        fe = eng.dev(fe)
+        P = eng.form_factor_2d(0, phys, fe, gen["ud"]["angle"], gen["Va"]["angle"], save=True)
+    else:
+        fe = fe.reshape(1, -1)
+        P = eng.form_factor(0, phys, fe)
+    rec = [eng.last_launch()]
+    E = eng.ats_spectrum(P[0], np.ones(rows), p[L.P_LAM], p[L.P_AMP1], p[L.P_AMP2])
+    rec.append(eng.last_launch())
+    Pbar, _ = eng.ats_adjoint(P[0], np.ones(rows), p[L.P_LAM], p[L.P_AMP1], p[L.P_AMP2], torch.ones_like(E))
+    rec.append(eng.last_launch())
+    if two_d:
+        eng.form_factor_2d_grad(0, phys, fe, Pbar.reshape(P.shape), gen["ud"]["angle"], gen["Va"]["angle"], want_table=True, use_saved=True)
+    else:
+        eng.form_factor_grad(0, phys, fe, Pbar.reshape(P.shape), want_fe=True)
+    rec.append(eng.last_launch())
+    torch.cuda.synchronize()
+    return rec
+
+
+def _assert_epoch_is_its_entry_points(eng, cfg, per, two_d):
+    """one epoch's record = k_ang_leaves, the form factor, the ATS chain, the loss, the ATS adjoint, the form-factor adjoint,
+    the chain rule and the optimiser: the loop enqueues what the stand-alone entry points enqueue"""
+    fwd, spec, adj, grad = _stage_records(eng, cfg, two_d)
+    assert all(len(r) > 0 for r in (fwd, spec, adj, grad))
+    assert per[0].startswith("k_ang_leaves<") and per[-2].startswith("k_ang_chain<") and per[-1] == "k_ang_opt"
+    assert per[1:-2] == fwd + spec + ["k_ang_loss", "k_ang_loss_sum"] + adj + grad, (per, fwd, spec, adj, grad)
+
+
 @pytest.mark.gpu
 def test_angular_fit_launch_record(torch_mod):
     from tsadar_amd import _lib as L
@@ -318,6 +358,7 @@ def test_angular_fit_launch_record(torch_mod):
     assert rec == per * 3, rec
     for k in ("k_form_factor_2d<", "k_ats_resunit", "k_ang_loss", "k_ats_resunit_adj", "k_form_factor_2d_adj<", "k_ang_chain<", "k_ang_opt"):
         assert any(r.startswith(k) for r in per), (k, per)
+    _assert_epoch_is_its_entry_points(eng, cfg, per, True)
     # a refused call enqueues nothing
     x = eng.dev(np.zeros(eng.NP))
     spec = dict(generator=L.ANG_DLM, nv=48, active_slots=[L.P_TE, L.P_TE], loss_method=0, un=1.0, dvx=0.25, method=L.ANG_ADAM,
@@ -327,3 +368,43 @@ def test_angular_fit_launch_record(torch_mod):
     with pytest.raises(L.TsffError):
         eng.angular_fit(x, spec, data, 4)
     assert eng.last_launch() == []
+    # the 1-D deck (m a leaf: the adjoint with its f_e tail)
+    cfg, all_data, sa = _case("dlm", "adam", n_epochs=1)
+    _, _, loss_fn, _ = _device(cfg, all_data, sa)
+    eng = loss_fn.ts_diag.engine(True)
+    per = eng.last_launch()
+    assert any(r.startswith("k_form_factor<") for r in per) and "k_fe_adjoint" in per, per
+    _assert_epoch_is_its_entry_points(eng, cfg, per, False)
+
+
+@pytest.mark.gpu
+def test_angular_fit_invalidates_saved_projection_records(torch_mod, monkeypatch):
+    """The fit runs saving 2-D forwards of its own: a token taken from tsff_form_factor_2d_save before the fit is stale after it."""
+    import ctypes as C
+
+    from tsadar_amd import ThomsonParams
+    from tsadar_amd.engine import Engine
+
+    cfg, all_data, sa = _case("arb", "adam", n_epochs=1)
+    tp = ThomsonParams(cfg["parameters"], 1, batch=False, activate=True)
+    phys, fe2 = tp.physical_matrix(), np.ascontiguousarray(tp()["electron"]["fe"], dtype=np.float64)
+    assert fe2.shape == (48, 48)
+    taken = {}
+    fit = Engine.angular_fit
+
+    def save_then_fit(self, *a, **kw):
+        taken["P"] = self.form_factor_2d(0, phys, fe2, save=True)
+        taken.update(self._saved_2d)
+        return fit(self, *a, **kw)
+
+    monkeypatch.setattr(Engine, "angular_fit", save_then_fit)
+    _, _, loss_fn, _ = _device(cfg, all_data, sa)
+    eng = loss_fn.ts_diag.engine(True)
+    assert taken["token"] != 0
+    torch = eng.torch
+    Pbar = torch.ones_like(taken["P"])
+    gp = torch.empty((1, eng.NP), dtype=torch.float64, device=eng.device)
+    eng._sync_stream()
+    rc = eng.lib.tsff_form_factor_2d_grad(eng.h, 0, eng._ptr(taken["phys_d"]), eng._ptr(taken["fe_d"]), 48, 0.0, 0.0, 1, 0, -1,
+                                          C.c_uint64(taken["token"]), eng._ptr(Pbar), eng._ptr(gp), None)
+    assert rc == -22 and "stale or foreign token" in eng.lib.tsff_last_error(eng.h).decode()

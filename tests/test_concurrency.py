@@ -622,11 +622,58 @@ def test_refused_calls_enqueue_nothing(kind, blocks):
         _same(kind, got, ref, f"after '{what}'")
 
 
+@pytest.mark.parametrize("path", ["forward", "adjoint"])
+def test_refusal_after_partial_warm_up_enqueues_nothing(path):
+    """A 2-D call whose warm-up sized only some of its buffers: a 160 x 160 table does not fit LDS, so the plain forward
+    (the adjoint without the table) sizes the padded copy, and the saving forward (the adjoint with the table) still has to
+    grow the projection records (the table adjoint's scratch).  Inside a capture that is refused -- before k_pad2d or
+    anything else is enqueued -- and the handle then computes what a fresh one does."""
+    torch = _torch()
+    from tsadar_amd._lib import TsffError
+
+    cfg = _deck({})
+    sa = dict(sa=np.linspace(53.6, 66.1, 4), weights=np.ones((1, 4)) / 4)
+    eng, fresh = _engine(cfg, sa), _engine(cfg, sa)
+    X = torch.as_tensor(_phys(cfg, sa, 1, 1, 62)[1], device=eng.device)
+    fe2 = torch.as_tensor(_fe2d(160)[1], device=eng.device)
+    Pbar = torch.as_tensor(np.random.default_rng(41).standard_normal((1, 1, eng.npts, 4)), device=eng.device)
+    s = torch.cuda.Stream()
+    if path == "forward":
+        warm = lambda: eng.form_factor_2d(1, X, fe2, 25.0, -40.0)
+        refused = lambda: eng.form_factor_2d(1, X, fe2, 25.0, -40.0, save=True)
+    else:
+        warm = lambda: eng.form_factor_2d_grad(1, X, fe2, Pbar, 25.0, -40.0, want_table=False)
+        refused = lambda: eng.form_factor_2d_grad(1, X, fe2, Pbar, 25.0, -40.0, want_table=True)
+    with torch.cuda.stream(s):
+        warm()
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with pytest.raises(TsffError, match="graph capture"):
+        with torch.cuda.graph(g, stream=s):
+            refused()
+    assert eng.last_launch() == []
+
+    def valid(e):
+        if path == "forward":
+            P = e.form_factor_2d(1, X, fe2, 25.0, -40.0, save=True)
+            gp, _ = e.form_factor_2d_grad(1, X, fe2, Pbar, 25.0, -40.0, want_table=False, use_saved=True)
+            return _host(dict(P=P, gp=gp))
+        gp, gf = e.form_factor_2d_grad(1, X, fe2, Pbar, 25.0, -40.0, want_table=True)
+        return _host(dict(gp=gp, gf2d=gf))
+
+    with torch.cuda.stream(s):
+        got = valid(eng)
+    torch.cuda.synchronize()
+    ref = valid(fresh)
+    torch.cuda.synchronize()
+    _same(path, got, ref, "after the refused capture")
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # graph capture
 # ---------------------------------------------------------------------------------------------------------------------
 
-CAPTURE = [("headline", {}, 512), ("rows_split", {"ppp": 5, "m": True, "nvx": 320}, 16), ("dlm", {"m": True}, 256)]
+CAPTURE =[("headline", {}, 512), ("rows_split", {"ppp": 5, "m": True, "nvx": 320}, 16), ("dlm", {"m": True}, 256)]
 
 
 @pytest.mark.parametrize("name,d,B", CAPTURE, ids=[c[0] for c in CAPTURE])

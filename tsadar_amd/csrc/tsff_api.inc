@@ -28,6 +28,19 @@ struct DevBuf {
   template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
+// what the projection records of a saving 2-D forward were made from: the adjoint may use them for exactly that (use_saved)
+struct ProjRecords {
+  long begin = -1, end = -1;
+  int nv = 0, feature = -1, B = 0;
+  const void *phys = nullptr, *fe = nullptr;
+  double ud = 0.0, va = 0.0;
+  void invalidate() { begin = end = -1; }
+  bool covers(long b, long e, int nv_, int feature_) const { return begin == b && end == e && nv == nv_ && feature == feature_; }
+  bool made_from(const void* phys_, const void* fe_, double ud_, double va_, int B_) const {
+    return phys == phys_ && fe == fe_ && ud == ud_ && va == va_ && B == B_;
+  }
+};
+
 }  // namespace tsff
 
 struct tsff_handle {
@@ -76,10 +89,7 @@ struct tsff_handle {
   tsff::DevBuf tickets;      // per (lineout, feature) arrival counters of its split form (small batches)
   tsff::DevBuf proj;         // projection records of tsff_form_factor_2d_save (proj2d_doubles per point)
   tsff::DevBuf fbar_parts;   // per-workgroup partial tiles of the table adjoint
-  long proj_begin = -1, proj_end = -1;
-  int proj_nv = 0, proj_feature = -1, proj_B = 0;
-  const void* proj_phys = nullptr; const void* proj_fe = nullptr;   // what the records were made from (checked by use_saved)
-  double proj_ud = 0.0, proj_va = 0.0;
+  tsff::ProjRecords proj_rec;
   uint64_t proj_token = 0, proj_counter = 0;   // generation token of the records (0: none); see tsff_form_factor_2d_save
   tsff::DevBuf lbparts;      // per-worker partials of the lineout-scalar adjoints (summed in a fixed order by k_lbacc_reduce)
   tsff::DevBuf lbacc, f1bar, fbar_pad;  // adjoint of the 2-D path: lineout-scalar adjoints, f1bar per point, padded table adjoint
@@ -1201,20 +1211,57 @@ int tsff_chi_table(tsff_handle* h, const double* fe, int32_t n, double* W) {
   return 0;
 }
 
-static int form_factor_impl(tsff_handle* h, int32_t feature, const double* phys, const double* fe, int32_t B, double* P) {
-  if (!h || !phys || !P || B < 1 || feature < 0 || feature > 1) return fail(h, -1, "bad argument");
-  if (h->fe_mode == TSFF_FE_DLM) return fail(h, -3, "tsff_form_factor takes explicit distribution functions (fe_mode SHARED or PER_LINEOUT)");
-  int rc = check_fe(h, fe);
-  if (rc) return rc;
-  if ((rc = ensure_workspace(h, B))) return rc;
+// The form-factor, 2-D and ATS paths below have the shape of the loss + gradient path (loss_grad_prepare / loss_grad_enqueue).
+// A plan struct holds what the launches of a path need.  X_prepare takes the shapes of a call: it refuses what they rule out
+// (a point range, an LDS budget), then sizes every buffer of the path -- when it returns non-zero, nothing has been enqueued.
+// X_enqueue takes the plan and the call's pointers and only launches (kernels, memsets, the timing ring's events): it allocates
+// and refuses nothing, only a HIP error can fail it.  An entry point is its own argument checks + prepare + enqueue;
+// tsff_angular_fit prepares its stages once and enqueues them every epoch.  dry: the refusals only, the handle stays as it is
+// (tsff_angular_fit asks for every stage's refusals before it allocates anything).
+
+// The tail of the f_e adjoint (tsff_form_factor_grad, tsff_loss_grad_fe): `lead` blocks [B][.] of table adjoints in Wb and Hys,
+// which the caller sums into the first block (k_sum_chunks / k_add_parts), then Yt = Lg^T Wb (k_wgemm_t) and k_fe_adjoint
+static int fe_tail_prepare(tsff_handle* h, size_t lead, int B) {
+  TSFF_ENSURE(h, h->Wb, lead * B * kNXi2 * sizeof(double));
+  TSFF_ENSURE(h, h->Hys, lead * B * 2 * h->S.nvx * sizeof(double));
+  TSFF_ENSURE(h, h->Yt, (size_t)B * 2 * kNXi1 * sizeof(double));
+  return 0;
+}
+static void fe_tail_outputs(tsff_handle* h, KCall& K, int B) {
+  K.Wb_out = h->Wb.as<double>();
+  K.Hy_out = h->Hys.as<double>();
+  K.Hs_out = K.Hy_out + (size_t)B * h->S.nvx;
+  K.htm = nullptr; K.Wm = nullptr;  // the LDS region of the tangent tables holds the table adjoints
+}
+static int fe_tail_enqueue(tsff_handle* h, const KCall& K, int B, double* grad_fe) {
+  dim3 ggrid(kNXi1 / kGN, (2 * B + kGM - 1) / kGM);
+  TSFF_LAUNCH0(h, k_wgemm_t, ggrid, dim3(kThreads), 0, h->stream, h->S.lg, K.Wb_out, h->S.xi2, (int)B, h->Yt.as<double>());
+  TSFF_HIP(h, hipGetLastError());
+  TSFF_LAUNCH0(h, k_fe_adjoint, dim3(B), dim3(kThreads), h->smem_adjoint, h->stream, h->S, K.ht, h->Yt.as<double>(),
+                     K.Wb_out, K.Hy_out, K.Hs_out, grad_fe);
+  TSFF_HIP(h, hipGetLastError());
+  return 0;
+}
+
+// ---- the 1-D form factor
+struct FormFactorPlan {
+  int feature = 0, B = 0;
+  dim3 grid;
+};
+
+static int form_factor_prepare(tsff_handle* h, int feature, int B, FormFactorPlan& p, bool dry = false) {
+  p.feature = feature; p.B = B;
+  p.grid = dim3(B, angle_chunks(h, B));
+  return dry ? 0 : ensure_workspace(h, B);
+}
+
+static int form_factor_enqueue(tsff_handle* h, const FormFactorPlan& p, const double* phys, const double* fe, double* P) {
   KCall K{};
-  K.params = phys; K.B = B;
-  rc = prepare_tables(h, phys, fe, B, K);
-  if (rc) return rc;
-  dim3 grid(B, angle_chunks(h, B)), block(kThreads);
+  K.params = phys; K.B = p.B;
+  if (int rc = prepare_tables(h, phys, fe, p.B, K)) return rc;
   with_ion<TSFF_MAX_ION>(h->n_ion, [&](auto N) {
-    TSFF_LAUNCH(h, k_form_factor, (N.value), grid, block, h->smem_spectrum, h->stream, h->S, K, (int)feature, h->S.omgs[feature],
-                h->S.npts, P);
+    TSFF_LAUNCH(h, k_form_factor, (N.value), p.grid, dim3(kThreads), h->smem_spectrum, h->stream, h->S, K, p.feature,
+                h->S.omgs[p.feature], h->S.npts, P);
   });
   TSFF_HIP(h, hipGetLastError());
   return 0;
@@ -1222,172 +1269,149 @@ static int form_factor_impl(tsff_handle* h, int32_t feature, const double* phys,
 
 int tsff_form_factor(tsff_handle* h, int32_t feature, const double* phys, const double* fe, int32_t B, double* P) {
   DevGuard dg__(h);
-  return form_factor_impl(h, feature, phys, fe, B, P);
-}
-
-// LDS of k_form_factor_adj (with the f_e adjoint or without)
-static size_t form_factor_grad_smem(const tsff_handle* h, bool grad_fe) {
-  return sizeof(double) * smem_doubles(h->S, 1, grad_fe ? 2 : 0, false);
-}
-
-static int form_factor_grad_impl(tsff_handle* h, int32_t feature, const double* phys, const double* fe, int32_t B, const double* Pbar,
-                                 double* grad_phys, double* grad_fe) {
-  if (!h || !phys || !Pbar || !grad_phys || B < 1 || feature < 0 || feature > 1) return fail(h, -1, "bad argument");
-  if (h->fe_mode == TSFF_FE_DLM) return fail(h, -3, "tsff_form_factor_grad takes explicit distribution functions (fe_mode SHARED or PER_LINEOUT)");
-  if (grad_fe && h->fe_mode != TSFF_FE_PER_LINEOUT) return fail(h, -2, "gradient w.r.t. f_e needs fe_mode == TSFF_FE_PER_LINEOUT");
-  if (int rc = check_fe(h, fe)) return rc;
-  const size_t smem = form_factor_grad_smem(h, grad_fe != nullptr);
-  if (smem > kLdsLimit) return fail(h, TSFF_ERR_LDS, "LDS budget exceeded (%zu B)", smem);
-  int rc = ensure_workspace(h, B);
+  if (!h || !phys || !P || B < 1 || feature < 0 || feature > 1) return fail(h, -1, "bad argument");
+  if (h->fe_mode == TSFF_FE_DLM) return fail(h, -3, "tsff_form_factor takes explicit distribution functions (fe_mode SHARED or PER_LINEOUT)");
+  FormFactorPlan p;
+  int rc = check_fe(h, fe);
+  if (!rc) rc = form_factor_prepare(h, feature, B, p);
   if (rc) return rc;
+  return form_factor_enqueue(h, p, phys, fe, P);
+}
+
+// ---- its adjoint (grad_fe: with the f_e adjoint)
+struct FormFactorAdjPlan {
+  int feature = 0, B = 0;
+  bool grad_fe = false;
+  size_t smem = 0;                    // LDS of k_form_factor_adj
+  unsigned nchunk = 1; int nworker = 0;   // angle chunks (blockIdx.y); partials of the lineout-scalar adjoints: one per wavefront
+};                                        // and angle chunk (every slot is written)
+
+static int form_factor_adj_prepare(tsff_handle* h, int feature, int B, bool grad_fe, FormFactorAdjPlan& p, bool dry = false) {
+  p.feature = feature; p.B = B; p.grad_fe = grad_fe;
+  p.smem = sizeof(double) * smem_doubles(h->S, 1, grad_fe ? 2 : 0, false);
+  if (p.smem > kLdsLimit) return fail(h, TSFF_ERR_LDS, "LDS budget exceeded (%zu B)", p.smem);
+  p.nchunk = angle_chunks(h, B);
+  p.nworker = (int)p.nchunk * (kThreads / 64);
+  if (dry) return 0;
+  if (int rc = ensure_workspace(h, B)) return rc;
+  const int NLB = 9 + 3 * h->n_ion;
+  TSFF_ENSURE(h, h->lbacc, (size_t)B * h->S.G * NLB * sizeof(double));
+  TSFF_ENSURE(h, h->lbparts, (size_t)B * h->S.G * p.nworker * NLB * sizeof(double));
+  return grad_fe ? fe_tail_prepare(h, p.nchunk, B) : 0;   // per-chunk blocks [chunk][B][.], summed in order by k_sum_chunks
+}
+
+static int form_factor_adj_enqueue(tsff_handle* h, const FormFactorAdjPlan& p, const double* phys, const double* fe, const double* Pbar,
+                                   double* grad_phys, double* grad_fe) {
+  const int B = p.B, NLB = 9 + 3 * h->n_ion;
   KCall K{};
   K.params = phys; K.B = B;
-  const int NLB = 9 + 3 * h->n_ion, nvx = h->S.nvx;
-  const unsigned nchunk = angle_chunks(h, B);
-  const int nworker = (int)nchunk * (kThreads / 64);   // one partial per wavefront and angle chunk (every slot is written)
-  TSFF_ENSURE(h, h->lbacc, (size_t)B * h->S.G * NLB * sizeof(double));
-  TSFF_ENSURE(h, h->lbparts, (size_t)B * h->S.G * nworker * NLB * sizeof(double));
-  if (grad_fe) {   // per-chunk blocks [chunk][B][.], summed in order by k_sum_chunks
-    TSFF_ENSURE(h, h->Wb, (size_t)nchunk * B * kNXi2 * sizeof(double));
-    TSFF_ENSURE(h, h->Hys, (size_t)nchunk * B * 2 * nvx * sizeof(double));
-    TSFF_ENSURE(h, h->Yt, (size_t)B * 2 * kNXi1 * sizeof(double));
-  }
-  rc = prepare_tables(h, phys, fe, B, K);
+  int rc = prepare_tables(h, phys, fe, B, K);
   if (rc) return rc;
-  if (grad_fe) {
-    K.Wb_out = h->Wb.as<double>();
-    K.Hy_out = h->Hys.as<double>();
-    K.Hs_out = K.Hy_out + (size_t)B * nvx;
-    K.htm = nullptr; K.Wm = nullptr;
-  }
-  dim3 grid(B, nchunk), block(kThreads);
+  if (p.grad_fe) fe_tail_outputs(h, K, B);
+  dim3 grid(B, p.nchunk), block(kThreads);
   rc = with_ion<TSFF_MAX_ION>(h->n_ion, [&](auto N) {
-    return with_bool(grad_fe != nullptr, [&](auto FE) {
-      TSFF_LAUNCH_LDS(h, k_form_factor_adj, (N.value, FE.value ? 2 : 0), kLdsLimit, grid, block, smem, h->stream, h->S, K, (int)feature,
-                      h->S.omgs[feature], h->S.npts, Pbar, h->lbparts.as<double>());
-      TSFF_LAUNCH0(h, k_lbacc_reduce, dim3(B * h->S.G), dim3(kThreads), 0, h->stream, h->lbparts.as<double>(), nworker, NLB,
+    return with_bool(p.grad_fe, [&](auto FE) {
+      TSFF_LAUNCH_LDS(h, k_form_factor_adj, (N.value, FE.value ? 2 : 0), kLdsLimit, grid, block, p.smem, h->stream, h->S, K, p.feature,
+                      h->S.omgs[p.feature], h->S.npts, Pbar, h->lbparts.as<double>());
+      TSFF_LAUNCH0(h, k_lbacc_reduce, dim3(B * h->S.G), dim3(kThreads), 0, h->stream, h->lbparts.as<double>(), p.nworker, NLB,
                    h->lbacc.as<double>());
-      TSFF_LAUNCH(h, k_ff2d_lines_adj, (N.value), dim3((B + 63) / 64), dim3(64), 0, h->stream, h->S, phys, (int)feature, (int)B,
+      TSFF_LAUNCH(h, k_ff2d_lines_adj, (N.value), dim3((B + 63) / 64), dim3(64), 0, h->stream, h->S, phys, p.feature, B,
                   h->lbacc.as<double>(), grad_phys, 1);
       return 0;
     });
   });
   if (rc) return rc;
   TSFF_HIP(h, hipGetLastError());
-  if (grad_fe) {
-    if (nchunk > 1) {
-      const long nw = (long)B * kNXi2, nh = (long)2 * B * nvx;
-      TSFF_LAUNCH0(h, k_sum_chunks, dim3((unsigned)std::min<long>((nw + kThreads - 1) / kThreads, 1024)), dim3(kThreads), 0, h->stream,
-                         K.Wb_out, nw, (int)nchunk);
-      TSFF_LAUNCH0(h, k_sum_chunks, dim3((unsigned)std::min<long>((nh + kThreads - 1) / kThreads, 1024)), dim3(kThreads), 0, h->stream,
-                         K.Hy_out, nh, (int)nchunk);
-    }
-    dim3 ggrid(kNXi1 / kGN, (2 * B + kGM - 1) / kGM);
-    TSFF_LAUNCH0(h, k_wgemm_t, ggrid, dim3(kThreads), 0, h->stream, h->S.lg, K.Wb_out, h->S.xi2, (int)B, h->Yt.as<double>());
-    TSFF_HIP(h, hipGetLastError());
-    TSFF_LAUNCH0(h, k_fe_adjoint, dim3(B), dim3(kThreads), h->smem_adjoint, h->stream, h->S, K.ht, h->Yt.as<double>(),
-                       K.Wb_out, K.Hy_out, K.Hs_out, grad_fe);
-    TSFF_HIP(h, hipGetLastError());
+  if (!p.grad_fe) return 0;
+  if (p.nchunk > 1) {
+    const long nw = (long)B * kNXi2, nh = (long)2 * B * h->S.nvx;
+    TSFF_LAUNCH0(h, k_sum_chunks, dim3((unsigned)std::min<long>((nw + kThreads - 1) / kThreads, 1024)), dim3(kThreads), 0, h->stream,
+                       K.Wb_out, nw, (int)p.nchunk);
+    TSFF_LAUNCH0(h, k_sum_chunks, dim3((unsigned)std::min<long>((nh + kThreads - 1) / kThreads, 1024)), dim3(kThreads), 0, h->stream,
+                       K.Hy_out, nh, (int)p.nchunk);
   }
-  return 0;
+  return fe_tail_enqueue(h, K, B, grad_fe);
 }
 
 int tsff_form_factor_grad(tsff_handle* h, int32_t feature, const double* phys, const double* fe, int32_t B, const double* Pbar,
                           double* grad_phys, double* grad_fe) {
   DevGuard dg__(h);
-  return form_factor_grad_impl(h, feature, phys, fe, B, Pbar, grad_phys, grad_fe);
-}
-
-int tsff_form_factor_2d(tsff_handle* h, int32_t feature, const double* phys, const double* fe2d, int32_t nv,
-                        int32_t shared_fe, double ud_angle_deg, double va_angle_deg, int32_t B, double* P) {
-  return tsff_form_factor_2d_range(h, feature, phys, fe2d, nv, shared_fe, ud_angle_deg, va_angle_deg, B, 0, -1, P);
-}
-
-static int form_factor_2d_impl(tsff_handle* h, int32_t feature, const double* phys, const double* fe2d, int32_t nv,
-                               int32_t shared_fe, double ud_angle_deg, double va_angle_deg, int32_t B, int64_t point_begin,
-                               int64_t point_end, double* P, bool save);
-
-int tsff_form_factor_2d_range(tsff_handle* h, int32_t feature, const double* phys, const double* fe2d, int32_t nv,
-                              int32_t shared_fe, double ud_angle_deg, double va_angle_deg, int32_t B, int64_t point_begin,
-                              int64_t point_end, double* P) {
-  DevGuard dg__(h);
-  return form_factor_2d_impl(h, feature, phys, fe2d, nv, shared_fe, ud_angle_deg, va_angle_deg, B, point_begin, point_end, P, false);
-}
-
-int tsff_form_factor_2d_save(tsff_handle* h, int32_t feature, const double* phys, const double* fe2d, int32_t nv,
-                             double ud_angle_deg, double va_angle_deg, int32_t B, int64_t point_begin, int64_t point_end,
-                             double* P, uint64_t* token) {
-  DevGuard dg__(h);
-  if (!h) return -1;
-  if (!token) return fail(h, -1, "tsff_form_factor_2d_save: token missing");
-  *token = 0;
-  if (nv > 256) return fail(h, -2, "tsff_form_factor_2d_save: nv <= 256");
-  const int rc = form_factor_2d_impl(h, feature, phys, fe2d, nv, 1, ud_angle_deg, va_angle_deg, B, point_begin, point_end, P, true);
+  if (!h || !phys || !Pbar || !grad_phys || B < 1 || feature < 0 || feature > 1) return fail(h, -1, "bad argument");
+  if (h->fe_mode == TSFF_FE_DLM) return fail(h, -3, "tsff_form_factor_grad takes explicit distribution functions (fe_mode SHARED or PER_LINEOUT)");
+  if (grad_fe && h->fe_mode != TSFF_FE_PER_LINEOUT) return fail(h, -2, "gradient w.r.t. f_e needs fe_mode == TSFF_FE_PER_LINEOUT");
+  FormFactorAdjPlan p;
+  int rc = check_fe(h, fe);
+  if (!rc) rc = form_factor_adj_prepare(h, feature, B, grad_fe != nullptr, p);
   if (rc) return rc;
-  // generation token: a per-handle call counter mixed with what the records were made from (buffers, angles, range) -- never 0
-  auto mix = [](uint64_t a, uint64_t b) { a ^= b + 0x9e3779b97f4a7c15ull + (a << 6) + (a >> 2); return a; };
-  uint64_t t = ++h->proj_counter, bits;
-  t = mix(t, (uint64_t)(uintptr_t)phys); t = mix(t, (uint64_t)(uintptr_t)fe2d);
-  std::memcpy(&bits, &ud_angle_deg, 8); t = mix(t, bits);
-  std::memcpy(&bits, &va_angle_deg, 8); t = mix(t, bits);
-  t = mix(t, (uint64_t)h->proj_begin); t = mix(t, (uint64_t)h->proj_end);
-  h->proj_token = (t << 16) | (h->proj_counter & 0xffff) | 1ull << 63;
-  *token = h->proj_token;
+  return form_factor_adj_enqueue(h, p, phys, fe, Pbar, grad_phys, grad_fe);
+}
+
+// ---- the 2-D form factor (save: with the projection records of its points for the adjoint that follows)
+struct FormFactor2dPlan {
+  int feature = 0, nv = 0, B = 0;
+  bool shared = true, save = false;
+  long begin = 0, end = 0;          // the points [begin, end) of the flat point list (empty: nothing to launch)
+  bool lds = false; int groups = 0; // the table fits LDS (nv <= 128; else read through L1/L2 from a padded copy); point groups per workgroup
+  size_t smem = 0, tstride = 0;     // dynamic LDS; doubles from one lineout's table to the next
+  long max_grid = 0;                // persistent workgroups of groups x 256 threads: one per CU with the table in LDS
+};
+
+// any 2-D forward invalidates the projection records of an earlier save, and their token
+static void invalidate_proj(tsff_handle* h) {
+  h->proj_rec.invalidate();
+  h->proj_token = 0;
+}
+
+static int form_factor_2d_prepare(tsff_handle* h, int feature, int nv, bool shared, int B, int64_t point_begin, int64_t point_end,
+                                  bool save, FormFactor2dPlan& p, bool dry = false) {
+  p.feature = feature; p.nv = nv; p.B = B; p.shared = shared; p.save = save;
+  const long ntotal = (long)B * h->S.G * h->S.npts * h->S.n_angles;
+  p.begin = point_begin; p.end = point_end < 0 ? ntotal : point_end;
+  if (p.begin < 0 || p.end > ntotal || p.begin > p.end) return fail(h, -1, "bad point range");
+  if (!dry) invalidate_proj(h);
+  if (p.begin == p.end) return 0;
+  constexpr int kGL = TSFF_2D_GROUPS_LDS, kGG = TSFF_2D_GROUPS_L2;
+  p.lds = sizeof(double) * smem2d_doubles(nv, true, kGL) <= kLdsLimit;
+  p.groups = p.lds ? kGL : kGG;
+  p.smem = sizeof(double) * smem2d_doubles(nv, p.lds, p.groups);
+  if (p.smem > kLdsLimit) return fail(h, -2, "nv = %d needs %zu B of LDS scratch", nv, p.smem);
+  p.max_grid = (long)h->ncu2d() * (p.lds ? 1 : 8);  // (the L2 variant is register-limited to two workgroups per CU)
+  p.tstride = p.lds ? (size_t)nv * nv : pad2d_doubles(nv);
+  if (dry) return 0;
+  if (!p.lds) TSFF_ENSURE(h, h->fpad, p.tstride * (shared ? 1 : B) * sizeof(double));
+  if (save) TSFF_ENSURE(h, h->proj, (size_t)(p.end - p.begin) * proj2d_doubles(nv) * sizeof(double));
   return 0;
 }
 
-static int form_factor_2d_impl(tsff_handle* h, int32_t feature, const double* phys, const double* fe2d, int32_t nv,
-                               int32_t shared_fe, double ud_angle_deg, double va_angle_deg, int32_t B, int64_t point_begin,
-                               int64_t point_end, double* P, bool save) {
-  if (!h || !phys || !fe2d || !P || B < 1 || feature < 0 || feature > 1 || nv < 4 || nv > 2048)
-    return fail(h, -1, "bad argument");
-  const long ntotal = (long)B * h->S.G * h->S.npts * h->S.n_angles;
-  const long pbegin = point_begin, pend = point_end < 0 ? ntotal : point_end;
-  if (pbegin < 0 || pend > ntotal || pbegin > pend) return fail(h, -1, "bad point range");
-  h->proj_begin = h->proj_end = -1; h->proj_token = 0;   // any 2-D forward invalidates the projection records of an earlier save
-  if (pbegin == pend) return 0;
-  constexpr int kGL = TSFF_2D_GROUPS_LDS, kGG = TSFF_2D_GROUPS_L2;  // point groups per workgroup
-  const bool lds = sizeof(double) * smem2d_doubles(nv, true, kGL) <= kLdsLimit;  // nv <= 128
-  const int kG2 = lds ? kGL : kGG;
-  const size_t smem = sizeof(double) * smem2d_doubles(nv, lds, kG2);
-  if (smem > kLdsLimit) return fail(h, -2, "nv = %d needs %zu B of LDS scratch", (int)nv, smem);
-  // persistent workgroups of kG2 x 256 threads: one per CU with the table in LDS
-  int ncu = 256;
-  (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->device);
-  const long want = (long)ncu * (lds ? 1 : 8);  // (the L2 variant is register-limited to two workgroups per CU)
+static int form_factor_2d_enqueue(tsff_handle* h, const FormFactor2dPlan& p, const double* phys, const double* fe2d, double ud_angle_deg,
+                                  double va_angle_deg, double* P) {
+  if (p.begin == p.end) return 0;
   const long per_lineout = (long)h->S.G * h->S.npts * h->S.n_angles;
   // one table per launch: a shared table covers the whole range, per-lineout tables one launch per lineout
-  const int b_first = shared_fe ? 0 : (int)(pbegin / per_lineout), b_last = shared_fe ? 0 : (int)((pend - 1) / per_lineout);
+  const int b_first = p.shared ? 0 : (int)(p.begin / per_lineout), b_last = p.shared ? 0 : (int)((p.end - 1) / per_lineout);
   const double* tables = fe2d;
-  size_t tstride = (size_t)nv * nv;
-  if (!lds) {  // tables that do not fit LDS are read through L1/L2 from a padded copy (ghost cells by k_pad2d)
-    const int ntab = shared_fe ? 1 : B;
-    tstride = pad2d_doubles((int)nv);
-    TSFF_ENSURE(h, h->fpad, tstride * ntab * sizeof(double));
-    TSFF_LAUNCH0(h, k_pad2d, dim3(ntab), dim3(kThreads), 0, h->stream, fe2d, (int)nv, h->fpad.as<double>());
+  if (!p.lds) {   // ghost cells by k_pad2d
+    TSFF_LAUNCH0(h, k_pad2d, dim3(p.shared ? 1 : p.B), dim3(kThreads), 0, h->stream, fe2d, p.nv, h->fpad.as<double>());
     TSFF_HIP(h, hipGetLastError());
-    tables = h->fpad.as<double>() + pad2d_margin((int)nv);   // (the padded table behind its leading margin; per-lineout tables tstride apart)
+    tables = h->fpad.as<double>() + pad2d_margin(p.nv);   // (the padded table behind its leading margin; per-lineout tables tstride apart)
   }
   double* proj = nullptr;
-  h->proj_begin = h->proj_end = -1; h->proj_token = 0;
-  if (save) {   // projection records of the points [pbegin, pend) for the adjoint that follows (tsff_form_factor_2d_grad)
-    TSFF_ENSURE(h, h->proj, (size_t)(pend - pbegin) * proj2d_doubles(nv) * sizeof(double));
+  if (p.save) {
     proj = h->proj.as<double>();
-    h->proj_begin = pbegin; h->proj_end = pend; h->proj_nv = nv; h->proj_feature = feature;
-    h->proj_phys = phys; h->proj_fe = fe2d; h->proj_ud = ud_angle_deg; h->proj_va = va_angle_deg; h->proj_B = B;
+    h->proj_rec = {p.begin, p.end, p.nv, p.feature, p.B, phys, fe2d, ud_angle_deg, va_angle_deg};
   }
   for (int b = b_first; b <= b_last; ++b) {
-    const long lo = shared_fe ? pbegin : std::max(pbegin, (long)b * per_lineout);
-    const long hi = shared_fe ? pend : std::min(pend, (long)(b + 1) * per_lineout);
-    const double* table = tables + (shared_fe ? 0 : (size_t)b * tstride);
-    dim3 grid((unsigned)std::min((hi - lo + kG2 - 1) / kG2, want)), block(kG2 * kThreads);
+    const long lo = p.shared ? p.begin : std::max(p.begin, (long)b * per_lineout);
+    const long hi = p.shared ? p.end : std::min(p.end, (long)(b + 1) * per_lineout);
+    const double* table = tables + (p.shared ? 0 : (size_t)b * p.tstride);
+    dim3 grid((unsigned)std::min((hi - lo + p.groups - 1) / p.groups, p.max_grid)), block(p.groups * kThreads);
     if (int rc = timing_begin(h)) return rc;
     int rc = with_ion<TSFF_MAX_ION>(h->n_ion, [&](auto N) {
-      return with_bool(lds, [&](auto LDS) {
-        return with_bool(save, [&](auto SAVE) {
-          TSFF_LAUNCH_LDS(h, k_form_factor_2d, (N.value, LDS.value, LDS.value ? kGL : kGG, SAVE.value), kLdsLimit, grid, block, smem,
-                          h->stream, h->S, phys, table, (int)nv, ud_angle_deg * kPi / 180.0, va_angle_deg * kPi / 180.0, (int)feature,
-                          lo, hi, P, proj);
+      return with_bool(p.lds, [&](auto LDS) {
+        return with_bool(p.save, [&](auto SAVE) {
+          constexpr int kG2 = LDS.value ? TSFF_2D_GROUPS_LDS : TSFF_2D_GROUPS_L2;
+          TSFF_LAUNCH_LDS(h, k_form_factor_2d, (N.value, LDS.value, kG2, SAVE.value), kLdsLimit, grid, block, p.smem, h->stream, h->S,
+                          phys, table, p.nv, ud_angle_deg * kPi / 180.0, va_angle_deg * kPi / 180.0, p.feature, lo, hi, P, proj);
           return 0;
         });
       });
@@ -1399,19 +1423,136 @@ static int form_factor_2d_impl(tsff_handle* h, int32_t feature, const double* ph
   return 0;
 }
 
-static int table_adjoint_2d(tsff_handle* h, int nv, long npoint, double* grad_fe2d);
-static int form_factor_2d_grad_impl(tsff_handle* h, int32_t feature, const double* phys, const double* fe2d, int32_t nv,
-                                    double ud_angle_deg, double va_angle_deg, int32_t B, int64_t point_begin, int64_t point_end,
-                                    const double* proj, const double* Pbar, double* grad_phys, double* grad_fe2d);
+static int form_factor_2d(tsff_handle* h, int32_t feature, const double* phys, const double* fe2d, int32_t nv, int32_t shared_fe,
+                          double ud_angle_deg, double va_angle_deg, int32_t B, int64_t point_begin, int64_t point_end, double* P,
+                          bool save) {
+  if (!h || !phys || !fe2d || !P || B < 1 || feature < 0 || feature > 1 || nv < 4 || nv > 2048)
+    return fail(h, -1, "bad argument");
+  FormFactor2dPlan p;
+  if (int rc = form_factor_2d_prepare(h, feature, nv, shared_fe != 0, B, point_begin, point_end, save, p)) return rc;
+  return form_factor_2d_enqueue(h, p, phys, fe2d, ud_angle_deg, va_angle_deg, P);
+}
 
-// LDS of k_form_factor_2d_adj for a table of nv x nv (lds: the table fits LDS)
-static size_t form_factor_2d_grad_smem(int nv, bool* lds_out) {
-  auto gsz = [&](int n) { return (2 + (size_t)(n <= 64 ? 4 : (n <= 128 ? 2 : 1))) * n + 2 * (size_t)n + 16 + 96; };
+int tsff_form_factor_2d_range(tsff_handle* h, int32_t feature, const double* phys, const double* fe2d, int32_t nv,
+                              int32_t shared_fe, double ud_angle_deg, double va_angle_deg, int32_t B, int64_t point_begin,
+                              int64_t point_end, double* P) {
+  DevGuard dg__(h);
+  return form_factor_2d(h, feature, phys, fe2d, nv, shared_fe, ud_angle_deg, va_angle_deg, B, point_begin, point_end, P, false);
+}
+
+int tsff_form_factor_2d(tsff_handle* h, int32_t feature, const double* phys, const double* fe2d, int32_t nv,
+                        int32_t shared_fe, double ud_angle_deg, double va_angle_deg, int32_t B, double* P) {
+  return tsff_form_factor_2d_range(h, feature, phys, fe2d, nv, shared_fe, ud_angle_deg, va_angle_deg, B, 0, -1, P);
+}
+
+int tsff_form_factor_2d_save(tsff_handle* h, int32_t feature, const double* phys, const double* fe2d, int32_t nv,
+                             double ud_angle_deg, double va_angle_deg, int32_t B, int64_t point_begin, int64_t point_end,
+                             double* P, uint64_t* token) {
+  DevGuard dg__(h);
+  if (!h) return -1;
+  if (!token) return fail(h, -1, "tsff_form_factor_2d_save: token missing");
+  *token = 0;
+  if (nv > 256) return fail(h, -2, "tsff_form_factor_2d_save: nv <= 256");
+  const int rc = form_factor_2d(h, feature, phys, fe2d, nv, 1, ud_angle_deg, va_angle_deg, B, point_begin, point_end, P, true);
+  if (rc) return rc;
+  // generation token: a per-handle call counter mixed with what the records were made from (buffers, angles, range) -- never 0
+  auto mix = [](uint64_t a, uint64_t b) { a ^= b + 0x9e3779b97f4a7c15ull + (a << 6) + (a >> 2); return a; };
+  uint64_t t = ++h->proj_counter, bits;
+  t = mix(t, (uint64_t)(uintptr_t)phys); t = mix(t, (uint64_t)(uintptr_t)fe2d);
+  std::memcpy(&bits, &ud_angle_deg, 8); t = mix(t, bits);
+  std::memcpy(&bits, &va_angle_deg, 8); t = mix(t, bits);
+  t = mix(t, (uint64_t)h->proj_rec.begin); t = mix(t, (uint64_t)h->proj_rec.end);
+  h->proj_token = (t << 16) | (h->proj_counter & 0xffff) | 1ull << 63;
+  *token = h->proj_token;
+  return 0;
+}
+
+// ---- its adjoint for the points [begin, end) (a rank's share; the adjoints are sums over points) of one table shared by all
+// lineouts (the 2-D path is never batched in the reference); table: with the table adjoint
+struct FormFactor2dAdjPlan {
+  int feature = 0, nv = 0, B = 0;
+  long begin = 0, end = 0;
+  bool lds = false, table = false;  // the table fits LDS; with the table adjoint
+  int groups = 0, nworker = 0;      // point groups per workgroup; partial slots of the lineout-scalar adjoints: one per point
+  size_t smem = 0;                  // group and (lineout, gradient point); LDS of k_form_factor_2d_adj
+  dim3 grid, block;
+  // k_ff2d_table_adj: tiles of the table, workgroups per tile, LDS, doubles of a partial tile
+  int ntiles = 0; unsigned per_tile = 0; size_t tile_smem = 0, slab = 0;
+};
+
+static int form_factor_2d_adj_prepare(tsff_handle* h, int feature, int nv, int B, long begin, long end, bool table,
+                                      FormFactor2dAdjPlan& p, bool dry = false) {
+  p.feature = feature; p.nv = nv; p.B = B; p.begin = begin; p.end = end; p.table = table;
+  const int NLB = kNLB2 + 3 * h->n_ion;
+  const long npoint = end - begin;
   constexpr int kGL = TSFF_2D_GROUPS_LDS, kGG = TSFF_2D_GROUPS_L2;
-  const bool lds = sizeof(double) * (kGL * gsz(nv) + (size_t)(nv + 2) * pitch2d(nv, true)) <= kLdsLimit;
-  if (lds_out) *lds_out = lds;
-  const int kG2 = lds ? kGL : kGG;
-  return sizeof(double) * (kG2 * gsz(nv) + (lds ? (size_t)(nv + 2) * pitch2d(nv, true) : 0));
+  const size_t gsz = (2 + (size_t)(nv <= 64 ? 4 : (nv <= 128 ? 2 : 1))) * nv + 2 * (size_t)nv + 16 + 96;   // doubles per point group
+  const size_t tsz = (size_t)(nv + 2) * pitch2d(nv, true);                                                 // the table in LDS
+  p.lds = sizeof(double) * (kGL * gsz + tsz) <= kLdsLimit;
+  p.groups = p.lds ? kGL : kGG;
+  p.smem = sizeof(double) * (p.groups * gsz + (p.lds ? tsz : 0));
+  if (p.smem > kLdsLimit) return fail(h, -2, "nv = %d needs %zu B of LDS scratch", nv, p.smem);
+  const long want = (long)h->ncu2d() * (p.lds ? 1 : 8);
+  p.grid = dim3((unsigned)std::max<long>(1, std::min((npoint + p.groups - 1) / p.groups, want)));
+  p.block = dim3(p.groups * kThreads);
+  p.nworker = (int)p.grid.x * p.groups;
+  if (table) {
+    const int ncell = nv - 1, ntx = (ncell + kTile2 - 1) / kTile2, tmax = std::min(ncell, kTile2) + 3;
+    p.ntiles = ntx * ntx;
+    p.tile_smem = sizeof(double) * (size_t)tmax * (tmax | 1);
+    p.per_tile = (unsigned)std::max<long>(1, std::min<long>((npoint + 3) / 4, h->ncu2d() / p.ntiles));
+    p.slab = (size_t)tmax * tmax;
+  }
+  if (dry) return 0;
+  TSFF_ENSURE(h, h->lbacc, (size_t)B * h->S.G * NLB * sizeof(double));
+  if (table) TSFF_ENSURE(h, h->f1bar, (size_t)npoint * (nv + 2) * sizeof(double));
+  if (!p.lds) TSFF_ENSURE(h, h->fpad, pad2d_doubles(nv) * sizeof(double));
+  TSFF_ENSURE(h, h->lbparts, (size_t)B * h->S.G * p.nworker * NLB * sizeof(double));
+  if (table) {
+    TSFF_ENSURE(h, h->fbar_pad, (size_t)(nv + 2) * (nv + 2) * sizeof(double));
+    TSFF_ENSURE(h, h->fbar_parts, (size_t)p.per_tile * p.ntiles * p.slab * sizeof(double));
+  }
+  return 0;
+}
+
+// proj: the projection records of the saving forward of exactly these points and inputs (checked by the caller), or nullptr
+static int form_factor_2d_adj_enqueue(tsff_handle* h, const FormFactor2dAdjPlan& p, const double* phys, const double* fe2d,
+                                      double ud_angle_deg, double va_angle_deg, const double* proj, const double* Pbar, double* grad_phys,
+                                      double* grad_fe2d) {
+  const int nv = p.nv, B = p.B, NLB = kNLB2 + 3 * h->n_ion;
+  double* f1bar = p.table ? h->f1bar.as<double>() : nullptr;
+  const double* table = fe2d;
+  if (!p.lds) {
+    TSFF_LAUNCH0(h, k_pad2d, dim3(1), dim3(kThreads), 0, h->stream, fe2d, nv, h->fpad.as<double>());
+    table = h->fpad.as<double>() + pad2d_margin(nv);
+  }
+  const double ud = ud_angle_deg * kPi / 180.0, va = va_angle_deg * kPi / 180.0;
+  // a point group only writes the partial slots of the (b, g) it meets, the others stay zero
+  TSFF_HIP(h, hipMemsetAsync(h->lbparts.p, 0, (size_t)B * h->S.G * p.nworker * NLB * sizeof(double), h->stream));
+  int rc = with_ion<TSFF_MAX_ION>(h->n_ion, [&](auto N) {
+    return with_bool(p.lds, [&](auto LDS) {
+      constexpr int kG2 = LDS.value ? TSFF_2D_GROUPS_LDS : TSFF_2D_GROUPS_L2;
+      TSFF_LAUNCH_LDS(h, k_form_factor_2d_adj, (N.value, LDS.value, kG2), kLdsLimit, p.grid, p.block, p.smem, h->stream, h->S, phys,
+                      table, nv, ud, va, p.feature, p.begin, p.end, Pbar, h->lbparts.as<double>(), f1bar, proj);
+      TSFF_LAUNCH0(h, k_lbacc_reduce, dim3(B * h->S.G), dim3(kThreads), 0, h->stream, h->lbparts.as<double>(), p.nworker, NLB,
+                   h->lbacc.as<double>());
+      TSFF_LAUNCH(h, k_ff2d_lines_adj, (N.value), dim3((B + 63) / 64), dim3(64), 0, h->stream, h->S, phys, p.feature, B,
+                  h->lbacc.as<double>(), grad_phys, 0);
+      return 0;
+    });
+  });
+  if (rc) return rc;
+  TSFF_HIP(h, hipGetLastError());
+  if (!p.table) return 0;
+  TSFF_HIP(h, hipMemsetAsync(h->fbar_pad.p, 0, (size_t)(nv + 2) * (nv + 2) * sizeof(double), h->stream));
+  TSFF_LAUNCH0_LDS(h, k_ff2d_table_adj, kLdsLimit, dim3(p.per_tile, p.ntiles), dim3(4 * kThreads), p.tile_smem, h->stream, nv, f1bar,
+                   p.end - p.begin, h->fbar_parts.as<double>(), p.slab);
+  for (int t = 0; t < p.ntiles; ++t)   // one launch per tile, in order: the overlapping halos of neighbouring tiles add up without atomics
+    TSFF_LAUNCH0(h, k_ff2d_sum_tiles, dim3((unsigned)((p.slab + kThreads - 1) / kThreads)), dim3(kThreads), 0, h->stream, nv,
+                       h->fbar_parts.as<double>(), (int)p.per_tile, p.slab, h->fbar_pad.as<double>(), t);
+  TSFF_LAUNCH0(h, k_ff2d_fold_ghosts, dim3(1), dim3(kThreads), 0, h->stream, nv, h->fbar_pad.as<double>(), grad_fe2d);
+  TSFF_HIP(h, hipGetLastError());
+  return 0;
 }
 
 int tsff_form_factor_2d_grad(tsff_handle* h, int32_t feature, const double* phys, const double* fe2d, int32_t nv,
@@ -1424,89 +1565,19 @@ int tsff_form_factor_2d_grad(tsff_handle* h, int32_t feature, const double* phys
   const long per_lineout = (long)h->S.G * h->S.npts * h->S.n_angles, nall = per_lineout * B;
   const long pb = point_begin, pe = point_end < 0 ? nall : point_end;
   if (pb < 0 || pe > nall || pb > pe) return fail(h, -1, "point range [%ld, %ld) outside [0, %ld]", pb, pe, nall);
-  const double* proj = nullptr;
   if (use_saved) {
     if (saved_token != h->proj_token)
       return fail(h, -22, "saved_token: stale or foreign token (the projection records belong to the LAST tsff_form_factor_2d_save of this "
                           "handle; any later 2-D forward invalidates them)");
-    if (h->proj_begin != pb || h->proj_end != pe || h->proj_nv != nv || h->proj_feature != feature)
+    if (!h->proj_rec.covers(pb, pe, nv, feature))
       return fail(h, -2, "use_saved: no projection records of tsff_form_factor_2d_save for this point range / table size");
-    if (h->proj_phys != phys || h->proj_fe != fe2d || h->proj_ud != ud_angle_deg || h->proj_va != va_angle_deg || h->proj_B != B)
+    if (!h->proj_rec.made_from(phys, fe2d, ud_angle_deg, va_angle_deg, B))
       return fail(h, -2, "use_saved: the projection records were made from other inputs (phys / fe2d buffers, drift or flow angle, B)");
-    proj = h->proj.as<double>();
   }
-  return form_factor_2d_grad_impl(h, feature, phys, fe2d, nv, ud_angle_deg, va_angle_deg, B, pb, pe, proj, Pbar, grad_phys, grad_fe2d);
-}
-
-// proj: the projection records of the saving forward of exactly these points and inputs (checked by the caller), or nullptr
-static int form_factor_2d_grad_impl(tsff_handle* h, int32_t feature, const double* phys, const double* fe2d, int32_t nv,
-                                    double ud_angle_deg, double va_angle_deg, int32_t B, int64_t pb, int64_t pe,
-                                    const double* proj, const double* Pbar, double* grad_phys, double* grad_fe2d) {
-  const int NLB = kNLB2 + 3 * h->n_ion;
-  const long ntotal = pe - pb;   // points of this call (a rank's share; the adjoints are sums over points)
-  constexpr int kGL = TSFF_2D_GROUPS_LDS, kGG = TSFF_2D_GROUPS_L2;
-  bool lds = false;
-  const size_t smem = form_factor_2d_grad_smem(nv, &lds);
-  const int kG2 = lds ? kGL : kGG;
-  if (smem > kLdsLimit) return fail(h, -2, "nv = %d needs %zu B of LDS scratch", (int)nv, smem);
-  TSFF_ENSURE(h, h->lbacc, (size_t)B * h->S.G * NLB * sizeof(double));
-  double* f1bar = nullptr;
-  if (grad_fe2d) {
-    TSFF_ENSURE(h, h->f1bar, (size_t)ntotal * (nv + 2) * sizeof(double));
-    f1bar = h->f1bar.as<double>();
-  }
-  const double* table = fe2d;  // (one table shared by all lineouts: the 2-D path is never batched in the reference)
-  if (!lds) {
-    TSFF_ENSURE(h, h->fpad, pad2d_doubles((int)nv) * sizeof(double));
-    TSFF_LAUNCH0(h, k_pad2d, dim3(1), dim3(kThreads), 0, h->stream, fe2d, (int)nv, h->fpad.as<double>());
-    table = h->fpad.as<double>() + pad2d_margin((int)nv);
-  }
-  const long want = (long)h->ncu2d() * (lds ? 1 : 8);
-  dim3 grid((unsigned)std::max<long>(1, std::min((ntotal + kG2 - 1) / kG2, want))), block(kG2 * kThreads);
-  const double ud = ud_angle_deg * kPi / 180.0, va = va_angle_deg * kPi / 180.0;
-  // one partial slot per point group and (lineout, gradient point); a group only writes the slots of the (b, g) it meets,
-  // the others stay zero
-  const int nworker = (int)grid.x * kG2;
-  TSFF_ENSURE(h, h->lbparts, (size_t)B * h->S.G * nworker * NLB * sizeof(double));
-  TSFF_HIP(h, hipMemsetAsync(h->lbparts.p, 0, (size_t)B * h->S.G * nworker * NLB * sizeof(double), h->stream));
-  int rc = with_ion<TSFF_MAX_ION>(h->n_ion, [&](auto N) {
-    return with_bool(lds, [&](auto LDS) {
-      TSFF_LAUNCH_LDS(h, k_form_factor_2d_adj, (N.value, LDS.value, LDS.value ? kGL : kGG), kLdsLimit, grid, block, smem, h->stream, h->S,
-                      phys, table, (int)nv, ud, va, (int)feature, pb, pe, Pbar, h->lbparts.as<double>(), f1bar, proj);
-      TSFF_LAUNCH0(h, k_lbacc_reduce, dim3(B * h->S.G), dim3(kThreads), 0, h->stream, h->lbparts.as<double>(), nworker, NLB,
-                   h->lbacc.as<double>());
-      TSFF_LAUNCH(h, k_ff2d_lines_adj, (N.value), dim3((B + 63) / 64), dim3(64), 0, h->stream, h->S, phys, (int)feature, (int)B,
-                  h->lbacc.as<double>(), grad_phys, 0);
-      return 0;
-    });
-  });
-  if (rc) return rc;
-  TSFF_HIP(h, hipGetLastError());
-  if (grad_fe2d) {
-    rc = table_adjoint_2d(h, nv, ntotal, grad_fe2d);
-    if (rc) return rc;
-  }
-  return 0;
-}
-
-static int table_adjoint_2d(tsff_handle* h, int nv, long npoint, double* grad_fe2d) {
-  const size_t padn = (size_t)(nv + 2) * (nv + 2);
-  TSFF_ENSURE(h, h->fbar_pad, padn * sizeof(double));
-  TSFF_HIP(h, hipMemsetAsync(h->fbar_pad.p, 0, padn * sizeof(double), h->stream));
-  const int ncell = nv - 1, ntx = (ncell + kTile2 - 1) / kTile2, ntiles = ntx * ntx;
-  const int tmax = std::min(ncell, kTile2) + 3;
-  const size_t smem = sizeof(double) * (size_t)tmax * (tmax | 1);
-  const unsigned per_tile = (unsigned)std::max<long>(1, std::min<long>((npoint + 3) / 4, h->ncu2d() / ntiles));
-  const size_t slab = (size_t)tmax * tmax;
-  TSFF_ENSURE(h, h->fbar_parts, (size_t)per_tile * ntiles * slab * sizeof(double));
-  TSFF_LAUNCH0_LDS(h, k_ff2d_table_adj, kLdsLimit, dim3(per_tile, ntiles), dim3(4 * kThreads), smem, h->stream, nv, h->f1bar.as<double>(),
-                   npoint, h->fbar_parts.as<double>(), slab);
-  for (int t = 0; t < ntiles; ++t)   // one launch per tile, in order: the overlapping halos of neighbouring tiles add up without atomics
-    TSFF_LAUNCH0(h, k_ff2d_sum_tiles, dim3((unsigned)((slab + kThreads - 1) / kThreads)), dim3(kThreads), 0, h->stream, nv,
-                       h->fbar_parts.as<double>(), (int)per_tile, slab, h->fbar_pad.as<double>(), t);
-  TSFF_LAUNCH0(h, k_ff2d_fold_ghosts, dim3(1), dim3(kThreads), 0, h->stream, nv, h->fbar_pad.as<double>(), grad_fe2d);
-  TSFF_HIP(h, hipGetLastError());
-  return 0;
+  FormFactor2dAdjPlan p;
+  if (int rc = form_factor_2d_adj_prepare(h, feature, nv, B, pb, pe, grad_fe2d != nullptr, p)) return rc;
+  return form_factor_2d_adj_enqueue(h, p, phys, fe2d, ud_angle_deg, va_angle_deg, use_saved ? h->proj.as<double>() : nullptr, Pbar,
+                                    grad_phys, grad_fe2d);
 }
 
 int tsff_ats_setup(tsff_handle* h, const tsff_ats_config* c) {
@@ -1530,22 +1601,41 @@ int tsff_ats_setup(tsff_handle* h, const tsff_ats_config* c) {
   return 0;
 }
 
-// phys (device, optional): lam, amp1 and amp2 read from these physical parameters on the device instead of the scalars
-static int ats_spectrum_impl(tsff_handle* h, const double* P, const double* e_amps, double lam, double amp1, double amp2,
-                             const double* phys, double* ThryE) {
-  if (!h || !P || !ThryE || !e_amps) return fail(h, -1, "bad argument");
+// ---- the ATS instrument chain and its reverse.  adjoint: the reverse chain's refusal and buffers too
+static int ats_prepare(tsff_handle* h, bool adjoint, bool dry = false) {
   if (h->ats_npx == 0) return fail(h, -2, "tsff_ats_setup has not been called");
+  if (!adjoint) return 0;
+  const int npts = h->S.npts, npx = h->ats_npx, rows = h->ats_row_end - h->ats_row_start;
+  if (npts / h->ats_lam_step > TSFF_NBINS) return fail(h, -2, "more than %d wavelength resolution units per row", TSFF_NBINS);
+  if (dry) return 0;
+  const size_t img = (size_t)npx * npts * sizeof(double);
+  TSFF_ENSURE(h, h->ats_C, img);
+  TSFF_ENSURE(h, h->ats_D, img);
+  TSFF_ENSURE(h, h->ats_stats, (size_t)npx * 4 * sizeof(double) + (size_t)rows * 2 * sizeof(double));
+  return 0;
+}
+
+// the forward chain up to the unscaled convolved image: M = weights x P, A = M * taps_ang, B = A * taps_lam
+static void ats_forward_chain(tsff_handle* h, const double* P) {
   const int npts = h->S.npts, npx = h->ats_npx;
   dim3 block(kThreads), grid((npts + kThreads - 1) / kThreads, npx);
   double* M = h->ats_M.as<double>();
   double* A = h->ats_A.as<double>();
-  double* Bm = h->ats_B.as<double>();
   TSFF_LAUNCH0(h, k_ats_weights, grid, block, 0, h->stream, P, h->ats_w.as<double>(), h->S.filt, h->S.G, npts,
                      h->S.n_angles, npx, M);
   TSFF_LAUNCH0(h, k_ats_conv, grid, block, 0, h->stream, M, h->ats_ta.as<double>(), h->ats_nta, h->ats_offa, 1, npx, npts, A);
-  TSFF_LAUNCH0(h, k_ats_conv, grid, block, 0, h->stream, A, h->ats_tl.as<double>(), h->ats_ntl, h->ats_offl, 0, npx, npts, Bm);
-  TSFF_LAUNCH0(h, k_ats_rownorm, dim3(npx), block, 0, h->stream, M, Bm, npts);
-  TSFF_LAUNCH0(h, k_ats_resunit, dim3(h->ats_row_end - h->ats_row_start), block, 0, h->stream, Bm, h->ats_lam.as<double>(),
+  TSFF_LAUNCH0(h, k_ats_conv, grid, block, 0, h->stream, A, h->ats_tl.as<double>(), h->ats_ntl, h->ats_offl, 0, npx, npts,
+                     h->ats_B.as<double>());
+}
+
+// phys (device, optional): lam, amp1 and amp2 read from these physical parameters on the device instead of the scalars
+static int ats_spectrum_enqueue(tsff_handle* h, const double* P, const double* e_amps, double lam, double amp1, double amp2,
+                                const double* phys, double* ThryE) {
+  const int npts = h->S.npts;
+  double* Bm = h->ats_B.as<double>();
+  ats_forward_chain(h, P);
+  TSFF_LAUNCH0(h, k_ats_rownorm, dim3(h->ats_npx), dim3(kThreads), 0, h->stream, h->ats_M.as<double>(), Bm, npts);
+  TSFF_LAUNCH0(h, k_ats_resunit, dim3(h->ats_row_end - h->ats_row_start), dim3(kThreads), 0, h->stream, Bm, h->ats_lam.as<double>(),
                      npts, h->ats_lam_step, h->ats_ang_step, h->ats_row_start, e_amps, lam, amp1, amp2, phys, ThryE);
   TSFF_HIP(h, hipGetLastError());
   return 0;
@@ -1553,20 +1643,17 @@ static int ats_spectrum_impl(tsff_handle* h, const double* P, const double* e_am
 
 int tsff_ats_spectrum(tsff_handle* h, const double* P, const double* e_amps, double lam, double amp1, double amp2, double* ThryE) {
   DevGuard dg__(h);
-  return ats_spectrum_impl(h, P, e_amps, lam, amp1, amp2, nullptr, ThryE);
+  if (!h || !P || !ThryE || !e_amps) return fail(h, -1, "bad argument");
+  if (int rc = ats_prepare(h, false)) return rc;
+  return ats_spectrum_enqueue(h, P, e_amps, lam, amp1, amp2, nullptr, ThryE);
 }
 
-// the reverse chain; the amplitude adjoints stay on the device, per output row: *ampb_out = [rows][2] (handle scratch)
-static int ats_adjoint_impl(tsff_handle* h, const double* P, const double* e_amps, double lam, double amp1, double amp2,
-                            const double* phys, const double* Ebar, double* Pbar, double** ampb_out) {
-  if (!h || !P || !e_amps || !Ebar || !Pbar) return fail(h, -1, "bad argument");
-  if (h->ats_npx == 0) return fail(h, -2, "tsff_ats_setup has not been called");
+// the amplitude adjoints of the reverse chain stay on the device, per output row: [rows][2] behind the row statistics
+static double* ats_amp_bar(tsff_handle* h) { return h->ats_stats.as<double>() + (size_t)h->ats_npx * 4; }
+
+static int ats_adjoint_enqueue(tsff_handle* h, const double* P, const double* e_amps, double lam, double amp1, double amp2,
+                               const double* phys, const double* Ebar, double* Pbar) {
   const int npts = h->S.npts, npx = h->ats_npx, rows = h->ats_row_end - h->ats_row_start;
-  if (npts / h->ats_lam_step > TSFF_NBINS) return fail(h, -2, "more than %d wavelength resolution units per row", TSFF_NBINS);
-  const size_t img = (size_t)npx * npts * sizeof(double);
-  TSFF_ENSURE(h, h->ats_C, img);
-  TSFF_ENSURE(h, h->ats_D, img);
-  TSFF_ENSURE(h, h->ats_stats, (size_t)npx * 4 * sizeof(double) + (size_t)rows * 2 * sizeof(double));
   dim3 block(kThreads), grid((npts + kThreads - 1) / kThreads, npx);
   double* M = h->ats_M.as<double>();
   double* A = h->ats_A.as<double>();
@@ -1574,17 +1661,12 @@ static int ats_adjoint_impl(tsff_handle* h, const double* P, const double* e_amp
   double* Cb = h->ats_C.as<double>();
   double* Db = h->ats_D.as<double>();
   double* stats = h->ats_stats.as<double>();
-  double* ampb = stats + (size_t)npx * 4;
-  // forward up to the unscaled convolved image
-  TSFF_LAUNCH0(h, k_ats_weights, grid, block, 0, h->stream, P, h->ats_w.as<double>(), h->S.filt, h->S.G, npts,
-                     h->S.n_angles, npx, M);
-  TSFF_LAUNCH0(h, k_ats_conv, grid, block, 0, h->stream, M, h->ats_ta.as<double>(), h->ats_nta, h->ats_offa, 1, npx, npts, A);
-  TSFF_LAUNCH0(h, k_ats_conv, grid, block, 0, h->stream, A, h->ats_tl.as<double>(), h->ats_ntl, h->ats_offl, 0, npx, npts, Bm);
+  ats_forward_chain(h, P);
   TSFF_LAUNCH0(h, k_ats_rowstats, dim3(npx), block, 0, h->stream, M, Bm, npts, stats);
   // reverse
-  TSFF_HIP(h, hipMemsetAsync(Cb, 0, img, h->stream));
+  TSFF_HIP(h, hipMemsetAsync(Cb, 0, (size_t)npx * npts * sizeof(double), h->stream));
   TSFF_LAUNCH0(h, k_ats_resunit_adj, dim3(rows), block, 0, h->stream, Bm, stats, h->ats_lam.as<double>(), npts, h->ats_lam_step,
-                     h->ats_ang_step, h->ats_row_start, e_amps, lam, amp1, amp2, phys, Ebar, Cb, ampb);
+                     h->ats_ang_step, h->ats_row_start, e_amps, lam, amp1, amp2, phys, Ebar, Cb, ats_amp_bar(h));
   TSFF_LAUNCH0(h, k_ats_rownorm_adj, dim3(npx), block, 0, h->stream, Bm, stats, npts, Cb, Db);              // Cb -> Bmbar, Db = Mbar one-hots
   TSFF_LAUNCH0(h, k_ats_conv_adj, grid, block, 0, h->stream, Cb, h->ats_tl.as<double>(), h->ats_ntl, h->ats_offl, 0, npx, npts, 0, A);   // A = Abar
   TSFF_LAUNCH0(h, k_ats_conv_adj, grid, block, 0, h->stream, A, h->ats_ta.as<double>(), h->ats_nta, h->ats_offa, 1, npx, npts, 1, Db);  // Db += conv^T
@@ -1592,21 +1674,20 @@ static int ats_adjoint_impl(tsff_handle* h, const double* P, const double* e_amp
   TSFF_LAUNCH0(h, k_ats_weights_adj, wgrid, block, 0, h->stream, Db, h->ats_w.as<double>(), h->S.filt, h->S.G, npts, h->S.n_angles,
                      npx, Pbar);
   TSFF_HIP(h, hipGetLastError());
-  *ampb_out = ampb;
   return 0;
 }
 
 int tsff_ats_adjoint(tsff_handle* h, const double* P, const double* e_amps, double lam, double amp1, double amp2,
                      const double* Ebar, double* Pbar, double* amp_bar) {
   DevGuard dg__(h);
-  if (!amp_bar) return fail(h, -1, "bad argument");
-  double* ampb = nullptr;
-  int rc = ats_adjoint_impl(h, P, e_amps, lam, amp1, amp2, nullptr, Ebar, Pbar, &ampb);
+  if (!amp_bar || !h || !P || !e_amps || !Ebar || !Pbar) return fail(h, -1, "bad argument");
+  int rc = ats_prepare(h, true);
+  if (!rc) rc = ats_adjoint_enqueue(h, P, e_amps, lam, amp1, amp2, nullptr, Ebar, Pbar);
   if (rc) return rc;
   const int rows = h->ats_row_end - h->ats_row_start;
   // amp adjoints: sum over the rows (host: a few hundred numbers)
   std::vector<double> hb((size_t)rows * 2);
-  TSFF_HIP(h, hipMemcpyAsync(hb.data(), ampb, hb.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  TSFF_HIP(h, hipMemcpyAsync(hb.data(), ats_amp_bar(h), hb.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   TSFF_HIP(h, hipStreamSynchronize(h->stream));
   amp_bar[0] = amp_bar[1] = 0.0;
   for (int r = 0; r < rows; ++r) { amp_bar[0] += hb[2 * r]; amp_bar[1] += hb[2 * r + 1]; }
@@ -1690,11 +1771,7 @@ static int loss_grad_prepare(tsff_handle* h, LossGradCall& c) {
   rc = c.want_fe ? size_plan<1, 2>(h, B, c.plan) : c.with_m ? size_plan<1, 1>(h, B, c.plan) : size_plan<1, 0>(h, B, c.plan);
   if (rc) return rc;
   if ((rc = ensure_workspace(h, B))) return rc;
-  if (c.want_fe) {
-    TSFF_ENSURE(h, h->Wb, (size_t)2 * B * kNXi2 * sizeof(double));    // (x 2: per-feature parts of the interleaved plan)
-    TSFF_ENSURE(h, h->Hys, (size_t)2 * B * 2 * h->S.nvx * sizeof(double));
-    TSFF_ENSURE(h, h->Yt, (size_t)B * 2 * kNXi1 * sizeof(double));
-  }
+  if (c.want_fe && (rc = fe_tail_prepare(h, 2, B))) return rc;    // (x 2: per-feature parts of the interleaved plan)
   if (po) TSFF_ENSURE(h, h->gradws, (size_t)B * h->S.NP * sizeof(double));
   return 0;
 }
@@ -1715,27 +1792,18 @@ static int loss_grad_enqueue(tsff_handle* h, const LossGradCall& c) {
   K.denom_mode = h->denom_mode;
   const bool parts = c.plan.gpart != 0, lbrec = c.plan.form == SpectrumForm::one_sweep;
   if (c.want_fe) {
-    const int nvx = h->S.nvx;
-    K.Wb_out = h->Wb.as<double>();
-    K.Hy_out = h->Hys.as<double>();
-    K.Hs_out = K.Hy_out + (size_t)B * nvx;
-    K.htm = nullptr; K.Wm = nullptr;  // the LDS region of the tangent tables holds the table adjoints
+    fe_tail_outputs(h, K, B);
     rc = launch_spectrum<1, 2>(h, K, c.plan, h->gmask.as<uint8_t>(), grad);
     if (rc) return rc;
     if (parts) {
-      const long nw = (long)B * kNXi2, nh = (long)2 * B * nvx;
+      const long nw = (long)B * kNXi2, nh = (long)2 * B * h->S.nvx;
       TSFF_LAUNCH0(h, k_add_parts, dim3((unsigned)std::min<long>((nw + kThreads - 1) / kThreads, 1024)), dim3(kThreads), 0, h->stream,
                          K.Wb_out, K.Wb_out + nw, nw);
       TSFF_LAUNCH0(h, k_add_parts, dim3((unsigned)std::min<long>((nh + kThreads - 1) / kThreads, 1024)), dim3(kThreads), 0, h->stream,
                          K.Hy_out, K.Hy_out + nh, nh);
       TSFF_HIP(h, hipGetLastError());
     }
-    dim3 ggrid(kNXi1 / kGN, (2 * B + kGM - 1) / kGM);
-    TSFF_LAUNCH0(h, k_wgemm_t, ggrid, dim3(kThreads), 0, h->stream, h->S.lg, K.Wb_out, h->S.xi2, (int)B, h->Yt.as<double>());
-    TSFF_HIP(h, hipGetLastError());
-    TSFF_LAUNCH0(h, k_fe_adjoint, dim3(B), dim3(kThreads), h->smem_adjoint, h->stream, h->S, K.ht, h->Yt.as<double>(),
-                       K.Wb_out, K.Hy_out, K.Hs_out, c.grad_fe);
-    TSFF_HIP(h, hipGetLastError());
+    if ((rc = fe_tail_enqueue(h, K, B, c.grad_fe))) return rc;
   } else {
     rc = with_m ? launch_spectrum<1, 1>(h, K, c.plan, h->gmask.as<uint8_t>(), grad)
                 : launch_spectrum<1>(h, K, c.plan, h->gmask.as<uint8_t>(), grad);
@@ -1857,8 +1925,8 @@ int tsff_adam_fit(tsff_handle* h, double* params, const double* fe, const double
 
 // the angular (ARTS) fit on the device (k_angular.inc): n_epochs x (leaves -> physical parameters and f_e, form factor, ATS
 // chain, loss and seed, ATS adjoint, form-factor adjoint, chain rule, optimiser + early stop), all enqueued on the handle's
-// stream.  Every refusal is checked before the first launch; the handle's scratch is sized by the first epoch, so the later
-// ones allocate nothing, and nothing synchronises.
+// stream.  The stages are prepared once, for one lineout and all its points -- every refusal before anything is allocated,
+// every buffer before the first launch; the epochs only enqueue, and nothing synchronises.
 int tsff_angular_fit(tsff_handle* h, const tsff_angular_spec* sp, double* leaves, const double* gen_data, const double* e_data,
                      const double* noise_e, const double* wcol, const double* e_amps, double* moments, double* best, int32_t* ctl,
                      double* loss_hist, double* best_hist) {
@@ -1887,18 +1955,24 @@ int tsff_angular_fit(tsff_handle* h, const tsff_angular_spec* sp, double* leaves
   const int rows = h->ats_row_end - h->ats_row_start, nJ = npts / h->ats_lam_step;
   if (nJ > TSFF_NBINS) return fail(h, -2, "more than %d wavelength resolution units per row", TSFF_NBINS);
   const bool want_dm = gm[TSFF_P_M] != 0, train_table = n_table > 0;
-  // the LDS budgets of the form-factor kernels (their entry points would refuse in the first epoch)
-  if (two_d) {
-    constexpr int kGL = TSFF_2D_GROUPS_LDS, kGG = TSFF_2D_GROUPS_L2;
-    const bool lds = sizeof(double) * smem2d_doubles(nv, true, kGL) <= kLdsLimit;
-    if (sizeof(double) * smem2d_doubles(nv, lds, lds ? kGL : kGG) > kLdsLimit || form_factor_2d_grad_smem(nv, nullptr) > kLdsLimit)
-      return fail(h, -2, "nv = %d needs more LDS than a CU has", nv);
-  } else if (form_factor_grad_smem(h, want_dm) > kLdsLimit) {
-    return fail(h, TSFF_ERR_LDS, "LDS budget exceeded (%zu B)", form_factor_grad_smem(h, want_dm));
-  }
-  if (sp->n_epochs == 0) return 0;
-  // scratch: phys | fe | dfe (2 nv) | aux | P | ThryE | Ebar | Pbar | gphys | gfe | grad | loss
   const size_t nP = (size_t)G * npts * NA, nimg = (size_t)rows * nJ;
+  // the stages of an epoch: the form factor (2-D: saving), the ATS chain and its reverse, the form-factor adjoint (with the table
+  // adjoint when the table is trained, the f_e adjoint when m is a leaf)
+  FormFactorPlan ff;
+  FormFactorAdjPlan ffa;
+  FormFactor2dPlan ff2;
+  FormFactor2dAdjPlan ff2a;
+  auto prepare_stages = [&](bool dry) {
+    int rc = two_d ? form_factor_2d_prepare(h, 0, nv, true, 1, 0, -1, true, ff2, dry) : form_factor_prepare(h, 0, 1, ff, dry);
+    if (!rc) rc = ats_prepare(h, false, dry);
+    if (!rc) rc = ats_prepare(h, true, dry);
+    if (!rc) rc = two_d ? form_factor_2d_adj_prepare(h, 0, nv, 1, 0, (long)nP, train_table, ff2a, dry)
+                        : form_factor_adj_prepare(h, 0, 1, want_dm, ffa, dry);
+    return rc;
+  };
+  int rc = prepare_stages(true);
+  if (rc || sp->n_epochs == 0) return rc;
+  // scratch: phys | fe | dfe (2 nv) | aux | P | ThryE | Ebar | Pbar | gphys | gfe | grad | loss
   const size_t nfe = two_d ? (size_t)nv * nv : (size_t)nv;
   size_t off = 0;
   auto take = [&](size_t k) { const size_t o = off; off += (k + 1) & ~(size_t)1; return o; };
@@ -1906,8 +1980,8 @@ int tsff_angular_fit(tsff_handle* h, const tsff_angular_spec* sp, double* leaves
                o_E = take(nimg), o_Eb = take(nimg), o_Pb = take(nP), o_gp = take(NP), o_gfe = take(nfe), o_grad = take(n),
                o_loss = take(1), o_part = take(kAngLossBlocks);
   TSFF_ENSURE(h, h->ang_ws, off * sizeof(double));
-  int rc = 0;
   if (sp->n_active > 0 && (rc = upload_slots(h, sp->active_slots, sp->n_active))) return rc;
+  if ((rc = prepare_stages(false))) return rc;
   double* ws = h->ang_ws.as<double>();
   double *phys = ws + o_phys, *fe = ws + o_fe, *dfe = ws + o_dfe, *aux = ws + o_aux, *P = ws + o_P, *E = ws + o_E, *Eb = ws + o_Eb,
          *Pb = ws + o_Pb, *gphys = ws + o_gp, *gfe = ws + o_gfe, *grad = ws + o_grad, *lossv = ws + o_loss,
@@ -1918,7 +1992,7 @@ int tsff_angular_fit(tsff_handle* h, const tsff_angular_spec* sp, double* leaves
   const bool adam = sp->method == TSFF_ANG_ADAM;
   const double b1 = sp->b1, b2 = adam ? sp->b2 : sp->decay, omb1 = 1.0 - b1, omb2 = 1.0 - b2, neg_lr = -sp->lr;
   const int* act = sp->n_active > 0 ? h->act.as<int>() : nullptr;
-  const long nall = (long)nP;
+  const double* ampb = ats_amp_bar(h);
   const unsigned nloss = (unsigned)std::min<long>(kAngLossBlocks, ((long)nimg + kThreads - 1) / kThreads);   // (a fixed partition)
   for (int t = 0; t < sp->n_epochs; ++t) {
     const int epoch = sp->epoch0 + t;
@@ -1929,23 +2003,20 @@ int tsff_angular_fit(tsff_handle* h, const tsff_angular_spec* sp, double* leaves
     });
     if (rc) return rc;
     TSFF_HIP(h, hipGetLastError());
-    rc = two_d ? form_factor_2d_impl(h, 0, phys, table, nv, 1, sp->ud_angle, sp->va_angle, 1, 0, -1, P, true)
-               : form_factor_impl(h, 0, phys, fe, 1, P);
+    rc = two_d ? form_factor_2d_enqueue(h, ff2, phys, table, sp->ud_angle, sp->va_angle, P) : form_factor_enqueue(h, ff, phys, fe, P);
     if (rc) return rc;
-    if ((rc = ats_spectrum_impl(h, P, e_amps, 0.0, 0.0, 0.0, phys, E))) return rc;
+    if ((rc = ats_spectrum_enqueue(h, P, e_amps, 0.0, 0.0, 0.0, phys, E))) return rc;
     TSFF_LAUNCH0(h, k_ang_loss, dim3(nloss), dim3(kThreads), 0, h->stream, (const double*)E, noise_e, e_data, wcol, rows, nJ,
                  (int)sp->loss_method, sp->un, Eb, lpart);
     TSFF_LAUNCH0(h, k_ang_loss_sum, dim3(1), dim3(kThreads), 0, h->stream, (const double*)lpart, (int)nloss, lossv);
     TSFF_HIP(h, hipGetLastError());
-    double* ampb = nullptr;
-    if ((rc = ats_adjoint_impl(h, P, e_amps, 0.0, 0.0, 0.0, phys, Eb, Pb, &ampb))) return rc;
-    rc = two_d ? form_factor_2d_grad_impl(h, 0, phys, table, nv, sp->ud_angle, sp->va_angle, 1, 0, nall, h->proj.as<double>(), Pb,
-                                          gphys, train_table ? gfe : nullptr)
-               : form_factor_grad_impl(h, 0, phys, fe, 1, Pb, gphys, want_dm ? gfe : nullptr);
+    if ((rc = ats_adjoint_enqueue(h, P, e_amps, 0.0, 0.0, 0.0, phys, Eb, Pb))) return rc;
+    rc = two_d ? form_factor_2d_adj_enqueue(h, ff2a, phys, table, sp->ud_angle, sp->va_angle, h->proj.as<double>(), Pb, gphys, gfe)
+               : form_factor_adj_enqueue(h, ffa, phys, fe, Pb, gphys, gfe);
     if (rc) return rc;
     rc = with_ion<TSFF_MAX_ION>(h->n_ion, [&](auto N) {
       TSFF_LAUNCH(h, k_ang_chain, (N.value), dim3(1), dim3(kThreads), 0, h->stream, h->S, (const double*)leaves, (const double*)gphys,
-                  (const double*)ampb, rows, (const double*)gfe, want_dm ? (const double*)dfe : nullptr, nv, (int)train_table,
+                  ampb, rows, (const double*)gfe, want_dm ? (const double*)dfe : nullptr, nv, (int)train_table,
                   (int)sp->learn_log, nv, (const double*)aux, cvjp, ln10, act, (int)sp->n_active, grad);
       return 0;
     });
