@@ -54,7 +54,7 @@
 extern "C" {
 #endif
 
-#define TSFF_ABI_VERSION 13
+#define TSFF_ABI_VERSION 14
 /* error codes (every entry point returns 0 or one of these; text via tsff_last_error):
  * -1 bad argument, -2 unsupported configuration / option, -3 not a differentiable leaf, -5 HIP runtime error,
  * -22 stale or foreign token of saved projection records (tsff_form_factor_2d_grad),
@@ -400,7 +400,7 @@ int tsff_lbfgs_fit(tsff_handle *h, double *params, const double *fe, const doubl
  *   spec (HOST): the deck and the optimiser, below;
  *   leaves (device [NP + nv^2 for TSFF_ANG_ARB2V], in/out): the normalised leaves of the one plasma condition, then fval;
  *   gen_data (device): TSFF_ANG_DLM [nv][31] DLM table | [31] m axis (tsadar_amd.distribution.dlm_table, M_AXIS);
- *   TSFF_ANG_TABLE2D the constant table [nv][nv]; TSFF_ANG_ARB2V unused;
+ *   TSFF_ANG_TABLE2D the constant table [nv][nv]; TSFF_ANG_ARB2V unused; TSFF_ANG_SPH: the generator's constants, below;
  *   e_data, noise_e (device [rows][nJ]), wcol (device [nJ]: blue / red masks over rows x mask count, halved when both are
  *   fitted), e_amps (device [rows]);
  *   moments (device [2 n] Adam (mu | nu), [n] RMSProp, n = n_active + nv^2 for ARB2V, else n_active; in/out): the active
@@ -410,10 +410,23 @@ int tsff_lbfgs_fit(tsff_handle *h, double *params, const double *fe, const doubl
  *   epoch the fit ended after, [2] g_wait, [3] b_wait (the reference's counters), [4] 1 once a best exists;
  *   loss_hist (device [n_epochs] or NULL): each epoch's loss (NaN after the end);
  *   best_hist (device [n_epochs][NP] or NULL): the best scalar leaves after each epoch (save_state), untouched while none exists.
+ * TSFF_ANG_SPH (a trained SphericalHarmonics generator, k_sph.inc) widens the layouts by its n_gen parameters, in the order of
+ * SphericalHarmonics.get_params() (per harmonic (l, m), sorted: log_10_LT for TSFF_SPH_MORA_YAHI, flm_sign[nvr] then flm_mag[nvr]
+ * for TSFF_SPH_ARBITRARY; then normed_m): leaves [NP | n_gen], moments over n_active + n_gen, best [1 + NP + n_gen], best_hist rows
+ * of NP + n_gen.  Its gen_data holds everything that does not depend on the trained parameters (doubles, integers stored as
+ * doubles; n2 = nv^2, H = n_harm; tsadar_amd.distribution.sph_gen_data packs it):
+ *   vr[nvr] | cell[n2] | wt[n2] | inside[n2] | Y[H][n2]       the radial axis; per grid point the radial cell, the weight in it and
+ *                                                             1 inside the axis (np.interp), Re Y_l^m per harmonic and point;
+ *   | M[nvr][nvr] | ptr[nvr + 1] | pt[2 n2] | cw[2 n2]        TSFF_SPH_ARBITRARY only: the smoothing matrix and, for the transposed
+ *                                                             interpolation, per radial node k the grid points pt[e] and weights
+ *                                                             cw[e] that reach it, e in [ptr[k], ptr[k + 1]) (unused tail: zeros).
  * Chunks: epoch0 = the epochs done so far (Adam's bias correction); a fit in chunks is bit for bit one call.
  * Refusals: a null pointer, a slot out of range or repeated -1, TSFF_P_M outside DLM decks -2, an ion's A slot -3, an unknown
- * generator, optimiser or loss method, nv outside 4 .. 256 for 2-D tables, too little LDS -2 (TSFF_ERR_LDS for the 1-D adjoint). */
-enum { TSFF_ANG_TABLE2D = 0, TSFF_ANG_DLM = 1, TSFF_ANG_ARB2V = 2 };
+ * generator, optimiser or loss method, nv outside 4 .. 256 for 2-D tables, too little LDS -2 (TSFF_ERR_LDS for the 1-D adjoint);
+ * TSFF_ANG_SPH: an unknown radial type, n_harm != 2 for Mora-Yahi (l = 1 only) or outside 1 .. 64, nvr < 2, or n_gen other than
+ * n_harm + 1 (Mora-Yahi) / 2 n_harm nvr + 1 (free radial functions) -2. */
+enum { TSFF_ANG_TABLE2D = 0, TSFF_ANG_DLM = 1, TSFF_ANG_ARB2V = 2, TSFF_ANG_SPH = 3 };
+enum { TSFF_SPH_MORA_YAHI = 0, TSFF_SPH_ARBITRARY = 1 }; /* flm_type of a SphericalHarmonics generator */
 enum { TSFF_ANG_ADAM = 0, TSFF_ANG_RMSPROP = 1 };
 typedef struct {
   int32_t generator;            /* TSFF_ANG_* */
@@ -429,10 +442,23 @@ typedef struct {
   double lr, b1, b2, eps;       /* Adam: optax's (b1, b2, eps); RMSProp: eps */
   double decay;                 /* RMSProp */
   int32_t n_epochs, epoch0;
+  int32_t sph_type;             /* TSFF_ANG_SPH: TSFF_SPH_* */
+  int32_t n_harm, nvr, n_gen;   /* TSFF_ANG_SPH: harmonics (l, m), radial nodes, trained generator parameters */
 } tsff_angular_spec;
 int tsff_angular_fit(tsff_handle *h, const tsff_angular_spec *spec, double *leaves, const double *gen_data, const double *e_data,
                      const double *noise_e, const double *wcol, const double *e_amps, double *moments, double *best, int32_t *ctl,
                      double *loss_hist, double *best_hist);
+
+/* The SphericalHarmonics generator on its own (k_sph.inc; the kernels of TSFF_ANG_SPH), asynchronous on the handle's stream:
+ *   tsff_sph_table:     theta (device [n_gen], get_params() order) -> fe (device [nv][nv]) = SphericalHarmonics.__call__();
+ *   tsff_sph_table_vjp: theta, fe_bar (device [nv][nv]) = d loss / d fe -> grad (device [n_gen]) = d loss / d theta, exact (no
+ *   finite differences) and bit-reproducible from run to run (every sum in a fixed order, no atomics).
+ * sph_type, n_harm, nvr, n_gen and gen_data as for TSFF_ANG_SPH; dvx = vx[1] - vx[0]; nv = 2 .. 4096.  The scratch is the handle's
+ * and is sized on the first call at a given size: later calls allocate nothing.  Refusals as for TSFF_ANG_SPH; a null pointer -1. */
+int tsff_sph_table(tsff_handle *h, int32_t sph_type, int32_t n_harm, int32_t nv, int32_t nvr, int32_t n_gen, double dvx,
+                   const double *theta, const double *gen_data, double *fe);
+int tsff_sph_table_vjp(tsff_handle *h, int32_t sph_type, int32_t n_harm, int32_t nv, int32_t nvr, int32_t n_gen, double dvx,
+                       const double *theta, const double *gen_data, const double *fe_bar, double *grad);
 
 /* Exact per-lineout Hessian of the fit loss: LossFunction._loss_for_hess_fn_ / h_loss_wrt_params
  * (inverse/loss_function.py:170-188, equinox.filter_hessian) for every lineout b, with respect to the normalised leaves

@@ -1,15 +1,17 @@
 """Per-epoch wall time of the angular (ARTS) fit at the reference's full size (1024 x 1024 CCD, 860 lineout rows, 241 angles;
 the shapes of scripts/time_angular.py): the host loop over LossFunction.vg_loss with tree.Adam against loops.angular_loop
-(tsff_angular_fit), for a 1-D DLM deck (nvx 256), a 2-D Arbitrary2V deck (nvx 128, table trained) and a 2-D constant-table
-SphericalHarmonics deck (nvx 128).
+(tsff_angular_fit), for a 1-D DLM deck (nvx 256), a 2-D Arbitrary2V deck (nvx 128, table trained), a 2-D constant-table
+SphericalHarmonics deck (nvx 128) and the reference's arts2v deck: a TRAINED Mora-Yahi SphericalHarmonics generator (nvx 128,
+nvr 64, rmsprop; angular_loop(train_generator=True) against the host loop, whose generator gradient is by central differences).
 
 Both figures count epochs only.  The host loop is timed after a warm-up evaluation.  Every angular_loop call builds its own
 LossFunction, engine and scratch, so its per-epoch time is the difference of two calls of N1 and N2 epochs over N2 - N1.
 
-  --deck NAME        one deck only (dlm1d, arb2d, sph2d)
+  --deck NAME        one deck only (dlm1d, arb2d, sph2d, sphtrain)
   --device-only      angular_loop alone (run it under rocprofv3 --kernel-trace --output-format csv)
   --kernel-sum CSV   per-epoch kernel sum of such a trace: the durations of every kernel from one epoch's k_ang_leaves up to
-                     the next one's, median over the epochs of the trace
+                     the next one's, median over the epochs of the trace; generator_ms_per_epoch: the share of k_sph_table and
+                     k_sph_vjp in it (the trained generator)
 Prints one JSON line per deck."""
 import copy, csv, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -18,23 +20,30 @@ import numpy as np
 
 SPH = {"active": False, "dim": 2, "type": "sphericalharmonic", "nvx": 128,
        "params": {"flm_type": "mora-yahi", "init_m": 2.2, "LTx": 225000.0, "LTy": 400000.0, "Nl": 1, "nvr": 128}}
-DECKS = (("dlm1d", 1, 256), ("arb2d", 2, 128), ("sph2d", 2, 128))
+SPH_TRAIN = {"active": True, "dim": 2, "type": "sphericalharmonic", "nvx": 128,
+             "params": {"flm_type": "mora-yahi", "init_m": 2.2, "LTx": 225000.0, "LTy": 400000.0, "Nl": 1, "nvr": 64}}
+DECKS = (("dlm1d", 1, 256), ("arb2d", 2, 128), ("sph2d", 2, 128), ("sphtrain", 2, 128))
 N1, N2 = 16, 48
 
 
 def kernel_sum(path):
     with open(path) as f:
         rows = sorted(csv.DictReader(f), key=lambda r: int(r["Start_Timestamp"]))
-    epochs, cur = [], None
+    epochs, gens, cur, gen = [], [], None, 0
     for r in rows:
         if r["Kernel_Name"].startswith("void tsff::k_ang_leaves"):
             if cur is not None:
                 epochs.append(cur)
-            cur = 0
+                gens.append(gen)
+            cur, gen = 0, 0
         if cur is not None:
-            cur += int(r["End_Timestamp"]) - int(r["Start_Timestamp"])
+            dt = int(r["End_Timestamp"]) - int(r["Start_Timestamp"])
+            cur += dt
+            if "tsff::k_sph_" in r["Kernel_Name"]:
+                gen += dt
     # (the last epoch of the trace is cut short by what follows it: dropped with the others' tail)
-    return dict(kernel_ms_per_epoch=float(np.median(epochs)) * 1e-6, epochs_in_trace=len(epochs))
+    return dict(kernel_ms_per_epoch=float(np.median(epochs)) * 1e-6, generator_ms_per_epoch=float(np.median(gens)) * 1e-6,
+                epochs_in_trace=len(epochs))
 
 
 def main():
@@ -52,10 +61,11 @@ def main():
         if only and name != only:
             continue
         cfg = decks.deck_angular(dim, nvx)
-        if name == "sph2d":
-            cfg["parameters"]["electron"]["fe"] = copy.deepcopy(SPH)
+        if name in ("sph2d", "sphtrain"):
+            cfg["parameters"]["electron"]["fe"] = copy.deepcopy(SPH if name == "sph2d" else SPH_TRAIN)
+        train = name == "sphtrain"
         cfg["other"]["ang_res_unit"] = 1
-        cfg["optimizer"].update(method="adam", learning_rate=1e-3, save_state=False)
+        cfg["optimizer"].update(method="rmsprop" if train else "adam", learning_rate=1e-4 if train else 1e-3, save_state=False)
         cfg["other"]["extraoptions"]["spectype"] = "angular"
         sa = calibration.get_scattering_angles(cfg)
         cfg["other"]["extraoptions"]["spectype"] = "angular_full"
@@ -75,7 +85,7 @@ def main():
             lf = LossFunction(copy.deepcopy(cfg), sa, batch)
             batch1 = dict(batch, e_data=e_data[a:b])
             diff, static = tree.partition(tp, tree.get_filter_spec(cfg["parameters"], tp))
-            opt = tree.Adam(1e-3)
+            opt = tree.RMSProp(1e-4) if train else tree.Adam(1e-3)
             st = opt.init(diff)
             lf.vg_loss(diff, static, batch1)
             torch.cuda.synchronize()
@@ -93,7 +103,7 @@ def main():
             info = {}
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            loops.angular_loop(c, all_data, sa, info=info)
+            loops.angular_loop(c, all_data, sa, info=info, train_generator=train)
             torch.cuda.synchronize()
             assert info["stopped_after"] is None, "the timing runs must not stop early"
             return time.perf_counter() - t0

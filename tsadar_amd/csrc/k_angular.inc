@@ -16,6 +16,7 @@
 //   DLM (1-D): fe = DLM1V(m) (distribution.dlm: linear in m between the 31 table columns, normalised to unit integral) and, for
 //              the chain rule of m, dfe = (dlm(m + h) - dlm(m - h)) / (2 h), h = 1e-6 (LossFunction._vg_angular_adjoint);
 //   Arbitrary2V: fe = f / sum f / dv^2 with f = fval^2 (learn_log: 10^-fval^2) (distribution.arbitrary_2v); aux[0] = sum f.
+//   SphericalHarmonics (TSFF_ANG_SPH): k_sph_table after this kernel and k_sph_vjp after k_ang_chain (k_sph.inc).
 __device__ __forceinline__ void ang_dlm(const double* __restrict__ tab, const double* __restrict__ maxis, int nvx, double dvx, double m,
                                         double* __restrict__ out, double* red) {
   int k = 0;   // searchsorted(M_AXIS, m, side="right") clipped to [1, 30]
@@ -183,13 +184,14 @@ __global__ __launch_bounds__(kThreads) void k_ang_chain(KStatic S, const double*
 //   (the reference's "elif val > best" sits under "if val < best" and never runs).
 // ctl (int32): [0] status (0 running, 1 ended), [1] the epoch it ended after, [2] g_wait, [3] b_wait, [4] 1 once a best exists.
 // Once ended, later epochs change nothing and log NaN.  method 0: Adam (mu = mom[0..n), nu = mom[n..2n)), 1: RMSProp (nu = mom[0..n)).
-// best_hist (optional) [epochs][NP]: the best scalar leaves after each epoch (save_state), untouched while no best exists.
+// best_hist (optional) [epochs][n_hist]: the best scalar leaves after each epoch (save_state; n_hist = NP, or NP + n_gen with the
+// parameters of a trained SphericalHarmonics generator behind them), untouched while no best exists.
 __global__ __launch_bounds__(kThreads) void k_ang_opt(const double* __restrict__ loss, const double* __restrict__ grad,
                                                       const int* __restrict__ act, int n_act, int NP, long n_table,
                                                       double* __restrict__ leaves, double* __restrict__ mom, int method, double b1,
                                                       double omb1, double b2, double omb2, double neg_lr, double c1, double c2, double eps,
                                                       int* __restrict__ ctl, double* __restrict__ best, int epoch,
-                                                      double* __restrict__ loss_hist, double* __restrict__ best_hist) {
+                                                      double* __restrict__ loss_hist, double* __restrict__ best_hist, int n_hist) {
 #pragma clang fp contract(off)
   __shared__ int dec[2];
   const double val = *loss;
@@ -230,5 +232,5 @@ __global__ __launch_bounds__(kThreads) void k_ang_opt(const double* __restrict__
   }
   __syncthreads();
   if (best_hist && running && dec[0])
-    for (int s = threadIdx.x; s < NP; s += kThreads) best_hist[s] = best[1 + s];
+    for (int s = threadIdx.x; s < n_hist; s += kThreads) best_hist[s] = best[1 + s];
 }

@@ -109,6 +109,7 @@ struct tsff_handle {
   tsff::DevBuf fit_packed;
   tsff::DevBuf adam_best;                // tsff_adam_fit: the ping-pong pair of best losses
   tsff::DevBuf ang_ws;                   // tsff_angular_fit: parameters, tables, image, seed and adjoints of one epoch
+  tsff::DevBuf sph_ws;                   // tsff_sph_table(_vjp): the radial functions and the point adjoint (k_sph.inc)
   std::vector<int32_t> act_host;
   tsff::DevBuf hws, hout;          // tsff_loss_hess: hyper-dual spectra of the persistent workgroups, per-task sums
   tsff::DevBuf htmm, Xmm, cstmm, Wmm, Wmm_unused;   // tsff_loss_hess with the DLM order m: second m-derivative tables
@@ -1923,6 +1924,48 @@ int tsff_adam_fit(tsff_handle* h, double* params, const double* fe, const double
   return 0;
 }
 
+// ---- the SphericalHarmonics generator (k_sph.inc).  sph_check: the refusals; sph_prepare: the handle's scratch
+static int sph_check(tsff_handle* h, int type, int H, int nv, int nvr, int n_gen) {
+  if (type != TSFF_SPH_MORA_YAHI && type != TSFF_SPH_ARBITRARY) return fail(h, -2, "unknown radial type %d", type);
+  if (type == TSFF_SPH_MORA_YAHI && H != 2) return fail(h, -2, "Mora-Yahi radial functions: l = 1 only (n_harm = 2), got %d", H);
+  if (H < 1 || H > kSphMaxH) return fail(h, -2, "n_harm must be 1 .. %d, got %d", kSphMaxH, H);
+  if (nvr < 2) return fail(h, -2, "nvr must be >= 2, got %d", nvr);
+  if (nv < 2 || nv > 4096) return fail(h, -2, "nv must be 2 .. 4096, got %d", nv);
+  const long want = type == TSFF_SPH_MORA_YAHI ? (long)H + 1 : 2L * H * nvr + 1;
+  if (n_gen != want) return fail(h, -2, "n_gen = %d, the generator has %ld parameters", n_gen, want);
+  return 0;
+}
+
+static int sph_prepare(tsff_handle* h, int type, int H, int nv, int nvr, int n_gen) {
+  if (int rc = sph_check(h, type, H, nv, nvr, n_gen)) return rc;
+  TSFF_ENSURE(h, h->sph_ws, sph_ws_doubles(H, nv, nvr) * sizeof(double));
+  return 0;
+}
+
+int tsff_sph_table(tsff_handle* h, int32_t sph_type, int32_t n_harm, int32_t nv, int32_t nvr, int32_t n_gen, double dvx,
+                   const double* theta, const double* gen_data, double* fe) {
+  DevGuard dg__(h);
+  if (!h) return -1;
+  if (!theta || !gen_data || !fe) return fail(h, -1, "bad argument");
+  if (int rc = sph_prepare(h, sph_type, n_harm, nv, nvr, n_gen)) return rc;
+  TSFF_LAUNCH0(h, k_sph_table, dim3(1), dim3(kThreads), 0, h->stream, sph_gen(sph_type, n_harm, nv, nvr, gen_data), theta, (int)n_gen,
+               dvx * dvx, h->sph_ws.as<double>(), fe);
+  TSFF_HIP(h, hipGetLastError());
+  return 0;
+}
+
+int tsff_sph_table_vjp(tsff_handle* h, int32_t sph_type, int32_t n_harm, int32_t nv, int32_t nvr, int32_t n_gen, double dvx,
+                       const double* theta, const double* gen_data, const double* fe_bar, double* grad) {
+  DevGuard dg__(h);
+  if (!h) return -1;
+  if (!theta || !gen_data || !fe_bar || !grad) return fail(h, -1, "bad argument");
+  if (int rc = sph_prepare(h, sph_type, n_harm, nv, nvr, n_gen)) return rc;
+  TSFF_LAUNCH0(h, k_sph_vjp, dim3(1), dim3(kThreads), 0, h->stream, sph_gen(sph_type, n_harm, nv, nvr, gen_data), theta, (int)n_gen,
+               1.0 / (dvx * dvx), std::log(10.0), fe_bar, h->sph_ws.as<double>(), grad);
+  TSFF_HIP(h, hipGetLastError());
+  return 0;
+}
+
 // the angular (ARTS) fit on the device (k_angular.inc): n_epochs x (leaves -> physical parameters and f_e, form factor, ATS
 // chain, loss and seed, ATS adjoint, form-factor adjoint, chain rule, optimiser + early stop), all enqueued on the handle's
 // stream.  The stages are prepared once, for one lineout and all its points -- every refusal before anything is allocated,
@@ -1939,22 +1982,26 @@ int tsff_angular_fit(tsff_handle* h, const tsff_angular_spec* sp, double* leaves
   if (h->ats_npx == 0) return fail(h, -2, "tsff_ats_setup has not been called");
   if (h->fe_mode != TSFF_FE_PER_LINEOUT) return fail(h, -2, "tsff_angular_fit needs fe_mode == TSFF_FE_PER_LINEOUT");
   const int gen = sp->generator, nv = sp->nv;
-  if (gen != TSFF_ANG_TABLE2D && gen != TSFF_ANG_DLM && gen != TSFF_ANG_ARB2V) return fail(h, -2, "unknown generator %d", gen);
+  if (gen != TSFF_ANG_TABLE2D && gen != TSFF_ANG_DLM && gen != TSFF_ANG_ARB2V && gen != TSFF_ANG_SPH)
+    return fail(h, -2, "unknown generator %d", gen);
   const bool two_d = gen != TSFF_ANG_DLM;
   if (gen == TSFF_ANG_DLM && nv != h->S.nvx) return fail(h, -1, "DLM: nv must be the handle's nvx (%d)", h->S.nvx);
   if (two_d && (nv < 4 || nv > 256)) return fail(h, -2, "2-D tables of nv = 4 .. 256 (the fit keeps the projection records)");
   if (gen != TSFF_ANG_ARB2V && !gen_data) return fail(h, -1, "gen_data missing");
+  if (gen == TSFF_ANG_SPH)
+    if (int rc = sph_check(h, sp->sph_type, sp->n_harm, nv, sp->nvr, sp->n_gen)) return rc;
   if (sp->method != TSFF_ANG_ADAM && sp->method != TSFF_ANG_RMSPROP) return fail(h, -2, "unknown optimiser %d", sp->method);
   if (sp->loss_method < 0 || sp->loss_method > 3) return fail(h, -2, "unknown loss method %d", sp->loss_method);
   uint8_t gm[kNP_MAX];
   if (int rc = check_slots(h, sp->active_slots, sp->n_active, gm, gen == TSFF_ANG_DLM)) return rc;   // (m: a leaf of DLM decks only)
-  const long n_table = gen == TSFF_ANG_ARB2V ? (long)nv * nv : 0;
+  const bool sph = gen == TSFF_ANG_SPH;
+  const long n_table = gen == TSFF_ANG_ARB2V ? (long)nv * nv : sph ? (long)sp->n_gen : 0;   // the leaves behind the NP scalars
   const long n = sp->n_active + n_table;
   if (n < 1) return fail(h, -1, "nothing to train");
   const int npts = h->S.npts, NA = h->S.n_angles, G = h->S.G, NP = h->S.NP;
   const int rows = h->ats_row_end - h->ats_row_start, nJ = npts / h->ats_lam_step;
   if (nJ > TSFF_NBINS) return fail(h, -2, "more than %d wavelength resolution units per row", TSFF_NBINS);
-  const bool want_dm = gm[TSFF_P_M] != 0, train_table = n_table > 0;
+  const bool want_dm = gm[TSFF_P_M] != 0, train_table = gen == TSFF_ANG_ARB2V, want_gfe = train_table || sph;
   const size_t nP = (size_t)G * npts * NA, nimg = (size_t)rows * nJ;
   // the stages of an epoch: the form factor (2-D: saving), the ATS chain and its reverse, the form-factor adjoint (with the table
   // adjoint when the table is trained, the f_e adjoint when m is a leaf)
@@ -1966,19 +2013,20 @@ int tsff_angular_fit(tsff_handle* h, const tsff_angular_spec* sp, double* leaves
     int rc = two_d ? form_factor_2d_prepare(h, 0, nv, true, 1, 0, -1, true, ff2, dry) : form_factor_prepare(h, 0, 1, ff, dry);
     if (!rc) rc = ats_prepare(h, false, dry);
     if (!rc) rc = ats_prepare(h, true, dry);
-    if (!rc) rc = two_d ? form_factor_2d_adj_prepare(h, 0, nv, 1, 0, (long)nP, train_table, ff2a, dry)
+    if (!rc) rc = two_d ? form_factor_2d_adj_prepare(h, 0, nv, 1, 0, (long)nP, want_gfe, ff2a, dry)
                         : form_factor_adj_prepare(h, 0, 1, want_dm, ffa, dry);
     return rc;
   };
   int rc = prepare_stages(true);
   if (rc || sp->n_epochs == 0) return rc;
-  // scratch: phys | fe | dfe (2 nv) | aux | P | ThryE | Ebar | Pbar | gphys | gfe | grad | loss
+  // scratch: phys | fe | dfe (2 nv) | aux | P | ThryE | Ebar | Pbar | gphys | gfe | grad | loss | the generator's (TSFF_ANG_SPH)
   const size_t nfe = two_d ? (size_t)nv * nv : (size_t)nv;
   size_t off = 0;
   auto take = [&](size_t k) { const size_t o = off; off += (k + 1) & ~(size_t)1; return o; };
   const size_t o_phys = take(NP + 1), o_fe = take(nfe), o_dfe = take(2 * (size_t)nv), o_aux = take(4), o_P = take(nP),
                o_E = take(nimg), o_Eb = take(nimg), o_Pb = take(nP), o_gp = take(NP), o_gfe = take(nfe), o_grad = take(n),
-               o_loss = take(1), o_part = take(kAngLossBlocks);
+               o_loss = take(1), o_part = take(kAngLossBlocks),
+               o_sph = take(sph ? sph_ws_doubles(sp->n_harm, nv, sp->nvr) : 0);
   TSFF_ENSURE(h, h->ang_ws, off * sizeof(double));
   if (sp->n_active > 0 && (rc = upload_slots(h, sp->active_slots, sp->n_active))) return rc;
   if ((rc = prepare_stages(false))) return rc;
@@ -1987,6 +2035,9 @@ int tsff_angular_fit(tsff_handle* h, const tsff_angular_spec* sp, double* leaves
          *Pb = ws + o_Pb, *gphys = ws + o_gp, *gfe = ws + o_gfe, *grad = ws + o_grad, *lossv = ws + o_loss,
          *lpart = ws + o_part;
   const double* table = gen == TSFF_ANG_TABLE2D ? gen_data : fe;
+  const SphGen SG = sph ? sph_gen(sp->sph_type, sp->n_harm, nv, sp->nvr, gen_data) : SphGen{};
+  const double* theta = leaves + NP;   // (TSFF_ANG_SPH: the generator's parameters)
+  const int n_hist = NP + (sph ? (int)n_table : 0);
   const double dv2 = sp->dvx * sp->dvx, cvjp = 1.0 / dv2, ln10 = std::log(10.0);
   // the optimiser's scalars as tree.Adam / tree.RMSProp compute them in Python (1 - b1, -lr, 1 - b1**count with glibc pow)
   const bool adam = sp->method == TSFF_ANG_ADAM;
@@ -2002,6 +2053,8 @@ int tsff_angular_fit(tsff_handle* h, const tsff_angular_spec* sp, double* leaves
       return 0;
     });
     if (rc) return rc;
+    if (sph)
+      TSFF_LAUNCH0(h, k_sph_table, dim3(1), dim3(kThreads), 0, h->stream, SG, theta, (int)sp->n_gen, dv2, ws + o_sph, fe);
     TSFF_HIP(h, hipGetLastError());
     rc = two_d ? form_factor_2d_enqueue(h, ff2, phys, table, sp->ud_angle, sp->va_angle, P) : form_factor_enqueue(h, ff, phys, fe, P);
     if (rc) return rc;
@@ -2021,12 +2074,15 @@ int tsff_angular_fit(tsff_handle* h, const tsff_angular_spec* sp, double* leaves
       return 0;
     });
     if (rc) return rc;
+    if (sph)   // grad: [n_act | n_gen]
+      TSFF_LAUNCH0(h, k_sph_vjp, dim3(1), dim3(kThreads), 0, h->stream, SG, theta, (int)sp->n_gen, cvjp, ln10, (const double*)gfe,
+                   ws + o_sph, grad + sp->n_active);
     TSFF_HIP(h, hipGetLastError());
     const double count = (double)epoch + 1;
     const double c1 = 1.0 - std::pow(b1, count), c2 = 1.0 - std::pow(b2, count);
     TSFF_LAUNCH0(h, k_ang_opt, dim3(1), dim3(kThreads), 0, h->stream, (const double*)lossv, (const double*)grad, act, (int)sp->n_active,
                  NP, n_table, leaves, moments, adam ? 0 : 1, b1, omb1, b2, omb2, neg_lr, c1, c2, sp->eps, ctl, best, epoch,
-                 loss_hist ? loss_hist + t : nullptr, best_hist ? best_hist + (size_t)t * NP : nullptr);
+                 loss_hist ? loss_hist + t : nullptr, best_hist ? best_hist + (size_t)t * n_hist : nullptr, n_hist);
     TSFF_HIP(h, hipGetLastError());
   }
   return 0;

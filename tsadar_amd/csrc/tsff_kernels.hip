@@ -13,6 +13,7 @@
 //   k_adam_step    loops.py:59-95        : one Adam step + best tracking on the packed loss and gradient (tsff_adam_fit, k_adam.inc)
 //   k_lbfgs_step   loops.py:20-56        : one evaluation's step of unbounded L-BFGS-B on the packed loss and gradient (tsff_lbfgs_fit)
 //   k_ang_*        loops.py:167-275      : the angular fit's generator, loss and seed, chain rule and optimiser step (tsff_angular_fit)
+//   k_sph_*        spherical_harmonics.py: the SphericalHarmonics f_e generator and its exact adjoint (tsff_sph_table(_vjp), TSFF_ANG_SPH)
 #include "tsff_device.h"
 
 namespace tsff {
@@ -100,6 +101,7 @@ constexpr int kFusedMaxIon = 2;  // k_spectrum_fused is instantiated for n_ion <
 #include "k_adam.inc"
 #include "k_lbfgs.inc"
 #include "k_angular.inc"
+#include "k_sph.inc"
 
 }  // namespace tsff
 

@@ -409,6 +409,72 @@ class SphericalHarmonics:
         return f / (np.sum(f) * (self.vx[1] - self.vx[0]) ** 2)
 
 
+from ._lib import SPH_ARBITRARY, SPH_MORA_YAHI   # noqa: E402  (TSFF_SPH_*: the radial types the device generator builds)
+
+
+def sph_gen_layout(sph_type: int, n_harm: int, nv: int, nvr: int) -> dict:
+    """name -> (offset, shape) of the blocks of ``gen_data`` of a device SphericalHarmonics generator (tsff.h, TSFF_ANG_SPH),
+    and "size": the number of doubles."""
+    n2 = nv * nv
+    blocks = [("vr", (nvr,)), ("cell", (n2,)), ("wt", (n2,)), ("inside", (n2,)), ("Y", (n_harm, n2))]
+    if sph_type == SPH_ARBITRARY:
+        blocks += [("M", (nvr, nvr)), ("ptr", (nvr + 1,)), ("pt", (2 * n2,)), ("cw", (2 * n2,))]
+    out, o = {}, 0
+    for name, shape in blocks:
+        out[name] = (o, shape)
+        o += int(np.prod(shape))
+    out["size"] = o
+    return out
+
+
+def sph_gen_data(sph: "SphericalHarmonics"):
+    """Everything of ``sph()`` and its adjoint that does not depend on the trained parameters, packed for the device generator
+    (tsff_sph_table, tsff_sph_table_vjp, TSFF_ANG_SPH) -> (gen_data [float64], meta).  ``meta``: sph_type, n_harm, nv, nvr,
+    n_gen (= ``sph.get_params().size``).  Per grid point (row-major over ``sph.vr_vxvy``): the radial cell, the weight in it
+    and the inside flag of ``np.interp(vr_vxvy, vr, ., right=...)``; ``real_sph_harm`` per harmonic in sorted (l, m) order;
+    for the free radial functions the Hanning smoothing matrix M (sm(a) = M @ a) and the transposed interpolation as a CSR
+    list -- radial node k receives ``cw[e] * g[pt[e]]`` for e in [ptr[k], ptr[k + 1]), in that order (the ``np.bincount`` pair
+    of :meth:`SphericalHarmonics.vjp`).  ``flm_type`` "nn" is not built on the device (NotImplementedError)."""
+    if sph.flm_type not in ("mora-yahi", "arbitrary"):
+        raise NotImplementedError(f"flm_type {sph.flm_type!r} is not built on the device (mora-yahi and arbitrary are)")
+    sph_type = SPH_MORA_YAHI if sph.flm_type == "mora-yahi" else SPH_ARBITRARY
+    keys = sorted(sph.flm)
+    nv, nvr = sph.nvx, sph.vr.size
+    lay = sph_gen_layout(sph_type, len(keys), nv, nvr)
+    out = np.zeros(lay["size"])
+
+    def put(name, a):
+        o, shape = lay[name]
+        out[o : o + int(np.prod(shape))] = np.asarray(a, dtype=np.float64).ravel()
+
+    q = sph.vr_vxvy.ravel()
+    i = np.clip(np.searchsorted(sph.vr, q, side="right") - 1, 0, nvr - 2)
+    t = np.clip((q - sph.vr[i]) / (sph.vr[i + 1] - sph.vr[i]), 0.0, 1.0)
+    inside = q <= sph.vr[-1]
+    put("vr", sph.vr)
+    put("cell", i)
+    put("wt", t)
+    put("inside", inside)
+    put("Y", np.stack([real_sph_harm(l, m, sph.phi, sph.th).ravel() for (l, m) in keys]))
+    if sph_type == SPH_ARBITRARY:
+        w = np.hanning(nvr // 4)
+        w = w / w.sum()
+        put("M", np.stack([np.convolve(e, w, mode="same") for e in np.eye(nvr)], axis=1))
+        p = np.nonzero(inside)[0]
+        node = np.concatenate([i[p], i[p] + 1])
+        pt = np.concatenate([p, p])
+        cw = np.concatenate([1.0 - t[p], t[p]])
+        order = np.lexsort((pt, node))   # by node, then by grid point
+        ptr = np.concatenate([[0], np.cumsum(np.bincount(node, minlength=nvr))])
+        put("ptr", ptr)
+        o = lay["pt"][0]
+        out[o : o + pt.size] = pt[order]
+        o = lay["cw"][0]
+        out[o : o + pt.size] = cw[order]
+    meta = dict(sph_type=sph_type, n_harm=len(keys), nv=nv, nvr=nvr, n_gen=int(sph.get_params().size))
+    return out, meta
+
+
 # ---------------------------------------------------------------------------------------------
 # Arbitrary1V (base.py:157-204): free-form 1-D distribution function.  Stored leaf: fval [nvx];
 # f_e = normalise(10 ** -((7 smooth(fval)) ** 2)), smooth = forward-backward second-order Butterworth filter

@@ -696,7 +696,9 @@ class Engine:
         fields of tsff_angular_spec (generator, nv, learn_log, active_slots, loss_method, un, ud_angle, va_angle, dvx, method,
         lr, b1, b2, eps, decay).  ``data``: device tensors gen_data, e_data and noise_e [rows, nJ], wcol [nJ], e_amps [rows].
         -> (leaves, state = (moments, best, ctl), loss_hist [n_epochs] or None, best_hist [n_epochs, NP] (NaN rows: no best yet)
-        or None) as CUDA tensors;
+        or None) as CUDA tensors.  Generator ANG_SPH (a trained SphericalHarmonics): ``spec`` also carries sph_type, n_harm, nvr
+        and n_gen (the ``meta`` of distribution.sph_gen_data, whose array is ``data["gen_data"]``), ``leaves`` is
+        [NP | get_params()] and the rows of best_hist are NP + n_gen wide;
         ``leaves`` and ``state`` are updated in place when they are CUDA tensors already (pass the returned ones to the next
         chunk, with ``epoch0`` the epochs done so far).  ``state=None`` starts a fit: zero moments, best = [100 | leaves]
         (angular_optax's best_loss = 100.0), ctl zeros."""
@@ -712,7 +714,8 @@ class Engine:
         mom, best, ctl = state
         assert mom.numel() == (2 if adam else 1) * n and best.numel() == 1 + x.numel() and ctl.dtype == torch.int32
         hist = torch.empty(max(int(n_epochs), 0), dtype=torch.float64, device=self.device) if loss_hist else None
-        bh = torch.full((max(int(n_epochs), 0), self.NP), float("nan"), dtype=torch.float64, device=self.device) if best_hist else None
+        n_hist = self.NP + (int(spec["n_gen"]) if int(spec["generator"]) == L.ANG_SPH else 0)
+        bh = torch.full((max(int(n_epochs), 0), n_hist), float("nan"), dtype=torch.float64, device=self.device) if best_hist else None
         c = L.TsffAngularSpec()
         c.generator, c.nv, c.learn_log = int(spec["generator"]), int(spec["nv"]), int(bool(spec.get("learn_log", False)))
         c.n_active, c.active_slots = int(act.size), act.ctypes.data_as(C.POINTER(C.c_int32))
@@ -721,12 +724,46 @@ class Engine:
         c.method = int(spec["method"])
         c.lr, c.b1, c.b2, c.eps, c.decay = (float(spec.get(k, 0.0)) for k in ("lr", "b1", "b2", "eps", "decay"))
         c.n_epochs, c.epoch0 = int(n_epochs), int(epoch0)
+        c.sph_type, c.n_harm, c.nvr, c.n_gen = (int(spec.get(k, 0)) for k in ("sph_type", "n_harm", "nvr", "n_gen"))
         self._sync_stream()
         rc = self.lib.tsff_angular_fit(self.h, C.byref(c), self._ptr(x), self._ptr(data.get("gen_data")), self._ptr(data["e_data"]),
                                        self._ptr(data["noise_e"]), self._ptr(data["wcol"]), self._ptr(data["e_amps"]), self._ptr(mom),
                                        self._ptr(best), self._ptr(ctl), self._ptr(hist), self._ptr(bh))
         L.check(self.lib, self.h, rc)
         return x, (mom, best, ctl), hist, bh
+
+    def _sph_args(self, meta: dict, dvx):
+        return [int(meta[k]) for k in ("sph_type", "n_harm", "nv", "nvr", "n_gen")] + [float(dvx)]
+
+    def sph_table(self, theta, gen_data, meta: dict, dvx=None, out=None):
+        """tsff_sph_table: the SphericalHarmonics generator on the device, ``theta`` [n_gen] (``get_params()`` order) ->
+        f_e [nv, nv] (CUDA tensor; nothing is synchronised).  ``gen_data``, ``meta``: distribution.sph_gen_data(sph);
+        ``dvx``: vx[1] - vx[0] (default: the reference's grid, 12 / nv)."""
+        torch = self.torch
+        nv = int(meta["nv"])
+        th, gd = self.dev(theta).reshape(-1), self.dev(gen_data)
+        assert th.numel() == int(meta["n_gen"]) and gd.numel() == D.sph_gen_layout(meta["sph_type"], meta["n_harm"], nv, meta["nvr"])["size"]
+        fe = out if out is not None else torch.empty((nv, nv), dtype=torch.float64, device=self.device)
+        self._sync_stream()
+        rc = self.lib.tsff_sph_table(self.h, *self._sph_args(meta, 12.0 / nv if dvx is None else dvx), self._ptr(th), self._ptr(gd),
+                                     self._ptr(fe))
+        L.check(self.lib, self.h, rc)
+        return fe
+
+    def sph_table_vjp(self, theta, gen_data, meta: dict, fe_bar, dvx=None, out=None):
+        """tsff_sph_table_vjp: ``fe_bar`` [nv, nv] = d loss / d f_e -> d loss / d theta [n_gen] (CUDA tensor; nothing is
+        synchronised), exact and bit-reproducible from run to run.  Arguments as :meth:`sph_table`."""
+        torch = self.torch
+        nv = int(meta["nv"])
+        th, gd, fb = self.dev(theta).reshape(-1), self.dev(gen_data), self.dev(fe_bar).reshape(-1)
+        assert th.numel() == int(meta["n_gen"]) and fb.numel() == nv * nv
+        assert gd.numel() == D.sph_gen_layout(meta["sph_type"], meta["n_harm"], nv, meta["nvr"])["size"]
+        g = out if out is not None else torch.empty(int(meta["n_gen"]), dtype=torch.float64, device=self.device)
+        self._sync_stream()
+        rc = self.lib.tsff_sph_table_vjp(self.h, *self._sph_args(meta, 12.0 / nv if dvx is None else dvx), self._ptr(th),
+                                         self._ptr(gd), self._ptr(fb), self._ptr(g))
+        L.check(self.lib, self.h, rc)
+        return g
 
     def lbfgs_fit(self, params, batch, weights, active_slots, n_evals, opts=(10, 2.220446049250313e-09, 1e-5, 15000, 15000, 20),
                   state=None, f_hist=True, info=None, fe=None):

@@ -133,7 +133,7 @@ RMSPROP_DECAY, RMSPROP_EPS = 0.9, 1e-8   # optax.rmsprop's defaults
 
 
 def angular_loop(config: Dict, all_data: Dict, sa: Dict, chunk: Optional[int] = None, progress=None, states: Optional[Dict] = None,
-                 info: Optional[Dict] = None, distributed: bool = False):
+                 info: Optional[Dict] = None, distributed: bool = False, train_generator: bool = False):
     """``angular_optax(config, all_data, sa)`` -> (best_weights, epoch_loss, loss_fn), run on the device by
     ``Engine.angular_fit`` (tsff_angular_fit, k_angular.inc).
 
@@ -151,10 +151,19 @@ def angular_loop(config: Dict, all_data: Dict, sa: Dict, chunk: Optional[int] = 
     (every ``save_state_freq``-th epoch that does not end the fit; an epoch before any best exists, where the reference would
     fail on ``{}``, is skipped); writing the file and logging stay with the caller.  ``info``: a dict that receives
     ``loss_hist`` (the loss of every epoch run, NaN after the end: the reference's per-epoch "epoch loss" metric),
-    ``stopped_after`` (the epoch of the early stop, or None) and ``leaves`` (the final normalised leaves, then fval).
+    ``stopped_after`` (the epoch of the early stop, or None) and ``leaves`` (the final normalised leaves, then fval or the
+    generator's parameters).
+
+    ``train_generator=True``: a trainable ``sphericalharmonic`` f_e of ``flm_type`` "mora-yahi" or "arbitrary" (the reference's
+    arts2v deck) is trained on the device: the table is built from ``SphericalHarmonics.get_params()`` every epoch and its
+    adjoint is chained to them exactly (k_sph.inc), where ``LossFunction.vg_loss`` takes central differences for the order of
+    f00 and the Mora-Yahi gradient lengths.  ``best_weights.sph`` is that of the best iterate, ``info["leaves"]`` the scalars
+    then the generator's parameters, and each saved state carries the best iterate's radial functions under
+    ``["electron"]["flm"]`` (the reference's layout).  The default refuses such a deck, as before.
 
     Not built (NotImplementedError, raised before any device work): methods other than adam and rmsprop, multiplexed decks
-    (``shotnum`` a list), ``distributed=True``, trainable SphericalHarmonics generators, 1-D decks other than DLM1V."""
+    (``shotnum`` a list), ``distributed=True``, trainable SphericalHarmonics generators without ``train_generator`` or of
+    ``flm_type`` "nn", 1-D decks other than DLM1V."""
     from . import _lib as L
     from . import distribution as Dist
     from .loss_function import LossFunction
@@ -170,8 +179,14 @@ def angular_loop(config: Dict, all_data: Dict, sa: Dict, chunk: Optional[int] = 
     fecfg = config["parameters"]["electron"]["fe"]
     dim = int(fecfg.get("dim", 1))
     if dim == 2 and "sph" in str(fecfg["type"]).casefold() and fecfg.get("active", False):
-        raise NotImplementedError("angular_loop: a trainable SphericalHarmonics generator is not built on the device (use the host "
-                                  "loop over LossFunction.vg_loss)")
+        if not train_generator:
+            raise NotImplementedError("angular_loop: a trainable SphericalHarmonics generator is not built on the device (use the "
+                                      "host loop over LossFunction.vg_loss)")
+        flm_type = str(fecfg["params"].get("flm_type", "arbitrary")).casefold()
+        if flm_type not in ("mora-yahi", "arbitrary"):
+            raise NotImplementedError(f"angular_loop: train_generator with flm_type {flm_type!r} -- only mora-yahi and arbitrary "
+                                      "radial functions are built on the device; flm_type nn stays on the host (the loop over "
+                                      "LossFunction.vg_loss)")
     if dim == 1 and str(fecfg.get("type", "dlm")).casefold() != "dlm":
         raise NotImplementedError(f"angular_loop: 1-D f_e of type {fecfg.get('type')!r} -- only DLM1V is built")
 
@@ -186,11 +201,12 @@ def angular_loop(config: Dict, all_data: Dict, sa: Dict, chunk: Optional[int] = 
     loss_fn = LossFunction(config, sa, batch1)
     ts_params = ThomsonParams(config["parameters"], num_params=1, batch=False, activate=True)
     sm = ts_params.slots
-    if sm.gen2d_active or ts_params.fval is not None or (dim == 1 and not sm.has_m):
+    if (sm.gen2d_active and not train_generator) or ts_params.fval is not None or (dim == 1 and not sm.has_m):
         raise NotImplementedError("angular_loop: this distribution function is not built on the device")
     diff, _ = tree.partition(ts_params, tree.get_filter_spec(config["parameters"], ts_params))
     act = [s for _, s in diff.slots if s >= 0]
     train_table = any(s == tree.FVAL2D_SLOT for _, s in diff.slots)
+    train_gen = any(s == tree.GEN2D_SLOT for _, s in diff.slots)
 
     eng = loss_fn.ts_diag.engine(ts_params.activate)
     torch = eng.torch
@@ -217,6 +233,10 @@ def angular_loop(config: Dict, all_data: Dict, sa: Dict, chunk: Optional[int] = 
             spec.update(generator=L.ANG_ARB2V, learn_log=ts_params.learn_log)
             leaves = np.concatenate([leaves, ts_params.fval2d.ravel()])
             gen_data = None
+        elif train_gen:
+            gen_data, meta = Dist.sph_gen_data(ts_params.sph)
+            spec.update(generator=L.ANG_SPH, **meta)
+            leaves = np.concatenate([leaves, ts_params.sph.get_params()])
         else:   # a constant table (SphericalHarmonics or Arbitrary2V not trained), built once on the host
             spec["generator"] = L.ANG_TABLE2D
             gen_data = np.ascontiguousarray(ts_params()["electron"]["fe"], dtype=np.float64)
@@ -258,8 +278,11 @@ def angular_loop(config: Dict, all_data: Dict, sa: Dict, chunk: Optional[int] = 
         for i in range(last_epoch if ctl[0] != 0 else n_epochs):
             if i % freq == 0 and not np.isnan(bh[i, 0]):
                 snap = ts_params.copy()
-                snap.X[0] = bh[i]
+                snap.X[0] = bh[i, : eng.NP]
                 states[i] = snap.get_unnormed_params()
+                if train_gen:
+                    snap.sph.set_params(bh[i, eng.NP :])
+                    states[i]["electron"]["flm"] = snap.sph.get_unnormed_params()["flm"]
     if ctl[4] == 0:   # (no epoch improved on 100.0: the reference returns the dict it started with)
         return {}, epoch_loss, loss_fn
     best = eng.download(state[1])
@@ -267,4 +290,6 @@ def angular_loop(config: Dict, all_data: Dict, sa: Dict, chunk: Optional[int] = 
     best_weights.X[0] = best[1 : 1 + eng.NP]
     if train_table:
         best_weights.fval2d = best[1 + eng.NP :].reshape(ts_params.fval2d.shape).copy()
+    if train_gen:
+        best_weights.sph.set_params(best[1 + eng.NP :])
     return best_weights, epoch_loss, loss_fn
