@@ -54,7 +54,7 @@
 extern "C" {
 #endif
 
-#define TSFF_ABI_VERSION 14
+#define TSFF_ABI_VERSION 15
 /* error codes (every entry point returns 0 or one of these; text via tsff_last_error):
  * -1 bad argument, -2 unsupported configuration / option, -3 not a differentiable leaf, -5 HIP runtime error,
  * -22 stale or foreign token of saved projection records (tsff_form_factor_2d_grad),
@@ -398,7 +398,7 @@ int tsff_lbfgs_fit(tsff_handle *h, double *params, const double *fe, const doubl
  * allocated, and the handle's scratch is sized before the first launch: no epoch allocates, and nothing synchronises.  Needs
  * fe_mode == TSFF_FE_PER_LINEOUT and tsff_ats_setup.
  *   spec (HOST): the deck and the optimiser, below;
- *   leaves (device [NP + nv^2 for TSFF_ANG_ARB2V], in/out): the normalised leaves of the one plasma condition, then fval;
+ *   leaves (device [NP + nv^2 for TSFF_ANG_ARB2V, NP + nv for TSFF_ANG_ARB1V], in/out): the normalised leaves of the one plasma condition, then fval;
  *   gen_data (device): TSFF_ANG_DLM [nv][31] DLM table | [31] m axis (tsadar_amd.distribution.dlm_table, M_AXIS);
  *   TSFF_ANG_TABLE2D the constant table [nv][nv]; TSFF_ANG_ARB2V unused; TSFF_ANG_SPH: the generator's constants, below;
  *   e_data, noise_e (device [rows][nJ]), wcol (device [nJ]: blue / red masks over rows x mask count, halved when both are
@@ -420,17 +420,24 @@ int tsff_lbfgs_fit(tsff_handle *h, double *params, const double *fe, const doubl
  *   | M[nvr][nvr] | ptr[nvr + 1] | pt[2 n2] | cw[2 n2]        TSFF_SPH_ARBITRARY only: the smoothing matrix and, for the transposed
  *                                                             interpolation, per radial node k the grid points pt[e] and weights
  *                                                             cw[e] that reach it, e in [ptr[k], ptr[k + 1]) (unused tail: zeros).
+ * TSFF_ANG_ARB1V (a trained free-form 1-D f_e, the reference's Arbitrary1V; k_arb1v.inc) follows the 1-D path with nv the handle's
+ * nvx: f_e = normalise(10^-(7 S fval)^2) with S the constant forward-backward Butterworth matrix, built from the leaves every
+ * epoch, and d loss / d f_e (the 1-D form-factor adjoint with its f_e tail) chained to fval exactly.  leaves [NP | fval[nv]],
+ * moments over n_active + nv, best [1 + NP + nv], best_hist rows of NP + nv.  gen_data: S[nv][nv] | S^T[nv][nv], row-major
+ * (tsadar_amd.distribution.arb1v_gen_data).  Four launches more per epoch than a DLM deck without m: S fval and the pointwise
+ * kernel after k_ang_leaves, the pointwise adjoint and S^T g_u after k_ang_chain.  The spec gets no field of its own.
  * Chunks: epoch0 = the epochs done so far (Adam's bias correction); a fit in chunks is bit for bit one call.
  * Refusals: a null pointer, a slot out of range or repeated -1, TSFF_P_M outside DLM decks -2, an ion's A slot -3, an unknown
  * generator, optimiser or loss method, nv outside 4 .. 256 for 2-D tables, too little LDS -2 (TSFF_ERR_LDS for the 1-D adjoint);
  * TSFF_ANG_SPH: an unknown radial type, n_harm != 2 for Mora-Yahi (l = 1 only) or outside 1 .. 64, nvr < 2, or n_gen other than
- * n_harm + 1 (Mora-Yahi) / 2 n_harm nvr + 1 (free radial functions) -2. */
-enum { TSFF_ANG_TABLE2D = 0, TSFF_ANG_DLM = 1, TSFF_ANG_ARB2V = 2, TSFF_ANG_SPH = 3 };
+ * n_harm + 1 (Mora-Yahi) / 2 n_harm nvr + 1 (free radial functions) -2; TSFF_ANG_ARB1V: nv other than the handle's nvx -1,
+ * TSFF_P_M among the active slots -2 (the deck has no DLM order). */
+enum { TSFF_ANG_TABLE2D = 0, TSFF_ANG_DLM = 1, TSFF_ANG_ARB2V = 2, TSFF_ANG_SPH = 3, TSFF_ANG_ARB1V = 4 };
 enum { TSFF_SPH_MORA_YAHI = 0, TSFF_SPH_ARBITRARY = 1 }; /* flm_type of a SphericalHarmonics generator */
 enum { TSFF_ANG_ADAM = 0, TSFF_ANG_RMSPROP = 1 };
 typedef struct {
   int32_t generator;            /* TSFF_ANG_* */
-  int32_t nv;                   /* velocity points per axis (DLM: the handle's nvx) */
+  int32_t nv;                   /* velocity points per axis (DLM, ARB1V: the handle's nvx) */
   int32_t learn_log;            /* TSFF_ANG_ARB2V: fval^2 is -log10 f */
   int32_t n_active;             /* trained scalar slots */
   const int32_t *active_slots;  /* HOST [n_active] */
@@ -459,6 +466,17 @@ int tsff_sph_table(tsff_handle *h, int32_t sph_type, int32_t n_harm, int32_t nv,
                    const double *theta, const double *gen_data, double *fe);
 int tsff_sph_table_vjp(tsff_handle *h, int32_t sph_type, int32_t n_harm, int32_t nv, int32_t nvr, int32_t n_gen, double dvx,
                        const double *theta, const double *gen_data, const double *fe_bar, double *grad);
+
+/* The free-form 1-D generator on its own (k_arb1v.inc; the kernels of TSFF_ANG_ARB1V), asynchronous on the handle's stream:
+ *   tsff_arb1v_table:     fval (device [nv]) -> fe (device [nv]) = Arbitrary1V.__call__() (distribution.arbitrary_1v);
+ *   tsff_arb1v_table_vjp: fval, fe_bar (device [nv]) = d loss / d fe -> grad (device [nv]) = d loss / d fval
+ *   (distribution.arbitrary_1v_vjp), bit-reproducible from run to run (every sum in a fixed order, no atomics).
+ * gen_data (device): S[nv][nv] | S^T[nv][nv]; dvx = vx[1] - vx[0]; nv = 4 .. 4096 (need not be the handle's nvx).  The matrix
+ * products run one wavefront per row on (nv + 3) / 4 workgroups.  The scratch (2 nv doubles) is the handle's and is sized on the
+ * first call at a given size: later calls allocate nothing.  Refusals: a null pointer -1, nv outside 4 .. 4096 -2. */
+int tsff_arb1v_table(tsff_handle *h, int32_t nv, double dvx, const double *fval, const double *gen_data, double *fe);
+int tsff_arb1v_table_vjp(tsff_handle *h, int32_t nv, double dvx, const double *fval, const double *gen_data, const double *fe_bar,
+                         double *grad);
 
 /* Exact per-lineout Hessian of the fit loss: LossFunction._loss_for_hess_fn_ / h_loss_wrt_params
  * (inverse/loss_function.py:170-188, equinox.filter_hessian) for every lineout b, with respect to the normalised leaves

@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtsff.so")
 LIB_PATH = os.environ.get("TSFF_LIBRARY", LIB_PATH)  # A/B experiments: another in-tree build of the same ABI
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 MAX_ION = 4
 NBINS = 1024
 NXI1 = 1024
@@ -29,7 +29,7 @@ OPT_DENOM_MODE = 1
 OPT_LAUNCH_PLAN = 2
 OPT_DLM_BLOCKS = 3
 ERR_LDS = -7  # TSFF_ERR_LDS: more LDS needed than a CU has
-ANG_TABLE2D, ANG_DLM, ANG_ARB2V, ANG_SPH = range(4)   # tsff_angular_fit's generators
+ANG_TABLE2D, ANG_DLM, ANG_ARB2V, ANG_SPH, ANG_ARB1V = range(5)   # tsff_angular_fit's generators
 SPH_MORA_YAHI, SPH_ARBITRARY = range(2)      # the radial types of ANG_SPH (tsff_sph_table, tsff_sph_table_vjp)
 ANG_ADAM, ANG_RMSPROP = range(2)             # and optimisers
 
@@ -165,6 +165,8 @@ _SIGNATURES = {
     "tsff_angular_fit": (C.c_int, [_vp, C.POINTER(TsffAngularSpec)] + [_vp] * 11),
     "tsff_sph_table": (C.c_int, [_vp] + [C.c_int32] * 5 + [C.c_double, _vp, _vp, _vp]),
     "tsff_sph_table_vjp": (C.c_int, [_vp] + [C.c_int32] * 5 + [C.c_double, _vp, _vp, _vp, _vp]),
+    "tsff_arb1v_table": (C.c_int, [_vp, C.c_int32, C.c_double, _vp, _vp, _vp]),
+    "tsff_arb1v_table_vjp": (C.c_int, [_vp, C.c_int32, C.c_double, _vp, _vp, _vp, _vp]),
     "tsff_loss_hess": (C.c_int, [_vp] + [_vp] * 8 + [C.c_int32, c_double_p, C.POINTER(C.c_int32), C.c_int32, _vp, _vp, _vp]),
     "tsff_array_loss": (C.c_int, [_vp] + [_vp] * 8 + [C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "tsff_enable_timing": (C.c_int, [_vp, C.c_int32]),

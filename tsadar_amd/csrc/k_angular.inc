@@ -17,6 +17,8 @@
 //              the chain rule of m, dfe = (dlm(m + h) - dlm(m - h)) / (2 h), h = 1e-6 (LossFunction._vg_angular_adjoint);
 //   Arbitrary2V: fe = f / sum f / dv^2 with f = fval^2 (learn_log: 10^-fval^2) (distribution.arbitrary_2v); aux[0] = sum f.
 //   SphericalHarmonics (TSFF_ANG_SPH): k_sph_table after this kernel and k_sph_vjp after k_ang_chain (k_sph.inc).
+//   Arbitrary1V (TSFF_ANG_ARB1V): k_arb1v_matvec and k_arb1v_point after this kernel, and again, in the other order, after
+//              k_ang_chain (k_arb1v.inc); this kernel writes the physical parameters only.
 __device__ __forceinline__ void ang_dlm(const double* __restrict__ tab, const double* __restrict__ maxis, int nvx, double dvx, double m,
                                         double* __restrict__ out, double* red) {
   int k = 0;   // searchsorted(M_AXIS, m, side="right") clipped to [1, 30]
@@ -185,7 +187,7 @@ __global__ __launch_bounds__(kThreads) void k_ang_chain(KStatic S, const double*
 // ctl (int32): [0] status (0 running, 1 ended), [1] the epoch it ended after, [2] g_wait, [3] b_wait, [4] 1 once a best exists.
 // Once ended, later epochs change nothing and log NaN.  method 0: Adam (mu = mom[0..n), nu = mom[n..2n)), 1: RMSProp (nu = mom[0..n)).
 // best_hist (optional) [epochs][n_hist]: the best scalar leaves after each epoch (save_state; n_hist = NP, or NP + n_gen with the
-// parameters of a trained SphericalHarmonics generator behind them), untouched while no best exists.
+// parameters of a trained SphericalHarmonics generator, NP + nv with the fval of a trained Arbitrary1V, behind them), untouched while no best exists.
 __global__ __launch_bounds__(kThreads) void k_ang_opt(const double* __restrict__ loss, const double* __restrict__ grad,
                                                       const int* __restrict__ act, int n_act, int NP, long n_table,
                                                       double* __restrict__ leaves, double* __restrict__ mom, int method, double b1,

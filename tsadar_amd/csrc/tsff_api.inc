@@ -110,6 +110,7 @@ struct tsff_handle {
   tsff::DevBuf adam_best;                // tsff_adam_fit: the ping-pong pair of best losses
   tsff::DevBuf ang_ws;                   // tsff_angular_fit: parameters, tables, image, seed and adjoints of one epoch
   tsff::DevBuf sph_ws;                   // tsff_sph_table(_vjp): the radial functions and the point adjoint (k_sph.inc)
+  tsff::DevBuf arb1v_ws;                 // tsff_arb1v_table(_vjp): u = S fval and its adjoint (k_arb1v.inc)
   std::vector<int32_t> act_host;
   tsff::DevBuf hws, hout;          // tsff_loss_hess: hyper-dual spectra of the persistent workgroups, per-task sums
   tsff::DevBuf htmm, Xmm, cstmm, Wmm, Wmm_unused;   // tsff_loss_hess with the DLM order m: second m-derivative tables
@@ -1966,6 +1967,53 @@ int tsff_sph_table_vjp(tsff_handle* h, int32_t sph_type, int32_t n_harm, int32_t
   return 0;
 }
 
+// ---- the free-form 1-D generator (k_arb1v.inc).  arb1v_forward: fval -> u (ws) -> fe; arb1v_adjoint: u (ws, left by the
+// forward), fe_bar -> g_u (ws) -> grad.  gen_data: S | S^T.  Launches only: the caller has checked nv and sized ws.
+static int arb1v_check(tsff_handle* h, int nv) {
+  if (nv < 4 || nv > kArb1vMaxNv) return fail(h, -2, "nv must be 4 .. %d, got %d", kArb1vMaxNv, nv);
+  return 0;
+}
+
+static void arb1v_matvec(tsff_handle* h, const double* M, const double* x, int nv, double* y) {
+  TSFF_LAUNCH0(h, k_arb1v_matvec, dim3((unsigned)((nv + kArb1vRows - 1) / kArb1vRows)), dim3(kThreads), 0, h->stream, M, x, nv, y);
+}
+
+static int arb1v_forward(tsff_handle* h, int nv, double dvx, const double* fval, const double* gen_data, double* ws, double* fe) {
+  arb1v_matvec(h, gen_data, fval, nv, ws);
+  TSFF_LAUNCH0(h, k_arb1v_point, dim3(1), dim3(kThreads), 0, h->stream, (const double*)ws, nv, dvx, std::log(10.0),
+               (const double*)nullptr, fe);
+  TSFF_HIP(h, hipGetLastError());
+  return 0;
+}
+
+static int arb1v_adjoint(tsff_handle* h, int nv, double dvx, const double* gen_data, const double* fe_bar, double* ws, double* grad) {
+  TSFF_LAUNCH0(h, k_arb1v_point, dim3(1), dim3(kThreads), 0, h->stream, (const double*)ws, nv, dvx, std::log(10.0), fe_bar, ws + nv);
+  arb1v_matvec(h, gen_data + (size_t)nv * nv, ws + nv, nv, grad);
+  TSFF_HIP(h, hipGetLastError());
+  return 0;
+}
+
+int tsff_arb1v_table(tsff_handle* h, int32_t nv, double dvx, const double* fval, const double* gen_data, double* fe) {
+  DevGuard dg__(h);
+  if (!h) return -1;
+  if (!fval || !gen_data || !fe) return fail(h, -1, "bad argument");
+  if (int rc = arb1v_check(h, nv)) return rc;
+  TSFF_ENSURE(h, h->arb1v_ws, arb1v_ws_doubles(nv) * sizeof(double));
+  return arb1v_forward(h, nv, dvx, fval, gen_data, h->arb1v_ws.as<double>(), fe);
+}
+
+int tsff_arb1v_table_vjp(tsff_handle* h, int32_t nv, double dvx, const double* fval, const double* gen_data, const double* fe_bar,
+                         double* grad) {
+  DevGuard dg__(h);
+  if (!h) return -1;
+  if (!fval || !gen_data || !fe_bar || !grad) return fail(h, -1, "bad argument");
+  if (int rc = arb1v_check(h, nv)) return rc;
+  TSFF_ENSURE(h, h->arb1v_ws, arb1v_ws_doubles(nv) * sizeof(double));
+  double* ws = h->arb1v_ws.as<double>();
+  arb1v_matvec(h, gen_data, fval, nv, ws);   // (u alone: the adjoint's pointwise kernel rebuilds f_e from it)
+  return arb1v_adjoint(h, nv, dvx, gen_data, fe_bar, ws, grad);
+}
+
 // the angular (ARTS) fit on the device (k_angular.inc): n_epochs x (leaves -> physical parameters and f_e, form factor, ATS
 // chain, loss and seed, ATS adjoint, form-factor adjoint, chain rule, optimiser + early stop), all enqueued on the handle's
 // stream.  The stages are prepared once, for one lineout and all its points -- every refusal before anything is allocated,
@@ -1982,10 +2030,14 @@ int tsff_angular_fit(tsff_handle* h, const tsff_angular_spec* sp, double* leaves
   if (h->ats_npx == 0) return fail(h, -2, "tsff_ats_setup has not been called");
   if (h->fe_mode != TSFF_FE_PER_LINEOUT) return fail(h, -2, "tsff_angular_fit needs fe_mode == TSFF_FE_PER_LINEOUT");
   const int gen = sp->generator, nv = sp->nv;
-  if (gen != TSFF_ANG_TABLE2D && gen != TSFF_ANG_DLM && gen != TSFF_ANG_ARB2V && gen != TSFF_ANG_SPH)
+  if (gen != TSFF_ANG_TABLE2D && gen != TSFF_ANG_DLM && gen != TSFF_ANG_ARB2V && gen != TSFF_ANG_SPH && gen != TSFF_ANG_ARB1V)
     return fail(h, -2, "unknown generator %d", gen);
-  const bool two_d = gen != TSFF_ANG_DLM;
+  const bool arb1v = gen == TSFF_ANG_ARB1V;
+  const bool two_d = gen != TSFF_ANG_DLM && !arb1v;
   if (gen == TSFF_ANG_DLM && nv != h->S.nvx) return fail(h, -1, "DLM: nv must be the handle's nvx (%d)", h->S.nvx);
+  if (arb1v && nv != h->S.nvx) return fail(h, -1, "free-form 1-D f_e: nv must be the handle's nvx (%d), got %d", h->S.nvx, nv);
+  if (arb1v)
+    if (int rc = arb1v_check(h, nv)) return rc;
   if (two_d && (nv < 4 || nv > 256)) return fail(h, -2, "2-D tables of nv = 4 .. 256 (the fit keeps the projection records)");
   if (gen != TSFF_ANG_ARB2V && !gen_data) return fail(h, -1, "gen_data missing");
   if (gen == TSFF_ANG_SPH)
@@ -1995,7 +2047,7 @@ int tsff_angular_fit(tsff_handle* h, const tsff_angular_spec* sp, double* leaves
   uint8_t gm[kNP_MAX];
   if (int rc = check_slots(h, sp->active_slots, sp->n_active, gm, gen == TSFF_ANG_DLM)) return rc;   // (m: a leaf of DLM decks only)
   const bool sph = gen == TSFF_ANG_SPH;
-  const long n_table = gen == TSFF_ANG_ARB2V ? (long)nv * nv : sph ? (long)sp->n_gen : 0;   // the leaves behind the NP scalars
+  const long n_table = gen == TSFF_ANG_ARB2V ? (long)nv * nv : sph ? (long)sp->n_gen : arb1v ? (long)nv : 0;   // the leaves behind the NP scalars
   const long n = sp->n_active + n_table;
   if (n < 1) return fail(h, -1, "nothing to train");
   const int npts = h->S.npts, NA = h->S.n_angles, G = h->S.G, NP = h->S.NP;
@@ -2004,7 +2056,7 @@ int tsff_angular_fit(tsff_handle* h, const tsff_angular_spec* sp, double* leaves
   const bool want_dm = gm[TSFF_P_M] != 0, train_table = gen == TSFF_ANG_ARB2V, want_gfe = train_table || sph;
   const size_t nP = (size_t)G * npts * NA, nimg = (size_t)rows * nJ;
   // the stages of an epoch: the form factor (2-D: saving), the ATS chain and its reverse, the form-factor adjoint (with the table
-  // adjoint when the table is trained, the f_e adjoint when m is a leaf)
+  // adjoint when the table is trained, the f_e adjoint when m is a leaf or the free-form 1-D f_e is trained)
   FormFactorPlan ff;
   FormFactorAdjPlan ffa;
   FormFactor2dPlan ff2;
@@ -2014,19 +2066,19 @@ int tsff_angular_fit(tsff_handle* h, const tsff_angular_spec* sp, double* leaves
     if (!rc) rc = ats_prepare(h, false, dry);
     if (!rc) rc = ats_prepare(h, true, dry);
     if (!rc) rc = two_d ? form_factor_2d_adj_prepare(h, 0, nv, 1, 0, (long)nP, want_gfe, ff2a, dry)
-                        : form_factor_adj_prepare(h, 0, 1, want_dm, ffa, dry);
+                        : form_factor_adj_prepare(h, 0, 1, want_dm || arb1v, ffa, dry);
     return rc;
   };
   int rc = prepare_stages(true);
   if (rc || sp->n_epochs == 0) return rc;
-  // scratch: phys | fe | dfe (2 nv) | aux | P | ThryE | Ebar | Pbar | gphys | gfe | grad | loss | the generator's (TSFF_ANG_SPH)
+  // scratch: phys | fe | dfe (2 nv) | aux | P | ThryE | Ebar | Pbar | gphys | gfe | grad | loss | the generator's (TSFF_ANG_SPH, TSFF_ANG_ARB1V)
   const size_t nfe = two_d ? (size_t)nv * nv : (size_t)nv;
   size_t off = 0;
   auto take = [&](size_t k) { const size_t o = off; off += (k + 1) & ~(size_t)1; return o; };
   const size_t o_phys = take(NP + 1), o_fe = take(nfe), o_dfe = take(2 * (size_t)nv), o_aux = take(4), o_P = take(nP),
                o_E = take(nimg), o_Eb = take(nimg), o_Pb = take(nP), o_gp = take(NP), o_gfe = take(nfe), o_grad = take(n),
                o_loss = take(1), o_part = take(kAngLossBlocks),
-               o_sph = take(sph ? sph_ws_doubles(sp->n_harm, nv, sp->nvr) : 0);
+               o_sph = take(sph ? sph_ws_doubles(sp->n_harm, nv, sp->nvr) : arb1v ? arb1v_ws_doubles(nv) : 0);
   TSFF_ENSURE(h, h->ang_ws, off * sizeof(double));
   if (sp->n_active > 0 && (rc = upload_slots(h, sp->active_slots, sp->n_active))) return rc;
   if ((rc = prepare_stages(false))) return rc;
@@ -2036,8 +2088,8 @@ int tsff_angular_fit(tsff_handle* h, const tsff_angular_spec* sp, double* leaves
          *lpart = ws + o_part;
   const double* table = gen == TSFF_ANG_TABLE2D ? gen_data : fe;
   const SphGen SG = sph ? sph_gen(sp->sph_type, sp->n_harm, nv, sp->nvr, gen_data) : SphGen{};
-  const double* theta = leaves + NP;   // (TSFF_ANG_SPH: the generator's parameters)
-  const int n_hist = NP + (sph ? (int)n_table : 0);
+  const double* theta = leaves + NP;   // (TSFF_ANG_SPH: the generator's parameters; TSFF_ANG_ARB1V: fval)
+  const int n_hist = NP + (sph || arb1v ? (int)n_table : 0);
   const double dv2 = sp->dvx * sp->dvx, cvjp = 1.0 / dv2, ln10 = std::log(10.0);
   // the optimiser's scalars as tree.Adam / tree.RMSProp compute them in Python (1 - b1, -lr, 1 - b1**count with glibc pow)
   const bool adam = sp->method == TSFF_ANG_ADAM;
@@ -2056,6 +2108,7 @@ int tsff_angular_fit(tsff_handle* h, const tsff_angular_spec* sp, double* leaves
     if (sph)
       TSFF_LAUNCH0(h, k_sph_table, dim3(1), dim3(kThreads), 0, h->stream, SG, theta, (int)sp->n_gen, dv2, ws + o_sph, fe);
     TSFF_HIP(h, hipGetLastError());
+    if (arb1v && (rc = arb1v_forward(h, nv, sp->dvx, theta, gen_data, ws + o_sph, fe))) return rc;
     rc = two_d ? form_factor_2d_enqueue(h, ff2, phys, table, sp->ud_angle, sp->va_angle, P) : form_factor_enqueue(h, ff, phys, fe, P);
     if (rc) return rc;
     if ((rc = ats_spectrum_enqueue(h, P, e_amps, 0.0, 0.0, 0.0, phys, E))) return rc;
@@ -2078,6 +2131,7 @@ int tsff_angular_fit(tsff_handle* h, const tsff_angular_spec* sp, double* leaves
       TSFF_LAUNCH0(h, k_sph_vjp, dim3(1), dim3(kThreads), 0, h->stream, SG, theta, (int)sp->n_gen, cvjp, ln10, (const double*)gfe,
                    ws + o_sph, grad + sp->n_active);
     TSFF_HIP(h, hipGetLastError());
+    if (arb1v && (rc = arb1v_adjoint(h, nv, sp->dvx, gen_data, (const double*)gfe, ws + o_sph, grad + sp->n_active))) return rc;
     const double count = (double)epoch + 1;
     const double c1 = 1.0 - std::pow(b1, count), c2 = 1.0 - std::pow(b2, count);
     TSFF_LAUNCH0(h, k_ang_opt, dim3(1), dim3(kThreads), 0, h->stream, (const double*)lossv, (const double*)grad, act, (int)sp->n_active,

@@ -14,6 +14,7 @@
 //   k_lbfgs_step   loops.py:20-56        : one evaluation's step of unbounded L-BFGS-B on the packed loss and gradient (tsff_lbfgs_fit)
 //   k_ang_*        loops.py:167-275      : the angular fit's generator, loss and seed, chain rule and optimiser step (tsff_angular_fit)
 //   k_sph_*        spherical_harmonics.py: the SphericalHarmonics f_e generator and its exact adjoint (tsff_sph_table(_vjp), TSFF_ANG_SPH)
+//   k_arb1v_*      base.py:157-204       : the free-form 1-D f_e generator (Arbitrary1V) and its adjoint (tsff_arb1v_table(_vjp), TSFF_ANG_ARB1V)
 #include "tsff_device.h"
 
 namespace tsff {
@@ -102,6 +103,7 @@ constexpr int kFusedMaxIon = 2;  // k_spectrum_fused is instantiated for n_ion <
 #include "k_lbfgs.inc"
 #include "k_angular.inc"
 #include "k_sph.inc"
+#include "k_arb1v.inc"
 
 }  // namespace tsff
 

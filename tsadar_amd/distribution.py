@@ -511,6 +511,13 @@ def butterworth_matrix(n: int, f_sampling: float = 100.0, f_cutoff: float = 6.0)
     return S
 
 
+def arb1v_gen_data(nvx: int) -> np.ndarray:
+    """``gen_data`` of the device Arbitrary1V generator (tsff_arb1v_table, tsff_arb1v_table_vjp, TSFF_ANG_ARB1V): S [nvx, nvx] then
+    S^T [nvx, nvx], row-major float64 [2 nvx^2] -- the adjoint reads the stored transpose along rows, as the forward reads S."""
+    S = butterworth_matrix(int(nvx))
+    return np.concatenate([S.ravel(), S.T.ravel()])
+
+
 def arbitrary_1v_init(m: float, nvx: int) -> np.ndarray:
     """Arbitrary1V.init_dlm (base.py:188-196): fval of a super-Gaussian of order m (v_th = 1 here)."""
     vx = velocity_grid(nvx)

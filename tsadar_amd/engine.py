@@ -698,7 +698,9 @@ class Engine:
         -> (leaves, state = (moments, best, ctl), loss_hist [n_epochs] or None, best_hist [n_epochs, NP] (NaN rows: no best yet)
         or None) as CUDA tensors.  Generator ANG_SPH (a trained SphericalHarmonics): ``spec`` also carries sph_type, n_harm, nvr
         and n_gen (the ``meta`` of distribution.sph_gen_data, whose array is ``data["gen_data"]``), ``leaves`` is
-        [NP | get_params()] and the rows of best_hist are NP + n_gen wide;
+        [NP | get_params()] and the rows of best_hist are NP + n_gen wide.  Generator ANG_ARB1V (a trained free-form 1-D f_e):
+        ``data["gen_data"]`` is distribution.arb1v_gen_data(nv), ``leaves`` is [NP | fval[nv]] and the rows of best_hist are
+        NP + nv wide;
         ``leaves`` and ``state`` are updated in place when they are CUDA tensors already (pass the returned ones to the next
         chunk, with ``epoch0`` the epochs done so far).  ``state=None`` starts a fit: zero moments, best = [100 | leaves]
         (angular_optax's best_loss = 100.0), ctl zeros."""
@@ -714,7 +716,7 @@ class Engine:
         mom, best, ctl = state
         assert mom.numel() == (2 if adam else 1) * n and best.numel() == 1 + x.numel() and ctl.dtype == torch.int32
         hist = torch.empty(max(int(n_epochs), 0), dtype=torch.float64, device=self.device) if loss_hist else None
-        n_hist = self.NP + (int(spec["n_gen"]) if int(spec["generator"]) == L.ANG_SPH else 0)
+        n_hist = self.NP + {L.ANG_SPH: int(spec.get("n_gen", 0)), L.ANG_ARB1V: int(spec["nv"])}.get(int(spec["generator"]), 0)
         bh = torch.full((max(int(n_epochs), 0), n_hist), float("nan"), dtype=torch.float64, device=self.device) if best_hist else None
         c = L.TsffAngularSpec()
         c.generator, c.nv, c.learn_log = int(spec["generator"]), int(spec["nv"]), int(bool(spec.get("learn_log", False)))
@@ -762,6 +764,36 @@ class Engine:
         self._sync_stream()
         rc = self.lib.tsff_sph_table_vjp(self.h, *self._sph_args(meta, 12.0 / nv if dvx is None else dvx), self._ptr(th),
                                          self._ptr(gd), self._ptr(fb), self._ptr(g))
+        L.check(self.lib, self.h, rc)
+        return g
+
+    def arb1v_table(self, fval, gen_data, dvx=None, out=None):
+        """tsff_arb1v_table: the free-form 1-D generator (Arbitrary1V, distribution.arbitrary_1v) on the device, ``fval`` [nv] ->
+        f_e [nv] (CUDA tensor; nothing is synchronised).  ``gen_data``: distribution.arb1v_gen_data(nv); ``dvx``: vx[1] - vx[0]
+        (default: the reference's grid, 12 / nv)."""
+        torch = self.torch
+        fv, gd = self.dev(fval).reshape(-1), self.dev(gen_data).reshape(-1)
+        nv = int(fv.numel())
+        assert gd.numel() == 2 * nv * nv, "gen_data: S | S^T of the size of fval"
+        fe = out if out is not None else torch.empty(nv, dtype=torch.float64, device=self.device)
+        assert fe.numel() == nv
+        self._sync_stream()
+        rc = self.lib.tsff_arb1v_table(self.h, nv, float(12.0 / nv if dvx is None else dvx), self._ptr(fv), self._ptr(gd), self._ptr(fe))
+        L.check(self.lib, self.h, rc)
+        return fe
+
+    def arb1v_table_vjp(self, fval, gen_data, fe_bar, dvx=None, out=None):
+        """tsff_arb1v_table_vjp: ``fe_bar`` [nv] = d loss / d f_e -> d loss / d fval [nv] (CUDA tensor; nothing is synchronised),
+        the chain of distribution.arbitrary_1v_vjp, bit-reproducible from run to run.  Arguments as :meth:`arb1v_table`."""
+        torch = self.torch
+        fv, gd, fb = self.dev(fval).reshape(-1), self.dev(gen_data).reshape(-1), self.dev(fe_bar).reshape(-1)
+        nv = int(fv.numel())
+        assert gd.numel() == 2 * nv * nv and fb.numel() == nv
+        g = out if out is not None else torch.empty(nv, dtype=torch.float64, device=self.device)
+        assert g.numel() == nv
+        self._sync_stream()
+        rc = self.lib.tsff_arb1v_table_vjp(self.h, nv, float(12.0 / nv if dvx is None else dvx), self._ptr(fv), self._ptr(gd),
+                                           self._ptr(fb), self._ptr(g))
         L.check(self.lib, self.h, rc)
         return g
 

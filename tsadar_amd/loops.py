@@ -161,9 +161,15 @@ def angular_loop(config: Dict, all_data: Dict, sa: Dict, chunk: Optional[int] = 
     then the generator's parameters, and each saved state carries the best iterate's radial functions under
     ``["electron"]["flm"]`` (the reference's layout).  The default refuses such a deck, as before.
 
+    ``train_generator=True`` also runs a trained free-form 1-D f_e (``fe: {dim: 1, type: arbitrary, active: true}``, the
+    reference's Arbitrary1V): f_e is built from ``fval`` every epoch and d loss / d f_e is chained to it on the device
+    (k_arb1v.inc; the chain of ``distribution.arbitrary_1v_vjp``).  ``best_weights.fval`` is the best iterate's,
+    ``info["leaves"]`` the scalars then fval, and each saved state's ``["electron"]["f"]`` is the f_e of that epoch's best fval.
+
     Not built (NotImplementedError, raised before any device work): methods other than adam and rmsprop, multiplexed decks
     (``shotnum`` a list), ``distributed=True``, trainable SphericalHarmonics generators without ``train_generator`` or of
-    ``flm_type`` "nn", 1-D decks other than DLM1V."""
+    ``flm_type`` "nn", 1-D decks other than DLM1V and, with ``train_generator``, a trained free-form f_e (a free-form 1-D f_e
+    that is not trained stays refused)."""
     from . import _lib as L
     from . import distribution as Dist
     from .loss_function import LossFunction
@@ -187,8 +193,12 @@ def angular_loop(config: Dict, all_data: Dict, sa: Dict, chunk: Optional[int] = 
             raise NotImplementedError(f"angular_loop: train_generator with flm_type {flm_type!r} -- only mora-yahi and arbitrary "
                                       "radial functions are built on the device; flm_type nn stays on the host (the loop over "
                                       "LossFunction.vg_loss)")
-    if dim == 1 and str(fecfg.get("type", "dlm")).casefold() != "dlm":
+    arb1v = train_generator and dim == 1 and str(fecfg.get("type", "dlm")).casefold() == "arbitrary"
+    if dim == 1 and str(fecfg.get("type", "dlm")).casefold() != "dlm" and not arb1v:
         raise NotImplementedError(f"angular_loop: 1-D f_e of type {fecfg.get('type')!r} -- only DLM1V is built")
+    if arb1v and not fecfg.get("active", False):
+        raise NotImplementedError("angular_loop: a free-form 1-D f_e that is not trained (a constant table) is not built on the "
+                                  "device (use the host loop over LossFunction.vg_loss)")
 
     # loops.py:197-227, as written
     config["optimizer"]["batch_size"] = 1
@@ -201,7 +211,7 @@ def angular_loop(config: Dict, all_data: Dict, sa: Dict, chunk: Optional[int] = 
     loss_fn = LossFunction(config, sa, batch1)
     ts_params = ThomsonParams(config["parameters"], num_params=1, batch=False, activate=True)
     sm = ts_params.slots
-    if (sm.gen2d_active and not train_generator) or ts_params.fval is not None or (dim == 1 and not sm.has_m):
+    if (sm.gen2d_active and not train_generator) or ((ts_params.fval is not None or (dim == 1 and not sm.has_m)) and not arb1v):
         raise NotImplementedError("angular_loop: this distribution function is not built on the device")
     diff, _ = tree.partition(ts_params, tree.get_filter_spec(config["parameters"], ts_params))
     act = [s for _, s in diff.slots if s >= 0]
@@ -224,7 +234,11 @@ def angular_loop(config: Dict, all_data: Dict, sa: Dict, chunk: Optional[int] = 
         spec.update(method=L.ANG_ADAM, b1=ADAM_B1, b2=ADAM_B2, eps=ADAM_EPS)
     else:
         spec.update(method=L.ANG_RMSPROP, decay=RMSPROP_DECAY, eps=RMSPROP_EPS)
-    if dim == 1:
+    if arb1v:
+        spec["generator"] = L.ANG_ARB1V
+        gen_data = Dist.arb1v_gen_data(nvx)
+        leaves = np.concatenate([leaves, ts_params.fval.ravel()])
+    elif dim == 1:
         spec["generator"] = L.ANG_DLM
         gen_data = np.concatenate([Dist.dlm_table(nvx).ravel(), Dist.M_AXIS])
     else:
@@ -279,6 +293,8 @@ def angular_loop(config: Dict, all_data: Dict, sa: Dict, chunk: Optional[int] = 
             if i % freq == 0 and not np.isnan(bh[i, 0]):
                 snap = ts_params.copy()
                 snap.X[0] = bh[i, : eng.NP]
+                if arb1v:
+                    snap.fval = bh[i, eng.NP :].reshape(ts_params.fval.shape).copy()
                 states[i] = snap.get_unnormed_params()
                 if train_gen:
                     snap.sph.set_params(bh[i, eng.NP :])
@@ -292,4 +308,6 @@ def angular_loop(config: Dict, all_data: Dict, sa: Dict, chunk: Optional[int] = 
         best_weights.fval2d = best[1 + eng.NP :].reshape(ts_params.fval2d.shape).copy()
     if train_gen:
         best_weights.sph.set_params(best[1 + eng.NP :])
+    if arb1v:
+        best_weights.fval = best[1 + eng.NP :].reshape(ts_params.fval.shape).copy()
     return best_weights, epoch_loss, loss_fn
