@@ -398,40 +398,47 @@ int tsff_lbfgs_fit(tsff_handle *h, double *params, const double *fe, const doubl
  * allocated, and the handle's scratch is sized before the first launch: no epoch allocates, and nothing synchronises.  Needs
  * fe_mode == TSFF_FE_PER_LINEOUT and tsff_ats_setup.
  *   spec (HOST): the deck and the optimiser, below;
- *   leaves (device [NP + nv^2 for TSFF_ANG_ARB2V, NP + nv for TSFF_ANG_ARB1V], in/out): the normalised leaves of the one plasma condition, then fval;
- *   gen_data (device): TSFF_ANG_DLM [nv][31] DLM table | [31] m axis (tsadar_amd.distribution.dlm_table, M_AXIS);
- *   TSFF_ANG_TABLE2D the constant table [nv][nv]; TSFF_ANG_ARB2V unused; TSFF_ANG_SPH: the generator's constants, below;
+ *   leaves (device [NP + n_table], in/out): the normalised leaves of the one plasma condition, then the generator's;
+ *   gen_data (device): the generator's constants, by generator below;
  *   e_data, noise_e (device [rows][nJ]), wcol (device [nJ]: blue / red masks over rows x mask count, halved when both are
  *   fitted), e_amps (device [rows]);
- *   moments (device [2 n] Adam (mu | nu), [n] RMSProp, n = n_active + nv^2 for ARB2V, else n_active; in/out): the active
- *   scalar slots in the order of active_slots, then the table;
- *   best (device [1 + NP + nv^2 for ARB2V], in/out): [best loss | the leaves after the update of the best epoch]; start at 100;
+ *   moments (device [2 n] Adam (mu | nu), [n] RMSProp, n = n_active + n_table; in/out): the active scalar slots in the order
+ *   of active_slots, then the generator's leaves;
+ *   best (device [1 + NP + n_table], in/out): [best loss | the leaves after the update of the best epoch]; start at 100;
  *   ctl (device int32 [8], in/out, zeros to start): [0] status (0 running, 1 ended: later epochs change nothing), [1] the
  *   epoch the fit ended after, [2] g_wait, [3] b_wait (the reference's counters), [4] 1 once a best exists;
  *   loss_hist (device [n_epochs] or NULL): each epoch's loss (NaN after the end);
- *   best_hist (device [n_epochs][NP] or NULL): the best scalar leaves after each epoch (save_state), untouched while none exists.
- * TSFF_ANG_SPH (a trained SphericalHarmonics generator, k_sph.inc) widens the layouts by its n_gen parameters, in the order of
- * SphericalHarmonics.get_params() (per harmonic (l, m), sorted: log_10_LT for TSFF_SPH_MORA_YAHI, flm_sign[nvr] then flm_mag[nvr]
- * for TSFF_SPH_ARBITRARY; then normed_m): leaves [NP | n_gen], moments over n_active + n_gen, best [1 + NP + n_gen], best_hist rows
- * of NP + n_gen.  Its gen_data holds everything that does not depend on the trained parameters (doubles, integers stored as
+ *   best_hist (device [n_epochs][NP + tail] or NULL): the best leaves after each epoch (save_state), untouched while none exists.
+ * The generators (spec.generator; nv = spec.nv, n_gen = spec.n_gen):
+ *   generator         f_e      n_table  f_e built by                       chained back by                       adjoint returns  tail   m a   gen_data
+ *                                                                                                                d loss / d f_e          leaf
+ *   TSFF_ANG_TABLE2D  [nv][nv] 0        nothing: gen_data is the table     nothing                               no               0      no    the table [nv][nv]
+ *   TSFF_ANG_DLM      [nv]     0        k_ang_leaves                       k_ang_chain (dot with d f_e / d m)    when m is a leaf 0      yes   [nv][31] DLM table | [31] m axis
+ *   TSFF_ANG_ARB2V    [nv][nv] nv^2     k_ang_leaves                       k_ang_chain (the Arbitrary2V VJP)     yes              0      no    unused (may be NULL)
+ *   TSFF_ANG_SPH      [nv][nv] n_gen    k_ang_leaves, k_sph_table          k_ang_chain, k_sph_vjp                yes              n_gen  no    the constants below
+ *   TSFF_ANG_ARB1V    [nv]     nv       k_ang_leaves, k_arb1v_matvec,      k_ang_chain, k_arb1v_point,           yes              nv     no    S[nv][nv] | S^T[nv][nv]
+ *                                       k_arb1v_point                      k_arb1v_matvec
+ * 1-D generators (f_e [nv]) need nv == the handle's nvx and run tsff_form_factor and its adjoint, 2-D ones (nv = 4 .. 256) the
+ * saving tsff_form_factor_2d and its adjoint from the saved records.  The scratch of k_sph.inc and k_arb1v.inc is part of the
+ * fit's.  TSFF_ANG_DLM: tsadar_amd.distribution.dlm_table, M_AXIS.
+ * TSFF_ANG_SPH (a trained SphericalHarmonics generator, k_sph.inc): its leaves are in the order of SphericalHarmonics.get_params()
+ * (per harmonic (l, m), sorted: log_10_LT for TSFF_SPH_MORA_YAHI, flm_sign[nvr] then flm_mag[nvr] for TSFF_SPH_ARBITRARY; then
+ * normed_m).  Its gen_data holds everything that does not depend on the trained parameters (doubles, integers stored as
  * doubles; n2 = nv^2, H = n_harm; tsadar_amd.distribution.sph_gen_data packs it):
  *   vr[nvr] | cell[n2] | wt[n2] | inside[n2] | Y[H][n2]       the radial axis; per grid point the radial cell, the weight in it and
  *                                                             1 inside the axis (np.interp), Re Y_l^m per harmonic and point;
  *   | M[nvr][nvr] | ptr[nvr + 1] | pt[2 n2] | cw[2 n2]        TSFF_SPH_ARBITRARY only: the smoothing matrix and, for the transposed
  *                                                             interpolation, per radial node k the grid points pt[e] and weights
  *                                                             cw[e] that reach it, e in [ptr[k], ptr[k + 1]) (unused tail: zeros).
- * TSFF_ANG_ARB1V (a trained free-form 1-D f_e, the reference's Arbitrary1V; k_arb1v.inc) follows the 1-D path with nv the handle's
- * nvx: f_e = normalise(10^-(7 S fval)^2) with S the constant forward-backward Butterworth matrix, built from the leaves every
- * epoch, and d loss / d f_e (the 1-D form-factor adjoint with its f_e tail) chained to fval exactly.  leaves [NP | fval[nv]],
- * moments over n_active + nv, best [1 + NP + nv], best_hist rows of NP + nv.  gen_data: S[nv][nv] | S^T[nv][nv], row-major
- * (tsadar_amd.distribution.arb1v_gen_data).  Four launches more per epoch than a DLM deck without m: S fval and the pointwise
- * kernel after k_ang_leaves, the pointwise adjoint and S^T g_u after k_ang_chain.  The spec gets no field of its own.
+ * TSFF_ANG_ARB1V (a trained free-form 1-D f_e, the reference's Arbitrary1V; k_arb1v.inc): f_e = normalise(10^-(7 S fval)^2) with S
+ * the constant forward-backward Butterworth matrix, row-major (tsadar_amd.distribution.arb1v_gen_data), and d loss / d f_e
+ * chained to fval exactly.  The spec has no field of its own for it.
  * Chunks: epoch0 = the epochs done so far (Adam's bias correction); a fit in chunks is bit for bit one call.
- * Refusals: a null pointer, a slot out of range or repeated -1, TSFF_P_M outside DLM decks -2, an ion's A slot -3, an unknown
- * generator, optimiser or loss method, nv outside 4 .. 256 for 2-D tables, too little LDS -2 (TSFF_ERR_LDS for the 1-D adjoint);
- * TSFF_ANG_SPH: an unknown radial type, n_harm != 2 for Mora-Yahi (l = 1 only) or outside 1 .. 64, nvr < 2, or n_gen other than
- * n_harm + 1 (Mora-Yahi) / 2 n_harm nvr + 1 (free radial functions) -2; TSFF_ANG_ARB1V: nv other than the handle's nvx -1,
- * TSFF_P_M among the active slots -2 (the deck has no DLM order). */
+ * Refusals, in this order: a null pointer -1; an unknown generator -2; a 1-D generator's nv other than the handle's nvx -1;
+ * nv outside 4 .. 256 for 2-D tables -2; gen_data missing -1; TSFF_ANG_SPH: an unknown radial type, n_harm != 2 for Mora-Yahi
+ * (l = 1 only) or outside 1 .. 64, nvr < 2, or n_gen other than n_harm + 1 (Mora-Yahi) / 2 n_harm nvr + 1 (free radial
+ * functions) -2; an unknown optimiser or loss method -2; a slot out of range or repeated -1, TSFF_P_M where m is no leaf -2, an
+ * ion's A slot -3; nothing to train -1; too little LDS -2 (TSFF_ERR_LDS for the 1-D adjoint). */
 enum { TSFF_ANG_TABLE2D = 0, TSFF_ANG_DLM = 1, TSFF_ANG_ARB2V = 2, TSFF_ANG_SPH = 3, TSFF_ANG_ARB1V = 4 };
 enum { TSFF_SPH_MORA_YAHI = 0, TSFF_SPH_ARBITRARY = 1 }; /* flm_type of a SphericalHarmonics generator */
 enum { TSFF_ANG_ADAM = 0, TSFF_ANG_RMSPROP = 1 };

@@ -12,6 +12,10 @@ import numpy as np
 import pytest
 
 import decks
+import test_arb1v_generator_device as arb1v_deck
+import test_sph_generator_device as sph_deck
+from tsadar_amd import _lib as L
+from util import _angular_sa, _device, _host_loop, _rel, _stage_records
 
 N_EPOCHS = 30
 ROWS = (10, 110)   # lineouts of the 128 x 256 CCD (as test_angular_optax_loop_like_reference)
@@ -82,6 +86,54 @@ def test_angular_loop_refuses_before_device_work():
     assert cfg["data"]["lineouts"]["start"] == ROWS[0] and c["data"]["lineouts"]["start"] == ROWS[0]
 
 
+def _fe_deck(dim, nvx, fe=None):
+    cfg = decks.deck_angular(dim, nvx, (128, 256), *ROWS)
+    if fe is not None:
+        cfg["parameters"]["electron"]["fe"] = copy.deepcopy(fe)
+    return cfg
+
+
+# kind -> (deck, generator, length of the leaves' tail, size of gen_data (the layout's for a trained SphericalHarmonics), the
+# spec fields the generator adds): the rows of tsff_angular_fit's table (include/tsff.h) for the decks of the GPU tests
+ANGLES = {"ud_angle", "va_angle"}
+SPH_META = {"sph_type", "n_harm", "nv", "nvr", "n_gen"}
+GENERATORS = {
+    "dlm": (lambda: _fe_deck(1, 64), L.ANG_DLM, 0, 64 * 31 + 31, set()),
+    "arb": (lambda: _fe_deck(2, 48), L.ANG_ARB2V, 48 * 48, None, ANGLES | {"learn_log"}),
+    "sph": (lambda: _fe_deck(2, 48, SPH_FE), L.ANG_TABLE2D, 0, 48 * 48, ANGLES),
+    "mora-yahi": (lambda: _fe_deck(2, 48, sph_deck._fe_cfg("mora-yahi", 48, 48)), L.ANG_SPH, 3, "layout", ANGLES | SPH_META),
+    "free": (lambda: _fe_deck(2, 48, sph_deck._fe_cfg("arbitrary", 48, 40)), L.ANG_SPH, 2 * 2 * 40 + 1, "layout", ANGLES | SPH_META),
+    "arb1v": (lambda: _fe_deck(1, arb1v_deck.NV, arb1v_deck.FE), L.ANG_ARB1V, arb1v_deck.NV, 2 * arb1v_deck.NV**2, set()),
+}
+
+
+@pytest.mark.parametrize("kind", list(GENERATORS))
+def test_generator_description(kind):
+    """loops._generator, without a device: the generator's code, the sizes of its leaves and constants, the spec fields it adds,
+    and the write-back of a perturbed tail, read again bit for bit."""
+    from tsadar_amd import ThomsonParams, loops
+    from tsadar_amd import distribution as Dist
+
+    deck, code, n_tail, n_data, keys = GENERATORS[kind]
+    cfg = deck()
+    tp = ThomsonParams(cfg["parameters"], num_params=1, batch=False, activate=True)
+    g = loops._generator(cfg, tp, True)
+    assert g.code == code and g.tail.shape == (n_tail,) and g.tail.dtype == np.float64
+    if n_data == "layout":
+        n_data = Dist.sph_gen_layout(*(g.spec[k] for k in ("sph_type", "n_harm", "nv", "nvr")))["size"]
+        assert g.spec["n_gen"] == n_tail and g.spec["nv"] == 48
+    assert (g.gen_data is None) if n_data is None else (g.gen_data.size == n_data and g.gen_data.dtype == np.float64)
+    assert set(g.spec) == keys, g.spec
+    other = tp.copy()
+    tail = g.tail + 0.01 * np.random.default_rng(1).standard_normal(n_tail)
+    g.write_back(other, tail)
+    assert np.array_equal(loops._generator(cfg, other, True).tail, tail)
+    assert np.array_equal(loops._generator(cfg, tp, True).tail, g.tail), "the write-back touched the original"
+    assert (set(g.state_extra(other)) == {"flm"}) if code == L.ANG_SPH else (g.state_extra(other) == {})
+    if code in (L.ANG_SPH, L.ANG_ARB1V):   # the two generators that train_generator switches on
+        assert loops._generator(cfg, tp, False) is None
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # GPU
 # ---------------------------------------------------------------------------------------------------------------------
@@ -91,16 +143,6 @@ def torch_mod():
 
     assert torch.cuda.is_available(), "gpu tests need a HIP device"
     return torch
-
-
-def _angular_sa(cfg):
-    from tsadar_amd import calibration
-
-    cfg["other"]["extraoptions"]["spectype"] = "angular"
-    sa = calibration.get_scattering_angles(cfg)
-    cfg["other"]["extraoptions"]["spectype"] = "angular_full"
-    sa["angAxis"] = calibration.angular_pixel_axis()
-    return sa
 
 
 def _case(kind, method, lr=0.002, n_epochs=N_EPOCHS, noise=0.0, offset=0.0, loss_method="l2", truth_start=False, noise_e=0.0):
@@ -148,72 +190,9 @@ def _case(kind, method, lr=0.002, n_epochs=N_EPOCHS, noise=0.0, offset=0.0, loss
     return cfg, all_data, sa
 
 
-def _host_loop(config, all_data, sa):
-    """The reference's loop body (loops.py:197-270) over LossFunction.vg_loss with tree.Adam / tree.RMSProp."""
-    from tsadar_amd import ThomsonParams, tree
-    from tsadar_amd.loss_function import LossFunction
-
-    config = copy.deepcopy(config)
-    config["optimizer"]["batch_size"] = 1
-    lo = config["data"]["lineouts"]
-    lo["start"] = int(lo["start"] / config["other"]["ang_res_unit"])
-    lo["end"] = int(lo["end"] / config["other"]["ang_res_unit"])
-    a, b = lo["start"], lo["end"]
-    batch1 = {"e_data": all_data["e_data"][a:b, :], "e_amps": all_data["e_amps"][a:b, :], "i_data": all_data["i_data"],
-              "i_amps": all_data["i_amps"], "noise_e": all_data["noiseE"][a:b, :], "noise_i": all_data["noiseI"][a:b, :]}
-    loss_fn = LossFunction(config, sa, batch1)
-    opt = config["optimizer"]
-    solver = (tree.Adam if opt["method"] == "adam" else tree.RMSProp)(opt["learning_rate"])
-    ts_params = ThomsonParams(config["parameters"], num_params=1, batch=False, activate=True)
-    diff_params, static_params = tree.partition(ts_params, tree.get_filter_spec(config["parameters"], ts_params))
-    opt_state = solver.init(diff_params)
-    best_weights, epoch_loss, best_loss, num_g_wait, num_b_wait = {}, 0.0, 100.0, 0, 0
-    losses, states, stopped = [], {}, None
-    for i_epoch in range(opt["num_epochs"]):
-        (val, aux), grad = loss_fn.vg_loss(diff_params, static_params, batch1)
-        updates, opt_state = solver.update(grad, opt_state)
-        diff_params = tree.apply_updates(diff_params, updates)
-        epoch_loss = val
-        losses.append(val)
-        if epoch_loss < best_loss:
-            if best_loss - epoch_loss < 0.000001:
-                best_loss = epoch_loss
-                best_weights = tree.combine(diff_params, static_params)
-                num_g_wait += 1
-                if num_g_wait > 5:
-                    stopped = i_epoch
-                    break
-            elif epoch_loss > best_loss:
-                num_b_wait += 1
-                if num_b_wait > 5:
-                    break
-            else:
-                best_loss = epoch_loss
-                best_weights = tree.combine(diff_params, static_params)
-                num_b_wait = 0
-                num_g_wait = 0
-        if opt["save_state"] and i_epoch % opt["save_state_freq"] == 0 and best_weights != {}:
-            states[i_epoch] = best_weights.get_unnormed_params()
-    final = tree.combine(diff_params, static_params)
-    return dict(best=best_weights, epoch_loss=epoch_loss, losses=np.array(losses), states=states, stopped=stopped, final=final)
-
-
 def _leaves(tp):
     v = tp.X[0]
     return np.concatenate([v, tp.fval2d.ravel()]) if getattr(tp, "fval2d", None) is not None and tp.slots.fval2d_active else v
-
-
-def _rel(a, b, floor=0.0):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return float(np.max(np.abs(a - b) / np.maximum(np.abs(b), max(floor, 1e-300)))) if a.size else 0.0
-
-
-def _device(cfg, all_data, sa, **kw):
-    from tsadar_amd import loops
-
-    info = {}
-    best, epoch_loss, loss_fn = loops.angular_loop(copy.deepcopy(cfg), all_data, sa, info=info, **kw)
-    return best, epoch_loss, loss_fn, info
 
 
 @pytest.mark.gpu
@@ -305,60 +284,56 @@ def test_angular_loop_chunks_are_bit_identical(torch_mod):
         assert np.array_equal(best.X, runs[0][0].X) and epoch_loss == runs[0][1]
 
 
-def _stage_records(eng, cfg, two_d):
-    """The launch records of the entry points an epoch is made of, called one by one at the fit's shapes (one lineout, all its
-    points; the table adjoint / the f_e adjoint as the fit of these decks asks for them)."""
-    from tsadar_amd import ThomsonParams
-    from tsadar_amd import _lib as L
-
-    torch = eng.torch
-    tp = ThomsonParams(cfg["parameters"], 1, batch=False, activate=True)
-    phys = tp.physical_matrix()
-    p, gen, rows = phys[0], cfg["parameters"]["general"], eng._ats_shape[0]
-    fe = np.ascontiguousarray(tp()["electron"]["fe"], dtype=np.float64)
-    if two_d:
-        fe = eng.dev(fe)
-        P = eng.form_factor_2d(0, phys, fe, gen["ud"]["angle"], gen["Va"]["angle"], save=True)
-    else:
-        fe = fe.reshape(1, -1)
-        P = eng.form_factor(0, phys, fe)
-    rec = [eng.last_launch()]
-    E = eng.ats_spectrum(P[0], np.ones(rows), p[L.P_LAM], p[L.P_AMP1], p[L.P_AMP2])
-    rec.append(eng.last_launch())
-    Pbar, _ = eng.ats_adjoint(P[0], np.ones(rows), p[L.P_LAM], p[L.P_AMP1], p[L.P_AMP2], torch.ones_like(E))
-    rec.append(eng.last_launch())
-    if two_d:
-        eng.form_factor_2d_grad(0, phys, fe, Pbar.reshape(P.shape), gen["ud"]["angle"], gen["Va"]["angle"], want_table=True, use_saved=True)
-    else:
-        eng.form_factor_grad(0, phys, fe, Pbar.reshape(P.shape), want_fe=True)
-    rec.append(eng.last_launch())
-    torch.cuda.synchronize()
-    return rec
-
-
-def _assert_epoch_is_its_entry_points(eng, cfg, per, two_d):
-    """one epoch's record = k_ang_leaves, the form factor, the ATS chain, the loss, the ATS adjoint, the form-factor adjoint,
-    the chain rule and the optimiser: the loop enqueues what the stand-alone entry points enqueue"""
-    fwd, spec, adj, grad = _stage_records(eng, cfg, two_d)
-    assert all(len(r) > 0 for r in (fwd, spec, adj, grad))
-    assert per[0].startswith("k_ang_leaves<") and per[-2].startswith("k_ang_chain<") and per[-1] == "k_ang_opt"
-    assert per[1:-2] == fwd + spec + ["k_ang_loss", "k_ang_loss_sum"] + adj + grad, (per, fwd, spec, adj, grad)
+# kind -> (the generator's kernels after k_ang_leaves, its kernels after k_ang_chain): TABLE2D, DLM, ARB2V, SPH, ARB1V
+LAUNCHES = {"sph": ([], []), "dlm": ([], []), "arb": ([], []), "sphtrain": (["k_sph_table"], ["k_sph_vjp"]),
+            "arb1v": (["k_arb1v_matvec", "k_arb1v_point"], ["k_arb1v_point", "k_arb1v_matvec"])}
 
 
 @pytest.mark.gpu
-def test_angular_fit_launch_record(torch_mod):
+@pytest.mark.parametrize("kind", list(LAUNCHES))
+def test_angular_fit_launch_record(torch_mod, monkeypatch, kind):
+    """One epoch's record = k_ang_leaves, the generator's forward kernels, then what the stand-alone entry points enqueue (form
+    factor, ATS chain, loss, ATS adjoint, form-factor adjoint), k_ang_chain, the generator's adjoint kernels and k_ang_opt --
+    the same list every epoch (arb1v: with the timing ring on as without)."""
     from tsadar_amd import _lib as L
+    from tsadar_amd.engine import Engine
 
-    cfg, all_data, sa = _case("arb", "rmsprop", n_epochs=3)
-    _, _, loss_fn, _ = _device(cfg, all_data, sa, chunk=3)
+    gen_fwd, gen_adj = LAUNCHES[kind]
+    two_d = kind not in ("dlm", "arb1v")
+    if kind == "sphtrain":
+        cfg, all_data, sa = sph_deck._case("mora-yahi", "rmsprop", n_epochs=3)
+    elif kind == "arb1v":
+        cfg, all_data, sa = arb1v_deck._case("rmsprop", arb1v_deck.LR["rmsprop"])
+        cfg = copy.deepcopy(cfg)
+        cfg["optimizer"]["num_epochs"] = 3
+        fit = Engine.angular_fit
+
+        def timed(self, *a, **kw):
+            self.enable_timing(64)
+            return fit(self, *a, **kw)
+
+        monkeypatch.setattr(Engine, "angular_fit", timed)
+    else:
+        cfg, all_data, sa = _case(kind, "rmsprop" if kind == "arb" else "adam", n_epochs=3)
+    _, _, loss_fn, _ = _device(cfg, all_data, sa, chunk=3, train_generator=kind in ("sphtrain", "arb1v"))
+    monkeypatch.undo()
     eng = loss_fn.ts_diag.engine(True)
     rec = eng.last_launch()
     assert len(rec) % 3 == 0 and rec[0].startswith("k_ang_leaves<")
     per = rec[: len(rec) // 3]
     assert rec == per * 3, rec
+    fwd, spec, adj, grad = _stage_records(eng, cfg, two_d, want_gfe=kind != "sph")
+    assert all(len(r) > 0 for r in (fwd, spec, adj, grad))
+    nf, na = len(gen_fwd), len(gen_adj)
+    assert per[0].startswith("k_ang_leaves<") and per[1 : 1 + nf] == gen_fwd, per
+    assert per[1 + nf : -2 - na] == fwd + spec + ["k_ang_loss", "k_ang_loss_sum"] + adj + grad, (per, fwd, spec, adj, grad)
+    assert per[-2 - na].startswith("k_ang_chain<") and per[-1 - na :] == gen_adj + ["k_ang_opt"], per
+    if not two_d:   # the 1-D decks (m a leaf, or fval trained): the adjoint with its f_e tail
+        assert any(r.startswith("k_form_factor<") for r in per) and "k_fe_adjoint" in per and "k_fe_adjoint" in grad, per
+    if kind != "arb":
+        return
     for k in ("k_form_factor_2d<", "k_ats_resunit", "k_ang_loss", "k_ats_resunit_adj", "k_form_factor_2d_adj<", "k_ang_chain<", "k_ang_opt"):
         assert any(r.startswith(k) for r in per), (k, per)
-    _assert_epoch_is_its_entry_points(eng, cfg, per, True)
     # a refused call enqueues nothing
     x = eng.dev(np.zeros(eng.NP))
     spec = dict(generator=L.ANG_DLM, nv=48, active_slots=[L.P_TE, L.P_TE], loss_method=0, un=1.0, dvx=0.25, method=L.ANG_ADAM,
@@ -368,13 +343,6 @@ def test_angular_fit_launch_record(torch_mod):
     with pytest.raises(L.TsffError):
         eng.angular_fit(x, spec, data, 4)
     assert eng.last_launch() == []
-    # the 1-D deck (m a leaf: the adjoint with its f_e tail)
-    cfg, all_data, sa = _case("dlm", "adam", n_epochs=1)
-    _, _, loss_fn, _ = _device(cfg, all_data, sa)
-    eng = loss_fn.ts_diag.engine(True)
-    per = eng.last_launch()
-    assert any(r.startswith("k_form_factor<") for r in per) and "k_fe_adjoint" in per, per
-    _assert_epoch_is_its_entry_points(eng, cfg, per, False)
 
 
 @pytest.mark.gpu

@@ -16,9 +16,11 @@ import numpy as np
 import pytest
 
 import decks
-from test_angular_loop_device import ROWS, _angular_sa, _host_loop, _rel, _stage_records
+import util
+from util import _angular_sa, _host_loop, _rel
 
 N_EPOCHS = 30
+ROWS = (10, 110)   # lineouts of the 128 x 256 CCD (as tests/test_angular_loop_device.py)
 NV = 64
 FE = {"active": True, "type": "arbitrary", "dim": 1, "nvx": NV, "params": {"init_m": 2.5}}
 SIZES = (8, 50, 64, 256, 320)   # less than a wavefront, no multiple of 64, one wavefront, 64 workgroups, more rows than 256
@@ -201,12 +203,7 @@ def _leaves(tp):
     return np.concatenate([tp.X[0], tp.fval.ravel()])
 
 
-def _device(cfg, all_data, sa, **kw):
-    from tsadar_amd import loops
-
-    info = {}
-    best, epoch_loss, loss_fn = loops.angular_loop(copy.deepcopy(cfg), all_data, sa, info=info, train_generator=True, **kw)
-    return best, epoch_loss, loss_fn, info
+_device = functools.partial(util._device, train_generator=True)
 
 
 @pytest.mark.gpu
@@ -269,37 +266,6 @@ def test_saved_states_carry_the_best_fe(torch_mod):
                 if k != "f":
                     assert _rel(s[sp][k], h[sp][k]) < 1e-8, (i, sp, k)
     assert len(fs) < 2 or not np.array_equal(fs[0], fs[-1]), "every state carries the same f_e"
-
-
-@pytest.mark.gpu
-def test_launch_record(torch_mod, monkeypatch):
-    """An epoch is k_ang_leaves, S fval and the pointwise kernel, then what the stand-alone entry points enqueue (form factor,
-    ATS chain, loss, ATS adjoint, form-factor adjoint with its f_e tail), k_ang_chain, the pointwise adjoint and S^T g_u, and
-    k_ang_opt -- the same list every epoch, with the timing ring on as without."""
-    from tsadar_amd.engine import Engine
-
-    cfg, all_data, sa = _case("rmsprop", LR["rmsprop"])
-    cfg = copy.deepcopy(cfg)
-    cfg["optimizer"]["num_epochs"] = 3
-    fit = Engine.angular_fit
-
-    def timed(self, *a, **kw):
-        self.enable_timing(64)
-        return fit(self, *a, **kw)
-
-    monkeypatch.setattr(Engine, "angular_fit", timed)
-    _, _, loss_fn, _ = _device(cfg, all_data, sa, chunk=3)
-    monkeypatch.setattr(Engine, "angular_fit", fit)
-    eng = loss_fn.ts_diag.engine(True)
-    rec = eng.last_launch()
-    assert len(rec) % 3 == 0
-    per = rec[: len(rec) // 3]
-    assert rec == per * 3, rec
-    fwd, spec, adj, grad = _stage_records(eng, cfg, False)
-    assert all(len(r) > 0 for r in (fwd, spec, adj, grad)) and "k_fe_adjoint" in grad
-    assert per[0].startswith("k_ang_leaves<") and per[1:3] == ["k_arb1v_matvec", "k_arb1v_point"]
-    assert per[3:-4] == fwd + spec + ["k_ang_loss", "k_ang_loss_sum"] + adj + grad, (per, fwd, spec, adj, grad)
-    assert per[-4].startswith("k_ang_chain<") and per[-3:] == ["k_arb1v_point", "k_arb1v_matvec", "k_ang_opt"]
 
 
 @pytest.mark.gpu

@@ -12,12 +12,15 @@ so only an exact adjoint passes.  Loop: the project's own bounds for the angular
 1e-8 on the final and best leaves, against the host loop with ``SphericalHarmonics.vjp`` replaced by the twin's autograd (both
 sides then take exact gradients)."""
 import copy
+import functools
 import inspect
 
 import numpy as np
 import pytest
 
 import decks
+import util
+from util import _angular_sa, _host_loop, _rel
 
 N_EPOCHS = 30
 ROWS = (10, 110)   # lineouts of the 128 x 256 CCD (as tests/test_angular_loop_device.py)
@@ -266,16 +269,6 @@ def torch_mod():
     return torch
 
 
-def _angular_sa(cfg):
-    from tsadar_amd import calibration
-
-    cfg["other"]["extraoptions"]["spectype"] = "angular"
-    sa = calibration.get_scattering_angles(cfg)
-    cfg["other"]["extraoptions"]["spectype"] = "angular_full"
-    sa["angAxis"] = calibration.angular_pixel_axis()
-    return sa
-
-
 @pytest.fixture(scope="module")
 def eng(torch_mod):
     """One engine for the stand-alone generator calls (they use the handle's stream and scratch only)."""
@@ -386,73 +379,11 @@ def _case(flm_type, method, n_epochs=N_EPOCHS):
     return cfg, all_data, sa
 
 
-def _host_loop(config, all_data, sa):
-    """The reference's loop body (loops.py:197-270) over LossFunction.vg_loss with tree.Adam / tree.RMSProp (the restatement
-    of tests/test_angular_loop_device.py; a saved state also carries the generator's radial functions, as the reference's)."""
-    from tsadar_amd import ThomsonParams, tree
-    from tsadar_amd.loss_function import LossFunction
-
-    config = copy.deepcopy(config)
-    config["optimizer"]["batch_size"] = 1
-    lo = config["data"]["lineouts"]
-    lo["start"] = int(lo["start"] / config["other"]["ang_res_unit"])
-    lo["end"] = int(lo["end"] / config["other"]["ang_res_unit"])
-    a, b = lo["start"], lo["end"]
-    batch1 = {"e_data": all_data["e_data"][a:b, :], "e_amps": all_data["e_amps"][a:b, :], "i_data": all_data["i_data"],
-              "i_amps": all_data["i_amps"], "noise_e": all_data["noiseE"][a:b, :], "noise_i": all_data["noiseI"][a:b, :]}
-    loss_fn = LossFunction(config, sa, batch1)
-    opt = config["optimizer"]
-    solver = (tree.Adam if opt["method"] == "adam" else tree.RMSProp)(opt["learning_rate"])
-    ts_params = ThomsonParams(config["parameters"], num_params=1, batch=False, activate=True)
-    diff_params, static_params = tree.partition(ts_params, tree.get_filter_spec(config["parameters"], ts_params))
-    opt_state = solver.init(diff_params)
-    best_weights, epoch_loss, best_loss, num_g_wait, num_b_wait = {}, 0.0, 100.0, 0, 0
-    losses, states, stopped = [], {}, None
-    for i_epoch in range(opt["num_epochs"]):
-        (val, aux), grad = loss_fn.vg_loss(diff_params, static_params, batch1)
-        updates, opt_state = solver.update(grad, opt_state)
-        diff_params = tree.apply_updates(diff_params, updates)
-        epoch_loss = val
-        losses.append(val)
-        if epoch_loss < best_loss:
-            if best_loss - epoch_loss < 0.000001:
-                best_loss = epoch_loss
-                best_weights = tree.combine(diff_params, static_params)
-                num_g_wait += 1
-                if num_g_wait > 5:
-                    stopped = i_epoch
-                    break
-            elif epoch_loss > best_loss:
-                num_b_wait += 1
-                if num_b_wait > 5:
-                    break
-            else:
-                best_loss = epoch_loss
-                best_weights = tree.combine(diff_params, static_params)
-                num_b_wait = 0
-                num_g_wait = 0
-        if opt["save_state"] and i_epoch % opt["save_state_freq"] == 0 and best_weights != {}:
-            states[i_epoch] = best_weights.get_unnormed_params()
-            states[i_epoch]["electron"]["flm"] = best_weights.sph.get_unnormed_params()["flm"]
-    final = tree.combine(diff_params, static_params)
-    return dict(best=best_weights, epoch_loss=epoch_loss, losses=np.array(losses), states=states, stopped=stopped, final=final)
-
-
 def _leaves(tp):
     return np.concatenate([tp.X[0], tp.sph.get_params()])
 
 
-def _rel(a, b):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return float(np.max(np.abs(a - b) / np.maximum(np.abs(b), 1e-300))) if a.size else 0.0
-
-
-def _device(cfg, all_data, sa, **kw):
-    from tsadar_amd import loops
-
-    info = {}
-    best, epoch_loss, loss_fn = loops.angular_loop(copy.deepcopy(cfg), all_data, sa, info=info, train_generator=True, **kw)
-    return best, epoch_loss, loss_fn, info
+_device = functools.partial(util._device, train_generator=True)
 
 
 @pytest.fixture

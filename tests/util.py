@@ -1,5 +1,7 @@
-"""Shared helpers of the test-suite: synthetic lineouts, oracle <-> engine parameter layouts."""
+"""Shared helpers of the test-suite: synthetic lineouts, oracle <-> engine parameter layouts, the angular (ARTS) fit's host loop."""
 from __future__ import annotations
+
+import copy
 
 import numpy as np
 
@@ -96,3 +98,111 @@ def rel_err(a, b, floor=1e-12):
     a, b = np.asarray(a), np.asarray(b)
     scale = np.maximum(np.abs(b), floor * np.max(np.abs(b), axis=-1, keepdims=True))
     return float(np.max(np.abs(a - b) / scale))
+
+
+# ---- the angular (ARTS) fit: tests/test_angular_loop_device.py, test_sph_generator_device.py, test_arb1v_generator_device.py
+def _angular_sa(cfg):
+    from tsadar_amd import calibration
+
+    cfg["other"]["extraoptions"]["spectype"] = "angular"
+    sa = calibration.get_scattering_angles(cfg)
+    cfg["other"]["extraoptions"]["spectype"] = "angular_full"
+    sa["angAxis"] = calibration.angular_pixel_axis()
+    return sa
+
+
+def _host_loop(config, all_data, sa):
+    """The reference's loop body (loops.py:197-270) over LossFunction.vg_loss with tree.Adam / tree.RMSProp.  A saved state of a
+    trained SphericalHarmonics also carries the generator's radial functions, as the reference's."""
+    from tsadar_amd import ThomsonParams, tree
+    from tsadar_amd.loss_function import LossFunction
+
+    config = copy.deepcopy(config)
+    config["optimizer"]["batch_size"] = 1
+    lo = config["data"]["lineouts"]
+    lo["start"] = int(lo["start"] / config["other"]["ang_res_unit"])
+    lo["end"] = int(lo["end"] / config["other"]["ang_res_unit"])
+    a, b = lo["start"], lo["end"]
+    batch1 = {"e_data": all_data["e_data"][a:b, :], "e_amps": all_data["e_amps"][a:b, :], "i_data": all_data["i_data"],
+              "i_amps": all_data["i_amps"], "noise_e": all_data["noiseE"][a:b, :], "noise_i": all_data["noiseI"][a:b, :]}
+    loss_fn = LossFunction(config, sa, batch1)
+    opt = config["optimizer"]
+    solver = (tree.Adam if opt["method"] == "adam" else tree.RMSProp)(opt["learning_rate"])
+    ts_params = ThomsonParams(config["parameters"], num_params=1, batch=False, activate=True)
+    diff_params, static_params = tree.partition(ts_params, tree.get_filter_spec(config["parameters"], ts_params))
+    opt_state = solver.init(diff_params)
+    best_weights, epoch_loss, best_loss, num_g_wait, num_b_wait = {}, 0.0, 100.0, 0, 0
+    losses, states, stopped = [], {}, None
+    for i_epoch in range(opt["num_epochs"]):
+        (val, aux), grad = loss_fn.vg_loss(diff_params, static_params, batch1)
+        updates, opt_state = solver.update(grad, opt_state)
+        diff_params = tree.apply_updates(diff_params, updates)
+        epoch_loss = val
+        losses.append(val)
+        if epoch_loss < best_loss:
+            if best_loss - epoch_loss < 0.000001:
+                best_loss = epoch_loss
+                best_weights = tree.combine(diff_params, static_params)
+                num_g_wait += 1
+                if num_g_wait > 5:
+                    stopped = i_epoch
+                    break
+            elif epoch_loss > best_loss:
+                num_b_wait += 1
+                if num_b_wait > 5:
+                    break
+            else:
+                best_loss = epoch_loss
+                best_weights = tree.combine(diff_params, static_params)
+                num_b_wait = 0
+                num_g_wait = 0
+        if opt["save_state"] and i_epoch % opt["save_state_freq"] == 0 and best_weights != {}:
+            states[i_epoch] = best_weights.get_unnormed_params()
+            if best_weights.slots.gen2d_active:
+                states[i_epoch]["electron"]["flm"] = best_weights.sph.get_unnormed_params()["flm"]
+    final = tree.combine(diff_params, static_params)
+    return dict(best=best_weights, epoch_loss=epoch_loss, losses=np.array(losses), states=states, stopped=stopped, final=final)
+
+
+def _rel(a, b, floor=0.0):
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    return float(np.max(np.abs(a - b) / np.maximum(np.abs(b), max(floor, 1e-300)))) if a.size else 0.0
+
+
+def _device(cfg, all_data, sa, **kw):
+    from tsadar_amd import loops
+
+    info = {}
+    best, epoch_loss, loss_fn = loops.angular_loop(copy.deepcopy(cfg), all_data, sa, info=info, **kw)
+    return best, epoch_loss, loss_fn, info
+
+
+def _stage_records(eng, cfg, two_d, want_gfe=True):
+    """The launch records of the entry points an epoch is made of, called one by one at the fit's shapes (one lineout, all its
+    points; want_gfe: with the table adjoint / the f_e adjoint, as the fit of a deck asks for them)."""
+    from tsadar_amd import ThomsonParams
+    from tsadar_amd import _lib as L
+
+    torch = eng.torch
+    tp = ThomsonParams(cfg["parameters"], 1, batch=False, activate=True)
+    phys = tp.physical_matrix()
+    p, gen, rows = phys[0], cfg["parameters"]["general"], eng._ats_shape[0]
+    fe = np.ascontiguousarray(tp()["electron"]["fe"], dtype=np.float64)
+    if two_d:
+        fe = eng.dev(fe)
+        P = eng.form_factor_2d(0, phys, fe, gen["ud"]["angle"], gen["Va"]["angle"], save=True)
+    else:
+        fe = fe.reshape(1, -1)
+        P = eng.form_factor(0, phys, fe)
+    rec = [eng.last_launch()]
+    E = eng.ats_spectrum(P[0], np.ones(rows), p[L.P_LAM], p[L.P_AMP1], p[L.P_AMP2])
+    rec.append(eng.last_launch())
+    Pbar, _ = eng.ats_adjoint(P[0], np.ones(rows), p[L.P_LAM], p[L.P_AMP1], p[L.P_AMP2], torch.ones_like(E))
+    rec.append(eng.last_launch())
+    if two_d:
+        eng.form_factor_2d_grad(0, phys, fe, Pbar.reshape(P.shape), gen["ud"]["angle"], gen["Va"]["angle"], want_table=want_gfe, use_saved=True)
+    else:
+        eng.form_factor_grad(0, phys, fe, Pbar.reshape(P.shape), want_fe=want_gfe)
+    rec.append(eng.last_launch())
+    torch.cuda.synchronize()
+    return rec

@@ -30,6 +30,7 @@ OPT_LAUNCH_PLAN = 2
 OPT_DLM_BLOCKS = 3
 ERR_LDS = -7  # TSFF_ERR_LDS: more LDS needed than a CU has
 ANG_TABLE2D, ANG_DLM, ANG_ARB2V, ANG_SPH, ANG_ARB1V = range(5)   # tsff_angular_fit's generators
+ANG_HIST_TAIL = (ANG_SPH, ANG_ARB1V)         # those whose leaves a row of best_hist keeps behind the NP scalars
 SPH_MORA_YAHI, SPH_ARBITRARY = range(2)      # the radial types of ANG_SPH (tsff_sph_table, tsff_sph_table_vjp)
 ANG_ADAM, ANG_RMSPROP = range(2)             # and optimisers
 

@@ -1925,7 +1925,9 @@ int tsff_adam_fit(tsff_handle* h, double* params, const double* fe, const double
   return 0;
 }
 
-// ---- the SphericalHarmonics generator (k_sph.inc).  sph_check: the refusals; sph_prepare: the handle's scratch
+// ---- the trained f_e generators (k_sph.inc, k_arb1v.inc).  sph_check, arb1v_check: the refusals; gen_forward, gen_adjoint: the
+// launches of generator gen (TSFF_ANG_SPH: S, n_gen parameters; TSFF_ANG_ARB1V: gen_data = S | S^T; any other: none), for the stand-alone
+// entry points and for tsff_angular_fit.  The caller has checked the sizes and holds sph_ws_doubles / arb1v_ws_doubles in ws.
 static int sph_check(tsff_handle* h, int type, int H, int nv, int nvr, int n_gen) {
   if (type != TSFF_SPH_MORA_YAHI && type != TSFF_SPH_ARBITRARY) return fail(h, -2, "unknown radial type %d", type);
   if (type == TSFF_SPH_MORA_YAHI && H != 2) return fail(h, -2, "Mora-Yahi radial functions: l = 1 only (n_harm = 2), got %d", H);
@@ -1937,9 +1939,36 @@ static int sph_check(tsff_handle* h, int type, int H, int nv, int nvr, int n_gen
   return 0;
 }
 
-static int sph_prepare(tsff_handle* h, int type, int H, int nv, int nvr, int n_gen) {
-  if (int rc = sph_check(h, type, H, nv, nvr, n_gen)) return rc;
-  TSFF_ENSURE(h, h->sph_ws, sph_ws_doubles(H, nv, nvr) * sizeof(double));
+static int arb1v_check(tsff_handle* h, int nv) {
+  return nv < 4 || nv > kArb1vMaxNv ? fail(h, -2, "nv must be 4 .. %d, got %d", kArb1vMaxNv, nv) : 0;
+}
+
+static void arb1v_matvec(tsff_handle* h, const double* M, const double* x, int nv, double* y) {
+  TSFF_LAUNCH0(h, k_arb1v_matvec, dim3((unsigned)((nv + kArb1vRows - 1) / kArb1vRows)), dim3(kThreads), 0, h->stream, M, x, nv, y);
+}
+
+// theta -> fe.  TSFF_ANG_ARB1V: fval -> u (ws) -> fe
+static int gen_forward(tsff_handle* h, int gen, const SphGen& S, int n_gen, const double* gen_data, int nv, double dvx,
+                       const double* theta, double* ws, double* fe) {
+  if (gen == TSFF_ANG_SPH) TSFF_LAUNCH0(h, k_sph_table, dim3(1), dim3(kThreads), 0, h->stream, S, theta, n_gen, dvx * dvx, ws, fe);
+  if (gen == TSFF_ANG_ARB1V) {
+    arb1v_matvec(h, gen_data, theta, nv, ws);
+    TSFF_LAUNCH0(h, k_arb1v_point, dim3(1), dim3(kThreads), 0, h->stream, (const double*)ws, nv, dvx, std::log(10.0), (const double*)nullptr, fe);
+  }
+  TSFF_HIP(h, hipGetLastError());
+  return 0;
+}
+
+// fe_bar = d loss / d fe -> grad = d loss / d theta.  TSFF_ANG_ARB1V: u (ws, left by the forward), fe_bar -> g_u (ws) -> grad
+static int gen_adjoint(tsff_handle* h, int gen, const SphGen& S, int n_gen, const double* gen_data, int nv, double dvx,
+                       const double* theta, const double* fe_bar, double* ws, double* grad) {
+  if (gen == TSFF_ANG_SPH)
+    TSFF_LAUNCH0(h, k_sph_vjp, dim3(1), dim3(kThreads), 0, h->stream, S, theta, n_gen, 1.0 / (dvx * dvx), std::log(10.0), fe_bar, ws, grad);
+  if (gen == TSFF_ANG_ARB1V) {
+    TSFF_LAUNCH0(h, k_arb1v_point, dim3(1), dim3(kThreads), 0, h->stream, (const double*)ws, nv, dvx, std::log(10.0), fe_bar, ws + nv);
+    arb1v_matvec(h, gen_data + (size_t)nv * nv, ws + nv, nv, grad);
+  }
+  TSFF_HIP(h, hipGetLastError());
   return 0;
 }
 
@@ -1948,11 +1977,9 @@ int tsff_sph_table(tsff_handle* h, int32_t sph_type, int32_t n_harm, int32_t nv,
   DevGuard dg__(h);
   if (!h) return -1;
   if (!theta || !gen_data || !fe) return fail(h, -1, "bad argument");
-  if (int rc = sph_prepare(h, sph_type, n_harm, nv, nvr, n_gen)) return rc;
-  TSFF_LAUNCH0(h, k_sph_table, dim3(1), dim3(kThreads), 0, h->stream, sph_gen(sph_type, n_harm, nv, nvr, gen_data), theta, (int)n_gen,
-               dvx * dvx, h->sph_ws.as<double>(), fe);
-  TSFF_HIP(h, hipGetLastError());
-  return 0;
+  if (int rc = sph_check(h, sph_type, n_harm, nv, nvr, n_gen)) return rc;
+  TSFF_ENSURE(h, h->sph_ws, sph_ws_doubles(n_harm, nv, nvr) * sizeof(double));
+  return gen_forward(h, TSFF_ANG_SPH, sph_gen(sph_type, n_harm, nv, nvr, gen_data), n_gen, nullptr, nv, dvx, theta, h->sph_ws.as<double>(), fe);
 }
 
 int tsff_sph_table_vjp(tsff_handle* h, int32_t sph_type, int32_t n_harm, int32_t nv, int32_t nvr, int32_t n_gen, double dvx,
@@ -1960,37 +1987,10 @@ int tsff_sph_table_vjp(tsff_handle* h, int32_t sph_type, int32_t n_harm, int32_t
   DevGuard dg__(h);
   if (!h) return -1;
   if (!theta || !gen_data || !fe_bar || !grad) return fail(h, -1, "bad argument");
-  if (int rc = sph_prepare(h, sph_type, n_harm, nv, nvr, n_gen)) return rc;
-  TSFF_LAUNCH0(h, k_sph_vjp, dim3(1), dim3(kThreads), 0, h->stream, sph_gen(sph_type, n_harm, nv, nvr, gen_data), theta, (int)n_gen,
-               1.0 / (dvx * dvx), std::log(10.0), fe_bar, h->sph_ws.as<double>(), grad);
-  TSFF_HIP(h, hipGetLastError());
-  return 0;
-}
-
-// ---- the free-form 1-D generator (k_arb1v.inc).  arb1v_forward: fval -> u (ws) -> fe; arb1v_adjoint: u (ws, left by the
-// forward), fe_bar -> g_u (ws) -> grad.  gen_data: S | S^T.  Launches only: the caller has checked nv and sized ws.
-static int arb1v_check(tsff_handle* h, int nv) {
-  if (nv < 4 || nv > kArb1vMaxNv) return fail(h, -2, "nv must be 4 .. %d, got %d", kArb1vMaxNv, nv);
-  return 0;
-}
-
-static void arb1v_matvec(tsff_handle* h, const double* M, const double* x, int nv, double* y) {
-  TSFF_LAUNCH0(h, k_arb1v_matvec, dim3((unsigned)((nv + kArb1vRows - 1) / kArb1vRows)), dim3(kThreads), 0, h->stream, M, x, nv, y);
-}
-
-static int arb1v_forward(tsff_handle* h, int nv, double dvx, const double* fval, const double* gen_data, double* ws, double* fe) {
-  arb1v_matvec(h, gen_data, fval, nv, ws);
-  TSFF_LAUNCH0(h, k_arb1v_point, dim3(1), dim3(kThreads), 0, h->stream, (const double*)ws, nv, dvx, std::log(10.0),
-               (const double*)nullptr, fe);
-  TSFF_HIP(h, hipGetLastError());
-  return 0;
-}
-
-static int arb1v_adjoint(tsff_handle* h, int nv, double dvx, const double* gen_data, const double* fe_bar, double* ws, double* grad) {
-  TSFF_LAUNCH0(h, k_arb1v_point, dim3(1), dim3(kThreads), 0, h->stream, (const double*)ws, nv, dvx, std::log(10.0), fe_bar, ws + nv);
-  arb1v_matvec(h, gen_data + (size_t)nv * nv, ws + nv, nv, grad);
-  TSFF_HIP(h, hipGetLastError());
-  return 0;
+  if (int rc = sph_check(h, sph_type, n_harm, nv, nvr, n_gen)) return rc;
+  TSFF_ENSURE(h, h->sph_ws, sph_ws_doubles(n_harm, nv, nvr) * sizeof(double));
+  return gen_adjoint(h, TSFF_ANG_SPH, sph_gen(sph_type, n_harm, nv, nvr, gen_data), n_gen, nullptr, nv, dvx, theta, fe_bar,
+                     h->sph_ws.as<double>(), grad);
 }
 
 int tsff_arb1v_table(tsff_handle* h, int32_t nv, double dvx, const double* fval, const double* gen_data, double* fe) {
@@ -1999,7 +1999,7 @@ int tsff_arb1v_table(tsff_handle* h, int32_t nv, double dvx, const double* fval,
   if (!fval || !gen_data || !fe) return fail(h, -1, "bad argument");
   if (int rc = arb1v_check(h, nv)) return rc;
   TSFF_ENSURE(h, h->arb1v_ws, arb1v_ws_doubles(nv) * sizeof(double));
-  return arb1v_forward(h, nv, dvx, fval, gen_data, h->arb1v_ws.as<double>(), fe);
+  return gen_forward(h, TSFF_ANG_ARB1V, SphGen{}, 0, gen_data, nv, dvx, fval, h->arb1v_ws.as<double>(), fe);
 }
 
 int tsff_arb1v_table_vjp(tsff_handle* h, int32_t nv, double dvx, const double* fval, const double* gen_data, const double* fe_bar,
@@ -2011,13 +2011,43 @@ int tsff_arb1v_table_vjp(tsff_handle* h, int32_t nv, double dvx, const double* f
   TSFF_ENSURE(h, h->arb1v_ws, arb1v_ws_doubles(nv) * sizeof(double));
   double* ws = h->arb1v_ws.as<double>();
   arb1v_matvec(h, gen_data, fval, nv, ws);   // (u alone: the adjoint's pointwise kernel rebuilds f_e from it)
-  return arb1v_adjoint(h, nv, dvx, gen_data, fe_bar, ws, grad);
+  return gen_adjoint(h, TSFF_ANG_ARB1V, SphGen{}, 0, gen_data, nv, dvx, fval, fe_bar, ws, grad);
+}
+
+// ---- tsff_angular_fit's f_e generator: a row of the table in include/tsff.h; ang_gen_describe makes every generator refusal of the fit
+struct AngGen {
+  bool two_d, m_leaf;        // f_e is an nv x nv table through the 2-D form factor (else nv values, 1-D); m may be an active slot
+  bool fe_is_data, fe_bar;   // no f_e is built, gen_data is the table; the form-factor adjoint must return d loss / d f_e
+  long n_table, hist_tail;   // leaves behind the NP scalars; how many of them a row of best_hist keeps
+  size_t ws_doubles;         // the generator's scratch
+  SphGen sph;                // TSFF_ANG_SPH: its constants
+};
+static int ang_gen_describe(tsff_handle* h, const tsff_angular_spec* sp, const double* gen_data, AngGen& G) {
+  const int gen = sp->generator, nv = sp->nv, nvx = h->S.nvx;
+  switch (gen) {   //            two_d  m_leaf fe_is_data fe_bar n_table hist_tail ws_doubles
+    case TSFF_ANG_TABLE2D: G = {true, false, true, false, 0, 0, 0}; break;
+    case TSFF_ANG_DLM: G = {false, true, false, false, 0, 0, 0}; break;   // (fe_bar: the fit asks for it when m is a leaf)
+    case TSFF_ANG_ARB2V: G = {true, false, false, true, (long)nv * nv, 0, 0}; break;
+    case TSFF_ANG_SPH: G = {true, false, false, true, sp->n_gen, sp->n_gen, 0}; break;   // (ws_doubles: below, once checked)
+    case TSFF_ANG_ARB1V: G = {false, false, false, true, nv, nv, arb1v_ws_doubles(nv)}; break;
+    default: return fail(h, -2, "unknown generator %d", gen);
+  }
+  int rc = 0;
+  if (gen == TSFF_ANG_DLM && nv != nvx) return fail(h, -1, "DLM: nv must be the handle's nvx (%d)", nvx);
+  if (gen == TSFF_ANG_ARB1V && nv != nvx) return fail(h, -1, "free-form 1-D f_e: nv must be the handle's nvx (%d), got %d", nvx, nv);
+  if (gen == TSFF_ANG_ARB1V && (rc = arb1v_check(h, nv))) return rc;
+  if (G.two_d && (nv < 4 || nv > 256)) return fail(h, -2, "2-D tables of nv = 4 .. 256 (the fit keeps the projection records)");
+  if (gen != TSFF_ANG_ARB2V && !gen_data) return fail(h, -1, "gen_data missing");
+  if (gen != TSFF_ANG_SPH || (rc = sph_check(h, sp->sph_type, sp->n_harm, nv, sp->nvr, sp->n_gen))) return rc;
+  G.ws_doubles = sph_ws_doubles(sp->n_harm, nv, sp->nvr);
+  G.sph = sph_gen(sp->sph_type, sp->n_harm, nv, sp->nvr, gen_data);
+  return 0;
 }
 
 // the angular (ARTS) fit on the device (k_angular.inc): n_epochs x (leaves -> physical parameters and f_e, form factor, ATS
 // chain, loss and seed, ATS adjoint, form-factor adjoint, chain rule, optimiser + early stop), all enqueued on the handle's
 // stream.  The stages are prepared once, for one lineout and all its points -- every refusal before anything is allocated,
-// every buffer before the first launch; the epochs only enqueue, and nothing synchronises.
+// every buffer before the first launch; the epochs only enqueue, nothing synchronises.  The generator: AngGen, gen_forward, gen_adjoint.
 int tsff_angular_fit(tsff_handle* h, const tsff_angular_spec* sp, double* leaves, const double* gen_data, const double* e_data,
                      const double* noise_e, const double* wcol, const double* e_amps, double* moments, double* best, int32_t* ctl,
                      double* loss_hist, double* best_hist) {
@@ -2029,67 +2059,51 @@ int tsff_angular_fit(tsff_handle* h, const tsff_angular_spec* sp, double* leaves
     return fail(h, -1, "bad argument");
   if (h->ats_npx == 0) return fail(h, -2, "tsff_ats_setup has not been called");
   if (h->fe_mode != TSFF_FE_PER_LINEOUT) return fail(h, -2, "tsff_angular_fit needs fe_mode == TSFF_FE_PER_LINEOUT");
-  const int gen = sp->generator, nv = sp->nv;
-  if (gen != TSFF_ANG_TABLE2D && gen != TSFF_ANG_DLM && gen != TSFF_ANG_ARB2V && gen != TSFF_ANG_SPH && gen != TSFF_ANG_ARB1V)
-    return fail(h, -2, "unknown generator %d", gen);
-  const bool arb1v = gen == TSFF_ANG_ARB1V;
-  const bool two_d = gen != TSFF_ANG_DLM && !arb1v;
-  if (gen == TSFF_ANG_DLM && nv != h->S.nvx) return fail(h, -1, "DLM: nv must be the handle's nvx (%d)", h->S.nvx);
-  if (arb1v && nv != h->S.nvx) return fail(h, -1, "free-form 1-D f_e: nv must be the handle's nvx (%d), got %d", h->S.nvx, nv);
-  if (arb1v)
-    if (int rc = arb1v_check(h, nv)) return rc;
-  if (two_d && (nv < 4 || nv > 256)) return fail(h, -2, "2-D tables of nv = 4 .. 256 (the fit keeps the projection records)");
-  if (gen != TSFF_ANG_ARB2V && !gen_data) return fail(h, -1, "gen_data missing");
-  if (gen == TSFF_ANG_SPH)
-    if (int rc = sph_check(h, sp->sph_type, sp->n_harm, nv, sp->nvr, sp->n_gen)) return rc;
+  AngGen G;
+  if (int rc = ang_gen_describe(h, sp, gen_data, G)) return rc;
   if (sp->method != TSFF_ANG_ADAM && sp->method != TSFF_ANG_RMSPROP) return fail(h, -2, "unknown optimiser %d", sp->method);
   if (sp->loss_method < 0 || sp->loss_method > 3) return fail(h, -2, "unknown loss method %d", sp->loss_method);
   uint8_t gm[kNP_MAX];
-  if (int rc = check_slots(h, sp->active_slots, sp->n_active, gm, gen == TSFF_ANG_DLM)) return rc;   // (m: a leaf of DLM decks only)
-  const bool sph = gen == TSFF_ANG_SPH;
-  const long n_table = gen == TSFF_ANG_ARB2V ? (long)nv * nv : sph ? (long)sp->n_gen : arb1v ? (long)nv : 0;   // the leaves behind the NP scalars
-  const long n = sp->n_active + n_table;
+  if (int rc = check_slots(h, sp->active_slots, sp->n_active, gm, G.m_leaf)) return rc;
+  const long n = sp->n_active + G.n_table;
   if (n < 1) return fail(h, -1, "nothing to train");
-  const int npts = h->S.npts, NA = h->S.n_angles, G = h->S.G, NP = h->S.NP;
+  const int gen = sp->generator, nv = sp->nv, npts = h->S.npts, NA = h->S.n_angles, NP = h->S.NP;
   const int rows = h->ats_row_end - h->ats_row_start, nJ = npts / h->ats_lam_step;
   if (nJ > TSFF_NBINS) return fail(h, -2, "more than %d wavelength resolution units per row", TSFF_NBINS);
-  const bool want_dm = gm[TSFF_P_M] != 0, train_table = gen == TSFF_ANG_ARB2V, want_gfe = train_table || sph;
-  const size_t nP = (size_t)G * npts * NA, nimg = (size_t)rows * nJ;
-  // the stages of an epoch: the form factor (2-D: saving), the ATS chain and its reverse, the form-factor adjoint (with the table
-  // adjoint when the table is trained, the f_e adjoint when m is a leaf or the free-form 1-D f_e is trained)
+  const bool want_dm = gm[TSFF_P_M] != 0, train_table = gen == TSFF_ANG_ARB2V;
+  const size_t nP = (size_t)h->S.G * npts * NA, nimg = (size_t)rows * nJ;
+  // the stages of an epoch: the form factor (2-D: saving), the ATS chain and its reverse, the form-factor adjoint (with the
+  // table or f_e adjoint when the generator chains it back, or when m is a leaf)
   FormFactorPlan ff;
   FormFactorAdjPlan ffa;
   FormFactor2dPlan ff2;
   FormFactor2dAdjPlan ff2a;
   auto prepare_stages = [&](bool dry) {
-    int rc = two_d ? form_factor_2d_prepare(h, 0, nv, true, 1, 0, -1, true, ff2, dry) : form_factor_prepare(h, 0, 1, ff, dry);
+    int rc = G.two_d ? form_factor_2d_prepare(h, 0, nv, true, 1, 0, -1, true, ff2, dry) : form_factor_prepare(h, 0, 1, ff, dry);
     if (!rc) rc = ats_prepare(h, false, dry);
     if (!rc) rc = ats_prepare(h, true, dry);
-    if (!rc) rc = two_d ? form_factor_2d_adj_prepare(h, 0, nv, 1, 0, (long)nP, want_gfe, ff2a, dry)
-                        : form_factor_adj_prepare(h, 0, 1, want_dm || arb1v, ffa, dry);
+    if (!rc) rc = G.two_d ? form_factor_2d_adj_prepare(h, 0, nv, 1, 0, (long)nP, G.fe_bar, ff2a, dry)
+                          : form_factor_adj_prepare(h, 0, 1, want_dm || G.fe_bar, ffa, dry);
     return rc;
   };
   int rc = prepare_stages(true);
   if (rc || sp->n_epochs == 0) return rc;
-  // scratch: phys | fe | dfe (2 nv) | aux | P | ThryE | Ebar | Pbar | gphys | gfe | grad | loss | the generator's (TSFF_ANG_SPH, TSFF_ANG_ARB1V)
-  const size_t nfe = two_d ? (size_t)nv * nv : (size_t)nv;
+  // scratch: phys | fe | dfe (2 nv) | aux | P | ThryE | Ebar | Pbar | gphys | gfe | grad | loss | its partial sums | the generator's
+  const size_t nfe = G.two_d ? (size_t)nv * nv : (size_t)nv;
   size_t off = 0;
   auto take = [&](size_t k) { const size_t o = off; off += (k + 1) & ~(size_t)1; return o; };
   const size_t o_phys = take(NP + 1), o_fe = take(nfe), o_dfe = take(2 * (size_t)nv), o_aux = take(4), o_P = take(nP),
                o_E = take(nimg), o_Eb = take(nimg), o_Pb = take(nP), o_gp = take(NP), o_gfe = take(nfe), o_grad = take(n),
-               o_loss = take(1), o_part = take(kAngLossBlocks),
-               o_sph = take(sph ? sph_ws_doubles(sp->n_harm, nv, sp->nvr) : arb1v ? arb1v_ws_doubles(nv) : 0);
+               o_loss = take(1), o_part = take(kAngLossBlocks), o_gen = take(G.ws_doubles);
   TSFF_ENSURE(h, h->ang_ws, off * sizeof(double));
   if (sp->n_active > 0 && (rc = upload_slots(h, sp->active_slots, sp->n_active))) return rc;
   if ((rc = prepare_stages(false))) return rc;
   double* ws = h->ang_ws.as<double>();
   double *phys = ws + o_phys, *fe = ws + o_fe, *dfe = ws + o_dfe, *aux = ws + o_aux, *P = ws + o_P, *E = ws + o_E, *Eb = ws + o_Eb,
          *Pb = ws + o_Pb, *gphys = ws + o_gp, *gfe = ws + o_gfe, *grad = ws + o_grad, *lossv = ws + o_loss,
-         *lpart = ws + o_part;
-  const double* table = gen == TSFF_ANG_TABLE2D ? gen_data : fe;
-  const SphGen SG = sph ? sph_gen(sp->sph_type, sp->n_harm, nv, sp->nvr, gen_data) : SphGen{};
-  const double* theta = leaves + NP;   // (TSFF_ANG_SPH: the generator's parameters; TSFF_ANG_ARB1V: fval)
-  const int n_hist = NP + (sph || arb1v ? (int)n_table : 0);
+         *lpart = ws + o_part, *gws = ws + o_gen;
+  const double *table = G.fe_is_data ? gen_data : fe, *theta = leaves + NP;
+  const int n_hist = NP + (int)G.hist_tail;
   const double dv2 = sp->dvx * sp->dvx, cvjp = 1.0 / dv2, ln10 = std::log(10.0);
   // the optimiser's scalars as tree.Adam / tree.RMSProp compute them in Python (1 - b1, -lr, 1 - b1**count with glibc pow)
   const bool adam = sp->method == TSFF_ANG_ADAM;
@@ -2105,11 +2119,8 @@ int tsff_angular_fit(tsff_handle* h, const tsff_angular_spec* sp, double* leaves
       return 0;
     });
     if (rc) return rc;
-    if (sph)
-      TSFF_LAUNCH0(h, k_sph_table, dim3(1), dim3(kThreads), 0, h->stream, SG, theta, (int)sp->n_gen, dv2, ws + o_sph, fe);
-    TSFF_HIP(h, hipGetLastError());
-    if (arb1v && (rc = arb1v_forward(h, nv, sp->dvx, theta, gen_data, ws + o_sph, fe))) return rc;
-    rc = two_d ? form_factor_2d_enqueue(h, ff2, phys, table, sp->ud_angle, sp->va_angle, P) : form_factor_enqueue(h, ff, phys, fe, P);
+    if ((rc = gen_forward(h, gen, G.sph, sp->n_gen, gen_data, nv, sp->dvx, theta, gws, fe))) return rc;
+    rc = G.two_d ? form_factor_2d_enqueue(h, ff2, phys, table, sp->ud_angle, sp->va_angle, P) : form_factor_enqueue(h, ff, phys, fe, P);
     if (rc) return rc;
     if ((rc = ats_spectrum_enqueue(h, P, e_amps, 0.0, 0.0, 0.0, phys, E))) return rc;
     TSFF_LAUNCH0(h, k_ang_loss, dim3(nloss), dim3(kThreads), 0, h->stream, (const double*)E, noise_e, e_data, wcol, rows, nJ,
@@ -2117,8 +2128,8 @@ int tsff_angular_fit(tsff_handle* h, const tsff_angular_spec* sp, double* leaves
     TSFF_LAUNCH0(h, k_ang_loss_sum, dim3(1), dim3(kThreads), 0, h->stream, (const double*)lpart, (int)nloss, lossv);
     TSFF_HIP(h, hipGetLastError());
     if ((rc = ats_adjoint_enqueue(h, P, e_amps, 0.0, 0.0, 0.0, phys, Eb, Pb))) return rc;
-    rc = two_d ? form_factor_2d_adj_enqueue(h, ff2a, phys, table, sp->ud_angle, sp->va_angle, h->proj.as<double>(), Pb, gphys, gfe)
-               : form_factor_adj_enqueue(h, ffa, phys, fe, Pb, gphys, gfe);
+    rc = G.two_d ? form_factor_2d_adj_enqueue(h, ff2a, phys, table, sp->ud_angle, sp->va_angle, h->proj.as<double>(), Pb, gphys, gfe)
+                 : form_factor_adj_enqueue(h, ffa, phys, fe, Pb, gphys, gfe);
     if (rc) return rc;
     rc = with_ion<TSFF_MAX_ION>(h->n_ion, [&](auto N) {
       TSFF_LAUNCH(h, k_ang_chain, (N.value), dim3(1), dim3(kThreads), 0, h->stream, h->S, (const double*)leaves, (const double*)gphys,
@@ -2127,15 +2138,11 @@ int tsff_angular_fit(tsff_handle* h, const tsff_angular_spec* sp, double* leaves
       return 0;
     });
     if (rc) return rc;
-    if (sph)   // grad: [n_act | n_gen]
-      TSFF_LAUNCH0(h, k_sph_vjp, dim3(1), dim3(kThreads), 0, h->stream, SG, theta, (int)sp->n_gen, cvjp, ln10, (const double*)gfe,
-                   ws + o_sph, grad + sp->n_active);
-    TSFF_HIP(h, hipGetLastError());
-    if (arb1v && (rc = arb1v_adjoint(h, nv, sp->dvx, gen_data, (const double*)gfe, ws + o_sph, grad + sp->n_active))) return rc;
+    if ((rc = gen_adjoint(h, gen, G.sph, sp->n_gen, gen_data, nv, sp->dvx, theta, gfe, gws, grad + sp->n_active))) return rc;
     const double count = (double)epoch + 1;
     const double c1 = 1.0 - std::pow(b1, count), c2 = 1.0 - std::pow(b2, count);
     TSFF_LAUNCH0(h, k_ang_opt, dim3(1), dim3(kThreads), 0, h->stream, (const double*)lossv, (const double*)grad, act, (int)sp->n_active,
-                 NP, n_table, leaves, moments, adam ? 0 : 1, b1, omb1, b2, omb2, neg_lr, c1, c2, sp->eps, ctl, best, epoch,
+                 NP, G.n_table, leaves, moments, adam ? 0 : 1, b1, omb1, b2, omb2, neg_lr, c1, c2, sp->eps, ctl, best, epoch,
                  loss_hist ? loss_hist + t : nullptr, best_hist ? best_hist + (size_t)t * n_hist : nullptr, n_hist);
     TSFF_HIP(h, hipGetLastError());
   }

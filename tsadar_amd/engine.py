@@ -692,18 +692,18 @@ class Engine:
 
     def angular_fit(self, leaves, spec: dict, data: dict, n_epochs, state=None, epoch0=0, loss_hist=True, best_hist=False):
         """tsff_angular_fit: ``n_epochs`` epochs of the angular (ARTS) fit on the device, enqueued at once; nothing is synchronised
-        (call ats_setup first).  ``leaves`` [NP (+ nv^2 of a trained Arbitrary2V table)]: the normalised leaves.  ``spec``: the
-        fields of tsff_angular_spec (generator, nv, learn_log, active_slots, loss_method, un, ud_angle, va_angle, dvx, method,
-        lr, b1, b2, eps, decay).  ``data``: device tensors gen_data, e_data and noise_e [rows, nJ], wcol [nJ], e_amps [rows].
-        -> (leaves, state = (moments, best, ctl), loss_hist [n_epochs] or None, best_hist [n_epochs, NP] (NaN rows: no best yet)
-        or None) as CUDA tensors.  Generator ANG_SPH (a trained SphericalHarmonics): ``spec`` also carries sph_type, n_harm, nvr
-        and n_gen (the ``meta`` of distribution.sph_gen_data, whose array is ``data["gen_data"]``), ``leaves`` is
-        [NP | get_params()] and the rows of best_hist are NP + n_gen wide.  Generator ANG_ARB1V (a trained free-form 1-D f_e):
-        ``data["gen_data"]`` is distribution.arb1v_gen_data(nv), ``leaves`` is [NP | fval[nv]] and the rows of best_hist are
-        NP + nv wide;
-        ``leaves`` and ``state`` are updated in place when they are CUDA tensors already (pass the returned ones to the next
-        chunk, with ``epoch0`` the epochs done so far).  ``state=None`` starts a fit: zero moments, best = [100 | leaves]
-        (angular_optax's best_loss = 100.0), ctl zeros."""
+        (call ats_setup first).  ``spec``: the fields of tsff_angular_spec (generator, nv, active_slots, loss_method, un, dvx,
+        method, lr, b1, b2, eps, decay; 2-D generators: ud_angle, va_angle).  ``data``: device tensors gen_data, e_data and
+        noise_e [rows, nJ], wcol [nJ], e_amps [rows].  ``leaves``: the NP normalised leaves, then the generator's tail:
+          generator    tail                      data["gen_data"]                      spec also carries          best_hist row
+          ANG_TABLE2D  none                      the table [nv, nv]                                               NP
+          ANG_DLM      none                      distribution.dlm_table(nv) | M_AXIS                              NP
+          ANG_ARB2V    fval2d [nv^2]             None                                  learn_log                  NP
+          ANG_SPH      sph.get_params() [n_gen]  distribution.sph_gen_data(sph)[0]     its meta, sph_gen_data[1]  NP + n_gen
+          ANG_ARB1V    fval [nv]                 distribution.arb1v_gen_data(nv)                                  NP + nv
+        -> (leaves, state = (moments, best, ctl), loss_hist [n_epochs] or None, best_hist (NaN rows: no best yet) or None) as CUDA
+        tensors.  ``leaves`` and ``state`` are updated in place when they are CUDA tensors already (pass the returned ones to the next
+        chunk, with ``epoch0`` the epochs done so far).  ``state=None``: zero moments, best = [100 | leaves] (angular_optax), ctl zeros."""
         torch = self.torch
         x = self.dev(leaves).reshape(-1)
         act = np.ascontiguousarray(spec.get("active_slots", ()), dtype=np.int32)
@@ -716,7 +716,7 @@ class Engine:
         mom, best, ctl = state
         assert mom.numel() == (2 if adam else 1) * n and best.numel() == 1 + x.numel() and ctl.dtype == torch.int32
         hist = torch.empty(max(int(n_epochs), 0), dtype=torch.float64, device=self.device) if loss_hist else None
-        n_hist = self.NP + {L.ANG_SPH: int(spec.get("n_gen", 0)), L.ANG_ARB1V: int(spec["nv"])}.get(int(spec["generator"]), 0)
+        n_hist = int(x.numel()) if int(spec["generator"]) in L.ANG_HIST_TAIL else self.NP
         bh = torch.full((max(int(n_epochs), 0), n_hist), float("nan"), dtype=torch.float64, device=self.device) if best_hist else None
         c = L.TsffAngularSpec()
         c.generator, c.nv, c.learn_log = int(spec["generator"]), int(spec["nv"]), int(bool(spec.get("learn_log", False)))

@@ -10,7 +10,7 @@ weights are tracked as the reference tracks them: the iterate AFTER the update o
 """
 from __future__ import annotations
 
-from typing import Dict, Optional, Tuple
+from typing import Callable, Dict, NamedTuple, Optional, Tuple
 
 import numpy as np
 
@@ -128,6 +128,42 @@ def lbfgs_loop(config: Dict, loss_fn, previous_weights: Optional[ThomsonParams],
     return res["f"], out
 
 
+class _Generator(NamedTuple):
+    """An angular deck's f_e generator as ``angular_loop`` uses it: a row of tsff_angular_fit's table (include/tsff.h)."""
+    code: int                                      # L.ANG_*
+    spec: Dict                                     # the fields of tsff_angular_spec it adds
+    gen_data: Optional[np.ndarray]                 # its constants (``data["gen_data"]`` of Engine.angular_fit)
+    tail: np.ndarray = np.zeros(0)                 # its leaves, behind the NP scalars
+    write_back: Callable = lambda tp, tail: None   # (ThomsonParams, such a tail): the tail into the weights
+    state_extra: Callable = lambda tp: {}          # ThomsonParams -> what ["electron"] of a saved state gains
+
+
+def _generator(config: Dict, ts_params: ThomsonParams, train_generator: bool) -> Optional[_Generator]:
+    """The generator of ``config``'s f_e at the values of ``ts_params``; None: the device builds none for this f_e."""
+    from . import _lib as L
+    from . import distribution as Dist
+
+    fecfg, sm, gen = config["parameters"]["electron"]["fe"], ts_params.slots, config["parameters"]["general"]
+    nvx, dim = int(fecfg["nvx"]), int(fecfg.get("dim", 1))
+    if (dim == 1 and not (sm.has_m or sm.fval_active)) or ((sm.fval_active or sm.gen2d_active) and not train_generator):
+        return None
+    if sm.fval_active:   # a trained Arbitrary1V
+        return _Generator(L.ANG_ARB1V, {}, Dist.arb1v_gen_data(nvx), ts_params.fval.ravel(),
+                          lambda tp, tail: setattr(tp, "fval", tail.reshape(tp.fval.shape).copy()))
+    if dim == 1:
+        return _Generator(L.ANG_DLM, {}, np.concatenate([Dist.dlm_table(nvx).ravel(), Dist.M_AXIS]))
+    angles = dict(ud_angle=gen["ud"]["angle"], va_angle=gen["Va"]["angle"])
+    if sm.fval2d_active:   # a trained Arbitrary2V table
+        return _Generator(L.ANG_ARB2V, dict(angles, learn_log=ts_params.learn_log), None, ts_params.fval2d.ravel(),
+                          lambda tp, tail: setattr(tp, "fval2d", tail.reshape(tp.fval2d.shape).copy()))
+    if sm.gen2d_active:   # a trained SphericalHarmonics
+        gen_data, meta = Dist.sph_gen_data(ts_params.sph)
+        return _Generator(L.ANG_SPH, dict(angles, **meta), gen_data, ts_params.sph.get_params(), lambda tp, tail: tp.sph.set_params(tail),
+                          lambda tp: {"flm": tp.sph.get_unnormed_params()["flm"]})
+    # a constant table (SphericalHarmonics or Arbitrary2V not trained), built once on the host
+    return _Generator(L.ANG_TABLE2D, angles, np.ascontiguousarray(ts_params()["electron"]["fe"], dtype=np.float64))
+
+
 ANGULAR_CHUNK = 16   # epochs per enqueued chunk of angular_loop (at most this many minus one run after the early stop)
 RMSPROP_DECAY, RMSPROP_EPS = 0.9, 1e-8   # optax.rmsprop's defaults
 
@@ -154,17 +190,13 @@ def angular_loop(config: Dict, all_data: Dict, sa: Dict, chunk: Optional[int] = 
     ``stopped_after`` (the epoch of the early stop, or None) and ``leaves`` (the final normalised leaves, then fval or the
     generator's parameters).
 
-    ``train_generator=True``: a trainable ``sphericalharmonic`` f_e of ``flm_type`` "mora-yahi" or "arbitrary" (the reference's
-    arts2v deck) is trained on the device: the table is built from ``SphericalHarmonics.get_params()`` every epoch and its
-    adjoint is chained to them exactly (k_sph.inc), where ``LossFunction.vg_loss`` takes central differences for the order of
-    f00 and the Mora-Yahi gradient lengths.  ``best_weights.sph`` is that of the best iterate, ``info["leaves"]`` the scalars
-    then the generator's parameters, and each saved state carries the best iterate's radial functions under
-    ``["electron"]["flm"]`` (the reference's layout).  The default refuses such a deck, as before.
-
-    ``train_generator=True`` also runs a trained free-form 1-D f_e (``fe: {dim: 1, type: arbitrary, active: true}``, the
-    reference's Arbitrary1V): f_e is built from ``fval`` every epoch and d loss / d f_e is chained to it on the device
-    (k_arb1v.inc; the chain of ``distribution.arbitrary_1v_vjp``).  ``best_weights.fval`` is the best iterate's,
-    ``info["leaves"]`` the scalars then fval, and each saved state's ``["electron"]["f"]`` is the f_e of that epoch's best fval.
+    ``train_generator=True`` trains two more generators on the device, exactly (``LossFunction.vg_loss`` takes central differences
+    for the order of f00 and the Mora-Yahi gradient lengths) and with f_e rebuilt from their parameters every epoch: a trainable
+    ``sphericalharmonic`` f_e of ``flm_type`` "mora-yahi" or "arbitrary" (the reference's arts2v deck; k_sph.inc) -- ``best_weights.sph``
+    is the best iterate's, each saved state carries its radial functions under ``["electron"]["flm"]`` (the reference's layout) --
+    and a trained free-form 1-D f_e (``fe: {dim: 1, type: arbitrary, active: true}``, the reference's Arbitrary1V; k_arb1v.inc) --
+    ``best_weights.fval`` is the best iterate's, each saved state's ``["electron"]["f"]`` the f_e of that epoch's best fval.
+    ``info["leaves"]`` is then the scalars followed by those parameters.  The default refuses both decks, as before.
 
     Not built (NotImplementedError, raised before any device work): methods other than adam and rmsprop, multiplexed decks
     (``shotnum`` a list), ``distributed=True``, trainable SphericalHarmonics generators without ``train_generator`` or of
@@ -210,13 +242,11 @@ def angular_loop(config: Dict, all_data: Dict, sa: Dict, chunk: Optional[int] = 
               "i_amps": all_data["i_amps"], "noise_e": all_data["noiseE"][a:b, :], "noise_i": all_data["noiseI"][a:b, :]}
     loss_fn = LossFunction(config, sa, batch1)
     ts_params = ThomsonParams(config["parameters"], num_params=1, batch=False, activate=True)
-    sm = ts_params.slots
-    if (sm.gen2d_active and not train_generator) or ((ts_params.fval is not None or (dim == 1 and not sm.has_m)) and not arb1v):
+    g = _generator(config, ts_params, train_generator)
+    if g is None:
         raise NotImplementedError("angular_loop: this distribution function is not built on the device")
     diff, _ = tree.partition(ts_params, tree.get_filter_spec(config["parameters"], ts_params))
     act = [s for _, s in diff.slots if s >= 0]
-    train_table = any(s == tree.FVAL2D_SLOT for _, s in diff.slots)
-    train_gen = any(s == tree.GEN2D_SLOT for _, s in diff.slots)
 
     eng = loss_fn.ts_diag.engine(ts_params.activate)
     torch = eng.torch
@@ -226,36 +256,13 @@ def angular_loop(config: Dict, all_data: Dict, sa: Dict, chunk: Optional[int] = 
     wcol = loss_fn._angular_wcol(diag._ats_lam_axis(eng, lam_step), rows)
     nvx = int(fecfg["nvx"])
     vx = Dist.velocity_grid(nvx)
-    gen = config["parameters"]["general"]
-    leaves = ts_params.X[0].copy()
-    spec = dict(nv=nvx, active_slots=act, loss_method=L.LOSS_METHODS[opt["loss_method"]], un=loss_fn.e_norm**2,
+    leaves = np.concatenate([ts_params.X[0], g.tail])
+    spec = dict(g.spec, generator=g.code, nv=nvx, active_slots=act, loss_method=L.LOSS_METHODS[opt["loss_method"]], un=loss_fn.e_norm**2,
                 dvx=vx[1] - vx[0], lr=float(opt["learning_rate"]))
-    if method == "adam":
-        spec.update(method=L.ANG_ADAM, b1=ADAM_B1, b2=ADAM_B2, eps=ADAM_EPS)
-    else:
-        spec.update(method=L.ANG_RMSPROP, decay=RMSPROP_DECAY, eps=RMSPROP_EPS)
-    if arb1v:
-        spec["generator"] = L.ANG_ARB1V
-        gen_data = Dist.arb1v_gen_data(nvx)
-        leaves = np.concatenate([leaves, ts_params.fval.ravel()])
-    elif dim == 1:
-        spec["generator"] = L.ANG_DLM
-        gen_data = np.concatenate([Dist.dlm_table(nvx).ravel(), Dist.M_AXIS])
-    else:
-        spec.update(ud_angle=gen["ud"]["angle"], va_angle=gen["Va"]["angle"])
-        if train_table:
-            spec.update(generator=L.ANG_ARB2V, learn_log=ts_params.learn_log)
-            leaves = np.concatenate([leaves, ts_params.fval2d.ravel()])
-            gen_data = None
-        elif train_gen:
-            gen_data, meta = Dist.sph_gen_data(ts_params.sph)
-            spec.update(generator=L.ANG_SPH, **meta)
-            leaves = np.concatenate([leaves, ts_params.sph.get_params()])
-        else:   # a constant table (SphericalHarmonics or Arbitrary2V not trained), built once on the host
-            spec["generator"] = L.ANG_TABLE2D
-            gen_data = np.ascontiguousarray(ts_params()["electron"]["fe"], dtype=np.float64)
+    spec.update(dict(method=L.ANG_ADAM, b1=ADAM_B1, b2=ADAM_B2, eps=ADAM_EPS) if method == "adam" else
+                dict(method=L.ANG_RMSPROP, decay=RMSPROP_DECAY, eps=RMSPROP_EPS))
     img = lambda v: eng.dev(np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (rows, nJ))))
-    data = dict(gen_data=eng.dev(gen_data), e_data=img(batch1["e_data"]), noise_e=img(np.atleast_1d(batch1["noise_e"])),
+    data = dict(gen_data=eng.dev(g.gen_data), e_data=img(batch1["e_data"]), noise_e=img(np.atleast_1d(batch1["noise_e"])),
                 wcol=eng.dev(wcol), e_amps=eng.dev(np.broadcast_to(np.asarray(batch1["e_amps"], dtype=np.float64).reshape(-1, 1),
                                                                    (rows, 1)).reshape(-1)))
 
@@ -293,21 +300,14 @@ def angular_loop(config: Dict, all_data: Dict, sa: Dict, chunk: Optional[int] = 
             if i % freq == 0 and not np.isnan(bh[i, 0]):
                 snap = ts_params.copy()
                 snap.X[0] = bh[i, : eng.NP]
-                if arb1v:
-                    snap.fval = bh[i, eng.NP :].reshape(ts_params.fval.shape).copy()
+                if bh.shape[1] > eng.NP:   # (the generators whose leaves best_hist keeps)
+                    g.write_back(snap, bh[i, eng.NP :])
                 states[i] = snap.get_unnormed_params()
-                if train_gen:
-                    snap.sph.set_params(bh[i, eng.NP :])
-                    states[i]["electron"]["flm"] = snap.sph.get_unnormed_params()["flm"]
+                states[i]["electron"].update(g.state_extra(snap))
     if ctl[4] == 0:   # (no epoch improved on 100.0: the reference returns the dict it started with)
         return {}, epoch_loss, loss_fn
     best = eng.download(state[1])
     best_weights = ts_params.copy()
     best_weights.X[0] = best[1 : 1 + eng.NP]
-    if train_table:
-        best_weights.fval2d = best[1 + eng.NP :].reshape(ts_params.fval2d.shape).copy()
-    if train_gen:
-        best_weights.sph.set_params(best[1 + eng.NP :])
-    if arb1v:
-        best_weights.fval = best[1 + eng.NP :].reshape(ts_params.fval.shape).copy()
+    g.write_back(best_weights, best[1 + eng.NP :])
     return best_weights, epoch_loss, loss_fn
