@@ -69,22 +69,28 @@ else:
 hw = t[:, 0]
 loc = ((hw >> 32) & 0xF) * 65536 + (hw & 0xFFFFFFFF & 0xFF00)   # (XCC id, SE/SH/CU bits of HW_ID): one value per CU
 cus, cu_idx = np.unique(loc, return_inverse=True)
-T = t[:, 1:9].astype(np.float64) * 0.01   # microseconds (100 MHz)
+# (stamps 1 .. 6 and 8: slot 7 was the chain rule at the end of the workgroup, now k_fused_finish's work, and is not written)
+STAMPS = [1, 2, 3, 4, 5, 6, 8]
+LAST = len(STAMPS) - 1
+T = t[:, STAMPS].astype(np.float64) * 0.01   # microseconds (100 MHz)
 t0 = T[:, 0].min()
 T -= t0
-end = T[:, 7].max()
+end = T[:, LAST].max()
 print(f"B {B}: kernel by HIP events {np.round(kt, 4)} ms; span of the stamps {end:.1f} us; distinct CU ids {len(cus)}; workgroups {nwg}")
-names = ["prologue", "sweep", "conv1+argmax", "loss+sums", "ybar+conv2", "xbar+contract+wavesums", "chain+store"]
+names = ["prologue", "sweep", "conv1+argmax", "loss+sums", "ybar+conv2", "xbar+contract+wavesums+store"]
 for f, nm in ((0, "EPW"), (1, "IAW")):
     sl = slice(f * B, (f + 1) * B)
     d = np.diff(T[sl], axis=1)
-    tot = T[sl, 7] - T[sl, 0]
+    tot = T[sl, LAST] - T[sl, 0]
     print(f"  {nm}: workgroup latency mean {tot.mean():.1f} us (p5 {np.percentile(tot, 5):.1f}, p95 {np.percentile(tot, 95):.1f}); phases (mean us): "
           + ", ".join(f"{n} {v:.1f}" for n, v in zip(names, d.mean(axis=0))))
+    # the two IRF convolutions (conv4_phase) with their surroundings: the phases a change of the convolution loops moves
+    print(f"       convolutions: conv1+argmax {d[:, 2].mean():.2f} us (median {np.median(d[:, 2]):.2f}), ybar+conv2 {d[:, 4].mean():.2f} us (median {np.median(d[:, 4]):.2f}), "
+          f"together {100 * (d[:, 2] + d[:, 4]).mean() / tot.mean():.1f} % of the workgroup latency")
     wv = t[sl, 9:13].astype(np.float64) * 0.01 - t0 - T[sl, 1:2]   # each wavefront's sweep end, from the start of the sweep
     print(f"       sweep end per wavefront (mean us from sweep start): {np.round(wv.mean(axis=0), 1)}; barrier wait = max - mean: {np.mean(wv.max(axis=1) - wv.mean(axis=1)):.1f}")
 # per CU: first start, last end, busy intervals
-starts, ends = T[:, 0], T[:, 7]
+starts, ends = T[:, 0], T[:, LAST]
 per_cu_first = np.array([starts[cu_idx == c].min() for c in range(len(cus))])
 per_cu_last = np.array([ends[cu_idx == c].max() for c in range(len(cus))])
 per_cu_n = np.bincount(cu_idx)

@@ -150,7 +150,7 @@ __device__ __forceinline__ void load_tables(const Smem& m, const KStatic& S, con
 // workgroup.)  Not staged: the LDS copy of ln f_e itself, which the one-sweep kernel does not read.  No barrier inside.
 // entries of the zero-padded tap array the phase-layout convolutions touch (forward: ascending from cf_i0; adjoint: descending from ca_i0)
 __host__ __device__ inline int padded_taps(const KStatic& S, int f) {
-  const int a = S.cf_i0[f] + 4 * S.cf_na[f] + 4, b = S.ca_i0[f] + 1;   // (+ 4: the software-pipelined loop requests one group ahead)
+  const int a = S.cf_i0[f] + 4 * S.cf_na[f] + 8, b = S.ca_i0[f] + 1;   // (+ 8: conv4_phase requests two groups beyond its last one; <= ntaps + 14)
   return a > b ? a : b;
 }
 constexpr int kStageK = 10;   // 10 x 256 threads x 16 B = 40 KB >= the full Z' table (26 KB) + W (13 KB)

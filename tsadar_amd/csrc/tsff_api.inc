@@ -972,10 +972,12 @@ int tsff_create(const tsff_config* c, tsff_handle** out) {
     S.cf_a0[f] = u0f / 4; S.cf_na[f] = (pre + n + 3) / 4; S.cf_i0[f] = 3 - pre;
     const int uamin = -toff - n + 1, u0a = 4 * fdiv4(uamin), prea = uamin - u0a;
     S.ca_a0[f] = u0a / 4; S.ca_na[f] = (prea + n + 3) / 4; S.ca_i0[f] = 3 + n - 1 + prea;
-    std::vector<double> pt(n + 12, 0.0);
-    for (int k = 0; k < n; ++k) pt[3 + k] = tp[f][k];
+    // (kTapLead zeros in front of entry 0 and 13 behind the last tap: the pipelined convolution reads two groups beyond its last
+    //  one in either direction, entries -kTapLead .. n + 13 -- conv4_phase shows the index arithmetic)
+    std::vector<double> pt(kTapLead + n + 16, 0.0);
+    for (int k = 0; k < n; ++k) pt[kTapLead + 3 + k] = tp[f][k];
     TSFF_HIPC(upload(h->ptaps[f], pt.data(), pt.size()));
-    S.ptaps[f] = h->ptaps[f].as<double>();
+    S.ptaps[f] = h->ptaps[f].as<double>() + kTapLead;
     S.hs = std::max(S.hs, std::max(std::max(-S.cf_a0[f], S.cf_a0[f] + S.cf_na[f]), std::max(-S.ca_a0[f], S.ca_a0[f] + S.ca_na[f])) + 1);
   }
   for (int f = 0; f < 2; ++f) {
