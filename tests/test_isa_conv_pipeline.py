@@ -1,4 +1,4 @@
-"""Static check of the software-pipelined IRF convolutions (conv4_phase, k_spectrum_fused.inc).
+"""Static check of the software-pipelined IRF convolutions (conv4_phase, k_conv.inc).
 
 The phase-layout convolution walks its taps in groups of four; sixteen FP64 FMAs per group, four explicit chains.  The rolled
 loop requested the operands of two groups (LDS reads of the window, scalar loads of the taps) at the top of an iteration and
@@ -15,16 +15,9 @@ loops of the sweep).  In every convolution loop, walking the body cyclically,
 
 The one-sweep kernel has two such loops (forward and adjoint convolution), the forward-only kernel one.
 """
-import os
-import re
-import shutil
-import subprocess
-import tempfile
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+import isa
 
 _FUSED = "template __global__ void tsff::k_spectrum_fused<{n}, {gm}, false, true>(tsff::KStatic, tsff::KCall, int, int, const double*);"
 _PAIRS = "template __global__ void tsff::k_forward_pairs<1, true, 2, 2>(tsff::KStatic, tsff::KCall, int, int, const double*);"
@@ -37,52 +30,6 @@ KERNELS = {
     "k_forward_pairs<1, true, 2, 2>": (_PAIRS, "_ZN4tsff15k_forward_pairsILi1ELb1ELi2ELi2EE", 1),
 }
 MIN_FMAS = 32   # two tap groups
-
-
-def compile_assembly(root):
-    """device assembly of every instantiation of KERNELS from the sources under root, one compile"""
-    with tempfile.TemporaryDirectory() as d:
-        src, out = os.path.join(d, "conv.hip"), os.path.join(d, "conv.s")
-        insts = "\n".join(v[0] for v in KERNELS.values())
-        open(src, "w").write('#define TSFF_NO_API\n#include "%s"\n%s\n' % (os.path.join(root, "tsadar_amd", "csrc", "tsff_kernels.hip"), insts))
-        subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-I" + os.path.join(root, "include"),
-                        "-o", out, src], check=True, stderr=subprocess.DEVNULL)
-        return open(out).read()
-
-
-def function_body(asm, prefix):
-    """the assembly of the one function whose mangled name starts with prefix, up to the end of its resource comments"""
-    lines = asm.split("\n")
-    starts = [i for i, l in enumerate(lines) if l.startswith(prefix) and re.match(r"^_ZN4tsff\w+:", l)]
-    assert len(starts) == 1, (prefix, len(starts))
-    s = starts[0]
-    e = next(i for i in range(s, len(lines)) if lines[i].startswith("; Occupancy:"))
-    return "\n".join(lines[s:e + 1])
-
-
-def innermost_loops(body):
-    """instruction lists of the innermost loops of a function: from a label to the last backward branch to it, with no other
-    backward branch's target strictly inside"""
-    insts, labels = [], {}
-    for l in body.split("\n"):
-        t = l.split(";")[0].strip()
-        if not t:
-            continue
-        m = re.match(r"^([.\w$]+):", t)
-        if m:
-            labels[m.group(1)] = len(insts)
-            continue
-        if not t.startswith("."):
-            insts.append(t)
-    spans = {}
-    for i, t in enumerate(insts):
-        p = t.split(None, 1)
-        if (p[0] == "s_branch" or p[0].startswith("s_cbranch")) and len(p) > 1:
-            tgt = labels.get(p[1].split(",")[0].strip())
-            if tgt is not None and tgt <= i:
-                spans[tgt] = max(spans.get(tgt, i), i)
-    inner = [(s, e) for s, e in spans.items() if not any((s2, e2) != (s, e) and s <= s2 and e2 <= e for s2, e2 in spans.items())]
-    return [insts[s:e + 1] for s, e in sorted(inner)]
 
 
 def is_fma(t):
@@ -98,7 +45,8 @@ def is_lgkm_wait(t):
 
 
 def conv_loops(body):
-    return [ops for ops in innermost_loops(body)
+    insts, inner = isa.innermost_loops(body)
+    return [ops for ops in (insts[s:e + 1] for s, e in inner)
             if sum(map(is_fma, ops)) >= MIN_FMAS and any(t.startswith("s_load") for t in ops) and any(t.startswith("ds_read") for t in ops)
             and not any("wave_shl:1" in t for t in ops)]
 
@@ -120,13 +68,13 @@ def fmas_behind_requests(ops):
 
 @pytest.fixture(scope="module")
 def assembly():
-    return compile_assembly(ROOT)
+    return isa.compile_assembly(v[0] for v in KERNELS.values())
 
 
 @pytest.mark.parametrize("name", sorted(KERNELS))
 def test_requests_fly_under_the_fma_chains(assembly, name):
     _, prefix, nconv = KERNELS[name]
-    found = conv_loops(function_body(assembly, prefix))
+    found = conv_loops(isa.function(assembly, prefix)[1])
     assert len(found) == nconv, (name, "convolution loops", len(found), nconv)
     for ops in found:
         behind = fmas_behind_requests(ops)
@@ -139,7 +87,7 @@ def test_requests_fly_under_the_fma_chains(assembly, name):
 @pytest.mark.parametrize("name", sorted(KERNELS))
 def test_no_spill_traffic_in_the_convolution_loops(assembly, name):
     _, prefix, nconv = KERNELS[name]
-    found = conv_loops(function_body(assembly, prefix))
+    found = conv_loops(isa.function(assembly, prefix)[1])
     assert len(found) == nconv, (name, "convolution loops", len(found), nconv)
     for ops in found:
         bad = [t for t in ops if t.startswith(("scratch_", "buffer_", "v_readlane", "v_writelane"))]

@@ -14,18 +14,11 @@ of launch_spectrum; no GPU needed, one compile of about a minute) and reads the 
 * the exchange costs no registers: spilled VGPRs and scratch bytes are not above, and the occupancy not below, what the same
   instantiation had with the exchange through LDS.  PARENT holds those figures, read from the kernel metadata
   (`.vgpr_spill_count`, `.private_segment_fixed_size`, `; Occupancy:`) of a build of the commit before the exchange moved into
-  registers, by this file's own `resources()`.  The one-sweep kernel stays at two wavefronts per SIMD.
+  registers, by `isa.resources()`.  The one-sweep kernel stays at two wavefronts per SIMD.
 """
-import os
-import re
-import shutil
-import subprocess
-import tempfile
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+import isa
 
 _FUSED = "template __global__ void tsff::k_spectrum_fused<{n}, {gm}, {zh}, true>(tsff::KStatic, tsff::KCall, int, int, const double*);"
 _PAIRS = "template __global__ void tsff::k_forward_pairs<{n}, {zh}, {exm}, {npair}>(tsff::KStatic, tsff::KCall, int, int, const double*);"
@@ -65,68 +58,9 @@ PARENT = {
 }
 
 
-def compile_assembly(root, defines=()):
-    """device assembly of every instantiation of KERNELS from the sources under root, one compile"""
-    with tempfile.TemporaryDirectory() as d:
-        src, out = os.path.join(d, "all.hip"), os.path.join(d, "all.s")
-        insts = "\n".join(v[0] for v in KERNELS.values())
-        open(src, "w").write('#define TSFF_NO_API\n#include "%s"\n%s\n' % (os.path.join(root, "tsadar_amd", "csrc", "tsff_kernels.hip"), insts))
-        subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-I" + os.path.join(root, "include"),
-                        *defines, "-o", out, src], check=True, stderr=subprocess.DEVNULL)
-        return open(out).read()
-
-
-def _function(asm, prefix):
-    """the assembly of the one function whose mangled name starts with prefix, up to the end of its resource comments"""
-    lines = asm.split("\n")
-    starts = [i for i, l in enumerate(lines) if l.startswith(prefix) and re.match(r"^_ZN4tsff\w+:", l)]
-    assert len(starts) == 1, (prefix, len(starts))
-    s = starts[0]
-    e = next(i for i in range(s, len(lines)) if lines[i].startswith("; Occupancy:"))
-    return re.match(r"^(\w+):", lines[s]).group(1), "\n".join(lines[s:e + 1])
-
-
-def resources(asm):
-    """name -> (spilled VGPRs, scratch bytes, occupancy) of every instantiation of KERNELS"""
-    out = {}
-    for name, (_, prefix, _, _) in KERNELS.items():
-        mangled, body = _function(asm, prefix)
-        meta = asm[re.search(r"^\s*\.name:\s+%s$" % re.escape(mangled), asm, re.M).start():]
-        spill = int(re.search(r"\.vgpr_spill_count:\s*(\d+)", meta).group(1))
-        scratch = int(re.search(r"\.private_segment_fixed_size:\s*(\d+)", meta).group(1))
-        occ = int(re.search(r"; Occupancy:\s*(\d+)", body).group(1))
-        out[name] = (spill, scratch, occ)
-    return out
-
-
-def loops(body):
-    """innermost loops of a function: lists of instruction lines from a label to the last backward branch to it, with no
-    other backward branch's target strictly inside"""
-    insts, labels = [], {}
-    for l in body.split("\n"):
-        t = l.split(";")[0].strip()
-        if not t:
-            continue
-        m = re.match(r"^([.\w$]+):", t)
-        if m:
-            labels[m.group(1)] = len(insts)
-            continue
-        if not t.startswith("."):
-            insts.append(t)
-    spans = {}
-    for i, t in enumerate(insts):
-        p = t.split(None, 1)
-        if (p[0] == "s_branch" or p[0].startswith("s_cbranch")) and len(p) > 1:
-            tgt = labels.get(p[1].split(",")[0].strip())
-            if tgt is not None and tgt <= i:
-                spans[tgt] = max(spans.get(tgt, i), i)
-    inner = [(s, e) for s, e in spans.items() if not any((s2, e2) != (s, e) and s <= s2 and e2 <= e for s2, e2 in spans.items())]
-    return insts, sorted(inner)
-
-
 @pytest.fixture(scope="module")
 def assembly():
-    return compile_assembly(ROOT)
+    return isa.compile_assembly(v[0] for v in KERNELS.values())
 
 
 def test_parent_table_is_complete():
@@ -136,8 +70,8 @@ def test_parent_table_is_complete():
 @pytest.mark.parametrize("name", sorted(KERNELS))
 def test_angle_loops_exchange_in_registers(assembly, name):
     _, prefix, nsweep, nmov = KERNELS[name]
-    _, body = _function(assembly, prefix)
-    insts, inner = loops(body)
+    _, body = isa.function(assembly, prefix)
+    insts, inner = isa.innermost_loops(body)
     angle = [(s, e) for s, e in inner if any("wave_shl:1" in t for t in insts[s:e + 1])]
     assert len(angle) == nsweep, (name, "angle loops", len(angle), nsweep)
     for s, e in angle:
@@ -152,7 +86,7 @@ def test_angle_loops_exchange_in_registers(assembly, name):
 
 @pytest.mark.parametrize("name", sorted(KERNELS))
 def test_exchange_costs_no_registers(assembly, name):
-    spill, scratch, occ = resources(assembly)[name]
+    spill, scratch, occ = isa.resources(assembly, {k: v[1] for k, v in KERNELS.items()})[name]
     pspill, pscratch, pocc = PARENT[name]
     print(f"{name}: spilled VGPRs {spill} (parent {pspill}), scratch {scratch} B (parent {pscratch}), occupancy {occ} (parent {pocc})")
     assert spill <= pspill, (name, "spilled VGPRs", spill, pspill)

@@ -15,14 +15,10 @@ The LDS-resident forms (<N, true, 4, *>) read the table from LDS and must carry 
 here and needs the walk).  Needs hipcc (cross-compiles without a GPU): one compile of all instantiations, about 20 s."""
 import os
 import re
-import shutil
-import subprocess
-import tempfile
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+import isa
 
 _FWD = "template __global__ void tsff::k_form_factor_2d<{n}, {lds}, {g}, {save}>(tsff::KStatic, const double*, const double*, int, double, double, int, long, long, double*, double*);"
 _ADJ = "template __global__ void tsff::k_form_factor_2d_adj<{n}, {lds}, {g}>(tsff::KStatic, const double*, const double*, int, double, double, int, long, long, const double*, double*, double*, const double*);"
@@ -41,23 +37,7 @@ for _n in (1, 2, 3, 4):
 @pytest.fixture(scope="module")
 def assembly():
     """device assembly of every instantiation of KERNELS, one compile"""
-    with tempfile.TemporaryDirectory() as d:
-        src, out = os.path.join(d, "all.hip"), os.path.join(d, "all.s")
-        insts = "\n".join(v[0] for v in KERNELS.values())
-        open(src, "w").write('#define TSFF_NO_API\n#include "%s"\n%s\n' % (os.path.join(ROOT, "tsadar_amd", "csrc", "tsff_kernels.hip"), insts))
-        subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-I" + os.path.join(ROOT, "include"),
-                        "-o", out, src], check=True, stderr=subprocess.DEVNULL)
-        return open(out).read()
-
-
-def _function(asm, prefix):
-    """the assembly of the one function whose mangled name starts with prefix"""
-    lines = asm.split("\n")
-    starts = [i for i, l in enumerate(lines) if l.startswith(prefix) and re.match(r"^_ZN4tsff\w+:", l)]
-    assert len(starts) == 1, (prefix, len(starts))
-    s = starts[0]
-    e = next(i for i in range(s, len(lines)) if lines[i].startswith(".Lfunc_end"))
-    return "\n".join(lines[s:e + 1])
+    return isa.compile_assembly(v[0] for v in KERNELS.values())
 
 
 def _regs(tok):
@@ -171,10 +151,10 @@ def _hand_written_requests(asm):
     return sum(1 for op, _, in_asm in insts if in_asm and op.startswith(_VMEM_LOAD))
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
+@pytest.mark.skipif(not os.path.exists(isa.HIPCC), reason="needs hipcc")
 @pytest.mark.parametrize("name", sorted(KERNELS))
 def test_request_registers_are_untouched_until_waited_for(assembly, name):
-    fn = _function(assembly, KERNELS[name][1])
+    fn = isa.function(assembly, KERNELS[name][1], end=".Lfunc_end")[1]
     n = _check(fn)
     if ", true, 4" in name:   # LDS-resident table: no hand-written requests (one added later needs this walk)
         assert n == 0 and _hand_written_requests(fn) == 0, n

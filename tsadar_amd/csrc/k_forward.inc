@@ -59,7 +59,7 @@ __global__ __launch_bounds__(kHalf * (3 - NPAIR), 2) void k_forward_pairs(KStati
   const int item = blockIdx.x;
   const int f_il = interleaved ? (int)(item >= K.B) : 0;
   const int b = item - f_il * K.B, tid = threadIdx.x;
-  constexpr int TPF = kHalf, NW = NT / 64, kPair = 2;
+  constexpr int TPF = kHalf, NW = NT / 64;
   const int ht = tid, lane = tid & 63, hw = tid >> 6;
   const int f = __builtin_amdgcn_readfirstlane(interleaved ? f_il : f0);
   extern __shared__ __align__(16) unsigned char smem[];
@@ -93,23 +93,16 @@ __global__ __launch_bounds__(kHalf * (3 - NPAIR), 2) void k_forward_pairs(KStati
     } else {   // the lineout scalars as k_fused_prep left them (wavefront-uniform address)
       lines_load<NI>(lrec + (size_t)item * kLineRec, 1, [](double v) { return uni(v); }, L);
     }
-    if (use_ks) {
-#pragma unroll
-      for (int p = 0; p < NPAIR; ++p)
-#pragma unroll
-        for (int q = 0; q <= kPair; ++q) ksc[min(jp[p] + q, npts - 1)] = ks_eval(ws[p][q], L.wpe2);
-    }
-    for (int i = ht; i < 8 * hs; i += NT) { const int ph_ = i / (2 * hs), o = i - ph_ * 2 * hs; xs[ph_ * Ls + (o < hs ? o : Ls - 2 * hs + o)] = 0.0; }
-    if (ht < 2) xs[4 * Ls + ht] = 0.0;
+    if (use_ks) ks_cache_fill(ksc, jp, ws, L.wpe2, npts);
+    zero_phase_halos(xs, Ls, hs, ht, NT);
   }
   // the two ends of a wavefront's 128-sample unit: first frequency of lane 0, third of lane 63 (see k_spectrum_fused)
   double w_hi[NPAIR];
   bool far[NPAIR];
 #pragma unroll
   for (int p = 0; p < NPAIR; ++p) {
-    const double w_lo = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(ws[p][0]), 0), __builtin_amdgcn_readlane(__double2loint(ws[p][0]), 0));
-    w_hi[p] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(ws[p][kPair]), 63), __builtin_amdgcn_readlane(__double2loint(ws[p][kPair]), 63));
-    far[p] = far_range_w<NI>(w_lo, w_hi[p], L);
+    w_hi[p] = lane_f64(ws[p][kPair], 63);
+    far[p] = far_range_w<NI>(lane_f64(ws[p][0], 0), w_hi[p], L);
   }
   const double ex_wse = (NPAIR == 2 && ((lane >> 4) & 1)) ? w_hi[NPAIR - 1] : w_hi[0];
   __syncthreads();
@@ -117,12 +110,7 @@ __global__ __launch_bounds__(kHalf * (3 - NPAIR), 2) void k_forward_pairs(KStati
   auto unit_of = [&](int P) { return NPAIR == 1 ? hw : 2 * hw + P; };   // 128-sample unit of this wavefront's pair P
   if (EX) {   // the unit-boundary base points of this wavefront's unit(s), all angles at once (lane = 16 P + a)
     const int Pb = (lane >> 4) & 1, ab = lane & 15;
-    if (lane < 16 * NPAIR && ab < NA) {
-      Base be;
-      base_eval<NI>(ex_wse, ks_eval(ex_wse, L.wpe2), m.cosa[ab], L, T, be);
-      double* o = exb + 16 * unit_of(Pb) + ab;
-      o[0] = be.wd; o[kExBound] = be.ik; o[2 * kExBound] = be.xe; o[3 * kExBound] = be.F; o[4 * kExBound] = be.dH;
-    }
+    if (lane < 16 * NPAIR && ab < NA) unit_boundary_fill<NI>(ex_wse, m.cosa[ab], L, T, exb + 16 * unit_of(Pb) + ab);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -148,14 +136,9 @@ __global__ __launch_bounds__(kHalf * (3 - NPAIR), 2) void k_forward_pairs(KStati
         const int j = jb + i;
         const bool has_next = (j + 1) < npts;
         Base b1;
-        if (EX && i == kPair - 1) {   // the next lane's first base point, register to register; the last lane takes the unit's boundary point
-          // (next_lane_f64: all 64 lanes are here -- the branches and loops around it are wavefront-uniform.  The forward value reads
-          //  xi_e and F of this point alone: the compiler drops the other three shifts and their boundary reads)
-          const double* src = exb + 16 * unit_of(P) + a;
-          b1.wd = next_lane_f64(b0f.wd, src[0]); b1.ik = next_lane_f64(b0f.ik, src[kExBound]); b1.xe = next_lane_f64(b0f.xe, src[2 * kExBound]);
-          b1.F = next_lane_f64(b0f.F, src[3 * kExBound]); b1.dH = next_lane_f64(b0f.dH, src[4 * kExBound]);
-          b1.ks = ks2;
-          b1.k2 = base_k2<NI>(ks2, ct, L);
+        if (EX && i == kPair - 1) {   // the next lane's first base point; the last lane takes the unit's boundary point
+          // (The forward value reads xi_e and F of this point alone: the compiler drops the other three shifts and their boundary reads)
+          neighbour_take<NI>(b0f, exb + 16 * unit_of(P) + a, ks2, ct, L, b1);
         } else {
           base_eval<NI>(ws[P][i + 1], use_ks ? ksc[min(j + 1, npts - 1)] : ks_eval(ws[P][i + 1], L.wpe2), ct, L, T, b1);
         }
@@ -173,10 +156,7 @@ __global__ __launch_bounds__(kHalf * (3 - NPAIR), 2) void k_forward_pairs(KStati
 #pragma unroll
     for (int p = 0; p < NPAIR; ++p)
 #pragma unroll
-      for (int i = 0; i < kPair; ++i) {
-        const double w = ws[p][i];
-        xs[XA(jp[p] + i)] = xa[p][i] * (filt ? w * w * S.filt[jp[p] + i] : w * w);
-      }
+      for (int i = 0; i < kPair; ++i) store_scaled(xs + XA(jp[p] + i), xa[p][i], ws[p][i], filt, S.filt, jp[p] + i);
   }
   __syncthreads();
 

@@ -483,8 +483,7 @@ __global__ __launch_bounds__(2 * kHalf, TSFF_OCC) void k_spectrum(KStatic S, KCa
     // FMAs of the linear form: the convolution stops being LDS-bandwidth bound.
     // (constant address space: the padded taps are read-only for the whole launch, so the wavefront-uniform reads
     //  below become scalar loads and cost neither LDS bandwidth nor vector-memory instructions)
-    typedef const double __attribute__((address_space(4))) cdouble;
-    cdouble* pt = (cdouble*)(S.ptaps[f] + S.cf_i0[f]);
+    cdouble_t* pt = (cdouble_t*)(S.ptaps[f] + S.cf_i0[f]);
     const double* __restrict__ X0 = xs, * __restrict__ X1 = xs + Ls, * __restrict__ X2 = xs + 2 * Ls, * __restrict__ X3 = xs + 3 * Ls;
     int sl = ht + S.cf_a0[f] + hs;
     double V0 = X0[sl], V1 = X1[sl], V2 = X2[sl];
@@ -493,10 +492,7 @@ __global__ __launch_bounds__(2 * kHalf, TSFF_OCC) void k_spectrum(KStatic S, KCa
       const double V3 = X3[sl], V4 = X0[sl + 1], V5 = X1[sl + 1], V6 = X2[sl + 1];
       const double g0 = pt[4 * a], g1 = pt[4 * a + 1], g2 = pt[4 * a + 2], g3 = pt[4 * a + 3];
       // (index % BPT: the branch is dead, but must compile, in the 512-threads-per-feature instantiation)
-      ybin[0] = __builtin_fma(g3, V3, __builtin_fma(g2, V2, __builtin_fma(g1, V1, __builtin_fma(g0, V0, ybin[0]))));
-      ybin[1 % BPT] = __builtin_fma(g3, V4, __builtin_fma(g2, V3, __builtin_fma(g1, V2, __builtin_fma(g0, V1, ybin[1 % BPT]))));
-      ybin[2 % BPT] = __builtin_fma(g3, V5, __builtin_fma(g2, V4, __builtin_fma(g1, V3, __builtin_fma(g0, V2, ybin[2 % BPT]))));
-      ybin[3 % BPT] = __builtin_fma(g3, V6, __builtin_fma(g2, V5, __builtin_fma(g1, V4, __builtin_fma(g0, V3, ybin[3 % BPT]))));
+      conv_taps4(g0, g1, g2, g3, V0, V1, V2, V3, V4, V5, V6, ybin[0], ybin[1 % BPT], ybin[2 % BPT], ybin[3 % BPT]);
       V0 = V4; V1 = V5; V2 = V6;
     }
   } else {
@@ -586,8 +582,7 @@ __global__ __launch_bounds__(2 * kHalf, TSFF_OCC) void k_spectrum(KStatic S, KCa
   // ================= adjoint of convolution + binning: xbar_i = filt_i sum_p ybar_p hb[i - p ppp - toff] =================
   if (ph) {
     // xbar[4 ht + r] = sum_u g'(u) ybar[4 ht + r + u], g'(u) = hb[-toff - u]: the same sliding window, taps read backwards
-    typedef const double __attribute__((address_space(4))) cdouble;
-    cdouble* pt = (cdouble*)(S.ptaps[f] + S.ca_i0[f]);
+    cdouble_t* pt = (cdouble_t*)(S.ptaps[f] + S.ca_i0[f]);
     const double* __restrict__ Y0 = ybs, * __restrict__ Y1 = ybs + Ls, * __restrict__ Y2 = ybs + 2 * Ls, * __restrict__ Y3 = ybs + 3 * Ls;
     int sl = ht + S.ca_a0[f] + hs;
     double V0 = Y0[sl], V1 = Y1[sl], V2 = Y2[sl];
@@ -596,10 +591,7 @@ __global__ __launch_bounds__(2 * kHalf, TSFF_OCC) void k_spectrum(KStatic S, KCa
     for (int a = 0; a < na; ++a, ++sl) {
       const double V3 = Y3[sl], V4 = Y0[sl + 1], V5 = Y1[sl + 1], V6 = Y2[sl + 1];
       const double g0 = pt[-4 * a], g1 = pt[-4 * a - 1], g2 = pt[-4 * a - 2], g3 = pt[-4 * a - 3];
-      sx[0] = __builtin_fma(g3, V3, __builtin_fma(g2, V2, __builtin_fma(g1, V1, __builtin_fma(g0, V0, sx[0]))));
-      sx[1] = __builtin_fma(g3, V4, __builtin_fma(g2, V3, __builtin_fma(g1, V2, __builtin_fma(g0, V1, sx[1]))));
-      sx[2] = __builtin_fma(g3, V5, __builtin_fma(g2, V4, __builtin_fma(g1, V3, __builtin_fma(g0, V2, sx[2]))));
-      sx[3] = __builtin_fma(g3, V6, __builtin_fma(g2, V5, __builtin_fma(g1, V4, __builtin_fma(g0, V3, sx[3]))));
+      conv_taps4(g0, g1, g2, g3, V0, V1, V2, V3, V4, V5, V6, sx[0], sx[1], sx[2], sx[3]);
       V0 = V4; V1 = V5; V2 = V6;
     }
     __syncthreads();   // (ybar and x share their memory: every read of ybar before the first write of xbar)

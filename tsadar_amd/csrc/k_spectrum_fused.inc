@@ -25,141 +25,6 @@
 // Reference rows: a4-a15 of SURVEY.md section 8 exactly as k_spectrum (form_factor.py:182-298, generate_spectra.py:139-220,
 // irf.py:50-132, loss_function.py:190-418, and reverse-mode differentiation of those, loss_function.py:108).
 
-// point_reverse with the seed PQ = w_a pref (no spectrum adjoint yet): returns S (1 + 2w/wL), whose PQ-fold is the contribution
-// to x_j (before the factor ws^2), the adjoints of this point's base quantities (ba) and of the right neighbour's (xi_e, F),
-// and accumulates the direct lineout-scalar adjoints into the row J.  cw = -i2wL^2 / 2 folds the adjoint of 2/wL into wL.
-// The deferred factor of a_i (x -1/2) is applied after the contraction (see the kernel); pref's adjoint is x_j itself.
-template <int NI, int GM, bool ZH, bool FAR = false>
-__device__ __forceinline__ double point_fused(const Base& b, const Base& bn, bool has_next, const LineS<NI>& L, const Tables& T,
-                                              double PQ, double cw, BaseAdj& ba, double& xen, double& Fn, LineS<NI>& J) {
-  // ---- forward (form_factor.py:243-296) ----
-  PointF<NI> pf;
-  point_core<NI, ZH, FAR>(b, bn, has_next, L, T, pf);
-  const double ik2 = pf.ik2, ike2 = pf.ike2, vph = pf.vph, gsum = pf.gsum, Wl = pf.Wl, dW = pf.dW, idx = pf.idx, D = pf.D;
-  const double cer = pf.cer, cei = pf.cei, opc = pf.opc, cim = pf.cim, er = pf.er, ei = pf.ei, ieps2 = pf.ieps2, ce2 = pf.ce2, ci2 = pf.ci2;
-  const double N = pf.N, t1 = pf.t1, S = pf.S, dop = pf.dop;
-  const double* xi = pf.xi; const double* zr = pf.zr; const double* zi = pf.zi; const double* dzr = pf.dzr; const double* dzi = pf.dzi;
-  const double* hk = pf.hk; const double* gs = pf.gs;
-  // ---- reverse with the seed PQ ----
-  const double Sb = PQ * dop;
-  const double PSQ = PQ * S;
-  const double fwd = S * dop;   // (x PQ by the caller: the association of k_spectrum's forward sweep, bit for bit)
-  J.wL = __builtin_fma(PSQ * b.wd, cw, J.wL);
-  const double Nb = Sb * t1;
-  const double ikb0 = Sb * N * ieps2;
-  const double e2 = -2.0 * (ikb0 * t1);
-  const double NbI = Nb * L.ivTe;
-  const double ci2b2 = 2.0 * (NbI * b.F);
-  ba.F = NbI * ci2;
-  J.ivTe += (Nb * ci2) * b.F;
-  const double erb = e2 * er, eib = e2 * ei;
-  double cerb = erb, ceib = eib, cimb = eib;
-  if (!FAR) {   // (FAR: gsum = 0 and Im chi_i = 0 identically)
-    const double ce2b2 = 2.0 * (Nb * gsum);       // 2 x adjoint of |chi_e|^2
-    cerb = erb + ce2b2 * cer; ceib = eib + ce2b2 * cei;
-    cimb = eib + ci2b2 * cim;
-  }
-  const double creb = erb + ci2b2 * opc;
-  const double cp = ceib * kPi;
-  const double ike2b = cp * D - cerb * Wl;
-  const double Wlb = -cerb * ike2;
-  ba.xe = Wlb * dW;
-  if (GM == 1) {
-    double Wml, dWm;
-    w_lookup(T.Wm, b.xe, Wml, dWm);
-    J.m += Wlb * Wml;
-  }
-  Fn = (cp * ike2) * idx;
-  ba.F -= Fn;
-  xen = -Fn * D;
-  ba.xe -= xen;
-  double k2acc = 0.0, vphb = 0.0;
-  const double u = FAR ? 0.0 : Nb * ce2;
-#pragma unroll
-  for (int s = 0; s < NI; ++s) {
-    double w, xib;
-    if (FAR) {   // gs = Im Z' = d Im Z' = 0
-      w = creb * zr[s];
-      xib = hk[s] * (creb * dzr[s]);
-    } else {
-      const double v = u * gs[s];
-      J.cs[s] += v;
-      w = creb * zr[s] + cimb * zi[s];
-      xib = -2.0 * (v * xi[s] * L.cs[s]) + hk[s] * (creb * dzr[s] + cimb * dzi[s]);
-    }
-    const double wk = w * ik2;
-    J.a_i[s] += wk;
-    k2acc += wk * hk[s];
-    vphb += xib * L.ixi[s];
-    J.ixi[s] += xib * vph;
-  }
-  const double we = ike2b * ik2;
-  J.a_e += we;
-  ba.k2 = -k2acc - we * ike2;
-  ba.wd = PSQ * L.i2wL + vphb * b.ik;
-  ba.ik = ikb0 + vphb * b.wd;
-  return fwd;
-}
-
-// The adjoint of k^2 = k_s^2 + k_L^2 - 2 k_s k_L cos(theta) flows to k_L and, through k_s(lambda), to omega_pe^2:
-//   kLbar += k22 (k_L - k_s ct),   wpe2bar -= k22 (k_s - k_L ct) / (2 c^2 k_s),      k22 = 2 x adjoint of k^2.
-// k_s depends on the wavelength sample only and ct = cos(theta_a) on the angle only, so a row accumulates P1 = sum_a k22 and
-// P2 = sum_a k22 ct per base point (its own sample and the right neighbour) -- two instructions per base where the direct form
-// took ten, a reciprocal of k_s among them -- and the two columns are assembled once per sample after the angle loop:
-//   kLbar = k_L (P1a + P1b) - (k_s,j P2a + k_s,j+1 P2b),   wpe2bar = -[P1a + P1b - k_L (P2a / k_s,j + P2b / k_s,j+1)] / (2 c^2).
-struct KsAcc { double p1a, p2a, p1b, p2b; };
-
-// base_reverse (tsff_device.h) without its k_L / omega_pe^2 tail: returns k22
-template <int NI, int GM>
-__device__ __forceinline__ double base_reverse_fused(const Base& b, const LineS<NI>& L, const Tables& T, const BaseAdj& ba,
-                                                     LineS<NI>& LB) {
-  const double Hb = ba.F * b.F;  // adjoint of H = ln f_e(xi_e)
-  if (GM == 1) {  // d ln f_e(xi_e)/dm: Hermite interpolant of the tangent table (zero outside the vx grid)
-    Tables Tm = T;
-    Tm.hc = T.hcm;
-    double Hm, dHm;
-    hermite_lookup_c(Tm, b.xe, Hm, dHm);
-    LB.m += (b.xe < T.vx0 || b.xe > T.vxlast) ? 0.0 : Hb * Hm;
-  }
-  const double xeb = ba.xe + Hb * b.dH;
-  const double vph = b.wd * b.ik, k = b.k2 * b.ik;
-  const double vphb = xeb * L.ivTe;
-  LB.Ud -= vphb;
-  LB.ivTe += xeb * (vph - L.Ud);
-  const double wdb = ba.wd + vphb * b.ik;
-  const double ikb = ba.ik + vphb * b.wd;
-  LB.wL -= wdb;
-  LB.Vd -= wdb * k;
-  const double kb = wdb * L.Vd + ikb * (b.ik * b.ik);
-  return 2.0 * ba.k2 - kb * b.ik;
-}
-
-// the same for a base point that receives adjoints of (xi_e, F) only: the right neighbour of a point, through the finite
-// difference D = (F_{j+1} - F_j)/(xi_{e,j+1} - xi_{e,j})
-template <int NI, int GM>
-__device__ __forceinline__ double base_reverse_xf(const Base& b, const LineS<NI>& L, const Tables& T, double xeb_in, double Fb,
-                                                  LineS<NI>& LB) {
-  const double Hb = Fb * b.F;
-  if (GM == 1) {
-    Tables Tm = T;
-    Tm.hc = T.hcm;
-    double Hm, dHm;
-    hermite_lookup_c(Tm, b.xe, Hm, dHm);
-    LB.m += (b.xe < T.vx0 || b.xe > T.vxlast) ? 0.0 : Hb * Hm;
-  }
-  const double xeb = xeb_in + Hb * b.dH;
-  const double vph = b.wd * b.ik, k = b.k2 * b.ik;
-  const double vphb = xeb * L.ivTe;
-  LB.Ud -= vphb;
-  LB.ivTe += xeb * (vph - L.Ud);
-  const double wdb = vphb * b.ik;
-  const double ikb = vphb * b.wd;
-  LB.wL -= wdb;
-  LB.Vd -= wdb * k;
-  const double kb = wdb * L.Vd + ikb * (b.ik * b.ik);
-  return -kb * b.ik;
-}
-
 // TSFF_TRACE (measurement builds only, scripts/trace_fused.py): phase time stamps of every workgroup (s_memrealtime, 100 MHz)
 #ifdef TSFF_TRACE
 __device__ unsigned long long* g_trace_buf = nullptr;
@@ -171,107 +36,6 @@ __device__ unsigned long long* g_trace_buf = nullptr;
 #define TSFF_STAMP_WAVE(k) do {} while (0)
 #define TSFF_STAMP_HW() do {} while (0)
 #endif
-// The phase-layout convolution of k_spectrum (four adjacent outputs per thread, groups of four taps read by scalar loads from the
-// zero-padded tap array in constant memory, the explicit FMA chains that pin the roundings), unrolled by two so that the sliding
-// window of seven spectrum values is renamed instead of moved (three 64-bit moves per 16 FMAs in the rolled form).  DIR = +1: taps
-// ascending (forward), -1: descending (adjoint).  Same sums, same order, same bits as k_spectrum's loop.
-// (Tried and dropped, profiles/r03k: the same loop software-pipelined with the taps read from an LDS copy -- scalar and LDS loads
-//  share one counter that can only be drained completely, and the kernel has no SGPRs left to carry a group of taps across the back
-//  edge -- costs more VALU instructions for its addresses than the waits it removes: conv + arg-max 5.5 / 8.0 us against 4.8 / 6.7.)
-//
-// r08_conv (DESIGN.md section 4.1b): the loop is software-pipelined over SETS of two tap groups.  A set is what the 32 FMAs of two groups read:
-// eleven window values (22 VGPRs) and eight taps (16 SGPRs).  The rolled form requested its set at the top of an
-// iteration and waited for it in front of the first FMA -- an LDS plus scalar-cache round trip exposed before every 32 FMAs, with
-// nothing in flight while they issue.  Now the set of groups a + 2, a + 3 is requested while the FMAs of groups a, a + 1 issue:
-//   wait (everything outstanding: exactly the current set) | request the next set | 32 FMAs on the current set
-// twice per loop body, the two register sets changing roles by renaming.  Scalar loads and LDS reads share one counter and scalar
-// loads return out of order, so the only exact wait is "all of it": it is written out (conv_wait) where NOTHING but the current
-// set is outstanding, and the request follows it at once; the scheduling barriers keep the machine scheduler from sinking the
-// requests to their uses (as it did with the boundary point of the sweep, DESIGN.md section 4.1b).
-// Same sums, same order, same bits: the four accumulators are the same explicit chains over the groups 0 .. na - 1.
-//
-// Reading ahead.  Every request is for two groups (a, a + 1) with a even and a <= na (the first one, a = 0; in the loop body a + 4
-// <= na; in the tail a + 2 <= na), so the highest group ever read is na + 1 -- two beyond the last one used.
-//   taps, forward (pt = ptaps + cf_i0, ascending): highest entry cf_i0 + 4 (na + 1) + 3 = cf_i0 + 4 na + 7 < padded_taps() =
-//     cf_i0 + 4 na + 8; the host array has kTapLead + n + 16 entries and cf_i0 + 4 na + 7 <= (3 - pre) + (pre + n + 3) + 7 = n + 13.
-//   taps, adjoint (pt = ptaps + ca_i0, descending): lowest entry ca_i0 - 4 (na + 1) - 3 >= (n + 2 + prea) - (prea + n + 3) - 7
-//     = -8 = -kTapLead: S.ptaps points kTapLead zeros INTO its allocation (tsff_api.inc), the highest entry is ca_i0 <= n + 5.
-//   window: sl = ht + a0 + hs with 0 <= ht < 256 and, by the definition of S.hs, -a0 <= hs - 1 and a0 + na <= hs - 1, so
-//     sl >= 1; the highest index is X2[(na + 1) + 1] = 2 Ls + sl + na + 2 <= 2 Ls + 255 + 2 hs + 1 = 3 Ls (Ls = 256 + 2 hs), and
-//     X3[na + 1] <= 3 Ls + Ls - 1: inside the four phase arrays (4 Ls + 2 doubles) for every na >= 1.
-// What is read beyond group na - 1 is never used.
-// PIPE = false: the rolled loop (k_forward_pairs: see there).
-typedef const double __attribute__((address_space(4))) cdouble_t;
-struct ConvSet { double w[11], g[8]; };
-// groups a, a + 1: the window values V0 .. V6 of the first, V3 .. V6 of the second and their taps.  (V0 .. V2 are the V4 .. V6 of
-// the group before and could be inherited from the previous set -- but then three registers of a set are still read when the set
-// is requested again, the allocator loads into temporaries and copies them behind a wait of its own in the middle of the FMAs.)
-template <int DIR>
-__device__ __forceinline__ void conv_request(const double* __restrict__ X0, const double* __restrict__ X1, const double* __restrict__ X2,
-                                             const double* __restrict__ X3, cdouble_t* pt, int a, int at, ConvSet& s) {
-  s.w[0] = X0[a]; s.w[1] = X1[a]; s.w[2] = X2[a];
-  s.w[3] = X3[a]; s.w[4] = X0[a + 1]; s.w[5] = X1[a + 1]; s.w[6] = X2[a + 1];
-  s.w[7] = X3[a + 1]; s.w[8] = X0[a + 2]; s.w[9] = X1[a + 2]; s.w[10] = X2[a + 2];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) s.g[k] = pt[DIR * (4 * at + k)];
-  __builtin_amdgcn_sched_barrier(0);
-}
-__device__ __forceinline__ void conv_wait() {
-  __builtin_amdgcn_sched_barrier(0);
-  __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0), vmcnt and expcnt left alone
-  __builtin_amdgcn_sched_barrier(0);
-}
-// one tap group (H = 0, 1: which half of the set); the window slides by renaming
-template <int H>
-__device__ __forceinline__ void conv_group(const ConvSet& s, double (&acc)[4]) {
-  const double V0 = s.w[4 * H], V1 = s.w[4 * H + 1], V2 = s.w[4 * H + 2];
-  const double V3 = s.w[4 * H + 3], V4 = s.w[4 * H + 4], V5 = s.w[4 * H + 5], V6 = s.w[4 * H + 6];
-  const double g0 = s.g[4 * H], g1 = s.g[4 * H + 1], g2 = s.g[4 * H + 2], g3 = s.g[4 * H + 3];
-  acc[0] = __builtin_fma(g3, V3, __builtin_fma(g2, V2, __builtin_fma(g1, V1, __builtin_fma(g0, V0, acc[0]))));
-  acc[1] = __builtin_fma(g3, V4, __builtin_fma(g2, V3, __builtin_fma(g1, V2, __builtin_fma(g0, V1, acc[1]))));
-  acc[2] = __builtin_fma(g3, V5, __builtin_fma(g2, V4, __builtin_fma(g1, V3, __builtin_fma(g0, V2, acc[2]))));
-  acc[3] = __builtin_fma(g3, V6, __builtin_fma(g2, V5, __builtin_fma(g1, V4, __builtin_fma(g0, V3, acc[3]))));
-}
-template <int DIR, bool PIPE = true>
-__device__ __forceinline__ void conv4_phase(const double* __restrict__ xs, int Ls, int sl, cdouble_t* pt, int na, double (&acc)[4]) {
-  const double* __restrict__ X0 = xs + sl, * __restrict__ X1 = X0 + Ls, * __restrict__ X2 = X1 + Ls, * __restrict__ X3 = X2 + Ls;
-  if (!PIPE) {
-    double V0 = X0[0], V1 = X1[0], V2 = X2[0];
-#pragma unroll 2
-    for (int a = 0; a < na; ++a) {
-      const double V3 = X3[a], V4 = X0[a + 1], V5 = X1[a + 1], V6 = X2[a + 1];
-      const double g0 = pt[4 * DIR * a], g1 = pt[4 * DIR * a + DIR], g2 = pt[4 * DIR * a + 2 * DIR], g3 = pt[4 * DIR * a + 3 * DIR];
-      acc[0] = __builtin_fma(g3, V3, __builtin_fma(g2, V2, __builtin_fma(g1, V1, __builtin_fma(g0, V0, acc[0]))));
-      acc[1] = __builtin_fma(g3, V4, __builtin_fma(g2, V3, __builtin_fma(g1, V2, __builtin_fma(g0, V1, acc[1]))));
-      acc[2] = __builtin_fma(g3, V5, __builtin_fma(g2, V4, __builtin_fma(g1, V3, __builtin_fma(g0, V2, acc[2]))));
-      acc[3] = __builtin_fma(g3, V6, __builtin_fma(g2, V5, __builtin_fma(g1, V4, __builtin_fma(g0, V3, acc[3]))));
-      V0 = V4; V1 = V5; V2 = V6;
-    }
-    return;
-  }
-  ConvSet A, B;
-  conv_request<DIR>(X0, X1, X2, X3, pt, 0, 0, A);
-  int a = 0;
-  for (; a + 4 <= na; a += 4) {   // two sets per body: A holds groups a, a + 1 on entry
-    conv_wait();
-    conv_request<DIR>(X0, X1, X2, X3, pt, a + 2, 2, B);
-    conv_group<0>(A, acc); conv_group<1>(A, acc);
-    conv_wait();
-    conv_request<DIR>(X0, X1, X2, X3, pt, a + 4, 4, A);
-    conv_group<0>(B, acc); conv_group<1>(B, acc);
-    pt += 16 * DIR;   // (the taps through a running scalar pointer, the window through the index: the fewest address instructions)
-  }
-  // the last na - a = 0 .. 3 groups: A holds the first two of them (requested, not yet waited for)
-  conv_wait();
-  if (na - a >= 2) {
-    conv_request<DIR>(X0, X1, X2, X3, pt, a + 2, 2, B);
-    conv_group<0>(A, acc); conv_group<1>(A, acc);
-    conv_wait();
-    if (na - a == 3) conv_group<0>(B, acc);
-  } else if (na - a == 1) {
-    conv_group<0>(A, acc);
-  }
-}
 
 constexpr int kRedSums = 32;   // offset (doubles) of the five partial block sums in the reduction scratch
 // EX: the third base point of a pair -- the right neighbour of its second sample, which is the FIRST sample of the next
@@ -318,7 +82,6 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_fused(KStatic S, KCall K,
   Tables T;
   const double lam_shift = S.lam_shift[f];
   const double* __restrict__ omgs = S.omgs[f];
-  constexpr int kPair = 2;
   const int jp[2] = {kPair * ht, npts / 2 + kPair * ht};
   double ws[2][kPair + 1];
   LineS<NI> L;
@@ -340,17 +103,8 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_fused(KStatic S, KCall K,
     {
       lines_load<NI>(lrec + gitem * kLineRec, 1, [](double v) { return uni(v); }, L);
     }
-    if (use_ks) {
-      // k_s(lambda) of this lineout (angle independent, form_factor.py:218), by every wavefront for the samples its own lanes read:
-      // its two 128-sample units and the sample right of each (which the next wavefront writes too -- the same value)
-#pragma unroll
-      for (int p = 0; p < 2; ++p)
-#pragma unroll
-        for (int q = 0; q <= kPair; ++q) ksc[min(jp[p] + q, npts - 1)] = ks_eval(ws[p][q], L.wpe2);
-    }
-    // the halos of the four phase arrays (the samples themselves are all written at the end of the sweep)
-    for (int i = ht; i < 8 * hs; i += TPF) { const int ph_ = i / (2 * hs), o = i - ph_ * 2 * hs; xs[ph_ * Ls + (o < hs ? o : Ls - 2 * hs + o)] = 0.0; }
-    if (ht < 2) xs[4 * Ls + ht] = 0.0;
+    if (use_ks) ks_cache_fill(ksc, jp, ws, L.wpe2, npts);
+    zero_phase_halos(xs, Ls, hs, ht, TPF);
   }
   // Away from the laser line every point of a wavefront's pair sees |xi_i| >> 1: the ion terms are the asymptote and
   // exp(-xi_i^2) = 0 exactly (point_core<FAR>).  Decided once per (wavefront, pair) from a bound that holds for all its 128
@@ -360,8 +114,8 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_fused(KStatic S, KCall K,
   double w_lo[2], w_hi[2];
 #pragma unroll
   for (int p = 0; p < 2; ++p) {
-    w_lo[p] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(ws[p][0]), 0), __builtin_amdgcn_readlane(__double2loint(ws[p][0]), 0));
-    w_hi[p] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(ws[p][kPair]), 63), __builtin_amdgcn_readlane(__double2loint(ws[p][kPair]), 63));
+    w_lo[p] = lane_f64(ws[p][0], 0);
+    w_hi[p] = lane_f64(ws[p][kPair], 63);
   }
   const bool far0 = far_range_w<NI>(w_lo[0], w_hi[0], L), far1 = far_range_w<NI>(w_lo[1], w_hi[1], L);
   // (EX) frequency of the unit-boundary base point this lane evaluates behind the barrier (lane = 16 P + a)
@@ -386,13 +140,7 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_fused(KStatic S, KCall K,
   double* exb = m.ex;
   if (EX) {   // the unit-boundary base points of this wavefront's two units, all angles at once (lane = 16 P + a)
     const int Pb = (lane >> 4) & 1, ab = lane & 15;
-    if (lane < 32 && ab < NA) {
-      const double wse = ex_wse;
-      Base be;
-      base_eval<NI>(wse, ks_eval(wse, L.wpe2), m.cosa[ab], L, T, be);   // (k_s directly: the cache entry may belong to another wavefront)
-      double* o = exb + 16 * (2 * hw + Pb) + ab;
-      o[0] = be.wd; o[kExBound] = be.ik; o[2 * kExBound] = be.xe; o[3 * kExBound] = be.F; o[4 * kExBound] = be.dH;
-    }
+    if (lane < 32 && ab < NA) unit_boundary_fill<NI>(ex_wse, m.cosa[ab], L, T, exb + 16 * (2 * hw + Pb) + ab);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   // (the sweep reads other lanes' boundary points)
@@ -412,34 +160,22 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_fused(KStatic S, KCall K,
       Base b0;
       base_eval<NI>(ws[P][0], use_ks ? ksc[jb] : ks_eval(ws[P][0], L.wpe2), ct, L, T, b0);
       // (EX) the lane's FIRST base point of this angle is what its left neighbour asks for: b0 itself is the second one by then
-      const double f_wd = b0.wd, f_ik = b0.ik, f_xe = b0.xe, f_F = b0.F, f_dH = b0.dH;
+      const Base b0f = b0;
 #pragma unroll
       for (int i = 0; i < kPair; ++i) {
         constexpr int q0 = kPair * P;
         const int q = q0 + i, j = jb + i;
         const bool has_next = (j + 1) < npts;
         Base b1;
-        if (EX && i == kPair - 1) {   // the neighbour lane's first base point (the unit's boundary point for the last lane), register
-          // to register (next_lane_f64; all 64 lanes are here: the branches and loops around it are wavefront-uniform)
+        if (EX && i == kPair - 1) {   // the neighbour lane's first base point (the unit's boundary point for the last lane)
           // (The boundary point is read HERE.  Read an iteration ahead, as ct_n / wa_n are, or at the top of the iteration, its five
           //  doubles live across the pair's first point and the allocator spills 26 / 10 registers outside the loops where this form
           //  spills none; measured, DESIGN.md section 4.1b.)
-          const double* src = exu + a;
-          b1.wd = next_lane_f64(f_wd, src[0]); b1.ik = next_lane_f64(f_ik, src[kExBound]); b1.xe = next_lane_f64(f_xe, src[2 * kExBound]);
-          b1.F = next_lane_f64(f_F, src[3 * kExBound]); b1.dH = next_lane_f64(f_dH, src[4 * kExBound]);
-          b1.ks = ks2;
-          b1.k2 = base_k2<NI>(ks2, ct, L);   // (base_eval's own expression: the same bits; k itself -- a separately rounded
-                                             //  square root there, not k2 * ik -- only enters through wd, which is exchanged)
+          neighbour_take<NI>(b0f, exu + a, ks2, ct, L, b1);
         } else {
           base_eval<NI>(ws[P][i + 1], use_ks ? ksc[min(j + 1, npts - 1)] : ks_eval(ws[P][i + 1], L.wpe2), ct, L, T, b1);
         }
-        BaseAdj ba;
-        double xen, Fn;
-        xa[q] = __builtin_fma(wa, point_fused<NI, GM, ZH, FAR>(b0, b1, has_next, L, T, wa, cw, ba, xen, Fn, J[q]), xa[q]);
-        const double k22a = base_reverse_fused<NI, GM>(b0, L, T, ba, J[q]);
-        const double k22b = base_reverse_xf<NI, GM>(b1, L, T, xen, Fn, J[q]);   // (xen = Fn = 0 at the last sample)
-        KA[q].p1a += k22a; KA[q].p2a = __builtin_fma(k22a, ct, KA[q].p2a);
-        KA[q].p1b += k22b; KA[q].p2b = __builtin_fma(k22b, ct, KA[q].p2b);
+        row_step<NI, GM, ZH, FAR>(b0, b1, has_next, L, T, ct, wa, cw, xa[q], J[q], KA[q]);
         b0 = b1;
       }
     }
@@ -452,24 +188,18 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_fused(KStatic S, KCall K,
     const int j = JQ(q);
     const double ksa = use_ks ? ksc[j] : ks_eval(ws[q >> 1][q & 1], L.wpe2);
     const double ksb = use_ks ? ksc[min(j + 1, npts - 1)] : ks_eval(ws[q >> 1][(q & 1) + 1], L.wpe2);
-    const double p1 = KA[q].p1a + KA[q].p1b;
-    J[q].kL = L.kL * p1 - (ksa * KA[q].p2a + ksb * KA[q].p2b);
-    J[q].wpe2 = -(0.5 / (kC * kC)) * (p1 - L.kL * (KA[q].p2a / ksa + KA[q].p2b / ksb));
+    ks_columns<NI>(KA[q], ksa, ksb, L, J[q]);
   }
   {   // the factor ws^2 (left out of the sweep) and the notch filter of the electron feature: x_j and xbar_j carry it
     const bool filt = f == TSFF_FEATURE_ELE && S.filt;
 #pragma unroll
-    for (int q = 0; q < kStrip; ++q) {
-      const double w = ws[q >> 1][q & 1];
-      xs[XA(JQ(q))] = xa[q] * (filt ? w * w * S.filt[JQ(q)] : w * w);
-    }
+    for (int q = 0; q < kStrip; ++q) store_scaled(xs + XA(JQ(q)), xa[q], ws[q >> 1][q & 1], filt, S.filt, JQ(q));
   }
   __syncthreads();
   TSFF_STAMP(3);
 
   // ================= IRF convolution ("same"), bin average, normalisation (phase layout, see k_spectrum) =================
   constexpr int BPT = 4;
-  typedef const double __attribute__((address_space(4))) cdouble;
   // What the chain needs from global memory is requested HERE, ahead of the convolution -- the chain is a sequence of latencies and
   // every microsecond of it is a microsecond in which this wavefront's SIMD issues at half rate: the measured data of the
   // thread's four bins (first touch: HBM), masks, bin wavelengths and the last stage's parameter transform.

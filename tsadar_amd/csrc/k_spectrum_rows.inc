@@ -1,6 +1,6 @@
 // k_spectrum_rows.inc -- k_spectrum_rows: the one-sweep loss + gradient kernel for points_per_pixel > 1 (the reference's default
 // decks: 5 points per pixel, 5120 wavelength samples per feature).  Part of the single translation unit tsff_kernels.hip
-// (included inside namespace tsff, after k_spectrum_fused.inc whose per-point functions it uses).
+// (included inside namespace tsff, after k_pairs.inc whose per-point functions and sweep steps it uses).
 //
 // k_spectrum_fused keeps the Jacobian rows J[j][k] of a thread's four samples in registers until the adjoint xbar_j of the
 // spectrum is known.  With npts = 1024 ppp samples a thread owns 4 ppp of them and the rows no longer fit: here the sweep runs
@@ -113,7 +113,6 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_rows(KStatic S, KCall K, 
     make_lines_uniform<NI>(p, lam_shift, 0, 1, L);
   }
   __syncthreads();
-  constexpr int kPair = 2;
   const double cw = -0.5 * L.i2wL * L.i2wL;
   const bool split = flags & 16;
   const int rd_first = split ? (int)blockIdx.y : 0, rd_last = split ? (int)blockIdx.y + 1 : ppp;
@@ -141,11 +140,7 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_rows(KStatic S, KCall K, 
       const int Pb = (lane >> 4) & 1, ab = lane & 15;
       if (lane < 32 && ab < NA) {
         const int jend = min(rd * TSFF_NBINS + (Pb ? TSFF_NBINS / 2 : 0) + kPair * 64 * (hw + 1), npts - 1);
-        const double wse = omgs[jend];
-        Base be;
-        base_eval<NI>(wse, ks_eval(wse, L.wpe2), m.cosa[ab], L, T, be);
-        double* o = exb + 16 * (2 * hw + Pb) + ab;
-        o[0] = be.wd; o[kExBound] = be.ik; o[2 * kExBound] = be.xe; o[3 * kExBound] = be.F; o[4 * kExBound] = be.dH;
+        unit_boundary_fill<NI>(omgs[jend], m.cosa[ab], L, T, exb + 16 * (2 * hw + Pb) + ab);
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
@@ -184,13 +179,7 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_rows(KStatic S, KCall K, 
           if constexpr (FWD) {
             xa[q] = __builtin_fma(wa, point_forward_sd<NI, ZH, FAR>(b0, b1, has_next, L, T), xa[q]);
           } else {
-            BaseAdj ba;
-            double xen, Fn;
-            xa[q] = __builtin_fma(wa, point_fused<NI, GM, ZH, FAR>(b0, b1, has_next, L, T, wa, cw, ba, xen, Fn, J[q]), xa[q]);
-            const double k22a = base_reverse_fused<NI, GM>(b0, L, T, ba, J[q]);
-            const double k22b = base_reverse_xf<NI, GM>(b1, L, T, xen, Fn, J[q]);   // (xen = Fn = 0 at the last sample)
-            KA[q].p1a += k22a; KA[q].p2a = __builtin_fma(k22a, ct, KA[q].p2a);
-            KA[q].p1b += k22b; KA[q].p2b = __builtin_fma(k22b, ct, KA[q].p2b);
+            row_step<NI, GM, ZH, FAR>(b0, b1, has_next, L, T, ct, wa, cw, xa[q], J[q], KA[q]);
           }
           b0 = b1;
         }
@@ -200,12 +189,8 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_rows(KStatic S, KCall K, 
     if (far_unit(1)) sweep(std::integral_constant<int, 1>{}, std::true_type{}); else sweep(std::integral_constant<int, 1>{}, std::false_type{});
     if constexpr (!FWD) {
 #pragma unroll
-      for (int q = 0; q < kStrip; ++q) {   // the k_L and omega_pe^2 columns of the rows from their angle sums (KsAcc, k_spectrum_fused.inc)
-        const double ksa = ks_eval(ws[q >> 1][q & 1], L.wpe2), ksb = ks_eval(ws[q >> 1][(q & 1) + 1], L.wpe2);
-        const double p1 = KA[q].p1a + KA[q].p1b;
-        J[q].kL = L.kL * p1 - (ksa * KA[q].p2a + ksb * KA[q].p2b);
-        J[q].wpe2 = -(0.5 / (kC * kC)) * (p1 - L.kL * (KA[q].p2a / ksa + KA[q].p2b / ksb));
-      }
+      for (int q = 0; q < kStrip; ++q)   // the k_L and omega_pe^2 columns of the rows from their angle sums (KsAcc, k_pairs.inc)
+        ks_columns<NI>(KA[q], ks_eval(ws[q >> 1][q & 1], L.wpe2), ks_eval(ws[q >> 1][(q & 1) + 1], L.wpe2), L, J[q]);
     }
     // rows of the round -> scratch: per component the pair's two consecutive samples as one 16-byte store
 #pragma unroll
@@ -267,8 +252,7 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_rows(KStatic S, KCall K, 
   const int nh = S.ntaps[f], toff = S.toff[f];
   // (constant address space: the taps are read-only for the whole launch and their index is wavefront-uniform, so the reads
   //  below are scalar loads -- no LDS traffic, no vector-memory instructions)
-  typedef const double __attribute__((address_space(4))) cdouble;
-  cdouble* taps = (cdouble*)S.taps[f];
+  cdouble_t* taps = (cdouble_t*)S.taps[f];
   auto PB = [&](int r) { return adj4 ? BPT * ht + r : ht + TPF * r; };   // r-th bin of this thread
   double ybin[BPT];
 #pragma unroll
@@ -281,7 +265,7 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_rows(KStatic S, KCall K, 
   auto fconv = [&](auto ppp_tag) {
     constexpr int PP = decltype(ppp_tag)::value, Q = BPT * PP;
     static_assert(BPT == 4 && 3 * PP <= kTapPad, "four adjacent bins per thread, taps padded by 3 ppp");
-    cdouble* ptp = (cdouble*)(S.ptaps[f] + kTapPad);
+    cdouble_t* ptp = (cdouble_t*)(S.ptaps[f] + kTapPad);
     const double* __restrict__ xl = xs + (Q + 1) * ht;
     const int c = H + toff, n = nh + 3 * PP;
 #pragma unroll 4
@@ -381,7 +365,7 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_rows(KStatic S, KCall K, 
     auto bins = [&](auto ppp_tag) {
       constexpr int PP = decltype(ppp_tag)::value;
       const int dlo = -((-toff + PP - 1) / PP), dhi = (nh - 1 + toff) / PP;   // (toff <= 0 < nh + toff) every d in [dlo, dhi] has a valid r
-      cdouble* ptp = (cdouble*)(S.ptaps[f] + kTapPad);
+      cdouble_t* ptp = (cdouble_t*)(S.ptaps[f] + kTapPad);
 #pragma unroll 1
       for (int r4 = 0; r4 < BPT; ++r4) {
         const int u = ht + TPF * r4;   // (bin-per-lane mapping whatever the forward convolution used: conflict-free reads of ybar)

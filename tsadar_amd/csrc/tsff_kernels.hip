@@ -7,6 +7,12 @@
 //                                          loss partials and -- MODE 1 -- the hand-written adjoint incl. the
 //                                          chain rule to the normalised leaves
 //   k_loss_reduce  a14                   : deterministic reduction of the masked loss sums
+//   k_conv.inc     a12                   : the phase-layout IRF convolution: the FMAs of a tap group (every spectrum kernel) and
+//                                          the pipelined loop (conv4_phase) of the pair-sweep kernels
+//   k_pairs.inc    a4-a10, a15           : what the pair-sweep kernels share: the per-point functions of the one-sweep reverse
+//                                          (point_fused, base_reverse_*, KsAcc) and the steps of the sweep, each once
+//   k_spectrum_fused, k_forward_pairs, k_spectrum_rows : the pair sweeps -- loss + gradient in one sweep, forward only,
+//                                          several points per pixel (k_spectrum_fused.inc, k_forward.inc, k_spectrum_rows.inc)
 //   k_form_factor  a4-a10                : raw FormFactor.__call__ output (known-answer tests)
 //   k_chain.inc    a12, a14, a15         : the chain's rules around the sweeps (amplitudes, loss, their adjoint, gradient tail), once
 //   k_hess_pairs   a16                   : exact per-lineout Hessian of the fit loss (hyper-dual forward mode, k_hessian.inc)
@@ -88,10 +94,12 @@ struct KCall {
 
 #include "k_chain.inc"
 #include "k_tables.inc"
+#include "k_conv.inc"
 #include "k_spectrum.inc"
 constexpr int kLineRec = 24;     // doubles per item of k_fused_prep's record: 9 + 4 n_ion lineout scalars + lam, amp1, amp2, amp3
 constexpr int kLBRec = 20;       // doubles per (item, wavefront) record of k_spectrum_fused: 9 + 3 n_ion sums + the two amplitude adjoints
 constexpr int kFusedMaxIon = 2;  // k_spectrum_fused is instantiated for n_ion <= 2 (4 x (7 + 3 n_ion) register accumulators per thread)
+#include "k_pairs.inc"
 #include "k_spectrum_fused.inc"
 #include "k_forward.inc"
 #include "k_spectrum_rows.inc"
