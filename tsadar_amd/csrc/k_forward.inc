@@ -38,7 +38,7 @@ __device__ __forceinline__ Smem carve_fwd(unsigned char* smem, const KStatic& S,
   m.W = reinterpret_cast<double*>(m.ht + S.nvx);
   double* p = m.W + kNXi2;
   m.x = p; m.yb = p; p += xbuf_doubles(S);
-  m.hc = reinterpret_cast<double2*>(p); p += 4 * (size_t)S.nvx;
+  m.hc = reinterpret_cast<double2*>(p); p += 4 * (size_t)S.nvx;   // (nvx cells: nvx - 1 intervals + the out-of-grid cell, stage_commit fills both)
   m.hcm = nullptr; m.Wm = nullptr;
   m.ksc = nullptr;
   if (with_ks) { m.ksc = p; p += S.npts + 2; }
@@ -54,6 +54,7 @@ __device__ __forceinline__ Smem carve_fwd(unsigned char* smem, const KStatic& S,
 template <int NI, bool ZH, int EXM, int NPAIR>
 __global__ __launch_bounds__(kHalf * (3 - NPAIR), 2) void k_forward_pairs(KStatic S, KCall K, int f0, int flags, const double* __restrict__ lrec) {
   constexpr bool EX = EXM != 0;
+  constexpr bool PAD = kSelectFree<NI>;   // the Hermite lookups read the out-of-grid cell that stage_commit writes (k_pairs.inc)
   constexpr int NT = kHalf * (3 - NPAIR);   // threads of the workgroup
   const bool use_ks = flags & 2, interleaved = flags & 4, own_scalars = flags & 8;
   const int item = blockIdx.x;
@@ -79,7 +80,7 @@ __global__ __launch_bounds__(kHalf * (3 - NPAIR), 2) void k_forward_pairs(KStati
   {
     TSFF_STAGE_LOCALS;
     stage_issue(TSFF_STAGE_ARGS, m, S, K, S.shared_fe ? 0 : b, ZH, f);
-    stage_commit(TSFF_STAGE_ARGS, m, S, K, S.shared_fe ? 0 : b, T, ZH, f);
+    stage_commit(TSFF_STAGE_ARGS, m, S, K, S.shared_fe ? 0 : b, T, ZH, f, PAD);
 #pragma unroll
     for (int p = 0; p < NPAIR; ++p)
 #pragma unroll
@@ -110,7 +111,7 @@ __global__ __launch_bounds__(kHalf * (3 - NPAIR), 2) void k_forward_pairs(KStati
   auto unit_of = [&](int P) { return NPAIR == 1 ? hw : 2 * hw + P; };   // 128-sample unit of this wavefront's pair P
   if (EX) {   // the unit-boundary base points of this wavefront's unit(s), all angles at once (lane = 16 P + a)
     const int Pb = (lane >> 4) & 1, ab = lane & 15;
-    if (lane < 16 * NPAIR && ab < NA) unit_boundary_fill<NI>(ex_wse, m.cosa[ab], L, T, exb + 16 * unit_of(Pb) + ab);
+    if (lane < 16 * NPAIR && ab < NA) unit_boundary_fill<NI, PAD>(ex_wse, m.cosa[ab], L, T, exb + 16 * unit_of(Pb) + ab);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -129,18 +130,18 @@ __global__ __launch_bounds__(kHalf * (3 - NPAIR), 2) void k_forward_pairs(KStati
       const double ct = uni(ct_n), wa = uni(wa_n * L.pref);
       { const int an = min(a + 1, NA - 1); ct_n = m.cosa[an]; wa_n = m.wsa[an]; }
       Base b0;
-      base_eval<NI>(ws[P][0], use_ks ? ksc[jb] : ks_eval(ws[P][0], L.wpe2), ct, L, T, b0);
+      base_eval<NI, PAD>(ws[P][0], use_ks ? ksc[jb] : ks_eval(ws[P][0], L.wpe2), ct, L, T, b0);
       const Base b0f = b0;   // (the thread's FIRST base point of this angle: what its left neighbour asks for)
 #pragma unroll
       for (int i = 0; i < kPair; ++i) {
         const int j = jb + i;
-        const bool has_next = (j + 1) < npts;
+        const bool has_next = pair_has_next<NI, P, NPAIR>(i, j, npts);
         Base b1;
         if (EX && i == kPair - 1) {   // the next lane's first base point; the last lane takes the unit's boundary point
           // (The forward value reads xi_e and F of this point alone: the compiler drops the other three shifts and their boundary reads)
           neighbour_take<NI>(b0f, exb + 16 * unit_of(P) + a, ks2, ct, L, b1);
         } else {
-          base_eval<NI>(ws[P][i + 1], use_ks ? ksc[min(j + 1, npts - 1)] : ks_eval(ws[P][i + 1], L.wpe2), ct, L, T, b1);
+          base_eval<NI, PAD>(ws[P][i + 1], use_ks ? ksc[min(j + 1, npts - 1)] : ks_eval(ws[P][i + 1], L.wpe2), ct, L, T, b1);
         }
         xa[P][i] = __builtin_fma(wa, point_forward_sd<NI, ZH, FAR>(b0, b1, has_next, L, T), xa[P][i]);
         b0 = b1;

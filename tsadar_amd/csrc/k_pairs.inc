@@ -89,7 +89,7 @@ __device__ __forceinline__ double point_fused(const Base& b, const Base& bn, boo
 struct KsAcc { double p1a, p2a, p1b, p2b; };
 
 // base_reverse (tsff_device.h) without its k_L / omega_pe^2 tail: returns k22
-template <int NI, int GM>
+template <int NI, int GM, bool PAD = false>
 __device__ __forceinline__ double base_reverse_fused(const Base& b, const LineS<NI>& L, const Tables& T, const BaseAdj& ba,
                                                      LineS<NI>& LB) {
   const double Hb = ba.F * b.F;  // adjoint of H = ln f_e(xi_e)
@@ -97,7 +97,7 @@ __device__ __forceinline__ double base_reverse_fused(const Base& b, const LineS<
     Tables Tm = T;
     Tm.hc = T.hcm;
     double Hm, dHm;
-    hermite_lookup_c(Tm, b.xe, Hm, dHm);
+    hermite_lookup_c<PAD>(Tm, b.xe, Hm, dHm);
     LB.m += (b.xe < T.vx0 || b.xe > T.vxlast) ? 0.0 : Hb * Hm;
   }
   const double xeb = ba.xe + Hb * b.dH;
@@ -115,7 +115,7 @@ __device__ __forceinline__ double base_reverse_fused(const Base& b, const LineS<
 
 // the same for a base point that receives adjoints of (xi_e, F) only: the right neighbour of a point, through the finite
 // difference D = (F_{j+1} - F_j)/(xi_{e,j+1} - xi_{e,j})
-template <int NI, int GM>
+template <int NI, int GM, bool PAD = false>
 __device__ __forceinline__ double base_reverse_xf(const Base& b, const LineS<NI>& L, const Tables& T, double xeb_in, double Fb,
                                                   LineS<NI>& LB) {
   const double Hb = Fb * b.F;
@@ -123,7 +123,7 @@ __device__ __forceinline__ double base_reverse_xf(const Base& b, const LineS<NI>
     Tables Tm = T;
     Tm.hc = T.hcm;
     double Hm, dHm;
-    hermite_lookup_c(Tm, b.xe, Hm, dHm);
+    hermite_lookup_c<PAD>(Tm, b.xe, Hm, dHm);
     LB.m += (b.xe < T.vx0 || b.xe > T.vxlast) ? 0.0 : Hb * Hm;
   }
   const double xeb = xeb_in + Hb * b.dH;
@@ -140,6 +140,23 @@ __device__ __forceinline__ double base_reverse_xf(const Base& b, const LineS<NI>
 }
 
 constexpr int kPair = 2;   // consecutive samples a thread sweeps with one chain of base points
+
+// Two selects that the inputs of a pair sweep already decide (DESIGN.md section 4.1b, profiles/r10_selects_isa.txt):
+// * has_next, the test for a right neighbour in point_core: a round of the sweep covers 1024 samples and npts is a multiple of 1024,
+//   so only the second sample of the LAST pair of a thread can be sample npts - 1.  Everywhere else the test is the constant true and
+//   the four selects per point that it feeds fold away (pair_has_next).
+// * the out-of-grid selects of the Hermite lookup: hermite_lookup_c<true> reads the out-of-grid cell instead (k_spectrum_fused and
+//   k_forward_pairs, whose tables stage_commit fills with that cell).
+// Both are taken by the single-species instantiations only -- the ones every bench.py line and the reference's decks run.  The
+// two-species instantiations sit at 256 VGPRs with 57 - 122 registers spilled, and either form moved the spill count of several of
+// them up (by up to 19 registers; tests/test_isa_lane_exchange.py pins two of them): they keep the parent's code, text for text.
+template <int NI>
+constexpr bool kSelectFree = NI == 1;
+// has a right neighbour: sample i of pair P (of NPAIR pairs per thread) at index j of npts samples
+template <int NI, int P, int NPAIR>
+__device__ __forceinline__ bool pair_has_next(int i, int j, int npts) {
+  return (kSelectFree<NI> && (P < NPAIR - 1 || i < kPair - 1)) || (j + 1) < npts;
+}
 
 // v of lane l (wavefront-uniform l): two scalar reads of another lane's registers, no LDS
 __device__ __forceinline__ double lane_f64(double v, int l) {
@@ -165,10 +182,10 @@ __device__ __forceinline__ void ks_cache_fill(double* __restrict__ ksc, const in
 
 // The base point right of a 128-sample unit at one angle, which the unit's last lane takes for its missing neighbour lane: evaluated
 // at the frequency wse of that sample (k_s directly: a cache entry may belong to another wavefront), component c at o[c kExBound].
-template <int NI>
+template <int NI, bool PAD = false>
 __device__ __forceinline__ void unit_boundary_fill(double wse, double ct, const LineS<NI>& L, const Tables& T, double* o) {
   Base be;
-  base_eval<NI>(wse, ks_eval(wse, L.wpe2), ct, L, T, be);
+  base_eval<NI, PAD>(wse, ks_eval(wse, L.wpe2), ct, L, T, be);
   o[0] = be.wd; o[kExBound] = be.ik; o[2 * kExBound] = be.xe; o[3 * kExBound] = be.F; o[4 * kExBound] = be.dH;
 }
 
@@ -186,14 +203,14 @@ __device__ __forceinline__ void neighbour_take(const Base& bf, const double* src
 
 // One point of a Jacobian row: the forward value into xa, the reverse with the seed wa into the row J, the k^2 adjoints of the
 // point's own base b0 and of its right neighbour b1 into the row's angle sums KA.
-template <int NI, int GM, bool ZH, bool FAR>
+template <int NI, int GM, bool ZH, bool FAR, bool PAD = false>
 __device__ __forceinline__ void row_step(const Base& b0, const Base& b1, bool has_next, const LineS<NI>& L, const Tables& T, double ct,
                                          double wa, double cw, double& xa, LineS<NI>& J, KsAcc& KA) {
   BaseAdj ba;
   double xen, Fn;
   xa = __builtin_fma(wa, point_fused<NI, GM, ZH, FAR>(b0, b1, has_next, L, T, wa, cw, ba, xen, Fn, J), xa);
-  const double k22a = base_reverse_fused<NI, GM>(b0, L, T, ba, J);
-  const double k22b = base_reverse_xf<NI, GM>(b1, L, T, xen, Fn, J);   // (xen = Fn = 0 at the last sample)
+  const double k22a = base_reverse_fused<NI, GM, PAD>(b0, L, T, ba, J);
+  const double k22b = base_reverse_xf<NI, GM, PAD>(b1, L, T, xen, Fn, J);   // (xen = Fn = 0 at the last sample)
   KA.p1a += k22a; KA.p2a = __builtin_fma(k22a, ct, KA.p2a);
   KA.p1b += k22b; KA.p2b = __builtin_fma(k22b, ct, KA.p2b);
 }

@@ -84,7 +84,7 @@ __device__ __forceinline__ Smem carve(unsigned char* smem, const KStatic& S, int
   // spectrum; zero halos on both sides so the convolutions need no bounds checks
   m.x = p; p += (size_t)nfeat * xbuf_doubles(S);
   if (alias) m.yb = m.x; else { m.yb = p; p += (size_t)nfeat * ybuf_doubles(S); }
-  m.hc = reinterpret_cast<double2*>(p); p += 4 * (size_t)S.nvx;
+  m.hc = reinterpret_cast<double2*>(p); p += 4 * (size_t)S.nvx;   // (nvx cells: nvx - 1 intervals + one more, the out-of-grid cell that stage_commit(pad) fills)
   m.hcm = nullptr; m.Wm = nullptr;
   if (gm) { m.hcm = reinterpret_cast<double2*>(p); p += 4 * (size_t)S.nvx; }
   if (gm == 2) { m.Wm = p; p += kNXi2; }
@@ -188,8 +188,9 @@ __device__ __forceinline__ void stage_issue(TSFF_STAGE_PARAMS, const Smem& m, co
   if (tid < padded_taps(S, f)) r.tp = S.ptaps[f][tid];
 }
 // taps: the feature's zero-padded tap array (S.ptaps[f]: hb[s] at 3 + s, points_per_pixel 1) goes to m.taps[0 .. padded_taps)
+// pad: also write the out-of-grid cell of the Hermite coefficient tables (for kernels whose lookups are hermite_lookup_c<true>)
 __device__ __forceinline__ void stage_commit(TSFF_STAGE_PARAMS, const Smem& m, const KStatic& S, const KCall& K, int slot, Tables& T,
-                                             bool zh, int f) {
+                                             bool zh, int f, bool pad = false) {
   const StageRefs r{v0, v1, v2, v3, v4, v5, v6, v7, v8, v9, ha, hb, ma, mb, ang_c, ang_w, et, tp};
   const int tid = threadIdx.x, nthr = blockDim.x;
   const int n0 = zh ? kNZh : kNXi2, total = n0 + kNXi2 / 2, nvx = S.nvx;
@@ -223,6 +224,10 @@ __device__ __forceinline__ void stage_commit(TSFF_STAGE_PARAMS, const Smem& m, c
       hermite_coeffs(r.ma, r.mb, S.dv, c01, c23);
       m.hcm[2 * tid] = c01; m.hcm[2 * tid + 1] = c23;
     }
+  }
+  if (pad) {   // (cell nvx - 1 of the 2 nvx carved)
+    hermite_pad_cell(m.hc, nvx, -50.0, tid);
+    if (m.hcm && K.htm) hermite_pad_cell(m.hcm, nvx, 0.0, tid);
   }
   if (m.Wm && K.Wm)
     for (int i = tid; i < kNXi2; i += nthr) m.Wm[i] = K.Wm[(size_t)slot * kNXi2 + i];

@@ -67,6 +67,7 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_fused(KStatic S, KCall K,
   //  column block this launch covers)
   const size_t gitem = (size_t)f_il * K.Btot + b;
   constexpr int TPF = kHalf, NW = TPF / 64;
+  constexpr bool PAD = kSelectFree<NI>;   // the Hermite lookups read the out-of-grid cell that stage_commit writes (k_pairs.inc)
   const int ht = tid, lane = tid & 63, hw = tid >> 6;
   const int f = __builtin_amdgcn_readfirstlane(interleaved ? f_il : f0);
   extern __shared__ __align__(16) unsigned char smem[];
@@ -92,7 +93,7 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_fused(KStatic S, KCall K,
     stage_issue(TSFF_STAGE_ARGS, m, S, K, S.shared_fe ? 0 : b, ZH, f);
     // (written to LDS right away: holding the sixty staged registers across the scalar chain below makes the allocator spill
     //  them, and the DLM instantiation without the lane exchange then produced wrong spectra -- variant A of the bisection)
-    stage_commit(TSFF_STAGE_ARGS, m, S, K, S.shared_fe ? 0 : b, T, ZH, f);
+    stage_commit(TSFF_STAGE_ARGS, m, S, K, S.shared_fe ? 0 : b, T, ZH, f, PAD);
 #pragma unroll
     for (int p = 0; p < 2; ++p)
 #pragma unroll
@@ -140,7 +141,7 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_fused(KStatic S, KCall K,
   double* exb = m.ex;
   if (EX) {   // the unit-boundary base points of this wavefront's two units, all angles at once (lane = 16 P + a)
     const int Pb = (lane >> 4) & 1, ab = lane & 15;
-    if (lane < 32 && ab < NA) unit_boundary_fill<NI>(ex_wse, m.cosa[ab], L, T, exb + 16 * (2 * hw + Pb) + ab);
+    if (lane < 32 && ab < NA) unit_boundary_fill<NI, PAD>(ex_wse, m.cosa[ab], L, T, exb + 16 * (2 * hw + Pb) + ab);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   // (the sweep reads other lanes' boundary points)
@@ -158,14 +159,14 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_fused(KStatic S, KCall K,
       const double ct = uni(ct_n), wa = uni(wa_n * L.pref);
       { const int an = min(a + 1, NA - 1); ct_n = m.cosa[an]; wa_n = m.wsa[an]; }
       Base b0;
-      base_eval<NI>(ws[P][0], use_ks ? ksc[jb] : ks_eval(ws[P][0], L.wpe2), ct, L, T, b0);
+      base_eval<NI, PAD>(ws[P][0], use_ks ? ksc[jb] : ks_eval(ws[P][0], L.wpe2), ct, L, T, b0);
       // (EX) the lane's FIRST base point of this angle is what its left neighbour asks for: b0 itself is the second one by then
       const Base b0f = b0;
 #pragma unroll
       for (int i = 0; i < kPair; ++i) {
         constexpr int q0 = kPair * P;
         const int q = q0 + i, j = jb + i;
-        const bool has_next = (j + 1) < npts;
+        const bool has_next = pair_has_next<NI, P, 2>(i, j, npts);
         Base b1;
         if (EX && i == kPair - 1) {   // the neighbour lane's first base point (the unit's boundary point for the last lane)
           // (The boundary point is read HERE.  Read an iteration ahead, as ct_n / wa_n are, or at the top of the iteration, its five
@@ -173,9 +174,9 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_fused(KStatic S, KCall K,
           //  spills none; measured, DESIGN.md section 4.1b.)
           neighbour_take<NI>(b0f, exu + a, ks2, ct, L, b1);
         } else {
-          base_eval<NI>(ws[P][i + 1], use_ks ? ksc[min(j + 1, npts - 1)] : ks_eval(ws[P][i + 1], L.wpe2), ct, L, T, b1);
+          base_eval<NI, PAD>(ws[P][i + 1], use_ks ? ksc[min(j + 1, npts - 1)] : ks_eval(ws[P][i + 1], L.wpe2), ct, L, T, b1);
         }
-        row_step<NI, GM, ZH, FAR>(b0, b1, has_next, L, T, ct, wa, cw, xa[q], J[q], KA[q]);
+        row_step<NI, GM, ZH, FAR, PAD>(b0, b1, has_next, L, T, ct, wa, cw, xa[q], J[q], KA[q]);
         b0 = b1;
       }
     }

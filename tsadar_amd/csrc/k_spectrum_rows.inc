@@ -163,7 +163,10 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_rows(KStatic S, KCall K, 
         for (int i = 0; i < kPair; ++i) {
           constexpr int q0 = kPair * P;
           const int q = q0 + i, j = jb + i;
-          const bool has_next = (j + 1) < npts;
+          // (The lookups keep their selects here: load_tables writes no out-of-grid cell.  With hermite_lookup_c<true> the forward
+          //  form <1, 0, false, true, true> went from 123 to 129 VGPRs, four to three wavefronts per SIMD, and <1, 0, false, false,
+          //  false> from 2 to 4 spilled registers; profiles/r10_selects_isa.txt.)
+          const bool has_next = pair_has_next<NI, P, 2>(i, j, npts);
           Base b1;
           if (EX && i == kPair - 1) {   // the neighbour lane's first base point (or the unit's boundary point for the last lane)
             __builtin_amdgcn_wave_barrier();

@@ -141,20 +141,26 @@ struct Tables {
   const double2* zp;   // [1640] (Re Z', Im Z') on xi2
   const double* W;     // [1640] Re(chi_e) table on xi2
   const double2* ht;   // [nvx]  (ln fe, node slope) on vx            (k_fe_prepare)
-  const double2* hc;   // [2*(nvx-1)] cubic coefficients per interval: (f0, m0), (c2, c3)   (spectrum kernels)
-  const double2* hcm;  // the same for d(ln fe)/dm (gradient w.r.t. the DLM order), or nullptr
+  const double2* hc;   // [2*nvx] cubic coefficients per interval: (f0, m0), (c2, c3)   (spectrum kernels).  Cells 0 .. nvx-2 are
+                       // the intervals; cell nvx-1 is the OUT-OF-GRID cell (-50, 0 | 0, 0) that hermite_lookup_c<true> sends every
+                       // position outside the grid to -- written by hermite_pad_cell() in stage_commit(pad); a table filled elsewhere
+                       // (load_tables, the table kernels) leaves the cell unwritten and is read by hermite_lookup_c<false> only
+  const double2* hcm;  // the same for d(ln fe)/dm (gradient w.r.t. the DLM order; out-of-grid cell all zero), or nullptr
   const double* Wm;    // [1640] dW/dm, or nullptr
   double* Wb;          // [1640] adjoint of W            (gradient w.r.t. the distribution function itself, GM == 2)
   double* Hy;          // [nvx]  adjoint of the ln fe node values
   double* Hs;          // [nvx]  adjoint of the ln fe node slopes
   double vx0, dv, idv, vxlast;
-  double u0, utop;     // -vx0 / dv and (nvx - 1)(1 - 2^-52): hermite_lookup_c's position in cell units and its clamp
+  double u0, utop;     // -vx0 / dv and (nvx - 1)(1 - 2^-53): the position in cell units and the last in-grid position.  utop is
+                       // the double just below nvx - 1 for EVERY nvx (the product lies (nvx - 1) 2^-53 below nvx - 1: more than half
+                       // a spacing of the doubles there, and exactly one spacing when nvx - 1 is a power of two)
+  double uhi;          // nvx - 1, the first position right of the grid: hermite_lookup_c<true>'s upper clamp (its floor is the out-of-grid cell)
   const double* etab;  // [64] 2^(j/64) in LDS (fexp_t), or nullptr: polynomial exp
   int nvx;
 };
 __device__ __forceinline__ void tables_set_grid(Tables& T, double vx0, double dv, int nvx) {
   T.vx0 = vx0; T.dv = dv; T.idv = 1.0 / dv; T.vxlast = vx0 + (nvx - 1) * dv; T.nvx = nvx;
-  T.u0 = -vx0 * T.idv; T.utop = (double)(nvx - 1) * (1.0 - 1.1102230246251565e-16);
+  T.u0 = -vx0 * T.idv; T.utop = (double)(nvx - 1) * (1.0 - 1.1102230246251565e-16); T.uhi = (double)(nvx - 1);
 }
 
 // Gradient w.r.t. the tabulated distribution function (GM == 2): every point scatters the adjoint of its two table
@@ -229,18 +235,33 @@ __device__ __forceinline__ void hermite_coeffs(double2 a, double2 b, double dv, 
   c23 = make_double2(-3.0 * f0 + 3.0 * f1 - 2.0 * m0 - m1, 2.0 * f0 - 2.0 * f1 + m0 + m1);
 }
 
+// The out-of-grid cell of a coefficient table hc [2 nvx] (cell nvx - 1, behind the nvx - 1 intervals): the cubic that is the
+// constant `outside` with slope exactly +0 for every finite t >= 0 -- -50 for ln f_e (interp1d's extrap), 0 for its m-tangents.
+// Thread `tid` 0 of the filling workgroup writes it; the barrier that publishes the table publishes the cell.
+__device__ __forceinline__ void hermite_pad_cell(double2* hc, int nvx, double outside, int tid) {
+  if (tid == 0) { hc[2 * (nvx - 1)] = make_double2(outside, 0.0); hc[2 * (nvx - 1) + 1] = make_double2(0.0, 0.0); }
+}
+
 // the same lookup as hermite_lookup() below from the per-interval coefficient table
+// PAD = false: a position that the clamp to [0, utop] moves lies outside the grid, where the interpolant is the constant -50 with
+//   slope 0: one comparison and four selects behind the cubic.
+// PAD = true: no comparison and no select.  Inside the grid, 0 <= u <= utop (the double just below nvx - 1), the cell is floor(u)
+//   and t = u - floor(u) as before.  Everything else -- u < 0, u >= nvx - 1, NaN (fmax returns the -1) -- is clamped to
+//   [-1, nvx - 1]: floor gives -1 or nvx - 1, and the UNSIGNED minimum with nvx - 1 sends both to the out-of-grid cell nvx - 1
+//   (hermite_pad_cell: the caller's table must have it); t stays in [0, 1], where that cell's cubic is exactly its constant
+//   (-50 for ln f_e) with slope +0.  The same bits as PAD = false for every double x.
+template <bool PAD = false>
 __device__ __forceinline__ void hermite_lookup_c(const Tables& T, double x, double& H, double& dH) {
 #pragma clang fp contract(off)
-  // (same index arithmetic as w_lookup; T.u0 = -vx0 / dv, T.utop = (nvx - 1)(1 - 2^-52): a position that the clamp moves
-  //  lies outside the grid, where the interpolant is the constant -50)
+  // (same index arithmetic as w_lookup; T.u0 = -vx0 / dv)
   const double u = __builtin_fma(x, T.idv, T.u0);
-  const double uc = fmin(fmax(u, 0.0), T.utop);
+  const double uc = PAD ? fmin(fmax(u, -1.0), T.uhi) : fmin(fmax(u, 0.0), T.utop);
   const double fl = __builtin_floor(uc);
   const double t = uc - fl;
-  const int i = (int)fl;
+  int i = (int)fl;
+  if (PAD) { const unsigned iu = (unsigned)i, itop = (unsigned)(T.nvx - 1); i = (int)(iu < itop ? iu : itop); }
   const double2 c01 = T.hc[2 * i], c23 = T.hc[2 * i + 1];
-  const bool out = u != uc;
+  const bool out = !PAD && u != uc;
   const double Hi = __builtin_fma(t, __builtin_fma(t, __builtin_fma(t, c23.y, c23.x), c01.y), c01.x);
   const double dHi = __builtin_fma(t, __builtin_fma(3.0 * t, c23.y, 2.0 * c23.x), c01.y) * T.idv;
   H = out ? -50.0 : Hi;
@@ -463,7 +484,8 @@ __device__ __forceinline__ double base_k2(double ks, double ct, const LineS<NI>&
   return __builtin_fma(ks, ks - c1, c0);
 }
 
-template <int NI>
+// PAD: the form of the Hermite lookup (hermite_lookup_c)
+template <int NI, bool PAD = false>
 __device__ __forceinline__ void base_eval(double ws, double ks, double ct, const LineS<NI>& L, const Tables& T,
                                           Base& b) {
 #pragma clang fp contract(off)
@@ -474,7 +496,7 @@ __device__ __forceinline__ void base_eval(double ws, double ks, double ct, const
   b.wd = __builtin_fma(-k, L.Vd, ws - L.wL);               // :216, 222-223
   b.xe = __builtin_fma(b.wd, b.ik, -L.Ud) * L.ivTe;        // :253
   double H;
-  hermite_lookup_c(T, b.xe, H, b.dH);
+  hermite_lookup_c<PAD>(T, b.xe, H, b.dH);
   b.F = T.etab ? fexp_t<false>(H, T.etab) : fexp<false>(H);   // :256  (T.etab is set or not per kernel: folded at compile time)
 }
 
