@@ -735,13 +735,13 @@ def _fe2d(nv, kind):
     return vx, f / (f.sum() * (vx[1] - vx[0]) ** 2)
 
 
-@pytest.mark.parametrize("kind,nv", [("maxwellian", 48), ("anisotropic", 48), ("anisotropic", 132), ("anisotropic", 133)])
+@pytest.mark.parametrize("kind,nv", [("maxwellian", 48), ("anisotropic", 48), ("anisotropic", 132), ("anisotropic", 133), ("anisotropic", 257)])
 def test_form_factor_2d_matches_oracle(torch_mod, kind, nv):
     """a16: FormFactor.calc_in_2D (rotate + project + ratintn per (lambda, theta) point) vs the oracle's
     restatement on a subset of wavelengths; non-zero drift and flow at oblique angles.  (Parity with the reference
     itself is unpinned for this path: its goldens are not in the reference tree.)"""
     cfg = decks.deck_fit()
-    B = 2  # nv = 48: table resident in LDS; nv = 132 (> 128): table read through L1/L2; 133: an odd number of samples per line (the sampler's loop is unrolled by two)
+    B = 2  # nv = 48: table resident in LDS; nv = 132 (> 128): table read through L1/L2; 133: an odd number of samples per line (the sampler's loop is unrolled by two); 257: several columns per thread (thread 0 owns columns 0 and 256)
     sa = dict(sa=np.array([35.0, 60.0, 110.0]), weights=np.ones((B, 3)) / 3)
     eng = _engine(cfg, sa)
     normed = util.random_lineouts(cfg, B, seed=61, ranges=dict(ud=(-1.5, 1.5)))
@@ -1667,11 +1667,13 @@ def test_ats_adjoint_directional_derivatives(torch_mod, ccd, n_lam, start, end):
     assert abs((func(Pn, a1, a2 + h) - func(Pn, a1, a2 - h)) / (2 * h) - a2b) < 1e-7 * abs(a2b)
 
 
-@pytest.mark.parametrize("nv,n_ion,G", [(48, 2, 3), (132, 1, 1)])
+@pytest.mark.parametrize("nv,n_ion,G", [(48, 2, 3), (132, 1, 1), (257, 1, 1)])
 def test_form_factor_2d_grad_finite_differences(torch_mod, nv, n_ion, G):
     """Adjoint of the 2-D path (tsff_form_factor_2d_grad): J = <Pbar, P(phys, fe2d)>.  d J / d phys and d J / d fe2d[i][j]
     against central differences of the (oracle-checked) forward tsff_form_factor_2d.  nv = 48: tables in LDS, two ion
-    species, three gradient points; nv = 132: table and its adjoint through L2 / global atomics."""
+    species, three gradient points; nv = 132: table read through L1/L2, the lineout-scalar adjoints through fixed-order partial
+    slots (k_lbacc_reduce), the table adjoint in tiles; nv = 257: several columns per thread -- the adjoint's second sampling
+    sweep, and no projection records."""
     torch = torch_mod
     cfg = decks.deck_fit(n_ion=n_ion)
     if G > 1:

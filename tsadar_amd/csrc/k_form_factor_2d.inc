@@ -12,6 +12,12 @@
 //      interior, modified in the first/last cell).
 //   3. gradient of the projection, the two linear interpolations at |xi_e| and the rationally-centred integral
 //      over the nv-2 intervals (:372-387), spectrum assembly (:560-585).
+// k_form_factor_2d_adj repeats all of that before it reverses it.  What the two kernels have in common is defined once, below:
+//   sizes and slots   parts2d, nvp2d, group2d_doubles / group2d_adj_doubles, smem2d_doubles / smem2d_adj_doubles (the host sizes the
+//                     dynamic LDS from the same functions), the SC_* slots of the per-group scalar scratch sc[]
+//   shared steps      stage_table_2d, point_id_2d / point_setup_2d, project_point_2d, column_sums_2d, gradient_2d,
+//                     assemble_point_2d; catmull_rom_d for the samplers that are not hand-scheduled
+// Each kernel keeps its own point loop and barrier sequence, and its own form of the ratintn interval (see the shared steps).
 // ------------------------------------------------------------------------------------------
 // interior-cell (Catmull-Rom) weights of the four nodes c-1..c+2
 __device__ __forceinline__ void catmull_rom(double t, double w[4]) {
@@ -23,6 +29,12 @@ __device__ __forceinline__ void catmull_rom(double t, double w[4]) {
   w[1] = __builtin_fma(1.5, b, __builtin_fma(-2.5, a, 1.0));
   w[2] = __builtin_fma(-1.5, b, __builtin_fma(2.0, a, ht));
   w[3] = __builtin_fma(0.5, b, -ha);
+}
+// their derivatives in t, for the samplers that are not hand-scheduled (project_rolling keeps a Horner form of its own, with pinned
+// roundings, next to its window arithmetic)
+__device__ __forceinline__ void catmull_rom_d(double t, double d[4]) {
+  d[0] = -0.5 * (3.0 * t * t - 4.0 * t + 1.0); d[1] = 4.5 * t * t - 5.0 * t;
+  d[2] = -4.5 * t * t + 4.0 * t + 0.5;         d[3] = 1.5 * t * t - t;
 }
 
 // One bicubic sample at (xq, yq) of a table that carries one GHOST row / column on every side, filled by linear
@@ -387,7 +399,6 @@ __global__ __launch_bounds__(kThreads) void k_pad2d(const double* __restrict__ F
 #ifndef TSFF_2D_GROUPS_L2
 #define TSFF_2D_GROUPS_L2 1
 #endif
-constexpr int kSc2 = 40;  // doubles of per-group scalar scratch
 // Row pitch of the padded (nv + 2)^2 table.  In LDS it is made odd: with an even (worse: power-of-two) pitch the rows
 // start in the same banks and the lanes of a wavefront (neighbouring points of a rotated line) collide whenever the line
 // runs along the first table axis.
@@ -401,14 +412,34 @@ __host__ __device__ inline int pitch2d(int nv, bool lds) {
   const int r = nv <= 96 ? 1 : 2;
   return nv + 2 + ((r - (nv + 2) % 32) + 32) % 32;
 }
-// per-group scratch: f1, d1 [nv], part [nparts][nv] (nparts = 4, 2, 1 for nv <= 64, 128, larger), red [8], scalars
-__host__ __device__ inline size_t group2d_doubles(int nv) {
-  const int nparts = nv <= 64 ? 4 : (nv <= 128 ? 2 : 1);
-  return (2 + (size_t)nparts) * nv + 8 + kSc2;
-}
-__host__ __device__ inline size_t smem2d_doubles(int nv, bool lds, int ng) {
-  return (size_t)ng * group2d_doubles(nv) + (lds ? (size_t)(nv + 2) * pitch2d(nv, true) : 0);
-}
+// ---- sizes and scratch slots of the two point kernels (k_form_factor_2d, k_form_factor_2d_adj): defined HERE, read by both
+// kernels and by the host (form_factor_2d_prepare, form_factor_2d_adj_prepare) ----
+// thread -> (column iy = gt % nvp2d, part gt / nvp2d of the column's ix range): nvp2d = nv rounded up to 64, 128 or 256, parts2d =
+// 256 / nvp2d; above 256 a thread owns several whole columns
+__host__ __device__ inline int parts2d(int nv) { return nv <= 64 ? 4 : (nv <= 128 ? 2 : 1); }
+__host__ __device__ inline int nvp2d(int nv) { return nv <= 64 ? 64 : (nv <= 128 ? 128 : 256); }
+constexpr int kSc2 = 40;  // doubles of per-group scalar scratch, forward
+constexpr int kScA = 96;  // the same of the adjoint: [0, SC_ACC) point scalars and adjoints, [SC_ACC, SC_ACC + NLB] running sums and their tag
+// per-group scratch of the forward: f1, d1 [nv], part [parts2d][nv], red [8], sc [kSc2]
+__host__ __device__ inline size_t group2d_doubles(int nv) { return (2 + (size_t)parts2d(nv)) * nv + 8 + kSc2; }
+// ... of the adjoint: f1, d1 [nv], part [parts2d][nv], c0, c1 [nv], red [16], sc [kScA]
+__host__ __device__ inline size_t group2d_adj_doubles(int nv) { return (2 + (size_t)parts2d(nv)) * nv + 2 * (size_t)nv + 16 + kScA; }
+// dynamic LDS of a workgroup of ng point groups: the groups' scratch, then the padded table (LDS variant)
+__host__ __device__ inline size_t table2d_doubles(int nv, bool lds) { return lds ? (size_t)(nv + 2) * pitch2d(nv, true) : 0; }
+__host__ __device__ inline size_t smem2d_doubles(int nv, bool lds, int ng) { return (size_t)ng * group2d_doubles(nv) + table2d_doubles(nv, lds); }
+__host__ __device__ inline size_t smem2d_adj_doubles(int nv, bool lds, int ng) { return (size_t)ng * group2d_adj_doubles(nv) + table2d_doubles(nv, lds); }
+// Slots of sc[]: what thread 0 of a point group leaves for the group, and for itself later in the point.
+constexpr int kNLB2 = 8;  // lineout-scalar adjoints: wpe2, wL, kL, ivTe, a_e, pref, Ud, Vd, + 3 per ion: ixi, a_i, cs
+enum {
+  SC_CB = 0, SC_SB, SC_XMAG, SC_K2, SC_K, SC_WD, SC_WS, SC_AE, SC_IVTE, SC_WL, SC_PREF,         // point scalars (point_setup_2d), both kernels
+  SC_KX, SC_KY, SC_AA, SC_XEX, SC_XEY, SC_KS, SC_VX, SC_VY, SC_UX, SC_UY, SC_CT, SC_ST, SC_BG,      // ... adjoint only; SC_BG = b G + g
+  SC_ION = 24,                                                                                  // [3 s + 0, 1, 2] = ixi, a_i, cs of species s, both kernels
+  SC_RB = 36, SC_FEVB, SC_DFEB, SC_IL, SC_T, SC_XMAGB, SC_WDB, SC_WLB,                          // the adjoint's reverse of the assembly
+  SC_IONB = 44,                                                                                 // [3 s + 0, 1, 2] = adjoints of ixi, a_i, cs
+  SC_PREFB = 56, SC_IVTEB, SC_AEB, SC_K2B,
+  SC_ACC = 64                                                                                   // [NLB] running sums per (b, g); [NLB]: the (b, g) they belong to
+};
+static_assert(SC_BG < SC_ION && SC_ION + 3 * TSFF_MAX_ION <= SC_RB && SC_IONB + 3 * TSFF_MAX_ION <= SC_PREFB && SC_K2B < SC_ACC, "sc[] slots overlap");
 // value and both first derivatives from ONE read of the stencil (the adjoint's projection pass carries the derivative
 // sums along: they do not depend on the seed, so the separate derivative sweep -- a second full round of LDS reads, the
 // resource this kernel is bound by -- is not needed)
@@ -422,10 +453,8 @@ __device__ __forceinline__ double bicubic_sample_vg(const double* __restrict__ F
   double wx[4], wy[4], dx[4], dy[4];
   catmull_rom(tx, wx);
   catmull_rom(ty, wy);
-  dx[0] = -0.5 * (3.0 * tx * tx - 4.0 * tx + 1.0); dx[1] = 4.5 * tx * tx - 5.0 * tx;
-  dx[2] = -4.5 * tx * tx + 4.0 * tx + 0.5;         dx[3] = 1.5 * tx * tx - tx;
-  dy[0] = -0.5 * (3.0 * ty * ty - 4.0 * ty + 1.0); dy[1] = 4.5 * ty * ty - 5.0 * ty;
-  dy[2] = -4.5 * ty * ty + 4.0 * ty + 0.5;         dy[3] = 1.5 * ty * ty - ty;
+  catmull_rom_d(tx, dx);
+  catmull_rom_d(ty, dy);
   const double* __restrict__ q0 = Fp + (size_t)cx * pitch + cy;
   double val = 0.0, sx = 0.0, sy = 0.0;
 #pragma unroll
@@ -451,10 +480,9 @@ __device__ __forceinline__ double bicubic_sample_vg(const double* __restrict__ F
 
 // doubles per point of the projection record a SAVE pass leaves for the adjoint: f1[nv], then the per-thread partial
 // derivative sums ds1[nparts][nv], ds2[nparts][nv] (nv <= 256 only)
-__host__ __device__ inline size_t proj2d_doubles(int nv) {
-  const int nvp = nv <= 64 ? 64 : (nv <= 128 ? 128 : 256);
-  return (size_t)nv * (1 + 2 * (kThreads / nvp));
-}
+__host__ __device__ inline size_t proj2d_doubles(int nv) { return (size_t)nv * (1 + 2 * parts2d(nv)); }
+template <class T>
+__device__ __forceinline__ T* proj2d_record(T* proj, long point, int nv) { return proj + (size_t)point * proj2d_doubles(nv); }
 // SAVE: the fit loop will reverse this very evaluation next (tsff_form_factor_2d_grad with use_saved): the projection f1
 // and the derivative sums of every point go to `proj` (proj2d_doubles per point), so that the adjoint does no sampling.
 #ifndef TSFF_2D_WAVES
@@ -483,125 +511,216 @@ __device__ __forceinline__ void point_scalars_2d(double ws, double th, const Lin
   const double beta = atan(q.xey / q.xex) + (q.xex >= 0.0 ? 0.0 : kPi);   // heaviside(x, 1) = 1 at x == 0  (:552-558)
   q.cb = cos(beta); q.sb = sin(beta);
 }
+// ------------------------------------------------------------------------------------------
+// The steps k_form_factor_2d and its adjoint share, each defined once.  The adjoint repeats the forward up to the point's spectrum,
+// and "the same projection, bit for bit" between the saving forward and the adjoint that reads its records rests on both running
+// the same text.  Each kernel keeps its point loop and its barrier sequence written out and calls these between the barriers
+// (k_pairs.inc: share the steps, not the loop).
+//   a. stage_table_2d     the table into LDS, ghost rows and columns
+//   b. point_id_2d, point_setup_2d   pid -> (a, j, g, b); thread 0's point scalars into sc[]
+//   c. project_point_2d   one point's partial column sums into part[] (plain, with derivative sums, several columns per thread)
+//   d. column_sums_2d, gradient_2d   f1 from part, d1 from f1
+//   e. assemble_point_2d  thread 0: the interpolations at |xi_e|, chi_e, the ion terms, epsilon, S(k, omega)
+// NOT shared: the ratintn interval between d. and e.  The forward takes the small-interval branch as fav / gav + tmp gdif / (12 gav^3),
+// the adjoint as fav ig + tmp c with ig = 1 / gav, c = gdif / (12 gav^3), which it needs for the partial derivatives: the same value
+// with other roundings, so one definition would change the bits of one of the kernels.
+// ------------------------------------------------------------------------------------------
+// a. the plain nv x nv table Fg into the padded table Fl in LDS, the ghost cells made here: all nthr threads of the workgroup
+__device__ __forceinline__ void stage_table_2d(const double* __restrict__ Fg, double* Fl, int nv, int pitch, int nthr) {
+  for (int i = threadIdx.x; i < nv * nv; i += nthr) Fl[(i / nv + 1) * pitch + (i % nv + 1)] = Fg[i];
+  __syncthreads();
+  ghost_rows(Fl, nv, pitch, threadIdx.x, nthr);
+  __syncthreads();
+  ghost_cols(Fl, nv, pitch, threadIdx.x, nthr);
+}
+// b. point of the flat list -> scattering angle a, wavelength j, gradient point g, lineout b
+struct PointId2D { int a, j, g, b; };
+__device__ __forceinline__ PointId2D point_id_2d(long pid, const KStatic& S) {
+  const int NA = S.n_angles, G = S.G, npts = S.npts;
+  PointId2D id;
+  id.a = (int)(pid % NA); id.j = (int)((pid / NA) % npts); id.g = (int)((pid / ((long)NA * npts)) % G);
+  id.b = (int)(pid / ((long)NA * npts * G));
+  return id;
+}
+// ... and its scalars into sc[] (one thread per point group); ADJ: also what the reverse of point_scalars_2d reads
+template <int NI, bool ADJ>
+__device__ __forceinline__ void point_setup_2d(const KStatic& S, const double* __restrict__ phys, int f, const PointId2D& id, double ud_ang,
+                                               double va_ang, double* sc) {
+  Phys<NI> p;
+  load_phys<NI>(phys + (size_t)id.b * S.NP, S.p_scale, S.p_shift, S.p_sig, S.ti_same, false, p);
+  LineS<NI> L;
+  make_lines<NI>(p, S.lam_shift[f], id.g, S.G, L);
+  // ---- point scalars (form_factor.py:515-558) ----
+  const double ws = S.omgs[f][id.j], th = S.sa_rad[id.a];
+  Point2D q;
+  point_scalars_2d<NI>(ws, th, L, va_ang, ud_ang, q);
+  sc[SC_CB] = q.cb; sc[SC_SB] = q.sb; sc[SC_XMAG] = q.xmag;   // cos / sin of beta (atan + heaviside of :552-558)
+  sc[SC_K2] = q.k2; sc[SC_K] = q.k; sc[SC_WD] = q.wd; sc[SC_WS] = ws; sc[SC_AE] = L.a_e; sc[SC_IVTE] = L.ivTe; sc[SC_WL] = L.wL; sc[SC_PREF] = L.pref;
+  if (ADJ) {
+    sc[SC_KX] = q.kx; sc[SC_KY] = q.ky; sc[SC_AA] = q.aa; sc[SC_XEX] = q.xex; sc[SC_XEY] = q.xey; sc[SC_KS] = q.ks; sc[SC_VX] = q.Vx; sc[SC_VY] = q.Vy;
+    sc[SC_UX] = q.Ux; sc[SC_UY] = q.Uy; sc[SC_CT] = q.ct; sc[SC_ST] = q.st;
+    sc[SC_BG] = (double)((long)id.b * S.G + id.g);
+  }
+#pragma unroll
+  for (int s = 0; s < NI; ++s) { sc[SC_ION + 3 * s] = L.ixi[s]; sc[SC_ION + 1 + 3 * s] = L.a_i[s]; sc[SC_ION + 2 + 3 * s] = L.cs[s]; }
+}
+// c. rotate + project (:300-324, 371): thread gt's partial column sums of one point into part[parts2d][nv].  VG: also the thread's sums
+// of d sample / d cos(beta), d sample / d sin(beta) (one column per thread, nv <= 256; zero otherwise); proj: they also go to record
+// `point` of the saving forward (stored here, next to where they are made: a record pointer formed ahead of the sampling stays live
+// through it and costs the saving forms a spill).  F: the padded table -- in LDS, or the copy of k_pad2d read through L1/L2.
+template <bool LDS, bool VG>
+__device__ __forceinline__ void project_point_2d(const double* __restrict__ F, int nv, int pitch, int nvp, int nparts, double cb, double sb,
+                                                 double dv, double v0, double idv, int gt, double* part, double& ds1, double& ds2, double* __restrict__ proj = nullptr, long point = 0) {
+  if (nv <= 256) {
+    const int iy = gt % nvp, pt = gt / nvp;
+    if (iy < nv) {
+      const int ix0 = (nv * pt) / nparts, ix1 = (nv * (pt + 1)) / nparts;
+      const double y = __builtin_fma((double)iy, dv, v0);
+      double acc = 0.0, ul, vl, xi_d = (double)ix0;
+      line_origin(cb, sb, y, v0, idv, ul, vl);
+      if (VG && !LDS) {
+        RollVG vg{idv, dv, v0, y, 0.0, 0.0};
+        acc = project_rolling_any<true>(F, nv, pitch, cb, sb, ul, vl, ix0, ix1, &vg);
+        ds1 = vg.ds1; ds2 = vg.ds2;
+      } else if (VG) {
+        for (int ix = ix0; ix < ix1; ++ix, xi_d += 1.0) {
+          const double x = __builtin_fma(xi_d, dv, v0);
+          double Sx, Sy;
+          acc += bicubic_sample_vg<LDS>(F, nv, pitch, idv, __builtin_fma(xi_d, cb, ul), __builtin_fma(xi_d, sb, vl), Sx, Sy);
+          ds1 += Sx * x + Sy * y;
+          ds2 += Sy * x - Sx * y;
+        }
+      } else if (LDS) {
+        for (int ix = ix0; ix < ix1; ++ix, xi_d += 1.0)
+          acc += bicubic_sample_lds(F, nv, pitch, __builtin_fma(xi_d, cb, ul), __builtin_fma(xi_d, sb, vl));
+      } else {
+        acc = project_rolling_any<false>(F, nv, pitch, cb, sb, ul, vl, ix0, ix1);
+      }
+      if (proj) {
+        double* rec = proj2d_record(proj, point, nv) + nv;
+        rec[pt * nv + iy] = ds1;
+        rec[(nparts + pt) * nv + iy] = ds2;
+      }
+      part[pt * nv + iy] = acc;
+    }
+  } else {
+    for (int iy = gt; iy < nv; iy += kThreads) {
+      const double y = __builtin_fma((double)iy, dv, v0);
+      double acc = 0.0, ul, vl, xi_d = 0.0;
+      line_origin(cb, sb, y, v0, idv, ul, vl);
+      for (int ix = 0; ix < nv; ++ix, xi_d += 1.0)
+        acc += bicubic_sample(F, nv, pitch, __builtin_fma(xi_d, cb, ul), __builtin_fma(xi_d, sb, vl));
+      part[iy] = acc;
+    }
+  }
+}
+// d. the projection f1 = column sums x dv (rec: also into the point's projection record), and its gradient d1: one-sided at the ends
+__device__ __forceinline__ void column_sums_2d(const double* part, int nv, int nparts, double dv, int gt, double* f1, double* __restrict__ rec = nullptr) {
+  for (int i = gt; i < nv; i += kThreads) {
+    double sacc = 0.0;
+    for (int q = 0; q < nparts; ++q) sacc += part[q * nv + i];
+    f1[i] = sacc * dv;
+    if (rec) rec[i] = sacc * dv;
+  }
+}
+__device__ __forceinline__ void gradient_2d(const double* f1, int nv, double idv, int gt, double* d1) {
+  for (int i = gt; i < nv; i += kThreads) {
+    double gd;
+    if (i == 0) gd = (f1[1] - f1[0]) * idv;
+    else if (i == nv - 1) gd = (f1[nv - 1] - f1[nv - 2]) * idv;
+    else gd = (f1[i + 1] - f1[i - 1]) * (0.5 * idv);
+    d1[i] = gd;
+  }
+}
+// e. thread 0: spectrum of the point from R = ratintn sum (red[0..3]), f1, d1 and the scalars in sc[] (:560-585).  Everything the
+// adjoint's reverse reads comes back; the forward uses Sv and dop.
+template <int NI>
+struct Assembly2D {
+  int i; bool tin; double t;   // cell and fraction of |xi_e| on the grid; tin: not clamped
+  double R, fe_vphi, dfe, ike2, vph, xi[NI], zr[NI], zi[NI], dzr[NI], dzi[NI], gs[NI], iki2[NI];
+  double cer, cei, cre, cim, gsum, er, ei, eps2, ce2, ci2, N, Sv, dop;
+};
+template <int NI, bool REV>
+__device__ __forceinline__ void assemble_point_2d(const double2* zp, const double* sc, const double* red, const double* f1, const double* d1,
+                                                  int nv, double dv, double v0, double idv, double xmag, Assembly2D<NI>& A) {
+  A.R = (red[0] + red[1]) + (red[2] + red[3]);
+  const double k2 = sc[SC_K2], k = sc[SC_K], wd = sc[SC_WD], a_e = sc[SC_AE], ivTe = sc[SC_IVTE], wL = sc[SC_WL];
+  // jnp.interp(|xi_e|, vx, .): clamps to the end values
+  double u = (xmag - v0) * idv;
+  int i = (int)u;
+  i = i < 0 ? 0 : (i > nv - 2 ? nv - 2 : i);
+  double t = (xmag - (v0 + i * dv)) * idv;
+  A.tin = t >= 0.0 && t <= 1.0;
+  t = t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t);
+  A.i = i; A.t = t;
+  A.fe_vphi = f1[i] + t * (f1[i + 1] - f1[i]);
+  A.dfe = d1[i] + t * (d1[i + 1] - d1[i]);
+  A.ike2 = a_e / k2;
+  A.cer = -A.ike2 * A.R; A.cei = kPi * A.ike2 * A.dfe;
+  A.cre = 0.0; A.cim = 0.0; A.gsum = 0.0;
+  A.vph = wd / k;
+#pragma unroll
+  for (int s = 0; s < NI; ++s) {
+    A.xi[s] = A.vph * sc[SC_ION + 3 * s];
+    ion_terms(zp, A.xi[s], A.zr[s], A.zi[s], A.dzr[s], A.dzi[s], A.gs[s]);   // (one thread per point: the Z' table is read from global memory)
+    A.iki2[s] = sc[SC_ION + 1 + 3 * s] / k2;
+    A.cre -= 0.5 * A.iki2[s] * A.zr[s];
+    A.cim -= 0.5 * A.iki2[s] * A.zi[s];
+    A.gsum += sc[SC_ION + 2 + 3 * s] * A.gs[s];
+  }
+  A.er = 1.0 + A.cer + A.cre; A.ei = A.cei + A.cim;
+  // Of a sum of two products one is fused into the FMA; which one is written out, so that the result does not depend on the caller
+  // (left to the compiler the choice follows the order and the use counts of the code around the call).  The two kernels keep the
+  // roundings each of them has always had -- REV (the adjoint): eps2 and ci2 fuse the imaginary part's square, the forward the real
+  // part's; ce2 and N are the same in both.
+  const double opc = 1.0 + A.cre;
+  A.eps2 = REV ? __builtin_fma(A.ei, A.ei, A.er * A.er) : __builtin_fma(A.er, A.er, A.ei * A.ei);
+  A.ce2 = __builtin_fma(A.cer, A.cer, A.cei * A.cei);
+  A.ci2 = REV ? __builtin_fma(A.cim, A.cim, opc * opc) : __builtin_fma(opc, opc, A.cim * A.cim);
+  A.N = __builtin_fma(A.gsum, A.ce2, A.ci2 * A.fe_vphi * ivTe);
+  A.Sv = A.N / (k * A.eps2);
+  A.dop = 1.0 + 2.0 * wd / wL;
+}
+
 template <int NI, bool LDS, int kG2, bool SAVE = false>
 __global__ __launch_bounds__(kG2 * kThreads, TSFF_2D_WAVES) void k_form_factor_2d(KStatic S, const double* __restrict__ phys,
                                                                    const double* __restrict__ Fg, int nv,
                                                                    double ud_ang, double va_ang, int f, long pbegin,
                                                                    long pend, double* __restrict__ P,
                                                                    double* __restrict__ proj = nullptr) {
+  static_assert(SC_ION + 3 * TSFF_MAX_ION <= kSc2, "the forward's sc[] slots fit kSc2");
   extern __shared__ __align__(16) unsigned char smem[];
   const int grp = threadIdx.x >> 8, gt = threadIdx.x & (kThreads - 1);
-  // thread -> (column iy, part of the ix range): nparts = 256 / nvp with nvp = nv rounded up to 64, 128 or 256
-  const int nvp = nv <= 64 ? 64 : (nv <= 128 ? 128 : 256);
-  const int nparts = nv <= 256 ? kThreads / nvp : 1;
+  const int nvp = nvp2d(nv), nparts = parts2d(nv);
   double* gbase = reinterpret_cast<double*>(smem) + (size_t)grp * group2d_doubles(nv);
   double* f1 = gbase;              // [nv] projected distribution
   double* d1 = f1 + nv;            // [nv] its gradient
   double* part = d1 + nv;          // [nparts][nv] partial column sums
-  double* red = part + (nv <= 64 ? 4 : (nv <= 128 ? 2 : 1)) * nv;  // [8]
+  double* red = part + nparts * nv;     // [8]
   double* sc = red + 8;            // [kSc2] point scalars
   double* Fl = reinterpret_cast<double*>(smem) + (size_t)kG2 * group2d_doubles(nv);  // padded table (LDS variant)
-  const int NA = S.n_angles, G = S.G, npts = S.npts;
   const double dv = 12.0 / nv, v0 = -6.0 + 0.5 * dv, idv = 1.0 / dv;  // base.py:333-335
   const int pitch = pitch2d(nv, LDS);
-  if (LDS) {  // Fg: the plain nv x nv table; the ghost cells are made here
-    for (int i = threadIdx.x; i < nv * nv; i += kG2 * kThreads) Fl[(i / nv + 1) * pitch + (i % nv + 1)] = Fg[i];
-    __syncthreads();
-    ghost_rows(Fl, nv, pitch, threadIdx.x, kG2 * kThreads);
-    __syncthreads();
-    ghost_cols(Fl, nv, pitch, threadIdx.x, kG2 * kThreads);
-  }
+  if (LDS) stage_table_2d(Fg, Fl, nv, pitch, kG2 * kThreads);  // Fg: the plain nv x nv table
   const double* __restrict__ F = LDS ? Fl : Fg;  // (not LDS: Fg is the padded copy made by k_pad2d)
   const long stride = (long)gridDim.x * kG2;
   for (long base = pbegin + (long)blockIdx.x * kG2; base < pend; base += stride) {
     const long pid = base + grp;
     const bool active = pid < pend;  // every group runs the same barrier sequence; idle groups skip the work
     __syncthreads();
-    if (active && gt == 0) {
-      const int a = (int)(pid % NA), j = (int)((pid / NA) % npts), g = (int)((pid / ((long)NA * npts)) % G);
-      const int b = (int)(pid / ((long)NA * npts * G));
-      Phys<NI> p;
-      load_phys<NI>(phys + (size_t)b * S.NP, S.p_scale, S.p_shift, S.p_sig, S.ti_same, false, p);
-      LineS<NI> L;
-      make_lines<NI>(p, S.lam_shift[f], g, G, L);
-      // ---- point scalars (form_factor.py:515-558) ----
-      const double ws = S.omgs[f][j], th = S.sa_rad[a];
-      Point2D q;
-      point_scalars_2d<NI>(ws, th, L, va_ang, ud_ang, q);
-      const double k2 = q.k2, k = q.k, wd = q.wd;
-      sc[0] = q.cb; sc[1] = q.sb; sc[2] = q.xmag;
-      sc[3] = k2; sc[4] = k; sc[5] = wd; sc[6] = ws; sc[7] = L.a_e; sc[8] = L.ivTe; sc[9] = L.wL; sc[10] = L.pref;
-#pragma unroll
-      for (int s = 0; s < NI; ++s) { sc[12 + 3 * s] = L.ixi[s]; sc[13 + 3 * s] = L.a_i[s]; sc[14 + 3 * s] = L.cs[s]; }
-    }
+    if (active && gt == 0) point_setup_2d<NI, false>(S, phys, f, point_id_2d(pid, S), ud_ang, va_ang, sc);
     __syncthreads();
-    const double cb = sc[0], sb = sc[1], xmag = sc[2];
-    // ---- rotate + project (:300-324, 371) ----
+    const double cb = sc[SC_CB], sb = sc[SC_SB], xmag = sc[SC_XMAG];
     if (active) {
-      if (nv <= 256) {
-        const int iy = gt % nvp, pt = gt / nvp;
-        if (iy < nv) {
-          const int ix0 = (nv * pt) / nparts, ix1 = (nv * (pt + 1)) / nparts;
-          const double y = __builtin_fma((double)iy, dv, v0);
-          double acc = 0.0, ul, vl, xi_d = (double)ix0;
-          line_origin(cb, sb, y, v0, idv, ul, vl);
-          if (SAVE) {
-            double ds1 = 0.0, ds2 = 0.0;
-            if (!LDS) {
-              RollVG vg{idv, dv, v0, y, 0.0, 0.0};
-              acc = project_rolling_any<true>(F, nv, pitch, cb, sb, ul, vl, ix0, ix1, &vg);
-              ds1 = vg.ds1; ds2 = vg.ds2;
-            } else
-            for (int ix = ix0; ix < ix1; ++ix, xi_d += 1.0) {
-              const double x = __builtin_fma(xi_d, dv, v0);
-              double Sx, Sy;
-              acc += bicubic_sample_vg<LDS>(F, nv, pitch, idv, __builtin_fma(xi_d, cb, ul), __builtin_fma(xi_d, sb, vl), Sx, Sy);
-              ds1 += Sx * x + Sy * y;
-              ds2 += Sy * x - Sx * y;
-            }
-            double* rec = proj + (size_t)(pid - pbegin) * proj2d_doubles(nv) + nv;
-            rec[pt * nv + iy] = ds1;
-            rec[(nparts + pt) * nv + iy] = ds2;
-          } else if (LDS) {
-            for (int ix = ix0; ix < ix1; ++ix, xi_d += 1.0)
-              acc += bicubic_sample_lds(F, nv, pitch, __builtin_fma(xi_d, cb, ul), __builtin_fma(xi_d, sb, vl));
-          } else {
-            acc = project_rolling_any<false>(F, nv, pitch, cb, sb, ul, vl, ix0, ix1);
-          }
-          part[pt * nv + iy] = acc;
-        }
-      } else {
-        for (int iy = gt; iy < nv; iy += kThreads) {
-          const double y = __builtin_fma((double)iy, dv, v0);
-          double acc = 0.0, ul, vl, xi_d = 0.0;
-          line_origin(cb, sb, y, v0, idv, ul, vl);
-          for (int ix = 0; ix < nv; ++ix, xi_d += 1.0)
-            acc += bicubic_sample(F, nv, pitch, __builtin_fma(xi_d, cb, ul), __builtin_fma(xi_d, sb, vl));
-          part[iy] = acc;
-        }
-      }
+      double ds1 = 0.0, ds2 = 0.0;
+      project_point_2d<LDS, SAVE>(F, nv, pitch, nvp, nparts, cb, sb, dv, v0, idv, gt, part, ds1, ds2, SAVE ? proj : nullptr, pid - pbegin);
     }
     __syncthreads();
-    if (active) {
-      for (int i = gt; i < nv; i += kThreads) {
-        double sacc = 0.0;
-        for (int q = 0; q < nparts; ++q) sacc += part[q * nv + i];
-        f1[i] = sacc * dv;
-        if (SAVE) proj[(size_t)(pid - pbegin) * proj2d_doubles(nv) + i] = sacc * dv;
-      }
-    }
+    if (active) column_sums_2d(part, nv, nparts, dv, gt, f1, SAVE ? proj2d_record(proj, pid - pbegin, nv) : nullptr);
     __syncthreads();
-    if (active) {
-      for (int i = gt; i < nv; i += kThreads) {
-        double gd;
-        if (i == 0) gd = (f1[1] - f1[0]) * idv;
-        else if (i == nv - 1) gd = (f1[nv - 1] - f1[nv - 2]) * idv;
-        else gd = (f1[i + 1] - f1[i - 1]) * (0.5 * idv);
-        d1[i] = gd;
-      }
-    }
+    if (active) gradient_2d(f1, nv, idv, gt, d1);
     __syncthreads();
-    // ---- ratintn(df, vx - |xi_e|, vx): nv - 2 intervals (:372-387) ----
+    // ---- ratintn(df, vx - |xi_e|, vx): nv - 2 intervals (:372-387); the adjoint has its own form of this loop, see above ----
     double psum = 0.0;
     if (active) {
       for (int i = gt; i < nv - 2; i += kThreads) {
@@ -619,41 +738,16 @@ __global__ __launch_bounds__(kG2 * kThreads, TSFF_2D_WAVES) void k_form_factor_2
     if ((gt & 63) == 0) red[gt >> 6] = psum;
     __syncthreads();
     if (active && gt == 0) {
-      const double R = (red[0] + red[1]) + (red[2] + red[3]);
-      const double k2 = sc[3], k = sc[4], wd = sc[5], ws = sc[6], a_e = sc[7], ivTe = sc[8], wL = sc[9], pref = sc[10];
-      // jnp.interp(|xi_e|, vx, .): clamps to the end values
-      double u = (xmag - v0) * idv;
-      int i = (int)u;
-      i = i < 0 ? 0 : (i > nv - 2 ? nv - 2 : i);
-      double t = (xmag - (v0 + i * dv)) * idv;
-      t = t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t);
-      const double fe_vphi = f1[i] + t * (f1[i + 1] - f1[i]);
-      const double dfe = d1[i] + t * (d1[i + 1] - d1[i]);
-      const double ike2 = a_e / k2;
-      const double cer = -ike2 * R, cei = kPi * ike2 * dfe;
-      double cre = 0.0, cim = 0.0, gsum = 0.0;
-      const double vph = wd / k;
-#pragma unroll
-      for (int s = 0; s < NI; ++s) {
-        const double xi = vph * sc[12 + 3 * s];
-        double zr, zi, dzr, dzi, gs;
-        ion_terms(S.zp, xi, zr, zi, dzr, dzi, gs);   // (one thread per point: the Z' table is read from global memory)
-        const double iki2 = sc[13 + 3 * s] / k2;
-        cre -= 0.5 * iki2 * zr;
-        cim -= 0.5 * iki2 * zi;
-        gsum += sc[14 + 3 * s] * gs;
-      }
-      const double er = 1.0 + cer + cre, ei = cei + cim;
-      const double eps2 = er * er + ei * ei, ce2 = cer * cer + cei * cei;
-      const double ci2 = (1.0 + cre) * (1.0 + cre) + cim * cim;
-      const double Sv = (gsum * ce2 + ci2 * fe_vphi * ivTe) / (k * eps2);
-      P[pid] = Sv * (1.0 + 2.0 * wd / wL) * pref * ws * ws;
+      Assembly2D<NI> A;
+      assemble_point_2d<NI, false>(S.zp, sc, red, f1, d1, nv, dv, v0, idv, xmag, A);
+      P[pid] = A.Sv * A.dop * sc[SC_PREF] * sc[SC_WS] * sc[SC_WS];
     }
   }
 }
 
 // ------------------------------------------------------------------------------------------
-// Adjoint of k_form_factor_2d.  Same workgroup structure; per point, after the forward projection f1:
+// Adjoint of k_form_factor_2d.  The same workgroup structure and, up to the point's spectrum, the same shared steps (the projection
+// with its derivative sums, or read from the records of a saving forward); then, per point:
 //   one thread reverses the spectrum assembly (-> adjoints of R, fe(v_phi), dfe and of the point scalars),
 //   the group reverses ratintn, the two interpolations and the finite-difference gradient (-> f1bar[iy]),
 //   a second sampling sweep with derivative weights gives the adjoint of the rotation (cos beta, sin beta),
@@ -661,36 +755,6 @@ __global__ __launch_bounds__(kG2 * kThreads, TSFF_2D_WAVES) void k_form_factor_2
 // f1bar is also written to global memory for the table adjoint (k_ff2d_table_adj): the scatter into the table needs the
 // sample weights only, not the table, so it runs as a separate pass whose LDS holds the table ADJOINT.
 // ------------------------------------------------------------------------------------------
-constexpr int kNLB2 = 8;  // + 3 per ion: wpe2, wL, kL, ivTe, a_e, pref, Ud, Vd | ixi, a_i, cs
-
-// value and both first derivatives of one bicubic sample (ghost-padded table, see bicubic_sample)
-__device__ __forceinline__ void bicubic_sample_grad(const double* __restrict__ Fp, int nv, int pitch, double idv, double u,
-                                                    double v, double& Sx, double& Sy) {
-  int cx, cy;
-  double tx, ty;
-  cell_of(u, nv, cx, tx);
-  cell_of(v, nv, cy, ty);
-  double wx[4], wy[4], dx[4], dy[4];
-  catmull_rom(tx, wx);
-  catmull_rom(ty, wy);
-  dx[0] = -0.5 * (3.0 * tx * tx - 4.0 * tx + 1.0); dx[1] = 4.5 * tx * tx - 5.0 * tx;
-  dx[2] = -4.5 * tx * tx + 4.0 * tx + 0.5;         dx[3] = 1.5 * tx * tx - tx;
-  dy[0] = -0.5 * (3.0 * ty * ty - 4.0 * ty + 1.0); dy[1] = 4.5 * ty * ty - 5.0 * ty;
-  dy[2] = -4.5 * ty * ty + 4.0 * ty + 0.5;         dy[3] = 1.5 * ty * ty - ty;
-  const double* __restrict__ q0 = Fp + (size_t)cx * pitch + cy;
-  double sx = 0.0, sy = 0.0;
-#pragma unroll
-  for (int m = 0; m < 4; ++m) {
-    const double* __restrict__ row = q0 + (size_t)m * pitch;
-    const double r = wy[0] * row[0] + wy[1] * row[1] + wy[2] * row[2] + wy[3] * row[3];
-    const double rd = dy[0] * row[0] + dy[1] * row[1] + dy[2] * row[2] + dy[3] * row[3];
-    sx += dx[m] * r;
-    sy += wx[m] * rd;
-  }
-  Sx = sx * idv;   // d / d xq = (1 / dv) d / du
-  Sy = sy * idv;
-}
-
 template <int NI, bool LDS, int kG2>
 __global__ __launch_bounds__(kG2 * kThreads) void k_form_factor_2d_adj(KStatic S, const double* __restrict__ phys,
                                                                        const double* __restrict__ Fg, int nv, double ud_ang,
@@ -698,124 +762,57 @@ __global__ __launch_bounds__(kG2 * kThreads) void k_form_factor_2d_adj(KStatic S
                                                                        const double* __restrict__ Pbar,
                                                                        double* __restrict__ LBacc, double* __restrict__ f1bar_out,
                                                                        const double* __restrict__ proj = nullptr) {
+  constexpr int NLB = kNLB2 + 3 * NI;
+  static_assert(SC_ACC + kNLB2 + 3 * TSFF_MAX_ION + 1 <= kScA, "the adjoint's sc[] slots fit kScA");
   extern __shared__ __align__(16) unsigned char smem[];
   const int grp = threadIdx.x >> 8, gt = threadIdx.x & (kThreads - 1);
-  const int nvp = nv <= 64 ? 64 : (nv <= 128 ? 128 : 256);
-  const int nparts = nv <= 256 ? kThreads / nvp : 1;
-  constexpr int kScA = 96;   // [0, 64) point scalars and adjoints, [64, 64 + NLB] running sums of the lineout-scalar adjoints
-  const size_t gsz = (2 + (size_t)(nv <= 64 ? 4 : (nv <= 128 ? 2 : 1))) * nv + 2 * (size_t)nv + 16 + kScA;
-  double* gbase = reinterpret_cast<double*>(smem) + (size_t)grp * gsz;
+  const int nvp = nvp2d(nv), nparts = parts2d(nv);
+  double* gbase = reinterpret_cast<double*>(smem) + (size_t)grp * group2d_adj_doubles(nv);
   double* f1 = gbase;              // [nv] projected distribution, later f1bar
   double* d1 = f1 + nv;            // [nv] its gradient, later d1bar
   double* part = d1 + nv;          // [nparts][nv] partial sums (two values per part in the derivative sweep: reused)
-  double* c0 = part + (nv <= 64 ? 4 : (nv <= 128 ? 2 : 1)) * nv;  // [nv] per-interval adjoint to d1[i]
+  double* c0 = part + nparts * nv;  // [nv] per-interval adjoint to d1[i]
   double* c1 = c0 + nv;            // [nv] per-interval adjoint to d1[i + 1]
   double* red = c1 + nv;           // [16]
   double* sc = red + 16;           // [kScA] point scalars and adjoints
-  double* Fl = reinterpret_cast<double*>(smem) + (size_t)kG2 * gsz;
-  const int NA = S.n_angles, G = S.G, npts = S.npts;
-  constexpr int NLB = kNLB2 + 3 * NI;
+  double* Fl = reinterpret_cast<double*>(smem) + (size_t)kG2 * group2d_adj_doubles(nv);
   const double dv = 12.0 / nv, v0 = -6.0 + 0.5 * dv, idv = 1.0 / dv;
   const int pitch = pitch2d(nv, LDS);
-  if (LDS) {
-    for (int i = threadIdx.x; i < nv * nv; i += kG2 * kThreads) Fl[(i / nv + 1) * pitch + (i % nv + 1)] = Fg[i];
-    __syncthreads();
-    ghost_rows(Fl, nv, pitch, threadIdx.x, kG2 * kThreads);
-    __syncthreads();
-    ghost_cols(Fl, nv, pitch, threadIdx.x, kG2 * kThreads);
-  }
+  if (LDS) stage_table_2d(Fg, Fl, nv, pitch, kG2 * kThreads);
   const double* __restrict__ F = LDS ? Fl : Fg;
-  if (gt == 0) sc[64 + NLB] = -1.0;   // no (lineout, gradient point) accumulated yet (each group's thread 0 owns its slot)
+  if (gt == 0) sc[SC_ACC + NLB] = -1.0;   // no (lineout, gradient point) accumulated yet (each group's thread 0 owns its slot)
   const int nworker = (int)gridDim.x * kG2, worker = (int)blockIdx.x * kG2 + grp;   // one partial slot per point group
   const long stride = (long)gridDim.x * kG2;
   for (long base = pbegin + (long)blockIdx.x * kG2; base < pend; base += stride) {
     const long pid = base + grp;
     const bool active = pid < pend;
-    const int a = (int)(pid % NA), j = (int)((pid / NA) % npts), g = (int)((pid / ((long)NA * npts)) % G);
-    const int b = (int)(pid / ((long)NA * npts * G));
     __syncthreads();
-    if (active && gt == 0) {
-      Phys<NI> p;
-      load_phys<NI>(phys + (size_t)b * S.NP, S.p_scale, S.p_shift, S.p_sig, S.ti_same, false, p);
-      LineS<NI> L;
-      make_lines<NI>(p, S.lam_shift[f], g, G, L);
-      const double ws = S.omgs[f][j], th = S.sa_rad[a];
-      Point2D q;
-      point_scalars_2d<NI>(ws, th, L, va_ang, ud_ang, q);   // (the forward's own function: the same rotation, the same projection, bit for bit)
-      const double ks = q.ks, ct = q.ct, st = q.st, kx = q.kx, ky = q.ky, k2 = q.k2, k = q.k, Vx = q.Vx, Vy = q.Vy, Ux = q.Ux, Uy = q.Uy;
-      const double wd = q.wd, aa = q.aa, xex = q.xex, xey = q.xey;
-      sc[0] = q.cb; sc[1] = q.sb; sc[2] = q.xmag;   // cos / sin of beta (atan + heaviside of :552-558)
-      sc[3] = k2; sc[4] = k; sc[5] = wd; sc[6] = ws; sc[7] = L.a_e; sc[8] = L.ivTe; sc[9] = L.wL; sc[10] = L.pref;
-      sc[11] = kx; sc[12] = ky; sc[13] = aa; sc[14] = xex; sc[15] = xey; sc[16] = ks; sc[17] = Vx; sc[18] = Vy;
-      sc[19] = Ux; sc[20] = Uy; sc[21] = ct; sc[22] = st;
-#pragma unroll
-      for (int s = 0; s < NI; ++s) { sc[24 + 3 * s] = L.ixi[s]; sc[25 + 3 * s] = L.a_i[s]; sc[26 + 3 * s] = L.cs[s]; }
-    }
+    if (active && gt == 0) point_setup_2d<NI, true>(S, phys, f, point_id_2d(pid, S), ud_ang, va_ang, sc);   // (the forward's own set-up: the same rotation, the same projection, bit for bit)
     __syncthreads();
-    const double cb = sc[0], sb = sc[1], xmag = sc[2];
+    const double cb = sc[SC_CB], sb = sc[SC_SB], xmag = sc[SC_XMAG];
     // ---- forward projection; with one column per thread (nv <= 256) also the derivative sums of that column ----
     double ds1 = 0.0, ds2 = 0.0;   // sum over the thread's samples of d sample / d cos(beta), d sample / d sin(beta)
     if (active && proj) {           // the SAVE pass of the forward left both: no sampling here
-      const double* rec = proj + (size_t)(pid - pbegin) * proj2d_doubles(nv);
+      const double* rec = proj2d_record(proj, pid - pbegin, nv);
       const int iy = gt % nvp, pt = gt / nvp;
       if (iy < nv) {
         ds1 = rec[nv + pt * nv + iy];
         ds2 = rec[nv + (nparts + pt) * nv + iy];
       }
     } else if (active) {
-      if (nv <= 256) {
-        const int iy = gt % nvp, pt = gt / nvp;
-        if (iy < nv) {
-          const int ix0 = (nv * pt) / nparts, ix1 = (nv * (pt + 1)) / nparts;
-          const double y = __builtin_fma((double)iy, dv, v0);
-          double acc = 0.0, ul, vl, xi_d = (double)ix0;
-          line_origin(cb, sb, y, v0, idv, ul, vl);
-          if (!LDS) {
-            RollVG vg{idv, dv, v0, y, 0.0, 0.0};
-            acc = project_rolling_any<true>(F, nv, pitch, cb, sb, ul, vl, ix0, ix1, &vg);
-            ds1 = vg.ds1; ds2 = vg.ds2;
-          } else
-          for (int ix = ix0; ix < ix1; ++ix, xi_d += 1.0) {
-            const double x = __builtin_fma(xi_d, dv, v0);
-            double Sx, Sy;
-            acc += bicubic_sample_vg<LDS>(F, nv, pitch, idv, __builtin_fma(xi_d, cb, ul), __builtin_fma(xi_d, sb, vl), Sx, Sy);
-            ds1 += Sx * x + Sy * y;
-            ds2 += Sy * x - Sx * y;
-          }
-          part[pt * nv + iy] = acc;
-        }
-      } else {
-        for (int iy = gt; iy < nv; iy += kThreads) {
-          const double y = __builtin_fma((double)iy, dv, v0);
-          double acc = 0.0, ul, vl, xi_d = 0.0;
-          line_origin(cb, sb, y, v0, idv, ul, vl);
-          for (int ix = 0; ix < nv; ++ix, xi_d += 1.0)
-            acc += bicubic_sample(F, nv, pitch, __builtin_fma(xi_d, cb, ul), __builtin_fma(xi_d, sb, vl));
-          part[iy] = acc;
-        }
-      }
+      project_point_2d<LDS, true>(F, nv, pitch, nvp, nparts, cb, sb, dv, v0, idv, gt, part, ds1, ds2);
     }
     __syncthreads();
     if (active && proj) {
-      const double* rec = proj + (size_t)(pid - pbegin) * proj2d_doubles(nv);
+      const double* rec = proj2d_record(proj, pid - pbegin, nv);
       for (int i = gt; i < nv; i += kThreads) f1[i] = rec[i];
     } else if (active)
-      for (int i = gt; i < nv; i += kThreads) {
-        double sacc = 0.0;
-        for (int q = 0; q < nparts; ++q) sacc += part[q * nv + i];
-        f1[i] = sacc * dv;
-      }
+      column_sums_2d(part, nv, nparts, dv, gt, f1);
     __syncthreads();
-    if (active)
-      for (int i = gt; i < nv; i += kThreads) {
-        double gd;
-        if (i == 0) gd = (f1[1] - f1[0]) * idv;
-        else if (i == nv - 1) gd = (f1[nv - 1] - f1[nv - 2]) * idv;
-        else gd = (f1[i + 1] - f1[i - 1]) * (0.5 * idv);
-        d1[i] = gd;
-      }
+    if (active) gradient_2d(f1, nv, idv, gt, d1);
     __syncthreads();
-    // ---- ratintn forward (value) and its partial derivatives per interval ----
+    // ---- ratintn forward (value) and its partial derivatives per interval (the small-interval branch through ig and c, which the
+    //      partials reuse: not the forward's roundings, see the shared steps) ----
     double psum = 0.0;
     if (active)
       for (int i = gt; i < nv - 2; i += kThreads) {
@@ -846,83 +843,57 @@ __global__ __launch_bounds__(kG2 * kThreads) void k_form_factor_2d_adj(KStatic S
     __syncthreads();
     // ---- one thread: forward assembly and its reverse ----
     if (active && gt == 0) {
-      const double R = (red[0] + red[1]) + (red[2] + red[3]);
-      const double k2 = sc[3], k = sc[4], wd = sc[5], ws = sc[6], a_e = sc[7], ivTe = sc[8], wL = sc[9], pref = sc[10];
-      double u = (xmag - v0) * idv;
-      int i = (int)u;
-      i = i < 0 ? 0 : (i > nv - 2 ? nv - 2 : i);
-      double t = (xmag - (v0 + i * dv)) * idv;
-      const bool tin = t >= 0.0 && t <= 1.0;
-      t = t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t);
-      const double fe_vphi = f1[i] + t * (f1[i + 1] - f1[i]);
-      const double dfe = d1[i] + t * (d1[i + 1] - d1[i]);
-      const double ike2 = a_e / k2;
-      const double cer = -ike2 * R, cei = kPi * ike2 * dfe;
-      double cre = 0.0, cim = 0.0, gsum = 0.0;
-      const double vph = wd / k;
-      double xi[NI], zr[NI], zi[NI], dzr[NI], dzi[NI], gs[NI], iki2[NI];
-#pragma unroll
-      for (int s = 0; s < NI; ++s) {
-        xi[s] = vph * sc[24 + 3 * s];
-        ion_terms(S.zp, xi[s], zr[s], zi[s], dzr[s], dzi[s], gs[s]);
-        iki2[s] = sc[25 + 3 * s] / k2;
-        cre -= 0.5 * iki2[s] * zr[s];
-        cim -= 0.5 * iki2[s] * zi[s];
-        gsum += sc[26 + 3 * s] * gs[s];
-      }
-      const double er = 1.0 + cer + cre, ei = cei + cim;
-      const double eps2 = er * er + ei * ei, ce2 = cer * cer + cei * cei;
-      const double ci2 = (1.0 + cre) * (1.0 + cre) + cim * cim;
-      const double N = gsum * ce2 + ci2 * fe_vphi * ivTe;
-      const double Sv = N / (k * eps2);
-      const double dop = 1.0 + 2.0 * wd / wL, Q = pref * ws * ws;
+      const double k2 = sc[SC_K2], k = sc[SC_K], wd = sc[SC_WD], ws = sc[SC_WS], a_e = sc[SC_AE], ivTe = sc[SC_IVTE], wL = sc[SC_WL];
+      Assembly2D<NI> A;
+      assemble_point_2d<NI, true>(S.zp, sc, red, f1, d1, nv, dv, v0, idv, xmag, A);
+      const double Q = sc[SC_PREF] * ws * ws;
       // reverse
       const double Pb = Pbar[pid];
-      const double Svb = Pb * dop * Q;
-      double wdb = Pb * Sv * Q * 2.0 / wL;
-      double wLb = -Pb * Sv * Q * 2.0 * wd / (wL * wL);
-      const double prefb = Pb * Sv * dop * ws * ws;
-      const double Nb = Svb / (k * eps2);
-      double kb = -Svb * N / (k * k * eps2);
-      const double eps2b = -Svb * N / (k * eps2 * eps2);
-      const double gsumb = Nb * ce2, ce2b = Nb * gsum, ci2b = Nb * fe_vphi * ivTe;
-      const double fevb = Nb * ci2 * ivTe;
-      double ivTeb = Nb * ci2 * fe_vphi;
-      const double erb = 2.0 * er * eps2b, eib = 2.0 * ei * eps2b;
-      const double cerb = erb + 2.0 * cer * ce2b, ceib = eib + 2.0 * cei * ce2b;
-      const double creb = erb + 2.0 * (1.0 + cre) * ci2b, cimb = eib + 2.0 * cim * ci2b;
-      double ike2b = -cerb * R + ceib * kPi * dfe;
-      const double Rb = -cerb * ike2, dfeb = ceib * kPi * ike2;
+      const double Svb = Pb * A.dop * Q;
+      double wdb = Pb * A.Sv * Q * 2.0 / wL;
+      double wLb = -Pb * A.Sv * Q * 2.0 * wd / (wL * wL);
+      const double prefb = Pb * A.Sv * A.dop * ws * ws;
+      const double Nb = Svb / (k * A.eps2);
+      double kb = -Svb * A.N / (k * k * A.eps2);
+      const double eps2b = -Svb * A.N / (k * A.eps2 * A.eps2);
+      const double gsumb = Nb * A.ce2, ce2b = Nb * A.gsum, ci2b = Nb * A.fe_vphi * ivTe;
+      const double fevb = Nb * A.ci2 * ivTe;
+      double ivTeb = Nb * A.ci2 * A.fe_vphi;
+      const double erb = 2.0 * A.er * eps2b, eib = 2.0 * A.ei * eps2b;
+      const double cerb = erb + 2.0 * A.cer * ce2b, ceib = eib + 2.0 * A.cei * ce2b;
+      const double creb = erb + 2.0 * (1.0 + A.cre) * ci2b, cimb = eib + 2.0 * A.cim * ci2b;
+      double ike2b = -cerb * A.R + ceib * kPi * A.dfe;
+      const double Rb = -cerb * A.ike2, dfeb = ceib * kPi * A.ike2;
       const double a_eb = ike2b / k2;
       double k2b = -ike2b * a_e / (k2 * k2);
       double vphb = 0.0;
-      double* ob = sc + 44;  // adjoints of the ion scalars: [ixi, a_i, cs] per species
+      double* ob = sc + SC_IONB;  // adjoints of the ion scalars: [ixi, a_i, cs] per species
 #pragma unroll
       for (int s = 0; s < NI; ++s) {
-        const double iki2b = -0.5 * (creb * zr[s] + cimb * zi[s]);
-        const double zrb = -0.5 * iki2[s] * creb, zib = -0.5 * iki2[s] * cimb;
-        const double gsb = gsumb * sc[26 + 3 * s];
-        const double xib = zrb * dzr[s] + zib * dzi[s] + gsb * gs[s] * (-2.0 * xi[s]);
-        ob[3 * s + 2] = gsumb * gs[s];            // cs
+        const double iki2b = -0.5 * (creb * A.zr[s] + cimb * A.zi[s]);
+        const double zrb = -0.5 * A.iki2[s] * creb, zib = -0.5 * A.iki2[s] * cimb;
+        const double gsb = gsumb * sc[SC_ION + 2 + 3 * s];
+        const double xib = zrb * A.dzr[s] + zib * A.dzi[s] + gsb * A.gs[s] * (-2.0 * A.xi[s]);
+        ob[3 * s + 2] = gsumb * A.gs[s];          // cs
         ob[3 * s + 1] = iki2b / k2;               // a_i
-        k2b -= iki2b * sc[25 + 3 * s] / (k2 * k2);
-        vphb += xib * sc[24 + 3 * s];
-        ob[3 * s] = xib * vph;                    // ixi
+        k2b -= iki2b * sc[SC_ION + 1 + 3 * s] / (k2 * k2);
+        vphb += xib * sc[SC_ION + 3 * s];
+        ob[3 * s] = xib * A.vph;                  // ixi
       }
       wdb += vphb / k;
       kb -= vphb * wd / (k * k);
       k2b += kb / (2.0 * k);
       // the two interpolations at |xi_e| (jnp.interp: zero slope where clamped)
-      double xmagb = tin ? (fevb * (f1[i + 1] - f1[i]) + dfeb * (d1[i + 1] - d1[i])) * idv : 0.0;
-      sc[36] = Rb; sc[37] = fevb; sc[38] = dfeb; sc[39] = (double)i; sc[40] = t;
-      sc[41] = xmagb; sc[42] = wdb; sc[43] = wLb; sc[56] = prefb; sc[57] = ivTeb; sc[58] = a_eb; sc[59] = k2b;
+      double xmagb = A.tin ? (fevb * (f1[A.i + 1] - f1[A.i]) + dfeb * (d1[A.i + 1] - d1[A.i])) * idv : 0.0;
+      sc[SC_RB] = Rb; sc[SC_FEVB] = fevb; sc[SC_DFEB] = dfeb; sc[SC_IL] = (double)A.i; sc[SC_T] = A.t;
+      sc[SC_XMAGB] = xmagb; sc[SC_WDB] = wdb; sc[SC_WLB] = wLb; sc[SC_PREFB] = prefb; sc[SC_IVTEB] = ivTeb; sc[SC_AEB] = a_eb; sc[SC_K2B] = k2b;
     }
     __syncthreads();
     // ---- group: d1bar, xmagbar (ratintn part), f1bar ----
     double xms = 0.0;
     if (active) {
-      const double Rb = sc[36], dfeb = sc[38], t = sc[40];
-      const int il = (int)sc[39];
+      const double Rb = sc[SC_RB], dfeb = sc[SC_DFEB], t = sc[SC_T];
+      const int il = (int)sc[SC_IL];
       for (int i = gt; i < nv - 2; i += kThreads) xms += part[i] * Rb;
       for (int i = gt; i < nv; i += kThreads) {
         double v = 0.0;
@@ -937,8 +908,8 @@ __global__ __launch_bounds__(kG2 * kThreads) void k_form_factor_2d_adj(KStatic S
     if ((gt & 63) == 0) red[8 + (gt >> 6)] = xms;
     __syncthreads();
     if (active) {
-      const double fevb = sc[37], t = sc[40];
-      const int il = (int)sc[39];
+      const double fevb = sc[SC_FEVB], t = sc[SC_T];
+      const int il = (int)sc[SC_IL];
       for (int i = gt; i < nv; i += kThreads) {   // gradient stencil transposed + the fe(v_phi) interpolation
         double v = 0.0;
         if (i + 1 <= nv - 2 && i + 1 >= 1) v -= 0.5 * idv * c0[i + 1];
@@ -976,7 +947,7 @@ __global__ __launch_bounds__(kG2 * kThreads) void k_form_factor_2d_adj(KStatic S
           for (int ix = 0; ix < nv; ++ix) {
             const double x = v0 + ix * dv;
             double Sx, Sy;
-            bicubic_sample_grad(F, nv, pitch, idv, __builtin_fma((double)ix, cb, ul), __builtin_fma((double)ix, sb, vl), Sx, Sy);
+            bicubic_sample_vg<false>(F, nv, pitch, idv, __builtin_fma((double)ix, cb, ul), __builtin_fma((double)ix, sb, vl), Sx, Sy);
             s1 += Sx * x + Sy * y;
             s2 += -Sx * y + Sy * x;
           }
@@ -992,13 +963,13 @@ __global__ __launch_bounds__(kG2 * kThreads) void k_form_factor_2d_adj(KStatic S
     // ---- one thread: chain to the lineout scalars ----
     if (active && gt == 0) {
       const double cbb = (red[0] + red[1]) + (red[2] + red[3]), sbb = (red[4] + red[5]) + (red[6] + red[7]);
-      double xmagb = sc[41] + (red[8] + red[9]) + (red[10] + red[11]);
-      double wdb = sc[42], wLb = sc[43], ivTeb = sc[57], k2b = sc[59];
-      const double prefb = sc[56], a_eb = sc[58];
-      const double k2 = sc[3], wd = sc[5], ivTe = sc[8], kx = sc[11], ky = sc[12], aa = sc[13], xex = sc[14], xey = sc[15];
-      const double ks = sc[16], Vx = sc[17], Vy = sc[18], Ux = sc[19], Uy = sc[20], ct = sc[21], st = sc[22];
+      double xmagb = sc[SC_XMAGB] + (red[8] + red[9]) + (red[10] + red[11]);
+      double wdb = sc[SC_WDB], wLb = sc[SC_WLB], ivTeb = sc[SC_IVTEB], k2b = sc[SC_K2B];
+      const double prefb = sc[SC_PREFB], a_eb = sc[SC_AEB];
+      const double k2 = sc[SC_K2], wd = sc[SC_WD], ivTe = sc[SC_IVTE], kx = sc[SC_KX], ky = sc[SC_KY], aa = sc[SC_AA], xex = sc[SC_XEX], xey = sc[SC_XEY];
+      const double ks = sc[SC_KS], Vx = sc[SC_VX], Vy = sc[SC_VY], Ux = sc[SC_UX], Uy = sc[SC_UY], ct = sc[SC_CT], st = sc[SC_ST];
       // cb = xex / xmag, sb = xey / xmag, xmag = |(xex, xey)|
-      const double xm = sc[2];
+      const double xm = sc[SC_XMAG];
       const double xmt = xmagb - (cbb * xex + sbb * xey) / (xm * xm);
       const double xexb = cbb / xm + xmt * xex / xm, xeyb = sbb / xm + xmt * xey / xm;
       // xex = (aa kx - Ux) ivTe
@@ -1021,11 +992,11 @@ __global__ __launch_bounds__(kG2 * kThreads) void k_form_factor_2d_adj(KStatic S
       const double wpe2b = -ksb / (2.0 * kC * kC * ks);
       const double Vdb = Vxb * cos(va_ang) + Vyb * sin(va_ang);
       const double Udb = Uxb * cos(ud_ang) + Uyb * sin(ud_ang);
-      // running sums per group in LDS, flushed with one set of global atomics when the (lineout, gradient point) of the
+      // running sums per group in LDS, flushed into the worker's partial slot when the (lineout, gradient point) of the
       // group's points changes and at the end: every point of an ARTS image belongs to the same (b, g), and 250 000 atomic
       // updates of the same eleven addresses had made this the longest phase of the kernel (24 of 28 ms)
-      double* accl = sc + 64;
-      const double bg = (double)((long)b * G + g);
+      double* accl = sc + SC_ACC;
+      const double bg = sc[SC_BG];
       if (accl[NLB] != bg) {
         if (accl[NLB] >= 0.0) {   // (plain stores into this worker's own slot: k_lbacc_reduce sums the workers in a fixed order)
           double* o = LBacc + ((size_t)accl[NLB] * nworker + worker) * NLB;
@@ -1037,12 +1008,12 @@ __global__ __launch_bounds__(kG2 * kThreads) void k_form_factor_2d_adj(KStatic S
       accl[0] += wpe2b; accl[1] += wLb; accl[2] += kLb; accl[3] += ivTeb;
       accl[4] += a_eb; accl[5] += prefb; accl[6] += Udb; accl[7] += Vdb;
 #pragma unroll
-      for (int s = 0; s < NI; ++s) { accl[8 + 3 * s] += sc[44 + 3 * s]; accl[9 + 3 * s] += sc[45 + 3 * s]; accl[10 + 3 * s] += sc[46 + 3 * s]; }
+      for (int s = 0; s < NI; ++s) { accl[kNLB2 + 3 * s] += sc[SC_IONB + 3 * s]; accl[kNLB2 + 1 + 3 * s] += sc[SC_IONB + 1 + 3 * s]; accl[kNLB2 + 2 + 3 * s] += sc[SC_IONB + 2 + 3 * s]; }
     }
   }
-  if (gt == 0 && sc[64 + NLB] >= 0.0) {   // flush of the last (lineout, gradient point) of this group
-    double* o = LBacc + ((size_t)sc[64 + NLB] * nworker + worker) * NLB;
-    for (int k = 0; k < NLB; ++k) o[k] = sc[64 + k];
+  if (gt == 0 && sc[SC_ACC + NLB] >= 0.0) {   // flush of the last (lineout, gradient point) of this group
+    double* o = LBacc + ((size_t)sc[SC_ACC + NLB] * nworker + worker) * NLB;
+    for (int k = 0; k < NLB; ++k) o[k] = sc[SC_ACC + k];
   }
 }
 

@@ -1490,11 +1490,9 @@ static int form_factor_2d_adj_prepare(tsff_handle* h, int feature, int nv, int B
   const int NLB = kNLB2 + 3 * h->n_ion;
   const long npoint = end - begin;
   constexpr int kGL = TSFF_2D_GROUPS_LDS, kGG = TSFF_2D_GROUPS_L2;
-  const size_t gsz = (2 + (size_t)(nv <= 64 ? 4 : (nv <= 128 ? 2 : 1))) * nv + 2 * (size_t)nv + 16 + 96;   // doubles per point group
-  const size_t tsz = (size_t)(nv + 2) * pitch2d(nv, true);                                                 // the table in LDS
-  p.lds = sizeof(double) * (kGL * gsz + tsz) <= kLdsLimit;
+  p.lds = sizeof(double) * smem2d_adj_doubles(nv, true, kGL) <= kLdsLimit;
   p.groups = p.lds ? kGL : kGG;
-  p.smem = sizeof(double) * (p.groups * gsz + (p.lds ? tsz : 0));
+  p.smem = sizeof(double) * smem2d_adj_doubles(nv, p.lds, p.groups);
   if (p.smem > kLdsLimit) return fail(h, -2, "nv = %d needs %zu B of LDS scratch", nv, p.smem);
   const long want = (long)h->ncu2d() * (p.lds ? 1 : 8);
   p.grid = dim3((unsigned)std::max<long>(1, std::min((npoint + p.groups - 1) / p.groups, want)));
