@@ -727,6 +727,7 @@ def form_factor_2d(lam_range, npts, lam_shift, sa_deg, num_grad_points, p, vx, f
     beta = np.arctan(xie[1] / xie[0]) + np.pi * (-np.heaviside(xie[0], 1) + 1)
     if debug is not None:   # (tests: which rotation angles a deck exercises)
         debug["beta"] = beta
+        debug["xie_mag"], debug["xii"] = xie_mag, xii   # (tests: how far a point lies from the kinks of the two lookups)
     shp = beta.shape
     fe_vphi = np.empty(shp)
     chiEI = np.empty(shp)

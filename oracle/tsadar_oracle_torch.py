@@ -8,6 +8,9 @@ reference's golden vector; its gradients are checked against finite differences 
 oracle.  Sub-gradient conventions are those of JAX: ``max`` -> one-hot at the arg-max (torch.amax
 splits ties evenly; ties have measure zero), linear interpolation -> slope of the active segment,
 ``where`` masks -> pass-through.
+
+The second half restates the oracle's 2-D form factor (rotate_df, calc_chi_vals_2d, form_factor_2d) and its ARTS instrument chain
+(ats_spectrum); ``ff2d_adjoint`` / ``ats_adjoint`` are the references of tests/test_ff2d_adjoint_twin.py.
 """
 from __future__ import annotations
 
@@ -62,21 +65,33 @@ def gradient_uniform(f, h):
     return torch.cat([((f[1] - f[0]) / h)[None], (f[2:] - f[:-2]) / (2 * h), ((f[-1] - f[-2]) / h)[None]])
 
 
+def ratcen(f, g):
+    """ratintn.py:26-52 (see tsadar_oracle.ratcen).  ``f``: [N], ``g``: [..., N]; the branch is chosen from detached values, and
+    the branch not taken is evaluated at a harmless argument so that it cannot leak a NaN into the gradient."""
+    fdif = f[1:-1] - f[0:-2]
+    gdif = g[..., 1:-1] - g[..., 0:-2]
+    fav = 0.5 * (f[1:-1] + f[0:-2])
+    gav = 0.5 * (g[..., 1:-1] + g[..., 0:-2])
+    small = (torch.abs(gdif) < 1.0e-4 * torch.abs(gav)).detach()
+    tmp = fav * gdif - gav * fdif
+    gav_s = torch.where(small, gav, torch.ones_like(gav))
+    rf = fav / gav_s + tmp * gdif / (12.0 * gav_s**3)
+    rfn = fdif / gdif + tmp * torch.log(torch.abs((gav + 0.5 * gdif) / (gav - 0.5 * gdif))) / gdif**2
+    return torch.where(small, rf, rfn)
+
+
+def ratintn(f, g, z):
+    """ratintn.py:4-23 (see tsadar_oracle.ratintn): sum(ratcen(f, g) * (z[1:-1] - z[0:-2]))."""
+    zdif = z[1:-1] - z[0:-2]
+    return torch.sum(ratcen(f, g) * zdif, dim=-1)
+
+
 def chi_table(vx, fe):
-    """form_factor.py:263-268 + ratintn.py (differentiable in fe)."""
+    """form_factor.py:263-268 (see tsadar_oracle.chi_table; differentiable in fe)."""
     xi1, xi2 = (_t(a) for a in orc.xi_grids())
     ratmod = torch.exp(interp_hermite(xi1, vx, torch.log(fe), -50.0, -50.0))
     ratdf = gradient_uniform(ratmod, xi1[1] - xi1[0])
-    g = xi1[None, :] - xi2[:, None]
-    f = ratdf
-    fdif = f[1:-1] - f[0:-2]
-    gdif = g[:, 1:-1] - g[:, 0:-2]
-    fav = 0.5 * (f[1:-1] + f[0:-2])
-    gav = 0.5 * (g[:, 1:-1] + g[:, 0:-2])
-    tmp = fav * gdif - gav * fdif
-    rfn = fdif / gdif + tmp * torch.log(torch.abs((gav + 0.5 * gdif) / (gav - 0.5 * gdif))) / gdif**2
-    zdif = xi1[1:-1] - xi1[0:-2]
-    return torch.sum(rfn * zdif, dim=1)
+    return ratintn(ratdf, xi1[None, :] - xi2[:, None], xi1)
 
 
 def dlm_fe(m, nvx):
@@ -186,6 +201,14 @@ def _conv_same(x, g):
     full = torch.nn.functional.conv1d(x.reshape(1, 1, -1), g.flip(0).reshape(1, 1, -1), padding=n - 1).reshape(-1)
     c = (n - 1) // 2
     return full[c : c + n]
+
+
+def _conv_same_matrix(g):
+    """The matrix T with T @ x = _conv_same(x, g) for len(x) = len(g) = n: T[i, j] = g[i + (n - 1) // 2 - j] inside the kernel,
+    zero outside.  One product convolves every column of an image."""
+    n = g.numel()
+    k = torch.arange(n)[:, None] + (n - 1) // 2 - torch.arange(n)[None, :]
+    return torch.where((k >= 0) & (k < n), g[k.clamp(0, n - 1)], torch.zeros((), dtype=DT))
 
 
 def _irf(lam, modl, stddev):
@@ -364,3 +387,282 @@ def value_and_grad_fe(cfg, sa, normed_np, batch, i_norm, e_norm, names, fe_batch
     grads = torch.autograd.grad(val, [normed[k] for k in names] + [fe], allow_unused=True)
     out = {k: (g.numpy() if g is not None else np.zeros_like(normed_np[k])) for k, g in zip(names, grads[:-1])}
     return float(val.detach()), out, grads[-1].numpy(), E.detach().numpy(), I.detach().numpy()
+
+
+# ---------------------------------------------------------------------------------------------
+# 2-D distribution functions: the twin of tsadar_oracle's restatement of FormFactor.calc_in_2D.  Every function below
+# restates the NumPy oracle's function of the same name (tsadar_oracle.py), which cites the reference lines it follows.
+# Cell indices and branches are taken from detached values; the query positions themselves stay differentiable.
+# ---------------------------------------------------------------------------------------------
+def approx_df_axis(x, f, axis):
+    """tsadar_oracle.approx_df_axis: mean of the two adjacent secants, one-sided at the ends."""
+    f = torch.movedim(f, axis, 0)
+    d = (f[1:] - f[:-1]) / (x[1:] - x[:-1]).reshape((-1,) + (1,) * (f.ndim - 1))
+    out = torch.cat([d[:1], 0.5 * (d[:-1] + d[1:]), d[-1:]], dim=0)
+    return torch.movedim(out, 0, axis)
+
+
+def interp2d_cubic_extrap(xq, yq, x, y, f):
+    """tsadar_oracle.interp2d_cubic_extrap: bicubic Hermite patch, the boundary patch outside the grid."""
+    x, y = _t(x), _t(y)
+    fx = approx_df_axis(x, f, 0)
+    fy = approx_df_axis(y, f, 1)
+    fxy = approx_df_axis(y, fx, 1)
+    i = torch.clamp(torch.searchsorted(x, xq.detach().contiguous(), right=True), 1, x.numel() - 1)
+    j = torch.clamp(torch.searchsorted(y, yq.detach().contiguous(), right=True), 1, y.numel() - 1)
+    dx = x[i] - x[i - 1]
+    dy = y[j] - y[j - 1]
+    tx = (xq - x[i - 1]) / dx
+    ty = (yq - y[j - 1]) / dy
+
+    def basis(t):
+        t2, t3 = t * t, t * t * t
+        return (2 * t3 - 3 * t2 + 1, -2 * t3 + 3 * t2), (t3 - 2 * t2 + t, t3 - t2)
+
+    (hx0, hx1), (gx0, gx1) = basis(tx)
+    (hy0, hy1), (gy0, gy1) = basis(ty)
+    out = 0.0
+    for a, (hxa, gxa) in enumerate(((hx0, gx0), (hx1, gx1))):
+        for b, (hyb, gyb) in enumerate(((hy0, gy0), (hy1, gy1))):
+            ii, jj = i - 1 + a, j - 1 + b
+            out = out + f[ii, jj] * hxa * hyb + fx[ii, jj] * dx * gxa * hyb + fy[ii, jj] * dy * hxa * gyb \
+                + fxy[ii, jj] * dx * dy * gxa * gyb
+    return out
+
+
+def rotate_df(vx, df, angle_deg):
+    """tsadar_oracle.rotate_df; ``angle_deg`` may be a tensor (differentiable)."""
+    vx = _t(vx)
+    rad = -_t(angle_deg) * (np.pi / 180)
+    c, s = torch.cos(rad), torch.sin(rad)
+    X, Y = torch.meshgrid(vx, vx, indexing="ij")
+    xq = c * X + s * Y
+    yq = -s * X + c * Y
+    return interp2d_cubic_extrap(xq.reshape(-1), yq.reshape(-1), vx, vx, df).reshape(vx.numel(), vx.numel())
+
+
+def calc_chi_vals_2d(vx, DF, beta, xie_mag, klde_mag):
+    """tsadar_oracle.calc_chi_vals_2d for one (lambda, theta) point (0-dim tensors)."""
+    vx = _t(vx)
+    dvx = vx[1] - vx[0]
+    fe_2D_k = rotate_df(vx, DF, beta * (180 / np.pi))
+    fe_1D_k = torch.sum(fe_2D_k, dim=0) * dvx
+    df = gradient_uniform(fe_1D_k, dvx)
+    xq = xie_mag.reshape(1)
+    fe_vphi = interp_linear(xq, vx, fe_1D_k)[0]
+    dfe = interp_linear(xq, vx, df)[0]
+    chiEI = np.pi / klde_mag**2 * dfe
+    chiERrat = -1.0 / klde_mag**2 * ratintn(df, vx - xie_mag, vx)
+    return fe_vphi, chiEI, chiERrat
+
+
+def form_factor_2d(lam_range, npts, lam_shift, sa_deg, num_grad_points, p, vx, fe2d, ud_angle, va_angle, lam_index=None,
+                   grad_index=None, debug=None, beta_of=None):
+    """tsadar_oracle.form_factor_2d for one lineout: ``p`` holds tensors Te, ne, lam, Va, ud, ne_gradient, Te_gradient, lists
+    of tensors Ti, Z, fract and plain numbers A; ``fe2d`` a tensor [nv, nv].  Returns (P[G, npts, ntheta], lam_cm), differentiable
+    in all of them.  The points are walked one at a time, O(nv^2) each.  ``grad_index`` restricts the gradient points the
+    way ``lam_index`` restricts the wavelengths (no coupling along either).  ``beta_of``: a map applied to the rotation angle
+    before the table is rotated (only to restate the problem on a mirrored table, see ff2d_adjoint)."""
+    _, xi2 = orc.xi_grids()
+    zr_tab, zi_tab = orc.zprime_tables()
+    G = num_grad_points
+    lam_axis = np.linspace(lam_range[0], lam_range[1], npts)
+    if lam_index is not None:
+        lam_axis = lam_axis[np.asarray(lam_index)]
+    omgL_num = 2 * np.pi * 1e7 * orc.C
+    omgs = _t(2e7 * np.pi * orc.C / lam_axis)[None, :, None]
+    # linspace(1 - v/200, 1 + v/200, G) = 1 + v * cg
+    cg = _t(np.linspace(-1.0 / 200, 1.0 / 200, G))
+    if grad_index is not None:
+        cg = cg[np.asarray(grad_index)]
+    ne = 1.0e20 * p["ne"] * (1 + p["ne_gradient"] * cg)
+    Te = p["Te"] * (1 + p["Te_gradient"] * cg)
+    lam = p["lam"] + lam_shift
+    A = _t(np.asarray(p["A"], dtype=np.float64))
+    Z = torch.stack(list(p["Z"])).reshape(1, 1, 1, -1)
+    Ti = torch.stack(list(p["Ti"]))
+    fract = torch.stack(list(p["fract"])).reshape(1, 1, 1, -1)
+    Va0, ud0 = p["Va"] * 1e6, p["ud"] * 1e6
+    Mi = (A * orc.MP).reshape(1, 1, 1, -1)
+    sarad = _t(np.asarray(sa_deg, dtype=np.float64) * np.pi / 180).reshape(1, 1, -1)
+    Va = (Va0 * np.cos(va_angle * np.pi / 180), Va0 * np.sin(va_angle * np.pi / 180))
+    ud = (ud0 * np.cos(ud_angle * np.pi / 180), ud0 * np.sin(ud_angle * np.pi / 180))
+    omgL = omgL_num / lam
+    omgpe = orc.C0 * torch.sqrt(ne[:, None, None])
+    omg = omgs - omgL
+    kLx = torch.sqrt(omgL**2 - omgpe**2) / orc.C
+    ks_mag = torch.sqrt(omgs**2 - omgpe**2) / orc.C
+    kx, ky = torch.cos(sarad) * ks_mag - kLx, torch.sin(sarad) * ks_mag - 0.0
+    k_mag = torch.sqrt(kx * kx + ky * ky)
+    omgdop = omg - (kx * Va[0] + ky * Va[1])
+    vTe = torch.sqrt(Te[:, None, None] / orc.ME)
+    klde_mag = (vTe / omgpe) * k_mag
+    Zbar = torch.sum(Z * fract)
+    ni = fract * ne[:, None, None, None] / Zbar
+    omgpi = orc.C0 * Z * torch.sqrt(ni * orc.ME / Mi)
+    vTi = torch.sqrt(Ti.reshape(1, 1, 1, -1) / Mi)
+    kldi = (vTi / omgpi) * k_mag[..., None]
+    xii = (1.0 / (np.sqrt(2.0) * vTi)) * (omgdop / k_mag)[..., None]
+    ZpiR = interp_linear(xii, xi2, zr_tab, left=xii**-2, right=xii**-2)
+    ZpiI = interp_linear(xii, xi2, zi_tab, left=torch.zeros_like(xii), right=torch.zeros_like(xii))
+    chiIr = torch.sum(-0.5 / kldi**2 * ZpiR, dim=3)
+    chiIi = torch.sum(-0.5 / kldi**2 * ZpiI, dim=3)
+    a = omgdop / k_mag**2
+    xie = ((a * kx - ud[0]) / vTe, (a * ky - ud[1]) / vTe)
+    xie_mag = torch.sqrt(xie[0] ** 2 + xie[1] ** 2)
+    # np.heaviside(x, 1) = 1 for x >= 0: the half plane is chosen from the detached value
+    beta = torch.atan(xie[1] / xie[0]) + np.pi * (xie[0].detach() < 0).to(DT)
+    if debug is not None:
+        debug.update(beta=beta.detach().numpy(), xie_mag=xie_mag.detach().numpy(), xii=xii.detach().numpy())
+    if beta_of is not None:
+        beta = beta_of(beta)
+    shp = tuple(beta.shape)
+    vals = [calc_chi_vals_2d(vx, fe2d, beta[idx], xie_mag[idx], klde_mag[idx]) for idx in np.ndindex(*shp)]
+    fe_vphi, chiEi, chiEr = (torch.stack([v[c] for v in vals]).reshape(shp) for c in range(3))
+    epsr = 1.0 + chiEr + chiIr
+    epsi = chiEi + chiIi
+    eps2 = epsr**2 + epsi**2
+    ion_fact = fract * Z**2 / Zbar / vTi
+    ion_comp = ion_fact * ((chiEr**2 + chiEi**2)[..., None] * torch.exp(-(xii**2)) / np.sqrt(2 * np.pi))
+    ele_comp = ((1.0 + chiIr) ** 2 + chiIi**2) * fe_vphi / vTe
+    S_ion = torch.sum(1.0 / k_mag[..., None] * ion_comp / eps2[..., None], dim=3)
+    S_ele = 1.0 / k_mag * ele_comp / eps2
+    PsOmg = (S_ion + S_ele) * (1 + 2 * omgdop / omgL) * orc.RE**2 * ne[:, None, None]
+    lams = 2 * np.pi * orc.C / omgs
+    return PsOmg * 2 * np.pi * orc.C / lams**2, lams[0, :, 0]
+
+
+def phys_names_2d(n_ion):
+    """The physical parameters of one lineout that the 2-D form factor depends on (A is a constant)."""
+    return ["Te", "ne", "lam", "ud", "Va", "Te_gradient", "ne_gradient"] + [f"{k}_{s+1}" for s in range(n_ion) for k in ("Ti", "Z", "fract")]
+
+
+def _leaf_params(p_np, names):
+    """Oracle lineout dict (tsadar_oracle.lineout_params) -> the same dict of 0-dim tensors, and the leaves named ``names``."""
+    p = {k: _t(p_np[k]).clone() for k in ["Te", "ne", "lam", "ud", "Va", "Te_gradient", "ne_gradient"]}
+    for k in ["Ti", "Z", "fract"]:
+        p[k] = [_t(v).clone() for v in p_np[k]]
+    p["A"] = list(p_np["A"])
+    leaves = []
+    for nm in names:
+        if "_" in nm and nm.rsplit("_", 1)[1].isdigit():
+            k, s = nm.rsplit("_", 1)
+            leaves.append(p[k][int(s) - 1].requires_grad_(True))
+        else:
+            leaves.append(p[nm].requires_grad_(True))
+    return p, leaves
+
+
+def ff2d_adjoint(lam_range, npts, lam_shift, sa_deg, num_grad_points, lineouts, vx, fe2d, ud_angle, va_angle, lam_index, Pbar,
+                 names, points=None, mirrored=False):
+    """Reverse mode of J = sum Pbar * P over the seeded points of form_factor_2d, one backward per point.
+
+    ``lineouts``: one oracle parameter dict per lineout (tsadar_oracle.lineout_params); ``Pbar`` [B, G, len(lam_index), ntheta]
+    (a point whose seed is exactly zero is not visited); ``names``: the parameters to differentiate (phys_names_2d).
+    ``points``: optional list of (b, g, l, t) -- the contribution of those points only (l indexes ``lam_index``).
+    ``mirrored``: the same mathematics in another summation order -- the transposed table rotated by the reflected angle
+    -pi/2 - beta gives every projection with its summed axis reversed; the table gradient is transposed back.
+
+    Returns (g_phys [B, len(names)], g_table [nv, nv], A_phys, A_table): the per-point gradients summed, and their absolute
+    values summed.  ``A`` is the scale at which two float64 summations of the same terms may legitimately differ, entry by entry;
+    max |g| is not (a handful of rim entries of the table carry weights orders of magnitude above the rest)."""
+    Pbar = np.asarray(Pbar, dtype=np.float64)
+    sa_deg = np.asarray(sa_deg, dtype=np.float64)
+    lam_index = np.asarray(lam_index)
+    B, nv = len(lineouts), len(vx)
+    assert Pbar.shape == (B, num_grad_points, lam_index.size, sa_deg.size), Pbar.shape
+    fe = _t(fe2d).clone()
+    fe = (fe.T.contiguous() if mirrored else fe).requires_grad_(True)
+    beta_of = (lambda beta: -np.pi / 2 - beta) if mirrored else None
+    g_phys, A_phys = np.zeros((B, len(names))), np.zeros((B, len(names)))
+    g_tab, A_tab = torch.zeros((nv, nv), dtype=DT), torch.zeros((nv, nv), dtype=DT)
+    todo = points if points is not None else [idx for idx in np.ndindex(*Pbar.shape)]
+    per_b = {}
+    for (b, g, l, t) in todo:
+        if Pbar[b, g, l, t] == 0.0:
+            continue
+        if b not in per_b:
+            per_b[b] = _leaf_params(lineouts[b], names)
+        p, leaves = per_b[b]
+        P, _ = form_factor_2d(lam_range, npts, lam_shift, sa_deg[t : t + 1], num_grad_points, p, vx, fe, ud_angle, va_angle,
+                              lam_index=lam_index[l : l + 1], grad_index=[g], beta_of=beta_of)
+        grads = torch.autograd.grad(P.reshape(()), leaves + [fe], allow_unused=True)
+        w = float(Pbar[b, g, l, t])
+        for c, gr in enumerate(grads[:-1]):
+            if gr is not None:
+                g_phys[b, c] += w * float(gr)
+                A_phys[b, c] += abs(w * float(gr))
+        g_tab += w * grads[-1]
+        A_tab += (w * grads[-1]).abs()
+    if mirrored:
+        g_tab, A_tab = g_tab.T.contiguous(), A_tab.T.contiguous()
+    return g_phys, g_tab.numpy(), A_phys, A_tab.numpy()
+
+
+# ---------------------------------------------------------------------------------------------
+# Angular (ARTS) instrument chain: the twin of tsadar_oracle.ats_model / add_ats_irf / reduce_ats_to_resunit / ats_spectrum,
+# differentiable in P, amp1 and amp2.  ``lam`` only selects between the two amplitudes (detached).
+# ---------------------------------------------------------------------------------------------
+def ats_model(cfg, weights, P, lam_nm):
+    """tsadar_oracle.ats_model: P [G, npts, n_angles] -> modlE [n_px, npts]."""
+    lam_nm = _t(lam_nm)
+    modl = _t(weights) @ torch.mean(P, dim=0).T
+    filt = cfg["other"]["iawfilter"]
+    if filt[0]:
+        fb, fr = filt[3] - filt[2] / 2, filt[3] + filt[2] / 2
+        if cfg["other"]["lamrangE"][0] < fr and cfg["other"]["lamrangE"][1] > fb:
+            modl = torch.where((fb < lam_nm) & (fr > lam_nm), modl * 10.0 ** (-filt[1]), modl)
+    return modl
+
+
+def add_ats_irf(cfg, ang_axis, lam_nm, modl):
+    """tsadar_oracle.add_ats_irf: "same" convolutions along the angular-pixel axis, then the wavelength axis."""
+    ang_axis, lam_nm = _t(ang_axis), _t(lam_nm)
+    wid = cfg["other"]["PhysParams"]["widIRF"]
+    s_lam, s_ang = wid["spect_FWHM_ele"] / 2.3548, wid["ang_FWHM_ele"] / 2.3548
+    o_lam = (lam_nm.max() + lam_nm.min()) / 2.0
+    o_ang = (ang_axis.max() + ang_axis.min()) / 2.0
+    g_lam = (1.0 / (s_lam * np.sqrt(2.0 * np.pi))) * torch.exp(-((lam_nm - o_lam) ** 2.0) / (2.0 * s_lam**2.0))
+    g_ang = (1.0 / (s_ang * np.sqrt(2.0 * np.pi))) * torch.exp(-((ang_axis - o_ang) ** 2.0) / (2.0 * s_ang**2.0))
+    y = (_conv_same_matrix(g_ang) @ modl).T      # [npts, n_px]: every wavelength column along the pixel axis
+    y = (_conv_same_matrix(g_lam) @ y).T        # [n_px, npts]: every pixel row along the wavelength axis
+    return torch.amax(modl, dim=1, keepdim=True) / torch.amax(y, dim=1, keepdim=True) * y
+
+
+def _block_means(y, step):
+    """[average(y[:, i : i + step], axis=1) for i in range(0, y.shape[1], step)] as one array [blocks, rows]."""
+    n = y.shape[1]
+    if n % step == 0:
+        return y.reshape(y.shape[0], n // step, step).mean(dim=2).T
+    return torch.stack([torch.mean(y[:, i : i + step], dim=1) for i in range(0, n, step)])
+
+
+def reduce_ats_to_resunit(cfg, y, lam_nm, n_lam_out, e_amps, p):
+    """tsadar_oracle.reduce_ats_to_resunit; ``p``: lam (number), amp1, amp2 (tensors)."""
+    lam_nm = _t(lam_nm)
+    lam_step = round(y.shape[1] / n_lam_out)
+    ang_step = round(y.shape[0] / cfg["other"]["CCDsize"][0])
+    y = _block_means(y, lam_step)
+    y = _block_means(y, ang_step)
+    lam = _block_means(lam_nm[None, :], lam_step)[:, 0]
+    y = y[cfg["data"]["lineouts"]["start"] : cfg["data"]["lineouts"]["end"], :]
+    y = _t(e_amps) * y / torch.amax(y, dim=1, keepdim=True)
+    y = torch.where(lam < float(p["lam"]), p["amp1"] * y, p["amp2"] * y)
+    return y, lam
+
+
+def ats_spectrum(cfg, weights, ang_axis, P, lam_nm, n_lam_out, e_amps, p):
+    """tsadar_oracle.ats_spectrum."""
+    modl = ats_model(cfg, weights, P, lam_nm)
+    y = add_ats_irf(cfg, ang_axis, lam_nm, modl)
+    return reduce_ats_to_resunit(cfg, y, lam_nm, n_lam_out, e_amps, p)
+
+
+def ats_adjoint(cfg, weights, ang_axis, P, lam_nm, n_lam_out, e_amps, p, Ebar):
+    """One backward of <Ebar, ats_spectrum(P, amp1, amp2)>: (Pbar [G, npts, n_angles], amp1_bar, amp2_bar)."""
+    Pt = _t(np.asarray(P, dtype=np.float64)).clone().requires_grad_(True)
+    a1 = _t(p["amp1"]).clone().requires_grad_(True)
+    a2 = _t(p["amp2"]).clone().requires_grad_(True)
+    y, _ = ats_spectrum(cfg, weights, ang_axis, Pt, lam_nm, n_lam_out, e_amps, dict(lam=p["lam"], amp1=a1, amp2=a2))
+    gP, g1, g2 = torch.autograd.grad(torch.sum(_t(Ebar) * y), [Pt, a1, a2])
+    return gP.numpy(), float(g1), float(g2)

@@ -726,13 +726,7 @@ def test_hessian_for_sigmas(torch_mod):
 
 
 def _fe2d(nv, kind):
-    vx = orc.velocity_grid(nv)
-    X, Y = np.meshgrid(vx, vx, indexing="ij")
-    if kind == "maxwellian":
-        f = np.exp(-(X**2 + Y**2) / 2)
-    else:  # anisotropic super-Gaussian with a drifting bump: no symmetry left for a transposed index to hide behind
-        f = np.exp(-((X / 1.3) ** 2 + (Y / 0.8) ** 2) ** 1.4 / 2) + 0.05 * np.exp(-((X - 2.0) ** 2 + (Y + 1.0) ** 2))
-    return vx, f / (f.sum() * (vx[1] - vx[0]) ** 2)
+    return util.fe2d(nv, kind)
 
 
 @pytest.mark.parametrize("kind,nv", [("maxwellian", 48), ("anisotropic", 48), ("anisotropic", 132), ("anisotropic", 133), ("anisotropic", 257)])

@@ -206,3 +206,100 @@ def _stage_records(eng, cfg, two_d, want_gfe=True):
     rec.append(eng.last_launch())
     torch.cuda.synchronize()
     return rec
+
+
+# ---- the 2-D form factor's adjoint against the oracle's autodiff twin: tests/test_ff2d_adjoint_twin.py, test_oracle_torch.py
+def fe2d(nv, kind="anisotropic"):
+    """A normalised 2-D f_e on the velocity grid.  "anisotropic": super-Gaussian with a drifting bump, no symmetry left for a
+    transposed or mirrored index to hide behind."""
+    vx = orc.velocity_grid(nv)
+    X, Y = np.meshgrid(vx, vx, indexing="ij")
+    if kind == "maxwellian":
+        f = np.exp(-(X**2 + Y**2) / 2)
+    else:
+        f = np.exp(-((X / 1.3) ** 2 + (Y / 0.8) ** 2) ** 1.4 / 2) + 0.05 * np.exp(-((X - 2.0) ** 2 + (Y + 1.0) ** 2))
+    return vx, f / (f.sum() * (vx[1] - vx[0]) ** 2)
+
+
+# Cases by table size.  lam: the seeded wavelength samples per feature (0: electron window, 1: ion window); drifts: (ud or None = the
+# lineouts' own, ud_angle, va_angle).  In the electron window |xi_e| stays on the velocity grid for samples ~260 .. 620 only, and one
+# sample of every list lies beside the laser line (sample 431 there): away from it every xi_i is beyond the Z' table, chi_i no longer
+# depends on T_i, and d P / d T_i would be a rounding residue with no scale of its own.
+_SA3 = [35.0, 60.0, 110.0]
+_DRIFT1 = [(None, 25.0, -40.0)]
+FF2D_TWIN_CASES = {
+    48: dict(n_ion=2, G=3, sa=_SA3, lam={0: [262, 333, 431, 610], 1: [0, 100, 511, 700]}, drifts=_DRIFT1),
+    129: dict(n_ion=1, G=1, sa=_SA3, lam={0: [300, 432], 1: [511]}, drifts=_DRIFT1),
+    # the angles and drift settings of test_rolling_sampler_every_walk_direction; the laser line lies at sample 234.7 of the ion window
+    132: dict(n_ion=1, G=1, sa=[25.0, 40.0, 62.0, 88.0, 115.0, 150.0], lam={1: [3, 231, 234, 235, 236, 239]},
+              drifts=[(1.4, 25.0, -40.0), (1.4, 115.0, 200.0), (-1.2, 60.0, 10.0), (0.9, 290.0, 135.0)]),
+    133: dict(n_ion=1, G=1, sa=_SA3, lam={0: [280, 430], 1: [236]}, drifts=_DRIFT1),
+    257: dict(n_ion=1, G=1, sa=_SA3, lam={0: [300, 431], 1: [511, 1023]}, drifts=_DRIFT1),
+    258: dict(n_ion=1, G=1, sa=_SA3, lam={0: [432, 600], 1: [100]}, drifts=_DRIFT1),
+}
+
+
+def ff2d_twin_case(nv):
+    """CPU-side set-up of one case of FF2D_TWIN_CASES: deck, angles, two lineouts, table."""
+    import decks
+
+    c = FF2D_TWIN_CASES[nv]
+    cfg = decks.deck_fit(n_ion=c["n_ion"])
+    if c["G"] > 1:
+        g = cfg["parameters"]["general"]
+        g["Te_gradient"].update(val=6.0, num_grad_points=c["G"])
+        g["ne_gradient"].update(val=9.0, num_grad_points=c["G"])
+    B = 2
+    sa = dict(sa=np.array(c["sa"]), weights=np.ones((B, len(c["sa"]))) / len(c["sa"]))
+    normed = random_lineouts(cfg, B, seed=67, ranges=dict(ud=(-1.5, 1.5)))
+    phys = orc.physical_params(cfg["parameters"], normed, True)
+    phys["ud"] = np.array([0.8, -1.1])
+    vx, fe2 = fe2d(nv)
+    return dict(cfg=cfg, sa=sa, B=B, G=c["G"], n_ion=c["n_ion"], phys=phys, vx=vx, fe2=fe2, lam=c["lam"], drifts=c["drifts"], nv=nv)
+
+
+def ff2d_with_drift(case, ud):
+    """The physical parameters of a case at one drift setting: (dict, matrix [B, NP], one oracle dict per lineout)."""
+    phys = dict(case["phys"])
+    if ud is not None:
+        phys["ud"] = np.array([ud, -0.7 * ud])
+    X = normed_to_matrix(phys, case["n_ion"])
+    return phys, X, [orc.lineout_params(phys, b, case["n_ion"]) for b in range(case["B"])]
+
+
+def ff2d_lam_range(case, feature):
+    return case["cfg"]["other"]["lamrangE" if feature == 0 else "lamrangI"]
+
+
+def ff2d_kink_distances(case, feature, lineouts, ud_angle, va_angle):
+    """How far the seeded points of one feature lie from the kinks of the forward, from the NumPy oracle's own intermediates:
+    (beta [B, G, nl, ntheta], distance of |xi_e| to the nearest vx node in cells -- negative outside the grid --, distance of
+    every xi_i inside the Z' table to its nearest node in cells).  Runs no rotation: the table is 4 x 4."""
+    vx = case["vx"]
+    dv = vx[1] - vx[0]
+    _, xi2 = orc.xi_grids()
+    beta, de, di = [], [], []
+    vx4, f4 = fe2d(4, "maxwellian")
+    for p in lineouts:
+        dbg = {}
+        orc.form_factor_2d(ff2d_lam_range(case, feature), 1024, 0.0, case["sa"]["sa"], case["G"], p, vx4, f4, ud_angle, va_angle,
+                           lam_index=np.array(case["lam"][feature]), debug=dbg)
+        beta.append(dbg["beta"])
+        t = (dbg["xie_mag"] - vx[0]) / dv
+        de.append(np.where((t < 0) | (t > len(vx) - 1), -1.0, np.abs(t - np.round(t))))
+        u = (dbg["xii"] - xi2[0]) / (xi2[1] - xi2[0])
+        di.append(np.where((u < 0) | (u > len(xi2) - 1), np.inf, np.abs(u - np.round(u))))
+    return np.array(beta), np.array(de), np.array(di)
+
+
+def smooth_positive_image(shape, seed):
+    """A random, positive, smooth image P [G, npts, n_angles] for the ARTS chain: a few low-frequency waves on a constant
+    (generic: no ties among the row maxima the chain normalises by)."""
+    rng = np.random.default_rng(seed)
+    G, n, m = shape
+    x, y = np.linspace(0, 1, n)[None, :, None], np.linspace(0, 1, m)[None, None, :]
+    P = np.full(shape, 1.5)
+    for _ in range(6):
+        fx, fy = rng.uniform(0.3, 3.0, 2)
+        P = P + rng.uniform(0.05, 0.2) * np.cos(2 * np.pi * (fx * x + fy * y) + rng.uniform(0, 2 * np.pi, (G, 1, 1)))
+    return P

@@ -1332,6 +1332,9 @@ __global__ void k_ff2d_lines_adj(KStatic S, const double* __restrict__ phys, int
     lines_adj_load<NI>(LBacc + ((size_t)b * S.G + g) * NLB, with_m, LB);
     make_lines_adjoint<NI>(p, S.lam_shift[f], g, S.G, L, LB, pb);
   }
+  // One species: fr cancels out of fr / Zbar, the only way it enters, so the derivative is identically zero; frb and Zbarb * Z
+  // are the same number with opposite signs and what their sum leaves behind (1e-16 of either) is rounding, not a gradient.
+  if (NI == 1) pb[TSFF_P_ION0 + TSFF_ION_FRACT] = 0.0;
 #pragma unroll
   for (int s = 0; s < NPk; ++s) gphys[(size_t)b * NPk + s] = pb[s];
 }
