@@ -21,6 +21,8 @@ __global__ __launch_bounds__(512) void k(double* out, int iters, double seed) {
         if (OP == 2) asm volatile("v_add_f64 %0, %0, %0" : "+v"(a[i]));
         if (OP == 3) asm volatile("v_rcp_f64 %0, %0" : "+v"(a[i]));
         if (OP == 4) asm volatile("v_fma_f32 %0, %0, %0, %0" : "+v"(*(float*)&a[i]));
+        if (OP == 5) asm volatile("v_floor_f64 %0, %0" : "+v"(a[i]));
+        if (OP == 6) asm volatile("v_fract_f64 %0, %0" : "+v"(a[i]));
       }
   }
   long long t1 = clock64();
@@ -34,11 +36,11 @@ int main() {
   double* d;
   CHECK(hipMalloc(&d, 2048 * sizeof(double)));
   double h[2048];
-  const char* ops[] = {"v_fma_f64", "v_mul_f64", "v_add_f64", "v_rcp_f64", "v_fma_f32"};
+  const char* ops[] = {"v_fma_f64", "v_mul_f64", "v_add_f64", "v_rcp_f64", "v_fma_f32", "v_floor_f64", "v_fract_f64"};
 #define RUN(NCH, OP, THREADS) hipLaunchKernelGGL((k<NCH, OP>), dim3(1), dim3(THREADS), 0, 0, d, 2000, 1.37); CHECK(hipDeviceSynchronize()); \
   CHECK(hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost)); \
   printf("%-10s chains %2d, %d wavefront(s) per SIMD: %.2f cycles per instruction of one wavefront -> SIMD issues one every %.2f cycles\n", ops[OP], NCH, THREADS / 256, h[1024], h[1024] / (THREADS / 256));
 #define ALL(OP) RUN(1, OP, 256) RUN(2, OP, 256) RUN(4, OP, 256) RUN(8, OP, 256) RUN(1, OP, 512) RUN(2, OP, 512) RUN(4, OP, 512) RUN(8, OP, 512)
-  ALL(0) ALL(1) ALL(2) ALL(3) ALL(4)
+  ALL(0) ALL(1) ALL(2) ALL(3) ALL(4) ALL(5) ALL(6)
   return 0;
 }

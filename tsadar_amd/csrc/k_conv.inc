@@ -43,16 +43,24 @@ __device__ __forceinline__ void conv_taps4(double g0, double g1, double g2, doub
 //     X3[na + 1] <= 3 Ls + Ls - 1: inside the four phase arrays (4 Ls + 2 doubles) for every na >= 1.
 // What is read beyond group na - 1 is never used.
 typedef const double __attribute__((address_space(4))) cdouble_t;
+typedef const double __attribute__((address_space(3))) ldouble_t;
 struct ConvSet { double w[11], g[8]; };
 // groups a, a + 1: the window values V0 .. V6 of the first, V3 .. V6 of the second and their taps.  (V0 .. V2 are the V4 .. V6 of
 // the group before and could be inherited from the previous set -- but then three registers of a set are still read when the set
 // is requested again, the allocator loads into temporaries and copies them behind a wait of its own in the middle of the FMAs.)
-template <int DIR>
-__device__ __forceinline__ void conv_request(const double* __restrict__ X0, const double* __restrict__ X1, const double* __restrict__ X2,
-                                             const double* __restrict__ X3, cdouble_t* pt, int a, int at, ConvSet& s) {
-  s.w[0] = X0[a]; s.w[1] = X1[a]; s.w[2] = X2[a];
-  s.w[3] = X3[a]; s.w[4] = X0[a + 1]; s.w[5] = X1[a + 1]; s.w[6] = X2[a + 1];
-  s.w[7] = X3[a + 1]; s.w[8] = X0[a + 2]; s.w[9] = X1[a + 2]; s.w[10] = X2[a + 2];
+// r12_loops: the window through four RUNNING LDS addresses p0 .. p3 (one per phase array, at group a of the loop body) and the
+// set's offset O = 0, 2, 4 from them as an immediate -- one address step per phase array and body, where the index form cost two.
+// And the compiler did inherit after all: it found w[8 .. 10] of one request in w[0 .. 2] of the next (the same LDS words), kept
+// those three and their ds_read2 partners -- six doubles -- across the request that reuses their registers and paid six v_mov_b64 per
+// body for it.  The empty asm makes the four addresses opaque in front of every request, so that each request reads its own
+// eleven values (three LDS reads more per body, no VALU instruction); the taps keep their running scalar pointer.
+template <int DIR, int O>
+__device__ __forceinline__ void conv_request(ldouble_t*& p0, ldouble_t*& p1, ldouble_t*& p2, ldouble_t*& p3, cdouble_t* pt, int at,
+                                             ConvSet& s) {
+  asm volatile("" : "+v"(p0), "+v"(p1), "+v"(p2), "+v"(p3));
+  s.w[0] = p0[O]; s.w[1] = p1[O]; s.w[2] = p2[O];
+  s.w[3] = p3[O]; s.w[4] = p0[O + 1]; s.w[5] = p1[O + 1]; s.w[6] = p2[O + 1];
+  s.w[7] = p3[O + 1]; s.w[8] = p0[O + 2]; s.w[9] = p1[O + 2]; s.w[10] = p2[O + 2];
 #pragma unroll
   for (int k = 0; k < 8; ++k) s.g[k] = pt[DIR * (4 * at + k)];
   __builtin_amdgcn_sched_barrier(0);
@@ -70,23 +78,24 @@ __device__ __forceinline__ void conv_group(const ConvSet& s, double (&acc)[4]) {
 }
 template <int DIR>
 __device__ __forceinline__ void conv4_phase(const double* __restrict__ xs, int Ls, int sl, cdouble_t* pt, int na, double (&acc)[4]) {
-  const double* __restrict__ X0 = xs + sl, * __restrict__ X1 = X0 + Ls, * __restrict__ X2 = X1 + Ls, * __restrict__ X3 = X2 + Ls;
+  ldouble_t* p0 = (ldouble_t*)xs + sl, * p1 = p0 + Ls, * p2 = p1 + Ls, * p3 = p2 + Ls;   // X0 .. X3 at group a
   ConvSet A, B;
-  conv_request<DIR>(X0, X1, X2, X3, pt, 0, 0, A);
+  conv_request<DIR, 0>(p0, p1, p2, p3, pt, 0, A);
   int a = 0;
   for (; a + 4 <= na; a += 4) {   // two sets per body: A holds groups a, a + 1 on entry
     conv_wait();
-    conv_request<DIR>(X0, X1, X2, X3, pt, a + 2, 2, B);
+    conv_request<DIR, 2>(p0, p1, p2, p3, pt, 2, B);
     conv_group<0>(A, acc); conv_group<1>(A, acc);
     conv_wait();
-    conv_request<DIR>(X0, X1, X2, X3, pt, a + 4, 4, A);
+    conv_request<DIR, 4>(p0, p1, p2, p3, pt, 4, A);
     conv_group<0>(B, acc); conv_group<1>(B, acc);
-    pt += 16 * DIR;   // (the taps through a running scalar pointer, the window through the index: the fewest address instructions)
+    pt += 16 * DIR;   // (the taps through a running scalar pointer, the window through four running addresses)
+    p0 += 4; p1 += 4; p2 += 4; p3 += 4;
   }
   // the last na - a = 0 .. 3 groups: A holds the first two of them (requested, not yet waited for)
   conv_wait();
   if (na - a >= 2) {
-    conv_request<DIR>(X0, X1, X2, X3, pt, a + 2, 2, B);
+    conv_request<DIR, 2>(p0, p1, p2, p3, pt, 2, B);
     conv_group<0>(A, acc); conv_group<1>(A, acc);
     conv_wait();
     if (na - a == 3) conv_group<0>(B, acc);

@@ -56,7 +56,8 @@ constexpr int kRedSums = 32;   // offset (doubles) of the five partial block sum
 template <int NI, int GM, bool ZH, bool EX = false>
 __global__ __launch_bounds__(kHalf, 2) void k_spectrum_fused(KStatic S, KCall K, int f0, int flags,
                                                              const double* __restrict__ lrec) {
-  // lrec: [items][kLineRec] the lineout scalars of every (lineout, feature) item, written by k_fused_prep just before this launch
+  // lrec: [items][kLineRec] the lineout scalars of every (lineout, feature) item, written by k_fused_prep just before this launch,
+  // and behind them, in the same buffer, [items][n_angles][2] the angle records (cos theta_a, w_a pref) of the items
   // flags as in k_spectrum: bit 1 k_s cache in LDS, bit 2 interleaved plan (grid 2B: workgroup f B + b evaluates feature f
   // of lineout b and leaves its part of the gradient in K.gpart[f][b][:]); otherwise grid B, feature f0, grad written
   const bool use_ks = flags & 2, interleaved = flags & 4;
@@ -146,18 +147,24 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_fused(KStatic S, KCall K,
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   // (the sweep reads other lanes' boundary points)
   }
+  // (the item's angle record, behind the line records of ALL items of the batch; wavefront-uniform address, constant address space: scalar loads)
+  cdouble_t* arp = (cdouble_t*)(lrec + (size_t)K.Btot * (interleaved ? 2 : 1) * kLineRec + gitem * 2 * (size_t)NA);
   auto sweep = [&](auto pair_tag, auto far_tag) {
     constexpr int P = decltype(pair_tag)::value;
     constexpr bool FAR = decltype(far_tag)::value;
     const int jb = jp[P];
     const int j2 = min(jb + kPair, npts - 1);
     const double ks2 = EX ? (use_ks ? ksc[j2] : ks_eval(ws[P][kPair], L.wpe2)) : 0.0;
-    double ct_n = m.cosa[0], wa_n = m.wsa[0];   // (the angle's constants are read from LDS one iteration ahead of their use)
+    // The angle's constants (cos theta_a, w_a pref) come from the item's record of k_fused_prep by ONE scalar load, straight into
+    // SGPRs, one iteration ahead of their use: wavefront-uniform and independent of the sample, they were two LDS reads, a
+    // multiplication and four v_readfirstlane_b32 per iteration.  The product is k_fused_prep's: the same factors, the same bits.
+    cdouble_t* pn = arp;
+    double ct_n = pn[0], wa_n = pn[1];
     // (EX) the unit's boundary point, which lane 63 takes for its missing neighbour
     const double* exu = EX ? exb + 16 * (2 * hw + P) : nullptr;
     for (int a = 0; a < NA; ++a) {
-      const double ct = uni(ct_n), wa = uni(wa_n * L.pref);
-      { const int an = min(a + 1, NA - 1); ct_n = m.cosa[an]; wa_n = m.wsa[an]; }
+      const double ct = ct_n, wa = wa_n;
+      { pn += a + 1 < NA ? 2 : 0; ct_n = pn[0]; wa_n = pn[1]; }   // (entry min(a + 1, NA - 1))
       Base b0;
       base_eval<NI, PAD>(ws[P][0], use_ks ? ksc[jb] : ks_eval(ws[P][0], L.wpe2), ct, L, T, b0);
       // (EX) the lane's FIRST base point of this angle is what its left neighbour asks for: b0 itself is the second one by then
@@ -171,7 +178,7 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_fused(KStatic S, KCall K,
         if (EX && i == kPair - 1) {   // the neighbour lane's first base point (the unit's boundary point for the last lane)
           // (The boundary point is read HERE.  Read an iteration ahead, as ct_n / wa_n are, or at the top of the iteration, its five
           //  doubles live across the pair's first point and the allocator spills 26 / 10 registers outside the loops where this form
-          //  spills none; measured, DESIGN.md section 4.1b.)
+          //  spills none; measured, DESIGN.md section 4.1b.  Tried again with the angle constants in SGPRs: still six.)
           neighbour_take<NI>(b0f, exu + a, ks2, ct, L, b1);
         } else {
           base_eval<NI, PAD>(ws[P][i + 1], use_ks ? ksc[min(j + 1, npts - 1)] : ks_eval(ws[P][i + 1], L.wpe2), ct, L, T, b1);
@@ -344,12 +351,14 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_fused(KStatic S, KCall K,
 
 // k_fused_prep: the lineout scalars of every (lineout, feature) item of a k_spectrum_fused launch -- one thread per item, the
 // very code of the spectrum kernels (load_phys, make_lines: the same bits), plus the four physical parameters the instrument chain
-// reads.  lrec[item][kLineRec]: the line record (lines_store) | lam, amp1, amp2, amp3.
+// reads.  lrec[item][kLineRec]: the line record (lines_store) | lam, amp1, amp2, amp3.  arec: see below.
 // finrec[k][item] (component-major, read by k_fused_finish with one item per lane): the physical parameters and the sum of the
 // un-normalised fractions (NP + 1), sigmoid(x) of the slots that have one (NP), and the lineout scalars once more (9 + 4 n_ion).
+// arec[item][n_angles][2] (or nullptr: the forward-only pair sweep reads none): the angle constants (cos theta_a, w_a pref) of the
+// one-sweep kernel's angle loops -- the product its threads formed in every iteration, once per item.
 template <int NI>
 __global__ __launch_bounds__(64) void k_fused_prep(KStatic S, const double* __restrict__ params, int B, int f0, int nload,
-                                                   double* __restrict__ lrec, double* __restrict__ finrec) {
+                                                   double* __restrict__ lrec, double* __restrict__ finrec, double* __restrict__ arec) {
   constexpr int NPk = TSFF_NP(NI);
   const int item = blockIdx.x * 64 + threadIdx.x;
   if (item >= B * nload) return;
@@ -376,6 +385,10 @@ __global__ __launch_bounds__(64) void k_fused_prep(KStatic S, const double* __re
   double* __restrict__ r = lrec + (size_t)item * kLineRec;
   lines_store<NI>(L, r, 1);
   r[9 + 4 * NI] = p.lam; r[10 + 4 * NI] = p.amp1; r[11 + 4 * NI] = p.amp2; r[12 + 4 * NI] = p.amp3;
+  if (arec) {
+    double2* __restrict__ ar = reinterpret_cast<double2*>(arec) + (size_t)item * S.n_angles;
+    for (int a = 0; a < S.n_angles; ++a) ar[a] = make_double2(S.cos_sa[a], S.w_sa[a] * L.pref);
+  }
 }
 
 // k_fused_finish: what remains of a fit step after k_spectrum_fused -- one thread per (lineout, feature) item, 256-thread

@@ -83,7 +83,8 @@ struct tsff_handle {
   tsff::DevBuf Wb, Hys, Yt;  // table adjoints of the f_e gradient
   tsff::DevBuf gpart;        // per-feature gradient parts of the interleaved launch plan
   tsff::DevBuf lbrec;        // per (item, wavefront) lineout-scalar adjoints of k_spectrum_fused (k_fused_finish)
-  tsff::DevBuf lrec, finrec; // per item lineout scalars of k_fused_prep (for the one-sweep kernel / for k_fused_finish)
+  tsff::DevBuf lrec, finrec; // per item lineout scalars of k_fused_prep (for the one-sweep kernel / for k_fused_finish); lrec holds, behind
+                             // the kLineRec doubles of every item, the angle records of the one-sweep kernel (2 n_angles doubles per item)
   tsff::DevBuf fpad;         // padded copies of 2-D tables that do not fit LDS
   tsff::DevBuf rows;         // Jacobian rows of k_spectrum_rows (points_per_pixel > 1)
   tsff::DevBuf tickets;      // per (lineout, feature) arrival counters of its split form (small batches)
@@ -382,7 +383,7 @@ static int ensure_workspace(tsff_handle* h, int B, bool with_rows = false) {
   // reserved handle allocates nothing (graph capture)
   const size_t nitems = (size_t)B * ((h->S.load[0] ? 1 : 0) + (h->S.load[1] ? 1 : 0));
   TSFF_ENSURE(h, h->lbrec, nitems * (kHalf / 64) * kLBRec * sizeof(double));
-  TSFF_ENSURE(h, h->lrec, nitems * kLineRec * sizeof(double));
+  TSFF_ENSURE(h, h->lrec, nitems * (kLineRec + 2 * (size_t)h->S.n_angles) * sizeof(double));
   TSFF_ENSURE(h, h->finrec, nitems * (2 * (size_t)h->S.NP + 1 + 9 + 4 * (size_t)h->n_ion) * sizeof(double));
   TSFF_ENSURE(h, h->gpart, (size_t)2 * B * h->S.NP * sizeof(double));
   TSFF_ENSURE(h, h->gradws, (size_t)B * h->S.NP * sizeof(double));
@@ -633,7 +634,7 @@ static SpectrumPlan plan_spectrum(const tsff_handle& h, int B, int nload) {
   if (fused_ok && small_wg && nlaunch == 1) {   // it leaves per-wavefront records; k_fused_finish turns them into the gradient
     p.form = SpectrumForm::one_sweep;
     p.lbrec = nitems * (kHalf / 64) * kLBRec * sizeof(double);
-    p.lrec = nitems * kLineRec * sizeof(double);
+    p.lrec = nitems * (kLineRec + 2 * (size_t)S.n_angles) * sizeof(double);   // (line records | angle records)
     p.finrec = finrec;
   } else if (p.interleaved && MODE == 1) {
     p.gpart = (size_t)2 * B * S.NP * sizeof(double);
@@ -651,7 +652,7 @@ static void launch_fused(tsff_handle* h, const KCall& K, const SpectrumPlan& p, 
   with_ion<kFusedMaxIon>(h->n_ion, [&](auto N) {
     const double* lrec = h->lrec.as<double>();
     TSFF_LAUNCH(h, k_fused_prep, (N.value), dim3((p.grid.x + 63) / 64), dim3(64), 0, h->stream, h->S, K.params, K.B, f0, nload,
-                h->lrec.as<double>(), h->finrec.as<double>());
+                h->lrec.as<double>(), h->finrec.as<double>(), h->lrec.as<double>() + (size_t)K.B * nload * kLineRec);   // (the angle records: behind the line records of all K.B * nload items)
     const int nblk = h->pipe_nblk > 1 ? h->pipe_nblk : 1;
     for (int i = 0; i < nblk; ++i) {
       KCall Kb = K;
@@ -732,7 +733,7 @@ static int launch_spectrum(tsff_handle* h, KCall& K, const SpectrumPlan& p, cons
               with_bool(p.zh, [&](auto ZH) { p.ex ? pairs(ZH, IntC<2>(), IntC<1>()) : pairs(ZH, IntC<0>(), IntC<1>()); });
             } else {
               TSFF_LAUNCH(h, k_fused_prep, (N.value), dim3((p.grid.x + 63) / 64), dim3(64), 0, h->stream, h->S, K.params, K.B, f0, nload,
-                          lrec, h->finrec.as<double>());
+                          lrec, h->finrec.as<double>(), (double*)nullptr);
               if (p.three && p.ex) pairs(std::true_type(), IntC<2>(), IntC<2>());
               else with_bool(p.zh, [&](auto ZH) { p.ex ? pairs(ZH, IntC<1>(), IntC<2>()) : pairs(ZH, IntC<0>(), IntC<2>()); });
             }
