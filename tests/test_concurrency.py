@@ -20,6 +20,7 @@ import util
 from oracle import tsadar_oracle as orc
 from test_kernel_matrix import (_cheap_batch, _deck, _fe2d, _ff2d_check_adjoint, _ff2d_check_forward, _free_form_fe, _phys,
                                 _spectrum_check, _spectrum_inputs)
+from util import _twin_weighted_grad
 
 pytestmark = pytest.mark.gpu
 
@@ -51,24 +52,6 @@ def _same(name, got, ref, what):
             assert err <= 1e-13 * np.max(np.abs(ref[k])), (name, what, k, err)
         else:
             assert np.array_equal(got[k], ref[k]), (name, what, k, np.max(np.abs(got[k] - ref[k])))
-
-
-def _twin_weighted_grad(cfg, sa, normed, batch, w, names, fe_batch=None):
-    """d (sum_k w[k] S_k) / d leaves of the given lineouts by reverse-mode autodiff of the torch twin: the per-lineout gradient
-    of the library's loss (weights fixed by the whole batch), whatever subset of lineouts is evaluated."""
-    import torch
-    from oracle import tsadar_oracle_torch as ot
-
-    nt = {k: ot._t(v).clone() for k, v in normed.items()}
-    for k in names:
-        nt[k].requires_grad_(True)
-    fb = None if fe_batch is None else torch.tensor(fe_batch, dtype=torch.float64, requires_grad=True)
-    S, _, E, I = ot.masked_sums(cfg, sa, nt, batch, True, fb)
-    val = (torch.as_tensor(np.asarray(w, dtype=np.float64)) * S).sum()
-    leaves = [nt[k] for k in names] + ([fb] if fb is not None else [])
-    grads = torch.autograd.grad(val, leaves, allow_unused=True)
-    out = {k: g.numpy() for k, g in zip(names, grads)}
-    return S.detach().numpy(), out, (grads[-1].numpy() if fb is not None else None), E.detach().numpy(), I.detach().numpy()
 
 
 # ---------------------------------------------------------------------------------------------------------------------

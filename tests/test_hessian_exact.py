@@ -421,11 +421,12 @@ def test_refusals():
         assert f"error {code}:" in str(e.value), (slots, str(e.value))   # (-2: this deck's f_e is not a DLM)
 
 
-def _case_vs_twin(cfg, B, seed, rows, engine_kw=None, activate=True, fe=None, tol=HESS_TOL):
-    """Engine.loss_hess on B lineouts, the twin on the lineouts ``rows``."""
+def _case_vs_twin(cfg, B, seed, rows, engine_kw=None, activate=True, fe=None, tol=HESS_TOL, ranges=None):
+    """Engine.loss_hess on B lineouts, the twin on the lineouts ``rows``.  ``ranges``: further leaves to draw per lineout
+    (util.random_lineouts)."""
     sa = util.sa_fit(B)
     batch = util.synthetic_batch(cfg, sa, B, seed=seed, activate=activate)
-    normed = util.random_lineouts(cfg, B, seed=seed + 50, activate=activate)
+    normed = util.random_lineouts(cfg, B, seed=seed + 50, activate=activate, ranges=ranges)
     _, names, act = _leaves(cfg)
     n_ion = sum(1 for k in cfg["parameters"] if k.startswith("ion-"))
     eng = _engine_kw(cfg, sa, activate=activate, **(engine_kw or {}))

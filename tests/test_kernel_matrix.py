@@ -527,10 +527,10 @@ def _ff_case(eng, cfg, sa, B, entry, kernels, n_ion):
         assert np.max(np.abs(a_ - r_)) <= 1e-7 * np.max(np.abs(r_)), np.max(np.abs(a_ - r_)) / np.max(np.abs(r_))
 
 
-def _fe2d(nv):
+def _fe2d(nv, width=1.3):
     vx = orc.velocity_grid(nv)
     X, Y = np.meshgrid(vx, vx, indexing="ij")
-    f = np.exp(-((X / 1.3) ** 2 + (Y / 0.8) ** 2) ** 1.4 / 2) + 0.05 * np.exp(-((X - 2.0) ** 2 + (Y + 1.0) ** 2))
+    f = np.exp(-((X / width) ** 2 + (Y / 0.8) ** 2) ** 1.4 / 2) + 0.05 * np.exp(-((X - 2.0) ** 2 + (Y + 1.0) ** 2))
     return vx, f / (f.sum() * (vx[1] - vx[0]) ** 2)
 
 

@@ -100,6 +100,26 @@ def rel_err(a, b, floor=1e-12):
     return float(np.max(np.abs(a - b) / scale))
 
 
+def _twin_weighted_grad(cfg, sa, normed, batch, w, names, fe_batch=None):
+    """d (sum_k w[k] S_k) / d leaves of the given lineouts by reverse-mode autodiff of the torch twin: the per-lineout gradient
+    of the library's loss (weights fixed by the whole batch), whatever subset of lineouts is evaluated.
+    -> (S [3], {leaf: gradient [n]}, d / d fe_batch [n, nvx] or None, ThryE, ThryI): tests/test_concurrency.py,
+    test_per_lineout_tables_gpu.py"""
+    import torch
+    from oracle import tsadar_oracle_torch as ot
+
+    nt = {k: ot._t(v).clone() for k, v in normed.items()}
+    for k in names:
+        nt[k].requires_grad_(True)
+    fb = None if fe_batch is None else torch.tensor(fe_batch, dtype=torch.float64, requires_grad=True)
+    S, _, E, I = ot.masked_sums(cfg, sa, nt, batch, True, fb)
+    val = (torch.as_tensor(np.asarray(w, dtype=np.float64)) * S).sum()
+    leaves = [nt[k] for k in names] + ([fb] if fb is not None else [])
+    grads = torch.autograd.grad(val, leaves, allow_unused=True)
+    out = {k: g.numpy() for k, g in zip(names, grads)}
+    return S.detach().numpy(), out, (grads[-1].numpy() if fb is not None else None), E.detach().numpy(), I.detach().numpy()
+
+
 # ---- the angular (ARTS) fit: tests/test_angular_loop_device.py, test_sph_generator_device.py, test_arb1v_generator_device.py
 def _angular_sa(cfg):
     from tsadar_amd import calibration
