@@ -218,8 +218,10 @@ def _irf(lam, modl, stddev):
     return (torch.amax(modl) / torch.amax(y)) * y
 
 
-def ts_diag(cfg, sa, normed, batch, activate=True, fe_batch=None):
-    """thomson_diagnostic.py:109-142 with tensors; returns (ThryE, ThryI, lamE, lamI) [B, 1024]."""
+def ts_diag(cfg, sa, normed, batch, activate=True, fe_batch=None, tap=None):
+    """thomson_diagnostic.py:109-142 with tensors; returns (ThryE, ThryI, lamE, lamI) [B, 1024].  ``tap``: a callable
+    (b, feature, P) -> P called right after form_factor; what it returns goes on in P's place (loss_adjoint splits the chain there).
+    Where f_e is differentiated it is also called as (b, "tables", (fe, W)) -> (fe, W) before the form factors of lineout b."""
     cfgp = cfg["parameters"]
     other = cfg["other"]
     ext = other["extraoptions"]
@@ -249,11 +251,15 @@ def ts_diag(cfg, sa, normed, batch, activate=True, fe_batch=None):
         else:
             fe = dlm_fe(phys["m"][b], nvx)
         W = chi_table(vx, fe) if fe.requires_grad else _t(orc.chi_table_cached(vx, fe.detach().numpy()))
+        if tap is not None and fe.requires_grad:
+            fe, W = tap(b, "tables", (fe, W))
         for feature in ("ion", "ele"):
             if not ext["load_ion_spec" if feature == "ion" else "load_ele_spec"]:
                 continue
             rng, shift = (other["lamrangI"], 0.0) if feature == "ion" else (other["lamrangE"], cfg["data"]["ele_lam_shift"])
             P, lam_cm = form_factor(rng, other["npts"], shift, sa["sa"], G, p, vx, fe, W)
+            if tap is not None:
+                P = tap(b, feature, P)
             lam = lam_cm * 1e7
             modl = torch.sum(torch.mean(P, dim=0) * w_ang, dim=1)
             if feature == "ele":
@@ -288,6 +294,12 @@ def masked_sums(cfg, sa, normed, batch, activate=True, fe_batch=None):
     """Un-normalised masked sums [S_iaw, S_blue, S_red] of the loss functional over the given lineouts,
     the number of fitted entries of each, and the spectra (loss_function.py:190-267 before the mean)."""
     ThryE, ThryI, lamE, lamI = ts_diag(cfg, sa, normed, batch, activate, fe_batch)
+    S, N = _sums_of_spectra(cfg, batch, ThryE, ThryI, lamE, lamI)
+    return S, N, ThryE, ThryI
+
+
+def _sums_of_spectra(cfg, batch, ThryE, ThryI, lamE, lamI):
+    """masked_sums from the spectra on: (S [3], N [3])."""
     ext = cfg["other"]["extraoptions"]
     method = cfg["optimizer"]["loss_method"]
     iaw, blue, red = orc.fit_masks(cfg, lamE.detach().numpy(), lamI.detach().numpy())
@@ -311,12 +323,17 @@ def masked_sums(cfg, sa, normed, batch, activate=True, fe_batch=None):
         S[1], N[1] = fun(batch["e_data"], ThryE)[torch.as_tensor(blue)].sum(), int(blue.sum())
     if ext["fit_EPWr"]:
         S[2], N[2] = fun(batch["e_data"], ThryE)[torch.as_tensor(red)].sum(), int(red.sum())
-    return torch.stack(S), N, ThryE, ThryI
+    return torch.stack(S), N
 
 
 def loss(cfg, sa, normed, batch, i_norm, e_norm, activate=True, fe_batch=None):
     """loss_function.py:364-373 (nanmean over the masked entries of the whole batch)."""
     S, N, ThryE, ThryI = masked_sums(cfg, sa, normed, batch, activate, fe_batch)
+    return _loss_of_sums(cfg, S, N, i_norm, e_norm), ThryE, ThryI
+
+
+def _loss_of_sums(cfg, S, N, i_norm, e_norm):
+    """loss from the masked sums on: the means, the halving, ion_loss_scale."""
     ext = cfg["other"]["extraoptions"]
     dep = cfg["optimizer"]["loss_method"] in ("l1", "l2")  # the other functionals ignore the denominator
     ui, ue = (i_norm**2, e_norm**2) if dep else (1.0, 1.0)
@@ -328,7 +345,7 @@ def loss(cfg, sa, normed, batch, i_norm, e_norm, activate=True, fe_batch=None):
         e_err = e_err + S[2] / (N[2] * ue)
         if ext["fit_EPWb"]:
             e_err = e_err * 0.5
-    return cfg["data"]["ion_loss_scale"] * i_err + e_err, ThryE, ThryI
+    return cfg["data"]["ion_loss_scale"] * i_err + e_err
 
 
 def hessian_loss(cfg, sa, normed, batch, activate=True):
@@ -387,6 +404,116 @@ def value_and_grad_fe(cfg, sa, normed_np, batch, i_norm, e_norm, names, fe_batch
     grads = torch.autograd.grad(val, [normed[k] for k in names] + [fe], allow_unused=True)
     out = {k: (g.numpy() if g is not None else np.zeros_like(normed_np[k])) for k, g in zip(names, grads[:-1])}
     return float(val.detach()), out, grads[-1].numpy(), E.detach().numpy(), I.detach().numpy()
+
+
+def _jacobian_rows(T, leaves, rows):
+    """d T / d leaf[rows[r]] for every leaf: a tensor [len(leaves), len(rows)] + T.shape by the double-backward trick --
+    h = grad(<T, v>, leaf) with the graph kept is linear in v, and grad(h[b], v) is d T / d leaf[b].  A leaf T does not depend on
+    gives zeros."""
+    J = torch.zeros((len(leaves), len(rows)) + tuple(T.shape), dtype=DT)
+    if not T.requires_grad:
+        return J
+    v = torch.ones_like(T, requires_grad=True)
+    h = torch.autograd.grad((T * v).sum(), leaves, create_graph=True, allow_unused=True)
+    for k, hk in enumerate(h):
+        if hk is None or not hk.requires_grad:
+            continue
+        for r, b in enumerate(rows):
+            J[k, r] = torch.autograd.grad(hk[b], v, retain_graph=True)[0]
+    return J
+
+
+def _sparse_jacobian(P, x, chunk=256):
+    """d P / d x for a table x [n] that every point of P reads a few nodes of: (node index, flat point index, value) of the
+    non-zero entries, by the double-backward trick of _jacobian_rows, a chunk of nodes per backward."""
+    v = torch.ones_like(P, requires_grad=True)
+    h, = torch.autograd.grad((P * v).sum(), x, create_graph=True)
+    n = x.numel()
+    ii, pp, vv = [], [], []
+    # the nodes some point reads, from random positive weights: a node that no point reads has an exactly zero row
+    hr, = torch.autograd.grad((P * (1.0 + torch.rand_like(P))).sum(), x, retain_graph=True)
+    nodes = torch.nonzero(hr, as_tuple=True)[0]
+    for lo in range(0, nodes.numel(), chunk):
+        sel = nodes[lo:lo + chunk]
+        eye = torch.zeros((sel.numel(), n), dtype=DT)
+        eye[torch.arange(sel.numel()), sel] = 1.0
+        J, = torch.autograd.grad(h, v, grad_outputs=eye, retain_graph=True, is_grads_batched=True)
+        J = J.reshape(sel.numel(), -1)
+        i, q = torch.nonzero(J, as_tuple=True)
+        ii.append(sel[i]); pp.append(q); vv.append(J[i, q])
+    return torch.cat(ii), torch.cat(pp), torch.cat(vv)
+
+
+def _adjoint_graph(cfg, sa, normed_np, batch, names, fe_batch, activate):
+    """What loss_adjoint needs that no seed changes: the chain cut at P -- leaves -> P (stage 1; kept as its Jacobian, the graph of
+    each form-factor call is dropped at once) and (P_leaf, leaves) -> T (stage 2; graph kept) -- and d T / d leaves at fixed P.
+    Where the DLM order is a leaf the chain is cut once more, at the tables m -> (f_e, W) -> P: d P / d m of one point is a sum over
+    the table nodes the point reads, whose terms cancel, and the terms of g[b, m] are then those of every (point, node)."""
+    normed = {k: _t(v).clone() for k, v in normed_np.items()}
+    leaves = [normed[k].requires_grad_(True) for k in names]
+    B = normed["Te"].numel()
+    P_leaf, JP, tables, JX = {}, {}, {}, {}
+
+    def tap(b, feature, P):
+        if feature == "tables":   # P = (fe, W): held as leaves; their own derivatives along m
+            d = [_jacobian_rows(x, [normed["m"]], [b])[0, 0] for x in P]
+            tables[b] = [x.detach().clone().requires_grad_(True) for x in P]
+            JX[b] = dict(d=d, J={})
+            return tuple(tables[b])
+        JP[(b, feature)] = _jacobian_rows(P, leaves, [b])[:, 0]          # [K, G, npts, n_angles]
+        if b in tables:
+            JX[b]["J"][feature] = [_sparse_jacobian(P, x) for x in tables[b]]
+        P_leaf[(b, feature)] = P.detach().clone().requires_grad_(True)
+        return P_leaf[(b, feature)]
+
+    E, I, lamE, lamI = ts_diag(cfg, sa, normed, batch, activate, fe_batch, tap=tap)
+    JT = []
+    for T in (E, I):   # [K, B, 1024]: lineout b's row of d T / d leaf[b] (the amplitudes; every other path runs through P)
+        J = _jacobian_rows(T, leaves, list(range(B)))
+        JT.append(torch.stack([J[:, b, b] for b in range(B)], dim=1))
+    return dict(E=E, I=I, lamE=lamE.detach(), lamI=lamI.detach(), P_leaf=P_leaf, JP=JP, JE=JT[0], JI=JT[1], JX=JX)
+
+
+def loss_adjoint(cfg, sa, normed_np, batch, i_norm, e_norm, names, seed_from=None, fe_batch=None, activate=True, cache=None):
+    """The loss gradient as the sum of its terms, and the sum of their absolute values:
+
+      g[b, k] = sum_(f,g,i,a) Pbar[f,g,i,a] dP[f,g,i,a]/dx_k + sum_(f,j) Tbar[f,j] (dT[f,j]/dx_k at fixed P),   A[b, k]: |.| of every term
+
+    P: what form_factor returns (feature f, gradient point g, wavelength sample i, angle a), T: ThryE / ThryI, Tbar = d loss / d T,
+    Pbar = d loss / d P.  A is the scale at which two float64 summations of these terms may differ, entry by entry (as in ff2d_adjoint).
+    ``seed_from`` = (E, I): Tbar is the derivative of the loss functional (loss()'s own weights, masks and halving) at those spectra
+    instead of the twin's own -- the adjoint of a device whose forward is pinned separately.  ``names``: the trainable leaves
+    (a tied Ti is not one; its adjoint arrives in ion-1's; for ``m`` the terms are those of every (point, table node), see
+    _adjoint_graph); ``cache``: a dict that keeps what does not depend on the seed.
+    Returns (g [B, K], A [B, K], ThryE, ThryI)."""
+    c = cache if cache is not None else {}
+    if "E" not in c:
+        c.update(_adjoint_graph(cfg, sa, normed_np, batch, names, fe_batch, activate))
+    E, I = c["E"], c["I"]
+    Es, Is = (E, I) if seed_from is None else (_t(np.asarray(seed_from[0])), _t(np.asarray(seed_from[1])))
+    Es, Is = Es.detach().clone().requires_grad_(True), Is.detach().clone().requires_grad_(True)
+    S, N = _sums_of_spectra(cfg, batch, Es, Is, c["lamE"], c["lamI"])
+    Eb, Ib = torch.autograd.grad(_loss_of_sums(cfg, S, N, i_norm, e_norm), [Es, Is], allow_unused=True)
+    Eb = torch.zeros_like(Es) if Eb is None else Eb
+    Ib = torch.zeros_like(Is) if Ib is None else Ib
+    keys = list(c["P_leaf"])
+    Pbar = torch.autograd.grad((Eb * E).sum() + (Ib * I).sum(), [c["P_leaf"][k] for k in keys], retain_graph=True)
+    B, K = E.shape[0], len(names)
+    g, A = torch.zeros((B, K), dtype=DT), torch.zeros((B, K), dtype=DT)
+    for (b, f), pb in zip(keys, Pbar):
+        t = pb[None] * c["JP"][(b, f)]
+        g[b] += t.sum(dim=(1, 2, 3))
+        A[b] += t.abs().sum(dim=(1, 2, 3))
+        if b in c["JX"]:   # the DLM order: Pbar[point] dP[point]/dx[node] dx[node]/dm over the nodes of f_e and of W
+            for (i, q, v), d in zip(c["JX"][b]["J"][f], c["JX"][b]["d"]):
+                t = pb.reshape(-1)[q] * v * d[i]
+                g[b, names.index("m")] += t.sum()
+                A[b, names.index("m")] += t.abs().sum()
+    for Tb, J in ((Eb, c["JE"]), (Ib, c["JI"])):
+        t = Tb[None] * J
+        g += t.sum(dim=2).T
+        A += t.abs().sum(dim=2).T
+    return g.numpy(), A.numpy(), E.detach().numpy(), I.detach().numpy()
 
 
 # ---------------------------------------------------------------------------------------------

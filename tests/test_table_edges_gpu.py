@@ -44,23 +44,6 @@ def _case(name):
     return dict(cfg=cfg, sa=sa, batch=batch, normed=normed, i_norm=i_norm, e_norm=e_norm, X=util.normed_to_matrix(normed, 1))
 
 
-def _positions(cfg, sa, p, feature):
-    """(xi_e, xi_i) [npts, n_angles] of one lineout's sweep over a feature: form_factor.py:215-253 as the oracle's form_factor() (G = 1)."""
-    o = cfg["other"]
-    rng = o["lamrangE"] if feature == 0 else o["lamrangI"]
-    shift = cfg["data"].get("ele_lam_shift", 0.0) if feature == 0 else 0.0
-    omgs = (2e7 * np.pi * orc.C / np.linspace(rng[0], rng[1], o["npts"]))[:, None]
-    omgL = 2 * np.pi * 1e7 * orc.C / (p["lam"] + shift)
-    omgpe = orc.C0 * np.sqrt(1.0e20 * p["ne"])
-    ks = np.sqrt(omgs**2 - omgpe**2) / orc.C
-    kL = np.sqrt(omgL**2 - omgpe**2) / orc.C
-    k = np.sqrt(ks**2 + kL**2 - 2 * ks * kL * np.cos(np.asarray(sa["sa"]) * np.pi / 180)[None, :])
-    omgdop = (omgs - omgL) - k * p["Va"] * 1e6
-    vTe = np.sqrt(p["Te"] / orc.ME)
-    vTi = np.sqrt(np.asarray(p["Ti"])[0] / (np.asarray(p["A"])[0] * orc.MP))
-    return omgdop / (k * vTe) - p["ud"] * 1e6 / vTe, (1.0 / (np.sqrt(2.0) * vTi)) * (omgdop / k)
-
-
 def _classes(name):
     s = _case(name)
     phys = orc.physical_params(s["cfg"]["parameters"], s["normed"], True)
@@ -70,7 +53,7 @@ def _classes(name):
     for b in range(B):
         p = orc.lineout_params(phys, b, 1)
         for f in (0, 1):
-            xe, xi = _positions(s["cfg"], s["sa"], p, f)
+            xe, xi = util.positions(s["cfg"], s["sa"], p, f)
             assert xe.shape == (1024, 10)
             if f == 0:
                 n["xe_left"] += int((xe < XI_LO).sum()); n["xe_right"] += int((xe > XI_HI).sum())

@@ -120,6 +120,36 @@ def _twin_weighted_grad(cfg, sa, normed, batch, w, names, fe_batch=None):
     return S.detach().numpy(), out, (grads[-1].numpy() if fb is not None else None), E.detach().numpy(), I.detach().numpy()
 
 
+def positions(cfg, sa, p, feature, ion=0, grad_point=None):
+    """(xi_e, xi_i) [npts, n_angles] of one lineout's sweep over a feature: form_factor.py:215-253 as the oracle's form_factor().
+    ``ion``: the species xi_i is of; ``grad_point``: the gradient point whose T_e and n_e the sweep runs at (None: the lineout's own,
+    G = 1).  tests/test_table_edges_gpu.py, test_loss_grad_entries.py"""
+    o = cfg["other"]
+    rng = o["lamrangE"] if feature == 0 else o["lamrangI"]
+    shift = cfg["data"].get("ele_lam_shift", 0.0) if feature == 0 else 0.0
+    Te, ne = p["Te"], p["ne"]
+    if grad_point is not None:   # linspace(1 - v / 200, 1 + v / 200, G)[grad_point]
+        G = cfg["parameters"]["general"]["Te_gradient"]["num_grad_points"]
+        at = lambda v: np.linspace(1 - v / 200, 1 + v / 200, G)[grad_point]
+        Te, ne = Te * at(p["Te_gradient"]), ne * at(p["ne_gradient"])
+    omgs = (2e7 * np.pi * orc.C / np.linspace(rng[0], rng[1], o["npts"]))[:, None]
+    omgL = 2 * np.pi * 1e7 * orc.C / (p["lam"] + shift)
+    omgpe = orc.C0 * np.sqrt(1.0e20 * ne)
+    ks = np.sqrt(omgs**2 - omgpe**2) / orc.C
+    kL = np.sqrt(omgL**2 - omgpe**2) / orc.C
+    k = np.sqrt(ks**2 + kL**2 - 2 * ks * kL * np.cos(np.asarray(sa["sa"]) * np.pi / 180)[None, :])
+    omgdop = (omgs - omgL) - k * p["Va"] * 1e6
+    vTe = np.sqrt(Te / orc.ME)
+    vTi = np.sqrt(np.asarray(p["Ti"])[ion] / (np.asarray(p["A"])[ion] * orc.MP))
+    return omgdop / (k * vTe) - p["ud"] * 1e6 / vTe, (1.0 / (np.sqrt(2.0) * vTi)) * (omgdop / k)
+
+
+def node_distance(x, nodes):
+    """distance of every x to the nearest node of a uniform grid, in cells (beyond the grid: to its end node)"""
+    t = (np.asarray(x) - nodes[0]) / (nodes[1] - nodes[0])
+    return np.abs(t - np.clip(np.round(t), 0, len(nodes) - 1))
+
+
 # ---- the angular (ARTS) fit: tests/test_angular_loop_device.py, test_sph_generator_device.py, test_arb1v_generator_device.py
 def _angular_sa(cfg):
     from tsadar_amd import calibration
