@@ -8,12 +8,11 @@
 // to x_j (before the factor ws^2), the adjoints of this point's base quantities (ba) and of the right neighbour's (xi_e, F),
 // and accumulates the direct lineout-scalar adjoints into the row J.  cw = -i2wL^2 / 2 folds the adjoint of 2/wL into wL.
 // The deferred factor of a_i (x -1/2) is applied after the contraction (see the kernel); pref's adjoint is x_j itself.
-template <int NI, int GM, bool ZH, bool FAR = false>
-__device__ __forceinline__ double point_fused(const Base& b, const Base& bn, bool has_next, const LineS<NI>& L, const Tables& T,
-                                              double PQ, double cw, BaseAdj& ba, double& xen, double& Fn, LineS<NI>& J) {
-  // ---- forward (form_factor.py:243-296) ----
-  PointF<NI> pf;
-  point_core<NI, ZH, FAR>(b, bn, has_next, L, T, pf);
+// point_fused_reverse is the reverse alone, of a point whose forward quantities pf the caller has (point_core, or its three steps:
+// pair_step_sched); point_fused is point_core followed by it.
+template <int NI, int GM, bool FAR = false>
+__device__ __forceinline__ double point_fused_reverse(const PointF<NI>& pf, const Base& b, const LineS<NI>& L, const Tables& T,
+                                                      double PQ, double cw, BaseAdj& ba, double& xen, double& Fn, LineS<NI>& J) {
   const double ik2 = pf.ik2, ike2 = pf.ike2, vph = pf.vph, gsum = pf.gsum, Wl = pf.Wl, dW = pf.dW, idx = pf.idx, D = pf.D;
   const double cer = pf.cer, cei = pf.cei, opc = pf.opc, cim = pf.cim, er = pf.er, ei = pf.ei, ieps2 = pf.ieps2, ce2 = pf.ce2, ci2 = pf.ci2;
   const double N = pf.N, t1 = pf.t1, S = pf.S, dop = pf.dop;
@@ -78,6 +77,14 @@ __device__ __forceinline__ double point_fused(const Base& b, const Base& bn, boo
   ba.wd = PSQ * L.i2wL + vphb * b.ik;
   ba.ik = ikb0 + vphb * b.wd;
   return fwd;
+}
+template <int NI, int GM, bool ZH, bool FAR = false>
+__device__ __forceinline__ double point_fused(const Base& b, const Base& bn, bool has_next, const LineS<NI>& L, const Tables& T,
+                                              double PQ, double cw, BaseAdj& ba, double& xen, double& Fn, LineS<NI>& J) {
+  // ---- forward (form_factor.py:243-296) ----
+  PointF<NI> pf;
+  point_core<NI, ZH, FAR>(b, bn, has_next, L, T, pf);
+  return point_fused_reverse<NI, GM, FAR>(pf, b, L, T, PQ, cw, ba, xen, Fn, J);
 }
 
 // The adjoint of k^2 = k_s^2 + k_L^2 - 2 k_s k_L cos(theta) flows to k_L and, through k_s(lambda), to omega_pe^2:
@@ -192,6 +199,19 @@ __device__ __forceinline__ void unit_boundary_fill(double wse, double ct, const 
 // The second base point of a pair from the neighbour lane's FIRST one of this angle (bf), register to register (next_lane_f64; all 64
 // lanes are here: the branches and loops around it are wavefront-uniform); the last lane takes the unit's boundary point at src
 // (unit_boundary_fill).  ks2: k_s of that sample.
+// (pair_step_sched asks for the boundary point ahead of the exchange: boundary_request, then neighbour_take with the values)
+struct Boundary { double wd, ik, xe, F, dH; };
+__device__ __forceinline__ void boundary_request(const double* src, Boundary& u) {
+  u.wd = src[0]; u.ik = src[kExBound]; u.xe = src[2 * kExBound]; u.F = src[3 * kExBound]; u.dH = src[4 * kExBound];
+}
+template <int NI>
+__device__ __forceinline__ void neighbour_take(const Base& bf, const Boundary& u, double ks2, double ct, const LineS<NI>& L, Base& b1) {
+  b1.wd = next_lane_f64(bf.wd, u.wd); b1.ik = next_lane_f64(bf.ik, u.ik); b1.xe = next_lane_f64(bf.xe, u.xe);
+  b1.F = next_lane_f64(bf.F, u.F); b1.dH = next_lane_f64(bf.dH, u.dH);
+  b1.ks = ks2;
+  b1.k2 = base_k2<NI>(ks2, ct, L);   // (base_eval's own expression: the same bits; k itself -- a separately rounded
+                                     //  square root there, not k2 * ik -- only enters through wd, which is exchanged)
+}
 template <int NI>
 __device__ __forceinline__ void neighbour_take(const Base& bf, const double* src, double ks2, double ct, const LineS<NI>& L, Base& b1) {
   b1.wd = next_lane_f64(bf.wd, src[0]); b1.ik = next_lane_f64(bf.ik, src[kExBound]); b1.xe = next_lane_f64(bf.xe, src[2 * kExBound]);
@@ -201,18 +221,97 @@ __device__ __forceinline__ void neighbour_take(const Base& bf, const double* src
                                      //  square root there, not k2 * ik -- only enters through wd, which is exchanged)
 }
 
-// One point of a Jacobian row: the forward value into xa, the reverse with the seed wa into the row J, the k^2 adjoints of the
-// point's own base b0 and of its right neighbour b1 into the row's angle sums KA.
-template <int NI, int GM, bool ZH, bool FAR, bool PAD = false>
-__device__ __forceinline__ void row_step(const Base& b0, const Base& b1, bool has_next, const LineS<NI>& L, const Tables& T, double ct,
-                                         double wa, double cw, double& xa, LineS<NI>& J, KsAcc& KA) {
+// The reverse of one point of a Jacobian row behind a forward the caller has made (pf: point_core of b0 with its right neighbour b1,
+// or its three steps): the forward value into xa, the reverse with the seed wa into the row J, the k^2 adjoints of the point's own
+// base b0 and of its right neighbour b1 into the row's angle sums KA.
+template <int NI, int GM, bool FAR, bool PAD = false>
+__device__ __forceinline__ void row_reverse(const PointF<NI>& pf, const Base& b0, const Base& b1, const LineS<NI>& L, const Tables& T,
+                                            double ct, double wa, double cw, double& xa, LineS<NI>& J, KsAcc& KA) {
   BaseAdj ba;
   double xen, Fn;
-  xa = __builtin_fma(wa, point_fused<NI, GM, ZH, FAR>(b0, b1, has_next, L, T, wa, cw, ba, xen, Fn, J), xa);
+  xa = __builtin_fma(wa, point_fused_reverse<NI, GM, FAR>(pf, b0, L, T, wa, cw, ba, xen, Fn, J), xa);
   const double k22a = base_reverse_fused<NI, GM, PAD>(b0, L, T, ba, J);
   const double k22b = base_reverse_xf<NI, GM, PAD>(b1, L, T, xen, Fn, J);   // (xen = Fn = 0 at the last sample)
   KA.p1a += k22a; KA.p2a = __builtin_fma(k22a, ct, KA.p2a);
   KA.p1b += k22b; KA.p2b = __builtin_fma(k22b, ct, KA.p2b);
+}
+// One point of a Jacobian row: forward and reverse
+template <int NI, int GM, bool ZH, bool FAR, bool PAD = false>
+__device__ __forceinline__ void row_step(const Base& b0, const Base& b1, bool has_next, const LineS<NI>& L, const Tables& T, double ct,
+                                         double wa, double cw, double& xa, LineS<NI>& J, KsAcc& KA) {
+  PointF<NI> pf;
+  point_core<NI, ZH, FAR>(b0, b1, has_next, L, T, pf);
+  row_reverse<NI, GM, FAR, PAD>(pf, b0, b1, L, T, ct, wa, cw, xa, J, KA);
+}
+
+// The scheduled order of one angle iteration of a pair (r13_sweep_sched, DESIGN.md section 4.1b; profiles/r13_sweep_sched_model.txt):
+// the instructions and the bits of base_eval / row_step twice, in an order that puts arithmetic which needs no table between every
+// table read's request and its first use.  The steps are separated by scheduling barriers: inside a step the compiler orders as it
+// likes, across them it moves nothing -- left alone it sinks every read back to its use (one to five instructions ahead of it: a wait
+// of an LDS round trip per lookup).
+//   1  geometry of both base points, the two square roots in lock step; both Hermite cells requested;
+//   2  under that wait: the first point's W pair requested (the second's too in the asymptotic form), and what needs only 1/k and
+//      w - k V of the first point (point_open: the k factors, xi_i, the asymptote or the ion requests);
+//   3  both Hermite finishes and exp reductions, the two 2^(j/64) entries requested (asymptotic form: the unit's boundary point too);
+//   4  under that wait: the first point's ion and W finishes (point_lookups) and, in the asymptotic form, the second point's open and finishes;
+//   5  both F, their polynomials in lock step; close and reverse of the first point;
+//   6  general form: the boundary point and the second point's W pair requested, under that wait its open with the ion requests, under
+//      theirs the lane exchange, then its finishes; both forms: close and reverse of the second point.
+// The reverse is where the kernel's register demand peaks.  The two reverses in one step (which the compiler then alternates) cost 16
+// spilled registers; in the general form a second point's ion cells or its W pair and the boundary point in flight across the first
+// point's reverse cost 46, 27 and 2: there the second point is opened behind that reverse.
+// Given to the instantiations kSweepSched names -- the single-species kernel with the lane exchange and the full Z' table, which every
+// bench.py line but --dlm runs; the half-table form spilled two registers with it, the DLM and two-species forms were not tried and
+// keep base_eval / row_step.
+template <int NI, int GM, bool ZH, bool EX>
+constexpr bool kSweepSched = NI == 1 && GM == 0 && !ZH && EX;
+__device__ __forceinline__ void sched_fence() { __builtin_amdgcn_sched_barrier(0); }
+template <int NI, int GM, bool ZH, bool FAR, bool PAD>
+__device__ __forceinline__ void pair_step_sched(const double (&w)[kPair + 1], double ksa, double ksb, double ks2, const double* exsrc,
+                                                bool has_next1, const LineS<NI>& L, const Tables& T, double ct, double wa, double cw,
+                                                double& xa0, LineS<NI>& J0, KsAcc& KA0, double& xa1, LineS<NI>& J1, KsAcc& KA1) {
+  Base b0, b1, b2;
+  HCell h0, h1;
+  base_request_pair<NI, PAD>(w[0], w[1], ksa, ksb, ct, L, T, b0, b1, h0, h1);
+  sched_fence();
+  WCell w0, w1;
+  PointF<NI> p0, p1;
+  IonCell i0[NI], i1[NI];
+  w_request(T.W, b0.xe, w0);
+  if (FAR) w_request(T.W, b1.xe, w1);
+  point_open<NI, ZH, FAR>(b0, L, T, p0, i0);
+  sched_fence();
+  ExpCell e0, e1;
+  Boundary ub;
+  base_finish_request(T, h0, b0, e0);
+  base_finish_request(T, h1, b1, e1);
+  if (FAR) boundary_request(exsrc, ub);
+  sched_fence();
+  point_lookups<NI, ZH, FAR>(L, T, i0, w0, p0);
+  if (FAR) {
+    point_open<NI, ZH, FAR>(b1, L, T, p1, i1);
+    point_lookups<NI, ZH, FAR>(L, T, i1, w1, p1);
+  }
+  sched_fence();
+  fexp_finish_pair(e0, e1, b0.F, b1.F);
+  point_close<NI, FAR>(b0, b1, true, L, p0);
+  row_reverse<NI, GM, FAR, PAD>(p0, b0, b1, L, T, ct, wa, cw, xa0, J0, KA0);
+  sched_fence();
+  // the lane's FIRST base point of this angle is what its left neighbour asks for
+  if (!FAR) {   // (the boundary point's wait under the ion requests, theirs under the lane exchange)
+    boundary_request(exsrc, ub);
+    w_request(T.W, b1.xe, w1);
+    sched_fence();
+    point_open<NI, ZH, FAR>(b1, L, T, p1, i1);
+    sched_fence();
+  }
+  neighbour_take<NI>(b0, ub, ks2, ct, L, b2);
+  if (!FAR) {
+    sched_fence();
+    point_lookups<NI, ZH, FAR>(L, T, i1, w1, p1);
+  }
+  point_close<NI, FAR>(b1, b2, has_next1, L, p1);
+  row_reverse<NI, GM, FAR, PAD>(p1, b1, b2, L, T, ct, wa, cw, xa1, J1, KA1);
 }
 
 // the k_L and omega_pe^2 columns of a row from its angle sums (see KsAcc); ksa, ksb: k_s of the row's sample and of its right neighbour

@@ -162,9 +162,23 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_fused(KStatic S, KCall K,
     double ct_n = pn[0], wa_n = pn[1];
     // (EX) the unit's boundary point, which lane 63 takes for its missing neighbour
     const double* exu = EX ? exb + 16 * (2 * hw + P) : nullptr;
+    // (pair_step_sched) k_s of the pair's two samples, which no angle changes: read once, not at the head of every iteration, where
+    // nothing stands between the read and the square root that waits for it
+    double ksa = 0.0, ksb = 0.0;
+    if constexpr (kSweepSched<NI, GM, ZH, EX>) {
+      ksa = use_ks ? ksc[jb] : ks_eval(ws[P][0], L.wpe2);
+      ksb = use_ks ? ksc[min(jb + 1, npts - 1)] : ks_eval(ws[P][1], L.wpe2);
+    }
     for (int a = 0; a < NA; ++a) {
       const double ct = ct_n, wa = wa_n;
       { pn += a + 1 < NA ? 2 : 0; ct_n = pn[0]; wa_n = pn[1]; }   // (entry min(a + 1, NA - 1))
+      if constexpr (kSweepSched<NI, GM, ZH, EX>) {   // the two points of the pair in flight together (pair_step_sched, k_pairs.inc)
+        constexpr int q0 = kPair * P;
+        static_assert(kPair == 2, "pair_step_sched is written out for two points");
+        pair_step_sched<NI, GM, ZH, FAR, PAD>(ws[P], ksa, ksb, ks2, exu + a, pair_has_next<NI, P, 2>(1, jb + 1, npts), L, T, ct, wa, cw,
+                                              xa[q0], J[q0], KA[q0], xa[q0 + 1], J[q0 + 1], KA[q0 + 1]);
+        continue;
+      }
       Base b0;
       base_eval<NI, PAD>(ws[P][0], use_ks ? ksc[jb] : ks_eval(ws[P][0], L.wpe2), ct, L, T, b0);
       // (EX) the lane's FIRST base point of this angle is what its left neighbour asks for: b0 itself is the second one by then

@@ -75,6 +75,27 @@ __device__ __forceinline__ void fsqrt2(double x, double& s, double& is) {
   is = h + h;
 }
 
+// fsqrt2 of two arguments in lock step (r13_sweep_sched): the expressions of fsqrt2 for each, one level of the two dependency chains
+// per scheduling region, so that every instruction has the other chain's between itself and its consumer (a dependent FP64
+// instruction issues 9 cycles after its producer, an independent one 6.75: profiles/r03b_ubench_dep.txt).  Left to itself the
+// compiler runs the two chains one after the other.
+__device__ __forceinline__ void fsqrt2_pair(double x0, double x1, double& s0, double& is0, double& s1, double& is1) {
+  static_assert(TSFF_NEWTON == 1, "fsqrt2_pair is written out for one refinement step");
+  const double y0 = __builtin_amdgcn_rsq(x0), y1 = __builtin_amdgcn_rsq(x1);
+  __builtin_amdgcn_sched_barrier(0);
+  double g0 = x0 * y0, g1 = x1 * y1, h0 = 0.5 * y0, h1 = 0.5 * y1;
+  __builtin_amdgcn_sched_barrier(0);
+  const double r0 = __builtin_fma(-h0, g0, 0.5), r1 = __builtin_fma(-h1, g1, 0.5);
+  __builtin_amdgcn_sched_barrier(0);
+  g0 = __builtin_fma(g0, r0, g0); g1 = __builtin_fma(g1, r1, g1);
+  h0 = __builtin_fma(h0, r0, h0); h1 = __builtin_fma(h1, r1, h1);
+  __builtin_amdgcn_sched_barrier(0);
+  const double d0 = __builtin_fma(-g0, g0, x0), d1 = __builtin_fma(-g1, g1, x1);
+  __builtin_amdgcn_sched_barrier(0);
+  s0 = __builtin_fma(d0, h0, g0); s1 = __builtin_fma(d1, h1, g1);
+  is0 = h0 + h0; is1 = h1 + h1;
+}
+
 // A value every lane of the wavefront holds identically (lineout scalars, per-angle constants):
 // move it to SGPRs so it stops occupying a VGPR pair in every lane.
 __device__ __forceinline__ double uni(double x) {
@@ -209,8 +230,13 @@ __device__ __forceinline__ void fe_add_h(FeAcc& a, const Tables& T, double x, do
   a.s1 += hb * (t3 - t2) * T.dv;
 }
 
+// A table lookup in two steps (r13_sweep_sched): the REQUEST computes the cell and issues the LDS read, the
+// FINISH takes the loaded values and does the arithmetic.  A caller that has other work puts it between the two (k_spectrum_fused's
+// angle loops, behind scheduling barriers); the one-call forms below are request immediately followed by finish -- the same
+// instructions in the same order as before the split.
+struct WCell { double a, b, t; bool in; };   // the two nodes, the weight, and whether the position lies inside the table
 // jnp.interp(xie, xi2, W): clamps to the end values outside the table (form_factor.py:270)
-__device__ __forceinline__ void w_lookup(const double* W, double xe, double& w, double& dw) {
+__device__ __forceinline__ void w_request(const double* W, double xe, WCell& c) {
 #pragma clang fp contract(off)   // (every rounding that reaches a spectrum is written out: the same bits from every kernel)
   // position in cell units, clamped into the table: outside it the clamped cell reproduces the end value (t = 0 at the left
   // end, t = 1 - 2^-52 at the right end) -- floor / subtract instead of convert-back / multiply-add, and ONE comparison
@@ -219,12 +245,21 @@ __device__ __forceinline__ void w_lookup(const double* W, double xe, double& w, 
   const double u = __builtin_fma(xe, kXi2_ih, -kXi2_0 * kXi2_ih);
   const double uc = fmin(fmax(u, 0.0), kTop);
   const double fl = __builtin_floor(uc);
-  const double t = uc - fl;
+  c.t = uc - fl;
   const int i = (int)fl;
-  const double a = W[i], b = W[i + 1];
-  const double d = b - a;
-  w = __builtin_fma(t, d, a);
-  dw = (u == uc) ? d * kXi2_ih : 0.0;
+  c.a = W[i]; c.b = W[i + 1];
+  c.in = u == uc;
+}
+__device__ __forceinline__ void w_finish(const WCell& c, double& w, double& dw) {
+#pragma clang fp contract(off)
+  const double d = c.b - c.a;
+  w = __builtin_fma(c.t, d, c.a);
+  dw = c.in ? d * kXi2_ih : 0.0;
+}
+__device__ __forceinline__ void w_lookup(const double* W, double xe, double& w, double& dw) {
+  WCell c;
+  w_request(W, xe, c);
+  w_finish(c, w, dw);
 }
 
 // cubic coefficients of interval i of the Hermite interpolant in t = (x - vx_i)/dv:
@@ -250,22 +285,33 @@ __device__ __forceinline__ void hermite_pad_cell(double2* hc, int nvx, double ou
 //   [-1, nvx - 1]: floor gives -1 or nvx - 1, and the UNSIGNED minimum with nvx - 1 sends both to the out-of-grid cell nvx - 1
 //   (hermite_pad_cell: the caller's table must have it); t stays in [0, 1], where that cell's cubic is exactly its constant
 //   (-50 for ln f_e) with slope +0.  The same bits as PAD = false for every double x.
+struct HCell { double2 c01, c23; double t; bool out; };   // the cell's cubic, the position in it, and (PAD = false) outside the grid
 template <bool PAD = false>
-__device__ __forceinline__ void hermite_lookup_c(const Tables& T, double x, double& H, double& dH) {
+__device__ __forceinline__ void hermite_request(const Tables& T, double x, HCell& c) {
 #pragma clang fp contract(off)
   // (same index arithmetic as w_lookup; T.u0 = -vx0 / dv)
   const double u = __builtin_fma(x, T.idv, T.u0);
   const double uc = PAD ? fmin(fmax(u, -1.0), T.uhi) : fmin(fmax(u, 0.0), T.utop);
   const double fl = __builtin_floor(uc);
-  const double t = uc - fl;
+  c.t = uc - fl;
   int i = (int)fl;
   if (PAD) { const unsigned iu = (unsigned)i, itop = (unsigned)(T.nvx - 1); i = (int)(iu < itop ? iu : itop); }
-  const double2 c01 = T.hc[2 * i], c23 = T.hc[2 * i + 1];
-  const bool out = !PAD && u != uc;
-  const double Hi = __builtin_fma(t, __builtin_fma(t, __builtin_fma(t, c23.y, c23.x), c01.y), c01.x);
-  const double dHi = __builtin_fma(t, __builtin_fma(3.0 * t, c23.y, 2.0 * c23.x), c01.y) * T.idv;
-  H = out ? -50.0 : Hi;
-  dH = out ? 0.0 : dHi;
+  c.c01 = T.hc[2 * i]; c.c23 = T.hc[2 * i + 1];
+  c.out = !PAD && u != uc;
+}
+__device__ __forceinline__ void hermite_finish(const Tables& T, const HCell& c, double& H, double& dH) {
+#pragma clang fp contract(off)
+  const double t = c.t;
+  const double Hi = __builtin_fma(t, __builtin_fma(t, __builtin_fma(t, c.c23.y, c.c23.x), c.c01.y), c.c01.x);
+  const double dHi = __builtin_fma(t, __builtin_fma(3.0 * t, c.c23.y, 2.0 * c.c23.x), c.c01.y) * T.idv;
+  H = c.out ? -50.0 : Hi;
+  dH = c.out ? 0.0 : dHi;
+}
+template <bool PAD = false>
+__device__ __forceinline__ void hermite_lookup_c(const Tables& T, double x, double& H, double& dH) {
+  HCell c;
+  hermite_request<PAD>(T, x, c);
+  hermite_finish(T, c, H, dH);
 }
 
 // interpax.interp1d(x, vx, ln fe, method="cubic", extrap=[-50,-50])  (form_factor.py:256,263)
@@ -464,7 +510,39 @@ __device__ __forceinline__ double fexp_t(double x, const double* __restrict__ ta
   const int ni = (int)n;
   return ldexp(p * tab[ni & (kNExpTab - 1)], ni >> 6);
 }
-
+// fexp_t in two steps (r13_sweep_sched): the reduction and the request of 2^(j/64), then the polynomial and the scaling -- the very
+// expressions of fexp_t, the table entry asked for ahead of the polynomial instead of behind it
+struct ExpCell { double r, tv; int ni; };   // the reduced argument, the table's 2^(j/64), and 64 n' + j
+template <bool CLAMP = true>
+__device__ __forceinline__ void fexp_request(double x, const double* __restrict__ tab, ExpCell& c) {
+  if (CLAMP) x = fmax(x, -800.0);
+  const double n = __builtin_rint(x * 92.332482616893656908);          // 64 / ln 2
+  double r = __builtin_fma(n, -0.01083042469326756, x);           // ln2/64, high part (trailing zeros: n * hi exact)
+  c.r = __builtin_fma(n, -2.9815858269852933e-12, r);              // low part
+  c.ni = (int)n;
+  c.tv = tab[c.ni & (kNExpTab - 1)];
+}
+__device__ __forceinline__ double fexp_finish(const ExpCell& c) {
+  const double r = c.r;
+  double p = 8.333333333333333e-03;                                    // 1/5!
+  p = __builtin_fma(p, r, 4.1666666666666664e-02);
+  p = __builtin_fma(p, r, 1.6666666666666666e-01);
+  p = __builtin_fma(p, r, 0.5);
+  p = __builtin_fma(p, r, 1.0);
+  p = __builtin_fma(p, r, 1.0);
+  return ldexp(p * c.tv, c.ni >> 6);
+}
+constexpr double kExpPoly[6] = {8.333333333333333e-03, 4.1666666666666664e-02, 1.6666666666666666e-01, 0.5, 1.0, 1.0};   // fexp_finish's
+// fexp_finish of two cells, the two Horner chains in lock step (one level per scheduling region, as fsqrt2_pair)
+__device__ __forceinline__ void fexp_finish_pair(const ExpCell& c0, const ExpCell& c1, double& f0, double& f1) {
+  double p0 = kExpPoly[0], p1 = kExpPoly[0];
+#pragma unroll
+  for (int k = 1; k < 6; ++k) {
+    p0 = __builtin_fma(p0, c0.r, kExpPoly[k]); p1 = __builtin_fma(p1, c1.r, kExpPoly[k]);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  f0 = ldexp(p0 * c0.tv, c0.ni >> 6); f1 = ldexp(p1 * c1.tv, c1.ni >> 6);
+}
 struct Base {  // quantities needed at point j AND as the right neighbour of point j-1
   double ks, k2, ik, wd, xe, F, dH;   // k = k2*ik, v_ph = wd*ik
 };
@@ -485,9 +563,10 @@ __device__ __forceinline__ double base_k2(double ks, double ct, const LineS<NI>&
 }
 
 // PAD: the form of the Hermite lookup (hermite_lookup_c)
+// base_request: the geometry of a base point and the request of its Hermite cell; base_finish: H, dH/dxi and F = exp(H) -- or, for
+// a caller that fills the exp table's wait too, base_finish_request (up to the request of 2^(j/64)) and fexp_finish.
 template <int NI, bool PAD = false>
-__device__ __forceinline__ void base_eval(double ws, double ks, double ct, const LineS<NI>& L, const Tables& T,
-                                          Base& b) {
+__device__ __forceinline__ void base_request(double ws, double ks, double ct, const LineS<NI>& L, const Tables& T, Base& b, HCell& c) {
 #pragma clang fp contract(off)
   b.ks = ks;
   b.k2 = base_k2<NI>(ks, ct, L);
@@ -495,9 +574,38 @@ __device__ __forceinline__ void base_eval(double ws, double ks, double ct, const
   fsqrt2(b.k2, k, b.ik);
   b.wd = __builtin_fma(-k, L.Vd, ws - L.wL);               // :216, 222-223
   b.xe = __builtin_fma(b.wd, b.ik, -L.Ud) * L.ivTe;        // :253
+  hermite_request<PAD>(T, b.xe, c);
+}
+// base_request of the two base points of a pair, their square roots in lock step (fsqrt2_pair)
+template <int NI, bool PAD = false>
+__device__ __forceinline__ void base_request_pair(double ws0, double ws1, double ks0, double ks1, double ct, const LineS<NI>& L,
+                                                  const Tables& T, Base& b0, Base& b1, HCell& c0, HCell& c1) {
+#pragma clang fp contract(off)
+  b0.ks = ks0; b1.ks = ks1;
+  b0.k2 = base_k2<NI>(ks0, ct, L); b1.k2 = base_k2<NI>(ks1, ct, L);
+  double k0, k1;
+  fsqrt2_pair(b0.k2, b1.k2, k0, b0.ik, k1, b1.ik);
+  b0.wd = __builtin_fma(-k0, L.Vd, ws0 - L.wL); b1.wd = __builtin_fma(-k1, L.Vd, ws1 - L.wL);                 // :216, 222-223
+  b0.xe = __builtin_fma(b0.wd, b0.ik, -L.Ud) * L.ivTe; b1.xe = __builtin_fma(b1.wd, b1.ik, -L.Ud) * L.ivTe;   // :253
+  hermite_request<PAD>(T, b0.xe, c0);
+  hermite_request<PAD>(T, b1.xe, c1);
+}
+__device__ __forceinline__ void base_finish_request(const Tables& T, const HCell& c, Base& b, ExpCell& e) {
   double H;
-  hermite_lookup_c<PAD>(T, b.xe, H, b.dH);
+  hermite_finish(T, c, H, b.dH);
+  fexp_request<false>(H, T.etab, e);
+}
+__device__ __forceinline__ void base_finish(const Tables& T, const HCell& c, Base& b) {
+  double H;
+  hermite_finish(T, c, H, b.dH);
   b.F = T.etab ? fexp_t<false>(H, T.etab) : fexp<false>(H);   // :256  (T.etab is set or not per kernel: folded at compile time)
+}
+template <int NI, bool PAD = false>
+__device__ __forceinline__ void base_eval(double ws, double ks, double ct, const LineS<NI>& L, const Tables& T,
+                                          Base& b) {
+  HCell c;
+  base_request<NI, PAD>(ws, ks, ct, L, T, b, c);
+  base_finish(T, c, b);
 }
 
 // ion terms of one species at normalised phase velocity xi (form_factor.py:243-249, 277-280):
@@ -556,6 +664,53 @@ __device__ __forceinline__ void ion_terms(const double2* zp, double xi, double& 
   const double di2 = -2.0 * i2 * i2 * xi;
   zr = out ? i2 : zr; zi = out ? 0.0 : zi; dzr = out ? di2 : dzr; dzi = out ? 0.0 : dzi;
 }
+// ion_terms in two steps (r13_sweep_sched): the very expressions of ion_terms above, in another order -- the requests first.  The one-sweep
+// kernel's spectra are held bit for bit against k_spectrum's, which calls ion_terms (tests/test_sweep_schedule_gpu.py).
+struct IonCell { double2 a, b; double t, i2, di2; int sx; bool out; ExpCell e; };   // the two Z' nodes, the weight, the asymptote
+// ion_request: the request of exp(-xi^2)'s table entry (with etab), the Z' cell and its read, and the asymptote xi^-2 with its slope
+// (which need no table: they stand under the reads' wait)
+template <bool ZH = true>
+__device__ __forceinline__ void ion_request(const double2* zp, double xi, IonCell& c, const double* etab = nullptr) {
+#pragma clang fp contract(off)
+  if (etab) fexp_request(-(xi * xi), etab, c.e);
+  constexpr double kTop = (double)(kNXi2 - 1) * (1.0 - 1.1102230246251565e-16);
+  const double u = __builtin_fma(xi, kXi2_ih, -kXi2_0 * kXi2_ih);
+  const double uc = fmin(fmax(u, 0.0), kTop);
+  const double fl = __builtin_floor(uc);
+  c.t = uc - fl;
+  const int i = (int)fl;
+  if (ZH) {
+    // the cell and the weight exactly as the full table takes them (below), then the two nodes through the mirror: node i of the
+    // full table, xi2[i] = -8.2 + 0.01 i, is node |i - 820| of the half table with the sign of i - 820 on the odd part.  The
+    // interpolation runs over the same two values in the same order: the same bits as ZH = false.
+    constexpr int kMid = kNZh - 1;   // full-table index of xi = 0
+    const int da = i - kMid, db = da + 1;
+    c.a = zp[da < 0 ? -da : da]; c.b = zp[db < 0 ? -db : db];
+    c.sx = da & (int)0x80000000;   // (node i + 1 = 0 when da = -1: its odd part is an exact zero, the sign is immaterial)
+  } else {
+    c.a = zp[i]; c.b = zp[i + 1];
+    c.sx = 0;
+  }
+  c.out = u != uc;   // (outside the table <=> the clamp moved the position)
+  c.i2 = frcp(xi * xi);
+  c.di2 = -2.0 * c.i2 * c.i2 * xi;
+}
+template <bool ZH = true>
+__device__ __forceinline__ void ion_finish(const IonCell& c, double xi, double& zr, double& zi, double& dzr, double& dzi, double& gs,
+                                           const double* etab = nullptr) {
+#pragma clang fp contract(off)
+  gs = (etab ? fexp_finish(c.e) : fexp(-(xi * xi))) * kInvSqrt2Pi;
+  double2 a = c.a, b = c.b;
+  if (ZH) {
+    a.y = __hiloint2double(__double2hiint(a.y) ^ c.sx, __double2loint(a.y));
+    b.y = __hiloint2double(__double2hiint(b.y) ^ c.sx, __double2loint(b.y));
+  }
+  const double dr = b.x - a.x, di = b.y - a.y;
+  zr = __builtin_fma(c.t, dr, a.x); zi = __builtin_fma(c.t, di, a.y); dzr = dr * kXi2_ih; dzi = di * kXi2_ih;
+  // straight-line form (selects instead of branches: one scheduling region per point; wavefront-uniform shortcuts for the
+  // far EPW window and for the in-table IAW window were both measured slower)
+  zr = c.out ? c.i2 : zr; zi = c.out ? 0.0 : zi; dzr = c.out ? c.di2 : dzr; dzi = c.out ? 0.0 : dzi;
+}
 
 // P(lambda_j, theta_a) of one gradient point (form_factor.py:247-296): the forward algebra shared by every kernel that
 // evaluates a point (forward sweep, reverse sweep, one-sweep kernel).  The roundings that reach the spectrum are pinned by
@@ -605,6 +760,79 @@ __device__ __forceinline__ void point_core(const Base& b, const Base& bn, bool h
   p.cei = p.pike * p.D;                                      // :261
   p.opc = opc;
   p.er = p.opc + p.cer;
+  p.ei = FAR ? p.cei : p.cei + cim;                          // :274   (cim = -0: x + -0 = x)
+  const double eps2 = __builtin_fma(p.er, p.er, p.ei * p.ei);
+  p.ieps2 = frcp(eps2);
+  if (FAR) {
+    p.ce2 = 0.0;                                             // (only ever multiplied by gsum = 0 or its adjoint)
+    p.ci2 = p.opc * p.opc;                                   // fma(opc, opc, +0) = round(opc^2)
+    p.N = (p.ci2 * b.F) * L.ivTe;                            // fma(+0, ce2, X) = X
+  } else {
+    p.ce2 = __builtin_fma(p.cer, p.cer, p.cei * p.cei);
+    p.ci2 = __builtin_fma(p.opc, p.opc, cim * cim);
+    p.N = __builtin_fma(gsum, p.ce2, (p.ci2 * b.F) * L.ivTe);  // :282-288
+  }
+  p.t1 = b.ik * p.ieps2;
+  p.S = p.N * p.t1;
+  p.dop = __builtin_fma(b.wd, L.i2wL, 1.0);                  // :291
+}
+// point_core in three steps, for a caller that has two points in flight (k_spectrum_fused, r13_sweep_sched): the very expressions
+// of point_core, which every other kernel keeps (bit for bit: tests/test_sweep_schedule_gpu.py).
+// point_open -- what needs nothing of a base point but 1/k and w - k V: the k factors, xi_i, the asymptote (FAR) or the requests of the
+//   ion lookups, the Doppler factor;
+// point_lookups -- the finish of the ion lookups and of the W lookup (requested by the caller from b.xe), Re chi_e, Re eps;
+// point_close -- what needs F of the point and (xi_e, F) of its right neighbour: the finite difference, |eps|^2 and the spectrum.
+template <int NI, bool ZH, bool FAR = false>
+__device__ __forceinline__ void point_open(const Base& b, const LineS<NI>& L, const Tables& T, PointF<NI>& p, IonCell (&ic)[NI]) {
+#pragma clang fp contract(off)
+  p.ik2 = b.ik * b.ik;
+  p.vph = b.wd * b.ik;
+  double opc = 1.0;   // opc = 1 + Re chi_i
+#pragma unroll
+  for (int s = 0; s < NI; ++s) {
+    p.xi[s] = p.vph * L.ixi[s];                              // :243
+    const double hk = L.hai[s] * p.ik2;
+    p.hk[s] = hk;
+    if (FAR) {
+      const double i2 = frcp(p.xi[s] * p.xi[s]);             // (the very expressions of ion_terms' asymptote branch)
+      p.zr[s] = i2; p.dzr[s] = -2.0 * i2 * i2 * p.xi[s];
+      p.zi[s] = 0.0; p.dzi[s] = 0.0; p.gs[s] = 0.0;
+      opc = __builtin_fma(hk, i2, opc);
+    } else {
+      ion_request<ZH>(T.zp, p.xi[s], ic[s], T.etab);
+    }
+  }
+  p.opc = opc;
+}
+template <int NI, bool ZH, bool FAR = false>
+__device__ __forceinline__ void point_lookups(const LineS<NI>& L, const Tables& T, const IonCell (&ic)[NI], const WCell& wc, PointF<NI>& p) {
+#pragma clang fp contract(off)
+  p.ike2 = L.a_e * p.ik2;
+  p.pike = kPi * p.ike2;
+  double opc = p.opc, cim = 0.0, gsum = 0.0;
+  if (!FAR) {
+#pragma unroll
+    for (int s = 0; s < NI; ++s) {
+      const double hk = p.hk[s];
+      ion_finish<ZH>(ic[s], p.xi[s], p.zr[s], p.zi[s], p.dzr[s], p.dzi[s], p.gs[s], T.etab);
+      opc = __builtin_fma(hk, p.zr[s], opc);                 // :249
+      cim = s == 0 ? hk * p.zi[s] : __builtin_fma(hk, p.zi[s], cim);
+      gsum = s == 0 ? L.cs[s] * p.gs[s] : __builtin_fma(L.cs[s], p.gs[s], gsum);   // :277-280
+    }
+  }
+  p.cim = cim; p.gsum = gsum;
+  w_finish(wc, p.Wl, p.dW);
+  p.cer = -p.ike2 * p.Wl;                                    // :270-271
+  p.opc = opc;
+  p.er = p.opc + p.cer;
+}
+template <int NI, bool FAR = false>
+__device__ __forceinline__ void point_close(const Base& b, const Base& bn, bool has_next, const LineS<NI>& L, PointF<NI>& p) {
+#pragma clang fp contract(off)
+  const double cim = p.cim, gsum = p.gsum;
+  p.idx = has_next ? frcp(bn.xe - b.xe) : 0.0;
+  p.D = has_next ? (bn.F - b.F) * p.idx : 0.0;               // :258-259
+  p.cei = p.pike * p.D;                                      // :261
   p.ei = FAR ? p.cei : p.cei + cim;                          // :274   (cim = -0: x + -0 = x)
   const double eps2 = __builtin_fma(p.er, p.er, p.ei * p.ei);
   p.ieps2 = frcp(eps2);
