@@ -38,6 +38,7 @@ def main():
     b, ob = by_name(b, ob)
     short = {m: m for m in oa}
     print("kernels: parent %d, new %d, same names (without argument lists) in the same order: %s" % (len(oa), len(ob), oa == ob))
+    print("same set of names: %s" % (sorted(oa) == sorted(ob)))
     fam = [m for m in oa if short[m].startswith(FAMILIES)]
     rest = [m for m in oa if m not in fam]
     print("kernels outside the four families with different text:", ", ".join(m for m in rest if a[m]["text"] != b[m]["text"]) or "none")

@@ -56,7 +56,7 @@ __global__ __launch_bounds__(kHalf * (3 - NPAIR), 2) void k_forward_pairs(KStati
   constexpr bool EX = EXM != 0;
   constexpr bool PAD = kSelectFree<NI>;   // the Hermite lookups read the out-of-grid cell that stage_commit writes (k_pairs.inc)
   constexpr int NT = kHalf * (3 - NPAIR);   // threads of the workgroup
-  const bool use_ks = flags & 2, interleaved = flags & 4, own_scalars = flags & 8;
+  const bool use_ks = flags & kFlagKsCache, interleaved = flags & kFlagInterleaved, own_scalars = flags & kFlagOwnScalars;
   const int item = blockIdx.x;
   const int f_il = interleaved ? (int)(item >= K.B) : 0;
   const int b = item - f_il * K.B, tid = threadIdx.x;

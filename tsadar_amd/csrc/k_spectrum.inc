@@ -366,7 +366,7 @@ __global__ __launch_bounds__(2 * kHalf, TSFF_OCC) void k_spectrum(KStatic S, KCa
   //       bit 1: k_s cache present in LDS;
   //       bit 2: interleaved plan -- grid 2B, workgroup f B + b evaluates feature f of lineout b and leaves its part of
   //              the gradient in K.gpart[f][b][:]; k_loss_reduce adds the two parts
-  const bool accumulate = flags & 1, use_ks = flags & 2, interleaved = flags & 4;
+  const bool accumulate = flags & kFlagAccumulate, use_ks = flags & kFlagKsCache, interleaved = flags & kFlagInterleaved;
   // unroll factor of the strip loops: two points in flight help the lean instantiations (-1.6 % plain, -1.9 % with the
   // tangent tables); the heavier ones (table adjoints: 2.0 -> 3.2 ms, more ion species, 512 threads) spill
   constexpr int kQU = (TSFF_QUNROLL > 0) ? TSFF_QUNROLL : ((NI == 1 && GM <= 1 && TPF == kHalf) ? 2 : 1);

@@ -60,7 +60,7 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_fused(KStatic S, KCall K,
   // and behind them, in the same buffer, [items][n_angles][2] the angle records (cos theta_a, w_a pref) of the items
   // flags as in k_spectrum: bit 1 k_s cache in LDS, bit 2 interleaved plan (grid 2B: workgroup f B + b evaluates feature f
   // of lineout b and leaves its part of the gradient in K.gpart[f][b][:]); otherwise grid B, feature f0, grad written
-  const bool use_ks = flags & 2, interleaved = flags & 4;
+  const bool use_ks = flags & kFlagKsCache, interleaved = flags & kFlagInterleaved;
   const int item = blockIdx.x;
   const int f_il = interleaved ? (int)(item >= K.B) : 0;
   const int b = K.b0 + item - f_il * K.B, tid = threadIdx.x;

@@ -65,7 +65,7 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_rows(KStatic S, KCall K, 
   // other XCDs) as MI355X_MICROARCH.md prescribes: every storing wavefront waits for its stores, workgroup barrier, one lane's
   // agent-scope release, then an agent-scope atomic ticket; the workgroup whose ticket is the last one does one agent-scope
   // acquire behind a barrier before anybody loads a row.  The same arithmetic in the same order: the same bits.
-  const bool interleaved = flags & 4;
+  const bool interleaved = flags & kFlagInterleaved;
   const int f_il = interleaved ? (int)(blockIdx.x >= (unsigned)K.B) : 0;
   const int b = interleaved ? (int)blockIdx.x - f_il * K.B : (int)blockIdx.x, tid = threadIdx.x;
   constexpr int TPF = kHalf, NW = TPF / 64;
@@ -114,7 +114,7 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_rows(KStatic S, KCall K, 
   }
   __syncthreads();
   const double cw = -0.5 * L.i2wL * L.i2wL;
-  const bool split = flags & 16;
+  const bool split = flags & kFlagSplit;
   const int rd_first = split ? (int)blockIdx.y : 0, rd_last = split ? (int)blockIdx.y + 1 : ppp;
   for (int rd = rd_first; rd < rd_last; ++rd) {
     // thread ht owns the pairs {2 ht, 2 ht + 1} and {512 + 2 ht, 513 + 2 ht} of the round's 1024 samples (k_spectrum_fused)

@@ -14,6 +14,17 @@ namespace tsff {
 static thread_local std::string g_create_error;
 constexpr size_t kLdsLimit = 160 * 1024;  // LDS per CU (and per workgroup) on gfx950
 
+enum PlanBit : int {   // the bits of TSFF_OPT_LAUNCH_PLAN (tsff.h; 16 and 128 are not in use and are refused)
+  kPlanNoInterleave = 1,   // never interleave the features (both in one workgroup / split as the budget allows), no split forms
+  kPlanTwoSweep = 2,       // never the one-sweep kernel (nor the rows kernel)
+  kPlanNeverThree = 4,     // never three forward workgroups per CU
+  kPlanNoExchange = 8,     // no base-point exchange
+  kPlanGemm128 = 32,       // the 128 x 128 tiling of the W-table GEMM
+  kPlanOnePerCU = 64,      // one workgroup per CU (measurements)
+  kPlanNoPairs = 256,      // never the pair-sweep forward kernel
+};
+constexpr int kPlanBits = kPlanNoInterleave | kPlanTwoSweep | kPlanNeverThree | kPlanNoExchange | kPlanGemm128 | kPlanOnePerCU | kPlanNoPairs;
+
 struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
@@ -173,8 +184,8 @@ struct DevGuard {
   DevGuard& operator=(const DevGuard&) = delete;
 };
 
-// tsff_last_launch: every kernel launch goes through TSFF_LAUNCH / TSFF_LAUNCH0, which append the kernel's name spelled like its
-// demangled device symbol (template arguments included, e.g. "k_spectrum_fused<1, 0, false, true>") to h->launched
+// tsff_last_launch: every kernel launch goes through TSFF_LAUNCH / TSFF_LAUNCH0 / TSFF_LAUNCH_FN, which append the kernel's name
+// spelled like its demangled device symbol (every template argument included, defaults too) to h->launched
 static void note_arg(std::string& s, bool v) { s += v ? "true" : "false"; }
 static void note_arg(std::string& s, int v) {
   char b[16];
@@ -182,9 +193,10 @@ static void note_arg(std::string& s, int v) {
   s += b;
 }
 template <class... A>
-static void note_launch(tsff_handle* h, const char* kernel, A... targs) {
+static const char* note_launch(tsff_handle* h, const char* kernel, A... targs) {   // (returns the name it appended)
   std::string& s = h->launched;
   if (!s.empty()) s += ';';
+  const size_t at = s.size();
   s += kernel;
   if constexpr (sizeof...(A) > 0) {
     int i = 0;
@@ -192,6 +204,7 @@ static void note_launch(tsff_handle* h, const char* kernel, A... targs) {
     ((s += i++ ? ", " : "", note_arg(s, targs)), ...);
     s += '>';
   }
+  return s.c_str() + at;
 }
 #define TSFF_UNPAREN(...) __VA_ARGS__
 // TSFF_LAUNCH(h, k_name, (template arguments), grid, block, smem, stream, kernel arguments...)
@@ -223,23 +236,15 @@ static void note_launch(tsff_handle* h, const char* kernel, A... targs) {
     }                                                                                                                     \
   } while (0)
 
-// kernels with more dynamic LDS than the default limit: the attribute is raised on exactly the instantiation that is launched
-// (TSFF_LAUNCH_LDS(h, k_name, (template arguments), attribute bytes, grid, block, smem, stream, kernel arguments...)); inside
-// graph capture it is left as the eager call the capture contract requires set it
-#define TSFF_LDS_ATTR(h, KFN, BYTES)                                                                                                \
-  do {                                                                                                                              \
-    if (!(h)->capturing)                                                                                                            \
-      TSFF_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(KFN), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(BYTES))); \
-  } while (0)
-#define TSFF_LAUNCH_LDS(h, K, TARGS, BYTES, ...)      \
-  do {                                                \
-    TSFF_LDS_ATTR(h, (K<TSFF_UNPAREN TARGS>), BYTES); \
-    TSFF_LAUNCH(h, K, TARGS, __VA_ARGS__);            \
-  } while (0)
-#define TSFF_LAUNCH0_LDS(h, K, BYTES, ...) \
-  do {                                     \
-    TSFF_LDS_ATTR(h, K, BYTES);            \
-    TSFF_LAUNCH0(h, K, __VA_ARGS__);       \
+// TSFF_LAUNCH_FN(h, selector's pointer, ("k_name", template arguments as run-time values), grid, block, smem, stream, kernel
+// arguments...): the launch of a family whose instantiations a selector names (below).  A null pointer -- the caller asked for
+// a form that does not ship -- is an internal error
+#define TSFF_LAUNCH_FN(h, FN, NAME, ...)                                                                        \
+  do {                                                                                                          \
+    const auto fn__ = (FN);                                                                                     \
+    const char* name__ = note_launch((h), TSFF_UNPAREN NAME);                                                   \
+    if (!fn__) return fail((h), -5, "internal error: %s is not a shipped instantiation", name__);               \
+    hipLaunchKernelGGL(fn__, __VA_ARGS__);                                                                      \
   } while (0)
 
 // runtime value -> template argument: f(std::integral_constant<int, n>) for n in [1, MAX] (nothing otherwise), f(bool_constant)
@@ -253,6 +258,11 @@ static auto with_ion(int n, F&& f) {
 }
 template <class F>
 static auto with_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+template <class F>
+static auto with_bools(bool a, bool b, F&& f) { return with_bool(a, [&](auto A) { return with_bool(b, [&](auto B) { return f(A, B); }); }); }
+template <int V> using IntC = std::integral_constant<int, V>;
+// TSFF_LAUNCH_ION(h, MAX, k_name, grid, ...): k_name<n_ion> for the handle's ion count (1 .. MAX; nothing otherwise)
+#define TSFF_LAUNCH_ION(h, MAX, K, ...) with_ion<MAX>((h)->n_ion, [&](auto N) { TSFF_LAUNCH(h, K, (N.value), __VA_ARGS__); })
 
 // timing ring: one event pair per main-kernel launch (tsff_enable_timing), recorded on the handle's stream
 static size_t timing_slot(const tsff_handle* h) { return h->ev0.empty() ? 0 : h->ev_count % h->ev0.size(); }
@@ -299,70 +309,128 @@ static hipError_t upload(DevBuf& b, const T* src, size_t n) {
   return hipSuccess;
 }
 
+// ---- What ships.  One selector per kernel family: the run-time values of its template arguments -> the instantiation's
+// pointer (all instantiations of a family have one function type), nullptr for a combination that does not ship.  A selector is
+// the only place that names its family's instantiations (one more name, one more kernel in the library): the launches ask it for
+// the pointer (TSFF_LAUNCH_FN), tsff_create walks its domain to raise the LDS limit (raise_lds_limits).
 
-template <int NI>
-static hipError_t set_smem_attrs() {
-  hipError_t e;
-#define TSFF_ATTR(k, n)                                                                                      \
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(n)); \
-  if (e != hipSuccess) return e;
-  TSFF_ATTR((k_spectrum<NI, 0>), kLdsLimit)
-  TSFF_ATTR((k_spectrum<NI, 1>), kLdsLimit)
-  TSFF_ATTR((k_spectrum<NI, 2>), kLdsLimit)
-  TSFF_ATTR((k_spectrum<NI, 1, 1>), kLdsLimit)
-  TSFF_ATTR((k_spectrum<NI, 1, 2>), kLdsLimit)
-  TSFF_ATTR((k_spectrum<NI, 0, 0, kHalf, false>), kLdsLimit)
-  TSFF_ATTR((k_spectrum<NI, 1, 0, kHalf, false>), kLdsLimit)
-  TSFF_ATTR((k_spectrum<NI, 2, 0, kHalf, false>), kLdsLimit)
-  TSFF_ATTR((k_spectrum<NI, 1, 1, kHalf, false>), kLdsLimit)
-  TSFF_ATTR((k_spectrum<NI, 1, 2, kHalf, false>), kLdsLimit)
-  TSFF_ATTR((k_spectrum<NI, 0, 0, 2 * kHalf>), kLdsLimit)
-  TSFF_ATTR((k_spectrum<NI, 1, 0, 2 * kHalf>), kLdsLimit)
-  TSFF_ATTR((k_spectrum<NI, 2, 0, 2 * kHalf>), kLdsLimit)
-  TSFF_ATTR((k_spectrum<NI, 1, 1, 2 * kHalf>), kLdsLimit)
-  TSFF_ATTR((k_spectrum<NI, 1, 2, 2 * kHalf>), kLdsLimit)
-  if constexpr (NI <= kFusedMaxIon) {
-    TSFF_ATTR((k_spectrum_fused<NI, 0, true>), kLdsLimit)
-    TSFF_ATTR((k_spectrum_fused<NI, 0, false>), kLdsLimit)
-    TSFF_ATTR((k_spectrum_fused<NI, 1, true>), kLdsLimit)
-    TSFF_ATTR((k_spectrum_fused<NI, 1, false>), kLdsLimit)
-    TSFF_ATTR((k_spectrum_fused<NI, 0, true, true>), kLdsLimit)
-    TSFF_ATTR((k_spectrum_fused<NI, 0, false, true>), kLdsLimit)
-    TSFF_ATTR((k_spectrum_fused<NI, 1, true, true>), kLdsLimit)
-    TSFF_ATTR((k_spectrum_fused<NI, 1, false, true>), kLdsLimit)
-    TSFF_ATTR((k_forward_pairs<NI, true, 2, 1>), kLdsLimit)
-    TSFF_ATTR((k_forward_pairs<NI, true, 0, 1>), kLdsLimit)
-    TSFF_ATTR((k_forward_pairs<NI, true, 1, 2>), kLdsLimit)
-    TSFF_ATTR((k_forward_pairs<NI, true, 2, 2>), kLdsLimit)
-    TSFF_ATTR((k_forward_pairs<NI, true, 0, 2>), kLdsLimit)
-    TSFF_ATTR((k_forward_pairs<NI, false, 2, 1>), kLdsLimit)
-    TSFF_ATTR((k_forward_pairs<NI, false, 0, 1>), kLdsLimit)
-    TSFF_ATTR((k_forward_pairs<NI, false, 1, 2>), kLdsLimit)
-    TSFF_ATTR((k_forward_pairs<NI, false, 0, 2>), kLdsLimit)
-    TSFF_ATTR((k_spectrum_rows<NI, 0, true, false>), kLdsLimit)
-    TSFF_ATTR((k_spectrum_rows<NI, 0, false, false>), kLdsLimit)
-    TSFF_ATTR((k_spectrum_rows<NI, 1, true, false>), kLdsLimit)
-    TSFF_ATTR((k_spectrum_rows<NI, 1, false, false>), kLdsLimit)
-    TSFF_ATTR((k_spectrum_rows<NI, 0, true, true>), kLdsLimit)
-    TSFF_ATTR((k_spectrum_rows<NI, 0, false, true>), kLdsLimit)
-    TSFF_ATTR((k_spectrum_rows<NI, 1, true, true>), kLdsLimit)
-    TSFF_ATTR((k_spectrum_rows<NI, 1, false, true>), kLdsLimit)
-    TSFF_ATTR((k_spectrum_rows<NI, 0, true, false, true>), kLdsLimit)
-    TSFF_ATTR((k_spectrum_rows<NI, 0, false, false, true>), kLdsLimit)
-    TSFF_ATTR((k_spectrum_rows<NI, 0, true, true, true>), kLdsLimit)
-    TSFF_ATTR((k_spectrum_rows<NI, 0, false, true, true>), kLdsLimit)
+// the two-sweep kernel: (MODE, GM) in {(0, 0), (1, 0), (1, 1), (1, 2), (2, 0)} x (TPF, ZH) in {(256, false), (256, true), (512, true)} --
+// 512 threads per feature ships with the half Z' table only
+static auto spectrum_kernel(int n_ion, int mode, int gm, int tpf, bool zh) {
+  using SpectrumFn = decltype(&k_spectrum<1, 0>);
+  return with_ion<TSFF_MAX_ION>(n_ion, [&](auto N) -> SpectrumFn {
+    auto tz = [&](auto MODE, auto GM) -> SpectrumFn {
+      if (tpf == kHalf) return zh ? &k_spectrum<N.value, MODE.value, GM.value, kHalf, true> : &k_spectrum<N.value, MODE.value, GM.value, kHalf, false>;
+      return tpf == 2 * kHalf && zh ? &k_spectrum<N.value, MODE.value, GM.value, 2 * kHalf, true> : nullptr;
+    };
+    if (mode == 1) return gm == 0 ? tz(IntC<1>(), IntC<0>()) : gm == 1 ? tz(IntC<1>(), IntC<1>()) : gm == 2 ? tz(IntC<1>(), IntC<2>()) : nullptr;
+    if (gm != 0) return nullptr;
+    return mode == 0 ? tz(IntC<0>(), IntC<0>()) : mode == 2 ? tz(IntC<2>(), IntC<0>()) : nullptr;
+  });
+}
+
+// the one-sweep kernel: GM 0 / 1 x ZH x EX, n_ion <= kFusedMaxIon
+static auto fused_kernel(int n_ion, int gm, bool zh, bool ex) {
+  using FusedFn = decltype(&k_spectrum_fused<1, 0, false>);
+  return with_ion<kFusedMaxIon>(n_ion, [&](auto N) -> FusedFn {
+    return with_bools(zh, ex, [&](auto ZH, auto EX) -> FusedFn {
+      return gm == 0 ? &k_spectrum_fused<N.value, 0, ZH.value, EX.value> : gm == 1 ? &k_spectrum_fused<N.value, 1, ZH.value, EX.value> : nullptr;
+    });
+  });
+}
+
+// the forward pair sweep: the nine (ZH, EXM, NPAIR) forms (., 0, 1), (., 2, 1), (., 0, 2), (., 1, 2) and (true, 2, 2).  EXM: 0 no exchange,
+// 1 and 2 the lane exchange (one form since it runs in registers; the planner's two-per-CU and wide / three-per-CU choices keep
+// their numbers, k_forward.inc)
+static auto pairs_kernel(int n_ion, bool zh, int exm, int npair) {
+  using PairsFn = decltype(&k_forward_pairs<1, false, 0, 1>);
+  return with_ion<kFusedMaxIon>(n_ion, [&](auto N) -> PairsFn {
+    auto z = [&](auto EXM, auto NPAIR) -> PairsFn {
+      return zh ? &k_forward_pairs<N.value, true, EXM.value, NPAIR.value> : &k_forward_pairs<N.value, false, EXM.value, NPAIR.value>;
+    };
+    if (npair == 1) return exm == 0 ? z(IntC<0>(), IntC<1>()) : exm == 2 ? z(IntC<2>(), IntC<1>()) : nullptr;
+    if (npair != 2) return nullptr;
+    if (exm == 2) return zh ? &k_forward_pairs<N.value, true, 2, 2> : nullptr;
+    return exm == 0 ? z(IntC<0>(), IntC<2>()) : exm == 1 ? z(IntC<1>(), IntC<2>()) : nullptr;
+  });
+}
+
+// the rows kernel (points_per_pixel > 1): loss + gradient (FWD false) GM 0 / 1 x ZH x EX; forward only (FWD true) with GM 0
+static auto rows_kernel(int n_ion, int gm, bool zh, bool ex, bool fwd) {
+  using RowsFn = decltype(&k_spectrum_rows<1, 0, false, false>);
+  return with_ion<kFusedMaxIon>(n_ion, [&](auto N) -> RowsFn {
+    return with_bools(zh, ex, [&](auto ZH, auto EX) -> RowsFn {
+      if (fwd) return gm == 0 ? &k_spectrum_rows<N.value, 0, ZH.value, EX.value, true> : nullptr;
+      return gm == 0 ? &k_spectrum_rows<N.value, 0, ZH.value, EX.value, false> : gm == 1 ? &k_spectrum_rows<N.value, 1, ZH.value, EX.value, false> : nullptr;
+    });
+  });
+}
+
+// the other families with more than 64 KB of dynamic LDS (the form-factor adjoint: GM 2 with the f_e adjoint; the 2-D kernels: the
+// point groups follow from where the table lives)
+static auto form_factor_kernel(int n_ion) { return with_ion<TSFF_MAX_ION>(n_ion, [](auto N) { return &k_form_factor<N.value>; }); }
+static auto fe_prepare_kernel(int n_ion) { return with_ion<TSFF_MAX_ION>(n_ion, [](auto N) { return &k_fe_prepare<N.value>; }); }
+static auto fe_vectors_kernel(int n_ion) { return with_ion<TSFF_MAX_ION>(n_ion, [](auto N) { return &k_fe_vectors<N.value>; }); }
+static auto hess_pairs_kernel(int n_ion) { return with_ion<TSFF_MAX_ION>(n_ion, [](auto N) { return &k_hess_pairs<N.value>; }); }
+static auto form_factor_adj_kernel(int n_ion, bool grad_fe) {
+  return with_ion<TSFF_MAX_ION>(n_ion, [&](auto N) { return grad_fe ? &k_form_factor_adj<N.value, 2> : &k_form_factor_adj<N.value, 0>; });
+}
+static auto form_factor_2d_kernel(int n_ion, bool lds, bool save) {
+  return with_ion<TSFF_MAX_ION>(n_ion, [&](auto N) {
+    return with_bools(lds, save, [&](auto LDS, auto SAVE) { return &k_form_factor_2d<N.value, LDS.value, LDS.value ? TSFF_2D_GROUPS_LDS : TSFF_2D_GROUPS_L2, SAVE.value>; });
+  });
+}
+static auto form_factor_2d_adj_kernel(int n_ion, bool lds) {
+  return with_ion<TSFF_MAX_ION>(n_ion, [&](auto N) { return lds ? &k_form_factor_2d_adj<N.value, true, TSFF_2D_GROUPS_LDS> : &k_form_factor_2d_adj<N.value, false, TSFF_2D_GROUPS_L2>; });
+}
+
+// More dynamic LDS than the default limit: raised once, at tsff_create, on every instantiation the selectors ship for the
+// handle's ion count and on the single kernels that need it; no launch sets it
+// (the attribute is process-wide, not per handle, and is never lowered: the families sized by the velocity grid get the CU's
+// whole LDS too, so that creating a handle with a smaller grid never lowers the limit another handle's launches rely on)
+static hipError_t raise_lds_limits(int n_ion) {
+  hipError_t e = hipSuccess;
+  auto raise = [&](auto fn, size_t bytes = kLdsLimit) {
+    if (fn && e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  };
+  for (int zh = 0; zh < 2; ++zh) {
+    for (int mode = 0; mode <= 2; ++mode)
+      for (int gm = 0; gm <= 2; ++gm)
+        for (int tpf = kHalf; tpf <= 2 * kHalf; tpf += kHalf) raise(spectrum_kernel(n_ion, mode, gm, tpf, zh));
+    for (int exm = 0; exm <= 2; ++exm)
+      for (int npair = 1; npair <= 2; ++npair) raise(pairs_kernel(n_ion, zh, exm, npair));
+    for (int ex = 0; ex < 2; ++ex)
+      for (int gm = 0; gm <= 1; ++gm) {
+        raise(fused_kernel(n_ion, gm, zh, ex));
+        for (int fwd = 0; fwd < 2; ++fwd) raise(rows_kernel(n_ion, gm, zh, ex, fwd));
+      }
   }
-  // (the attribute is process-wide, not per handle: the families sized by the velocity grid get the CU's whole LDS too, so that
-  // creating a handle with a smaller grid never lowers the limit another handle's launches rely on)
-  TSFF_ATTR((k_form_factor<NI>), kLdsLimit)
-  TSFF_ATTR((k_fe_prepare<NI>), kLdsLimit)
-  TSFF_ATTR((k_fe_vectors<NI>), kLdsLimit)
-  TSFF_ATTR(k_fe_adjoint, kLdsLimit)
-#undef TSFF_ATTR
-  return hipSuccess;
+  for (int a = 0; a < 2; ++a) {
+    raise(form_factor_adj_kernel(n_ion, a));
+    raise(form_factor_2d_adj_kernel(n_ion, a));
+    for (int save = 0; save < 2; ++save) raise(form_factor_2d_kernel(n_ion, a, save));
+  }
+  raise(form_factor_kernel(n_ion));
+  raise(fe_prepare_kernel(n_ion));
+  raise(fe_vectors_kernel(n_ion));
+  raise(hess_pairs_kernel(n_ion));
+  raise(&k_fe_adjoint);
+  raise(&k_ff2d_table_adj);
+  raise(&k_wgemm_w, kWgemmWSmem);
+  return e;
 }
 
 constexpr size_t kRowsScratchMax = (size_t)16 << 30;   // the row scratch of k_spectrum_rows (larger: the two-sweep kernel)
+
+// bytes of the scratch buffers of the spectrum plans (nitems: one-feature workgroups, lineouts x loaded features): plan_spectrum
+// sizes what a plan needs, ensure_workspace the largest a plan can need
+static size_t lbrec_bytes(size_t nitems) { return nitems * (kHalf / 64) * kLBRec * sizeof(double); }
+static size_t lrec_bytes(const KStatic& S, size_t nitems, bool angles) {   // (line records | the one-sweep kernel's angle records)
+  return nitems * (kLineRec + (angles ? 2 * (size_t)S.n_angles : 0)) * sizeof(double);
+}
+static size_t finrec_bytes(const tsff_handle& h, size_t nitems) { return nitems * (2 * (size_t)h.S.NP + 1 + 9 + 4 * (size_t)h.n_ion) * sizeof(double); }
+static size_t gpart_bytes(const KStatic& S, int B) { return (size_t)2 * B * S.NP * sizeof(double); }
+static size_t gradws_bytes(const KStatic& S, int B) { return (size_t)B * S.NP * sizeof(double); }
 
 static int ensure_workspace(tsff_handle* h, int B, bool with_rows = false) {
   if (with_rows && h->S.ppp > 1 && h->S.G == 1 && h->n_ion <= 2) {
@@ -382,11 +450,11 @@ static int ensure_workspace(tsff_handle* h, int B, bool with_rows = false) {
   // arrival resets its counter) at their largest over the plans plan_spectrum can pick for B lineouts -- so that a call on a
   // reserved handle allocates nothing (graph capture)
   const size_t nitems = (size_t)B * ((h->S.load[0] ? 1 : 0) + (h->S.load[1] ? 1 : 0));
-  TSFF_ENSURE(h, h->lbrec, nitems * (kHalf / 64) * kLBRec * sizeof(double));
-  TSFF_ENSURE(h, h->lrec, nitems * (kLineRec + 2 * (size_t)h->S.n_angles) * sizeof(double));
-  TSFF_ENSURE(h, h->finrec, nitems * (2 * (size_t)h->S.NP + 1 + 9 + 4 * (size_t)h->n_ion) * sizeof(double));
-  TSFF_ENSURE(h, h->gpart, (size_t)2 * B * h->S.NP * sizeof(double));
-  TSFF_ENSURE(h, h->gradws, (size_t)B * h->S.NP * sizeof(double));
+  TSFF_ENSURE(h, h->lbrec, lbrec_bytes(nitems));
+  TSFF_ENSURE(h, h->lrec, lrec_bytes(h->S, nitems, true));
+  TSFF_ENSURE(h, h->finrec, finrec_bytes(*h, nitems));
+  TSFF_ENSURE(h, h->gpart, gpart_bytes(h->S, B));
+  TSFF_ENSURE(h, h->gradws, gradws_bytes(h->S, B));
   TSFF_ENSURE(h, h->act, kNP_MAX * sizeof(int32_t));
   if (h->tickets.bytes < 1024 * sizeof(unsigned)) {
     TSFF_ENSURE(h, h->tickets, 1024 * sizeof(unsigned));
@@ -411,9 +479,8 @@ static int launch_prepare(tsff_handle* h, const double* fe_dev, int mode, const 
                           double2* ht, double* W, double* fe_out) {
   const int qsplit = slots >= 64 ? 1 : (slots >= 8 ? 4 : 16);
   dim3 grid(slots, qsplit), block(kThreads);
-  with_ion<TSFF_MAX_ION>(h->n_ion, [&](auto N) {
-    TSFF_LAUNCH(h, k_fe_prepare, (N.value), grid, block, h->smem_prepare, h->stream, h->S, fe_dev, mode, params, ht, W, fe_out);
-  });
+  TSFF_LAUNCH_FN(h, fe_prepare_kernel(h->n_ion), ("k_fe_prepare", h->n_ion), grid, block, h->smem_prepare, h->stream, h->S, fe_dev, mode,
+                 params, ht, W, fe_out);
   TSFF_HIP(h, hipGetLastError());
   return 0;
 }
@@ -449,16 +516,15 @@ static int launch_tables_block(tsff_handle* h, const double* params, const doubl
   double* X_b = h->X.as<double>() + (size_t)b0 * 4 * kNXi1; double* cst_b = h->cst.as<double>() + (size_t)b0 * 2;
   double* W_b = h->W.as<double>() + (size_t)b0 * kNXi2; double* Wm_b = h->Wm.as<double>() + (size_t)b0 * kNXi2;
   dim3 grid(nb), block(kThreads);
-  with_ion<TSFF_MAX_ION>(h->n_ion, [&](auto N) {
-    TSFF_LAUNCH(h, k_fe_vectors, (N.value), grid, block, h->smem_vectors, st, h->S, fe_b, h->fe_mode, par_b, ht_b, htm_b, X_b, cst_b);
-  });
+  TSFF_LAUNCH_FN(h, fe_vectors_kernel(h->n_ion), ("k_fe_vectors", h->n_ion), grid, block, h->smem_vectors, st, h->S, fe_b, h->fe_mode, par_b,
+                 ht_b, htm_b, X_b, cst_b);
   TSFF_HIP(h, hipGetLastError());
   const int nc = h->fe_mode == TSFF_FE_DLM ? 4 : 2;  // explicit f_e tables carry no tangent vectors
   const int nM = (nb + kGM / nc - 1) / (kGM / nc), nQ = (kNXi2 + kGN - 1) / kGN;
   dim3 ggrid(8 * ((nM + 7) / 8) * nQ);
-  if (nc == 4 && !(h->plan & 32)) {   // 128 x 144 tiles: no partial last round (k_wgemm_w); plan bit 5: the 128 x 128 form
+  if (nc == 4 && !(h->plan & kPlanGemm128)) {   // 128 x 144 tiles: no partial last round (k_wgemm_w); plan bit 5: the 128 x 128 form
     dim3 wgrid(8 * ((nM + 7) / 8) * ((kNXi2 + kGNw - 1) / kGNw));
-    TSFF_LAUNCH0_LDS(h, k_wgemm_w, kWgemmWSmem, wgrid, block, kWgemmWSmem, st, h->S.lg, X_b, cst_b, h->S.xi2, nb, W_b, Wm_b, h->kw_lo, h->kw_hi);
+    TSFF_LAUNCH0(h, k_wgemm_w, wgrid, block, kWgemmWSmem, st, h->S.lg, X_b, cst_b, h->S.xi2, nb, W_b, Wm_b, h->kw_lo, h->kw_hi);
   } else if (nc == 4)
     TSFF_LAUNCH(h, k_wgemm, (4), ggrid, block, 0, st, h->S.lg, X_b, cst_b, h->S.xi2, nb, W_b, Wm_b, h->kw_lo, h->kw_hi);
   else
@@ -518,8 +584,9 @@ static int prepare_tables(tsff_handle* h, const double* params, const double* fe
 //   split: one 512-thread launch per feature, the second accumulating into grad (LDS budget exceeded: points_per_pixel 5).
 // MODE 1 runs the one-sweep kernel k_spectrum_fused instead wherever its restrictions hold (see plan_spectrum).
 // One loaded feature: 256-thread workgroups when two fit a CU, else 512.  The k_s cache is used when it still fits.
-// TSFF_OPT_LAUNCH_PLAN (bit mask): bit 0 never interleave (both features in one workgroup / split as the budget allows),
-// bit 1 never use the one-sweep kernel.
+// The dispatch: MODE (0 forward, 1 loss + gradient, 2 array loss) and GM (0 plasma parameters, 1 + the DLM order, 2 + the table
+// adjoints) are run-time arguments.  plan_spectrum decides the form and its template arguments as fields of the plan (the
+// TSFF_OPT_LAUNCH_PLAN bits: PlanBit); launch_spectrum asks the form's selector for that instantiation and launches the pointer.
 enum class SpectrumForm { rows, pairs, one_sweep, two_sweep };
 
 struct SpectrumPlan {
@@ -533,37 +600,35 @@ struct SpectrumPlan {
   size_t rows = 0, tickets = 0, gpart = 0, lbrec = 0, lrec = 0, finrec = 0;   // bytes of the buffers the form needs (0: none)
 };
 
-template <int V> using IntC = std::integral_constant<int, V>;
-
-// the launch plan of one launch_spectrum call: decisions only, nothing allocated or launched
-template <int MODE, int GM>
-static SpectrumPlan plan_spectrum(const tsff_handle& h, int B, int nload) {
+// the launch plan of one launch_spectrum call: decisions only, nothing allocated or launched (MODE, GM: spelled like the template
+// arguments they select)
+static SpectrumPlan plan_spectrum(const tsff_handle& h, const int MODE, const int GM, int B, int nload) {
   const KStatic& S = h.S;
   const size_t nitems = (size_t)B * nload;   // one-feature workgroups
-  const size_t finrec = nitems * (2 * (size_t)S.NP + 1 + 9 + 4 * (size_t)h.n_ion) * sizeof(double);
+  const size_t finrec = finrec_bytes(h, nitems);
   // points_per_pixel > 1, loss + gradient: the one-sweep kernel with its rows in a global scratch array (k_spectrum_rows.inc) -- one
   // launch of 256-thread one-feature workgroups, two per CU (the full Z' table if that still fits, else the half table); the scratch
   // is capped at kRowsScratchMax (larger batches fall back to the two-sweep kernel).  Forward only: the forward form of the rounds
   // kernel (FWD) -- two 256-thread workgroups per CU and, for small batches, the rounds of a lineout on separate workgroups --
   // instead of k_spectrum MODE 0's one 512-thread workgroup per CU
-  if constexpr ((MODE == 1 && GM <= 1) || (MODE == 0 && GM == 0)) {
-    if (S.G == 1 && S.ppp > 1 && h.n_ion <= kFusedMaxIon && !(h.plan & 2) && !S.raw[0] && !S.raw[1] && nload >= 1) {
-      constexpr bool FWD = MODE == 0;
+  if ((MODE == 1 && GM <= 1) || (MODE == 0 && GM == 0)) {
+    if (S.G == 1 && S.ppp > 1 && h.n_ion <= kFusedMaxIon && !(h.plan & kPlanTwoSweep) && !S.raw[0] && !S.raw[1] && nload >= 1) {
+      const bool FWD = MODE == 0;
       SpectrumPlan p;
       p.form = SpectrumForm::rows;
       // (the exchange's 15 KB -- this kernel keeps the form through LDS -- live in the sweep's part of the LDS: free whenever the
       //  chain's buffers are the larger part)
       const size_t exd = kExLdsDoubles;
-      p.ex = S.n_angles <= 16 && !(h.plan & 8) && 2 * sizeof(double) * rows_smem_doubles(S, GM, true, exd) <= kLdsLimit;
+      p.ex = S.n_angles <= 16 && !(h.plan & kPlanNoExchange) && 2 * sizeof(double) * rows_smem_doubles(S, GM, true, exd) <= kLdsLimit;
       p.zh = 2 * sizeof(double) * rows_smem_doubles(S, GM, false, p.ex ? exd : 0) > kLdsLimit;
       p.smem = sizeof(double) * rows_smem_doubles(S, GM, p.zh, p.ex ? exd : 0);
       p.interleaved = nload == 2;
       p.rows = nitems * (FWD ? 1 : rows_components(h.n_ion, GM)) * (size_t)S.npts * sizeof(double);   // (forward: the value only)
       if (2 * p.smem <= kLdsLimit && (FWD || p.rows <= kRowsScratchMax)) {
         // small batches: one workgroup per (lineout, feature, ROUND), the last one of a (lineout, feature) runs the chain
-        p.split = nitems * 2 <= (size_t)h.ncu2d() && !(h.plan & 1);
+        p.split = nitems * 2 <= (size_t)h.ncu2d() && !(h.plan & kPlanNoInterleave);
         p.tickets = p.split ? nitems * sizeof(unsigned) : 0;
-        if (!FWD && p.interleaved) p.gpart = (size_t)2 * B * S.NP * sizeof(double);
+        if (!FWD && p.interleaved) p.gpart = gpart_bytes(S, B);
         p.grid = p.split ? dim3((unsigned)nitems, (unsigned)S.ppp) : dim3((unsigned)nitems);
         p.block = dim3(kHalf);
         return p;
@@ -572,14 +637,14 @@ static SpectrumPlan plan_spectrum(const tsff_handle& h, int B, int nload) {
   }
   // forward only (tsff_forward), one gradient point, one point per pixel: the pair-sweep kernel (k_forward.inc) -- two workgroups
   // per item while the whole batch fits one dispatch round of two items per CU (configs[1]), else one; plan bit 8 (256): never
-  if constexpr (MODE == 0 && GM == 0) {
-    if (S.G == 1 && S.ppp == 1 && h.n_ion <= kFusedMaxIon && !(h.plan & 256) && nload >= 1) {
+  if (MODE == 0 && GM == 0) {
+    if (S.G == 1 && S.ppp == 1 && h.n_ion <= kFusedMaxIon && !(h.plan & kPlanNoPairs) && nload >= 1) {
       SpectrumPlan p;
       p.form = SpectrumForm::pairs;
-      p.ex = S.n_angles <= 16 && !(h.plan & 8);
+      p.ex = S.n_angles <= 16 && !(h.plan & kPlanNoExchange);
       p.interleaved = nload == 2;
       // 512 threads per item (one pair per thread) while the batch fits one round of two items per CU
-      p.wide = nitems <= 2 * (size_t)h.ncu2d() && !(h.plan & 1);
+      p.wide = nitems <= 2 * (size_t)h.ncu2d() && !(h.plan & kPlanNoInterleave);
       // LDS of the forward workgroup (smem_fwd_doubles): two per CU (the full Z' table and the k_s cache as they fit), or -- batches
       // of more than two items per CU -- THREE per CU with the half Z' table and no k_s cache (plan bit 2 (4): never).  EXM 1 and 2
       // cost the same LDS: the exchange itself is in registers, only the unit-boundary points live in LDS
@@ -587,12 +652,12 @@ static SpectrumPlan plan_spectrum(const tsff_handle& h, int B, int nload) {
       const bool zh2 = 2 * sizeof(double) * smem_fwd_doubles(S, false, false, exd2) > kLdsLimit;
       const bool ks2 = 2 * sizeof(double) * smem_fwd_doubles(S, true, zh2, exd2) <= kLdsLimit;
       const size_t smem3 = sizeof(double) * smem_fwd_doubles(S, false, true, exd);
-      p.three = !p.wide && !(h.plan & 4) && nitems > 2 * (size_t)h.ncu2d() && 3 * smem3 <= kLdsLimit;
+      p.three = !p.wide && !(h.plan & kPlanNeverThree) && nitems > 2 * (size_t)h.ncu2d() && 3 * smem3 <= kLdsLimit;
       p.zh = p.three || zh2;
       p.ks = !p.three && ks2;
       p.smem = p.three ? smem3 : sizeof(double) * smem_fwd_doubles(S, ks2, zh2, exd);
       if (p.three || 2 * sizeof(double) * smem_fwd_doubles(S, ks2, zh2, p.wide ? exd : exd2) <= kLdsLimit) {
-        if (!p.wide) { p.lrec = nitems * kLineRec * sizeof(double); p.finrec = finrec; }
+        if (!p.wide) { p.lrec = lrec_bytes(S, nitems, false); p.finrec = finrec; }
         p.grid = dim3((unsigned)nitems);
         p.block = dim3(p.wide ? 2 * kHalf : kHalf);
         return p;
@@ -603,12 +668,12 @@ static SpectrumPlan plan_spectrum(const tsff_handle& h, int B, int nload) {
   // the one-sweep kernel (k_spectrum_fused.inc) wherever its restrictions hold: loss + gradient, one gradient point, one point
   // per pixel, 256-thread one-feature workgroups, no table adjoints; with the base-point exchange (EX: lane to lane in registers,
   // 5 KB of LDS for the unit-boundary points, n_angles <= 16) when two such workgroups still fit a CU (the half Z' table makes room)
-  const bool fused_ok = MODE == 1 && GM <= 1 && S.G == 1 && S.ppp == 1 && h.n_ion <= kFusedMaxIon && !(h.plan & 2);
-  p.ex = fused_ok && S.n_angles <= 16 && !(h.plan & 8) && 2 * sizeof(double) * smem_doubles(S, 1, GM, false, true, true, kExLdsDoubles) <= kLdsLimit;
+  const bool fused_ok = MODE == 1 && GM <= 1 && S.G == 1 && S.ppp == 1 && h.n_ion <= kFusedMaxIon && !(h.plan & kPlanTwoSweep);
+  p.ex = fused_ok && S.n_angles <= 16 && !(h.plan & kPlanNoExchange) && 2 * sizeof(double) * smem_doubles(S, 1, GM, false, true, true, kExLdsDoubles) <= kLdsLimit;
   // forward-only calls need 139 VGPRs: THREE one-feature workgroups fit a CU's registers, and its LDS too with the half Z' table
   // and without the k_s cache -- 3 wavefronts per SIMD hide the lookups' latency better than 2 (plan bit 2 (4): never); only when
   // there are more workgroups than two per CU (a grid that fits at two per CU gains nothing and pays for the half table)
-  p.three = MODE == 0 && !(h.plan & 4) && (long)nitems > 2L * h.ncu2d() &&
+  p.three = MODE == 0 && !(h.plan & kPlanNeverThree) && (long)nitems > 2L * h.ncu2d() &&
             3 * sizeof(double) * smem_doubles(S, 1, GM, false, alias_xy(S, 256), true) <= kLdsLimit;
   // zh: Z' table held for xi >= 0 only, 13 KB less LDS for about 1 % more instructions -- used only when the full table would
   // cost the two-workgroups-per-CU plan
@@ -620,7 +685,7 @@ static SpectrumPlan plan_spectrum(const tsff_handle& h, int B, int nload) {
     return sizeof(double) * smem_doubles(S, nf, GM, ks, alias_xy(S, tpf), p.zh, (p.ex && nf == 1 && tpf == 256) ? exc : 0);
   };
   const bool two_per_cu = 2 * bytes(1, false, 256) <= kLdsLimit;   // two one-feature workgroups per CU
-  p.interleaved = nload == 2 && two_per_cu && !(h.plan & 1);
+  p.interleaved = nload == 2 && two_per_cu && !(h.plan & kPlanNoInterleave);
   p.nfeat = nload;
   if (p.interleaved || bytes(p.nfeat, false, 256) > kLdsLimit) p.nfeat = 1;
   const bool small_wg = p.nfeat == 1 && two_per_cu;   // 256-thread one-feature workgroups
@@ -628,16 +693,16 @@ static SpectrumPlan plan_spectrum(const tsff_handle& h, int B, int nload) {
   const size_t budget = small_wg ? kLdsLimit / (p.three ? 3 : 2) : kLdsLimit;
   p.ks = bytes(p.nfeat, true, p.tpf) <= budget;
   p.smem = bytes(p.nfeat, p.ks, p.tpf, kExDoubles);
-  if ((h.plan & 64) && p.smem <= kLdsLimit / 2) p.smem = kLdsLimit / 2 + 1024;   // (experiments: one workgroup per CU)
+  if ((h.plan & kPlanOnePerCU) && p.smem <= kLdsLimit / 2) p.smem = kLdsLimit / 2 + 1024;   // (experiments: one workgroup per CU)
   // (the one-sweep kernel: also no second accumulating launch)
   const int nlaunch = p.interleaved ? 1 : nload / p.nfeat;
   if (fused_ok && small_wg && nlaunch == 1) {   // it leaves per-wavefront records; k_fused_finish turns them into the gradient
     p.form = SpectrumForm::one_sweep;
-    p.lbrec = nitems * (kHalf / 64) * kLBRec * sizeof(double);
-    p.lrec = nitems * (kLineRec + 2 * (size_t)S.n_angles) * sizeof(double);   // (line records | angle records)
+    p.lbrec = lbrec_bytes(nitems);
+    p.lrec = lrec_bytes(S, nitems, true);
     p.finrec = finrec;
   } else if (p.interleaved && MODE == 1) {
-    p.gpart = (size_t)2 * B * S.NP * sizeof(double);
+    p.gpart = gpart_bytes(S, B);
   }
   p.grid = dim3(p.interleaved ? 2 * B : B);
   p.block = dim3(small_wg ? kHalf : 2 * kHalf);
@@ -647,37 +712,31 @@ static SpectrumPlan plan_spectrum(const tsff_handle& h, int B, int nload) {
 // the one-sweep kernel k_spectrum_fused (GM: 0 plasma parameters, 1 + the DLM order): the lineout scalars of every item, one
 // thread each (k_fused_prep), then one launch over the whole batch, or -- the pipelined DLM plan -- one per column block, each
 // behind the event of its tables
-template <int GM>
-static void launch_fused(tsff_handle* h, const KCall& K, const SpectrumPlan& p, int f0, int flags, int nload) {
-  with_ion<kFusedMaxIon>(h->n_ion, [&](auto N) {
-    const double* lrec = h->lrec.as<double>();
-    TSFF_LAUNCH(h, k_fused_prep, (N.value), dim3((p.grid.x + 63) / 64), dim3(64), 0, h->stream, h->S, K.params, K.B, f0, nload,
-                h->lrec.as<double>(), h->finrec.as<double>(), h->lrec.as<double>() + (size_t)K.B * nload * kLineRec);   // (the angle records: behind the line records of all K.B * nload items)
-    const int nblk = h->pipe_nblk > 1 ? h->pipe_nblk : 1;
-    for (int i = 0; i < nblk; ++i) {
-      KCall Kb = K;
-      dim3 g = p.grid;
-      if (nblk > 1) {
-        Kb.b0 = i * h->pipe_nb; Kb.B = std::min(h->pipe_nb, K.B - Kb.b0);
-        g = dim3((unsigned)(Kb.B * nload));
-        (void)hipStreamWaitEvent(h->stream, h->blk_ev[i], 0);
-      }
-      with_bool(p.zh, [&](auto ZH) {
-        with_bool(p.ex, [&](auto EX) {
-          TSFF_LAUNCH(h, k_spectrum_fused, (N.value, GM, ZH.value, EX.value), g, p.block, p.smem, h->stream, h->S, Kb, f0, flags, lrec);
-        });
-      });
+static int launch_fused(tsff_handle* h, int gm, const KCall& K, const SpectrumPlan& p, int f0, int flags, int nload) {
+  const double* lrec = h->lrec.as<double>();
+  TSFF_LAUNCH_ION(h, kFusedMaxIon, k_fused_prep, dim3((p.grid.x + 63) / 64), dim3(64), 0, h->stream, h->S, K.params, K.B, f0, nload,
+                  h->lrec.as<double>(), h->finrec.as<double>(), h->lrec.as<double>() + (size_t)K.B * nload * kLineRec);   // (the angle records: behind the line records of all K.B * nload items)
+  const int nblk = h->pipe_nblk > 1 ? h->pipe_nblk : 1;
+  for (int i = 0; i < nblk; ++i) {
+    KCall Kb = K;
+    dim3 g = p.grid;
+    if (nblk > 1) {
+      Kb.b0 = i * h->pipe_nb; Kb.B = std::min(h->pipe_nb, K.B - Kb.b0);
+      g = dim3((unsigned)(Kb.B * nload));
+      (void)hipStreamWaitEvent(h->stream, h->blk_ev[i], 0);
     }
-  });
+    TSFF_LAUNCH_FN(h, fused_kernel(h->n_ion, gm, p.zh, p.ex), ("k_spectrum_fused", h->n_ion, gm, p.zh, p.ex), g, p.block, p.smem, h->stream,
+                   h->S, Kb, f0, flags, lrec);
+  }
   h->pipe_nblk = 0;
+  return 0;
 }
 
-// the plan launch_spectrum<MODE, GM> runs for B lineouts, its LDS budget checked and every scratch buffer of it sized (the
+// the plan launch_spectrum(mode, gm) runs for B lineouts, its LDS budget checked and every scratch buffer of it sized (the
 // arrival counters zeroed when they grow) -- before a call enqueues anything, so that a refusal leaves nothing behind
-template <int MODE, int GM>
-static int size_plan(tsff_handle* h, int B, SpectrumPlan& p) {
+static int size_plan(tsff_handle* h, int mode, int gm, int B, SpectrumPlan& p) {
   const int nload = (h->S.load[0] ? 1 : 0) + (h->S.load[1] ? 1 : 0);
-  p = plan_spectrum<MODE, GM>(*h, B, nload);
+  p = plan_spectrum(*h, mode, gm, B, nload);
   if (p.smem > kLdsLimit) return fail(h, TSFF_ERR_LDS, "LDS budget exceeded (%zu B): reduce npts or the IRF cutoff", p.smem);
   if (p.rows) TSFF_ENSURE(h, h->rows, p.rows);
   if (p.tickets && h->tickets.bytes < p.tickets) {
@@ -691,11 +750,11 @@ static int size_plan(tsff_handle* h, int B, SpectrumPlan& p) {
   return 0;
 }
 
-// the launches of a plan size_plan<MODE, GM> made for K.B lineouts: the KCall's pointers into the plan's buffers (K.gpart when
-// p.gpart, K.lbrec for the one-sweep form), the pipe, the timing ring, the kernels.  Allocates and refuses nothing.
-template <int MODE, int GM = 0>
-static int launch_spectrum(tsff_handle* h, KCall& K, const SpectrumPlan& p, const uint8_t* gmask = nullptr, double* grad = nullptr) {
-  const int nload = (h->S.load[0] ? 1 : 0) + (h->S.load[1] ? 1 : 0);
+// the launches of a plan size_plan(mode, gm) made for K.B lineouts: the KCall's pointers into the plan's buffers (K.gpart when
+// p.gpart, K.lbrec for the one-sweep form), the pipe, the timing ring, the kernels.  Allocates and refuses nothing; a form that
+// does not ship for (mode, gm) -- the planner never picks one -- gets no pointer from its selector: -5.
+static int launch_spectrum(tsff_handle* h, int mode, int gm, KCall& K, const SpectrumPlan& p, const uint8_t* gmask = nullptr, double* grad = nullptr) {
+  const int nload = (h->S.load[0] ? 1 : 0) + (h->S.load[1] ? 1 : 0), n = h->n_ion;
   // the one-sweep kernel takes the tables block by block; every other form waits for all of them (a no-op for forward calls:
   // only the loss + gradient builds its tables on the second stream)
   if (p.form != SpectrumForm::one_sweep)
@@ -706,53 +765,38 @@ static int launch_spectrum(tsff_handle* h, KCall& K, const SpectrumPlan& p, cons
   const int nlaunch = p.interleaved ? 1 : nload / p.nfeat;
   for (int l = 0; l < nlaunch; ++l) {
     const int f0 = nlaunch == 2 ? l : (h->S.load[0] ? 0 : 1);
-    const int flags = (l > 0 ? 1 : 0) | (p.ks ? 2 : 0) | (p.interleaved ? 4 : 0) | (p.wide ? 8 : 0) | (p.split ? 16 : 0);
+    const int flags = (l > 0 ? kFlagAccumulate : 0) | (p.ks ? kFlagKsCache : 0) | (p.interleaved ? kFlagInterleaved : 0) |
+                      (p.wide ? kFlagOwnScalars : 0) | (p.split ? kFlagSplit : 0);
     switch (p.form) {
-      case SpectrumForm::rows:
-        if constexpr ((MODE == 1 && GM <= 1) || (MODE == 0 && GM == 0))
-          with_ion<kFusedMaxIon>(h->n_ion, [&](auto N) {
-            with_bool(p.zh, [&](auto ZH) {
-              with_bool(p.ex, [&](auto EX) {
-                TSFF_LAUNCH(h, k_spectrum_rows, (N.value, GM, ZH.value, EX.value, MODE == 0), p.grid, p.block, p.smem, h->stream, h->S,
-                            K, f0, flags, gmask, grad, h->rows.as<double>(), p.split ? h->tickets.as<unsigned>() : nullptr);
-              });
-            });
-          });
+      case SpectrumForm::rows: {   // (loss + gradient, or its forward form)
+        const bool fwd = mode == 0;
+        TSFF_LAUNCH_FN(h, mode <= 1 ? rows_kernel(n, gm, p.zh, p.ex, fwd) : nullptr, ("k_spectrum_rows", n, gm, p.zh, p.ex, fwd), p.grid,
+                       p.block, p.smem, h->stream, h->S, K, f0, flags, gmask, grad, h->rows.as<double>(),
+                       p.split ? h->tickets.as<unsigned>() : nullptr);
         break;
-      case SpectrumForm::pairs:
-        if constexpr (MODE == 0 && GM == 0)
-          with_ion<kFusedMaxIon>(h->n_ion, [&](auto N) {
-            double* lrec = h->lrec.as<double>();
-            auto pairs = [&](auto ZH, auto EXM, auto NPAIR) {
-              TSFF_LAUNCH(h, k_forward_pairs, (N.value, ZH.value, EXM.value, NPAIR.value), p.grid, p.block, p.smem, h->stream, h->S, K,
-                          f0, flags, lrec);
-            };
-            // the nine shipped (ZH, EXM, NPAIR) forms; EXM: 0 no exchange, 1 and 2 the lane exchange (one form since it runs in
-            // registers; the planner's two-per-CU and wide / three-per-CU choices keep their numbers, k_forward.inc)
-            if (p.wide) {
-              with_bool(p.zh, [&](auto ZH) { p.ex ? pairs(ZH, IntC<2>(), IntC<1>()) : pairs(ZH, IntC<0>(), IntC<1>()); });
-            } else {
-              TSFF_LAUNCH(h, k_fused_prep, (N.value), dim3((p.grid.x + 63) / 64), dim3(64), 0, h->stream, h->S, K.params, K.B, f0, nload,
+      }
+      case SpectrumForm::pairs: {   // (forward only)
+        double* lrec = h->lrec.as<double>();
+        // the exchange goes by 2 wide and with three workgroups per CU (which has the half Z' table), else by 1 (pairs_kernel)
+        const bool three_ex = !p.wide && p.three && p.ex;
+        const bool zh = three_ex || p.zh;
+        const int exm = !p.ex ? 0 : (p.wide || three_ex) ? 2 : 1, npair = p.wide ? 1 : 2;
+        if (!p.wide)
+          TSFF_LAUNCH_ION(h, kFusedMaxIon, k_fused_prep, dim3((p.grid.x + 63) / 64), dim3(64), 0, h->stream, h->S, K.params, K.B, f0, nload,
                           lrec, h->finrec.as<double>(), (double*)nullptr);
-              if (p.three && p.ex) pairs(std::true_type(), IntC<2>(), IntC<2>());
-              else with_bool(p.zh, [&](auto ZH) { p.ex ? pairs(ZH, IntC<1>(), IntC<2>()) : pairs(ZH, IntC<0>(), IntC<2>()); });
-            }
-          });
+        TSFF_LAUNCH_FN(h, mode == 0 && gm == 0 ? pairs_kernel(n, zh, exm, npair) : nullptr, ("k_forward_pairs", n, zh, exm, npair), p.grid,
+                       p.block, p.smem, h->stream, h->S, K, f0, flags, lrec);
         break;
-      case SpectrumForm::one_sweep:
-        if constexpr (MODE == 1 && GM <= 1) launch_fused<GM>(h, K, p, f0, flags, nload);
+      }
+      case SpectrumForm::one_sweep:   // (loss + gradient)
+        if (int rc = launch_fused(h, mode == 1 ? gm : -1, K, p, f0, flags, nload)) return rc;
         break;
-      case SpectrumForm::two_sweep:
-        with_ion<TSFF_MAX_ION>(h->n_ion, [&](auto N) {
-          auto spectrum = [&](auto TPF, auto ZH) {
-            TSFF_LAUNCH(h, k_spectrum, (N.value, MODE, GM, TPF.value, ZH.value), p.grid, p.block, p.smem, h->stream, h->S, K, f0,
-                        p.nfeat, flags, gmask, grad);
-          };
-          // (512 threads per feature ships with the half Z' table only)
-          if (p.tpf == kHalf) with_bool(p.zh, [&](auto ZH) { spectrum(IntC<kHalf>(), ZH); });
-          else spectrum(IntC<2 * kHalf>(), std::true_type());
-        });
+      case SpectrumForm::two_sweep: {
+        const bool zh = p.tpf == kHalf ? p.zh : true;   // (512 threads per feature ships with the half Z' table only)
+        TSFF_LAUNCH_FN(h, spectrum_kernel(n, mode, gm, p.tpf, zh), ("k_spectrum", n, mode, gm, p.tpf, zh), p.grid, p.block, p.smem,
+                       h->stream, h->S, K, f0, p.nfeat, flags, gmask, grad);
         break;
+      }
     }
     TSFF_HIP(h, hipGetLastError());
   }
@@ -1027,9 +1071,7 @@ int tsff_create(const tsff_config* c, tsff_handle** out) {
   h->smem_prepare = sizeof(double) * (2 * (size_t)S.nvx + 3 * kNXi1 + 8) + sizeof(double2) * S.nvx;
   h->smem_vectors = sizeof(double2) * 6 * (size_t)S.nvx + sizeof(double) * (2 * (size_t)S.nvx + 4 * kNXi1 + 8);
   h->smem_adjoint = sizeof(double2) * 3 * (size_t)S.nvx + sizeof(double) * (2 * (size_t)S.nvx + 4 * kNXi1 + 8);
-  TSFF_HIPC(with_ion<TSFF_MAX_ION>(c->n_ion, [&](auto N) {
-    return set_smem_attrs<N.value>();
-  }));
+  TSFF_HIPC(raise_lds_limits(c->n_ion));
   // shared distribution function: build its tables once
   TSFF_HIPC(h->ht.ensure((size_t)S.nvx * sizeof(double2)));
   TSFF_HIPC(h->W.ensure((size_t)kNXi2 * sizeof(double)));
@@ -1086,7 +1128,7 @@ int tsff_set_stream(tsff_handle* h, void* s) {
 int tsff_set_option(tsff_handle* h, int32_t key, int32_t value) {
   if (!h) return -1;
   if (key == TSFF_OPT_LAUNCH_PLAN) {
-    if (value < 0 || value > 511 || (value & 16) || (value & 128)) return fail(h, -2, "TSFF_OPT_LAUNCH_PLAN is a bit mask: 1 never interleave the features, 2 never use the one-sweep kernel, 4 never three forward workgroups per CU, 8 no base-point exchange in the one-sweep kernel, 32 the 128 x 128 tiling of the W-table GEMM, 64 one workgroup per CU (measurements), 256 never the pair-sweep forward kernel");
+    if (value < 0 || (value & ~kPlanBits)) return fail(h, -2, "TSFF_OPT_LAUNCH_PLAN is a bit mask: 1 never interleave the features, 2 never use the one-sweep kernel, 4 never three forward workgroups per CU, 8 no base-point exchange in the one-sweep kernel, 32 the 128 x 128 tiling of the W-table GEMM, 64 one workgroup per CU (measurements), 256 never the pair-sweep forward kernel");
     h->plan = value;
     return 0;
   }
@@ -1264,10 +1306,8 @@ static int form_factor_enqueue(tsff_handle* h, const FormFactorPlan& p, const do
   KCall K{};
   K.params = phys; K.B = p.B;
   if (int rc = prepare_tables(h, phys, fe, p.B, K)) return rc;
-  with_ion<TSFF_MAX_ION>(h->n_ion, [&](auto N) {
-    TSFF_LAUNCH(h, k_form_factor, (N.value), p.grid, dim3(kThreads), h->smem_spectrum, h->stream, h->S, K, p.feature,
-                h->S.omgs[p.feature], h->S.npts, P);
-  });
+  TSFF_LAUNCH_FN(h, form_factor_kernel(h->n_ion), ("k_form_factor", h->n_ion), p.grid, dim3(kThreads), h->smem_spectrum, h->stream, h->S, K,
+                 p.feature, h->S.omgs[p.feature], h->S.npts, P);
   TSFF_HIP(h, hipGetLastError());
   return 0;
 }
@@ -1314,18 +1354,12 @@ static int form_factor_adj_enqueue(tsff_handle* h, const FormFactorAdjPlan& p, c
   if (rc) return rc;
   if (p.grad_fe) fe_tail_outputs(h, K, B);
   dim3 grid(B, p.nchunk), block(kThreads);
-  rc = with_ion<TSFF_MAX_ION>(h->n_ion, [&](auto N) {
-    return with_bool(p.grad_fe, [&](auto FE) {
-      TSFF_LAUNCH_LDS(h, k_form_factor_adj, (N.value, FE.value ? 2 : 0), kLdsLimit, grid, block, p.smem, h->stream, h->S, K, p.feature,
-                      h->S.omgs[p.feature], h->S.npts, Pbar, h->lbparts.as<double>());
-      TSFF_LAUNCH0(h, k_lbacc_reduce, dim3(B * h->S.G), dim3(kThreads), 0, h->stream, h->lbparts.as<double>(), p.nworker, NLB,
-                   h->lbacc.as<double>());
-      TSFF_LAUNCH(h, k_ff2d_lines_adj, (N.value), dim3((B + 63) / 64), dim3(64), 0, h->stream, h->S, phys, p.feature, B,
+  TSFF_LAUNCH_FN(h, form_factor_adj_kernel(h->n_ion, p.grad_fe), ("k_form_factor_adj", h->n_ion, p.grad_fe ? 2 : 0), grid, block, p.smem,
+                 h->stream, h->S, K, p.feature, h->S.omgs[p.feature], h->S.npts, Pbar, h->lbparts.as<double>());
+  TSFF_LAUNCH0(h, k_lbacc_reduce, dim3(B * h->S.G), dim3(kThreads), 0, h->stream, h->lbparts.as<double>(), p.nworker, NLB,
+               h->lbacc.as<double>());
+  TSFF_LAUNCH_ION(h, TSFF_MAX_ION, k_ff2d_lines_adj, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->S, phys, p.feature, B,
                   h->lbacc.as<double>(), grad_phys, 1);
-      return 0;
-    });
-  });
-  if (rc) return rc;
   TSFF_HIP(h, hipGetLastError());
   if (!p.grad_fe) return 0;
   if (p.nchunk > 1) {
@@ -1411,19 +1445,11 @@ static int form_factor_2d_enqueue(tsff_handle* h, const FormFactor2dPlan& p, con
     const double* table = tables + (p.shared ? 0 : (size_t)b * p.tstride);
     dim3 grid((unsigned)std::min((hi - lo + p.groups - 1) / p.groups, p.max_grid)), block(p.groups * kThreads);
     if (int rc = timing_begin(h)) return rc;
-    int rc = with_ion<TSFF_MAX_ION>(h->n_ion, [&](auto N) {
-      return with_bool(p.lds, [&](auto LDS) {
-        return with_bool(p.save, [&](auto SAVE) {
-          constexpr int kG2 = LDS.value ? TSFF_2D_GROUPS_LDS : TSFF_2D_GROUPS_L2;
-          TSFF_LAUNCH_LDS(h, k_form_factor_2d, (N.value, LDS.value, kG2, SAVE.value), kLdsLimit, grid, block, p.smem, h->stream, h->S,
-                          phys, table, p.nv, ud_angle_deg * kPi / 180.0, va_angle_deg * kPi / 180.0, p.feature, lo, hi, P, proj);
-          return 0;
-        });
-      });
-    });
-    if (rc) return rc;
+    TSFF_LAUNCH_FN(h, form_factor_2d_kernel(h->n_ion, p.lds, p.save), ("k_form_factor_2d", h->n_ion, p.lds, p.groups, p.save), grid, block,
+                   p.smem, h->stream, h->S, phys, table, p.nv, ud_angle_deg * kPi / 180.0, va_angle_deg * kPi / 180.0, p.feature, lo, hi, P,
+                   proj);
     TSFF_HIP(h, hipGetLastError());
-    if ((rc = timing_end(h))) return rc;
+    if (int rc = timing_end(h)) return rc;
   }
   return 0;
 }
@@ -1532,24 +1558,17 @@ static int form_factor_2d_adj_enqueue(tsff_handle* h, const FormFactor2dAdjPlan&
   const double ud = ud_angle_deg * kPi / 180.0, va = va_angle_deg * kPi / 180.0;
   // a point group only writes the partial slots of the (b, g) it meets, the others stay zero
   TSFF_HIP(h, hipMemsetAsync(h->lbparts.p, 0, (size_t)B * h->S.G * p.nworker * NLB * sizeof(double), h->stream));
-  int rc = with_ion<TSFF_MAX_ION>(h->n_ion, [&](auto N) {
-    return with_bool(p.lds, [&](auto LDS) {
-      constexpr int kG2 = LDS.value ? TSFF_2D_GROUPS_LDS : TSFF_2D_GROUPS_L2;
-      TSFF_LAUNCH_LDS(h, k_form_factor_2d_adj, (N.value, LDS.value, kG2), kLdsLimit, p.grid, p.block, p.smem, h->stream, h->S, phys,
-                      table, nv, ud, va, p.feature, p.begin, p.end, Pbar, h->lbparts.as<double>(), f1bar, proj);
-      TSFF_LAUNCH0(h, k_lbacc_reduce, dim3(B * h->S.G), dim3(kThreads), 0, h->stream, h->lbparts.as<double>(), p.nworker, NLB,
-                   h->lbacc.as<double>());
-      TSFF_LAUNCH(h, k_ff2d_lines_adj, (N.value), dim3((B + 63) / 64), dim3(64), 0, h->stream, h->S, phys, p.feature, B,
+  TSFF_LAUNCH_FN(h, form_factor_2d_adj_kernel(h->n_ion, p.lds), ("k_form_factor_2d_adj", h->n_ion, p.lds, p.groups), p.grid, p.block, p.smem,
+                 h->stream, h->S, phys, table, nv, ud, va, p.feature, p.begin, p.end, Pbar, h->lbparts.as<double>(), f1bar, proj);
+  TSFF_LAUNCH0(h, k_lbacc_reduce, dim3(B * h->S.G), dim3(kThreads), 0, h->stream, h->lbparts.as<double>(), p.nworker, NLB,
+               h->lbacc.as<double>());
+  TSFF_LAUNCH_ION(h, TSFF_MAX_ION, k_ff2d_lines_adj, dim3((B + 63) / 64), dim3(64), 0, h->stream, h->S, phys, p.feature, B,
                   h->lbacc.as<double>(), grad_phys, 0);
-      return 0;
-    });
-  });
-  if (rc) return rc;
   TSFF_HIP(h, hipGetLastError());
   if (!p.table) return 0;
   TSFF_HIP(h, hipMemsetAsync(h->fbar_pad.p, 0, (size_t)(nv + 2) * (nv + 2) * sizeof(double), h->stream));
-  TSFF_LAUNCH0_LDS(h, k_ff2d_table_adj, kLdsLimit, dim3(p.per_tile, p.ntiles), dim3(4 * kThreads), p.tile_smem, h->stream, nv, f1bar,
-                   p.end - p.begin, h->fbar_parts.as<double>(), p.slab);
+  TSFF_LAUNCH0(h, k_ff2d_table_adj, dim3(p.per_tile, p.ntiles), dim3(4 * kThreads), p.tile_smem, h->stream, nv, f1bar, p.end - p.begin,
+               h->fbar_parts.as<double>(), p.slab);
   for (int t = 0; t < p.ntiles; ++t)   // one launch per tile, in order: the overlapping halos of neighbouring tiles add up without atomics
     TSFF_LAUNCH0(h, k_ff2d_sum_tiles, dim3((unsigned)((p.slab + kThreads - 1) / kThreads)), dim3(kThreads), 0, h->stream, nv,
                        h->fbar_parts.as<double>(), (int)p.per_tile, p.slab, h->fbar_pad.as<double>(), t);
@@ -1716,12 +1735,12 @@ int tsff_forward(tsff_handle* h, const double* params, const double* fe, const d
   const Batch b{params, fe, {nullptr, nullptr}, {e_amps, i_amps}, {noise_e, noise_i}, B};
   SpectrumPlan plan;
   int rc = check_batch(h, b, false);
-  if (!rc) rc = size_plan<0, 0>(h, B, plan);
+  if (!rc) rc = size_plan(h, 0, 0, B, plan);
   if (!rc) rc = ensure_workspace(h, B);
   if (rc) return rc;
   KCall K{};
   if ((rc = fill_call(h, K, b, ThryE, ThryI))) return rc;
-  return launch_spectrum<0>(h, K, plan);
+  return launch_spectrum(h, 0, 0, K, plan);
 }
 
 struct PackedOut {   // tsff_loss_grad_packed
@@ -1743,6 +1762,7 @@ struct LossGradCall {
   double *ThryE, *ThryI;
   const PackedOut* po;     // the packed form (loss_terms and grad are then the handle's)
   bool with_m = false;     // loss_grad_prepare: the DLM order is a leaf
+  int gm = 0;              // loss_grad_prepare: GM of the spectrum kernels (0 plasma parameters, 1 + the DLM order, 2 + the table adjoints)
   SpectrumPlan plan;       // loss_grad_prepare: the sized plan
 };
 
@@ -1771,11 +1791,11 @@ static int loss_grad_prepare(tsff_handle* h, LossGradCall& c) {
   // (the pipelined DLM plan forks onto the handle's second stream: not inside a capture, which this library keeps to one stream)
   if (h->capturing && h->fe_mode == TSFF_FE_DLM && !c.want_fe && c.with_m && h->dlm_blocks > 1)
     return fail(h, -2, "graph capture: TSFF_OPT_DLM_BLOCKS > 1 would fork onto a second stream (set it to 0 before capturing)");
-  rc = c.want_fe ? size_plan<1, 2>(h, B, c.plan) : c.with_m ? size_plan<1, 1>(h, B, c.plan) : size_plan<1, 0>(h, B, c.plan);
-  if (rc) return rc;
+  c.gm = c.want_fe ? 2 : c.with_m ? 1 : 0;
+  if ((rc = size_plan(h, 1, c.gm, B, c.plan))) return rc;
   if ((rc = ensure_workspace(h, B))) return rc;
   if (c.want_fe && (rc = fe_tail_prepare(h, 2, B))) return rc;    // (x 2: per-feature parts of the interleaved plan)
-  if (po) TSFF_ENSURE(h, h->gradws, (size_t)B * h->S.NP * sizeof(double));
+  if (po) TSFF_ENSURE(h, h->gradws, gradws_bytes(h->S, B));
   return 0;
 }
 
@@ -1794,10 +1814,9 @@ static int loss_grad_enqueue(tsff_handle* h, const LossGradCall& c) {
   K.wts[0] = c.weights[0]; K.wts[1] = c.weights[1]; K.wts[2] = c.weights[2];
   K.denom_mode = h->denom_mode;
   const bool parts = c.plan.gpart != 0, lbrec = c.plan.form == SpectrumForm::one_sweep;
+  if (c.want_fe) fe_tail_outputs(h, K, B);
+  if ((rc = launch_spectrum(h, 1, c.gm, K, c.plan, h->gmask.as<uint8_t>(), grad))) return rc;
   if (c.want_fe) {
-    fe_tail_outputs(h, K, B);
-    rc = launch_spectrum<1, 2>(h, K, c.plan, h->gmask.as<uint8_t>(), grad);
-    if (rc) return rc;
     if (parts) {
       const long nw = (long)B * kNXi2, nh = (long)2 * B * h->S.nvx;
       TSFF_LAUNCH0(h, k_add_parts, dim3((unsigned)std::min<long>((nw + kThreads - 1) / kThreads, 1024)), dim3(kThreads), 0, h->stream,
@@ -1807,21 +1826,15 @@ static int loss_grad_enqueue(tsff_handle* h, const LossGradCall& c) {
       TSFF_HIP(h, hipGetLastError());
     }
     if ((rc = fe_tail_enqueue(h, K, B, c.grad_fe))) return rc;
-  } else {
-    rc = with_m ? launch_spectrum<1, 1>(h, K, c.plan, h->gmask.as<uint8_t>(), grad)
-                : launch_spectrum<1>(h, K, c.plan, h->gmask.as<uint8_t>(), grad);
-    if (rc) return rc;
   }
   const long ng = (long)B * h->S.NP;
   if (lbrec) {   // the one-sweep kernel ran: one thread per lineout finishes the gradient and packs it (k_spectrum_fused.inc)
     const int nload = (h->S.load[0] ? 1 : 0) + (h->S.load[1] ? 1 : 0), f0 = h->S.load[0] ? 0 : 1;
     const int per_wg = kThreads / nload;
     const dim3 fgrid((unsigned)((B + per_wg - 1) / per_wg) + 1);   // (+ 1: the last workgroup reduces the loss sums)
-    with_ion<kFusedMaxIon>(h->n_ion, [&](auto N) {
-      TSFF_LAUNCH(h, k_fused_finish, (N.value), fgrid, dim3(kThreads), 0, h->stream, h->S, h->finrec.as<double>(), K.lbrec, K.lpart, (int)B,
-                  f0, nload, with_m ? 1 : 0, h->gmask.as<uint8_t>(), grad, po ? nullptr : c.loss_terms, po ? h->act.as<int>() : nullptr,
-                  po ? (int)po->n_act : 0, po ? (long)po->B_global : 0L, po ? (long)po->b_off : 0L, po ? po->packed : nullptr);
-    });
+    TSFF_LAUNCH_ION(h, kFusedMaxIon, k_fused_finish, fgrid, dim3(kThreads), 0, h->stream, h->S, h->finrec.as<double>(), K.lbrec, K.lpart, (int)B,
+                    f0, nload, with_m ? 1 : 0, h->gmask.as<uint8_t>(), grad, po ? nullptr : c.loss_terms, po ? h->act.as<int>() : nullptr,
+                    po ? (int)po->n_act : 0, po ? (long)po->B_global : 0L, po ? (long)po->b_off : 0L, po ? po->packed : nullptr);
   } else if (po) {
     const long n = (long)po->n_act * po->B_global;
     TSFF_LAUNCH0(h, k_loss_reduce_packed, dim3((unsigned)std::max<long>(1, std::min<long>((n + kThreads - 1) / kThreads, 1024))), dim3(kThreads),
@@ -2114,12 +2127,8 @@ int tsff_angular_fit(tsff_handle* h, const tsff_angular_spec* sp, double* leaves
   const unsigned nloss = (unsigned)std::min<long>(kAngLossBlocks, ((long)nimg + kThreads - 1) / kThreads);   // (a fixed partition)
   for (int t = 0; t < sp->n_epochs; ++t) {
     const int epoch = sp->epoch0 + t;
-    rc = with_ion<TSFF_MAX_ION>(h->n_ion, [&](auto N) {
-      TSFF_LAUNCH(h, k_ang_leaves, (N.value), dim3(1), dim3(kThreads), 0, h->stream, h->S, (const double*)leaves, gen,
-                  (int)sp->learn_log, nv, gen_data, sp->dvx, dv2, (int)want_dm, phys, fe, dfe, aux);
-      return 0;
-    });
-    if (rc) return rc;
+    TSFF_LAUNCH_ION(h, TSFF_MAX_ION, k_ang_leaves, dim3(1), dim3(kThreads), 0, h->stream, h->S, (const double*)leaves, gen,
+                    (int)sp->learn_log, nv, gen_data, sp->dvx, dv2, (int)want_dm, phys, fe, dfe, aux);
     if ((rc = gen_forward(h, gen, G.sph, sp->n_gen, gen_data, nv, sp->dvx, theta, gws, fe))) return rc;
     rc = G.two_d ? form_factor_2d_enqueue(h, ff2, phys, table, sp->ud_angle, sp->va_angle, P) : form_factor_enqueue(h, ff, phys, fe, P);
     if (rc) return rc;
@@ -2132,13 +2141,9 @@ int tsff_angular_fit(tsff_handle* h, const tsff_angular_spec* sp, double* leaves
     rc = G.two_d ? form_factor_2d_adj_enqueue(h, ff2a, phys, table, sp->ud_angle, sp->va_angle, h->proj.as<double>(), Pb, gphys, gfe)
                  : form_factor_adj_enqueue(h, ffa, phys, fe, Pb, gphys, gfe);
     if (rc) return rc;
-    rc = with_ion<TSFF_MAX_ION>(h->n_ion, [&](auto N) {
-      TSFF_LAUNCH(h, k_ang_chain, (N.value), dim3(1), dim3(kThreads), 0, h->stream, h->S, (const double*)leaves, (const double*)gphys,
-                  ampb, rows, (const double*)gfe, want_dm ? (const double*)dfe : nullptr, nv, (int)train_table,
-                  (int)sp->learn_log, nv, (const double*)aux, cvjp, ln10, act, (int)sp->n_active, grad);
-      return 0;
-    });
-    if (rc) return rc;
+    TSFF_LAUNCH_ION(h, TSFF_MAX_ION, k_ang_chain, dim3(1), dim3(kThreads), 0, h->stream, h->S, (const double*)leaves, (const double*)gphys,
+                    ampb, rows, (const double*)gfe, want_dm ? (const double*)dfe : nullptr, nv, (int)train_table,
+                    (int)sp->learn_log, nv, (const double*)aux, cvjp, ln10, act, (int)sp->n_active, grad);
     if ((rc = gen_adjoint(h, gen, G.sph, sp->n_gen, gen_data, nv, sp->dvx, theta, gfe, gws, grad + sp->n_active))) return rc;
     const double count = (double)epoch + 1;
     const double c1 = 1.0 - std::pow(b1, count), c2 = 1.0 - std::pow(b2, count);
@@ -2263,25 +2268,19 @@ int tsff_loss_hess(tsff_handle* h, const double* params, const double* fe, const
   if (A.with_m) {   // second m-derivative tables: k_hess_mtab, then the shipped W-table GEMM on its rows
     const size_t nvx = h->S.nvx;
     const size_t smem_t = sizeof(double2) * 6 * nvx + sizeof(double) * (nvx + 2 * kNXi1 + 8);
-    with_ion<TSFF_MAX_ION>(h->n_ion, [&](auto N) {
-      TSFF_LAUNCH(h, k_hess_mtab, (N.value), dim3(B), dim3(kThreads), smem_t, h->stream, h->S, params, K.ht, K.htm, h->htmm.as<double2>(),
-                  h->Xmm.as<double>(), h->cstmm.as<double>());
-    });
+    TSFF_LAUNCH_ION(h, TSFF_MAX_ION, k_hess_mtab, dim3(B), dim3(kThreads), smem_t, h->stream, h->S, params, K.ht, K.htm, h->htmm.as<double2>(),
+                    h->Xmm.as<double>(), h->cstmm.as<double>());
     TSFF_HIP(h, hipGetLastError());
     const int nM = (B + kGM / 4 - 1) / (kGM / 4);
     dim3 wgrid(8 * ((nM + 7) / 8) * ((kNXi2 + kGNw - 1) / kGNw));
-    TSFF_LAUNCH0_LDS(h, k_wgemm_w, kWgemmWSmem, wgrid, dim3(kThreads), kWgemmWSmem, h->stream, h->S.lg, h->Xmm.as<double>(),
-                     h->cstmm.as<double>(), h->S.xi2, (int)B, h->Wmm.as<double>(), h->Wmm_unused.as<double>(), h->kw_lo, h->kw_hi);
+    TSFF_LAUNCH0(h, k_wgemm_w, wgrid, dim3(kThreads), kWgemmWSmem, h->stream, h->S.lg, h->Xmm.as<double>(), h->cstmm.as<double>(),
+                 h->S.xi2, (int)B, h->Wmm.as<double>(), h->Wmm_unused.as<double>(), h->kw_lo, h->kw_hi);
     TSFF_HIP(h, hipGetLastError());
     A.htmm = h->htmm.as<double2>();
     A.Wmm = h->Wmm.as<double>();
   }
-  rc = with_ion<TSFF_MAX_ION>(h->n_ion, [&](auto N) {
-    TSFF_LAUNCH_LDS(h, k_hess_pairs, (N.value), kLdsLimit, dim3(nwg), dim3(kThreads), smem, h->stream, h->S, K, A, h->hws.as<double>(),
-                    h->hout.as<double>());
-    return 0;
-  });
-  if (rc) return rc;
+  TSFF_LAUNCH_FN(h, hess_pairs_kernel(h->n_ion), ("k_hess_pairs", h->n_ion), dim3(nwg), dim3(kThreads), smem, h->stream, h->S, K, A,
+                 h->hws.as<double>(), h->hout.as<double>());
   TSFF_HIP(h, hipGetLastError());
   TSFF_LAUNCH0(h, k_hess_finish, dim3((B + kThreads - 1) / kThreads), dim3(kThreads), 0, h->stream, h->hout.as<double>(), A, (int)B,
                weights[0], weights[1], weights[2], K.lpart, grad, hess);
@@ -2301,7 +2300,7 @@ int tsff_array_loss(tsff_handle* h, const double* params, const double* fe, cons
   const Batch b{params, fe, {e_data, i_data}, {e_amps, i_amps}, {noise_e, noise_i}, B};
   SpectrumPlan plan;
   int rc = check_batch(h, b, true);
-  if (!rc) rc = size_plan<2, 0>(h, B, plan);
+  if (!rc) rc = size_plan(h, 2, 0, B, plan);
   if (!rc) rc = ensure_workspace(h, B);
   if (rc) return rc;
   KCall K{};
@@ -2309,7 +2308,7 @@ int tsff_array_loss(tsff_handle* h, const double* params, const double* fe, cons
   K.sqdev[0] = sqdev_e; K.sqdev[1] = sqdev_i;
   K.lpart = sums;
   TSFF_HIP(h, hipMemsetAsync(sums, 0, (size_t)B * 3 * sizeof(double), h->stream));
-  return launch_spectrum<2>(h, K, plan);
+  return launch_spectrum(h, 2, 0, K, plan);
 }
 
 #ifdef TSFF_TRACE

@@ -16,6 +16,16 @@ constexpr int kThreads = 256;    // 4 wavefronts of 64
 constexpr int kStrip = 4;        // consecutive wavelength samples owned by one thread
 constexpr int kNP_MAX = TSFF_NP(TSFF_MAX_ION);
 
+// the `flags` word of the spectrum kernels (k_spectrum, k_spectrum_fused, k_forward_pairs, k_spectrum_rows): launch_spectrum
+// builds it, a kernel reads the bits that mean something to it
+enum SpectrumFlag : int {
+  kFlagAccumulate = 1,    // the second launch of a split plan: add to grad
+  kFlagKsCache = 2,       // the k_s cache is in LDS
+  kFlagInterleaved = 4,   // both features' workgroups in one launch (the workgroup index says which feature it evaluates)
+  kFlagOwnScalars = 8,    // wide pair sweep: the workgroup computes its lineout scalars itself (no k_fused_prep record)
+  kFlagSplit = 16,        // rows kernel: one workgroup per (lineout, feature, round)
+};
+
 // physical constants (form_factor.py:123-125, 207-209)
 constexpr double kC = 2.99792458e10;
 constexpr double kMe = 510.9896 / (kC * kC);
