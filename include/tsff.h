@@ -23,6 +23,8 @@
  *   jax reverse mode through the above (equinox.filter_value_and_grad, loss_function.py:108)
  *       tsff_loss_grad(_fe), tsff_form_factor_grad, tsff_form_factor_2d_grad, tsff_ats_adjoint
  *   LossFunction.h_loss_wrt_params (equinox.filter_hessian) inverse/loss_function.py:170-188  tsff_loss_hess
+ *   jax.jacfwd of ThomsonScatteringDiagnostic.__call__ w.r.t. the normalised leaves (the reference has no such call: its
+ *       uncertainties come from the full Hessian, postprocess.py:188-251)           tsff_spectrum_jacobian / tsff_loss_gauss_newton
  *   _1d_adam_loop_ (optax.adam + eqx.apply_updates + best tracking)  inverse/loops.py:59-95        tsff_adam_fit
  *   _1d_scipy_loop_ (scipy L-BFGS-B, bounds=None)                     inverse/loops.py:20-56        tsff_lbfgs_fit
  *   angular_optax (optax adam / rmsprop + early stop, ARTS decks)    inverse/loops.py:167-275      tsff_angular_fit
@@ -34,7 +36,8 @@
  *   - the caller owns every buffer; the library never frees caller memory;
  *   - calls are asynchronous on the handle's stream (tsff_set_stream); the caller synchronises;
  *   - return value 0 = success, negative = error, text via tsff_last_error();
- *   - a refused call (negative return) of tsff_forward, tsff_loss_grad(_packed, _fe), tsff_loss_hess, tsff_array_loss,
+ *   - a refused call (negative return) of tsff_forward, tsff_loss_grad(_packed, _fe), tsff_loss_hess, tsff_spectrum_jacobian,
+ *     tsff_loss_gauss_newton, tsff_array_loss,
  *     tsff_adam_fit, tsff_angular_fit, tsff_form_factor(_grad), tsff_form_factor_2d(_range, _save, _grad), tsff_ats_spectrum
  *     and tsff_ats_adjoint has enqueued nothing: their arguments, LDS budgets and buffers are checked before the first
  *     launch, and tsff_last_launch reports an empty list (other entry points may have enqueued work before a failure);
@@ -54,7 +57,7 @@
 extern "C" {
 #endif
 
-#define TSFF_ABI_VERSION 15
+#define TSFF_ABI_VERSION 16
 /* error codes (every entry point returns 0 or one of these; text via tsff_last_error):
  * -1 bad argument, -2 unsupported configuration / option, -3 not a differentiable leaf, -5 HIP runtime error,
  * -22 stale or foreign token of saved projection records (tsff_form_factor_2d_grad),
@@ -502,6 +505,38 @@ int tsff_loss_hess(tsff_handle *h, const double *params, const double *fe, const
                    const double *e_amps, const double *i_amps, const double *noise_e, const double *noise_i, int32_t B,
                    const double *weights, const int32_t *active_slots, int32_t n_active, double *loss_terms,
                    double *grad, double *hess);
+
+/* Jacobian of the model spectra w.r.t. the normalised leaves of the slots active_slots (HOST [n_active], ravel order), for every
+ * lineout b:  jac_f[b][a][j] = d Thry_f[b][j] / d x[b][a], Thry_f what tsff_forward returns for the same arguments without the
+ * additive noise (jax.jacfwd of ThomsonScatteringDiagnostic.__call__; the reference has no such call).
+ *   jac_e, jac_i (device [B][n_active][1024] each): either may be NULL (that feature is then not evaluated and nothing of it is
+ *   written); asking for the Jacobian of a feature that is not loaded returns -1, as does asking for neither.
+ * The chain and table convention of tsff_loss_hess (Z' and W lookups carry their slope, the Hermite ln f_e lookup its true
+ * derivative), in one of two forms that tsff_last_launch names as k_jac_sweep<n_ion, W, rows>:
+ *   rows (1-2 ion species, one gradient point, TSFF_P_M not a leaf, both features through their instrument response): per point
+ *     the value and the reverse of the pair-sweep kernels give each sample's row w.r.t. the lineout scalars, which is contracted
+ *     with the scalars' tangents w.r.t. the leaves -- about two forward calls whatever n_active;
+ *   tangents (everything else): first-order forward mode, a value and a group of W tangents side by side per point, the groups of
+ *     leaves one after the other.  W = 3; W = 1 for a single leaf or when the spectrum with three tangents exceeds the LDS (e.g.
+ *     5 points per pixel) -- one full sweep per leaf then, no faster than central differences.
+ * Slots: as tsff_loss_hess (-1 out of range or repeated, -2 TSFF_P_M without TSFF_FE_DLM, -3 an ion's A slot); -2 when the
+ * tables and the spectrum of the narrowest group exceed the LDS of a workgroup.  Every sum runs in a fixed order: two calls give
+ * bit-identical output. */
+int tsff_spectrum_jacobian(tsff_handle *h, const double *params, const double *fe, const double *e_amps, const double *i_amps,
+                           int32_t B, const int32_t *active_slots, int32_t n_active, double *jac_e, double *jac_i);
+
+/* Gauss-Newton curvature of the loss of tsff_loss_hess (denominators |data| + 1e-10 for l2 whatever TSFF_OPT_DENOM_MODE says,
+ * sum reduce), per lineout b, from the Jacobian above without writing it to memory:
+ *   gn[b][a][c] = sum_k weights[k] sum_{j in mask_k} l''(d_j, t_j) J[a][j] J[c][j]     (device [B][n_active][n_active], symmetric,
+ *                 positive semi-definite; l'' = 2 / (|d| + 1e-10) for l2, sech^2(d - t) for log-cosh, d / t^2 for poisson),
+ *   grad[b][a]  = sum_k weights[k] sum_{j in mask_k} dl/dt(d_j, t_j) J[a][j]           (device [B][n_active]; tsff_loss_hess's grad),
+ *   loss_terms (device [3]): the un-weighted masked sums S_iaw, S_blue, S_red over the B lineouts.
+ * weights (HOST [3]) and the refusals are those of tsff_loss_hess and tsff_spectrum_jacobian; loss_method l1 returns -2 (its
+ * l'' is zero: the Gauss-Newton matrix of an l1 fit vanishes). */
+int tsff_loss_gauss_newton(tsff_handle *h, const double *params, const double *fe, const double *e_data, const double *i_data,
+                           const double *e_amps, const double *i_amps, const double *noise_e, const double *noise_i, int32_t B,
+                           const double *weights, const int32_t *active_slots, int32_t n_active, double *loss_terms,
+                           double *grad, double *gn);
 
 
 /* The same plus the gradient w.r.t. the tabulated distribution function itself: grad_fe [B][nvx] (device) =

@@ -11,8 +11,13 @@
 // no curvature; the cubic Hermite ln f_e lookup carries its true second derivative; the Z' asymptote xi^-2 and exp(-xi^2) are
 // differentiated exactly.
 
+// The chain functions below (make_lines_hd, hermite_hd, base_hd, point_hd, tie_and_renorm) are written once over the number type
+// N: HD here, and the value with W first-order tangents of k_jacobian.inc (TN<W>).  N supplies N::of(double), the member v, the
+// arithmetic operators with N and with double, hd_chain and hd_xm, and kSecondOrder (whether the second-order table terms are read).
 struct HD {   // hyper-dual number: value, the two first derivatives and the mixed second derivative
   double v, a, b, ab;
+  static constexpr bool kSecondOrder = true;
+  static __device__ __forceinline__ HD of(double c) { return HD{c, 0.0, 0.0, 0.0}; }
 };
 __device__ __forceinline__ HD hd(double v) { return HD{v, 0.0, 0.0, 0.0}; }
 __device__ __forceinline__ HD operator+(HD x, HD y) { return HD{x.v + y.v, x.a + y.a, x.b + y.b, x.ab + y.ab}; }
@@ -31,21 +36,25 @@ __device__ __forceinline__ HD operator*(HD x, HD y) {
 __device__ __forceinline__ HD hd_chain(HD x, double f, double d1, double d2) {
   return HD{f, d1 * x.a, d1 * x.b, d1 * x.ab + d2 * x.a * x.b};
 }
-__device__ __forceinline__ HD hd_rcp(HD x) {
+template <class N>
+__device__ __forceinline__ N hd_rcp(N x) {
   const double r = 1.0 / x.v;
   return hd_chain(x, r, -r * r, 2.0 * r * r * r);
 }
 __device__ __forceinline__ HD operator/(HD x, HD y) { return x * hd_rcp(y); }
 __device__ __forceinline__ HD operator/(double c, HD y) { return c * hd_rcp(y); }
-__device__ __forceinline__ HD hd_sqrt(HD x) {
+template <class N>
+__device__ __forceinline__ N hd_sqrt(N x) {
   const double s = sqrt(x.v);
   return hd_chain(x, s, 0.5 / s, -0.25 / (s * x.v));
 }
-__device__ __forceinline__ HD hd_exp(HD x) {
+template <class N>
+__device__ __forceinline__ N hd_exp(N x) {
   const double e = exp(x.v);
   return hd_chain(x, e, e, e);
 }
-__device__ __forceinline__ HD hd_sigmoid(HD x) {
+template <class N>
+__device__ __forceinline__ N hd_sigmoid(N x) {
   const double s = sigmoid(x.v), d = s * (1.0 - s);
   return hd_chain(x, s, d, d * (1.0 - 2.0 * s));
 }
@@ -69,18 +78,20 @@ __device__ __forceinline__ void hess_pair(int p, int n, int& a, int& c) {
 }
 
 // lineout scalars of one gradient point (make_lines) in hyper-dual form
-template <int NI>
-struct LineHD {
-  HD wpe2, wL, kL, ivTe, a_e, pref, Ud, Vd, i2wL;
-  HD ixi[NI], a_i[NI], cs[NI], hai[NI];
+template <class N, int NI>
+struct LineT {
+  N wpe2, wL, kL, ivTe, a_e, pref, Ud, Vd, i2wL;
+  N ixi[NI], a_i[NI], cs[NI], hai[NI];
 };
+template <int NI>
+using LineHD = LineT<HD, NI>;
 
 // ph: physical parameters [NP] (after activation, Ti tying and fraction renormalisation), as make_lines reads them
-template <int NI>
-__device__ __forceinline__ void make_lines_hd(const HD* ph, double lam_shift, int g, int G, LineHD<NI>& L) {
+template <int NI, class N>
+__device__ __forceinline__ void make_lines_hd(const N* ph, double lam_shift, int g, int G, LineT<N, NI>& L) {
   const double cg = grad_coef(g, G);
-  const HD ne_g = (1.0e20 * ph[TSFF_P_NE]) * (1.0 + ph[TSFF_P_NE_GRADIENT] * cg);
-  const HD Te_g = ph[TSFF_P_TE] * (1.0 + ph[TSFF_P_TE_GRADIENT] * cg);
+  const N ne_g = (1.0e20 * ph[TSFF_P_NE]) * (1.0 + ph[TSFF_P_NE_GRADIENT] * cg);
+  const N Te_g = ph[TSFF_P_TE] * (1.0 + ph[TSFF_P_TE_GRADIENT] * cg);
   L.wL = kOmgLnum / (ph[TSFF_P_LAM] + lam_shift);
   L.i2wL = 2.0 / L.wL;
   L.wpe2 = kC0sq * ne_g;
@@ -90,15 +101,15 @@ __device__ __forceinline__ void make_lines_hd(const HD* ph, double lam_shift, in
   L.pref = ne_g * (kRe * kRe / (2.0 * kPi * kC));
   L.Ud = ph[TSFF_P_UD] * 1e6;
   L.Vd = ph[TSFF_P_VA] * 1e6;
-  HD Zbar = hd(0.0);
+  N Zbar = N::of(0.0);
 #pragma unroll
   for (int s = 0; s < NI; ++s) Zbar = Zbar + ph[TSFF_P_ION0 + 4 * s + TSFF_ION_Z] * ph[TSFF_P_ION0 + 4 * s + TSFF_ION_FRACT];
 #pragma unroll
   for (int s = 0; s < NI; ++s) {
     const int o = TSFF_P_ION0 + 4 * s;
-    const HD Ti = ph[o + TSFF_ION_TI], Z = ph[o + TSFF_ION_Z], fr = ph[o + TSFF_ION_FRACT];
+    const N Ti = ph[o + TSFF_ION_TI], Z = ph[o + TSFF_ION_Z], fr = ph[o + TSFF_ION_FRACT];
     const double Ms = ph[o + TSFF_ION_A].v * kMp;
-    const HD vTi = hd_sqrt(Ti * (1.0 / Ms));
+    const N vTi = hd_sqrt(Ti * (1.0 / Ms));
     L.ixi[s] = 1.0 / (kSqrt2 * vTi);
     L.a_i[s] = (kC0sq * kMe) * Z * Z * fr * ne_g / (Zbar * Ti);
     L.cs[s] = fr * Z * Z / (Zbar * vTi);
@@ -106,9 +117,11 @@ __device__ __forceinline__ void make_lines_hd(const HD* ph, double lam_shift, in
   }
 }
 
-struct BaseHD {
-  HD ik, wd, xe, F;
+template <class N>
+struct BaseT {
+  N ik, wd, xe, F;
 };
+using BaseHD = BaseT<HD>;
 
 // f(x, m) of a table lookup from its partial derivatives (fxx: curvature in x; fxm, fmm: through the m-dependence of the table)
 __device__ __forceinline__ HD hd_xm(HD x, HD m, double f, double fx, double fm, double fxx, double fxm, double fmm) {
@@ -118,14 +131,16 @@ __device__ __forceinline__ HD hd_xm(HD x, HD m, double f, double fx, double fm, 
 
 // the tables' dependence on the DLM order m (with_m): dW/dm, d2W/dm2 on the xi2 grid and the Hermite coefficients of
 // d ln f_e / dm and d2 ln f_e / dm2; m is the physical order with its two seeds
-struct MTab {
+template <class N>
+struct MTabT {
   const double* Wm;
-  const double* Wmm;
+  const double* Wmm;     // (second order only)
   const double2* hcm;
-  const double2* hcmm;
-  HD m;
+  const double2* hcmm;   // (second order only)
+  N m;
   bool on;
 };
+using MTab = MTabT<HD>;
 
 __device__ __forceinline__ void cubic_at(const double2* hc, int i, double t, double idv, double& H, double& d1, double& d2) {
   const double2 c01 = hc[2 * i], c23 = hc[2 * i + 1];
@@ -136,27 +151,28 @@ __device__ __forceinline__ void cubic_at(const double2* hc, int i, double t, dou
 
 // hermite_lookup_c with the true second derivative of the cubic (-50 and no derivative outside the grid); with M.on the
 // node values depend on m as well
-__device__ __forceinline__ HD hermite_hd(const Tables& T, const MTab& M, HD x) {
+template <class N>
+__device__ __forceinline__ N hermite_hd(const Tables& T, const MTabT<N>& M, N x) {
   const double u = __builtin_fma(x.v, T.idv, T.u0);
   const double uc = fmin(fmax(u, 0.0), T.utop);
-  if (u != uc) return hd(-50.0);
+  if (u != uc) return N::of(-50.0);
   const double fl = __builtin_floor(uc);
   const double t = uc - fl;
   const int i = (int)fl;
   double H, d1, d2;
   cubic_at(T.hc, i, t, T.idv, H, d1, d2);
   if (!M.on) return hd_chain(x, H, d1, d2);
-  double Hm, Hxm, unused, Hmm, u1, u2;
+  double Hm, Hxm, unused, Hmm = 0.0, u1, u2;
   cubic_at(M.hcm, i, t, T.idv, Hm, Hxm, unused);
-  cubic_at(M.hcmm, i, t, T.idv, Hmm, u1, u2);
+  if constexpr (N::kSecondOrder) cubic_at(M.hcmm, i, t, T.idv, Hmm, u1, u2);
   return hd_xm(x, M.m, H, d1, Hm, d2, Hxm, Hmm);
 }
 
-template <int NI>
-__device__ __forceinline__ void base_hd(double ws, double ct, const LineHD<NI>& L, const Tables& T, const MTab& M, BaseHD& b) {
-  const HD ks = hd_sqrt(ws * ws - L.wpe2) * (1.0 / kC);
-  const HD k2 = ks * (ks - (2.0 * ct) * L.kL) + L.kL * L.kL;
-  const HD k = hd_sqrt(k2);
+template <int NI, class N>
+__device__ __forceinline__ void base_hd(double ws, double ct, const LineT<N, NI>& L, const Tables& T, const MTabT<N>& M, BaseT<N>& b) {
+  const N ks = hd_sqrt(ws * ws - L.wpe2) * (1.0 / kC);
+  const N k2 = ks * (ks - (2.0 * ct) * L.kL) + L.kL * L.kL;
+  const N k = hd_sqrt(k2);
   b.ik = hd_rcp(k);
   b.wd = (ws - L.wL) - k * L.Vd;
   b.xe = (b.wd * b.ik - L.Ud) * L.ivTe;
@@ -164,26 +180,26 @@ __device__ __forceinline__ void base_hd(double ws, double ct, const LineHD<NI>& 
 }
 
 // point_core / point_forward_sd in hyper-dual form: S (1 + 2 w / w_L)
-template <int NI>
-__device__ __forceinline__ HD point_hd(const BaseHD& b, const BaseHD& bn, bool has_next, const LineHD<NI>& L, const Tables& T,
-                                      const MTab& M) {
-  const HD ik2 = b.ik * b.ik;
-  const HD ike2 = L.a_e * ik2;
-  const HD vph = b.wd * b.ik;
-  HD opc = hd(1.0), cim = hd(0.0), gsum = hd(0.0);
+template <int NI, class N>
+__device__ __forceinline__ N point_hd(const BaseT<N>& b, const BaseT<N>& bn, bool has_next, const LineT<N, NI>& L, const Tables& T,
+                                     const MTabT<N>& M) {
+  const N ik2 = b.ik * b.ik;
+  const N ike2 = L.a_e * ik2;
+  const N vph = b.wd * b.ik;
+  N opc = N::of(1.0), cim = N::of(0.0), gsum = N::of(0.0);
 #pragma unroll
   for (int s = 0; s < NI; ++s) {
-    const HD xi = vph * L.ixi[s];
-    const HD hk = L.hai[s] * ik2;
+    const N xi = vph * L.ixi[s];
+    const N hk = L.hai[s] * ik2;
     // Z'(xi): the full table (slope, no curvature) or the asymptote xi^-2 + 0 i outside it
     constexpr double kTop = (double)(kNXi2 - 1) * (1.0 - 1.1102230246251565e-16);
     const double u = __builtin_fma(xi.v, kXi2_ih, -kXi2_0 * kXi2_ih);
     const double uc = fmin(fmax(u, 0.0), kTop);
-    HD zr, zi;
+    N zr, zi;
     if (u != uc) {
       const double r = 1.0 / xi.v, r2 = r * r;
       zr = hd_chain(xi, r2, -2.0 * r2 * r, 6.0 * r2 * r2);
-      zi = hd(0.0);
+      zi = N::of(0.0);
     } else {
       const double fl = __builtin_floor(uc);
       const double t = uc - fl;
@@ -193,31 +209,31 @@ __device__ __forceinline__ HD point_hd(const BaseHD& b, const BaseHD& bn, bool h
       zr = hd_chain(xi, __builtin_fma(t, dr, za.x), dr * kXi2_ih, 0.0);
       zi = hd_chain(xi, __builtin_fma(t, di, za.y), di * kXi2_ih, 0.0);
     }
-    const HD gs = hd_exp(-(xi * xi)) * kInvSqrt2Pi;
+    const N gs = hd_exp(-(xi * xi)) * kInvSqrt2Pi;
     opc = opc + hk * zr;
     cim = cim + hk * zi;
     gsum = gsum + L.cs[s] * gs;
   }
   double w, dw;
   w_lookup(T.W, b.xe.v, w, dw);
-  HD Wl;
+  N Wl;
   if (M.on) {   // W(x, m): no curvature in x; dW/dm and d2W/dm2 interpolated in the same cell, the slope of dW/dm for the mixed term
-    double wm, dwm, wmm, dwmm;
+    double wm, dwm, wmm = 0.0, dwmm;
     w_lookup(M.Wm, b.xe.v, wm, dwm);
-    w_lookup(M.Wmm, b.xe.v, wmm, dwmm);
+    if constexpr (N::kSecondOrder) w_lookup(M.Wmm, b.xe.v, wmm, dwmm);
     Wl = hd_xm(b.xe, M.m, w, dw, wm, 0.0, dwm, wmm);
   } else {
     Wl = hd_chain(b.xe, w, dw, 0.0);
   }
-  const HD D = has_next ? (bn.F - b.F) / (bn.xe - b.xe) : hd(0.0);
-  const HD cer = -(ike2 * Wl);
-  const HD cei = (kPi * ike2) * D;
-  const HD er = opc + cer, ei = cei + cim;
-  const HD eps2 = er * er + ei * ei;
-  const HD ce2 = cer * cer + cei * cei;
-  const HD ci2 = opc * opc + cim * cim;
-  const HD N = gsum * ce2 + ci2 * b.F * L.ivTe;
-  const HD S = N * b.ik / eps2;
+  const N D = has_next ? (bn.F - b.F) / (bn.xe - b.xe) : N::of(0.0);
+  const N cer = -(ike2 * Wl);
+  const N cei = (kPi * ike2) * D;
+  const N er = opc + cer, ei = cei + cim;
+  const N eps2 = er * er + ei * ei;
+  const N ce2 = cer * cer + cei * cei;
+  const N ci2 = opc * opc + cim * cim;
+  const N Nn = gsum * ce2 + ci2 * b.F * L.ivTe;
+  const N S = Nn * b.ik / eps2;
   return S * (1.0 + b.wd * L.i2wL);
 }
 
@@ -231,6 +247,19 @@ __device__ __forceinline__ HD loss_hd(int method, double d, HD t) {
   else { const double it = 1.0 / t.v; e = hd_chain(t, t.v - d * log(t.v), 1.0 - d * it, d * it * it); }
   if (method == TSFF_LOSS_L2 || method == TSFF_LOSS_L1) e = e * (1.0 / (fabs(d) + 1e-10));
   return e;
+}
+
+// Ti tying and fraction renormalisation of the physical parameters (the tail of stage_phys)
+template <int NI, class N>
+__device__ __forceinline__ void tie_and_renorm(const KStatic& S, N* ph) {
+  N fsum = N::of(0.0);
+  for (int s = 0; s < NI; ++s) {
+    const int o = TSFF_P_ION0 + 4 * s;
+    if (s > 0 && S.ti_same[s]) ph[o + TSFF_ION_TI] = ph[TSFF_P_ION0 + TSFF_ION_TI];
+    fsum = fsum + ph[o + TSFF_ION_FRACT];
+  }
+  const N ifs = hd_rcp(fsum);
+  for (int s = 0; s < NI; ++s) ph[TSFF_P_ION0 + 4 * s + TSFF_ION_FRACT] = ph[TSFF_P_ION0 + 4 * s + TSFF_ION_FRACT] * ifs;
 }
 
 __device__ __forceinline__ HD block_sum_hd(HD x, double* red) {
@@ -311,14 +340,7 @@ __global__ __launch_bounds__(kThreads) void k_hess_pairs(KStatic S, KCall K, Hes
         if (S.p_sig[s]) v = hd_sigmoid(v);
         ph[s] = v * S.p_scale[s] + S.p_shift[s];
       }
-      HD fsum = hd(0.0);
-      for (int s = 0; s < NI; ++s) {
-        const int o = TSFF_P_ION0 + 4 * s;
-        if (s > 0 && S.ti_same[s]) ph[o + TSFF_ION_TI] = ph[TSFF_P_ION0 + TSFF_ION_TI];
-        fsum = fsum + ph[o + TSFF_ION_FRACT];
-      }
-      const HD ifs = hd_rcp(fsum);
-      for (int s = 0; s < NI; ++s) ph[TSFF_P_ION0 + 4 * s + TSFF_ION_FRACT] = ph[TSFF_P_ION0 + 4 * s + TSFF_ION_FRACT] * ifs;
+      tie_and_renorm<NI>(S, ph);
     }
     __syncthreads();
     Tables T;

@@ -126,6 +126,8 @@ struct tsff_handle {
   std::vector<int32_t> act_host;
   tsff::DevBuf hws, hout;          // tsff_loss_hess: hyper-dual spectra of the persistent workgroups, per-task sums
   tsff::DevBuf htmm, Xmm, cstmm, Wmm, Wmm_unused;   // tsff_loss_hess with the DLM order m: second m-derivative tables
+  tsff::DevBuf jrows;              // tsff_spectrum_jacobian / tsff_loss_gauss_newton: per persistent workgroup the row form's spectrum and
+                                   // tangents ((1 + n_active) x npts doubles) and the Gauss-Newton call's Jacobian rows (n_active x 1024)
   size_t smem_adjoint = 0;
   tsff::DevBuf ats_w, ats_ta, ats_tl, ats_lam, ats_M, ats_A, ats_B, ats_C, ats_D, ats_stats;
   int ats_npx = 0, ats_nta = 0, ats_offa = 0, ats_ntl = 0, ats_offl = 0, ats_lam_step = 1, ats_ang_step = 1,
@@ -372,6 +374,16 @@ static auto form_factor_kernel(int n_ion) { return with_ion<TSFF_MAX_ION>(n_ion,
 static auto fe_prepare_kernel(int n_ion) { return with_ion<TSFF_MAX_ION>(n_ion, [](auto N) { return &k_fe_prepare<N.value>; }); }
 static auto fe_vectors_kernel(int n_ion) { return with_ion<TSFF_MAX_ION>(n_ion, [](auto N) { return &k_fe_vectors<N.value>; }); }
 static auto hess_pairs_kernel(int n_ion) { return with_ion<TSFF_MAX_ION>(n_ion, [](auto N) { return &k_hess_pairs<N.value>; }); }
+// the Jacobian sweep: groups of W = 3 tangents, or of 1 (a single leaf; a spectrum too long for the LDS with three); rows: the row
+// form of the sweep (W = 3, n_ion <= kFusedMaxIon: the reverse of the pair-sweep kernels)
+static auto jac_kernel(int n_ion, int width, bool rows) {
+  using JacFn = decltype(&k_jac_sweep<1, 1, false>);
+  if (rows)
+    return width != 3 ? JacFn(nullptr) : with_ion<kFusedMaxIon>(n_ion, [&](auto N) -> JacFn { return &k_jac_sweep<N.value, 3, true>; });
+  return with_ion<TSFF_MAX_ION>(n_ion, [&](auto N) -> JacFn {
+    return width == 3 ? &k_jac_sweep<N.value, 3, false> : width == 1 ? &k_jac_sweep<N.value, 1, false> : nullptr;
+  });
+}
 static auto form_factor_adj_kernel(int n_ion, bool grad_fe) {
   return with_ion<TSFF_MAX_ION>(n_ion, [&](auto N) { return grad_fe ? &k_form_factor_adj<N.value, 2> : &k_form_factor_adj<N.value, 0>; });
 }
@@ -414,6 +426,9 @@ static hipError_t raise_lds_limits(int n_ion) {
   raise(fe_prepare_kernel(n_ion));
   raise(fe_vectors_kernel(n_ion));
   raise(hess_pairs_kernel(n_ion));
+  raise(jac_kernel(n_ion, 1, false));
+  raise(jac_kernel(n_ion, 3, false));
+  raise(jac_kernel(n_ion, 3, true));
   raise(&k_fe_adjoint);
   raise(&k_ff2d_table_adj);
   raise(&k_wgemm_w, kWgemmWSmem);
@@ -2289,6 +2304,99 @@ int tsff_loss_hess(tsff_handle* h, const double* params, const double* fe, const
                (double*)nullptr);
   TSFF_HIP(h, hipGetLastError());
   return 0;
+}
+
+// Jacobian of the spectra and Gauss-Newton curvature (k_jacobian.inc): the deck's table kernels, then k_jac_sweep on persistent
+// workgroups (one lineout per task); tsff_loss_gauss_newton adds k_loss_reduce.  jac_prepare holds everything that can refuse,
+// allocate or upload; jac_enqueue only launches.
+constexpr int kJacMaxWG = 1024;   // persistent workgroups of k_jac_sweep (bounds the row scratch: n_active x 1024 doubles each)
+struct JacCall {
+  Batch b;
+  JacArgs A{};
+  double* loss_terms = nullptr;
+  int width = 0, nwg = 0;   // jac_prepare: tangents per group, workgroups
+  bool rows = false;        // jac_prepare: the row form of the sweep
+  size_t smem = 0;
+};
+
+static int jac_prepare(tsff_handle* h, JacCall& c, const int32_t* active_slots, int n_active, const char* who) {
+  uint8_t gm[kNP_MAX];
+  if (int rc = check_slots(h, active_slots, n_active, gm, h->fe_mode == TSFF_FE_DLM)) return rc;
+  JacArgs& A = c.A;
+  A.n = n_active;
+  std::copy(active_slots, active_slots + n_active, A.slot);
+  A.with_m = gm[TSFF_P_M];
+  if (int rc = check_batch(h, c.b, A.want_gn != 0)) return rc;
+  if (A.want_gn && h->S.loss_method == TSFF_LOSS_L1)
+    return fail(h, -2, "%s: loss_method l1 has l'' = 0, its Gauss-Newton matrix vanishes (use l2, log-cosh or poisson)", who);
+  // three tangents per group when the leaves and the LDS allow it, else one
+  c.width = n_active == 1 ? 1 : 3;
+  c.smem = sizeof(double) * jac_smem_doubles(h->S, A.with_m != 0, c.width);
+  if (c.smem > kLdsLimit) {
+    c.width = 1;
+    c.smem = sizeof(double) * jac_smem_doubles(h->S, A.with_m != 0, 1);
+  }
+  if (c.smem > kLdsLimit)
+    return fail(h, -2, "%s: LDS budget exceeded (%zu B with nvx = %d, npts = %d%s): reduce nvx or points_per_pixel", who, c.smem, h->S.nvx,
+                h->S.npts, A.with_m ? " and the DLM order as a leaf" : "");
+  c.nwg = std::min(c.b.B, kJacMaxWG);
+  // the row form where the reverse of the pair sweeps exists: 1-2 ion species, one gradient point, the DLM order not a leaf, both
+  // features through their instrument response, and three tangents per group
+  const size_t smem_rows = sizeof(double) * jac_rows_smem_doubles(h->S, n_active);
+  c.rows = c.width == 3 && h->n_ion <= kFusedMaxIon && h->S.G == 1 && !A.with_m && !h->S.raw[0] && !h->S.raw[1] && smem_rows <= kLdsLimit;
+  if (c.rows) c.smem = smem_rows;
+  const size_t xg_doubles = c.rows ? (size_t)(1 + n_active) * h->S.npts : 0;
+  TSFF_ENSURE(h, h->jrows, (size_t)c.nwg * (xg_doubles + (A.want_gn ? (size_t)n_active * TSFF_NBINS : 0)) * sizeof(double));
+  return ensure_workspace(h, c.b.B);
+}
+
+static int jac_enqueue(tsff_handle* h, JacCall& c) {
+  KCall K{};
+  if (int rc = fill_call(h, K, c.b, nullptr, nullptr)) return rc;
+  const size_t xg_doubles = c.rows ? (size_t)c.nwg * (1 + c.A.n) * h->S.npts : 0;   // (the row form's spectra in front of the rows)
+  c.A.xg = c.rows ? h->jrows.as<double>() : nullptr;
+  c.A.rows = c.A.want_gn ? h->jrows.as<double>() + xg_doubles : nullptr;
+  TSFF_LAUNCH_FN(h, jac_kernel(h->n_ion, c.width, c.rows), ("k_jac_sweep", h->n_ion, c.width, c.rows), dim3(c.nwg), dim3(kThreads), c.smem, h->stream,
+                 h->S, K, c.A);
+  TSFF_HIP(h, hipGetLastError());
+  if (c.A.want_gn) {
+    TSFF_LAUNCH0(h, k_loss_reduce, dim3(1), dim3(kThreads), 0, h->stream, K.lpart, (int)c.b.B, c.loss_terms, (const double*)nullptr, 0L,
+                 (double*)nullptr);
+    TSFF_HIP(h, hipGetLastError());
+  }
+  return 0;
+}
+
+int tsff_spectrum_jacobian(tsff_handle* h, const double* params, const double* fe, const double* e_amps, const double* i_amps, int32_t B,
+                           const int32_t* active_slots, int32_t n_active, double* jac_e, double* jac_i) {
+  DevGuard dg__(h);
+  if (!h) return -1;
+  if (!active_slots || (!jac_e && !jac_i) || n_active < 1 || n_active > h->S.NP) return fail(h, -1, "bad argument");
+  if ((jac_e && !h->S.load[0]) || (jac_i && !h->S.load[1]))
+    return fail(h, -1, "tsff_spectrum_jacobian: the Jacobian of a feature that is not loaded");
+  JacCall c;
+  c.b = Batch{params, fe, {nullptr, nullptr}, {e_amps, i_amps}, {nullptr, nullptr}, B};
+  c.A.jac[0] = jac_e; c.A.jac[1] = jac_i;
+  if (int rc = jac_prepare(h, c, active_slots, n_active, "tsff_spectrum_jacobian")) return rc;
+  return jac_enqueue(h, c);
+}
+
+int tsff_loss_gauss_newton(tsff_handle* h, const double* params, const double* fe, const double* e_data, const double* i_data,
+                           const double* e_amps, const double* i_amps, const double* noise_e, const double* noise_i, int32_t B,
+                           const double* weights, const int32_t* active_slots, int32_t n_active, double* loss_terms, double* grad,
+                           double* gn) {
+  DevGuard dg__(h);
+  if (!h) return -1;
+  if (!weights || !active_slots || !loss_terms || !grad || !gn || n_active < 1 || n_active > h->S.NP)
+    return fail(h, -1, "bad argument");
+  JacCall c;
+  c.b = Batch{params, fe, {e_data, i_data}, {e_amps, i_amps}, {noise_e, noise_i}, B};
+  c.A.want_gn = 1;
+  c.A.grad = grad; c.A.gn = gn;
+  std::copy(weights, weights + 3, c.A.w);
+  c.loss_terms = loss_terms;
+  if (int rc = jac_prepare(h, c, active_slots, n_active, "tsff_loss_gauss_newton")) return rc;
+  return jac_enqueue(h, c);
 }
 
 int tsff_array_loss(tsff_handle* h, const double* params, const double* fe, const double* e_data, const double* i_data,

@@ -16,6 +16,7 @@
 //   k_form_factor  a4-a10                : raw FormFactor.__call__ output (known-answer tests)
 //   k_chain.inc    a12, a14, a15         : the chain's rules around the sweeps (amplitudes, loss, their adjoint, gradient tail), once
 //   k_hess_pairs   a16                   : exact per-lineout Hessian of the fit loss (hyper-dual forward mode, k_hessian.inc)
+//   k_jac_sweep    jax.jacfwd of a1     : Jacobian of the spectra w.r.t. the leaves and the Gauss-Newton curvature (k_jacobian.inc)
 //   k_adam_step    loops.py:59-95        : one Adam step + best tracking on the packed loss and gradient (tsff_adam_fit, k_adam.inc)
 //   k_lbfgs_step   loops.py:20-56        : one evaluation's step of unbounded L-BFGS-B on the packed loss and gradient (tsff_lbfgs_fit)
 //   k_ang_*        loops.py:167-275      : the angular fit's generator, loss and seed, chain rule and optimiser step (tsff_angular_fit)
@@ -108,6 +109,7 @@ constexpr int kFusedMaxIon = 2;  // k_spectrum_fused is instantiated for n_ion <
 #include "k_ats.inc"
 #include "k_peak.inc"
 #include "k_hessian.inc"
+#include "k_jacobian.inc"
 #include "k_adam.inc"
 #include "k_lbfgs.inc"
 #include "k_angular.inc"

@@ -613,6 +613,47 @@ class Engine:
         L.check(self.lib, self.h, rc)
         return terms, grad, hess
 
+    def spectrum_jacobian(self, params, e_amps, i_amps, active_slots, fe=None):
+        """Jacobian of the model spectra (``forward`` without the noise) w.r.t. the normalised leaves of ``active_slots`` (ravel
+        order): -> (JE, JI), CUDA tensors [B, P, 1024]; a feature that is not loaded returns ``None``.  Nothing is synchronised
+        (tsff_spectrum_jacobian: the table convention of ``loss_hess``).  ``last_launch()`` names the form that ran,
+        ``k_jac_sweep<n_ion, W, rows>``: the row form (1-2 ion species, one gradient point, no DLM order among the leaves) costs
+        about two forwards whatever P; the tangent form carries W = 3 leaves per sweep; W = 1 -- a spectrum too long for the LDS
+        with three tangents, e.g. 5 points per pixel -- runs one full sweep per leaf, no faster than central differences."""
+        torch = self.torch
+        X = self.dev(params).reshape(-1, self.NP)
+        B = X.shape[0]
+        act = np.ascontiguousarray(active_slots, dtype=np.int32)
+        P = int(act.size)
+        keep, ba = self._batch_args(X, dict(e_amps=e_amps, i_amps=i_amps), fe, need_data=False)
+        JE = torch.empty((B, P, L.NBINS), dtype=torch.float64, device=self.device) if self.load_ele else None
+        JI = torch.empty((B, P, L.NBINS), dtype=torch.float64, device=self.device) if self.load_ion else None
+        self._sync_stream()
+        rc = self.lib.tsff_spectrum_jacobian(self.h, *ba[:2], *ba[4:6], B, act.ctypes.data_as(C.POINTER(C.c_int32)), P,
+                                             self._ptr(JE), self._ptr(JI))
+        L.check(self.lib, self.h, rc)
+        return JE, JI
+
+    def loss_gauss_newton(self, params, batch, weights, active_slots, fe=None):
+        """Gauss-Newton curvature of the loss of ``loss_hess``: -> (loss_terms[3], grad[B, P], gn[B, P, P]) as CUDA tensors,
+        gn[b] = sum_k weights[k] sum_{j in mask_k} l''(d_j, t_j) J[:, j] J[:, j]^T (symmetric, positive semi-definite), grad
+        that of ``loss_hess``; nothing is synchronised (tsff_loss_gauss_newton; the Jacobian is not written to memory)."""
+        torch = self.torch
+        X = self.dev(params).reshape(-1, self.NP)
+        B = X.shape[0]
+        act = np.ascontiguousarray(active_slots, dtype=np.int32)
+        P = int(act.size)
+        keep, ba = self._batch_args(X, batch, fe)
+        terms = torch.empty(3, dtype=torch.float64, device=self.device)
+        grad = torch.empty((B, P), dtype=torch.float64, device=self.device)
+        gn = torch.empty((B, P, P), dtype=torch.float64, device=self.device)
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        self._sync_stream()
+        rc = self.lib.tsff_loss_gauss_newton(self.h, *ba, w.ctypes.data_as(L.c_double_p), act.ctypes.data_as(C.POINTER(C.c_int32)), P,
+                                             self._ptr(terms), self._ptr(grad), self._ptr(gn))
+        L.check(self.lib, self.h, rc)
+        return terms, grad, gn
+
     def pack_fe_rows(self, terms, grad, gfe, active_slots, B_global=None, b_offset=0, out=None):
         """The packed buffer ``[3 | (P + nvx) x B_global]`` of a free-form f_e step from the outputs of ``loss_grad(want_fe_grad=True)``
         (tsff_pack_fe_rows: one transposing kernel, this rank's columns filled, the others zero)."""

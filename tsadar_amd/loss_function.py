@@ -454,3 +454,57 @@ class LossFunction:
             for b_, ((sp2, k2), _) in enumerate(leaves):
                 hess.setdefault(sp1, {}).setdefault(k1, {}).setdefault(sp2, {})[k2] = np.diag(H[:, a, b_])
         return hess
+
+    def _refuse_jacobian(self, weights: ThomsonParams, what: str):
+        """What the Jacobian path is not built for, refused before any device work (as ``method="exact"`` does)."""
+        if getattr(self, "angular", False):
+            raise NotImplementedError(f"{what} is not built for angular_full decks")
+        if getattr(weights, "fval", None) is not None and (weights.slots.fval_active or weights.slots.fval2d_active):
+            raise NotImplementedError(f"{what}: the Jacobian w.r.t. the free-form f_e values (nvx table leaves) is not built")
+
+    def jacobian(self, weights: ThomsonParams, batch: Dict):
+        """Jacobian of the model spectra w.r.t. the trainable normalised leaves, in one device call (Engine.spectrum_jacobian):
+        ``{"ele": [B, n, 1024], "ion": [B, n, 1024], "leaves": [(species, key), ...]}`` as NumPy arrays (a feature that is not
+        loaded: ``None``), the leaves in ravel order.  With ``distributed=True`` this rank's lineouts."""
+        self._refuse_jacobian(weights, "jacobian")
+        leaves = weights.slots.active_leaves
+        act = [s for _, s in leaves]
+        keys = [k for k, _ in leaves]
+        X = weights.to_matrix()
+        B = X.shape[0]
+        eng = self.ts_diag.engine(weights.activate)
+        if B == 0:   # (an empty shard of a distributed fit)
+            z = np.zeros((0, len(act), L.NBINS))
+            return {"ele": z if eng.load_ele else None, "ion": z.copy() if eng.load_ion else None, "leaves": keys}
+        db = self._device_batch(eng, batch, B)
+        JE, JI = eng.spectrum_jacobian(X, db["e_amps"], db["i_amps"], act, fe=weights.fe_table())
+        return {"ele": None if JE is None else JE.cpu().numpy(), "ion": None if JI is None else JI.cpu().numpy(), "leaves": keys}
+
+    def gn_loss_wrt_params(self, weights: ThomsonParams, batch: Dict):
+        """Gauss-Newton matrix of the loss ``h_loss_wrt_params`` differentiates, sum_j l''(d_j, t_j) J_j J_j^T per lineout
+        (Engine.loss_gauss_newton), in exactly the nested layout of ``h_loss_wrt_params``: ``hess[sp1][k1][sp2][k2]`` is a
+        [B, B] matrix with the per-lineout values on its diagonal, so ``postprocess.get_sigmas(hess, batch_size)`` reads it
+        unchanged.  Positive semi-definite by construction (the Fisher information of the fit); equal to the exact Hessian
+        where the residual vanishes.  Same weights [fit_iaw, c, c]; with ``distributed=True`` this rank's lineouts (an empty
+        shard gives [0, 0] blocks).  Not built for angular decks, a free-form f_e among the leaves, or ``loss_method: l1``
+        (its l'' is zero)."""
+        self._refuse_jacobian(weights, "gn_loss_wrt_params")
+        if self.cfg.get("optimizer", {}).get("loss_method", "l2") == "l1":
+            raise NotImplementedError("gn_loss_wrt_params: loss_method l1 has a vanishing second derivative, so its "
+                                      "Gauss-Newton matrix is zero (use l2, log-cosh or poisson)")
+        eng = self.ts_diag.engine(weights.activate)
+        X = weights.to_matrix()
+        B = X.shape[0]
+        c = 0.5 if (eng.fit_blue and eng.fit_red) else 1.0
+        w = np.array([1.0 if eng.fit_iaw else 0.0, c if eng.fit_blue else 0.0, c if eng.fit_red else 0.0])
+        leaves = weights.slots.active_leaves
+        act = [s for _, s in leaves]
+        if B == 0:
+            H = np.zeros((0, len(act), len(act)))
+        else:
+            H = eng.loss_gauss_newton(X, self._device_batch(eng, batch, B), w, act, fe=weights.fe_table())[2].cpu().numpy()
+        hess = {}
+        for a, ((sp1, k1), _) in enumerate(leaves):
+            for b_, ((sp2, k2), _) in enumerate(leaves):
+                hess.setdefault(sp1, {}).setdefault(k1, {}).setdefault(sp2, {})[k2] = np.diag(H[:, a, b_])
+        return hess
