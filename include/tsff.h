@@ -28,6 +28,7 @@
  *   _1d_adam_loop_ (optax.adam + eqx.apply_updates + best tracking)  inverse/loops.py:59-95        tsff_adam_fit
  *   _1d_scipy_loop_ (scipy L-BFGS-B, bounds=None)                     inverse/loops.py:20-56        tsff_lbfgs_fit
  *   angular_optax (optax adam / rmsprop + early stop, ARTS decks)    inverse/loops.py:167-275      tsff_angular_fit
+ *   (no reference row: each lineout of a 1-D batch fitted on its own by Levenberg-Marquardt)         tsff_lm_fit
  *
  * Conventions
  *   - every array pointer in a *call* is a DEVICE pointer (hipMalloc'ed or a torch CUDA tensor);
@@ -38,7 +39,7 @@
  *   - return value 0 = success, negative = error, text via tsff_last_error();
  *   - a refused call (negative return) of tsff_forward, tsff_loss_grad(_packed, _fe), tsff_loss_hess, tsff_spectrum_jacobian,
  *     tsff_loss_gauss_newton, tsff_array_loss,
- *     tsff_adam_fit, tsff_angular_fit, tsff_form_factor(_grad), tsff_form_factor_2d(_range, _save, _grad), tsff_ats_spectrum
+ *     tsff_adam_fit, tsff_lm_fit, tsff_angular_fit, tsff_form_factor(_grad), tsff_form_factor_2d(_range, _save, _grad), tsff_ats_spectrum
  *     and tsff_ats_adjoint has enqueued nothing: their arguments, LDS budgets and buffers are checked before the first
  *     launch, and tsff_last_launch reports an empty list (other entry points may have enqueued work before a failure);
  *   - a call that breaks several conditions is refused for the first of: the entry point's own arguments (-1), the active slot
@@ -57,7 +58,7 @@
 extern "C" {
 #endif
 
-#define TSFF_ABI_VERSION 16
+#define TSFF_ABI_VERSION 17
 /* error codes (every entry point returns 0 or one of these; text via tsff_last_error):
  * -1 bad argument, -2 unsupported configuration / option, -3 not a differentiable leaf, -5 HIP runtime error,
  * -22 stale or foreign token of saved projection records (tsff_form_factor_2d_grad),
@@ -537,6 +538,42 @@ int tsff_loss_gauss_newton(tsff_handle *h, const double *params, const double *f
                            const double *e_amps, const double *i_amps, const double *noise_e, const double *noise_i, int32_t B,
                            const double *weights, const int32_t *active_slots, int32_t n_active, double *loss_terms,
                            double *grad, double *gn);
+
+/* Every lineout of a 1-D batch fitted on its own by Levenberg-Marquardt (damped Gauss-Newton steps, Nielsen's damping: Madsen,
+ * Nielsen and Tingleff, "Methods for Non-Linear Least Squares Problems", 2004, Algorithm 3.16), on the device: n_evals x (the
+ * sweep of tsff_loss_gauss_newton -- per lineout b the loss F_b = (w[0] S_iaw[b] + w[1] S_blue[b]) + w[2] S_red[b], its gradient
+ * and its Gauss-Newton matrix at params -- then one launch of k_lm_step, one wavefront per lineout), all enqueued on the handle's
+ * stream; the call returns once they are enqueued (no synchronisation, allocation or upload between the evaluations).  The
+ * reference has no such optimiser; its 1-D loops treat the batch as one joint problem.  The method is restated on the host in
+ * tsadar_amd/lm.py, and the device reproduces that restatement bit for bit (ordered sums, nothing fused; k_lm.inc).
+ *   params (device [B][NP], in/out): normalised leaves; k_lm_step writes each lineout's next trial point into the active slots,
+ *   and its accepted point once the lineout's status is terminal;
+ *   fe, e_data .. noise_i, B, weights, active_slots, n_active: as tsff_loss_gauss_newton, with its refusals (a slot out of range
+ *   or repeated -1, TSFF_P_M without fe_mode == TSFF_FE_DLM -2, an ion's A slot -3, loss_method l1 -2, the LDS budget -2).  The
+ *   loss is the fit loss: with TSFF_OPT_DENOM_MODE 0 the l2 denominators are constants that the weights carry (e = r^2; the
+ *   Gauss-Newton matrix is then the exact Hessian of the quadratic model), with mode 2 they are |d| + 1e-10 per sample, as in
+ *   tsff_loss_gauss_newton; log-cosh and poisson have none;
+ *   opts (HOST [7]): tau (> 0: the first damping is tau max_a H[a][a]), gtol, ftol, xtol (>= 0), maxiter, maxfun (whole
+ *   numbers >= 0), lambda_max (> 0), all finite;
+ *   state (device [n_state], in/out), n_state >= tsff_lm_state_size(B, n_active), else -1:
+ *     [status int32 x B, padded to a whole double | B records], the record of lineout b being
+ *     [f, lam, nu, pred, nit, nfev, 0, 0 | x[n_active] | g[n_active] | A[n_active][n_active]]
+ *     -- the accepted point with its loss, gradient and Gauss-Newton matrix, the damping and its growth factor, the reduction the
+ *     model predicts for the trial point now in params, and the counts (whole numbers held as doubles).  All zeros starts a fit
+ *     at params.  status: 0 running, 1 max|g| <= gtol, 2 a step accepted with f_old - F <= ftol f_old, 3 ||delta|| <= xtol
+ *     (||x|| + xtol), 4 nit >= maxiter or nfev >= maxfun, 5 no acceptable step (lam > lambda_max, or lam no longer positive), 6 the first F is not finite.
+ *     A lineout whose status is not 0 is passed over by every later evaluation (its status word is the sweep's skip flag) and
+ *     nothing of it changes.  Chunks of 5 + 4 + 3 evaluations on one state are bit for bit one call of 12;
+ *   x_hist (device [n_evals][B][n_active] or NULL): the point each evaluation ran at;
+ *   eval_hist (device [n_evals][B][1 + n_active + n_active^2] or NULL): its F | G | H.  Both hold NaN for a lineout that was
+ *   terminal before the evaluation.
+ * n_evals == 0 returns 0 and enqueues nothing; n_evals < 0, a null params, weights, active_slots, opts or state, a bad option
+ * or a short state returns -1. */
+int tsff_lm_state_size(int32_t B, int32_t n_active, int64_t *n_doubles);
+int tsff_lm_fit(tsff_handle *h, double *params, const double *fe, const double *e_data, const double *i_data, const double *e_amps,
+                const double *i_amps, const double *noise_e, const double *noise_i, int32_t B, const double *weights,
+                const int32_t *active_slots, int32_t n_active, int32_t n_evals, const double *opts, double *state, int64_t n_state,
+                double *x_hist, double *eval_hist);
 
 
 /* The same plus the gradient w.r.t. the tabulated distribution function itself: grad_fe [B][nvx] (device) =

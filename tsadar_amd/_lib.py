@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtsff.so")
 LIB_PATH = os.environ.get("TSFF_LIBRARY", LIB_PATH)  # A/B experiments: another in-tree build of the same ABI
 
-ABI_VERSION = 16
+ABI_VERSION = 17
 MAX_ION = 4
 NBINS = 1024
 NXI1 = 1024
@@ -171,6 +171,9 @@ _SIGNATURES = {
     "tsff_loss_hess": (C.c_int, [_vp] + [_vp] * 8 + [C.c_int32, c_double_p, C.POINTER(C.c_int32), C.c_int32, _vp, _vp, _vp]),
     "tsff_spectrum_jacobian": (C.c_int, [_vp] + [_vp] * 4 + [C.c_int32, C.POINTER(C.c_int32), C.c_int32, _vp, _vp]),
     "tsff_loss_gauss_newton": (C.c_int, [_vp] + [_vp] * 8 + [C.c_int32, c_double_p, C.POINTER(C.c_int32), C.c_int32, _vp, _vp, _vp]),
+    "tsff_lm_state_size": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "tsff_lm_fit": (C.c_int, [_vp] + [_vp] * 8 + [C.c_int32, c_double_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, c_double_p,
+                              _vp, C.c_int64, _vp, _vp]),
     "tsff_array_loss": (C.c_int, [_vp] + [_vp] * 8 + [C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "tsff_enable_timing": (C.c_int, [_vp, C.c_int32]),
     "tsff_kernel_times": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_int32)]),

@@ -113,6 +113,8 @@ struct JacArgs {
   double* grad;          // [B][n]
   double* gn;            // [B][n][n]
   double w[3];           // weights of S_iaw, S_blue, S_red
+  int fit_denoms;        // want_gn, l2: the denominators are constants folded into w (the fit loss), not |d| + 1e-10
+  const int32_t* skip;   // [B] or nullptr: the persistent workgroups pass over lineout b when skip[b] != 0 (nothing of it is written)
 };
 
 // sample j of the LDS spectrum: the four samples of a strip lie a quarter of the (padded) array apart, so that the threads of a
@@ -139,10 +141,11 @@ __host__ __device__ inline size_t jac_rows_smem_doubles(const KStatic& S, int n)
 }
 
 // l'(d, t) and l''(d, t) w.r.t. the model value t, and the value, with the denominators of _loss_for_hess_fn_ (|d| + 1e-10 for l2)
-__device__ __forceinline__ void jac_loss(int method, double d, double t, double& e, double& e1, double& e2) {
+// or, fit_denoms, with l2's taken as constants that the weights carry (LossFunction.__loss__: e = r^2, e' = -2 r, e'' = 2)
+__device__ __forceinline__ void jac_loss(int method, bool fit_denoms, double d, double t, double& e, double& e1, double& e2) {
   const double r = d - t;
   if (method == TSFF_LOSS_L2) {
-    const double iu = 1.0 / (fabs(d) + 1e-10);
+    const double iu = fit_denoms ? 1.0 : 1.0 / (fabs(d) + 1e-10);
     e = r * r * iu; e1 = -2.0 * r * iu; e2 = 2.0 * iu;
   } else if (method == TSFF_LOSS_LOGCOSH) {
     const double th = tanh(r);
@@ -295,6 +298,7 @@ __global__ __launch_bounds__(kThreads, ((NI == 1 || ROWS) ? 2 : 1)) void k_jac_s
   int slot_prev = -1;
 
   for (int b = blockIdx.x; b < K.B; b += gridDim.x) {
+    if (A.skip && A.skip[b] != 0) continue;   // (the same for the whole workgroup)
     const int slot = S.shared_fe ? 0 : b;
     __syncthreads();   // (the previous lineout's readers of the tables are done)
     if (slot != slot_prev) {
@@ -442,7 +446,7 @@ __global__ __launch_bounds__(kThreads, ((NI == 1 || ROWS) ? 2 : 1)) void k_jac_s
             if (mk & 3) {
               double tv = t.v;
               if (K.noise[f]) tv += K.noise[f][(size_t)b * TSFF_NBINS + pbin];
-              jac_loss(S.loss_method, K.data[f][(size_t)b * TSFF_NBINS + pbin], tv, e, e1, e2);
+              jac_loss(S.loss_method, A.fit_denoms != 0, K.data[f][(size_t)b * TSFF_NBINS + pbin], tv, e, e1, e2);
             }
             e1w[r] = wb * e1; e2w[r] = wb * e2;
             if (f == TSFF_FEATURE_ELE) { lsum[1] += (mk & 1) ? e : 0.0; lsum[2] += (mk & 2) ? e : 0.0; }

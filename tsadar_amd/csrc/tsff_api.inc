@@ -128,6 +128,7 @@ struct tsff_handle {
   tsff::DevBuf htmm, Xmm, cstmm, Wmm, Wmm_unused;   // tsff_loss_hess with the DLM order m: second m-derivative tables
   tsff::DevBuf jrows;              // tsff_spectrum_jacobian / tsff_loss_gauss_newton: per persistent workgroup the row form's spectrum and
                                    // tangents ((1 + n_active) x npts doubles) and the Gauss-Newton call's Jacobian rows (n_active x 1024)
+  tsff::DevBuf lm_ws;              // tsff_lm_fit: the gradient [B][n_active] and Gauss-Newton matrix [B][n_active][n_active] of an evaluation
   size_t smem_adjoint = 0;
   tsff::DevBuf ats_w, ats_ta, ats_tl, ats_lam, ats_M, ats_A, ats_B, ats_C, ats_D, ats_stats;
   int ats_npx = 0, ats_nta = 0, ats_offa = 0, ats_ntl = 0, ats_offl = 0, ats_lam_step = 1, ats_ang_step = 1,
@@ -2307,8 +2308,8 @@ int tsff_loss_hess(tsff_handle* h, const double* params, const double* fe, const
 }
 
 // Jacobian of the spectra and Gauss-Newton curvature (k_jacobian.inc): the deck's table kernels, then k_jac_sweep on persistent
-// workgroups (one lineout per task); tsff_loss_gauss_newton adds k_loss_reduce.  jac_prepare holds everything that can refuse,
-// allocate or upload; jac_enqueue only launches.
+// workgroups (one lineout per task); tsff_loss_gauss_newton adds k_loss_reduce (a call with loss_terms).  jac_prepare holds
+// everything that can refuse, allocate or upload; jac_enqueue only launches.
 constexpr int kJacMaxWG = 1024;   // persistent workgroups of k_jac_sweep (bounds the row scratch: n_active x 1024 doubles each)
 struct JacCall {
   Batch b;
@@ -2359,7 +2360,7 @@ static int jac_enqueue(tsff_handle* h, JacCall& c) {
   TSFF_LAUNCH_FN(h, jac_kernel(h->n_ion, c.width, c.rows), ("k_jac_sweep", h->n_ion, c.width, c.rows), dim3(c.nwg), dim3(kThreads), c.smem, h->stream,
                  h->S, K, c.A);
   TSFF_HIP(h, hipGetLastError());
-  if (c.A.want_gn) {
+  if (c.A.want_gn && c.loss_terms) {
     TSFF_LAUNCH0(h, k_loss_reduce, dim3(1), dim3(kThreads), 0, h->stream, K.lpart, (int)c.b.B, c.loss_terms, (const double*)nullptr, 0L,
                  (double*)nullptr);
     TSFF_HIP(h, hipGetLastError());
@@ -2397,6 +2398,60 @@ int tsff_loss_gauss_newton(tsff_handle* h, const double* params, const double* f
   c.loss_terms = loss_terms;
   if (int rc = jac_prepare(h, c, active_slots, n_active, "tsff_loss_gauss_newton")) return rc;
   return jac_enqueue(h, c);
+}
+
+int tsff_lm_state_size(int32_t B, int32_t n_active, int64_t* n_doubles) {
+  if (B < 1 || n_active < 1 || n_active > kNP_MAX || !n_doubles) return -1;
+  *n_doubles = lm_rec_offset(B) + (int64_t)B * lm_rec_doubles(n_active);
+  return 0;
+}
+
+// the per-lineout Levenberg-Marquardt fit on the device (k_lm.inc): jac_prepare once, then n_evals x (jac_enqueue with want_gn
+// + k_lm_step), all enqueued on the handle's stream.  The status words at the head of the state are the sweep's skip flags: a
+// lineout that has ended is not evaluated again
+int tsff_lm_fit(tsff_handle* h, double* params, const double* fe, const double* e_data, const double* i_data, const double* e_amps,
+                const double* i_amps, const double* noise_e, const double* noise_i, int32_t B, const double* weights,
+                const int32_t* active_slots, int32_t n_active, int32_t n_evals, const double* opts, double* state, int64_t n_state,
+                double* x_hist, double* eval_hist) {
+  DevGuard dg__(h);
+  if (!h) return -1;
+  if (!params || B < 1 || !weights || !active_slots || !opts || !state || n_active < 1 || n_active > h->S.NP || n_evals < 0)
+    return fail(h, -1, "bad argument");
+  const double tau = opts[0], gtol = opts[1], ftol = opts[2], xtol = opts[3], maxiter = opts[4], maxfun = opts[5], lam_max = opts[6];
+  auto whole = [](double v) { return v >= 0.0 && v <= 0x7fffffff && v == std::floor(v); };
+  if (!(tau > 0.0) || !std::isfinite(tau) || !(gtol >= 0.0) || !(ftol >= 0.0) || !(xtol >= 0.0) || !whole(maxiter) || !whole(maxfun) ||
+      !(lam_max > 0.0) || !std::isfinite(lam_max))
+    return fail(h, -1, "bad option (opts = tau > 0, gtol >= 0, ftol >= 0, xtol >= 0, maxiter >= 0, maxfun >= 0, lambda_max > 0, all finite)");
+  int64_t need = 0;
+  if (tsff_lm_state_size(B, n_active, &need) || n_state < need)
+    return fail(h, -1, "state holds %lld doubles, needs %lld", (long long)n_state, (long long)need);
+  JacCall c;
+  c.b = Batch{params, fe, {e_data, i_data}, {e_amps, i_amps}, {noise_e, noise_i}, B};
+  c.A.want_gn = 1;
+  std::copy(weights, weights + 3, c.A.w);
+  c.A.fit_denoms = h->denom_mode == 0;
+  c.A.skip = reinterpret_cast<const int32_t*>(state);
+  if (int rc = jac_prepare(h, c, active_slots, n_active, "tsff_lm_fit")) return rc;
+  if (n_evals == 0) return 0;
+  const size_t n = n_active, row = lm_eval_doubles(n_active);
+  TSFF_ENSURE(h, h->lm_ws, (size_t)B * (n + n * n) * sizeof(double));
+  c.A.grad = h->lm_ws.as<double>();
+  c.A.gn = c.A.grad + (size_t)B * n;
+  LmArgs P{};
+  P.n = n_active; P.B = B; P.NP = h->S.NP;
+  std::copy(active_slots, active_slots + n_active, P.slot);
+  std::copy(weights, weights + 3, P.w);
+  P.tau = tau; P.gtol = gtol; P.ftol = ftol; P.xtol = xtol; P.maxiter = maxiter; P.maxfun = maxfun; P.lam_max = lam_max;
+  const dim3 grid((unsigned)((B + kLmWaves - 1) / kLmWaves));
+  const size_t smem = sizeof(double) * kLmWaves * lm_wave_doubles(n_active);
+  for (int t = 0; t < n_evals; ++t) {
+    if (int rc = jac_enqueue(h, c)) return rc;
+    TSFF_LAUNCH0(h, k_lm_step, grid, dim3(kLmWaves * 64), smem, h->stream, P, (const double*)h->lpart.as<double>(), (const double*)c.A.grad,
+                 (const double*)c.A.gn, params, state, x_hist ? x_hist + (size_t)t * B * n : nullptr,
+                 eval_hist ? eval_hist + (size_t)t * B * row : nullptr);
+    TSFF_HIP(h, hipGetLastError());
+  }
+  return 0;
 }
 
 int tsff_array_loss(tsff_handle* h, const double* params, const double* fe, const double* e_data, const double* i_data,

@@ -19,6 +19,8 @@
 //   k_jac_sweep    jax.jacfwd of a1     : Jacobian of the spectra w.r.t. the leaves and the Gauss-Newton curvature (k_jacobian.inc)
 //   k_adam_step    loops.py:59-95        : one Adam step + best tracking on the packed loss and gradient (tsff_adam_fit, k_adam.inc)
 //   k_lbfgs_step   loops.py:20-56        : one evaluation's step of unbounded L-BFGS-B on the packed loss and gradient (tsff_lbfgs_fit)
+//   k_lm_step      (no reference row)    : one evaluation's step of the per-lineout Levenberg-Marquardt fit on k_jac_sweep's loss,
+//                                          gradient and Gauss-Newton matrix (tsff_lm_fit, k_lm.inc)
 //   k_ang_*        loops.py:167-275      : the angular fit's generator, loss and seed, chain rule and optimiser step (tsff_angular_fit)
 //   k_sph_*        spherical_harmonics.py: the SphericalHarmonics f_e generator and its exact adjoint (tsff_sph_table(_vjp), TSFF_ANG_SPH)
 //   k_arb1v_*      base.py:157-204       : the free-form 1-D f_e generator (Arbitrary1V) and its adjoint (tsff_arb1v_table(_vjp), TSFF_ANG_ARB1V)
@@ -112,6 +114,7 @@ constexpr int kFusedMaxIon = 2;  // k_spectrum_fused is instantiated for n_ion <
 #include "k_jacobian.inc"
 #include "k_adam.inc"
 #include "k_lbfgs.inc"
+#include "k_lm.inc"
 #include "k_angular.inc"
 #include "k_sph.inc"
 #include "k_arb1v.inc"

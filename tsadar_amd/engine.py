@@ -889,6 +889,46 @@ class Engine:
             out["f"] = float(host[4])
         return out
 
+    def lm_fit(self, params, batch, weights, active_slots, n_evals, opts, state=None, hist=False, fe=None):
+        """tsff_lm_fit: ``n_evals`` evaluations of the per-lineout Levenberg-Marquardt fit (tsadar_amd.lm) on the active leaves,
+        enqueued at once; nothing is synchronised.  -> (params [B, NP], state, x_hist [n_evals, B, P] or None, eval_hist
+        [n_evals, B, 1 + P + P * P] (F | G | H) or None) as CUDA tensors.  ``params`` and ``state`` are updated in place when
+        they are float64 CUDA tensors already (pass the returned ones to the next chunk); otherwise they are copied to new ones.
+        ``state=None`` starts a fit (zeros) at ``params``.  ``opts`` = lm.Options (tau, gtol, ftol, xtol, maxiter, maxfun,
+        lam_max).  ``weights``: with ``loss_weights(1, ...)`` every lineout's loss is its own mean loss.  ``fe`` (fe_mode
+        PER_LINEOUT): a constant of the fit.  Read the outcome with :meth:`lm_info`."""
+        from . import lm
+
+        torch = self.torch
+        X = self.dev(params).reshape(-1, self.NP)
+        B = X.shape[0]
+        act = np.ascontiguousarray(active_slots, dtype=np.int32)
+        P = int(act.size)
+        keep, ba = self._batch_args(X, batch, fe)
+        op = np.ascontiguousarray(opts, dtype=np.float64)
+        assert op.size == 7, "opts = (tau, gtol, ftol, xtol, maxiter, maxfun, lam_max)"
+        state = torch.zeros(lm.state_size(B, P), dtype=torch.float64, device=self.device) if state is None else self.dev(state)
+        k = max(int(n_evals), 0)
+        xh = torch.empty((k, B, P), dtype=torch.float64, device=self.device) if hist else None
+        eh = torch.empty((k, B, 1 + P + P * P), dtype=torch.float64, device=self.device) if hist else None
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        self._sync_stream()
+        rc = self.lib.tsff_lm_fit(self.h, *ba, w.ctypes.data_as(L.c_double_p), act.ctypes.data_as(C.POINTER(C.c_int32)), P,
+                                  int(n_evals), op.ctypes.data_as(L.c_double_p), self._ptr(state), int(state.numel()),
+                                  self._ptr(xh), self._ptr(eh))
+        L.check(self.lib, self.h, rc)
+        self._lm_shape = (B, P)
+        return X, state, xh, eh
+
+    def lm_info(self, state, shape=None) -> dict:
+        """The outcome of :meth:`lm_fit` per lineout (one synchronising copy of the state): x [B, P] (the accepted points), f,
+        lam, status (tsadar_amd.lm: RUNNING .. BAD_START), nit, nfev.  ``shape`` = (B, P): of the most recent lm_fit by default."""
+        from . import lm
+
+        B, P = shape if shape is not None else self._lm_shape
+        st = lm.unpack(self.download(state), B, P)
+        return dict(x=st.x, f=st.f, lam=st.lam, status=st.status, nit=st.nit, nfev=st.nfev)
+
     def array_loss(self, params, batch, fe=None):
         torch = self.torch
         X = self.dev(params).reshape(-1, self.NP)

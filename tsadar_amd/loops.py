@@ -7,6 +7,9 @@ The reference alternates ``LossFunction.vg_loss`` (spectra and gradient to the h
 ``Engine.adam_fit`` (tsff_adam_fit: packed loss + gradient and one Adam update per step, k_adam.inc) and synchronises once per
 chunk.  The steps are those of ``tsadar_amd.tree.Adam`` + ``tree.apply_updates`` bit for bit (see include/tsff.h), and the best
 weights are tracked as the reference tracks them: the iterate AFTER the update of the step whose loss was the lowest.
+
+``lm_loop`` has the shape of ``lbfgs_loop`` but is not a drop-in for a loop of the reference: it fits every lineout of the batch
+on its own by Levenberg-Marquardt (tsadar_amd.lm, tsff_lm_fit), where the reference's 1-D loops fit the batch jointly.
 """
 from __future__ import annotations
 
@@ -126,6 +129,61 @@ def lbfgs_loop(config: Dict, loss_fn, previous_weights: Optional[ThomsonParams],
     out = ts_params.copy()
     out.X = eng.download(Xd).reshape(B, -1).copy()
     return res["f"], out
+
+
+LM_CHUNK = 8   # evaluations per enqueued chunk of lm_loop (a lineout that has ended costs the later ones of its chunk nothing)
+
+
+def lm_loop(config: Dict, loss_fn, previous_weights: Optional[ThomsonParams], batch: Dict, chunk: Optional[int] = None,
+            progress=None, info: Optional[Dict] = None) -> Tuple[float, ThomsonParams]:
+    """An opt-in replacement for ``_1d_scipy_loop_`` with its shape -> (best_loss, best_weights): every lineout of the batch is
+    fitted on its own by Levenberg-Marquardt (tsadar_amd.lm; Nielsen's damping on the Gauss-Newton matrix of its loss), run on
+    the device by ``Engine.lm_fit`` (tsff_lm_fit, k_lm.inc).  This is not the reference's optimiser: its 1-D loops minimise the
+    batch's mean loss as one joint problem, although the lineouts do not couple; here each lineout has its own step length and
+    its own stopping point.  A local method: from a start far from the minimum it can end in a side minimum, as any other.
+
+    ``maxiter = num_epochs`` accepted steps and ``maxfun = 2 num_epochs + 10`` evaluations per lineout, tau 1e-3, gtol 1e-8,
+    ftol 1e-12, xtol 1e-10, lam_max 1e12.  The loss of lineout b is its own mean loss (the weights of a batch of one), so the
+    tolerances do not depend on the batch size.  ``best_loss`` is the batch's mean loss at ``best_weights`` as ``vg_loss``
+    returns it there: one evaluation of its loss kernels at the end (the mean of the fit's own f_b is the same quantity from the
+    Jacobian sweep's sums, which lie some 1e-11 of it away -- the two value the narrow ion feature by different kernels -- and
+    ``progress`` and ``info`` report those).  ``previous_weights``: a ThomsonParams to continue from, else a fresh one of ``batch_size`` lineouts.
+    ``chunk``: evaluations per enqueued chunk (default 8); after each chunk the loop synchronises once, stops when every lineout
+    has ended, and reports to ``progress`` -- a tqdm-like object (``set_description``) or a callable ``progress(evaluations,
+    mean loss)``.  ``info``: a dict that receives ``Engine.lm_info`` of the end (x, f, lam, status, nit, nfev per lineout) and
+    ``n_evals``, the evaluations enqueued.
+
+    Not built (NotImplementedError, raised before any device work): ``loss_method`` l1 (its Gauss-Newton matrix vanishes),
+    angular decks, ``distributed=True`` loss functions and a trainable free-form f_e (Arbitrary1V.fval)."""
+    from . import lm
+
+    opt = config["optimizer"]
+    if opt.get("loss_method", "l2") == "l1":
+        raise NotImplementedError("lm_loop: loss_method l1 has no curvature, its Gauss-Newton matrix vanishes (use l2, log-cosh or poisson)")
+    ts_params, diff, act, eng, X, B, w_batch, db, fe = _one_d_setup("lm_loop", config, loss_fn, previous_weights, batch)
+    _, loss_fn.unravel_weights = tree.ravel_pytree(diff)   # (as lbfgs_loop leaves it: vg_loss takes the flat vector)
+    w = eng.loss_weights(1, loss_fn.i_norm, loss_fn.e_norm, config["data"]["ion_loss_scale"])
+    n_epochs = int(opt["num_epochs"])
+    opts = lm.Options(maxiter=n_epochs, maxfun=2 * n_epochs + 10)
+    step = max(1, int(chunk)) if chunk else LM_CHUNK
+    Xd, state, done = eng.dev(X), None, 0
+    while True:
+        Xd, state, _, _ = eng.lm_fit(Xd, db, w, act, step, opts, state=state, fe=fe)
+        done += step
+        res = eng.lm_info(state)   # the chunk's one synchronisation
+        loss = float(np.mean(res["f"]))
+        if progress is not None:
+            _report(progress, done, loss, f"Evaluation {done}, Loss {loss:.2e}")
+        if not np.any(res["status"] == lm.RUNNING):
+            break
+    if info is not None:
+        info.update(res, n_evals=done)
+    gm = np.zeros(eng.NP, dtype=np.uint8)
+    gm[act] = 1
+    host = eng.download(eng.loss_grad(Xd, db, w_batch, gm, fe=fe)[0])   # the loss terms of vg_loss's kernels at the returned weights
+    out = ts_params.copy()
+    out.X = eng.download(Xd).reshape(B, -1).copy()
+    return float(np.dot(host, w_batch)), out
 
 
 class _Generator(NamedTuple):
