@@ -1,7 +1,8 @@
-"""usage: isa_compare.py parent.s new.s -- the register / spill / scratch / occupancy / code-length listing of the four spectrum kernel
-families (k_spectrum, k_spectrum_fused, k_forward_pairs, k_spectrum_rows) from two `hipcc -S --cuda-device-only` dumps of the whole
-library, the way profiles/r10_selects_isa.txt and r12_loops_isa.txt list them, and the instantiations that break the conditions
-(spilled VGPRs and scratch bytes not above, occupancy not below the parent's)."""
+"""usage: isa_compare.py parent.s new.s [family prefix ...] -- the register / spill / scratch / occupancy / code-length listing of
+kernel families from two `hipcc -S --cuda-device-only` dumps of the whole library, the way profiles/r10_selects_isa.txt and
+r12_loops_isa.txt list them, and the instantiations that break the conditions (spilled VGPRs and scratch bytes not above, occupancy
+not below the parent's).  The families are name prefixes such as `k_hess_pairs<` `k_jac_sweep<`; without any, the four spectrum
+kernel families (k_spectrum, k_spectrum_fused, k_forward_pairs, k_spectrum_rows)."""
 import re
 import subprocess
 import sys
@@ -37,13 +38,15 @@ def main():
     a, oa = by_name(a, oa)
     b, ob = by_name(b, ob)
     short = {m: m for m in oa}
+    families = tuple(sys.argv[3:]) or FAMILIES
+    these = "the four families" if families == FAMILIES else "the families " + " ".join(families)
     print("kernels: parent %d, new %d, same names (without argument lists) in the same order: %s" % (len(oa), len(ob), oa == ob))
     print("same set of names: %s" % (sorted(oa) == sorted(ob)))
-    fam = [m for m in oa if short[m].startswith(FAMILIES)]
+    fam = [m for m in oa if short[m].startswith(families)]
     rest = [m for m in oa if m not in fam]
-    print("kernels outside the four families with different text:", ", ".join(m for m in rest if a[m]["text"] != b[m]["text"]) or "none")
-    print("kernels outside the four families: %d, with different text: %d" % (len(rest), sum(a[m]["text"] != b[m]["text"] for m in rest)))
-    print("kernels of the four families: %d, with identical text: %d" % (len(fam), sum(a[m]["text"] == b[m]["text"] for m in fam)))
+    print("kernels outside %s with different text:" % these, ", ".join(m for m in rest if a[m]["text"] != b[m]["text"]) or "none")
+    print("kernels outside %s: %d, with different text: %d" % (these, len(rest), sum(a[m]["text"] != b[m]["text"] for m in rest)))
+    print("kernels of %s: %d, with identical text: %d" % (these, len(fam), sum(a[m]["text"] == b[m]["text"] for m in fam)))
     print()
     print("%-52s %9s %9s %9s %7s %10s %5s %15s" % ("instantiation (parent -> new)", "VGPRs", "SGPRs", "spillV", "spillS", "scratch B", "occ", "codeLenInByte"))
     broken = []

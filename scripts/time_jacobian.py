@@ -7,6 +7,12 @@ defaults and its six active leaves -- against what they replace, and write profi
     ``--parent-tree DIR`` (a checkout of the parent commit with its library built) this part runs in a child process on that
     tree's package and library, on the same machine in the same invocation; without it, on this tree's forward (unchanged code).
 
+``--tangent`` adds the DLM order to the leaves at the same batch, so that the planner picks the tangent form of the sweep
+(k_jac_sweep<1, 3, false>) instead of the row form.  With ``--parent-tree`` every timed part of --what runs on both trees, each in a
+child process of its own under a time limit, parent and this tree alternating for ``--rounds`` rounds; the first non-zero exit ends
+the run.  ``ab`` then holds per part both trees' rounds and medians, s = the largest relative deviation of the parent's own rounds
+from its median, and ``within`` = (this tree's median <= the parent's median x (1 + s)); the parts' top-level ms are this tree's medians.
+
 Clocks are warm as in bench.py: every timed region follows an untimed spin of the same call (--spin-ms), and is K calls between
 two device synchronisations.  ``--kernel-times`` adds the device time of the sweep kernel from rocprofv3 --kernel-trace runs of
 their own, one per call type (the Jacobian call and the Gauss-Newton call run different tails of the same kernel), each averaged
@@ -34,18 +40,21 @@ for p in (os.path.join(THIS, "tests"), ROOT):   # (decks and util are this tree'
 import numpy as np  # noqa: E402
 
 
-def setup(B):
+TANGENT_LEAVES = ("Te", "ne", "Ti", "Va", "lam", "amp1", "m")
+
+
+def setup(B, tangent=False):
     import decks
     import util
     from tsadar_amd.engine import Engine
     from tsadar_amd.params import SlotMap
 
-    cfg = decks.deck_fit()
+    cfg = decks.deck_fit(active=TANGENT_LEAVES) if tangent else decks.deck_fit()
     sa = util.sa_fit(B)
     nb = 64   # (the data of 64 oracle lineouts, tiled: the timing does not depend on the values)
     small = util.synthetic_batch(cfg, util.sa_fit(nb), nb, seed=3)
     batch = {k: np.tile(v, (B // nb,) + (1,) * (np.ndim(v) - 1)) for k, v in small.items()}
-    normed = util.random_lineouts(cfg, B, seed=4)
+    normed = util.random_lineouts(cfg, B, seed=4, ranges=dict(m=(2.1, 4.3)) if tangent else None)
     act = [s for _, s in SlotMap(cfg["parameters"], True).active_leaves]
     eng = Engine(cfg, sa)
     X = eng.dev(util.normed_to_matrix(normed, 1))
@@ -96,7 +105,7 @@ def central_fn(eng, X, db, act, h=1e-6):
 
 
 def calls(args):
-    eng, X, db, w, act = setup(args.batch)
+    eng, X, db, w, act = setup(args.batch, args.tangent)
     out = {}
     if "central" in args.what:
         out["central"] = (central_fn(eng, X, db, act), eng)
@@ -134,8 +143,44 @@ def child(args, what, tree=None, extra=()):
         env["TSFF_TREE"] = os.path.abspath(tree)
         env.pop("TSFF_LIBRARY", None)
     cmd = [sys.executable, os.path.abspath(__file__), "--child", "--what", *what, "--batch", str(args.batch), "--steps", str(args.steps),
-           "--spin-ms", str(args.spin_ms), *extra]
+           "--spin-ms", str(args.spin_ms), *(["--tangent"] if args.tangent else []), *extra]
     return cmd, env
+
+
+def run_child(args, what, tree=None):
+    """measure() of ``what`` in a child process on ``tree`` (None: this tree), under a time limit -> its result, or None"""
+    cmd, env = child(args, what, tree=tree)
+    r = subprocess.run(["timeout", "-k", "10", str(args.child_timeout)] + cmd, env=env, capture_output=True, text=True)
+    line = [l for l in r.stdout.splitlines() if l.startswith("RESULT ")]
+    if r.returncode != 0 or not line:
+        print(f"child on {tree or THIS}: exit {r.returncode}", r.stdout[-2000:], r.stderr[-2000:], file=sys.stderr)
+        return None
+    return json.loads(line[-1][7:])
+
+
+def both_trees(args, res):
+    """every part of --what on the parent's tree and on this one, alternating for args.rounds rounds (central: parent, first round)"""
+    parts = [w for w in args.what if w != "central"]
+    ms = {"parent": {}, "new": {}}
+    for rnd in range(args.rounds):
+        for tag, tree in (("parent", args.parent_tree), ("new", None)):
+            what = parts + (["central"] if tag == "parent" and rnd == 0 and "central" in args.what else [])
+            out = run_child(args, what, tree)
+            if out is None:
+                return False
+            for k, v in out.items():
+                if k == "central_ms" or not k.endswith("_ms"):
+                    res[k if k.startswith("central") or tag == "new" else "parent_" + k] = v
+                else:
+                    ms[tag].setdefault(k[:-3], []).append(v)
+    res["ab"] = {}
+    for part in parts:
+        p, n = ms["parent"][part], ms["new"][part]
+        pm, nm = float(np.median(p)), float(np.median(n))
+        s = max(abs(v - pm) / pm for v in p)
+        res[part + "_ms"] = nm
+        res["ab"][part] = {"parent_ms": p, "new_ms": n, "parent_median_ms": pm, "new_median_ms": nm, "s": s, "within": bool(nm <= pm * (1.0 + s))}
+    return True
 
 
 def kernel_times(args, what):
@@ -169,6 +214,9 @@ def main():
     ap.add_argument("--spin-ms", type=float, default=300.0)
     ap.add_argument("--what", nargs="+", default=["jacobian", "gauss_newton", "loss_hess", "central"])
     ap.add_argument("--parent-tree", default=None, help="checkout of the parent commit with its library built: the central differences run there")
+    ap.add_argument("--tangent", action="store_true", help="the DLM order among the leaves: the tangent form of the sweep")
+    ap.add_argument("--rounds", type=int, default=3, help="with --parent-tree: rounds of (parent, this tree)")
+    ap.add_argument("--child-timeout", type=int, default=300, help="seconds per child process")
     ap.add_argument("--kernel-times", action="store_true", help="add rocprofv3 kernel times from a separate run")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--once", action="store_true", help=argparse.SUPPRESS)
@@ -180,21 +228,17 @@ def main():
         else:
             print("RESULT " + json.dumps(measure(args)), flush=True)
         return 0
-    res = {"shape": {"B": args.batch, "deck": "tests/decks.deck_fit()", "points_per_pixel": 1, "nvx": 128}, "steps": args.steps,
+    deck = "tests/decks.deck_fit(active=%r), m drawn in [2.1, 4.3]" % (TANGENT_LEAVES,) if args.tangent else "tests/decks.deck_fit()"
+    res = {"shape": {"B": args.batch, "deck": deck, "points_per_pixel": 1, "nvx": 128}, "steps": args.steps,
            "clock_warmup_ms": args.spin_ms}
     if args.parent_tree:
-        args.what = [w for w in args.what if w != "central"]
-        cmd, env = child(args, ["central"], tree=args.parent_tree)
-        r = subprocess.run(cmd, env=env, capture_output=True, text=True)
-        line = [l for l in r.stdout.splitlines() if l.startswith("RESULT ")]
-        if not line:
-            print(r.stdout[-2000:], r.stderr[-2000:], file=sys.stderr)
+        if not both_trees(args, res):
             return 1
-        res.update(json.loads(line[-1][7:]))
+        res["rounds"] = args.rounds
         res["central_on"] = "the parent commit's package and library (child process, same machine, same invocation)"
     else:
         res["central_on"] = "this tree's tsff_forward"
-    res.update(measure(args))
+        res.update(measure(args))
     n = res["n_active"]
     res["central_forward_calls"] = 2 * n
     if "jacobian_ms" in res and "central_ms" in res:
