@@ -22,6 +22,8 @@
  *       generate_spectra.py:193-216, irf.py:5-47, thomson_diagnostic.py:78-107           tsff_ats_setup / tsff_ats_spectrum
  *   jax reverse mode through the above (equinox.filter_value_and_grad, loss_function.py:108)
  *       tsff_loss_grad(_fe), tsff_form_factor_grad, tsff_form_factor_2d_grad, tsff_ats_adjoint
+ *   jax.jvp of FormFactor.__call__, and of add_ATS_IRF + reduce_ATS_to_resunit (the reference has no such call; its post-fit
+ *       half on angular decks, postprocess.py:106-136, differentiates the whole chain twice)   tsff_form_factor_jvp, tsff_ats_jvp
  *   LossFunction.h_loss_wrt_params (equinox.filter_hessian) inverse/loss_function.py:170-188  tsff_loss_hess
  *   jax.jacfwd of ThomsonScatteringDiagnostic.__call__ w.r.t. the normalised leaves (the reference has no such call: its
  *       uncertainties come from the full Hessian, postprocess.py:188-251)           tsff_spectrum_jacobian / tsff_loss_gauss_newton
@@ -39,8 +41,8 @@
  *   - return value 0 = success, negative = error, text via tsff_last_error();
  *   - a refused call (negative return) of tsff_forward, tsff_loss_grad(_packed, _fe), tsff_loss_hess, tsff_spectrum_jacobian,
  *     tsff_loss_gauss_newton, tsff_array_loss,
- *     tsff_adam_fit, tsff_lm_fit, tsff_angular_fit, tsff_form_factor(_grad), tsff_form_factor_2d(_range, _save, _grad), tsff_ats_spectrum
- *     and tsff_ats_adjoint has enqueued nothing: their arguments, LDS budgets and buffers are checked before the first
+ *     tsff_adam_fit, tsff_lm_fit, tsff_angular_fit, tsff_form_factor(_grad, _jvp), tsff_form_factor_2d(_range, _save, _grad),
+ *     tsff_ats_spectrum, tsff_ats_adjoint and tsff_ats_jvp has enqueued nothing: their arguments, LDS budgets and buffers are checked before the first
  *     launch, and tsff_last_launch reports an empty list (other entry points may have enqueued work before a failure);
  *   - a call that breaks several conditions is refused for the first of: the entry point's own arguments (-1), the active slot
  *     list (-1), a leaf the configuration does not have (-2), the leaf A (-3), the batch arguments (-1, then -2),
@@ -233,6 +235,18 @@ int tsff_form_factor(tsff_handle *h, int32_t feature, const double *phys, const 
 int tsff_form_factor_grad(tsff_handle *h, int32_t feature, const double *phys, const double *fe, int32_t B,
                           const double *Pbar, double *grad_phys, double *grad_fe);
 
+/* Forward mode of tsff_form_factor -- what jax.jvp of FormFactor.__call__ (core/physics/form_factor.py:163-298) gives -- for n_dir
+ * directions at once:  P_dot[k] = dP/dphys . phys_dot[k] + dP/dfe . fe_dot[k],  the same arguments, parameter handling (PHYSICAL
+ * parameters, Ti tying) and table convention as tsff_form_factor / tsff_loss_hess (the Z' and W lookups carry their slope, the
+ * Hermite ln f_e lookup its true derivative).
+ *   phys_dot [n_dir][B][NP] (device); fe_dot [n_dir][B][nvx] (device) or NULL: no direction of f_e (fe_mode PER_LINEOUT only: -2);
+ *   P [B][G][npts][n_angles] (device) or NULL: the value, bit for bit tsff_form_factor's;  P_dot [n_dir][B][G][npts][n_angles].
+ * The directions run three to a launch (the groups loop inside the call, n_dir is unbounded); with fe_dot each of the three
+ * carries its own tangent tables in LDS (13 KB + 32 nvx B each), one per launch when three do not fit, -2 when one does not.
+ * Two calls give bit-identical results (no atomics).  A null phys, phys_dot or P_dot, or n_dir < 1: -1. */
+int tsff_form_factor_jvp(tsff_handle *h, int32_t feature, const double *phys, const double *fe, int32_t B, int32_t n_dir,
+                         const double *phys_dot, const double *fe_dot, double *P, double *P_dot);
+
 /* FormFactor.calc_in_2D (core/physics/form_factor.py:449-587, with rotate :300-324 and calc_chi_vals :349-388)
  * for a 2-D electron distribution fe2d[nv][nv] on the grid linspace(-6 + dv/2, 6 - dv/2, nv) (first index = v_x;
  * one table shared by all lineouts when shared_fe != 0, else [B][nv][nv]): P[B][G][npts][n_angles].  `phys` holds
@@ -299,6 +313,15 @@ int tsff_ats_spectrum(tsff_handle *h, const double *P, const double *e_amps /* d
  * the blue / red split of the wavelength axis and carries no gradient, like in the reference's jnp.where. */
 int tsff_ats_adjoint(tsff_handle *h, const double *P, const double *e_amps, double lam, double amp1, double amp2,
                      const double *Ebar, double *Pbar, double *amp_bar);
+/* Forward mode of tsff_ats_spectrum -- jax.jvp of add_ATS_IRF + reduce_ATS_to_resunit (irf.py:5-47,
+ * thomson_diagnostic.py:78-107) behind the angular electron_spectrum -- for n_dir directions:
+ *   P_dot [n_dir][G][npts][n_angles] (device), amp_dot [n_dir][2] (HOST): the tangents of (amp1, amp2);
+ *   ThryE [rows][npts / lam_step] (device) or NULL: the value, bit for bit tsff_ats_spectrum's;  ThryE_dot [n_dir][rows][npts / lam_step].
+ * The weight matrix, the notch filter, the convolutions and the block means are linear; the two row normalisations take their
+ * tangent through 1 / max at the arg-max of the value (the first in index order).  `lam` only selects between the amplitudes
+ * and carries no tangent here (it does through P). */
+int tsff_ats_jvp(tsff_handle *h, const double *P, const double *P_dot, int32_t n_dir, const double *e_amps, double lam, double amp1,
+                 double amp2, const double *amp_dot, double *ThryE, double *ThryE_dot);
 
 /* ThomsonScatteringDiagnostic.__call__: ThryE/ThryI [B][1024].  noise_* may be NULL (= 0).
  * params: normalised leaves [B][NP]; fe: [B][nvx] when fe_mode == PER_LINEOUT else NULL. */

@@ -181,6 +181,58 @@ __global__ __launch_bounds__(kThreads) void k_ats_rownorm_adj(const double* __re
   }
 }
 
+// ---- forward mode of the two row normalisations (tsff_ats_jvp; the linear stages run the forward kernels on the tangent image) ----
+// tangent of k_ats_rownorm: Y = Bm sc, sc = mM / mB with the maxima where k_ats_rowstats found them (the first in index order), so
+// Y' = Bm' sc + Bm sc', sc' = M'[jM] / mB - mM Bm'[jB] / mB^2.  Ys: the SCALED image Y (k_ats_rownorm has run), Bd: Bm' in, Y' out.
+__global__ __launch_bounds__(kThreads) void k_ats_rownorm_jvp(const double* __restrict__ Ys, const double* __restrict__ stats,
+                                                              const double* __restrict__ Md, int npts, double* __restrict__ Bd) {
+  const int r = blockIdx.x;
+  const double mM = stats[4 * r], mB = stats[4 * r + 2];
+  const int jM = (int)stats[4 * r + 1], jB = (int)stats[4 * r + 3];
+  const double sc = mM / mB;
+  const double rel = Md[(size_t)r * npts + jM] / mM - Bd[(size_t)r * npts + jB] / mB;   // sc' / sc
+  __syncthreads();   // (Bm'[jB] is read by every thread before its owner overwrites it)
+  for (int j = threadIdx.x; j < npts; j += kThreads)
+    Bd[(size_t)r * npts + j] = Bd[(size_t)r * npts + j] * sc + Ys[(size_t)r * npts + j] * rel;
+}
+
+// tangent of k_ats_resunit: out = e_amps D / mx amp with D the block means, mx = D[js] its row maximum (the first in index order) and
+// amp = amp1 | amp2 by the wavelength, so out' = e_amps ((D' / mx - D mx' / mx^2) amp + D / mx amp'), mx' = D'[js].  `lam` only
+// selects between the amplitudes.  One workgroup per output row; at most TSFF_NBINS resolution units per row.
+__global__ __launch_bounds__(kThreads) void k_ats_resunit_jvp(const double* __restrict__ Y, const double* __restrict__ Yd,
+                                                              const double* __restrict__ lam_nm, int npts, int lam_step, int ang_step,
+                                                              int row_start, const double* __restrict__ e_amps, double lam, double amp1,
+                                                              double amp2, double amp1_dot, double amp2_dot, double* __restrict__ out_dot) {
+  __shared__ double red[8];
+  __shared__ double Dl[TSFF_NBINS], Dd[TSFF_NBINS];
+  const int R = blockIdx.x, nJ = npts / lam_step;
+  const int r0 = (row_start + R) * ang_step;
+  const double cnt = (double)(ang_step * lam_step);
+  double mx = -1e300;
+  int js = 0;
+  for (int J = threadIdx.x; J < nJ; J += kThreads) {
+    double acc = 0.0, accd = 0.0;
+    for (int dr = 0; dr < ang_step; ++dr)
+      for (int dj = 0; dj < lam_step; ++dj) {
+        acc += Y[(size_t)(r0 + dr) * npts + J * lam_step + dj];
+        accd += Yd[(size_t)(r0 + dr) * npts + J * lam_step + dj];
+      }
+    acc /= cnt; accd /= cnt;   // (the value as k_ats_resunit forms it: the same arg-max)
+    Dl[J] = acc; Dd[J] = accd;
+    if (acc > mx) { mx = acc; js = J; }
+  }
+  block_argmax(mx, js, red);   // (its barriers publish Dl and Dd)
+  const double mxd = Dd[js], ea = e_amps[R];
+  for (int J = threadIdx.x; J < nJ; J += kThreads) {
+    double lb = 0.0;
+    for (int dj = 0; dj < lam_step; ++dj) lb += lam_nm[J * lam_step + dj];
+    lb /= (double)lam_step;
+    const bool blue = lb < lam;
+    const double u = Dl[J] / mx, ud = (Dd[J] - u * mxd) / mx;
+    out_dot[(size_t)R * nJ + J] = ea * (ud * (blue ? amp1 : amp2) + u * (blue ? amp1_dot : amp2_dot));
+  }
+}
+
 // reverse of k_ats_conv: Xbar[i] (+)= sum_s taps[s] Ybar[i - off - s]
 __global__ void k_ats_conv_adj(const double* __restrict__ Yb, const double* __restrict__ taps, int nt, int off, int along_rows,
                                int npx, int npts, int accumulate, double* __restrict__ Xb) {

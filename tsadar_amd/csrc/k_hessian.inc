@@ -17,6 +17,7 @@
 struct HD {   // hyper-dual number: value, the two first derivatives and the mixed second derivative
   double v, a, b, ab;
   static constexpr bool kSecondOrder = true;
+  static constexpr int kLanes = 0;   // (no tangent lanes that carry a table direction of their own: MTabT)
   static __device__ __forceinline__ HD of(double c) { return HD{c, 0.0, 0.0, 0.0}; }
 };
 __device__ __forceinline__ HD hd(double v) { return HD{v, 0.0, 0.0, 0.0}; }
@@ -131,6 +132,9 @@ __device__ __forceinline__ HD hd_xm(HD x, HD m, double f, double fx, double fm, 
 
 // the tables' dependence on the DLM order m (with_m): dW/dm, d2W/dm2 on the xi2 grid and the Hermite coefficients of
 // d ln f_e / dm and d2 ln f_e / dm2; m is the physical order with its two seeds
+// The general case of a first-order number with tangent lanes (N::kLanes > 0, k_ffjvp): lane k < nlane carries a table direction
+// of its own, Wd[k][1640] = the tangent of W and hcd[k][2 nvx] = the Hermite coefficients of the tangent of ln f_e along it, which
+// the lookups add to that lane directly.  m is the special case of one direction shared by every lane through m's seeds.
 template <class N>
 struct MTabT {
   const double* Wm;
@@ -139,6 +143,10 @@ struct MTabT {
   const double2* hcmm;   // (second order only)
   N m;
   bool on;
+  int nlane = 0;         // lanes with a table direction (0: none)
+  const double* Wd = nullptr;
+  const double2* hcd = nullptr;
+  int hstride = 0;       // double2 per lane of hcd (2 nvx)
 };
 using MTab = MTabT<HD>;
 
@@ -161,6 +169,19 @@ __device__ __forceinline__ N hermite_hd(const Tables& T, const MTabT<N>& M, N x)
   const int i = (int)fl;
   double H, d1, d2;
   cubic_at(T.hc, i, t, T.idv, H, d1, d2);
+  if constexpr (N::kLanes > 0) {
+    if (M.nlane > 0) {
+      N r = hd_chain(x, H, d1, d2);
+#pragma unroll
+      for (int k = 0; k < N::kLanes; ++k)
+        if (k < M.nlane) {
+          double Hk, u1, u2;
+          cubic_at(M.hcd + (size_t)k * M.hstride, i, t, T.idv, Hk, u1, u2);
+          r.d[k] += Hk;
+        }
+      return r;
+    }
+  }
   if (!M.on) return hd_chain(x, H, d1, d2);
   double Hm, Hxm, unused, Hmm = 0.0, u1, u2;
   cubic_at(M.hcm, i, t, T.idv, Hm, Hxm, unused);
@@ -217,7 +238,20 @@ __device__ __forceinline__ N point_hd(const BaseT<N>& b, const BaseT<N>& bn, boo
   double w, dw;
   w_lookup(T.W, b.xe.v, w, dw);
   N Wl;
-  if (M.on) {   // W(x, m): no curvature in x; dW/dm and d2W/dm2 interpolated in the same cell, the slope of dW/dm for the mixed term
+  bool lanes = false;
+  if constexpr (N::kLanes > 0) lanes = M.nlane > 0;
+  if (lanes) {   // W(x) with a table tangent per lane, interpolated in the same cell
+    Wl = hd_chain(b.xe, w, dw, 0.0);
+    if constexpr (N::kLanes > 0) {
+#pragma unroll
+      for (int k = 0; k < N::kLanes; ++k)
+        if (k < M.nlane) {
+          double wk, dwk;
+          w_lookup(M.Wd + (size_t)k * kNXi2, b.xe.v, wk, dwk);
+          Wl.d[k] += wk;
+        }
+    }
+  } else if (M.on) {   // W(x, m): no curvature in x; dW/dm and d2W/dm2 interpolated in the same cell, the slope of dW/dm for the mixed term
     double wm, dwm, wmm = 0.0, dwmm;
     w_lookup(M.Wm, b.xe.v, wm, dwm);
     if constexpr (N::kSecondOrder) w_lookup(M.Wmm, b.xe.v, wmm, dwmm);

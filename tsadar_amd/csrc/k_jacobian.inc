@@ -19,6 +19,7 @@ template <int W>
 struct TN {   // a value and W first-order tangents
   double v, d[W];
   static constexpr bool kSecondOrder = false;
+  static constexpr int kLanes = W;   // (each tangent may carry a table direction of its own: MTabT)
   static __device__ __forceinline__ TN of(double c) {
     TN r;
     r.v = c;

@@ -117,6 +117,58 @@ __global__ __launch_bounds__(kThreads) void k_fe_prepare(KStatic S, const double
 // k_fe_vectors: grid B, 256 threads.  Outputs ht/htm [B][nvx], X [B][4][1024] = (A, s, dA/dm, ds/dm) zero
 // padded, cst [B][2] = (sum fdif, d/dm).
 // ------------------------------------------------------------------------------------------
+// fe_direction_rows: the tangent of a lineout's tables along one direction of ln f_e, given at the nodes (dln [nvx], LDS) -- the
+// DLM order m for k_fe_vectors, any direction of f_e for k_fe_direction.  All threads; T: the lineout's own ln f_e table (hc filled),
+// rat [1024]: ratmod = exp(H(xi1)) of the lineout.  Leaves (d ln f_e, its node slope) in htm / htm_out and their Hermite
+// coefficients in hcm, ratmod' = ratmod H'(xi1) (zero outside the grid) and its central differences in ratm / rdfm, the (A, s) rows
+// of the W-table GEMM in XA / XB [1024], and returns this thread's part of sum fdif' (the caller block_sums it).  Ends without a barrier.
+__device__ __forceinline__ double fe_direction_rows(const KStatic& S, const Tables& T, const double* dln, const double* rat, double2* htm,
+                                                    double2* hcm, double* ratm, double* rdfm, double2* __restrict__ htm_out,
+                                                    double* __restrict__ XA, double* __restrict__ XB) {
+  const int tid = threadIdx.x, nvx = S.nvx;
+  for (int i = tid; i < nvx; i += kThreads) {
+    const double ml = i > 0 ? (dln[i] - dln[i - 1]) / S.dv : 0.0, mr = i < nvx - 1 ? (dln[i + 1] - dln[i]) / S.dv : 0.0;
+    const double sm = i == 0 ? mr : (i == nvx - 1 ? ml : 0.5 * (ml + mr));
+    htm[i] = make_double2(dln[i], sm);
+    htm_out[i] = htm[i];
+  }
+  __syncthreads();
+  for (int i = tid; i < nvx - 1; i += kThreads) hermite_coeffs(htm[i], htm[i + 1], S.dv, hcm[2 * i], hcm[2 * i + 1]);
+  __syncthreads();
+  Tables Tm = T;
+  Tm.hc = hcm;
+  for (int i = tid; i < kNXi1; i += kThreads) {
+    const double x = S.xi1[i];
+    double Hm, dHm;
+    hermite_lookup_c(Tm, x, Hm, dHm);
+    const bool out = x < T.vx0 || x > T.vxlast;
+    ratm[i] = out ? 0.0 : rat[i] * Hm;
+  }
+  __syncthreads();
+  const double h1 = S.xi1[1] - S.xi1[0];
+  for (int i = tid; i < kNXi1; i += kThreads) {
+    double gm;
+    if (i == 0) gm = (ratm[1] - ratm[0]) / h1;
+    else if (i == kNXi1 - 1) gm = (ratm[i] - ratm[i - 1]) / h1;
+    else gm = (ratm[i + 1] - ratm[i - 1]) / (2.0 * h1);
+    rdfm[i] = gm;
+  }
+  __syncthreads();
+  double c1 = 0.0;
+  for (int i = tid; i < kNXi1; i += kThreads) {
+    double Am = 0.0, Bm = 0.0;
+    if (i < kNXi1 - 2) {
+      const double x0 = S.xi1[i], x1 = S.xi1[i + 1];
+      const double ih = 1.0 / (x1 - x0), mid = 0.5 * (x1 + x0);
+      const double fdm = rdfm[i + 1] - rdfm[i], fam = 0.5 * (rdfm[i + 1] + rdfm[i]);
+      Bm = fdm * ih; Am = fam - mid * Bm;
+      c1 += fdm;
+    }
+    XA[i] = Am; XB[i] = Bm;
+  }
+  return c1;
+}
+
 template <int NI>
 __global__ __launch_bounds__(kThreads) void k_fe_vectors(KStatic S, const double* __restrict__ fe_in, int fe_mode,
                                                          const double* __restrict__ params, double2* __restrict__ ht_out,
@@ -169,64 +221,91 @@ __global__ __launch_bounds__(kThreads) void k_fe_vectors(KStatic S, const double
   __syncthreads();
   for (int i = tid; i < nvx; i += kThreads) {
     const double dl = i > 0 ? (lnfe[i] - lnfe[i - 1]) / S.dv : 0.0, dr = i < nvx - 1 ? (lnfe[i + 1] - lnfe[i]) / S.dv : 0.0;
-    const double ml = i > 0 ? (dln[i] - dln[i - 1]) / S.dv : 0.0, mr = i < nvx - 1 ? (dln[i + 1] - dln[i]) / S.dv : 0.0;
     const double sl = i == 0 ? dr : (i == nvx - 1 ? dl : 0.5 * (dl + dr));
-    const double sm = i == 0 ? mr : (i == nvx - 1 ? ml : 0.5 * (ml + mr));
     ht[i] = make_double2(lnfe[i], sl);
-    htm[i] = make_double2(dln[i], sm);
     ht_out[(size_t)b * nvx + i] = ht[i];
-    htm_out[(size_t)b * nvx + i] = htm[i];
   }
   __syncthreads();
-  for (int i = tid; i < nvx - 1; i += kThreads) {
-    hermite_coeffs(ht[i], ht[i + 1], S.dv, hc[2 * i], hc[2 * i + 1]);
-    hermite_coeffs(htm[i], htm[i + 1], S.dv, hcm[2 * i], hcm[2 * i + 1]);
-  }
+  for (int i = tid; i < nvx - 1; i += kThreads) hermite_coeffs(ht[i], ht[i + 1], S.dv, hc[2 * i], hc[2 * i + 1]);
   __syncthreads();
   Tables T;
   T.zp = nullptr; T.W = nullptr; T.ht = ht; T.hc = hc; T.nvx = nvx; T.etab = nullptr;
   tables_set_grid(T, S.vx0, S.dv, nvx);
-  Tables Tm = T;
-  Tm.hc = hcm;
   for (int i = tid; i < kNXi1; i += kThreads) {
-    const double x = S.xi1[i];
-    double H, dH, Hm, dHm;
-    hermite_lookup_c(T, x, H, dH);
-    hermite_lookup_c(Tm, x, Hm, dHm);
-    const bool out = x < T.vx0 || x > T.vxlast;
-    const double r = exp(H);
-    rat[i] = r;
-    ratm[i] = out ? 0.0 : r * Hm;
+    double H, dH;
+    hermite_lookup_c(T, S.xi1[i], H, dH);
+    rat[i] = exp(H);
   }
   __syncthreads();
   const double h1 = S.xi1[1] - S.xi1[0];
   for (int i = tid; i < kNXi1; i += kThreads) {
-    double g, gm;
-    if (i == 0) { g = (rat[1] - rat[0]) / h1; gm = (ratm[1] - ratm[0]) / h1; }
-    else if (i == kNXi1 - 1) { g = (rat[i] - rat[i - 1]) / h1; gm = (ratm[i] - ratm[i - 1]) / h1; }
-    else { g = (rat[i + 1] - rat[i - 1]) / (2.0 * h1); gm = (ratm[i + 1] - ratm[i - 1]) / (2.0 * h1); }
+    double g;
+    if (i == 0) g = (rat[1] - rat[0]) / h1;
+    else if (i == kNXi1 - 1) g = (rat[i] - rat[i - 1]) / h1;
+    else g = (rat[i + 1] - rat[i - 1]) / (2.0 * h1);
     rdf[i] = g;
-    rdfm[i] = gm;
   }
-  __syncthreads();
-  double c0 = 0.0, c1 = 0.0;
   double* Xb = X + (size_t)b * 4 * kNXi1;
+  // the m direction (its barriers publish rdf as well)
+  double c1 = fe_direction_rows(S, T, dln, rat, htm, hcm, ratm, rdfm, htm_out + (size_t)b * nvx, Xb + 2 * kNXi1, Xb + 3 * kNXi1);
+  double c0 = 0.0;
   for (int i = tid; i < kNXi1; i += kThreads) {
-    double A = 0.0, Bs = 0.0, Am = 0.0, Bm = 0.0;
+    double A = 0.0, Bs = 0.0;
     if (i < kNXi1 - 2) {
       const double x0 = S.xi1[i], x1 = S.xi1[i + 1];
       const double ih = 1.0 / (x1 - x0), mid = 0.5 * (x1 + x0);
       const double fd = rdf[i + 1] - rdf[i], fa = 0.5 * (rdf[i + 1] + rdf[i]);
-      const double fdm = rdfm[i + 1] - rdfm[i], fam = 0.5 * (rdfm[i + 1] + rdfm[i]);
       Bs = fd * ih; A = fa - mid * Bs;
-      Bm = fdm * ih; Am = fam - mid * Bm;
-      c0 += fd; c1 += fdm;
+      c0 += fd;
     }
-    Xb[i] = A; Xb[kNXi1 + i] = Bs; Xb[2 * kNXi1 + i] = Am; Xb[3 * kNXi1 + i] = Bm;
+    Xb[i] = A; Xb[kNXi1 + i] = Bs;
   }
   c0 = block_sum(c0, red);
   c1 = block_sum(c1, red);
   if (tid == 0) { cst[2 * b] = c0; cst[2 * b + 1] = c1; }
+}
+
+// k_fe_direction: the table tangents of tsff_form_factor_jvp.  grid (n_dir * B), 256 threads; workgroup d * B + b takes direction d of
+// lineout b: d ln f_e = fe_dot / fe at the nodes, then fe_direction_rows, the body k_fe_vectors runs for the DLM order.  Outputs, all
+// indexed by r = d * B + b: htd [r][nvx] = (d ln f_e, its node slope), X [r][4][1024] = (A', s', 0, 0) and cst [r][2] = (sum fdif', 0)
+// -- the layout of the GEMM without m-tangents (k_wgemm<2>), which returns W' [r][1640] in place of W.
+__global__ __launch_bounds__(kThreads) void k_fe_direction(KStatic S, const double* __restrict__ fe, const double* __restrict__ fe_dot,
+                                                           const double2* __restrict__ ht_in, int B, double2* __restrict__ htd_out,
+                                                           double* __restrict__ X, double* __restrict__ cst) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  double2* ht = reinterpret_cast<double2*>(smem);         // [nvx]   (the layout of k_fe_vectors)
+  double2* htm = ht + S.nvx;                              // [nvx]
+  double2* hc = htm + S.nvx;                              // [2 nvx]
+  double2* hcm = hc + 2 * S.nvx;                          // [2 nvx]
+  double* lnfe = reinterpret_cast<double*>(hcm + 2 * S.nvx);  // [nvx] (unused here)
+  double* dln = lnfe + S.nvx;                             // [nvx]
+  double* rat = dln + S.nvx;                              // [1024]
+  double* ratm = rat + kNXi1;                             // [1024]
+  double* rdf = ratm + kNXi1;                             // [1024] (unused here)
+  double* rdfm = rdf + kNXi1;                             // [1024]
+  double* red = rdfm + kNXi1;                             // [8]
+  const int r = blockIdx.x, b = r % B, tid = threadIdx.x, nvx = S.nvx;
+  for (int i = tid; i < nvx; i += kThreads) {
+    ht[i] = ht_in[(size_t)b * nvx + i];
+    dln[i] = fe_dot[(size_t)r * nvx + i] / fe[(size_t)b * nvx + i];
+  }
+  __syncthreads();
+  for (int i = tid; i < nvx - 1; i += kThreads) hermite_coeffs(ht[i], ht[i + 1], S.dv, hc[2 * i], hc[2 * i + 1]);
+  __syncthreads();
+  Tables T;
+  T.zp = nullptr; T.W = nullptr; T.ht = ht; T.hc = hc; T.nvx = nvx; T.etab = nullptr;
+  tables_set_grid(T, S.vx0, S.dv, nvx);
+  for (int i = tid; i < kNXi1; i += kThreads) {
+    double H, dH;
+    hermite_lookup_c(T, S.xi1[i], H, dH);
+    rat[i] = exp(H);
+  }
+  __syncthreads();
+  double* Xr = X + (size_t)r * 4 * kNXi1;
+  double c1 = fe_direction_rows(S, T, dln, rat, htm, hcm, ratm, rdfm, htd_out + (size_t)r * nvx, Xr, Xr + kNXi1);
+  for (int i = tid; i < kNXi1; i += kThreads) { Xr[2 * kNXi1 + i] = 0.0; Xr[3 * kNXi1 + i] = 0.0; }
+  c1 = block_sum(c1, red);
+  if (tid == 0) { cst[2 * r] = c1; cst[2 * r + 1] = 0.0; }
 }
 
 // k_wgemm: W[b][q] = c0_b + sum_i Lg[q][i] (A_b[i] + xi2[q] s_b[i]) and the same for d/dm: the GEMM

@@ -128,6 +128,8 @@ struct tsff_handle {
   tsff::DevBuf htmm, Xmm, cstmm, Wmm, Wmm_unused;   // tsff_loss_hess with the DLM order m: second m-derivative tables
   tsff::DevBuf jrows;              // tsff_spectrum_jacobian / tsff_loss_gauss_newton: per persistent workgroup the row form's spectrum and
                                    // tangents ((1 + n_active) x npts doubles) and the Gauss-Newton call's Jacobian rows (n_active x 1024)
+  tsff::DevBuf jv_htd, jv_X, jv_cst, jv_Wd;   // tsff_form_factor_jvp: the table tangents of a block of directions (k_fe_direction + k_wgemm<2>)
+  tsff::DevBuf ats_E;              // tsff_ats_jvp: the third tangent image (ats_C, ats_D and this one hold M', A', B')
   tsff::DevBuf lm_ws;              // tsff_lm_fit: the gradient [B][n_active] and Gauss-Newton matrix [B][n_active][n_active] of an evaluation
   size_t smem_adjoint = 0;
   tsff::DevBuf ats_w, ats_ta, ats_tl, ats_lam, ats_M, ats_A, ats_B, ats_C, ats_D, ats_stats;
@@ -388,6 +390,8 @@ static auto jac_kernel(int n_ion, int width, bool rows) {
 static auto form_factor_adj_kernel(int n_ion, bool grad_fe) {
   return with_ion<TSFF_MAX_ION>(n_ion, [&](auto N) { return grad_fe ? &k_form_factor_adj<N.value, 2> : &k_form_factor_adj<N.value, 0>; });
 }
+// the forward mode of the 1-D form factor: groups of three directions
+static auto ffjvp_kernel(int n_ion) { return with_ion<TSFF_MAX_ION>(n_ion, [](auto N) { return &k_ffjvp<N.value, 3>; }); }
 static auto form_factor_2d_kernel(int n_ion, bool lds, bool save) {
   return with_ion<TSFF_MAX_ION>(n_ion, [&](auto N) {
     return with_bools(lds, save, [&](auto LDS, auto SAVE) { return &k_form_factor_2d<N.value, LDS.value, LDS.value ? TSFF_2D_GROUPS_LDS : TSFF_2D_GROUPS_L2, SAVE.value>; });
@@ -430,6 +434,8 @@ static hipError_t raise_lds_limits(int n_ion) {
   raise(jac_kernel(n_ion, 1, false));
   raise(jac_kernel(n_ion, 3, false));
   raise(jac_kernel(n_ion, 3, true));
+  raise(ffjvp_kernel(n_ion));
+  raise(&k_fe_direction);
   raise(&k_fe_adjoint);
   raise(&k_ff2d_table_adj);
   raise(&k_wgemm_w, kWgemmWSmem);
@@ -1401,6 +1407,98 @@ int tsff_form_factor_grad(tsff_handle* h, int32_t feature, const double* phys, c
   return form_factor_adj_enqueue(h, p, phys, fe, Pbar, grad_phys, grad_fe);
 }
 
+// ---- its forward mode: groups of kFfjvpW directions per launch, the table tangents built for a block of directions at a time
+constexpr int kFfjvpW = 3;
+struct FormFactorJvpPlan {
+  int feature = 0, B = 0, n_dir = 0;
+  bool tab = false;        // fe_dot given: every lane of a group carries a table direction
+  int gw = kFfjvpW;        // directions per group (1: the LDS holds one table lane only)
+  int dblk = 0;            // directions whose table tangents are built at once (a multiple of gw)
+  size_t smem = 0;
+  dim3 grid;
+};
+
+static int form_factor_jvp_prepare(tsff_handle* h, int feature, int B, int n_dir, bool tab, FormFactorJvpPlan& p) {
+  p.feature = feature; p.B = B; p.n_dir = n_dir; p.tab = tab;
+  p.gw = kFfjvpW;
+  p.smem = sizeof(double) * ffjvp_smem_doubles(h->S, tab ? kFfjvpW : 0, kFfjvpW);
+  if (p.smem > kLdsLimit && tab) {   // one table lane per group before giving up
+    p.gw = 1;
+    p.smem = sizeof(double) * ffjvp_smem_doubles(h->S, 1, kFfjvpW);
+  }
+  if (p.smem > kLdsLimit)
+    return fail(h, -2, "tsff_form_factor_jvp: LDS budget exceeded (%zu B with nvx = %d, %d angles%s): reduce nvx", p.smem, h->S.nvx,
+                h->S.n_angles, tab ? " and one table direction per group" : "");
+  p.grid = dim3(B, angle_chunks(h, B));
+  // (blocks of about 384 table rows: 12 MB of GEMM input, a grid of the GEMM that fills the device)
+  const int want = std::max(1, 384 / std::max(B, 1));
+  p.dblk = std::min(std::max(p.gw, want / p.gw * p.gw), (n_dir + p.gw - 1) / p.gw * p.gw);
+  if (int rc = ensure_workspace(h, B)) return rc;
+  if (tab) {
+    const size_t rows = (size_t)std::min(p.dblk, n_dir) * B;
+    TSFF_ENSURE(h, h->jv_htd, rows * h->S.nvx * sizeof(double2));
+    TSFF_ENSURE(h, h->jv_X, rows * 4 * kNXi1 * sizeof(double));
+    TSFF_ENSURE(h, h->jv_cst, rows * 2 * sizeof(double));
+    TSFF_ENSURE(h, h->jv_Wd, rows * kNXi2 * sizeof(double));
+  }
+  return 0;
+}
+
+static int form_factor_jvp_enqueue(tsff_handle* h, const FormFactorJvpPlan& p, const double* phys, const double* fe, const double* phys_dot,
+                                   const double* fe_dot, double* P, double* P_dot) {
+  const int B = p.B;
+  const size_t nvx = h->S.nvx;
+  if (int rc = timing_begin(h)) return rc;
+  KCall K{};
+  K.params = phys; K.B = B;
+  if (int rc = prepare_tables(h, phys, fe, B, K)) return rc;
+  if (P) {   // the value by the shipped forward: tsff_form_factor's bit for bit
+    TSFF_LAUNCH_FN(h, form_factor_kernel(h->n_ion), ("k_form_factor", h->n_ion), p.grid, dim3(kThreads), h->smem_spectrum, h->stream, h->S, K,
+                   p.feature, h->S.omgs[p.feature], h->S.npts, P);
+    TSFF_HIP(h, hipGetLastError());
+  }
+  for (int d0 = 0; d0 < p.n_dir; d0 += p.dblk) {
+    const int nb = std::min(p.dblk, p.n_dir - d0), rows = nb * B;
+    if (p.tab) {
+      TSFF_LAUNCH0(h, k_fe_direction, dim3(rows), dim3(kThreads), h->smem_vectors, h->stream, h->S, fe, fe_dot + (size_t)d0 * B * nvx, K.ht, B,
+                   h->jv_htd.as<double2>(), h->jv_X.as<double>(), h->jv_cst.as<double>());
+      const int nM = (rows + kGM / 2 - 1) / (kGM / 2), nQ = (kNXi2 + kGN - 1) / kGN;
+      TSFF_LAUNCH(h, k_wgemm, (2), dim3(8 * ((nM + 7) / 8) * nQ), dim3(kThreads), 0, h->stream, h->S.lg, h->jv_X.as<double>(),
+                  h->jv_cst.as<double>(), h->S.xi2, rows, h->jv_Wd.as<double>(), (double*)nullptr, h->kw_lo, h->kw_hi);
+      TSFF_HIP(h, hipGetLastError());
+    }
+    for (int g0 = 0; g0 < nb; g0 += p.gw) {
+      FfjvpArgs A{};
+      A.d0 = d0 + g0; A.nd = std::min(p.gw, nb - g0);
+      A.nlane = p.tab ? A.nd : 0;
+      A.phys_dot = phys_dot;
+      A.htd = p.tab ? h->jv_htd.as<double2>() + (size_t)g0 * B * nvx : nullptr;
+      A.Wd = p.tab ? h->jv_Wd.as<double>() + (size_t)g0 * B * kNXi2 : nullptr;
+      A.P_dot = P_dot;
+      // (the LDS is carved for the lanes of this group: a last partial group asks for less than the plan's budget)
+      const size_t smem = sizeof(double) * ffjvp_smem_doubles(h->S, A.nlane, kFfjvpW);
+      TSFF_LAUNCH_FN(h, ffjvp_kernel(h->n_ion), ("k_ffjvp", h->n_ion, kFfjvpW), p.grid, dim3(kThreads), smem, h->stream, h->S, K, A, p.feature,
+                     h->S.omgs[p.feature], h->S.npts);
+    }
+    TSFF_HIP(h, hipGetLastError());
+  }
+  return timing_end(h);
+}
+
+int tsff_form_factor_jvp(tsff_handle* h, int32_t feature, const double* phys, const double* fe, int32_t B, int32_t n_dir,
+                         const double* phys_dot, const double* fe_dot, double* P, double* P_dot) {
+  DevGuard dg__(h);
+  if (!h) return -1;
+  if (!phys || !phys_dot || !P_dot || B < 1 || n_dir < 1 || feature < 0 || feature > 1) return fail(h, -1, "bad argument");
+  if (h->fe_mode == TSFF_FE_DLM) return fail(h, -3, "tsff_form_factor_jvp takes explicit distribution functions (fe_mode SHARED or PER_LINEOUT)");
+  if (fe_dot && h->fe_mode != TSFF_FE_PER_LINEOUT) return fail(h, -2, "a direction of f_e needs fe_mode == TSFF_FE_PER_LINEOUT");
+  FormFactorJvpPlan p;
+  int rc = check_fe(h, fe);
+  if (!rc) rc = form_factor_jvp_prepare(h, feature, B, n_dir, fe_dot != nullptr, p);
+  if (rc) return rc;
+  return form_factor_jvp_enqueue(h, p, phys, fe, phys_dot, fe_dot, P, P_dot);
+}
+
 // ---- the 2-D form factor (save: with the projection records of its points for the adjoint that follows)
 struct FormFactor2dPlan {
   int feature = 0, nv = 0, B = 0;
@@ -1730,6 +1828,57 @@ int tsff_ats_adjoint(tsff_handle* h, const double* P, const double* e_amps, doub
   amp_bar[0] = amp_bar[1] = 0.0;
   for (int r = 0; r < rows; ++r) { amp_bar[0] += hb[2 * r]; amp_bar[1] += hb[2 * r + 1]; }
   return 0;
+}
+
+// ---- forward mode of the ATS chain.  The linear stages (weights, the two convolutions) run on each tangent image with the shipped
+// kernels; the two row normalisations take their tangent through 1 / max at the value's arg-max (k_ats_rownorm_jvp, k_ats_resunit_jvp)
+static int ats_jvp_prepare(tsff_handle* h) {
+  if (int rc = ats_prepare(h, true)) return rc;   // (the row statistics and two of the three tangent images are the reverse chain's buffers)
+  TSFF_ENSURE(h, h->ats_E, (size_t)h->ats_npx * h->S.npts * sizeof(double));
+  return 0;
+}
+
+static int ats_jvp_enqueue(tsff_handle* h, const double* P, const double* P_dot, int n_dir, const double* e_amps, double lam, double amp1,
+                           double amp2, const double* amp_dot, double* ThryE, double* ThryE_dot) {
+  const int npts = h->S.npts, npx = h->ats_npx, rows = h->ats_row_end - h->ats_row_start, nJ = npts / h->ats_lam_step;
+  dim3 block(kThreads), grid((npts + kThreads - 1) / kThreads, npx);
+  double* M = h->ats_M.as<double>();
+  double* Bm = h->ats_B.as<double>();
+  double* Md = h->ats_C.as<double>();
+  double* Ad = h->ats_D.as<double>();
+  double* Bd = h->ats_E.as<double>();
+  double* stats = h->ats_stats.as<double>();
+  if (int rc = timing_begin(h)) return rc;
+  // the value: tsff_ats_spectrum's launches, with the row statistics taken before k_ats_rownorm scales the image in place
+  ats_forward_chain(h, P);
+  TSFF_LAUNCH0(h, k_ats_rowstats, dim3(npx), block, 0, h->stream, M, Bm, npts, stats);
+  TSFF_LAUNCH0(h, k_ats_rownorm, dim3(npx), block, 0, h->stream, M, Bm, npts);
+  if (ThryE)
+    TSFF_LAUNCH0(h, k_ats_resunit, dim3(rows), block, 0, h->stream, Bm, h->ats_lam.as<double>(), npts, h->ats_lam_step, h->ats_ang_step,
+                 h->ats_row_start, e_amps, lam, amp1, amp2, (const double*)nullptr, ThryE);
+  TSFF_HIP(h, hipGetLastError());
+  const size_t pimg = (size_t)h->S.G * npts * h->S.n_angles;
+  for (int d = 0; d < n_dir; ++d) {
+    TSFF_LAUNCH0(h, k_ats_weights, grid, block, 0, h->stream, P_dot + (size_t)d * pimg, h->ats_w.as<double>(), h->S.filt, h->S.G, npts,
+                 h->S.n_angles, npx, Md);
+    TSFF_LAUNCH0(h, k_ats_conv, grid, block, 0, h->stream, Md, h->ats_ta.as<double>(), h->ats_nta, h->ats_offa, 1, npx, npts, Ad);
+    TSFF_LAUNCH0(h, k_ats_conv, grid, block, 0, h->stream, Ad, h->ats_tl.as<double>(), h->ats_ntl, h->ats_offl, 0, npx, npts, Bd);
+    TSFF_LAUNCH0(h, k_ats_rownorm_jvp, dim3(npx), block, 0, h->stream, Bm, stats, Md, npts, Bd);
+    TSFF_LAUNCH0(h, k_ats_resunit_jvp, dim3(rows), block, 0, h->stream, Bm, Bd, h->ats_lam.as<double>(), npts, h->ats_lam_step,
+                 h->ats_ang_step, h->ats_row_start, e_amps, lam, amp1, amp2, amp_dot[2 * d], amp_dot[2 * d + 1],
+                 ThryE_dot + (size_t)d * rows * nJ);
+    TSFF_HIP(h, hipGetLastError());
+  }
+  return timing_end(h);
+}
+
+int tsff_ats_jvp(tsff_handle* h, const double* P, const double* P_dot, int32_t n_dir, const double* e_amps, double lam, double amp1,
+                 double amp2, const double* amp_dot, double* ThryE, double* ThryE_dot) {
+  DevGuard dg__(h);
+  if (!h) return -1;
+  if (!P || !P_dot || !e_amps || !amp_dot || !ThryE_dot || n_dir < 1) return fail(h, -1, "bad argument");
+  if (int rc = ats_jvp_prepare(h)) return rc;
+  return ats_jvp_enqueue(h, P, P_dot, n_dir, e_amps, lam, amp1, amp2, amp_dot, ThryE, ThryE_dot);
 }
 
 // the KCall of a batch and its tables.  Launches only: the batch is checked (check_batch) and the workspace sized

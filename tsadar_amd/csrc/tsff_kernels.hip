@@ -17,7 +17,9 @@
 //   k_chain.inc    a12, a14, a15         : the chain's rules around the sweeps (amplitudes, loss, their adjoint, gradient tail), once
 //   k_hess_pairs   a16                   : exact per-lineout Hessian of the fit loss (hyper-dual forward mode, k_hessian.inc)
 //   k_jac_sweep    jax.jacfwd of a1     : Jacobian of the spectra w.r.t. the leaves and the Gauss-Newton curvature (k_jacobian.inc)
-//   k_adam_step    loops.py:59-95        : one Adam step + best tracking on the packed loss and gradient (tsff_adam_fit, k_adam.inc)
+//   k_ffjvp        jax.jvp of a4-a10     : forward mode of k_form_factor for arbitrary directions of the physical parameters and of f_e
+//                                          (k_ffjvp.inc; k_fe_direction: the table tangents; k_ats_*_jvp: the ARTS chain's tangent form)
+//   k_adam_step    loops.py:59-95       : one Adam step + best tracking on the packed loss and gradient (tsff_adam_fit, k_adam.inc)
 //   k_lbfgs_step   loops.py:20-56        : one evaluation's step of unbounded L-BFGS-B on the packed loss and gradient (tsff_lbfgs_fit)
 //   k_lm_step      (no reference row)    : one evaluation's step of the per-lineout Levenberg-Marquardt fit on k_jac_sweep's loss,
 //                                          gradient and Gauss-Newton matrix (tsff_lm_fit, k_lm.inc)
@@ -112,6 +114,7 @@ constexpr int kFusedMaxIon = 2;  // k_spectrum_fused is instantiated for n_ion <
 #include "k_peak.inc"
 #include "k_hessian.inc"
 #include "k_jacobian.inc"
+#include "k_ffjvp.inc"
 #include "k_adam.inc"
 #include "k_lbfgs.inc"
 #include "k_lm.inc"

@@ -551,3 +551,18 @@ def arbitrary_1v_vjp(fval: np.ndarray, g_fe: np.ndarray) -> np.ndarray:
     g_f = (g_fe / dv - np.sum(g_fe * fe, axis=-1, keepdims=True)) / Z
     g_u = g_f * (-np.log(10.0) * f) * (98.0 * u)
     return g_u @ S
+
+
+def arbitrary_1v_jvp(fval: np.ndarray, dfval: np.ndarray = None) -> np.ndarray:
+    """Forward mode of arbitrary_1v for one lineout: fval [nvx], dfval [n, nvx] -> d f_e [n, nvx] along each direction.
+    ``dfval=None``: every unit direction, i.e. the Jacobian rows J[j] = d f_e / d fval[j] (arbitrary_1v_vjp(fval, g) = g @ J.T)."""
+    fval = np.asarray(fval, dtype=np.float64).reshape(-1)
+    nvx = fval.size
+    dv = 12.0 / nvx
+    S = butterworth_matrix(nvx)
+    dfval = np.eye(nvx) if dfval is None else np.asarray(dfval, dtype=np.float64).reshape(-1, nvx)
+    u = S @ fval
+    f = np.power(10.0, -((7.0 * u) ** 2.0))
+    Z = np.sum(f)
+    df = (f * (-np.log(10.0)) * (98.0 * u))[None, :] * (dfval @ S.T)
+    return df / (Z * dv) - (f / (Z * dv))[None, :] * np.sum(df, axis=1, keepdims=True) / Z

@@ -408,6 +408,27 @@ class Engine:
                                                                  self._ptr(Pb), self._ptr(gp), self._ptr(gf)))
         return gp, gf
 
+    def form_factor_jvp(self, feature, phys, fe, phys_dot, fe_dot=None, want_P=False):
+        """Forward mode of form_factor (tsff_form_factor_jvp): phys_dot [n_dir, B, NP] and fe_dot [n_dir, B, nvx] (or None: no
+        direction of f_e) -> (P [B, G, npts, n_angles] or None, P_dot [n_dir, B, G, npts, n_angles]) as CUDA tensors,
+        P_dot[k] = dP/dphys . phys_dot[k] + dP/dfe . fe_dot[k]; nothing is synchronised."""
+        torch = self.torch
+        phys_d = self.dev(phys).reshape(-1, self.NP)
+        B = phys_d.shape[0]
+        pd = self.dev(phys_dot).reshape(-1, B, self.NP)
+        n_dir = int(pd.shape[0])
+        fe_d = self.dev(fe)
+        fd = self.dev(fe_dot)
+        if fd is not None:
+            fd = fd.reshape(n_dir, B, self.nvx)
+        G, NA = int(self._cfg_struct.num_grad_points), int(self._cfg_struct.n_angles)
+        P = torch.empty((B, G, self.npts, NA), dtype=torch.float64, device=self.device) if want_P else None
+        Pd = torch.empty((n_dir, B, G, self.npts, NA), dtype=torch.float64, device=self.device)
+        self._sync_stream()
+        L.check(self.lib, self.h, self.lib.tsff_form_factor_jvp(self.h, int(feature), self._ptr(phys_d), self._ptr(fe_d), B, n_dir,
+                                                                self._ptr(pd), self._ptr(fd), self._ptr(P), self._ptr(Pd)))
+        return P, Pd
+
     def form_factor_2d(self, feature, phys, fe2d, ud_angle=0.0, va_angle=0.0, point_range=None, out=None, save=False):
         """FormFactor.calc_in_2D: phys [B, NP] PHYSICAL parameters, fe2d [nv, nv] (shared) or [B, nv, nv]
         -> P [B, G, npts, n_angles].  ``point_range = (begin, end)`` evaluates that slice of the flat point list only
@@ -532,6 +553,26 @@ class Engine:
                                        self._ptr(Pbar), ab)
         L.check(self.lib, self.h, rc)
         return Pbar, (float(ab[0]), float(ab[1]))
+
+    def ats_jvp(self, P, P_dot, e_amps, lam, amp1, amp2, amp_dot=None, want_E=False):
+        """Forward mode of ats_spectrum (tsff_ats_jvp): P [G, npts, n_angles], P_dot [n_dir, G, npts, n_angles], amp_dot
+        [n_dir, 2] the tangents of (amp1, amp2) (None: zeros) -> (ThryE [rows, n_lam] or None, ThryE_dot [n_dir, rows, n_lam])
+        as CUDA tensors; nothing is synchronised."""
+        torch = self.torch
+        Pd = self.dev(P)
+        Pt = self.dev(P_dot).reshape((-1,) + tuple(Pd.shape))
+        n_dir = int(Pt.shape[0])
+        ea = self.dev(np.broadcast_to(np.asarray(e_amps, dtype=np.float64).reshape(-1), (self._ats_shape[0],)).copy()
+                      if not torch.is_tensor(e_amps) else e_amps.reshape(-1))
+        assert ea.numel() == self._ats_shape[0]
+        ad = np.zeros((n_dir, 2)) if amp_dot is None else np.ascontiguousarray(amp_dot, dtype=np.float64).reshape(n_dir, 2)
+        E = torch.empty(self._ats_shape, dtype=torch.float64, device=self.device) if want_E else None
+        Ed = torch.empty((n_dir,) + tuple(self._ats_shape), dtype=torch.float64, device=self.device)
+        self._sync_stream()
+        rc = self.lib.tsff_ats_jvp(self.h, self._ptr(Pd), self._ptr(Pt), n_dir, self._ptr(ea), float(lam), float(amp1), float(amp2),
+                                   ad.ctypes.data_as(L.c_double_p), self._ptr(E), self._ptr(Ed))
+        L.check(self.lib, self.h, rc)
+        return E, Ed
 
     def forward(self, params, e_amps, i_amps, noise_e=None, noise_i=None, fe=None):
         torch = self.torch

@@ -376,9 +376,42 @@ class LossFunction:
         value = float(np.dot(terms.cpu().numpy(), w))
         return value, [E.cpu().numpy(), weights()]
 
+    def _angular_array_loss(self, E, ThryI, lamE, batch):
+        """``post_loss`` of one ARTS image (calc_ei_error with denom = [ThryI, ThryE], reduce nanmean(axis=1)): E [rows, n_lam]
+        (noise added), lamE the resolution-unit axis.  -> (loss [rows], sqdev): per angular row the mean over the blue columns
+        plus the mean over the red columns, halved when both are fitted; sqdev["ele"] the nan_to_num'ed error image."""
+        d = np.asarray(batch["e_data"], dtype=np.float64)
+        method = self.cfg["optimizer"]["loss_method"]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            if method == "l1":
+                err = np.abs(d - E) / E
+            elif method == "l2":
+                err = np.square(d - E) / E
+            elif method == "log-cosh":
+                err = np.log(np.cosh(d - E))
+            else:
+                err = E - d * np.log(E)
+        ext, r = self.cfg["other"]["extraoptions"], self.cfg["data"]["fit_rng"]
+        e_err = np.zeros(E.shape[0])
+        sq = np.zeros(d.shape)
+        for on, lo, hi in ((ext["fit_EPWb"], r["blue_min"], r["blue_max"]), (ext["fit_EPWr"], r["red_min"], r["red_max"])):
+            if on:
+                masked = np.where(((lamE > lo) & (lamE < hi))[None, :], err, np.nan)
+                with np.errstate(invalid="ignore"):
+                    e_err = e_err + np.nanmean(masked, axis=1)
+                sq = sq + np.nan_to_num(masked)
+        if ext["fit_EPWb"] and ext["fit_EPWr"]:
+            e_err = e_err * 0.5
+        return e_err, {"ele": sq, "ion": np.zeros(np.shape(batch["i_data"]))}
+
     def array_loss(self, weights: ThomsonParams, batch: Dict):
         """loss_function.py:375-384 (``post_loss``): per-lineout nanmean(axis=1) with the theory spectra as
-        denominators.  -> (loss[B], sqdev{ele, ion}, ThryE, ThryI, params)."""
+        denominators.  -> (loss[B], sqdev{ele, ion}, ThryE, ThryI, params).  Angular decks: B is the angular rows of the one
+        image, the electron feature only (ARTS measures no ion feature: ThryI = 0 + noise_i, sqdev["ion"] zeros)."""
+        if getattr(self, "angular", False):
+            E, ThryI, lamE, _ = self.ts_diag(weights, batch)
+            total, sqdev = self._angular_array_loss(E, ThryI, lamE, batch)
+            return total, sqdev, E, ThryI, weights()
         eng = self.ts_diag.engine(weights.activate)
         X = weights.to_matrix()
         B = X.shape[0]
@@ -417,7 +450,8 @@ class LossFunction:
             raise ValueError(f"h_loss_wrt_params: unknown method {method!r} (central or exact)")
         if method == "exact":
             if getattr(self, "angular", False):
-                raise NotImplementedError("h_loss_wrt_params(method='exact') is not built for angular_full decks")
+                raise NotImplementedError("h_loss_wrt_params(method='exact') is not built for angular_full decks "
+                                          "(their Gauss-Newton curvature and sigmas: angular_gn_loss_wrt_params)")
             if getattr(weights, "fval", None) is not None and (weights.slots.fval_active or weights.slots.fval2d_active):
                 raise NotImplementedError("h_loss_wrt_params(method='exact'): the Hessian over the free-form f_e values "
                                           "(nvx table leaves) is not built")
@@ -458,7 +492,8 @@ class LossFunction:
     def _refuse_jacobian(self, weights: ThomsonParams, what: str):
         """What the Jacobian path is not built for, refused before any device work (as ``method="exact"`` does)."""
         if getattr(self, "angular", False):
-            raise NotImplementedError(f"{what} is not built for angular_full decks")
+            raise NotImplementedError(f"{what} is not built for angular_full decks (they have angular_jacobian and "
+                                      "angular_gn_loss_wrt_params)")
         if getattr(weights, "fval", None) is not None and (weights.slots.fval_active or weights.slots.fval2d_active):
             raise NotImplementedError(f"{what}: the Jacobian w.r.t. the free-form f_e values (nvx table leaves) is not built")
 
@@ -508,3 +543,134 @@ class LossFunction:
             for b_, ((sp2, k2), _) in enumerate(leaves):
                 hess.setdefault(sp1, {}).setdefault(k1, {}).setdefault(sp2, {})[k2] = np.diag(H[:, a, b_])
         return hess
+
+    # ---- the post-fit half of angular (ARTS) decks: Jacobian of the image, Gauss-Newton curvature, sigmas -----------------
+    def _refuse_angular_postfit(self, weights: ThomsonParams, what: str):
+        """What the angular Jacobian path is not built for, refused before any device work."""
+        if not getattr(self, "angular", False):
+            raise NotImplementedError(f"{what} is for angular_full decks (1-D decks: jacobian / gn_loss_wrt_params)")
+        if getattr(self, "multiplex_ang", False):
+            raise NotImplementedError(f"{what} is not built for multiplexed angular decks")
+        if self.distributed:
+            raise NotImplementedError(f"{what} is not built for distributed=True (one plasma condition: nothing to shard)")
+        if int(getattr(weights, "fe_dim", 1)) == 2:
+            raise NotImplementedError(f"{what}: the forward mode through the rotate-and-project sampler of a 2-D f_e is not built")
+
+    def _angular_directions(self, weights: ThomsonParams):
+        """The fitted leaves of an angular deck as directions of the device calls: -> (names, phys_dot [n, NP], fe_dot [n, nvx] or
+        None, amp_dot [n, 2]) in ravel order -- the leaves ``_vg_angular_adjoint`` differentiates.  Scalars: the forward of the
+        host transform (scale * sigmoid'(x), a tied Ti copied); the DLM order: d f_e / dm by central differences with the adjoint
+        path's h = 1e-6; ``Arbitrary1V.fval``: one direction per value, the rows of the host generator's Jacobian."""
+        from . import distribution as Dist
+
+        sm = weights.slots
+        x = weights.X[0]
+        sg = 1.0 / (1.0 + np.exp(-x))
+        dact = sm.scale * np.where(sm.sigmoid.astype(bool), sg * (1.0 - sg), 1.0)
+        nvx = int(self.cfg["parameters"]["electron"]["fe"]["nvx"])
+        names, pd, fd, ad = [], [], [], []
+        zero_p, zero_f = np.zeros(sm.NP), np.zeros(nvx)
+        for name, s in tree.get_filter_spec(None, weights):
+            if s == tree.FVAL_SLOT:
+                J = Dist.arbitrary_1v_jvp(weights.fval[0])
+                for j in range(J.shape[0]):
+                    names.append((name[0], name[1], j)); pd.append(zero_p); fd.append(J[j]); ad.append((0.0, 0.0))
+            elif s in (tree.GEN2D_SLOT, tree.FVAL2D_SLOT):
+                raise NotImplementedError("angular_jacobian: 2-D distribution-function leaves are not built")
+            elif s == L.P_M:
+                m, hm = float(weights.physical_matrix()[0, L.P_M]), 1e-6
+                names.append(name); pd.append(zero_p); ad.append((0.0, 0.0))
+                fd.append(dact[s] * (Dist.dlm(m + hm, nvx) - Dist.dlm(m - hm, nvx)) / (2 * hm))
+            else:
+                p = np.zeros(sm.NP)
+                p[s] = dact[s]
+                if s == L.P_ION0 + L.ION_TI:
+                    for i in range(1, sm.n_ion):
+                        if sm.ti_same[i]:
+                            p[L.P_ION0 + 4 * i + L.ION_TI] = dact[s]
+                names.append(name); pd.append(p); fd.append(zero_f)
+                ad.append((dact[s] if s == L.P_AMP1 else 0.0, dact[s] if s == L.P_AMP2 else 0.0))
+        with_fe = any(f is not zero_f for f in fd)
+        return names, np.array(pd).reshape(-1, sm.NP), (np.array(fd).reshape(-1, nvx) if with_fe else None), np.array(ad).reshape(-1, 2)
+
+    def _angular_jacobian_device(self, weights: ThomsonParams, batch: Dict, chunk: int):
+        """-> (engine, names, J [n, rows, cols] device, ThryE [rows, cols] device (the model image, no noise), lamE)."""
+        eng = self.ts_diag.engine(weights.activate)
+        torch = eng.torch
+        names, pd, fd, ad = self._angular_directions(weights)
+        if not names:
+            raise ValueError("angular_jacobian: the deck has no fitted leaf")
+        lam_step = self.ts_diag._ats_prepare(eng, batch)
+        phys = weights.physical_matrix()
+        p = phys[0]
+        fe1 = np.ascontiguousarray(np.asarray(weights()["electron"]["fe"], dtype=np.float64).reshape(1, -1))
+        rows = eng._ats_shape[0]
+        e_amps = np.array(np.broadcast_to(np.asarray(batch["e_amps"], dtype=np.float64).reshape(-1, 1), (rows, 1)))
+        phys_d, fe_d, ea_d = eng.dev(phys), eng.dev(fe1), eng.dev(e_amps)
+        J, E, P = [], None, None
+        chunk = max(int(chunk), 1)
+        for k0 in range(0, len(names), chunk):   # (P_dot is npts x n_angles doubles per direction: a chunk at a time)
+            k1 = min(k0 + chunk, len(names))
+            Pv, Pd = eng.form_factor_jvp(0, phys_d, fe_d, pd[k0:k1, None, :], None if fd is None else fd[k0:k1, None, :], want_P=P is None)
+            P = Pv if P is None else P
+            Ev, Ed = eng.ats_jvp(P[0], Pd[:, 0], ea_d, p[L.P_LAM], p[L.P_AMP1], p[L.P_AMP2], ad[k0:k1], want_E=E is None)
+            E = Ev if E is None else E
+            J.append(Ed)
+        return eng, names, (J[0] if len(J) == 1 else torch.cat(J)), E, self.ts_diag._ats_lam_axis(eng, lam_step)
+
+    def angular_jacobian(self, weights: ThomsonParams, batch: Dict, chunk: int = 32):
+        """Jacobian of the ARTS image w.r.t. every fitted normalised leaf of an angular deck with a 1-D f_e (the scalar slots, the
+        DLM order, the ``Arbitrary1V.fval`` values) by forward mode on the device (Engine.form_factor_jvp, Engine.ats_jvp), the
+        directions in chunks of ``chunk``: ``{"ele": J [n, rows, cols], "ThryE": [rows, cols] (the model image, no noise),
+        "leaves": [...]}`` as NumPy arrays, the leaves in ravel order (an fval entry j is named ("electron", "fval", j))."""
+        self._refuse_angular_postfit(weights, "angular_jacobian")
+        _, names, J, E, _ = self._angular_jacobian_device(weights, batch, chunk)
+        return {"ele": J.cpu().numpy(), "ThryE": E.cpu().numpy(), "leaves": names}
+
+    def angular_gn_loss_wrt_params(self, weights: ThomsonParams, batch: Dict, chunk: int = 32):
+        """Gauss-Newton curvature of the reference's Hessian loss (``_loss_for_hess_fn_``: denominators |e_data| + 1e-10 for l2,
+        sum reduce, the blue and red masks on the resolution-unit axis, halved when both are fitted) on the ARTS image
+        t = ThryE + noise_e:  H = sum_j w_j l''(d_j, t_j) J_j J_j^T,  grad = sum_j w_j l'(d_j, t_j) J_j,  from
+        ``angular_jacobian``'s J by a few torch operations on the device.  -> ``{"H", "grad", "loss", "leaves", "sigmas"}`` with
+        sigmas = sign(diag H^-1) sqrt|diag H^-1| (postprocess.get_sigmas); when every leaf is a scalar also ``"hess"``, the nested
+        layout ``hess[sp][k][sp2][k2]`` with 1 x 1 blocks that get_sigmas(hess, 1) reads.  ``loss_method: l1`` is refused."""
+        self._refuse_angular_postfit(weights, "angular_gn_loss_wrt_params")
+        method = self.cfg.get("optimizer", {}).get("loss_method", "l2")
+        if method == "l1":
+            raise NotImplementedError("angular_gn_loss_wrt_params: loss_method l1 has a vanishing second derivative, so its "
+                                      "Gauss-Newton matrix is zero (use l2, log-cosh or poisson)")
+        eng, names, J, E, lamE = self._angular_jacobian_device(weights, batch, chunk)
+        torch = eng.torch
+        ext, r = self.cfg["other"]["extraoptions"], self.cfg["data"]["fit_rng"]
+        c = 0.5 if (ext["fit_EPWb"] and ext["fit_EPWr"]) else 1.0
+        wcol = np.zeros(lamE.size)
+        for on, lo, hi in ((ext["fit_EPWb"], r["blue_min"], r["blue_max"]), (ext["fit_EPWr"], r["red_min"], r["red_max"])):
+            if on:
+                wcol += c * ((lamE > lo) & (lamE < hi))
+        w = eng.dev(wcol)[None, :]
+        d = eng.dev(np.ascontiguousarray(batch["e_data"], dtype=np.float64))
+        t = E + eng.dev(np.array(np.atleast_1d(np.asarray(batch["noise_e"], dtype=np.float64))))
+        res = d - t
+        if method == "l2":
+            iu = 1.0 / (d.abs() + 1e-10)
+            e, e1, e2 = res * res * iu, -2.0 * res * iu, 2.0 * iu
+        elif method == "log-cosh":
+            th = torch.tanh(res)
+            e, e1, e2 = torch.log(torch.cosh(res)), -th, 1.0 - th * th
+        else:   # poisson
+            e, e1, e2 = t - d * torch.log(t), 1.0 - d / t, d / (t * t)
+        n = J.shape[0]
+        Jf = J.reshape(n, -1)
+        H = (Jf * (w * e2).reshape(1, -1)) @ Jf.t()
+        H = 0.5 * (H + H.t())
+        grad = Jf @ (w * e1).reshape(-1)
+        out = {"H": H.cpu().numpy(), "grad": grad.cpu().numpy(), "loss": float((w * e).sum()), "leaves": names}
+        inv = np.linalg.inv(out["H"])
+        out["sigmas"] = np.sign(np.diag(inv)) * np.sqrt(np.abs(np.diag(inv)))
+        if all(len(nm) == 2 for nm in names):
+            hess = {}
+            for a, (sp1, k1) in enumerate(names):
+                for b_, (sp2, k2) in enumerate(names):
+                    hess.setdefault(sp1, {}).setdefault(k1, {}).setdefault(sp2, {})[k2] = out["H"][a:a + 1, b_:b_ + 1].copy()
+            out["hess"] = hess
+        return out
