@@ -85,17 +85,16 @@ def _directions(rng, X, fe, n_ion, n_dir, fe_dirs):
     return pd, fd
 
 
-@functools.lru_cache(maxsize=None)
-def _inputs(cid):
-    n_ion, nvx, mods, n_dir, fe_dirs = CASES[cid]
+def _build(n_ion, nvx, mods, n_dir, fe_dirs, nb=B):
+    """The inputs of a case (tests/test_forward_mode_plans_gpu.py builds its own with the same recipe)."""
     cfg = decks.deck_fit(nvx=nvx, n_ion=n_ion, active=("Te", "ne", "Ti", "Z", "Ti_same_3"))
     for m in mods:
         m(cfg)
-    sa = util.sa_fit(B)
-    normed = util.random_lineouts(cfg, B, seed=211, ranges=dict(ud=(-1.5, 1.5)))
+    sa = util.sa_fit(nb)
+    normed = util.random_lineouts(cfg, nb, seed=211, ranges=dict(ud=(-1.5, 1.5)))
     phys = orc.physical_params(cfg["parameters"], normed, True)
     X = util.normed_to_matrix(phys, n_ion)
-    fe = _free_form_fe(B, nvx, 9)
+    fe = _free_form_fe(nb, nvx, 9)
     pd, fd = _directions(np.random.default_rng(17), X, fe, n_ion, n_dir, fe_dirs)
     from tsadar_amd.params import SlotMap
 
@@ -103,16 +102,25 @@ def _inputs(cid):
 
 
 @functools.lru_cache(maxsize=None)
-def _twin(cid):
-    """The twin's P and P_dot of the case's lineouts: computed once, shared by the tests, never modified."""
-    s = _inputs(cid)
+def _inputs(cid):
+    return _build(*CASES[cid])
+
+
+def _twin_of(s):
+    """The twin's P and P_dot of the lineouts of ``s`` (_build)."""
     P, Pd = [], []
-    for b in range(B):
+    for b in range(s["X"].shape[0]):
         p, d = at.form_factor_jvp(s["cfg"], s["sa"]["sa"], s["n_ion"], s["ti_same"], s["X"][b], s["fe"][b], s["pd"][:, b],
                                   None if s["fd"] is None else s["fd"][:, b])
         P.append(p)
         Pd.append(d)
     return np.array(P), np.array(Pd).transpose(1, 0, 2, 3, 4)   # [B, G, npts, NA], [n_dir, B, G, npts, NA]
+
+
+@functools.lru_cache(maxsize=None)
+def _twin(cid):
+    """The twin's P and P_dot of the case's lineouts: computed once, shared by the tests, never modified."""
+    return _twin_of(_inputs(cid))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
