@@ -1,9 +1,13 @@
-"""A/B of the forward-mode kernels (k_hess_pairs, k_jac_sweep) between two builds of the library, bit for bit:
+"""A/B of the forward-mode kernels (k_hess_pairs, k_jac_sweep, k_ffjvp) and of the per-lineout table kernels between two builds of the
+library, bit for bit:
 
     python scripts/ab_fwdmode.py --parent-lib ab_prev/tsadar_amd/libtsff.so [--twin] [--out profiles/fwdmode_bits.txt]
 
 Engine.loss_hess, Engine.spectrum_jacobian and Engine.loss_gauss_newton run on every deck of CASES in tests/test_hessian_exact.py
-(B = 2) and tests/test_jacobian.py (B = 3), at the tests' own seeds.  Each library runs in a fresh child process of its own,
+(B = 2) and tests/test_jacobian.py (B = 3), at the tests' own seeds; Engine.form_factor_jvp (value and tangents) on every deck of
+CASES in tests/test_form_factor_jvp.py with that test's inputs, with its fe_dot and without any; Engine.loss_grad (terms, gradient,
+spectra and, on the free-form deck, the f_e gradient) on the DLM deck at B = 33 and the free-form deck at B = 65 of
+tests/test_per_lineout_tables_gpu.py (k_fe_vectors, k_fe_adjoint and the W-table GEMMs around them).  Each library runs in a fresh child process of its own,
 selected with TSFF_LIBRARY, under its own `timeout -k 10`, one after the other; the first non-zero exit ends the run.  A child
 catches nothing: a refusal, a HIP error or a fault that surfaces at a synchronise ends it there, with a non-zero exit, before
 anything else starts on the device.  Each child saves its arrays (.npz); this process compares them and prints the report (--out
@@ -30,8 +34,10 @@ import numpy as np  # noqa: E402
 def child(out):
     import torch
 
+    import test_form_factor_jvp as tf
     import test_hessian_exact as th
     import test_jacobian as tj
+    import test_per_lineout_tables_gpu as tp
     import util
 
     res = {}
@@ -64,6 +70,17 @@ def child(out):
         put(f"jac_cases/{cid}/gauss_newton", eng.loss_gauss_newton(s["X"], s["batch"], w, s["act"], fe=s["fe"]))
         put(f"jac_cases/{cid}/loss_hess", eng.loss_hess(s["X"], s["batch"], w, s["act"], fe=s["fe"]))
         print(f"jac_cases/{cid}: {form + [k for k in eng.last_launch() if k.startswith('k_hess_pairs')]}", flush=True)
+    for cid in tf.CASES:
+        s, eng = tf._inputs(cid), tf._engine(cid)
+        if s["fd"] is not None:
+            put(f"ffjvp_cases/{cid}/with_fe_dot", eng.form_factor_jvp(0, s["X"], s["fe"], s["pd"], s["fd"], want_P=True))
+        put(f"ffjvp_cases/{cid}/without_fe_dot", eng.form_factor_jvp(0, s["X"], s["fe"], s["pd"], None, want_P=True))
+        print(f"ffjvp_cases/{cid}: {[k for k in eng.last_launch() if k.startswith(('k_ffjvp', 'k_fe_direction'))]}", flush=True)
+    for name in ("dlm33", "fe65"):
+        r = tp.run(name)   # (the test's own call: loss_grad with the spectra, want_fe_grad on the free-form deck)
+        for k, v in r["host"].items():
+            res[f"table_cases/{name}/loss_grad/{k}"] = v
+        print(f"table_cases/{name}: {[k for k in r['launched'] if k.startswith(('k_fe_', 'k_wgemm'))]}", flush=True)
     np.savez(out, **res)
     return 0
 

@@ -1,14 +1,14 @@
 // k_ffjvp.inc -- forward mode of the raw 1-D form factor (tsff_form_factor_jvp): k_ffjvp.  Part of the single translation unit
 // tsff_kernels.hip (included inside namespace tsff, after k_jacobian.inc).
 //
-// P_dot[d] = dP/dphys . phys_dot[d] + dP/dfe . fe_dot[d] for arbitrary directions d: the chain functions of k_hessian.inc on the
+// P_dot[d] = dP/dphys . phys_dot[d] + dP/dfe . fe_dot[d] for arbitrary directions d: the chain functions of k_fwdmode.inc on the
 // value with W tangents of k_jacobian.inc (TN<W>), one group of W directions per launch.  The parameters are PHYSICAL, as
 // k_form_factor takes them (Ti tying as load_phys applies it, no activation, no fraction renormalisation), so a direction seeds the
 // physical parameters directly.  A direction of f_e reaches a point through the two tables: lane k of the group carries the tangent
 // of W and the Hermite coefficients of the tangent of ln f_e along its own direction (k_fe_direction + the W-table GEMM), which the
 // lookups add to that lane (MTabT's lanes).  Grid (B, angle chunks) as k_form_factor's; no atomics; DESIGN.md section 4.4c.
 //
-// Table convention: that of k_hessian.inc (Z' and W carry their slope, the Hermite ln f_e lookup its true derivative).
+// Table convention: that of k_fwdmode.inc (Z' and W carry their slope, the Hermite ln f_e lookup its true derivative).
 
 // one launch of k_ffjvp, passed by value
 struct FfjvpArgs {
@@ -76,9 +76,7 @@ __global__ __launch_bounds__(kThreads) void k_ffjvp(KStatic S, KCall K, FfjvpArg
       if (S.ti_same[s]) ph[TSFF_P_ION0 + 4 * s + TSFF_ION_TI] = ph[TSFF_P_ION0 + TSFF_ION_TI];
   }
   __syncthreads();
-  Tables T;
-  T.zp = zp; T.W = Wt; T.ht = nullptr; T.hc = hc; T.hcm = nullptr; T.Wm = nullptr; T.Wb = T.Hy = T.Hs = nullptr; T.etab = nullptr;
-  tables_set_grid(T, S.vx0, S.dv, nvx);
+  const Tables T = make_tables(S, zp, Wt, nullptr, hc);
   MTabT<N> Mt;
   Mt.on = false; Mt.Wm = nullptr; Mt.Wmm = nullptr; Mt.hcm = nullptr; Mt.hcmm = nullptr; Mt.m = N::of(0.0);
   Mt.nlane = A.nlane; Mt.Wd = Wd; Mt.hcd = hcd; Mt.hstride = 2 * nvx;

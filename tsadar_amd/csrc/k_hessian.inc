@@ -7,13 +7,9 @@
 // leaves the three masked sums S_iaw, S_blue, S_red with their first and mixed second derivatives.  k_hess_finish weights
 // them into grad[b][a] and the symmetric hess[b][a][c].  DESIGN.md section 4.4.
 //
-// Table convention (the reference's, which the torch twin follows): the piecewise-linear Z' and W lookups carry their slope and
-// no curvature; the cubic Hermite ln f_e lookup carries its true second derivative; the Z' asymptote xi^-2 and exp(-xi^2) are
-// differentiated exactly.
+// The chain functions are those of k_fwdmode.inc, written once over the number type: HD here, the value with W first-order tangents
+// in k_jacobian.inc (TN<W>).  Table convention: k_fwdmode.inc.
 
-// The chain functions below (make_lines_hd, hermite_hd, base_hd, point_hd, tie_and_renorm) are written once over the number type
-// N: HD here, and the value with W first-order tangents of k_jacobian.inc (TN<W>).  N supplies N::of(double), the member v, the
-// arithmetic operators with N and with double, hd_chain and hd_xm, and kSecondOrder (whether the second-order table terms are read).
 struct HD {   // hyper-dual number: value, the two first derivatives and the mixed second derivative
   double v, a, b, ab;
   static constexpr bool kSecondOrder = true;
@@ -37,28 +33,18 @@ __device__ __forceinline__ HD operator*(HD x, HD y) {
 __device__ __forceinline__ HD hd_chain(HD x, double f, double d1, double d2) {
   return HD{f, d1 * x.a, d1 * x.b, d1 * x.ab + d2 * x.a * x.b};
 }
-template <class N>
-__device__ __forceinline__ N hd_rcp(N x) {
-  const double r = 1.0 / x.v;
-  return hd_chain(x, r, -r * r, 2.0 * r * r * r);
-}
+// (hd_rcp, hd_sqrt, hd_exp, hd_sigmoid: the generic forms of k_fwdmode.inc)
 __device__ __forceinline__ HD operator/(HD x, HD y) { return x * hd_rcp(y); }
 __device__ __forceinline__ HD operator/(double c, HD y) { return c * hd_rcp(y); }
-template <class N>
-__device__ __forceinline__ N hd_sqrt(N x) {
-  const double s = sqrt(x.v);
-  return hd_chain(x, s, 0.5 / s, -0.25 / (s * x.v));
+// f(x, m) of a table lookup from its partial derivatives (fxx: curvature in x; fxm, fmm: through the m-dependence of the table)
+__device__ __forceinline__ HD hd_xm(HD x, HD m, double f, double fx, double fm, double fxx, double fxm, double fmm) {
+  return HD{f, fx * x.a + fm * m.a, fx * x.b + fm * m.b,
+            fx * x.ab + fm * m.ab + fxx * x.a * x.b + fxm * (x.a * m.b + m.a * x.b) + fmm * m.a * m.b};
 }
-template <class N>
-__device__ __forceinline__ N hd_exp(N x) {
-  const double e = exp(x.v);
-  return hd_chain(x, e, e, e);
-}
-template <class N>
-__device__ __forceinline__ N hd_sigmoid(N x) {
-  const double s = sigmoid(x.v), d = s * (1.0 - s);
-  return hd_chain(x, s, d, d * (1.0 - 2.0 * s));
-}
+template <int NI>
+using LineHD = LineT<HD, NI>;
+using BaseHD = BaseT<HD>;
+using MTab = MTabT<HD>;
 
 // the active leaves of one tsff_loss_hess call, passed by value
 struct HessArgs {
@@ -78,200 +64,9 @@ __device__ __forceinline__ void hess_pair(int p, int n, int& a, int& c) {
   c = a + p;
 }
 
-// lineout scalars of one gradient point (make_lines) in hyper-dual form
-template <class N, int NI>
-struct LineT {
-  N wpe2, wL, kL, ivTe, a_e, pref, Ud, Vd, i2wL;
-  N ixi[NI], a_i[NI], cs[NI], hai[NI];
-};
-template <int NI>
-using LineHD = LineT<HD, NI>;
-
-// ph: physical parameters [NP] (after activation, Ti tying and fraction renormalisation), as make_lines reads them
-template <int NI, class N>
-__device__ __forceinline__ void make_lines_hd(const N* ph, double lam_shift, int g, int G, LineT<N, NI>& L) {
-  const double cg = grad_coef(g, G);
-  const N ne_g = (1.0e20 * ph[TSFF_P_NE]) * (1.0 + ph[TSFF_P_NE_GRADIENT] * cg);
-  const N Te_g = ph[TSFF_P_TE] * (1.0 + ph[TSFF_P_TE_GRADIENT] * cg);
-  L.wL = kOmgLnum / (ph[TSFF_P_LAM] + lam_shift);
-  L.i2wL = 2.0 / L.wL;
-  L.wpe2 = kC0sq * ne_g;
-  L.kL = hd_sqrt(L.wL * L.wL - L.wpe2) * (1.0 / kC);
-  L.ivTe = 1.0 / hd_sqrt(Te_g * (1.0 / kMe));
-  L.a_e = L.wpe2 * L.ivTe * L.ivTe;
-  L.pref = ne_g * (kRe * kRe / (2.0 * kPi * kC));
-  L.Ud = ph[TSFF_P_UD] * 1e6;
-  L.Vd = ph[TSFF_P_VA] * 1e6;
-  N Zbar = N::of(0.0);
-#pragma unroll
-  for (int s = 0; s < NI; ++s) Zbar = Zbar + ph[TSFF_P_ION0 + 4 * s + TSFF_ION_Z] * ph[TSFF_P_ION0 + 4 * s + TSFF_ION_FRACT];
-#pragma unroll
-  for (int s = 0; s < NI; ++s) {
-    const int o = TSFF_P_ION0 + 4 * s;
-    const N Ti = ph[o + TSFF_ION_TI], Z = ph[o + TSFF_ION_Z], fr = ph[o + TSFF_ION_FRACT];
-    const double Ms = ph[o + TSFF_ION_A].v * kMp;
-    const N vTi = hd_sqrt(Ti * (1.0 / Ms));
-    L.ixi[s] = 1.0 / (kSqrt2 * vTi);
-    L.a_i[s] = (kC0sq * kMe) * Z * Z * fr * ne_g / (Zbar * Ti);
-    L.cs[s] = fr * Z * Z / (Zbar * vTi);
-    L.hai[s] = -0.5 * L.a_i[s];
-  }
-}
-
-template <class N>
-struct BaseT {
-  N ik, wd, xe, F;
-};
-using BaseHD = BaseT<HD>;
-
-// f(x, m) of a table lookup from its partial derivatives (fxx: curvature in x; fxm, fmm: through the m-dependence of the table)
-__device__ __forceinline__ HD hd_xm(HD x, HD m, double f, double fx, double fm, double fxx, double fxm, double fmm) {
-  return HD{f, fx * x.a + fm * m.a, fx * x.b + fm * m.b,
-            fx * x.ab + fm * m.ab + fxx * x.a * x.b + fxm * (x.a * m.b + m.a * x.b) + fmm * m.a * m.b};
-}
-
-// the tables' dependence on the DLM order m (with_m): dW/dm, d2W/dm2 on the xi2 grid and the Hermite coefficients of
-// d ln f_e / dm and d2 ln f_e / dm2; m is the physical order with its two seeds
-// The general case of a first-order number with tangent lanes (N::kLanes > 0, k_ffjvp): lane k < nlane carries a table direction
-// of its own, Wd[k][1640] = the tangent of W and hcd[k][2 nvx] = the Hermite coefficients of the tangent of ln f_e along it, which
-// the lookups add to that lane directly.  m is the special case of one direction shared by every lane through m's seeds.
-template <class N>
-struct MTabT {
-  const double* Wm;
-  const double* Wmm;     // (second order only)
-  const double2* hcm;
-  const double2* hcmm;   // (second order only)
-  N m;
-  bool on;
-  int nlane = 0;         // lanes with a table direction (0: none)
-  const double* Wd = nullptr;
-  const double2* hcd = nullptr;
-  int hstride = 0;       // double2 per lane of hcd (2 nvx)
-};
-using MTab = MTabT<HD>;
-
-__device__ __forceinline__ void cubic_at(const double2* hc, int i, double t, double idv, double& H, double& d1, double& d2) {
-  const double2 c01 = hc[2 * i], c23 = hc[2 * i + 1];
-  H = __builtin_fma(t, __builtin_fma(t, __builtin_fma(t, c23.y, c23.x), c01.y), c01.x);
-  d1 = __builtin_fma(t, __builtin_fma(3.0 * t, c23.y, 2.0 * c23.x), c01.y) * idv;
-  d2 = __builtin_fma(6.0 * t, c23.y, 2.0 * c23.x) * (idv * idv);
-}
-
-// hermite_lookup_c with the true second derivative of the cubic (-50 and no derivative outside the grid); with M.on the
-// node values depend on m as well
-template <class N>
-__device__ __forceinline__ N hermite_hd(const Tables& T, const MTabT<N>& M, N x) {
-  const double u = __builtin_fma(x.v, T.idv, T.u0);
-  const double uc = fmin(fmax(u, 0.0), T.utop);
-  if (u != uc) return N::of(-50.0);
-  const double fl = __builtin_floor(uc);
-  const double t = uc - fl;
-  const int i = (int)fl;
-  double H, d1, d2;
-  cubic_at(T.hc, i, t, T.idv, H, d1, d2);
-  if constexpr (N::kLanes > 0) {
-    if (M.nlane > 0) {
-      N r = hd_chain(x, H, d1, d2);
-#pragma unroll
-      for (int k = 0; k < N::kLanes; ++k)
-        if (k < M.nlane) {
-          double Hk, u1, u2;
-          cubic_at(M.hcd + (size_t)k * M.hstride, i, t, T.idv, Hk, u1, u2);
-          r.d[k] += Hk;
-        }
-      return r;
-    }
-  }
-  if (!M.on) return hd_chain(x, H, d1, d2);
-  double Hm, Hxm, unused, Hmm = 0.0, u1, u2;
-  cubic_at(M.hcm, i, t, T.idv, Hm, Hxm, unused);
-  if constexpr (N::kSecondOrder) cubic_at(M.hcmm, i, t, T.idv, Hmm, u1, u2);
-  return hd_xm(x, M.m, H, d1, Hm, d2, Hxm, Hmm);
-}
-
-template <int NI, class N>
-__device__ __forceinline__ void base_hd(double ws, double ct, const LineT<N, NI>& L, const Tables& T, const MTabT<N>& M, BaseT<N>& b) {
-  const N ks = hd_sqrt(ws * ws - L.wpe2) * (1.0 / kC);
-  const N k2 = ks * (ks - (2.0 * ct) * L.kL) + L.kL * L.kL;
-  const N k = hd_sqrt(k2);
-  b.ik = hd_rcp(k);
-  b.wd = (ws - L.wL) - k * L.Vd;
-  b.xe = (b.wd * b.ik - L.Ud) * L.ivTe;
-  b.F = hd_exp(hermite_hd(T, M, b.xe));
-}
-
-// point_core / point_forward_sd in hyper-dual form: S (1 + 2 w / w_L)
-template <int NI, class N>
-__device__ __forceinline__ N point_hd(const BaseT<N>& b, const BaseT<N>& bn, bool has_next, const LineT<N, NI>& L, const Tables& T,
-                                     const MTabT<N>& M) {
-  const N ik2 = b.ik * b.ik;
-  const N ike2 = L.a_e * ik2;
-  const N vph = b.wd * b.ik;
-  N opc = N::of(1.0), cim = N::of(0.0), gsum = N::of(0.0);
-#pragma unroll
-  for (int s = 0; s < NI; ++s) {
-    const N xi = vph * L.ixi[s];
-    const N hk = L.hai[s] * ik2;
-    // Z'(xi): the full table (slope, no curvature) or the asymptote xi^-2 + 0 i outside it
-    constexpr double kTop = (double)(kNXi2 - 1) * (1.0 - 1.1102230246251565e-16);
-    const double u = __builtin_fma(xi.v, kXi2_ih, -kXi2_0 * kXi2_ih);
-    const double uc = fmin(fmax(u, 0.0), kTop);
-    N zr, zi;
-    if (u != uc) {
-      const double r = 1.0 / xi.v, r2 = r * r;
-      zr = hd_chain(xi, r2, -2.0 * r2 * r, 6.0 * r2 * r2);
-      zi = N::of(0.0);
-    } else {
-      const double fl = __builtin_floor(uc);
-      const double t = uc - fl;
-      const int i = (int)fl;
-      const double2 za = T.zp[i], zb = T.zp[i + 1];
-      const double dr = zb.x - za.x, di = zb.y - za.y;
-      zr = hd_chain(xi, __builtin_fma(t, dr, za.x), dr * kXi2_ih, 0.0);
-      zi = hd_chain(xi, __builtin_fma(t, di, za.y), di * kXi2_ih, 0.0);
-    }
-    const N gs = hd_exp(-(xi * xi)) * kInvSqrt2Pi;
-    opc = opc + hk * zr;
-    cim = cim + hk * zi;
-    gsum = gsum + L.cs[s] * gs;
-  }
-  double w, dw;
-  w_lookup(T.W, b.xe.v, w, dw);
-  N Wl;
-  bool lanes = false;
-  if constexpr (N::kLanes > 0) lanes = M.nlane > 0;
-  if (lanes) {   // W(x) with a table tangent per lane, interpolated in the same cell
-    Wl = hd_chain(b.xe, w, dw, 0.0);
-    if constexpr (N::kLanes > 0) {
-#pragma unroll
-      for (int k = 0; k < N::kLanes; ++k)
-        if (k < M.nlane) {
-          double wk, dwk;
-          w_lookup(M.Wd + (size_t)k * kNXi2, b.xe.v, wk, dwk);
-          Wl.d[k] += wk;
-        }
-    }
-  } else if (M.on) {   // W(x, m): no curvature in x; dW/dm and d2W/dm2 interpolated in the same cell, the slope of dW/dm for the mixed term
-    double wm, dwm, wmm = 0.0, dwmm;
-    w_lookup(M.Wm, b.xe.v, wm, dwm);
-    if constexpr (N::kSecondOrder) w_lookup(M.Wmm, b.xe.v, wmm, dwmm);
-    Wl = hd_xm(b.xe, M.m, w, dw, wm, 0.0, dwm, wmm);
-  } else {
-    Wl = hd_chain(b.xe, w, dw, 0.0);
-  }
-  const N D = has_next ? (bn.F - b.F) / (bn.xe - b.xe) : N::of(0.0);
-  const N cer = -(ike2 * Wl);
-  const N cei = (kPi * ike2) * D;
-  const N er = opc + cer, ei = cei + cim;
-  const N eps2 = er * er + ei * ei;
-  const N ce2 = cer * cer + cei * cei;
-  const N ci2 = opc * opc + cim * cim;
-  const N Nn = gsum * ce2 + ci2 * b.F * L.ivTe;
-  const N S = Nn * b.ik / eps2;
-  return S * (1.0 + b.wd * L.i2wL);
-}
-
-// loss functional e(d, t) of one sample (loss_function.py:386-418) with the denominators of _loss_for_hess_fn_ (|d| + 1e-10, l1 / l2)
+// loss functional e(d, t) of one sample with the denominators of _loss_for_hess_fn_ (|d| + 1e-10, l1 / l2) in hyper-dual arithmetic.
+// The functional itself is defined in k_chain.inc (loss_point, with the denominator rule in bin_loss); this form evaluates l2 and l1
+// as hyper-dual products of r, whose last bit hd_chain on loss_point's derivatives would not reproduce.
 __device__ __forceinline__ HD loss_hd(int method, double d, HD t) {
   const HD r = d - t;
   HD e;
@@ -281,19 +76,6 @@ __device__ __forceinline__ HD loss_hd(int method, double d, HD t) {
   else { const double it = 1.0 / t.v; e = hd_chain(t, t.v - d * log(t.v), 1.0 - d * it, d * it * it); }
   if (method == TSFF_LOSS_L2 || method == TSFF_LOSS_L1) e = e * (1.0 / (fabs(d) + 1e-10));
   return e;
-}
-
-// Ti tying and fraction renormalisation of the physical parameters (the tail of stage_phys)
-template <int NI, class N>
-__device__ __forceinline__ void tie_and_renorm(const KStatic& S, N* ph) {
-  N fsum = N::of(0.0);
-  for (int s = 0; s < NI; ++s) {
-    const int o = TSFF_P_ION0 + 4 * s;
-    if (s > 0 && S.ti_same[s]) ph[o + TSFF_ION_TI] = ph[TSFF_P_ION0 + TSFF_ION_TI];
-    fsum = fsum + ph[o + TSFF_ION_FRACT];
-  }
-  const N ifs = hd_rcp(fsum);
-  for (int s = 0; s < NI; ++s) ph[TSFF_P_ION0 + 4 * s + TSFF_ION_FRACT] = ph[TSFF_P_ION0 + 4 * s + TSFF_ION_FRACT] * ifs;
 }
 
 __device__ __forceinline__ HD block_sum_hd(HD x, double* red) {
@@ -377,9 +159,7 @@ __global__ __launch_bounds__(kThreads) void k_hess_pairs(KStatic S, KCall K, Hes
       tie_and_renorm<NI>(S, ph);
     }
     __syncthreads();
-    Tables T;
-    T.zp = zp; T.W = Wt; T.ht = nullptr; T.hc = hc; T.hcm = nullptr; T.Wm = nullptr; T.Wb = T.Hy = T.Hs = nullptr; T.etab = nullptr;
-    tables_set_grid(T, S.vx0, S.dv, S.nvx);
+    const Tables T = make_tables(S, zp, Wt, nullptr, hc);
     MTab Mt;
     Mt.on = A.with_m != 0; Mt.Wm = Wm; Mt.Wmm = Wmm; Mt.hcm = hcm; Mt.hcmm = hcmm; Mt.m = ph[TSFF_P_M];
     HD sums[3] = {hd(0.0), hd(0.0), hd(0.0)};
@@ -528,35 +308,26 @@ __global__ __launch_bounds__(kThreads) void k_hess_mtab(KStatic S, const double*
   double* rdf = rat + kNXi1;                                   // [1024] ratdf''
   double* red = rdf + kNXi1;                                   // [8]
   const int b = blockIdx.x, tid = threadIdx.x, nvx = S.nvx;
-  Phys<NI> p;
-  load_phys<NI>(params + (size_t)b * S.NP, S.p_scale, S.p_shift, S.p_sig, S.ti_same, true, p);
-  const double m = p.m;
-  double u = (m - 2.0) * 10.0;
-  int k = (int)u;
-  k = k < 0 ? 0 : (k > TSFF_DLM_NM - 2 ? TSFF_DLM_NM - 2 : k);
-  double t = (m - (2.0 + 0.1 * k)) * 10.0;
-  const bool inside = m >= 2.0 && m <= 5.0;
-  t = m < 2.0 ? 0.0 : (m > 5.0 ? 1.0 : t);
+  const DlmCell cell = dlm_cell<NI>(S, params + (size_t)b * S.NP);
   double part = 0.0, dpart = 0.0;
   for (int i = tid; i < nvx; i += kThreads) {
-    const double a = S.dlm_table[i * TSFF_DLM_NM + k], c = S.dlm_table[i * TSFF_DLM_NM + k + 1];
-    part += a + t * (c - a);
-    dpart += inside ? (c - a) * 10.0 : 0.0;
+    double f, df;
+    dlm_node(S, cell, i, f, df);
+    part += f;
+    dpart += df;
   }
   const double tot = block_sum(part, red);
   const double dtot = block_sum(dpart, red);
   const double rt = dtot / tot;
   for (int i = tid; i < nvx; i += kThreads) {
-    const double a = S.dlm_table[i * TSFF_DLM_NM + k], c = S.dlm_table[i * TSFF_DLM_NM + k + 1];
-    const double q = inside ? (c - a) * 10.0 / (a + t * (c - a)) : 0.0;
+    double f, df;
+    dlm_node(S, cell, i, f, df);
+    const double q = df / f;   // (df = 0 outside the m axis)
     lmm[i] = rt * rt - q * q;
   }
   __syncthreads();
   double2* htmm_b = htmm_out + (size_t)b * nvx;
-  for (int i = tid; i < nvx; i += kThreads) {
-    const double dl = i > 0 ? (lmm[i] - lmm[i - 1]) / S.dv : 0.0, dr = i < nvx - 1 ? (lmm[i + 1] - lmm[i]) / S.dv : 0.0;
-    htmm_b[i] = make_double2(lmm[i], i == 0 ? dr : (i == nvx - 1 ? dl : 0.5 * (dl + dr)));
-  }
+  for (int i = tid; i < nvx; i += kThreads) htmm_b[i] = make_double2(lmm[i], node_slopes(lmm, i, nvx, S.dv));
   __syncthreads();
   const double2* ht_b = ht + (size_t)b * nvx;
   const double2* htm_b = htm + (size_t)b * nvx;
@@ -566,9 +337,7 @@ __global__ __launch_bounds__(kThreads) void k_hess_mtab(KStatic S, const double*
     hermite_coeffs(htmm_b[i], htmm_b[i + 1], S.dv, hcmm[2 * i], hcmm[2 * i + 1]);
   }
   __syncthreads();
-  Tables T;
-  T.zp = nullptr; T.W = nullptr; T.ht = nullptr; T.hc = hc; T.nvx = nvx; T.etab = nullptr;
-  tables_set_grid(T, S.vx0, S.dv, nvx);
+  const Tables T = make_tables(S, nullptr, nullptr, nullptr, hc);
   Tables Tm = T, Tmm = T;
   Tm.hc = hcm; Tmm.hc = hcmm;
   for (int i = tid; i < kNXi1; i += kThreads) {
@@ -581,28 +350,11 @@ __global__ __launch_bounds__(kThreads) void k_hess_mtab(KStatic S, const double*
     rat[i] = out ? 0.0 : exp(H) * (Hm * Hm + Hmm);
   }
   __syncthreads();
-  const double h1 = S.xi1[1] - S.xi1[0];
-  for (int i = tid; i < kNXi1; i += kThreads) {
-    double g;
-    if (i == 0) g = (rat[1] - rat[0]) / h1;
-    else if (i == kNXi1 - 1) g = (rat[i] - rat[i - 1]) / h1;
-    else g = (rat[i + 1] - rat[i - 1]) / (2.0 * h1);
-    rdf[i] = g;
-  }
+  ratdf_central(S.xi1, rat, rdf);
   __syncthreads();
-  double c0 = 0.0;
   double* Xb = X + (size_t)b * 4 * kNXi1;
-  for (int i = tid; i < kNXi1; i += kThreads) {
-    double A = 0.0, Bs = 0.0;
-    if (i < kNXi1 - 2) {
-      const double x0 = S.xi1[i], x1 = S.xi1[i + 1];
-      const double ih = 1.0 / (x1 - x0), mid = 0.5 * (x1 + x0);
-      const double fd = rdf[i + 1] - rdf[i], fa = 0.5 * (rdf[i + 1] + rdf[i]);
-      Bs = fd * ih; A = fa - mid * Bs;
-      c0 += fd;
-    }
-    Xb[i] = A; Xb[kNXi1 + i] = Bs; Xb[2 * kNXi1 + i] = 0.0; Xb[3 * kNXi1 + i] = 0.0;
-  }
+  double c0 = ratdf_rows(S.xi1, rdf, Xb, Xb + kNXi1);
+  for (int i = tid; i < kNXi1; i += kThreads) { Xb[2 * kNXi1 + i] = 0.0; Xb[3 * kNXi1 + i] = 0.0; }
   c0 = block_sum(c0, red);
   if (tid == 0) { cst[2 * b] = c0; cst[2 * b + 1] = 0.0; }
 }

@@ -1,7 +1,7 @@
 // k_jacobian.inc -- Jacobian of the model spectra w.r.t. the fitted leaves and the Gauss-Newton curvature of the fit loss:
 // k_jac_sweep.  Part of the single translation unit tsff_kernels.hip (included inside namespace tsff, after k_hessian.inc).
 //
-// First-order forward mode through the chain k_hessian.inc differentiates (its functions are generic over the number type): one
+// First-order forward mode through the chain k_hessian.inc differentiates (k_fwdmode.inc: generic over the number type): one
 // workgroup evaluates a lineout with a value and W tangents side by side -- table lookups, exp, reciprocals, square roots and the
 // Hermite cell are evaluated once per point and shared by the W leaves of a group; the groups of W leaves follow each other when
 // the call has more active leaves.  The spectrum of a feature ((1 + W) npts doubles) lives in LDS.  Per binned sample j the
@@ -13,7 +13,7 @@
 // Where the hand-written reverse of the pair sweeps exists (1-2 ion species, one gradient point, no DLM order among the leaves, no
 // raw feature) the sweep runs in its row form instead (k_jac_sweep<NI, 3, true>, jac_rows_sweep below); the tail is the same.
 //
-// Table convention: that of k_hessian.inc (Z' and W carry their slope, the Hermite ln f_e lookup its true derivative).
+// Table convention: that of k_fwdmode.inc (Z' and W carry their slope, the Hermite ln f_e lookup its true derivative).
 
 template <int W>
 struct TN {   // a value and W first-order tangents
@@ -317,9 +317,7 @@ __global__ __launch_bounds__(kThreads, ((NI == 1 || ROWS) ? 2 : 1)) void k_jac_s
         for (int i = tid; i < kNXi2; i += kThreads) Wm[i] = K.Wm[(size_t)slot * kNXi2 + i];
       slot_prev = slot;
     }
-    Tables T;
-    T.zp = zp; T.W = Wt; T.ht = nullptr; T.hc = hc; T.hcm = nullptr; T.Wm = nullptr; T.Wb = T.Hy = T.Hs = nullptr; T.etab = nullptr;
-    tables_set_grid(T, S.vx0, S.dv, S.nvx);
+    const Tables T = make_tables(S, zp, Wt, nullptr, hc);
     double lsum[3] = {0.0, 0.0, 0.0};
     bool first_feature = true;
 

@@ -2,6 +2,83 @@
 // Part of the single translation unit tsff_kernels.hip (included inside namespace tsff).
 
 // ------------------------------------------------------------------------------------------
+// The numerical steps of the table builders (k_fe_prepare, k_fe_vectors, fe_direction_rows, k_hess_mtab; k_fe_adjoint walks them
+// backwards), each stated once
+// ------------------------------------------------------------------------------------------
+// A kernel's Tables on the handle's vx grid: the tables it has (nullptr: none), no m-tangents, no adjoints, polynomial exp
+__device__ __forceinline__ Tables make_tables(const KStatic& S, const double2* zp, const double* Wt, const double2* ht, const double2* hc) {
+  Tables T;
+  T.zp = zp; T.W = Wt; T.ht = ht; T.hc = hc; T.hcm = nullptr; T.Wm = nullptr; T.Wb = T.Hy = T.Hs = nullptr; T.etab = nullptr;
+  tables_set_grid(T, S.vx0, S.dv, S.nvx);
+  return T;
+}
+
+// slope at node i of the nodal array y [n] with spacing dv: mean of the adjacent secants, one-sided at the ends (interpax _approx_df)
+__device__ __forceinline__ double node_slopes(const double* y, int i, int n, double dv) {
+  const double dl = i > 0 ? (y[i] - y[i - 1]) / dv : 0.0, dr = i < n - 1 ? (y[i + 1] - y[i]) / dv : 0.0;
+  return i == 0 ? dr : (i == n - 1 ? dl : 0.5 * (dl + dr));
+}
+
+// ratdf = gradient(ratmod, dxi1) (form_factor.py:264): central differences on the uniform xi1 grid, one-sided at the ends.
+// All threads; no barrier.
+__device__ __forceinline__ void ratdf_central(const double* xi1, const double* rat, double* rdf) {
+  const double h1 = xi1[1] - xi1[0];
+  for (int i = threadIdx.x; i < kNXi1; i += kThreads) {
+    double g;
+    if (i == 0) g = (rat[1] - rat[0]) / h1;
+    else if (i == kNXi1 - 1) g = (rat[i] - rat[i - 1]) / h1;
+    else g = (rat[i + 1] - rat[i - 1]) / (2.0 * h1);
+    rdf[i] = g;
+  }
+}
+
+// interval i of the xi1 grid as the W-table GEMM sees it: 1 / h_i and the midpoint (ratintn drops the last interval: i < 1022)
+__device__ __forceinline__ void xi1_cell(const double* xi1, int i, double& ih, double& mid) {
+  const double x0 = xi1[i], x1 = xi1[i + 1];
+  ih = 1.0 / (x1 - x0); mid = 0.5 * (x1 + x0);
+}
+
+// ratdf -> the (A, s) rows of the W-table GEMM, XA / XB [1024] zero padded: s_i = fdif_i / h_i, A_i = fav_i - xi1mid_i s_i.  All
+// threads; returns this thread's part of sum fdif (the caller block_sums it); no barrier.
+__device__ __forceinline__ double ratdf_rows(const double* xi1, const double* rdf, double* __restrict__ XA, double* __restrict__ XB) {
+  double c = 0.0;
+  for (int i = threadIdx.x; i < kNXi1; i += kThreads) {
+    double A = 0.0, Bs = 0.0;
+    if (i < kNXi1 - 2) {
+      double ih, mid;
+      xi1_cell(xi1, i, ih, mid);
+      const double fd = rdf[i + 1] - rdf[i], fa = 0.5 * (rdf[i + 1] + rdf[i]);
+      Bs = fd * ih; A = fa - mid * Bs;
+      c += fd;
+    }
+    XA[i] = A; XB[i] = Bs;
+  }
+  return c;
+}
+
+// DLM1V.__call__ (base.py:277-294) interpolates in the order m over m_ax = linspace(2, 5, 31): the cell of lineout xpar's m, the
+// weight t in it, and whether m lies inside the axis (jnp.interp clamps outside: zero slope there)
+struct DlmCell { int k; double t; bool inside; };
+template <int NI>
+__device__ __forceinline__ DlmCell dlm_cell(const KStatic& S, const double* __restrict__ xpar) {
+  Phys<NI> p;
+  load_phys<NI>(xpar, S.p_scale, S.p_shift, S.p_sig, S.ti_same, true, p);
+  const double m = p.m;
+  double u = (m - 2.0) * 10.0;
+  int k = (int)u;
+  k = k < 0 ? 0 : (k > TSFF_DLM_NM - 2 ? TSFF_DLM_NM - 2 : k);
+  double t = (m - (2.0 + 0.1 * k)) * 10.0;
+  t = m < 2.0 ? 0.0 : (m > 5.0 ? 1.0 : t);
+  return DlmCell{k, t, m >= 2.0 && m <= 5.0};
+}
+// node i of the un-normalised f_e in that cell and its derivative w.r.t. m
+__device__ __forceinline__ void dlm_node(const KStatic& S, const DlmCell& c, int i, double& f, double& df) {
+  const double a = S.dlm_table[i * TSFF_DLM_NM + c.k], b = S.dlm_table[i * TSFF_DLM_NM + c.k + 1];
+  f = a + c.t * (b - a);
+  df = c.inside ? (b - a) * 10.0 : 0.0;
+}
+
+// ------------------------------------------------------------------------------------------
 // k_fe_prepare: distribution function -> Hermite table of ln fe and the Re(chi_e) table W
 // grid (slots, qsplit), 256 threads.   reference: form_factor.py:263-268, ratintn.py:4-52,
 // base.py:277-294 (DLM), interpax _approx_df (node slopes)
@@ -24,19 +101,12 @@ __global__ __launch_bounds__(kThreads) void k_fe_prepare(KStatic S, const double
 
   // ---- fe on the vx grid ----
   if (fe_mode == TSFF_FE_DLM) {
-    // DLM1V.__call__ (base.py:277-294): interp in m over m_ax = linspace(2,5,31), then /sum/dv
-    Phys<NI> p;
-    load_phys<NI>(params + (size_t)slot * S.NP, S.p_scale, S.p_shift, S.p_sig, S.ti_same, true, p);
-    const double m = p.m;
-    double u = (m - 2.0) * 10.0;
-    int k = (int)u;
-    k = k < 0 ? 0 : (k > TSFF_DLM_NM - 2 ? TSFF_DLM_NM - 2 : k);
-    double t = (m - (2.0 + 0.1 * k)) * 10.0;
-    t = m < 2.0 ? 0.0 : (m > 5.0 ? 1.0 : t);
+    // DLM1V.__call__ (base.py:277-294): interp in m, then /sum/dv
+    const DlmCell cell = dlm_cell<NI>(S, params + (size_t)slot * S.NP);
     double part = 0.0;
     for (int i = tid; i < nvx; i += kThreads) {
-      const double a = S.dlm_table[i * TSFF_DLM_NM + k], b = S.dlm_table[i * TSFF_DLM_NM + k + 1];
-      const double f = a + t * (b - a);
+      double f, df;
+      dlm_node(S, cell, i, f, df);
       lnfe[i] = f;
       part += f;
     }
@@ -51,19 +121,15 @@ __global__ __launch_bounds__(kThreads) void k_fe_prepare(KStatic S, const double
   }
   for (int i = tid; i < kNXi1; i += kThreads) xi1[i] = S.xi1[i];
   __syncthreads();
-  // ---- node slopes: mean of adjacent secants, one-sided at the ends ----
+  // ---- node slopes ----
   for (int i = tid; i < nvx; i += kThreads) {
-    const double dl = i > 0 ? (lnfe[i] - lnfe[i - 1]) / S.dv : 0.0;
-    const double dr = i < nvx - 1 ? (lnfe[i + 1] - lnfe[i]) / S.dv : 0.0;
-    const double s = i == 0 ? dr : (i == nvx - 1 ? dl : 0.5 * (dl + dr));
+    const double s = node_slopes(lnfe, i, nvx, S.dv);
     slope[i] = s;
     ht[i] = make_double2(lnfe[i], s);
     if (blockIdx.y == 0) ht_out[(size_t)slot * nvx + i] = make_double2(lnfe[i], s);
   }
   __syncthreads();
-  Tables T;
-  T.zp = nullptr; T.W = nullptr; T.ht = ht; T.nvx = nvx; T.etab = nullptr;
-  tables_set_grid(T, S.vx0, S.dv, nvx);
+  const Tables T = make_tables(S, nullptr, nullptr, ht, nullptr);
   // ---- ratmod = exp(H(xi1)) (form_factor.py:263) ----
   for (int i = tid; i < kNXi1; i += kThreads) {
     double H, dH;
@@ -71,15 +137,7 @@ __global__ __launch_bounds__(kThreads) void k_fe_prepare(KStatic S, const double
     ratmod[i] = exp(H);
   }
   __syncthreads();
-  // ---- ratdf = gradient(ratmod, dxi1) (form_factor.py:264) ----
-  const double h1 = xi1[1] - xi1[0];
-  for (int i = tid; i < kNXi1; i += kThreads) {
-    double g;
-    if (i == 0) g = (ratmod[1] - ratmod[0]) / h1;
-    else if (i == kNXi1 - 1) g = (ratmod[kNXi1 - 1] - ratmod[kNXi1 - 2]) / h1;
-    else g = (ratmod[i + 1] - ratmod[i - 1]) / (2.0 * h1);
-    ratdf[i] = g;
-  }
+  ratdf_central(xi1, ratmod, ratdf);
   __syncthreads();
   // ---- W[q] = ratintn(ratdf, xi1 - xi2[q], xi1): one wavefront per q, lanes stride the 1022
   //      intervals, xor-shuffle reduction (ratintn.py:21, 41-52; the last interval is dropped) ----
@@ -127,9 +185,7 @@ __device__ __forceinline__ double fe_direction_rows(const KStatic& S, const Tabl
                                                     double* __restrict__ XA, double* __restrict__ XB) {
   const int tid = threadIdx.x, nvx = S.nvx;
   for (int i = tid; i < nvx; i += kThreads) {
-    const double ml = i > 0 ? (dln[i] - dln[i - 1]) / S.dv : 0.0, mr = i < nvx - 1 ? (dln[i + 1] - dln[i]) / S.dv : 0.0;
-    const double sm = i == 0 ? mr : (i == nvx - 1 ? ml : 0.5 * (ml + mr));
-    htm[i] = make_double2(dln[i], sm);
+    htm[i] = make_double2(dln[i], node_slopes(dln, i, nvx, S.dv));
     htm_out[i] = htm[i];
   }
   __syncthreads();
@@ -145,28 +201,9 @@ __device__ __forceinline__ double fe_direction_rows(const KStatic& S, const Tabl
     ratm[i] = out ? 0.0 : rat[i] * Hm;
   }
   __syncthreads();
-  const double h1 = S.xi1[1] - S.xi1[0];
-  for (int i = tid; i < kNXi1; i += kThreads) {
-    double gm;
-    if (i == 0) gm = (ratm[1] - ratm[0]) / h1;
-    else if (i == kNXi1 - 1) gm = (ratm[i] - ratm[i - 1]) / h1;
-    else gm = (ratm[i + 1] - ratm[i - 1]) / (2.0 * h1);
-    rdfm[i] = gm;
-  }
+  ratdf_central(S.xi1, ratm, rdfm);
   __syncthreads();
-  double c1 = 0.0;
-  for (int i = tid; i < kNXi1; i += kThreads) {
-    double Am = 0.0, Bm = 0.0;
-    if (i < kNXi1 - 2) {
-      const double x0 = S.xi1[i], x1 = S.xi1[i + 1];
-      const double ih = 1.0 / (x1 - x0), mid = 0.5 * (x1 + x0);
-      const double fdm = rdfm[i + 1] - rdfm[i], fam = 0.5 * (rdfm[i + 1] + rdfm[i]);
-      Bm = fdm * ih; Am = fam - mid * Bm;
-      c1 += fdm;
-    }
-    XA[i] = Am; XB[i] = Bm;
-  }
-  return c1;
+  return ratdf_rows(S.xi1, rdfm, XA, XB);
 }
 
 template <int NI>
@@ -189,20 +226,11 @@ __global__ __launch_bounds__(kThreads) void k_fe_vectors(KStatic S, const double
   const int b = blockIdx.x, tid = threadIdx.x, nvx = S.nvx;
 
   if (fe_mode == TSFF_FE_DLM) {
-    Phys<NI> p;
-    load_phys<NI>(params + (size_t)b * S.NP, S.p_scale, S.p_shift, S.p_sig, S.ti_same, true, p);
-    const double m = p.m;
-    double u = (m - 2.0) * 10.0;
-    int k = (int)u;
-    k = k < 0 ? 0 : (k > TSFF_DLM_NM - 2 ? TSFF_DLM_NM - 2 : k);
-    double t = (m - (2.0 + 0.1 * k)) * 10.0;
-    const bool inside = m >= 2.0 && m <= 5.0;   // jnp.interp clamps outside the m axis: zero slope there
-    t = m < 2.0 ? 0.0 : (m > 5.0 ? 1.0 : t);
+    const DlmCell cell = dlm_cell<NI>(S, params + (size_t)b * S.NP);
     double part = 0.0, dpart = 0.0;
     for (int i = tid; i < nvx; i += kThreads) {
-      const double a = S.dlm_table[i * TSFF_DLM_NM + k], c = S.dlm_table[i * TSFF_DLM_NM + k + 1];
-      const double f = a + t * (c - a);
-      const double df = inside ? (c - a) * 10.0 : 0.0;
+      double f, df;
+      dlm_node(S, cell, i, f, df);
       lnfe[i] = f;
       dln[i] = df;
       part += f;
@@ -220,46 +248,24 @@ __global__ __launch_bounds__(kThreads) void k_fe_vectors(KStatic S, const double
   }
   __syncthreads();
   for (int i = tid; i < nvx; i += kThreads) {
-    const double dl = i > 0 ? (lnfe[i] - lnfe[i - 1]) / S.dv : 0.0, dr = i < nvx - 1 ? (lnfe[i + 1] - lnfe[i]) / S.dv : 0.0;
-    const double sl = i == 0 ? dr : (i == nvx - 1 ? dl : 0.5 * (dl + dr));
-    ht[i] = make_double2(lnfe[i], sl);
+    ht[i] = make_double2(lnfe[i], node_slopes(lnfe, i, nvx, S.dv));
     ht_out[(size_t)b * nvx + i] = ht[i];
   }
   __syncthreads();
   for (int i = tid; i < nvx - 1; i += kThreads) hermite_coeffs(ht[i], ht[i + 1], S.dv, hc[2 * i], hc[2 * i + 1]);
   __syncthreads();
-  Tables T;
-  T.zp = nullptr; T.W = nullptr; T.ht = ht; T.hc = hc; T.nvx = nvx; T.etab = nullptr;
-  tables_set_grid(T, S.vx0, S.dv, nvx);
+  const Tables T = make_tables(S, nullptr, nullptr, ht, hc);
   for (int i = tid; i < kNXi1; i += kThreads) {
     double H, dH;
     hermite_lookup_c(T, S.xi1[i], H, dH);
     rat[i] = exp(H);
   }
   __syncthreads();
-  const double h1 = S.xi1[1] - S.xi1[0];
-  for (int i = tid; i < kNXi1; i += kThreads) {
-    double g;
-    if (i == 0) g = (rat[1] - rat[0]) / h1;
-    else if (i == kNXi1 - 1) g = (rat[i] - rat[i - 1]) / h1;
-    else g = (rat[i + 1] - rat[i - 1]) / (2.0 * h1);
-    rdf[i] = g;
-  }
+  ratdf_central(S.xi1, rat, rdf);
   double* Xb = X + (size_t)b * 4 * kNXi1;
   // the m direction (its barriers publish rdf as well)
   double c1 = fe_direction_rows(S, T, dln, rat, htm, hcm, ratm, rdfm, htm_out + (size_t)b * nvx, Xb + 2 * kNXi1, Xb + 3 * kNXi1);
-  double c0 = 0.0;
-  for (int i = tid; i < kNXi1; i += kThreads) {
-    double A = 0.0, Bs = 0.0;
-    if (i < kNXi1 - 2) {
-      const double x0 = S.xi1[i], x1 = S.xi1[i + 1];
-      const double ih = 1.0 / (x1 - x0), mid = 0.5 * (x1 + x0);
-      const double fd = rdf[i + 1] - rdf[i], fa = 0.5 * (rdf[i + 1] + rdf[i]);
-      Bs = fd * ih; A = fa - mid * Bs;
-      c0 += fd;
-    }
-    Xb[i] = A; Xb[kNXi1 + i] = Bs;
-  }
+  double c0 = ratdf_rows(S.xi1, rdf, Xb, Xb + kNXi1);
   c0 = block_sum(c0, red);
   c1 = block_sum(c1, red);
   if (tid == 0) { cst[2 * b] = c0; cst[2 * b + 1] = c1; }
@@ -292,9 +298,7 @@ __global__ __launch_bounds__(kThreads) void k_fe_direction(KStatic S, const doub
   __syncthreads();
   for (int i = tid; i < nvx - 1; i += kThreads) hermite_coeffs(ht[i], ht[i + 1], S.dv, hc[2 * i], hc[2 * i + 1]);
   __syncthreads();
-  Tables T;
-  T.zp = nullptr; T.W = nullptr; T.ht = ht; T.hc = hc; T.nvx = nvx; T.etab = nullptr;
-  tables_set_grid(T, S.vx0, S.dv, nvx);
+  const Tables T = make_tables(S, nullptr, nullptr, ht, hc);
   for (int i = tid; i < kNXi1; i += kThreads) {
     double H, dH;
     hermite_lookup_c(T, S.xi1[i], H, dH);
@@ -612,21 +616,19 @@ __global__ __launch_bounds__(kThreads) void k_fe_adjoint(KStatic S, const double
   const double c0b = block_sum(part, red);  // (contains the barrier that publishes ht)
   for (int i = tid; i < nvx - 1; i += kThreads) hermite_coeffs(ht[i], ht[i + 1], S.dv, hc[2 * i], hc[2 * i + 1]);
   __syncthreads();
-  Tables T;
-  T.zp = nullptr; T.W = nullptr; T.ht = ht; T.hc = hc; T.hcm = nullptr; T.Wm = nullptr; T.nvx = nvx; T.etab = nullptr;
-  T.Wb = nullptr; T.Hy = yb; T.Hs = sb;
-  tables_set_grid(T, S.vx0, S.dv, nvx);
+  Tables T = make_tables(S, nullptr, nullptr, ht, hc);
+  T.Hy = yb; T.Hs = sb;
   const double* Ab = Y + (size_t)b * 2 * kNXi1;
   const double* Sb = Ab + kNXi1;
   for (int i = tid; i < kNXi1; i += kThreads) {
     double H, dH;
     hermite_lookup_c(T, S.xi1[i], H, dH);
     rat[i] = exp(H);
-    // X construction (k_fe_vectors): Bs = fd ih, A = fa - mid Bs, c0 += fd   for i < 1022
+    // X construction (ratdf_rows): Bs = fd ih, A = fa - mid Bs, c0 += fd   for i < 1022
     double fd = 0.0, fa = 0.0;
     if (i < kNXi1 - 2) {
-      const double x0 = S.xi1[i], x1 = S.xi1[i + 1];
-      const double ih = 1.0 / (x1 - x0), mid = 0.5 * (x1 + x0);
+      double ih, mid;
+      xi1_cell(S.xi1, i, ih, mid);
       fa = Ab[i];
       fd = (Sb[i] - mid * fa) * ih + c0b;
     }

@@ -15,6 +15,8 @@
 //                                          several points per pixel (k_spectrum_fused.inc, k_forward.inc, k_spectrum_rows.inc)
 //   k_form_factor  a4-a10                : raw FormFactor.__call__ output (known-answer tests)
 //   k_chain.inc    a12, a14, a15         : the chain's rules around the sweeps (amplitudes, loss, their adjoint, gradient tail), once
+//   k_fwdmode.inc  a4-a10               : the chain of a point of the forward-mode kernels, once over the number type (make_lines_hd,
+//                                          hermite_hd, base_hd, point_hd, tie_and_renorm); the table builders' steps are in k_tables.inc
 //   k_hess_pairs   a16                   : exact per-lineout Hessian of the fit loss (hyper-dual forward mode, k_hessian.inc)
 //   k_jac_sweep    jax.jacfwd of a1     : Jacobian of the spectra w.r.t. the leaves and the Gauss-Newton curvature (k_jacobian.inc)
 //   k_ffjvp        jax.jvp of a4-a10     : forward mode of k_form_factor for arbitrary directions of the physical parameters and of f_e
@@ -112,6 +114,7 @@ constexpr int kFusedMaxIon = 2;  // k_spectrum_fused is instantiated for n_ion <
 #include "k_form_factor_2d.inc"
 #include "k_ats.inc"
 #include "k_peak.inc"
+#include "k_fwdmode.inc"
 #include "k_hessian.inc"
 #include "k_jacobian.inc"
 #include "k_ffjvp.inc"
