@@ -68,6 +68,13 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_fused(KStatic S, KCall K,
   //  column block this launch covers)
   const size_t gitem = (size_t)f_il * K.Btot + b;
   constexpr int TPF = kHalf, NW = TPF / 64;
+  // kLeanKs (the DLM instantiation with one species and the lane exchange): what the k_s evaluation needs does not live across the
+  // angle loops.  The fallbacks `use_ks ? cache : ks_eval` before and behind the sweeps share their expressions with the k_s cache
+  // fill of the prologue, and the compiler kept the fill's intermediates -- and the two frequencies no loop reads -- in registers
+  // for them: 17 VGPRs more than the file has, spilled to scratch.  Now the fill works on copies the compiler cannot tell from
+  // ws, and the third frequency of a pair is read again where a fallback needs it (w_third): the same values from the same
+  // expressions, no scratch.  (Measured, DESIGN.md section 4.1b.)
+  constexpr bool kLeanKs = GM == 1 && NI == 1 && EX;
   constexpr bool PAD = kSelectFree<NI>;   // the Hermite lookups read the out-of-grid cell that stage_commit writes (k_pairs.inc)
   const int ht = tid, lane = tid & 63, hw = tid >> 6;
   const int f = __builtin_amdgcn_readfirstlane(interleaved ? f_il : f0);
@@ -105,7 +112,16 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_fused(KStatic S, KCall K,
     {
       lines_load<NI>(lrec + gitem * kLineRec, 1, [](double v) { return uni(v); }, L);
     }
-    if (use_ks) ks_cache_fill(ksc, jp, ws, L.wpe2, npts);
+    if constexpr (kLeanKs) {   // (copies the compiler cannot tell from ws: the cache fill's square-root chains are its own)
+      double wsc[2][kPair + 1];
+#pragma unroll
+      for (int p = 0; p < 2; ++p)
+#pragma unroll
+        for (int q = 0; q <= kPair; ++q) { wsc[p][q] = ws[p][q]; asm volatile("" : "+v"(wsc[p][q])); }
+      if (use_ks) ks_cache_fill(ksc, jp, wsc, L.wpe2, npts);
+    } else {
+      if (use_ks) ks_cache_fill(ksc, jp, ws, L.wpe2, npts);
+    }
     zero_phase_halos(xs, Ls, hs, ht, TPF);
   }
   // Away from the laser line every point of a wavefront's pair sees |xi_i| >> 1: the ion terms are the asymptote and
@@ -119,6 +135,15 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_fused(KStatic S, KCall K,
     w_lo[p] = lane_f64(ws[p][0], 0);
     w_hi[p] = lane_f64(ws[p][kPair], 63);
   }
+  // (kLeanKs) the third frequency of a pair -- no angle loop reads it: the lane exchange stands for its base point -- comes from the
+  // frequency axis again where the fallbacks of the k_s cache before and behind the sweeps read it, by a load of its own each
+  // time, instead of living in a register across the four angle loops
+  auto w_third = [&](int p) {
+    const double* o = omgs;
+    int t = ht;
+    asm volatile("" : "+s"(o), "+v"(t));   // (the address too is formed here, not kept from the prologue)
+    return o[min(kPair * t + p * (npts / 2) + kPair, npts - 1)];
+  };
   const bool far0 = far_range_w<NI>(w_lo[0], w_hi[0], L), far1 = far_range_w<NI>(w_lo[1], w_hi[1], L);
   // (EX) frequency of the unit-boundary base point this lane evaluates behind the barrier (lane = 16 P + a)
   const double ex_wse = ((lane >> 4) & 1) ? w_hi[1] : w_hi[0];
@@ -154,7 +179,13 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_fused(KStatic S, KCall K,
     constexpr bool FAR = decltype(far_tag)::value;
     const int jb = jp[P];
     const int j2 = min(jb + kPair, npts - 1);
-    const double ks2 = EX ? (use_ks ? ksc[j2] : ks_eval(ws[P][kPair], L.wpe2)) : 0.0;
+    double wr[kPair + 1];
+    if constexpr (kLeanKs) {
+#pragma unroll
+      for (int q = 0; q <= kPair; ++q) wr[q] = q == kPair ? w_third(P) : ws[P][q];
+    }
+    const double (&wP)[kPair + 1] = [&]() -> const double (&)[kPair + 1] { if constexpr (kLeanKs) return wr; else return ws[P]; }();
+    const double ks2 = EX ? (use_ks ? ksc[j2] : ks_eval(wP[kPair], L.wpe2)) : 0.0;
     // The angle's constants (cos theta_a, w_a pref) come from the item's record of k_fused_prep by ONE scalar load, straight into
     // SGPRs, one iteration ahead of their use: wavefront-uniform and independent of the sample, they were two LDS reads, a
     // multiplication and four v_readfirstlane_b32 per iteration.  The product is k_fused_prep's: the same factors, the same bits.
@@ -180,7 +211,7 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_fused(KStatic S, KCall K,
         continue;
       }
       Base b0;
-      base_eval<NI, PAD>(ws[P][0], use_ks ? ksc[jb] : ks_eval(ws[P][0], L.wpe2), ct, L, T, b0);
+      base_eval<NI, PAD>(wP[0], use_ks ? ksc[jb] : ks_eval(wP[0], L.wpe2), ct, L, T, b0);
       // (EX) the lane's FIRST base point of this angle is what its left neighbour asks for: b0 itself is the second one by then
       const Base b0f = b0;
 #pragma unroll
@@ -195,7 +226,7 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_fused(KStatic S, KCall K,
           //  spills none; measured, DESIGN.md section 4.1b.  Tried again with the angle constants in SGPRs: still six.)
           neighbour_take<NI>(b0f, exu + a, ks2, ct, L, b1);
         } else {
-          base_eval<NI, PAD>(ws[P][i + 1], use_ks ? ksc[min(j + 1, npts - 1)] : ks_eval(ws[P][i + 1], L.wpe2), ct, L, T, b1);
+          base_eval<NI, PAD>(wP[i + 1], use_ks ? ksc[min(j + 1, npts - 1)] : ks_eval(wP[i + 1], L.wpe2), ct, L, T, b1);
         }
         row_step<NI, GM, ZH, FAR, PAD>(b0, b1, has_next, L, T, ct, wa, cw, xa[q], J[q], KA[q]);
         b0 = b1;
@@ -205,17 +236,25 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_fused(KStatic S, KCall K,
   if (far0) sweep(std::integral_constant<int, 0>{}, std::true_type{}); else sweep(std::integral_constant<int, 0>{}, std::false_type{});
   if (far1) sweep(std::integral_constant<int, 1>{}, std::true_type{}); else sweep(std::integral_constant<int, 1>{}, std::false_type{});
   TSFF_STAMP_WAVE(9);
+  double wl[2][kPair + 1];
+  if constexpr (kLeanKs) {
+#pragma unroll
+    for (int p = 0; p < 2; ++p)
+#pragma unroll
+      for (int q = 0; q <= kPair; ++q) wl[p][q] = q == kPair ? w_third(p) : ws[p][q];
+  }
+  const double (&wq)[2][kPair + 1] = [&]() -> const double (&)[2][kPair + 1] { if constexpr (kLeanKs) return wl; else return ws; }();
 #pragma unroll
   for (int q = 0; q < kStrip; ++q) {   // the k_L and omega_pe^2 columns of the rows from their angle sums (see KsAcc)
     const int j = JQ(q);
-    const double ksa = use_ks ? ksc[j] : ks_eval(ws[q >> 1][q & 1], L.wpe2);
-    const double ksb = use_ks ? ksc[min(j + 1, npts - 1)] : ks_eval(ws[q >> 1][(q & 1) + 1], L.wpe2);
+    const double ksa = use_ks ? ksc[j] : ks_eval(wq[q >> 1][q & 1], L.wpe2);
+    const double ksb = use_ks ? ksc[min(j + 1, npts - 1)] : ks_eval(wq[q >> 1][(q & 1) + 1], L.wpe2);
     ks_columns<NI>(KA[q], ksa, ksb, L, J[q]);
   }
   {   // the factor ws^2 (left out of the sweep) and the notch filter of the electron feature: x_j and xbar_j carry it
     const bool filt = f == TSFF_FEATURE_ELE && S.filt;
 #pragma unroll
-    for (int q = 0; q < kStrip; ++q) store_scaled(xs + XA(JQ(q)), xa[q], ws[q >> 1][q & 1], filt, S.filt, JQ(q));
+    for (int q = 0; q < kStrip; ++q) store_scaled(xs + XA(JQ(q)), xa[q], wq[q >> 1][q & 1], filt, S.filt, JQ(q));
   }
   __syncthreads();
   TSFF_STAMP(3);
@@ -281,13 +320,12 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_fused(KStatic S, KCall K,
   // adjoint instead: xbar_i -= (sn / M) h[i - p* - toff].  (Round 2 waited for half_sums here: two barriers and five butterflies
   // on the critical path of the chain, of which every microsecond is a microsecond of half-rate issue on this SIMD.)
   {
-    double v5[5] = {s0, s1, sn, a1b, a2b};
-#pragma unroll
-    for (int k = 0; k < 5; ++k) v5[k] = wave_sum(v5[k]);
-    if (lane == 0) {
-#pragma unroll
-      for (int k = 0; k < 5; ++k) m.red[kRedSums + k * NW + hw] = v5[k];   // (behind the slots of half_argmax, which a slower wavefront may still read)
-    }
+    // (one grouped reduction, wave_sums_scatter: 9 exchanges instead of 30, wave_sum's bits; the lane that holds sum k stores it)
+    const double v5[5] = {s0, s1, sn, a1b, a2b};
+    const double v = wave_sums_scatter<5>(v5, lane);
+    bool own;
+    const int k = scatter_lane<5>(lane, own);
+    if (own) m.red[kRedSums + k * NW + hw] = v;   // (behind the slots of half_argmax, which a slower wavefront may still read)
   }
   // (ybar lives in the memory of x: every thread has read its x window above -- half_argmax's barriers lie in between)
 #pragma unroll
@@ -340,9 +378,8 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_fused(KStatic S, KCall K,
 #pragma unroll
     for (int s = 0; s < NI; ++s) { LB.ixi[s] += xb * J[q].ixi[s]; LB.a_i[s] += xb * J[q].a_i[s]; LB.cs[s] += xb * J[q].cs[s]; }
   }
-  LB.pref *= 1.0 / L.pref;
-#pragma unroll
-  for (int s = 0; s < NI; ++s) LB.a_i[s] *= -0.5;   // deferred factor of point_fused
+  // (the factors 1 / pref of LB.pref -- d x_j / d pref = x_j / pref -- and -0.5 of LB.a_i, which point_fused defers, are applied in the
+  //  reduction below)
   // Every wavefront leaves the sums of its 64 lanes in global memory and is done: the sum over the four wavefronts and the two
   // features, the chain rule to the physical parameters (make_lines_adjoint), Ti tying, fraction renormalisation, activation and
   // the gradient mask are the work of one thread per LINEOUT in k_fused_finish, which runs behind this kernel in place of
@@ -350,15 +387,22 @@ __global__ __launch_bounds__(kHalf, 2) void k_spectrum_fused(KStatic S, KCall K,
   {
     double lb[kLBRec];
     lines_adj_store<NI>(LB, lb);
+    // One grouped reduction (wave_sums_scatter_scaled, tsff_device.h): the first lane of the group of four that holds sum k stores it,
+    // and the 63 copies of each sum that the butterflies made and threw away are not made.  The two factors go in with it: the same
+    // bits as the butterflies of the scaled values gave.
+    double lbs[NLB], lbc[NLB];
+    constexpr unsigned scaled = (1u << 5) | (1u << 9) | (NI > 1 ? 1u << 12 : 0u);   // (lines_adj_store: pref, a_i[s])
 #pragma unroll
-    for (int k = 0; k < NLB; ++k) lb[k] = wave_sum(lb[k]);
-    lb[NLB] = a1b; lb[NLB + 1] = a2b;   // (block sums: the same in every wavefront's record; the finish kernel reads wavefront 0's)
+    for (int k = 0; k < NLB; ++k) { lbs[k] = lb[k]; lbc[k] = k == 5 ? 1.0 / L.pref : ((scaled >> k) & 1u) ? -0.5 : 1.0; }
+    double mine = wave_sums_scatter_scaled<NLB, scaled>(lbs, lbc, lane);
+    bool own;
+    int k = scatter_lane<NLB>(lane, own);
+    // (block sums: the same in every wavefront's record; the finish kernel reads wavefront 0's.  Lanes 1 and 2 hold no sum to store)
+    if (lane == 1) { mine = a1b; k = NLB; }
+    if (lane == 2) { mine = a2b; k = NLB + 1; }
     // (component-major: lbrec[(k NW + hw) nitems + item] -- k_fused_finish reads it with one item per lane)
     const size_t nitems = (size_t)K.Btot * (interleaved ? 2 : 1);
-    double mine = 0.0;
-#pragma unroll
-    for (int k = 0; k < NLB + 2; ++k) mine = lane == k ? lb[k] : mine;
-    if (lane < NLB + 2) K.lbrec[((size_t)lane * NW + hw) * nitems + gitem] = mine;
+    if (own || lane == 1 || lane == 2) K.lbrec[((size_t)k * NW + hw) * nitems + gitem] = mine;
   }
   TSFF_STAMP(8);
 }

@@ -9,6 +9,7 @@
 #include <type_traits>
 
 #include "../../include/tsff.h"
+#include "wave_scatter.h"
 
 namespace tsff {
 
@@ -133,6 +134,108 @@ __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
+}
+
+// N sums at once by reduce-scatter along wave_sum's tree (the schedule: wave_scatter.h): value k ends in the lanes the schedule
+// names -- scatter_lane() tells a lane which -- with wave_sum's bits, after scatter_exchanges(N) exchanges instead of 6 N.
+// ONLY where all 64 lanes are active (DPP and lane swaps read disabled lanes' registers as they are).
+// One exchange at offset O: the lanes with bit O clear keep lo, the others hi; returns (kept) + (the partner's copy of the same value).
+//   32, 16: v_permlane32_swap / v_permlane16_swap exchange the upper half (odd rows) of the first operand with the lower half (even
+//           rows) of the second, so afterwards the two registers hold the kept value and the partner's in EVERY lane -- in either
+//           order, which the addition does not see.  No select, no LDS.
+//   8, 4:   the value to send is selected, goes through ds_bpermute (__shfl_xor), and is added to the selected kept one.
+template <int O>
+__device__ __forceinline__ double scatter_exchange_add(double lo, double hi, int lane) {
+  static_assert(O == 32 || O == 16 || O == 8 || O == 4, "offsets 2 and 1 never scatter");
+  if constexpr (O >= 16) {
+    const unsigned a0 = __double2loint(lo), a1 = __double2hiint(lo), b0 = __double2loint(hi), b1 = __double2hiint(hi);
+    if constexpr (O == 32) {
+      const auto r0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false), r1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
+      return __hiloint2double(r1[0], r0[0]) + __hiloint2double(r1[1], r0[1]);
+    } else {
+      const auto r0 = __builtin_amdgcn_permlane16_swap(a0, b0, false, false), r1 = __builtin_amdgcn_permlane16_swap(a1, b1, false, false);
+      return __hiloint2double(r1[0], r0[0]) + __hiloint2double(r1[1], r0[1]);
+    }
+  } else {
+    const bool up = lane & O;
+    return (up ? hi : lo) + __shfl_xor(up ? lo : hi, O, 64);
+  }
+}
+
+// v of lane ^ O.  8, 2, 1 by DPP (row_ror:8, quad_perm [2,3,0,1] and [1,0,3,2]: registers only), 4 by ds_bpermute
+template <int O>
+__device__ __forceinline__ double xor_lane_f64(double v) {
+  if constexpr (O == 8 || O == 2 || O == 1) {
+    constexpr int ctrl = O == 8 ? 0x128 : O == 2 ? 0x4E : 0xB1;
+    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), ctrl, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), ctrl, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+  } else {
+    return __shfl_xor(v, O, 64);
+  }
+}
+
+template <int N, int O>
+__device__ __forceinline__ double wave_sums_scatter_step(const double (&w)[N], int lane) {
+  if constexpr (O == 0) {
+    static_assert(N == 1, "one value per lane is left behind the last offset");
+    return w[0];
+  } else if constexpr (N > 1) {
+    constexpr int H = (N + 1) / 2;
+    double u[H];
+#pragma unroll
+    for (int i = 0; i < H; ++i) u[i] = scatter_exchange_add<O>(w[i], H + i < N ? w[H + i] : 0.0, lane);   // (0.0: the padding of an odd n)
+    return wave_sums_scatter_step<H, O / 2>(u, lane);
+  } else {
+    double u[1];
+    if constexpr (O >= 16) u[0] = scatter_exchange_add<O>(w[0], w[0], lane);   // (v + v[lane ^ O] in every lane)
+    else u[0] = w[0] + xor_lane_f64<O>(w[0]);
+    return wave_sums_scatter_step<1, O / 2>(u, lane);
+  }
+}
+
+template <int N>
+__device__ __forceinline__ double wave_sums_scatter(const double (&v)[N], int lane) {
+  static_assert(N >= 1 && N <= kScatterMax, "one value per group of four lanes at most");
+  return wave_sums_scatter_step<N, 32>(v, lane);
+}
+
+// The same with a factor c[k] (the same in every lane) on the values whose bit is set in SCALED: the sums of c[k] v[k].  What the
+// lanes hold is what wave_sum(c[k] * v[k]) left in the lanes 0 .. 31 -- the lanes whose copies the records of the one-sweep kernel
+// were stored from -- when it was compiled with floating-point contraction: its first step was not the sum of two rounded
+// products but  fma(v, c, round(c v[lane ^ 32])),  and from the offset 16 on the lanes 0 .. 31 add among themselves.  Here the
+// exchange at 32 carries the values without their factor; both lanes of a pair then hold the lower lane's value and the upper
+// lane's, and the one that keeps the slot evaluates the lower lane's expression.  (c = 1 for the other value of the slot: exact.)
+template <int N, unsigned SCALED>
+__device__ __forceinline__ double wave_sums_scatter_scaled(const double (&v)[N], const double (&c)[N], int lane) {
+  static_assert(N >= 2 && N <= kScatterMax && SCALED < (1u << N), "one value per group of four lanes at most; the offset 32 must scatter");
+  constexpr int H = (N + 1) / 2;
+  double u[H];
+#pragma unroll
+  for (int i = 0; i < H; ++i) {
+    const double lo = v[i], hi = H + i < N ? v[H + i] : 0.0;
+    const bool slo = (SCALED >> i) & 1u, shi = H + i < N && ((SCALED >> (H + i)) & 1u);
+    if (slo || shi) {
+      const double cc = (lane & 32) ? (shi ? c[H + i < N ? H + i : i] : 1.0) : (slo ? c[i] : 1.0);
+      const auto r0 = __builtin_amdgcn_permlane32_swap(__double2loint(lo), __double2loint(hi), false, false);
+      const auto r1 = __builtin_amdgcn_permlane32_swap(__double2hiint(lo), __double2hiint(hi), false, false);
+      const double lower = __hiloint2double(r1[0], r0[0]), upper = __hiloint2double(r1[1], r0[1]);   // (of the kept value: lane & 31's, lane | 32's)
+      u[i] = __builtin_fma(lower, cc, upper * cc);
+    } else {
+      u[i] = scatter_exchange_add<32>(lo, hi, lane);
+    }
+  }
+  return wave_sums_scatter_step<H, 16>(u, lane);
+}
+
+// the value whose sum wave_sums_scatter<N> left in this lane; own: this lane is the one of its group that stores it
+template <int N>
+__device__ __forceinline__ int scatter_lane(int lane, bool& own) {
+  constexpr uint64_t values = scatter_values(N);
+  constexpr uint32_t valid = scatter_valid(N);
+  const int g = lane >> 2;
+  own = (lane & 3) == 0 && ((valid >> g) & 1u);
+  return (int)(values >> (4 * g)) & 15;
 }
 
 // sum over the workgroup; result valid in every thread.  scratch: >= 4 doubles of LDS.
