@@ -10,7 +10,8 @@ splits ties evenly; ties have measure zero), linear interpolation -> slope of th
 ``where`` masks -> pass-through.
 
 The second half restates the oracle's 2-D form factor (rotate_df, calc_chi_vals_2d, form_factor_2d) and its ARTS instrument chain
-(ats_spectrum); ``ff2d_adjoint`` / ``ats_adjoint`` are the references of tests/test_ff2d_adjoint_twin.py.
+(ats_spectrum); ``ff2d_adjoint`` / ``ats_adjoint`` are the references of tests/test_ff2d_adjoint_twin.py, ``loss_adjoint`` of
+tests/test_loss_grad_entries.py and ``ff1d_adjoint`` of tests/test_form_factor_adjoint_twin.py.
 """
 from __future__ import annotations
 
@@ -391,6 +392,41 @@ def value_and_grad(cfg, sa, normed_np, batch, i_norm, e_norm, names, activate=Tr
     grads = torch.autograd.grad(val, [normed[k] for k in names], allow_unused=True)
     out = {k: (g.numpy() if g is not None else np.zeros_like(normed_np[k])) for k, g in zip(names, grads)}
     return float(val.detach()), out, E.detach().numpy(), I.detach().numpy()
+
+
+def ff1d_adjoint(f, x, fe, Pbar, slots, want_fe=True, chunk=16):
+    """The adjoint of the 1-D form factor of ONE lineout as the sum of its terms, and the sum of their absolute values:
+
+      g[k] = sum_(g,i,a) Pbar[g,i,a] dP[g,i,a]/dx_k,   A[k]: |.| of every term
+
+    ``f``: (px [NP], fe [nvx]) -> P [G, npts, n_angles], differentiable in both (tests/angular_twin.form_factor_fn: form_factor
+    with chi_table of the same fe; every species its own leaf, ti_same all zero); ``x`` [NP] physical, ``fe`` [nvx], ``Pbar`` the
+    seed, ``slots``: the entries of px to differentiate.  d P / d x is taken by forward mode, ``chunk`` unit directions at a time:
+    the terms are per point, the chain is not cut further (the path of an f_e node through W and its direct path arrive summed).
+    A is the scale at which two float64 summations of these terms may differ, entry by entry (as in ff2d_adjoint, loss_adjoint).
+    Returns (g_phys [len(slots)], A_phys, g_fe [nvx], A_fe); the last two None without ``want_fe``."""
+    x0, f0, Pb = _t(x), _t(fe), _t(np.asarray(Pbar, dtype=np.float64))
+    ns, nvx = len(slots), f0.numel()
+    n = ns + (nvx if want_fe else 0)
+    TX, TF = torch.zeros((n, x0.numel()), dtype=DT), torch.zeros((n, nvx), dtype=DT)
+    TX[torch.arange(ns), torch.as_tensor(list(slots))] = 1.0
+    if want_fe:
+        TF[ns + torch.arange(nvx), torch.arange(nvx)] = 1.0
+    one = lambda tx, tf: torch.func.jvp(f, (x0, f0), (tx, tf))[1]
+    g, A = [], []
+    for lo in range(0, n, chunk):
+        t = Pb[None] * torch.func.vmap(one)(TX[lo:lo + chunk], TF[lo:lo + chunk])   # [chunk, G, npts, n_angles]
+        g.append(t.sum(dim=(1, 2, 3)))
+        A.append(t.abs().sum(dim=(1, 2, 3)))
+    g, A = torch.cat(g).numpy(), torch.cat(A).numpy()
+    return (g[:ns], A[:ns], g[ns:], A[ns:]) if want_fe else (g, A, None, None)
+
+
+def ff1d_reverse(f, x, fe, Pbar):
+    """One backward of <Pbar, P>: (d / d px [NP], d / d fe [nvx]) -- what ff1d_adjoint's terms must sum to."""
+    x0, f0 = _t(x).clone().requires_grad_(True), _t(fe).clone().requires_grad_(True)
+    gx, gf = torch.autograd.grad((_t(np.asarray(Pbar, dtype=np.float64)) * f(x0, f0)).sum(), [x0, f0])
+    return gx.numpy(), gf.numpy()
 
 
 def value_and_grad_fe(cfg, sa, normed_np, batch, i_norm, e_norm, names, fe_batch, activate=True):

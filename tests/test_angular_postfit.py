@@ -340,6 +340,68 @@ def test_angular_jacobian_free_form(torch_mod):
     assert grad.shape == g.shape and np.all(np.abs(g - grad) <= bound), np.max(np.abs(g - grad) / bound)
 
 
+L1_OFFSET = 1.0   # the background tests/test_angular_loop_device.py puts under the data for l1: every |d - E| stays off zero
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("method", ["l2", "l1", "log-cosh", "poisson"])
+def test_angular_vg_loss_dlm_matches_twin(torch_mod, method):
+    """vg_loss on the DLM deck (leaves Te, ne, m, lam, amp1, amp2) for every loss functional, in three steps.  Value: the reference's
+    functional (orc.loss_functional, the blue / red masks on the resolution-unit axis, the mean of each over the image, halved:
+    _angular_wcol) evaluated on the host at the device's image, rtol 1e-12.  Seed: _angular_value_device's Ebar against torch
+    autograd of that functional at the device's image, 1e-12 of the seed's largest entry.  Gradient: per leaf within 1e-7 of its own
+    absolute accumulation sum |Jt| |Ebar| of the twin's image Jacobian (_twin_dlm) -- the bound of the free-form check above.
+    The test of tests/test_gpu_parity.py holds this gradient to difference quotients at 1e-4."""
+    import torch
+    from oracle import tsadar_oracle_torch as ot
+    from tsadar_amd import ThomsonParams, tree
+    from tsadar_amd.loss_function import LossFunction
+
+    cfg, sa, batch, lam = _setup(False)
+    cfg = copy.deepcopy(cfg)
+    cfg["optimizer"]["loss_method"] = method
+    batch = dict(batch)
+    if method == "l1":
+        batch["e_data"] = batch["e_data"] + L1_OFFSET
+    lf = LossFunction(cfg, sa, batch)
+    tp = ThomsonParams(cfg["parameters"], 1, batch=False, activate=True)
+    names, _, Jt = _twin_dlm()
+    diff, static = tree.partition(tp, tree.get_filter_spec(None, tp))
+    assert [k for (_, k), _ in diff.slots] == names == ["Te", "ne", "m", "lam", "amp1", "amp2"]   # (Jt's ravel order)
+    x, lf.unravel_weights = tree.ravel_pytree(diff)
+    value, grad = lf.vg_loss(x, static, batch)
+    eng = lf.ts_diag.engine(True)
+    val_dev, E, Ebar = lf._angular_value_device(eng, tp, batch, True)
+    Ebar = Ebar.cpu().numpy()
+    assert val_dev == value
+    d, un, r = batch["e_data"], lf.e_norm**2, cfg["data"]["fit_rng"]
+    blue, red = (lam > r["blue_min"]) & (lam < r["blue_max"]), (lam > r["red_min"]) & (lam < r["red_max"])
+    assert blue.any() and red.any() and E.shape == (ROWS, N_LAM)
+    if method == "l1":
+        assert np.min(np.abs(d - E)[:, blue | red]) > 1e-6 * np.max(E)
+    err = orc.loss_functional(d, E, un, method)
+    ref = 0.5 * (np.mean(err[:, blue]) + np.mean(err[:, red]))
+    assert abs(value - ref) <= 1e-12 * abs(ref), (method, value, ref)
+    # the seed: autograd of the same functional (the twin's, oracle/tsadar_oracle_torch.py: _sums_of_spectra.fun) at the device's image
+    Et, dt = ot._t(E).clone().requires_grad_(True), ot._t(d)
+    ft = {"l1": lambda: torch.abs(dt - Et) / un, "l2": lambda: torch.square(dt - Et) / un,
+          "log-cosh": lambda: torch.log(torch.cosh(dt - Et)), "poisson": lambda: Et - dt * torch.log(Et)}[method]()
+    tb, tr = torch.as_tensor(blue), torch.as_tensor(red)
+    val_t = 0.5 * (ft[:, tb].mean() + ft[:, tr].mean())
+    seed, = torch.autograd.grad(val_t, Et)
+    seed = seed.numpy()
+    assert abs(float(val_t) - ref) <= 1e-12 * abs(ref)
+    assert np.max(np.abs(Ebar - seed)) <= 1e-12 * np.max(np.abs(seed)), (method, np.max(np.abs(Ebar - seed)) / np.max(np.abs(seed)))
+    # the gradient, each leaf on its own scale
+    g = np.tensordot(Jt, Ebar, axes=([1, 2], [0, 1]))
+    A = np.tensordot(np.abs(Jt), np.abs(Ebar), axes=([1, 2], [0, 1]))
+    ratio = np.abs(grad - g) / A
+    record(f"angular_vg_loss[dlm-{method}]", f"max |grad - Jt.Ebar| / sum |Jt||Ebar| {np.max(ratio):.3e} (bound 1e-07), per leaf " +
+           " ".join(f"{n} {v:.1e}" for n, v in zip(names, ratio)))
+    print(method, "per leaf |grad - Jt.Ebar| / sum |Jt||Ebar|:", dict(zip(names, ratio)), "|g| / A:", dict(zip(names, np.abs(g) / A)))
+    assert grad.shape == g.shape and np.all(np.abs(grad - g) <= 1e-7 * A), (method, dict(zip(names, ratio)))
+
+
 def _get_sigmas(hess, batch_size):
     """postprocess.get_sigmas' arithmetic (postprocess.py:205-242) for 1 x 1 blocks."""
     keys = [(sp, k) for sp in hess for k in hess[sp]]
