@@ -24,6 +24,7 @@
  *       tsff_loss_grad(_fe), tsff_form_factor_grad, tsff_form_factor_2d_grad, tsff_ats_adjoint
  *   jax.jvp of FormFactor.__call__, and of add_ATS_IRF + reduce_ATS_to_resunit (the reference has no such call; its post-fit
  *       half on angular decks, postprocess.py:106-136, differentiates the whole chain twice)   tsff_form_factor_jvp, tsff_ats_jvp
+ *   jax.jvp of FormFactor.calc_in_2D (the post-fit half of the arts2v decks)                     tsff_form_factor_2d_jvp
  *   LossFunction.h_loss_wrt_params (equinox.filter_hessian) inverse/loss_function.py:170-188  tsff_loss_hess
  *   jax.jacfwd of ThomsonScatteringDiagnostic.__call__ w.r.t. the normalised leaves (the reference has no such call: its
  *       uncertainties come from the full Hessian, postprocess.py:188-251)           tsff_spectrum_jacobian / tsff_loss_gauss_newton
@@ -41,7 +42,7 @@
  *   - return value 0 = success, negative = error, text via tsff_last_error();
  *   - a refused call (negative return) of tsff_forward, tsff_loss_grad(_packed, _fe), tsff_loss_hess, tsff_spectrum_jacobian,
  *     tsff_loss_gauss_newton, tsff_array_loss,
- *     tsff_adam_fit, tsff_lm_fit, tsff_angular_fit, tsff_form_factor(_grad, _jvp), tsff_form_factor_2d(_range, _save, _grad),
+ *     tsff_adam_fit, tsff_lm_fit, tsff_angular_fit, tsff_form_factor(_grad, _jvp), tsff_form_factor_2d(_range, _save, _grad, _jvp),
  *     tsff_ats_spectrum, tsff_ats_adjoint and tsff_ats_jvp has enqueued nothing: their arguments, LDS budgets and buffers are checked before the first
  *     launch, and tsff_last_launch reports an empty list (other entry points may have enqueued work before a failure);
  *   - a call that breaks several conditions is refused for the first of: the entry point's own arguments (-1), the active slot
@@ -60,7 +61,7 @@
 extern "C" {
 #endif
 
-#define TSFF_ABI_VERSION 17
+#define TSFF_ABI_VERSION 18
 /* error codes (every entry point returns 0 or one of these; text via tsff_last_error):
  * -1 bad argument, -2 unsupported configuration / option, -3 not a differentiable leaf, -5 HIP runtime error,
  * -22 stale or foreign token of saved projection records (tsff_form_factor_2d_grad),
@@ -288,6 +289,28 @@ int tsff_form_factor_2d_grad(tsff_handle *h, int32_t feature, const double *phys
                              double ud_angle_deg, double va_angle_deg, int32_t B, int64_t point_begin,
                              int64_t point_end, uint64_t saved_token, const double *Pbar, double *grad_phys,
                              double *grad_fe2d);
+
+/* Forward mode of tsff_form_factor_2d for ONE shared table, 4 <= nv <= 256, and n_dir directions at once:
+ *   P_dot[k] = dP/dphys . phys_dot[k] + dP/dfe2d . fe2d_dot[k].
+ * `phys` [B][NP] holds PHYSICAL parameters, handled as tsff_form_factor_2d / _2d_grad handle them (no activation, Ti tying);
+ *   phys_dot [n_dir][B][NP] (device); fe2d_dot [n_dir][nv][nv] (device) or NULL: no table direction;
+ *   P [B][G][npts][n_angles] (device) or NULL: the value, bit for bit what tsff_form_factor_2d_save writes (that kernel writes it);
+ *   P_dot [n_dir][B][G][npts][n_angles] (device).
+ * [point_begin, point_end) as in tsff_form_factor_2d_range / _save (point_end < 0: to the end); points outside the range are left
+ * untouched in P and P_dot.  The call runs a saving forward (its records feed the tangents: proj2d_doubles(nv) doubles per point
+ * in the handle, and with fe2d_dot three projections of nv doubles per point more), so it INVALIDATES the token of any earlier
+ * tsff_form_factor_2d_save on the handle, and leaves none of its own.  The directions run three to a launch (the groups loop inside
+ * the call, n_dir is unbounded); with fe2d_dot the table of every direction that has a non-zero entry is projected
+ * (k_ff2d_project; a flag per direction is made on the device, the host does not look at it), and a direction whose table tangent
+ * is all zeros gives the same bits as the same call with fe2d_dot = NULL.  Conventions: the two linear lookups at |xi_e|
+ * carry their cell's slope where the position is not clamped and none where it is, the half-plane term of the rotation angle carries
+ * no tangent, the ion terms follow tsff_form_factor_jvp (Z' with its slope, no curvature).  Two calls give bit-identical results and
+ * a point's result does not depend on the range it was computed in (no atomics, every sum in a fixed order).
+ * nv > 256 (no records there): -2; per-lineout tables are not taken (the signature has none).  A null phys, fe2d, phys_dot or P_dot,
+ * n_dir < 1 or a bad range: -1. */
+int tsff_form_factor_2d_jvp(tsff_handle *h, int32_t feature, const double *phys, const double *fe2d, int32_t nv,
+                            double ud_angle_deg, double va_angle_deg, int32_t B, int32_t n_dir, const double *phys_dot,
+                            const double *fe2d_dot, int64_t point_begin, int64_t point_end, double *P, double *P_dot);
 
 /* Angular (ARTS) instrument chain for one image P[G][npts][n_angles] (device; from tsff_form_factor_2d or, for a 1-D
  * distribution function, tsff_form_factor): FitModel.electron_spectrum "angular_full" branch

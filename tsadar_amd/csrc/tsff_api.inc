@@ -129,6 +129,8 @@ struct tsff_handle {
   tsff::DevBuf jrows;              // tsff_spectrum_jacobian / tsff_loss_gauss_newton: per persistent workgroup the row form's spectrum and
                                    // tangents ((1 + n_active) x npts doubles) and the Gauss-Newton call's Jacobian rows (n_active x 1024)
   tsff::DevBuf jv_htd, jv_X, jv_cst, jv_Wd;   // tsff_form_factor_jvp: the table tangents of a block of directions (k_fe_direction + k_wgemm<2>)
+  tsff::DevBuf ff2j_tab, ff2j_pad, ff2j_P, ff2j_flags;   // tsff_form_factor_2d_jvp: the projections of a group's tangent tables, the padded tangent
+                                          // table (L1/L2 path), the value when the caller asks for none, which directions have a table tangent
   tsff::DevBuf ats_E;              // tsff_ats_jvp: the third tangent image (ats_C, ats_D and this one hold M', A', B')
   tsff::DevBuf lm_ws;              // tsff_lm_fit: the gradient [B][n_active] and Gauss-Newton matrix [B][n_active][n_active] of an evaluation
   size_t smem_adjoint = 0;
@@ -401,6 +403,13 @@ static auto form_factor_2d_adj_kernel(int n_ion, bool lds) {
   return with_ion<TSFF_MAX_ION>(n_ion, [&](auto N) { return lds ? &k_form_factor_2d_adj<N.value, true, TSFF_2D_GROUPS_LDS> : &k_form_factor_2d_adj<N.value, false, TSFF_2D_GROUPS_L2>; });
 }
 
+// the forward mode of the 2-D form factor: the projection of a tangent table (the forward's workgroup), the tail in groups of three
+constexpr int kFf2dJvpW = 3;
+static auto ff2d_project_kernel(int n_ion, bool lds) {
+  return with_ion<TSFF_MAX_ION>(n_ion, [&](auto N) { return lds ? &k_ff2d_project<N.value, true, TSFF_2D_GROUPS_LDS> : &k_ff2d_project<N.value, false, TSFF_2D_GROUPS_L2>; });
+}
+static auto ff2d_jvp_kernel(int n_ion) { return with_ion<TSFF_MAX_ION>(n_ion, [](auto N) { return &k_ff2d_jvp<N.value, kFf2dJvpW>; }); }
+
 // More dynamic LDS than the default limit: raised once, at tsff_create, on every instantiation the selectors ship for the
 // handle's ion count and on the single kernels that need it; no launch sets it
 // (the attribute is process-wide, not per handle, and is never lowered: the families sized by the velocity grid get the CU's
@@ -435,6 +444,7 @@ static hipError_t raise_lds_limits(int n_ion) {
   raise(jac_kernel(n_ion, 3, false));
   raise(jac_kernel(n_ion, 3, true));
   raise(ffjvp_kernel(n_ion));
+  for (int a = 0; a < 2; ++a) raise(ff2d_project_kernel(n_ion, a));
   raise(&k_fe_direction);
   raise(&k_fe_adjoint);
   raise(&k_ff2d_table_adj);
@@ -1610,6 +1620,84 @@ int tsff_form_factor_2d_save(tsff_handle* h, int32_t feature, const double* phys
   h->proj_token = (t << 16) | (h->proj_counter & 0xffff) | 1ull << 63;
   *token = h->proj_token;
   return 0;
+}
+
+// ---- its forward mode: the saving forward, per table direction the projection of the tangent table, then the tail in groups of
+// kFf2dJvpW directions (k_ff2d_jvp.inc)
+struct FormFactor2dJvpPlan {
+  FormFactor2dPlan fwd;            // the saving forward of the range
+  int n_dir = 0;
+  bool tab = false;                // fe2d_dot given: every direction's table is projected
+  long npoint = 0;
+  size_t tail_smem = 0;
+  unsigned tail_grid = 0;
+};
+
+static int form_factor_2d_jvp_prepare(tsff_handle* h, int feature, int nv, int B, int n_dir, bool tab, bool want_P, int64_t point_begin,
+                                      int64_t point_end, FormFactor2dJvpPlan& p) {
+  p.n_dir = n_dir; p.tab = tab;
+  if (int rc = form_factor_2d_prepare(h, feature, nv, true, B, point_begin, point_end, true, p.fwd)) return rc;
+  p.npoint = p.fwd.end - p.fwd.begin;
+  if (p.npoint == 0) return 0;
+  p.tail_smem = sizeof(double) * ff2d_jvp_smem_doubles(nv, kFf2dJvpW);
+  // one wavefront per workgroup, each with a contiguous run of points: enough of them to fill the device's wavefront slots
+  p.tail_grid = (unsigned)std::min<long>(p.npoint, (long)h->ncu2d() * 32);
+  if (tab) {
+    TSFF_ENSURE(h, h->ff2j_tab, (size_t)std::min(kFf2dJvpW, n_dir) * p.npoint * nv * sizeof(double));
+    if (!p.fwd.lds) TSFF_ENSURE(h, h->ff2j_pad, pad2d_doubles(nv) * sizeof(double));
+    TSFF_ENSURE(h, h->ff2j_flags, (size_t)n_dir * sizeof(int));
+  }
+  if (!want_P) TSFF_ENSURE(h, h->ff2j_P, (size_t)p.fwd.end * sizeof(double));
+  return 0;
+}
+
+static int form_factor_2d_jvp_enqueue(tsff_handle* h, const FormFactor2dJvpPlan& p, const double* phys, const double* fe2d, double ud_angle_deg,
+                                      double va_angle_deg, const double* phys_dot, const double* fe2d_dot, double* P, double* P_dot) {
+  if (p.npoint == 0) return 0;
+  const FormFactor2dPlan& q = p.fwd;
+  const int nv = q.nv;
+  if (int rc = form_factor_2d_enqueue(h, q, phys, fe2d, ud_angle_deg, va_angle_deg, P ? P : h->ff2j_P.as<double>())) return rc;
+  invalidate_proj(h);   // (the records are this call's own: no token names them)
+  if (int rc = timing_begin(h)) return rc;
+  const double ud = ud_angle_deg * kPi / 180.0, va = va_angle_deg * kPi / 180.0;
+  if (p.tab) TSFF_LAUNCH0(h, k_ff2d_tabflags, dim3(p.n_dir), dim3(kThreads), 0, h->stream, fe2d_dot, nv, h->ff2j_flags.as<int>());
+  for (int d0 = 0; d0 < p.n_dir; d0 += kFf2dJvpW) {
+    const int nd = std::min(kFf2dJvpW, p.n_dir - d0);
+    for (int k = 0; p.tab && k < nd; ++k) {
+      const double* table = fe2d_dot + (size_t)(d0 + k) * nv * nv;
+      if (!q.lds) {   // the padded copy of the tangent table: its ghost cells are the tangents of the table's
+        TSFF_LAUNCH0(h, k_pad2d, dim3(1), dim3(kThreads), 0, h->stream, table, nv, h->ff2j_pad.as<double>());
+        table = h->ff2j_pad.as<double>() + pad2d_margin(nv);
+      }
+      dim3 grid((unsigned)std::min((p.npoint + q.groups - 1) / q.groups, q.max_grid)), block(q.groups * kThreads);
+      TSFF_LAUNCH_FN(h, ff2d_project_kernel(h->n_ion, q.lds), ("k_ff2d_project", h->n_ion, q.lds, q.groups), grid, block, q.smem, h->stream,
+                     h->S, phys, table, nv, ud, va, q.feature, q.begin, q.end, h->ff2j_tab.as<double>() + (size_t)k * p.npoint * nv,
+                     h->ff2j_flags.as<int>() + d0 + k);
+    }
+    Ff2dJvpArgs A{};
+    A.d0 = d0; A.nd = nd; A.B = q.B; A.nv = nv; A.feature = q.feature;
+    A.pbegin = q.begin; A.pend = q.end; A.ud_ang = ud; A.va_ang = va;
+    A.phys = phys; A.phys_dot = phys_dot; A.proj = h->proj.as<double>();
+    A.f1tab = p.tab ? h->ff2j_tab.as<double>() : nullptr;
+    A.tabflags = p.tab ? h->ff2j_flags.as<int>() + d0 : nullptr;
+    A.P_dot = P_dot;
+    TSFF_LAUNCH_FN(h, ff2d_jvp_kernel(h->n_ion), ("k_ff2d_jvp", h->n_ion, kFf2dJvpW), dim3(p.tail_grid), dim3(kFf2dJvpThreads), p.tail_smem,
+                   h->stream, h->S, A);
+    TSFF_HIP(h, hipGetLastError());
+  }
+  return timing_end(h);
+}
+
+int tsff_form_factor_2d_jvp(tsff_handle* h, int32_t feature, const double* phys, const double* fe2d, int32_t nv, double ud_angle_deg,
+                            double va_angle_deg, int32_t B, int32_t n_dir, const double* phys_dot, const double* fe2d_dot,
+                            int64_t point_begin, int64_t point_end, double* P, double* P_dot) {
+  DevGuard dg__(h);
+  if (!h) return -1;
+  if (!phys || !fe2d || !phys_dot || !P_dot || B < 1 || n_dir < 1 || feature < 0 || feature > 1 || nv < 4) return fail(h, -1, "bad argument");
+  if (nv > 256) return fail(h, -2, "tsff_form_factor_2d_jvp: nv <= 256 (the forward mode reads the projection records of a saving forward)");
+  FormFactor2dJvpPlan p;
+  if (int rc = form_factor_2d_jvp_prepare(h, feature, nv, B, n_dir, fe2d_dot != nullptr, P != nullptr, point_begin, point_end, p)) return rc;
+  return form_factor_2d_jvp_enqueue(h, p, phys, fe2d, ud_angle_deg, va_angle_deg, phys_dot, fe2d_dot, P, P_dot);
 }
 
 // ---- its adjoint for the points [begin, end) (a rank's share; the adjoints are sums over points) of one table shared by all

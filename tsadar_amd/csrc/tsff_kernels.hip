@@ -21,6 +21,8 @@
 //   k_jac_sweep    jax.jacfwd of a1     : Jacobian of the spectra w.r.t. the leaves and the Gauss-Newton curvature (k_jacobian.inc)
 //   k_ffjvp        jax.jvp of a4-a10     : forward mode of k_form_factor for arbitrary directions of the physical parameters and of f_e
 //                                          (k_ffjvp.inc; k_fe_direction: the table tangents; k_ats_*_jvp: the ARTS chain's tangent form)
+//   k_ff2d_project, k_ff2d_jvp           : forward mode of k_form_factor_2d from the saving forward's records: the projection of a tangent
+//                                          table, and the tail on TN<W> (k_ff2d_jvp.inc)
 //   k_adam_step    loops.py:59-95       : one Adam step + best tracking on the packed loss and gradient (tsff_adam_fit, k_adam.inc)
 //   k_lbfgs_step   loops.py:20-56        : one evaluation's step of unbounded L-BFGS-B on the packed loss and gradient (tsff_lbfgs_fit)
 //   k_lm_step      (no reference row)    : one evaluation's step of the per-lineout Levenberg-Marquardt fit on k_jac_sweep's loss,
@@ -118,6 +120,7 @@ constexpr int kFusedMaxIon = 2;  // k_spectrum_fused is instantiated for n_ion <
 #include "k_hessian.inc"
 #include "k_jacobian.inc"
 #include "k_ffjvp.inc"
+#include "k_ff2d_jvp.inc"
 #include "k_adam.inc"
 #include "k_lbfgs.inc"
 #include "k_lm.inc"

@@ -365,6 +365,22 @@ class SphericalHarmonics:
         self.set_params(theta)
         return out
 
+    def jvp(self, step: float = 1e-6) -> np.ndarray:
+        """d f_e[nvx, nvx] / d get_params(): one table direction per generator value, [n, nvx, nvx], by central differences of the
+        generator with the step of ``_vjp_fd`` (the forward-mode counterpart of ``vjp``: <fe_bar, jvp()[j]> = vjp(fe_bar)[j])."""
+        theta = self.get_params()
+        out = np.zeros((theta.size, self.nvx, self.nvx))
+        for i in range(theta.size):
+            vals = []
+            for sgn in (+1.0, -1.0):
+                t = theta.copy()
+                t[i] += sgn * step
+                self.set_params(t)
+                vals.append(self())
+            out[i] = (vals[0] - vals[1]) / (2.0 * step)
+        self.set_params(theta)
+        return out
+
     def get_unnormed_m(self) -> float:
         return 1.0 / (1.0 + np.exp(-self.normed_m)) * self.m_scale + self.m_shift
 

@@ -489,6 +489,35 @@ class Engine:
         L.check(self.lib, self.h, rc)
         return gp, gf
 
+    def form_factor_2d_jvp(self, feature, phys, fe2d, phys_dot, fe2d_dot=None, ud_angle=0.0, va_angle=0.0, want_P=False, point_range=None):
+        """Forward mode of form_factor_2d for one shared table, nv <= 256 (tsff_form_factor_2d_jvp): phys_dot [n_dir, B, NP] and
+        fe2d_dot [n_dir, nv, nv] (or None: no table direction) -> (P [B, G, npts, n_angles] or None, P_dot [n_dir, B, G, npts,
+        n_angles]) as CUDA tensors, P_dot[k] = dP/dphys . phys_dot[k] + dP/dfe2d . fe2d_dot[k]; nothing is synchronised.
+        ``point_range = (begin, end)``: that slice of the flat point list only, the rest zero.  The call runs a saving forward of its
+        own: the records of an earlier ``form_factor_2d(save=True)`` are gone after it."""
+        torch = self.torch
+        phys_d = self.dev(phys).reshape(-1, self.NP)
+        B = phys_d.shape[0]
+        fe_d = self.dev(fe2d)
+        assert fe_d.dim() == 2 and fe_d.shape[0] == fe_d.shape[1], "form_factor_2d_jvp takes one shared table"
+        nv = int(fe_d.shape[0])
+        pd = self.dev(phys_dot).reshape(-1, B, self.NP)
+        n_dir = int(pd.shape[0])
+        fd = self.dev(fe2d_dot)
+        if fd is not None:
+            fd = fd.reshape(n_dir, nv, nv)
+        G, NA = int(self._cfg_struct.num_grad_points), int(self._cfg_struct.n_angles)
+        new = torch.zeros if point_range is not None else torch.empty
+        P = new((B, G, self.npts, NA), dtype=torch.float64, device=self.device) if want_P else None
+        Pd = new((n_dir, B, G, self.npts, NA), dtype=torch.float64, device=self.device)
+        lo, hi = point_range if point_range is not None else (0, -1)
+        self._sync_stream()
+        self._saved_2d = None
+        rc = self.lib.tsff_form_factor_2d_jvp(self.h, int(feature), self._ptr(phys_d), self._ptr(fe_d), nv, float(ud_angle), float(va_angle),
+                                              B, n_dir, self._ptr(pd), self._ptr(fd), int(lo), int(hi), self._ptr(P), self._ptr(Pd))
+        L.check(self.lib, self.h, rc)
+        return P, Pd
+
     def _same_input(self, a, ref, ref_dev) -> bool:
         """Is ``a`` what the saving forward was given?  A host array equal to the copy kept at the save, or a device tensor on
         the same memory (a device tensor rewritten in place between the two calls cannot be told apart: do not do that)."""

@@ -554,13 +554,22 @@ class LossFunction:
         if self.distributed:
             raise NotImplementedError(f"{what} is not built for distributed=True (one plasma condition: nothing to shard)")
         if int(getattr(weights, "fe_dim", 1)) == 2:
-            raise NotImplementedError(f"{what}: the forward mode through the rotate-and-project sampler of a 2-D f_e is not built")
+            sm = weights.slots
+            if getattr(sm, "fval2d_active", False):
+                raise NotImplementedError(f"{what}: a fitted Arbitrary2V.fval would be nvx^2 table directions; not built")
+            sph = getattr(weights, "sph", None)
+            if sph is not None and sph.flm_type == "nn":
+                raise NotImplementedError(f"{what}: the NN radial functions (flm_type: nn) are not built")
+            if int(self.cfg["parameters"]["electron"]["fe"]["nvx"]) > 256:
+                raise NotImplementedError(f"{what}: a 2-D f_e of more than 256 x 256 keeps no projection records; not built")
 
     def _angular_directions(self, weights: ThomsonParams):
-        """The fitted leaves of an angular deck as directions of the device calls: -> (names, phys_dot [n, NP], fe_dot [n, nvx] or
-        None, amp_dot [n, 2]) in ravel order -- the leaves ``_vg_angular_adjoint`` differentiates.  Scalars: the forward of the
-        host transform (scale * sigmoid'(x), a tied Ti copied); the DLM order: d f_e / dm by central differences with the adjoint
-        path's h = 1e-6; ``Arbitrary1V.fval``: one direction per value, the rows of the host generator's Jacobian."""
+        """The fitted leaves of an angular deck as directions of the device calls: -> (names, phys_dot [n, NP], fe_dot [n, nvx]
+        ([n, nvx, nvx] for a 2-D f_e) or None, amp_dot [n, 2]) in ravel order -- the leaves ``_vg_angular_adjoint`` differentiates.
+        Scalars: the forward of the host transform (scale * sigmoid'(x), a tied Ti copied); the DLM order: d f_e / dm by central
+        differences with the adjoint path's h = 1e-6; ``Arbitrary1V.fval``: one direction per value, the rows of the host
+        generator's Jacobian; the values of a 2-D generator (``SphericalHarmonics``: Mora-Yahi, free radial functions): one table
+        direction per value in ``get_params()`` order, named ("electron", "fe", j)."""
         from . import distribution as Dist
 
         sm = weights.slots
@@ -569,14 +578,19 @@ class LossFunction:
         dact = sm.scale * np.where(sm.sigmoid.astype(bool), sg * (1.0 - sg), 1.0)
         nvx = int(self.cfg["parameters"]["electron"]["fe"]["nvx"])
         names, pd, fd, ad = [], [], [], []
-        zero_p, zero_f = np.zeros(sm.NP), np.zeros(nvx)
+        two_d = int(getattr(weights, "fe_dim", 1)) == 2
+        zero_p, zero_f = np.zeros(sm.NP), np.zeros((nvx, nvx) if two_d else nvx)
         for name, s in tree.get_filter_spec(None, weights):
             if s == tree.FVAL_SLOT:
                 J = Dist.arbitrary_1v_jvp(weights.fval[0])
                 for j in range(J.shape[0]):
                     names.append((name[0], name[1], j)); pd.append(zero_p); fd.append(J[j]); ad.append((0.0, 0.0))
-            elif s in (tree.GEN2D_SLOT, tree.FVAL2D_SLOT):
-                raise NotImplementedError("angular_jacobian: 2-D distribution-function leaves are not built")
+            elif s == tree.GEN2D_SLOT:
+                J = weights.sph.jvp()
+                for j in range(J.shape[0]):
+                    names.append((name[0], name[1], j)); pd.append(zero_p); fd.append(J[j]); ad.append((0.0, 0.0))
+            elif s == tree.FVAL2D_SLOT:
+                raise NotImplementedError("angular_jacobian: a fitted Arbitrary2V.fval is not built")
             elif s == L.P_M:
                 m, hm = float(weights.physical_matrix()[0, L.P_M]), 1e-6
                 names.append(name); pd.append(zero_p); ad.append((0.0, 0.0))
@@ -591,7 +605,7 @@ class LossFunction:
                 names.append(name); pd.append(p); fd.append(zero_f)
                 ad.append((dact[s] if s == L.P_AMP1 else 0.0, dact[s] if s == L.P_AMP2 else 0.0))
         with_fe = any(f is not zero_f for f in fd)
-        return names, np.array(pd).reshape(-1, sm.NP), (np.array(fd).reshape(-1, nvx) if with_fe else None), np.array(ad).reshape(-1, 2)
+        return names, np.array(pd).reshape(-1, sm.NP), (np.array(fd).reshape((-1,) + zero_f.shape) if with_fe else None), np.array(ad).reshape(-1, 2)
 
     def _angular_jacobian_device(self, weights: ThomsonParams, batch: Dict, chunk: int):
         """-> (engine, names, J [n, rows, cols] device, ThryE [rows, cols] device (the model image, no noise), lamE)."""
@@ -603,7 +617,10 @@ class LossFunction:
         lam_step = self.ts_diag._ats_prepare(eng, batch)
         phys = weights.physical_matrix()
         p = phys[0]
-        fe1 = np.ascontiguousarray(np.asarray(weights()["electron"]["fe"], dtype=np.float64).reshape(1, -1))
+        two_d = int(getattr(weights, "fe_dim", 1)) == 2
+        fe1 = np.ascontiguousarray(np.asarray(weights()["electron"]["fe"], dtype=np.float64))
+        fe1 = fe1 if two_d else fe1.reshape(1, -1)
+        gen = self.cfg["parameters"]["general"]
         rows = eng._ats_shape[0]
         e_amps = np.array(np.broadcast_to(np.asarray(batch["e_amps"], dtype=np.float64).reshape(-1, 1), (rows, 1)))
         phys_d, fe_d, ea_d = eng.dev(phys), eng.dev(fe1), eng.dev(e_amps)
@@ -611,7 +628,11 @@ class LossFunction:
         chunk = max(int(chunk), 1)
         for k0 in range(0, len(names), chunk):   # (P_dot is npts x n_angles doubles per direction: a chunk at a time)
             k1 = min(k0 + chunk, len(names))
-            Pv, Pd = eng.form_factor_jvp(0, phys_d, fe_d, pd[k0:k1, None, :], None if fd is None else fd[k0:k1, None, :], want_P=P is None)
+            if two_d:   # the rotate-and-project sampler: the deck's drift and flow angles, one shared table
+                Pv, Pd = eng.form_factor_2d_jvp(0, phys_d, fe_d, pd[k0:k1, None, :], None if fd is None else fd[k0:k1],
+                                                gen["ud"]["angle"], gen["Va"]["angle"], want_P=P is None)
+            else:
+                Pv, Pd = eng.form_factor_jvp(0, phys_d, fe_d, pd[k0:k1, None, :], None if fd is None else fd[k0:k1, None, :], want_P=P is None)
             P = Pv if P is None else P
             Ev, Ed = eng.ats_jvp(P[0], Pd[:, 0], ea_d, p[L.P_LAM], p[L.P_AMP1], p[L.P_AMP2], ad[k0:k1], want_E=E is None)
             E = Ev if E is None else E
@@ -619,8 +640,9 @@ class LossFunction:
         return eng, names, (J[0] if len(J) == 1 else torch.cat(J)), E, self.ts_diag._ats_lam_axis(eng, lam_step)
 
     def angular_jacobian(self, weights: ThomsonParams, batch: Dict, chunk: int = 32):
-        """Jacobian of the ARTS image w.r.t. every fitted normalised leaf of an angular deck with a 1-D f_e (the scalar slots, the
-        DLM order, the ``Arbitrary1V.fval`` values) by forward mode on the device (Engine.form_factor_jvp, Engine.ats_jvp), the
+        """Jacobian of the ARTS image w.r.t. every fitted normalised leaf of an angular deck -- a 1-D f_e (the scalar slots, the
+        DLM order, the ``Arbitrary1V.fval`` values) or a 2-D f_e of at most 256 x 256 (the scalar slots on any table, the values of a
+        ``SphericalHarmonics`` generator) -- by forward mode on the device (Engine.form_factor_jvp / form_factor_2d_jvp, Engine.ats_jvp), the
         directions in chunks of ``chunk``: ``{"ele": J [n, rows, cols], "ThryE": [rows, cols] (the model image, no noise),
         "leaves": [...]}`` as NumPy arrays, the leaves in ravel order (an fval entry j is named ("electron", "fval", j))."""
         self._refuse_angular_postfit(weights, "angular_jacobian")
