@@ -61,7 +61,7 @@
 extern "C" {
 #endif
 
-#define TSFF_ABI_VERSION 18
+#define TSFF_ABI_VERSION 19
 /* error codes (every entry point returns 0 or one of these; text via tsff_last_error):
  * -1 bad argument, -2 unsupported configuration / option, -3 not a differentiable leaf, -5 HIP runtime error,
  * -22 stale or foreign token of saved projection records (tsff_form_factor_2d_grad),
@@ -552,6 +552,36 @@ int tsff_loss_hess(tsff_handle *h, const double *params, const double *fe, const
                    const double *e_amps, const double *i_amps, const double *noise_e, const double *noise_i, int32_t B,
                    const double *weights, const int32_t *active_slots, int32_t n_active, double *loss_terms,
                    double *grad, double *hess);
+
+/* Exact Hessian of the angular (ARTS) loss: LossFunction._loss_for_hess_fn_ / h_loss_wrt_params (inverse/loss_function.py:170-188,
+ * which process_angular_data -> recalculate_with_chosen_weights calls after an angular fit, postprocess.py:131-135) on an
+ * angular_full deck with a 1-D f_e: value, gradient and full second derivative of
+ *   loss = sum_j wcol[column of j] l(e_data_j, t_j),   t = ThryE + noise_e,
+ * w.r.t. the normalised leaves of the slots active_slots (HOST [n_active], ravel order; TSFF_P_M included on a DLM handle), in one
+ * stream-ordered call.  l is the functional of tsff_loss_hess with its denominators (|d| + 1e-10 for l2 and l1) for loss_method
+ * (TSFF_LOSS_*, whatever the handle's own); wcol (device [npts / lam_step]) carries the blue / red masks of the resolution-unit axis.
+ *   leaves (device [NP]): the normalised leaf row of the one plasma condition; fe (device [nvx]) as the handle's fe_mode says
+ *   (PER_LINEOUT: the table; SHARED / DLM: NULL, the DLM table is built from the leaves);
+ *   e_data, noise_e (device [rows][npts / lam_step]; noise_e may be NULL = 0), e_amps (device [rows]);
+ *   loss (device [1]), grad (device [n]), hess (device [n][n], symmetric, both triangles written),
+ *   gn (device [n][n]) = sum_j w_j l''(d_j, t_j) t_a t_c, the Gauss-Newton part of hess on its own;
+ *   optional outputs (device, NULL to skip): E [rows][nJ] the model image (bit for bit tsff_ats_spectrum of tsff_form_factor at the
+ *   physical parameters `phys`), E1 [n][rows][nJ] its first and E2 [n (n + 1) / 2][rows][nJ] its second derivatives, the pairs
+ *   (a <= c) row-major over the upper triangle; phys [NP] the physical parameters of the leaves.
+ * Second-order forward mode: k_ffhess evaluates the raw form factor in hyper-dual arithmetic, one task per pair of leaves that
+ * reach it (a pair with amp1, amp2 or amp3 has a vanishing second derivative of P and launches none), with tsff_loss_hess's table
+ * convention (the Z' and W lookups carry their slope and no curvature, the Hermite ln f_e lookup its true derivatives, the DLM
+ * table piecewise linear in m before its normalisation); the linear stages of the ARTS chain run on every derivative image and the
+ * two row normalisations take their second derivative at the arg-max of the value.  Every sum runs in a fixed order, no atomics:
+ * two calls give bit-identical output.  Nothing synchronises inside the call; its workspace is the handle's and grows only when a
+ * call needs more than the last one (refused with -2 inside graph capture, as tsff_reserve describes).
+ * Refusals, each with a tsff_last_error message and nothing enqueued: a null pointer, n_active < 1 or an unknown loss_method -1;
+ * a slot out of range or repeated -1, TSFF_P_M without fe_mode == TSFF_FE_DLM -2, an ion's A slot -3; fe missing on a PER_LINEOUT
+ * handle (among them the handles of 2-D f_e decks, which this call does not serve) -2; tsff_ats_setup not called -2; the tables
+ * of k_ffhess beyond the LDS of a workgroup (large nvx) -2. */
+int tsff_angular_loss_hess(tsff_handle *h, const double *leaves, const double *fe, const int32_t *active_slots, int32_t n_active,
+                           const double *e_data, const double *noise_e, const double *e_amps, const double *wcol, int32_t loss_method,
+                           double *loss, double *grad, double *hess, double *gn, double *E, double *E1, double *E2, double *phys);
 
 /* Jacobian of the model spectra w.r.t. the normalised leaves of the slots active_slots (HOST [n_active], ravel order), for every
  * lineout b:  jac_f[b][a][j] = d Thry_f[b][j] / d x[b][a], Thry_f what tsff_forward returns for the same arguments without the

@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtsff.so")
 LIB_PATH = os.environ.get("TSFF_LIBRARY", LIB_PATH)  # A/B experiments: another in-tree build of the same ABI
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 MAX_ION = 4
 NBINS = 1024
 NXI1 = 1024
@@ -173,6 +173,7 @@ _SIGNATURES = {
     "tsff_arb1v_table": (C.c_int, [_vp, C.c_int32, C.c_double, _vp, _vp, _vp]),
     "tsff_arb1v_table_vjp": (C.c_int, [_vp, C.c_int32, C.c_double, _vp, _vp, _vp, _vp]),
     "tsff_loss_hess": (C.c_int, [_vp] + [_vp] * 8 + [C.c_int32, c_double_p, C.POINTER(C.c_int32), C.c_int32, _vp, _vp, _vp]),
+    "tsff_angular_loss_hess": (C.c_int, [_vp, _vp, _vp, C.POINTER(C.c_int32), C.c_int32, _vp, _vp, _vp, _vp, C.c_int32] + [_vp] * 8),
     "tsff_spectrum_jacobian": (C.c_int, [_vp] + [_vp] * 4 + [C.c_int32, C.POINTER(C.c_int32), C.c_int32, _vp, _vp]),
     "tsff_loss_gauss_newton": (C.c_int, [_vp] + [_vp] * 8 + [C.c_int32, c_double_p, C.POINTER(C.c_int32), C.c_int32, _vp, _vp, _vp]),
     "tsff_lm_state_size": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),

@@ -233,6 +233,103 @@ __global__ __launch_bounds__(kThreads) void k_ats_resunit_jvp(const double* __re
   }
 }
 
+// ---- second-order forward mode of the two row normalisations (tsff_angular_loss_hess; the linear stages run the forward kernels on
+// the second-derivative image, as they do on a tangent image) ----
+// second derivative of k_ats_rownorm for a pair (a, c) of leaves: Y = B s, s = mM / mB, the maxima where k_ats_rowstats found them
+// (the first in index order, positions constant).  With rho_x = s_x / s = M_x[jM] / mM - B_x[jB] / mB and
+//   rho_ac = M_ac[jM] / mM - M_a[jM] M_c[jM] / mM^2 - B_ac[jB] / mB + B_a[jB] B_c[jB] / mB^2:
+//   Y_ac = B_ac s + B_a s rho_c + B_c s rho_a + B s (rho_a rho_c + rho_ac).
+// Ys: the SCALED image Y = B s (k_ats_rownorm has run); Ma, Mc, Mac: the weighted tangent images (before the convolutions);
+// Ba, Bc: the UNSCALED convolved tangent images; Bac: B_ac in, Y_ac out.
+__global__ __launch_bounds__(kThreads) void k_ats_rownorm_jvp2(const double* __restrict__ Ys, const double* __restrict__ stats,
+                                                               const double* __restrict__ Ma, const double* __restrict__ Mc,
+                                                               const double* __restrict__ Mac, const double* __restrict__ Ba,
+                                                               const double* __restrict__ Bc, int npts, double* __restrict__ Bac) {
+  const int r = blockIdx.x;
+  const double mM = stats[4 * r], mB = stats[4 * r + 2];
+  const int jM = (int)stats[4 * r + 1], jB = (int)stats[4 * r + 3];
+  const size_t o = (size_t)r * npts;
+  const double sc = mM / mB;
+  const double ma = Ma[o + jM] / mM, mc = Mc[o + jM] / mM, ba = Ba[o + jB] / mB, bc = Bc[o + jB] / mB;
+  const double rho_a = ma - ba, rho_c = mc - bc;
+  const double rho_ac = Mac[o + jM] / mM - ma * mc - Bac[o + jB] / mB + ba * bc;
+  __syncthreads();   // (B_ac[jB] is read by every thread before its owner overwrites it)
+  const double k = rho_a * rho_c + rho_ac;
+  for (int j = threadIdx.x; j < npts; j += kThreads)
+    Bac[o + j] = Bac[o + j] * sc + Ba[o + j] * (sc * rho_c) + Bc[o + j] * (sc * rho_a) + Ys[o + j] * k;
+}
+
+// second derivative of k_ats_resunit for a pair (a, c) of leaves: out = e_amps u amp, u = D / mx with D the block means and
+// mx = D[js] its row maximum (the first in index order), amp = amp1 | amp2 by the wavelength:
+//   u_x  = (D_x - u mx_x) / mx,   u_ac = (D_ac - u_a mx_c - u_c mx_a - u mx_ac) / mx,
+//   out_ac = e_amps (u_ac amp + u_a amp_c + u_c amp_a + u amp_ac).
+// lam, amp1 and amp2 are read from the physical parameters `phys` the value image was formed with (k_ats_resunit's); the amplitudes'
+// derivatives w.r.t. the NORMALISED leaves of the slots sa and sc come from the activation of the leaves on the device: amp_x is
+// non-zero only when x is that amplitude's own leaf, amp_ac only for a = c = that leaf, through the sigmoid's second derivative.
+// `lam` only selects the amplitude.
+// Y: the scaled value image; Ya, Yc, Yac: the scaled derivative images, each NULL when identically zero (a leaf that does not reach
+// the form factor).  out_a (optional): the first derivative w.r.t. leaf a, written with the diagonal pair.  One workgroup per
+// output row; at most TSFF_NBINS resolution units per row.
+__global__ __launch_bounds__(kThreads) void k_ats_resunit_jvp2(KStatic S, const double* __restrict__ leaves,
+                                                               const double* __restrict__ phys, int sa, int sc,
+                                                               const double* __restrict__ Y, const double* __restrict__ Ya,
+                                                               const double* __restrict__ Yc, const double* __restrict__ Yac,
+                                                               const double* __restrict__ lam_nm, int npts, int lam_step, int ang_step,
+                                                               int row_start, const double* __restrict__ e_amps,
+                                                               double* __restrict__ out_a, double* __restrict__ out_ac) {
+  __shared__ double red[8];
+  __shared__ double Dl[TSFF_NBINS], Da[TSFF_NBINS], Dc[TSFF_NBINS], Dac[TSFF_NBINS];
+  const int R = blockIdx.x, nJ = npts / lam_step;
+  const int r0 = (row_start + R) * ang_step;
+  const double cnt = (double)(ang_step * lam_step);
+  double mx = -1e300;
+  int js = 0;
+  for (int J = threadIdx.x; J < nJ; J += kThreads) {
+    double acc = 0.0, acca = 0.0, accc = 0.0, accac = 0.0;
+    for (int dr = 0; dr < ang_step; ++dr)
+      for (int dj = 0; dj < lam_step; ++dj) {
+        const size_t i = (size_t)(r0 + dr) * npts + J * lam_step + dj;
+        acc += Y[i];
+        if (Ya) acca += Ya[i];
+        if (Yc) accc += Yc[i];
+        if (Yac) accac += Yac[i];
+      }
+    acc /= cnt; acca /= cnt; accc /= cnt; accac /= cnt;   // (the value as k_ats_resunit forms it: the same arg-max)
+    Dl[J] = acc; Da[J] = acca; Dc[J] = accc; Dac[J] = accac;
+    if (acc > mx) { mx = acc; js = J; }
+  }
+  block_argmax(mx, js, red);   // (its barriers publish the four block-mean rows)
+  // lam and the two amplitudes: the values k_ats_resunit read (phys, staged once per call), the amplitudes' first and second
+  // derivatives w.r.t. their own normalised leaf from the activation (scale x sigmoid', scale x sigmoid'')
+  auto act_d = [&](int s, double& d1, double& d2) {
+    if (S.p_sig[s]) {
+      const double sg = sigmoid(leaves[s]), d = sg * (1.0 - sg);
+      d1 = d * S.p_scale[s]; d2 = d * (1.0 - 2.0 * sg) * S.p_scale[s];
+    } else {
+      d1 = S.p_scale[s]; d2 = 0.0;
+    }
+  };
+  const double lam = phys[TSFF_P_LAM], amp1 = phys[TSFF_P_AMP1], amp2 = phys[TSFF_P_AMP2];
+  double a1d, a1dd, a2d, a2dd;
+  act_d(TSFF_P_AMP1, a1d, a1dd);
+  act_d(TSFF_P_AMP2, a2d, a2dd);
+  const double mxa = Da[js], mxc = Dc[js], mxac = Dac[js], ea = e_amps[R];
+  for (int J = threadIdx.x; J < nJ; J += kThreads) {
+    double lb = 0.0;
+    for (int dj = 0; dj < lam_step; ++dj) lb += lam_nm[J * lam_step + dj];
+    lb /= (double)lam_step;
+    const bool blue = lb < lam;
+    const int own = blue ? TSFF_P_AMP1 : TSFF_P_AMP2;
+    const double amp = blue ? amp1 : amp2, ad = blue ? a1d : a2d, add = blue ? a1dd : a2dd;
+    const double amp_a = sa == own ? ad : 0.0, amp_c = sc == own ? ad : 0.0, amp_ac = (sa == own && sc == own) ? add : 0.0;
+    const double u = Dl[J] / mx;
+    const double ua = (Da[J] - u * mxa) / mx, uc = (Dc[J] - u * mxc) / mx;
+    const double uac = (Dac[J] - ua * mxc - uc * mxa - u * mxac) / mx;
+    out_ac[(size_t)R * nJ + J] = ea * (uac * amp + ua * amp_c + uc * amp_a + u * amp_ac);
+    if (out_a) out_a[(size_t)R * nJ + J] = ea * (ua * amp + u * amp_a);
+  }
+}
+
 // reverse of k_ats_conv: Xbar[i] (+)= sum_s taps[s] Ybar[i - off - s]
 __global__ void k_ats_conv_adj(const double* __restrict__ Yb, const double* __restrict__ taps, int nt, int off, int along_rows,
                                int npx, int npts, int accumulate, double* __restrict__ Xb) {

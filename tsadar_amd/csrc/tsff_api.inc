@@ -132,6 +132,7 @@ struct tsff_handle {
   tsff::DevBuf ff2j_tab, ff2j_pad, ff2j_P, ff2j_flags;   // tsff_form_factor_2d_jvp: the projections of a group's tangent tables, the padded tangent
                                           // table (L1/L2 path), the value when the caller asks for none, which directions have a table tangent
   tsff::DevBuf ats_E;              // tsff_ats_jvp: the third tangent image (ats_C, ats_D and this one hold M', A', B')
+  tsff::DevBuf ahess_ws;           // tsff_angular_loss_hess: the physical parameters, P and its derivative images, the per-leaf ARTS images, E / E1 / E2
   tsff::DevBuf lm_ws;              // tsff_lm_fit: the gradient [B][n_active] and Gauss-Newton matrix [B][n_active][n_active] of an evaluation
   size_t smem_adjoint = 0;
   tsff::DevBuf ats_w, ats_ta, ats_tl, ats_lam, ats_M, ats_A, ats_B, ats_C, ats_D, ats_stats;
@@ -394,6 +395,8 @@ static auto form_factor_adj_kernel(int n_ion, bool grad_fe) {
 }
 // the forward mode of the 1-D form factor: groups of three directions
 static auto ffjvp_kernel(int n_ion) { return with_ion<TSFF_MAX_ION>(n_ion, [](auto N) { return &k_ffjvp<N.value, 3>; }); }
+// its second-order forward mode (tsff_angular_loss_hess)
+static auto ffhess_kernel(int n_ion) { return with_ion<TSFF_MAX_ION>(n_ion, [](auto N) { return &k_ffhess<N.value>; }); }
 static auto form_factor_2d_kernel(int n_ion, bool lds, bool save) {
   return with_ion<TSFF_MAX_ION>(n_ion, [&](auto N) {
     return with_bools(lds, save, [&](auto LDS, auto SAVE) { return &k_form_factor_2d<N.value, LDS.value, LDS.value ? TSFF_2D_GROUPS_LDS : TSFF_2D_GROUPS_L2, SAVE.value>; });
@@ -444,6 +447,7 @@ static hipError_t raise_lds_limits(int n_ion) {
   raise(jac_kernel(n_ion, 3, false));
   raise(jac_kernel(n_ion, 3, true));
   raise(ffjvp_kernel(n_ion));
+  raise(ffhess_kernel(n_ion));
   for (int a = 0; a < 2; ++a) raise(ff2d_project_kernel(n_ion, a));
   raise(&k_fe_direction);
   raise(&k_fe_adjoint);
@@ -2542,6 +2546,178 @@ int tsff_loss_hess(tsff_handle* h, const double* params, const double* fe, const
                (double*)nullptr);
   TSFF_HIP(h, hipGetLastError());
   return 0;
+}
+
+// ---- exact Hessian of the angular (ARTS) loss: second-order forward mode of the form factor (k_ffhess.inc: one workgroup column
+// per pair of leaves that reach the form factor), the ARTS chain at second order (the linear stages on every derivative image, the
+// two row normalisations by k_ats_rownorm_jvp2 / k_ats_resunit_jvp2), k_ats_hess_reduce.  The value image is the shipped forward's
+// (k_form_factor on the physical parameters k_ang_leaves stages: tsff_form_factor's bits); the first-order images come from the
+// diagonal pairs of the same k_ffhess launch.  prepare: every refusal and every buffer; enqueue: launches only.
+// workgroups per CU the grid of k_ffhess aims at: angle chunks = min(n_angles, kFfhessWGPerCU x CUs / pairs).
+// The 4 is angle_chunks' figure, taken over; it has not been tuned for this kernel.
+constexpr int kFfhessWGPerCU = 4;
+struct AngHessCall {
+  const double *leaves, *fe, *e_data, *noise_e, *e_amps, *wcol;
+  int method = 0, n = 0;
+  double *loss, *grad, *hess, *gn, *E, *E1, *E2, *phys_out;
+};
+struct AngHessPlan {
+  int n = 0, npair = 0;
+  int slot[kNP_MAX];       // the active slots, ravel order
+  int ff[kNP_MAX];         // per active leaf: its index among the leaves that reach the form factor, or -1 (an amplitude)
+  FfhessArgs A{};
+  size_t smem = 0;
+  dim3 grid;
+  // the workspace (doubles into ahess_ws)
+  size_t o_phys = 0, o_P = 0, o_P1 = 0, o_P2 = 0, o_Md = 0, o_Bd = 0, o_Yd = 0, o_E = 0, o_E1 = 0, o_E2 = 0;
+};
+
+static int ang_hess_prepare(tsff_handle* h, const AngHessCall& c, const int32_t* active_slots, AngHessPlan& p) {
+  uint8_t gm[kNP_MAX];
+  if (int rc = check_slots(h, active_slots, c.n, gm, h->fe_mode == TSFF_FE_DLM)) return rc;
+  if (int rc = check_fe(h, c.fe)) return rc;
+  if (int rc = ats_jvp_prepare(h)) return rc;   // (tsff_ats_setup has run; the row statistics and the three images of a derivative)
+  p.n = c.n; p.npair = c.n * (c.n + 1) / 2;
+  FfhessArgs& A = p.A;
+  A.nf = 0;
+  for (int k = 0; k < c.n; ++k) {
+    const int s = active_slots[k];
+    p.slot[k] = s;
+    const bool amp = s == TSFF_P_AMP1 || s == TSFF_P_AMP2 || s == TSFF_P_AMP3;   // (the amplitudes never reach the form factor)
+    p.ff[k] = amp ? -1 : A.nf;
+    if (!amp) A.slot[A.nf++] = s;
+  }
+  A.npair = A.nf * (A.nf + 1) / 2;
+  A.with_m = gm[TSFF_P_M];
+  p.smem = sizeof(double) * ffhess_smem_doubles(h->S, A.with_m != 0);
+  if (p.smem > kLdsLimit)
+    return fail(h, -2, "tsff_angular_loss_hess: LDS budget exceeded (%zu B with nvx = %d, %d angles%s): reduce nvx", p.smem, h->S.nvx,
+                h->S.n_angles, A.with_m ? " and the DLM order as a leaf" : "");
+  const int want = kFfhessWGPerCU * h->ncu2d();
+  p.grid = dim3(std::max(A.npair, 1), (unsigned)std::max(1, std::min(h->S.n_angles, want / std::max(A.npair, 1))));
+  if (int rc = ensure_workspace(h, 1)) return rc;
+  if (A.with_m) {
+    const size_t nvx = h->S.nvx;
+    TSFF_ENSURE(h, h->htmm, nvx * sizeof(double2));
+    TSFF_ENSURE(h, h->Xmm, (size_t)4 * kNXi1 * sizeof(double));
+    TSFF_ENSURE(h, h->cstmm, (size_t)2 * sizeof(double));
+    TSFF_ENSURE(h, h->Wmm, (size_t)kNXi2 * sizeof(double));
+    TSFF_ENSURE(h, h->Wmm_unused, (size_t)kNXi2 * sizeof(double));
+  }
+  const size_t pimg = (size_t)h->S.G * h->S.npts * h->S.n_angles, aimg = (size_t)h->ats_npx * h->S.npts;
+  const size_t rimg = (size_t)(h->ats_row_end - h->ats_row_start) * (h->S.npts / h->ats_lam_step);
+  size_t o = 0;
+  auto carve = [&](size_t nd) { const size_t at = o; o += (nd + 1) & ~(size_t)1; return at; };
+  p.o_phys = carve(kNP_MAX + 1);
+  p.o_P = carve(pimg); p.o_P1 = carve(A.nf * pimg); p.o_P2 = carve(A.npair * pimg);
+  p.o_Md = carve(A.nf * aimg); p.o_Bd = carve(A.nf * aimg); p.o_Yd = carve(A.nf * aimg);
+  p.o_E = carve(c.E ? 0 : rimg); p.o_E1 = carve(c.E1 ? 0 : c.n * rimg); p.o_E2 = carve(c.E2 ? 0 : p.npair * rimg);
+  TSFF_ENSURE(h, h->ahess_ws, std::max<size_t>(o, 2) * sizeof(double));
+  return 0;
+}
+
+static int ang_hess_enqueue(tsff_handle* h, const AngHessCall& c, AngHessPlan& p) {
+  const int npts = h->S.npts, npx = h->ats_npx, rows = h->ats_row_end - h->ats_row_start, nJ = npts / h->ats_lam_step;
+  const size_t pimg = (size_t)h->S.G * npts * h->S.n_angles, aimg = (size_t)npx * npts, rimg = (size_t)rows * nJ;
+  double* ws = h->ahess_ws.as<double>();
+  double* phys = c.phys_out ? c.phys_out : ws + p.o_phys;
+  double *P = ws + p.o_P, *P1 = ws + p.o_P1, *P2 = ws + p.o_P2, *Md = ws + p.o_Md, *Bd = ws + p.o_Bd, *Yd = ws + p.o_Yd;
+  double* E = c.E ? c.E : ws + p.o_E;
+  double* E1 = c.E1 ? c.E1 : ws + p.o_E1;
+  double* E2 = c.E2 ? c.E2 : ws + p.o_E2;
+  FfhessArgs& A = p.A;
+  if (int rc = timing_begin(h)) return rc;
+  KCall K{};
+  K.params = c.leaves; K.B = 1;
+  if (int rc = prepare_tables(h, c.leaves, c.fe, 1, K)) return rc;
+  if (A.with_m) {   // second m-derivative tables, as tsff_loss_hess builds them: k_hess_mtab, then the shipped W-table GEMM on its rows
+    const size_t nvx = h->S.nvx;
+    const size_t smem_t = sizeof(double2) * 6 * nvx + sizeof(double) * (nvx + 2 * kNXi1 + 8);
+    TSFF_LAUNCH_ION(h, TSFF_MAX_ION, k_hess_mtab, dim3(1), dim3(kThreads), smem_t, h->stream, h->S, c.leaves, K.ht, K.htm, h->htmm.as<double2>(),
+                    h->Xmm.as<double>(), h->cstmm.as<double>());
+    TSFF_HIP(h, hipGetLastError());
+    const int nM = (1 + kGM / 4 - 1) / (kGM / 4);
+    dim3 wgrid(8 * ((nM + 7) / 8) * ((kNXi2 + kGNw - 1) / kGNw));
+    TSFF_LAUNCH0(h, k_wgemm_w, wgrid, dim3(kThreads), kWgemmWSmem, h->stream, h->S.lg, h->Xmm.as<double>(), h->cstmm.as<double>(),
+                 h->S.xi2, 1, h->Wmm.as<double>(), h->Wmm_unused.as<double>(), h->kw_lo, h->kw_hi);
+    TSFF_HIP(h, hipGetLastError());
+    A.htmm = h->htmm.as<double2>();
+    A.Wmm = h->Wmm.as<double>();
+  }
+  // the physical parameters (k_ang_leaves with a generator it has no table for: the parameters only) and the value image
+  TSFF_LAUNCH_ION(h, TSFF_MAX_ION, k_ang_leaves, dim3(1), dim3(kThreads), 0, h->stream, h->S, c.leaves, (int)TSFF_ANG_ARB1V, 0, 0,
+                  (const double*)nullptr, 0.0, 0.0, 0, phys, (double*)nullptr, (double*)nullptr, (double*)nullptr);
+  KCall Kp = K;
+  Kp.params = phys;
+  TSFF_LAUNCH_FN(h, form_factor_kernel(h->n_ion), ("k_form_factor", h->n_ion), dim3(1, angle_chunks(h, 1)), dim3(kThreads), h->smem_spectrum,
+                 h->stream, h->S, Kp, 0, h->S.omgs[0], npts, P);
+  TSFF_HIP(h, hipGetLastError());
+  if (A.nf > 0) {
+    A.P1 = P1; A.P2 = P2;
+    TSFF_LAUNCH_FN(h, ffhess_kernel(h->n_ion), ("k_ffhess", h->n_ion), p.grid, dim3(kThreads), p.smem, h->stream, h->S, K, A, 0, h->S.omgs[0], npts);
+    TSFF_HIP(h, hipGetLastError());
+  }
+  // ---- the ARTS chain: value, first order per leaf that reaches the form factor, second order per pair ----
+  dim3 block(kThreads), grid((npts + kThreads - 1) / kThreads, npx);
+  double* Bm = h->ats_B.as<double>();
+  double* Mt = h->ats_C.as<double>();
+  double* At = h->ats_D.as<double>();
+  double* Bt = h->ats_E.as<double>();
+  double* stats = h->ats_stats.as<double>();
+  const double *wts = h->ats_w.as<double>(), *ta = h->ats_ta.as<double>(), *tl = h->ats_tl.as<double>(), *lam_nm = h->ats_lam.as<double>();
+  ats_forward_chain(h, P);
+  TSFF_LAUNCH0(h, k_ats_rowstats, dim3(npx), block, 0, h->stream, h->ats_M.as<double>(), Bm, npts, stats);
+  TSFF_LAUNCH0(h, k_ats_rownorm, dim3(npx), block, 0, h->stream, h->ats_M.as<double>(), Bm, npts);
+  TSFF_LAUNCH0(h, k_ats_resunit, dim3(rows), block, 0, h->stream, Bm, lam_nm, npts, h->ats_lam_step, h->ats_ang_step, h->ats_row_start,
+               c.e_amps, 0.0, 0.0, 0.0, (const double*)phys, E);
+  TSFF_HIP(h, hipGetLastError());
+  for (int i = 0; i < A.nf; ++i) {
+    double *Mi = Md + i * aimg, *Bi = Bd + i * aimg, *Yi = Yd + i * aimg;
+    TSFF_LAUNCH0(h, k_ats_weights, grid, block, 0, h->stream, P1 + i * pimg, wts, h->S.filt, h->S.G, npts, h->S.n_angles, npx, Mi);
+    TSFF_LAUNCH0(h, k_ats_conv, grid, block, 0, h->stream, Mi, ta, h->ats_nta, h->ats_offa, 1, npx, npts, At);
+    TSFF_LAUNCH0(h, k_ats_conv, grid, block, 0, h->stream, At, tl, h->ats_ntl, h->ats_offl, 0, npx, npts, Bi);
+    TSFF_HIP(h, hipMemcpyAsync(Yi, Bi, aimg * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    TSFF_LAUNCH0(h, k_ats_rownorm_jvp, dim3(npx), block, 0, h->stream, Bm, stats, Mi, npts, Yi);
+    TSFF_HIP(h, hipGetLastError());
+  }
+  int pr = 0;
+  for (int a = 0; a < p.n; ++a)
+    for (int cc = a; cc < p.n; ++cc, ++pr) {
+      const int fa = p.ff[a], fc = p.ff[cc];
+      const double* Yac = nullptr;
+      if (fa >= 0 && fc >= 0) {   // (a pair with an amplitude has P2 = 0: no form-factor task, no image)
+        const int q = fa * A.nf - fa * (fa - 1) / 2 + (fc - fa);
+        TSFF_LAUNCH0(h, k_ats_weights, grid, block, 0, h->stream, P2 + q * pimg, wts, h->S.filt, h->S.G, npts, h->S.n_angles, npx, Mt);
+        TSFF_LAUNCH0(h, k_ats_conv, grid, block, 0, h->stream, Mt, ta, h->ats_nta, h->ats_offa, 1, npx, npts, At);
+        TSFF_LAUNCH0(h, k_ats_conv, grid, block, 0, h->stream, At, tl, h->ats_ntl, h->ats_offl, 0, npx, npts, Bt);
+        TSFF_LAUNCH0(h, k_ats_rownorm_jvp2, dim3(npx), block, 0, h->stream, Bm, stats, Md + fa * aimg, Md + fc * aimg, Mt, Bd + fa * aimg,
+                     Bd + fc * aimg, npts, Bt);
+        Yac = Bt;
+      }
+      TSFF_LAUNCH0(h, k_ats_resunit_jvp2, dim3(rows), block, 0, h->stream, h->S, c.leaves, (const double*)phys, p.slot[a], p.slot[cc], Bm,
+                   fa >= 0 ? Yd + fa * aimg : (const double*)nullptr, fc >= 0 ? Yd + fc * aimg : (const double*)nullptr, Yac, lam_nm, npts,
+                   h->ats_lam_step, h->ats_ang_step, h->ats_row_start, c.e_amps, a == cc ? E1 + a * rimg : (double*)nullptr, E2 + pr * rimg);
+      TSFF_HIP(h, hipGetLastError());
+    }
+  TSFF_LAUNCH0(h, k_ats_hess_reduce, dim3(p.npair), block, 0, h->stream, E, E1, E2, c.noise_e, c.e_data, c.wcol, rows, nJ, c.method, p.n,
+               c.loss, c.grad, c.hess, c.gn);
+  TSFF_HIP(h, hipGetLastError());
+  return timing_end(h);
+}
+
+int tsff_angular_loss_hess(tsff_handle* h, const double* leaves, const double* fe, const int32_t* active_slots, int32_t n_active,
+                           const double* e_data, const double* noise_e, const double* e_amps, const double* wcol, int32_t loss_method,
+                           double* loss, double* grad, double* hess, double* gn, double* E, double* E1, double* E2, double* phys) {
+  DevGuard dg__(h);
+  if (!h) return -1;
+  if (!leaves || !active_slots || !e_data || !e_amps || !wcol || !loss || !grad || !hess || !gn) return fail(h, -1, "bad argument");
+  if (n_active < 1 || n_active > h->S.NP) return fail(h, -1, "bad argument: n_active = %d", (int)n_active);
+  if (loss_method < TSFF_LOSS_L2 || loss_method > TSFF_LOSS_POISSON) return fail(h, -1, "bad argument: loss_method = %d", (int)loss_method);
+  if (!h->S.load[0]) return fail(h, -2, "tsff_angular_loss_hess needs the electron feature (load_ele)");
+  AngHessCall c{leaves, fe, e_data, noise_e, e_amps, wcol, (int)loss_method, (int)n_active, loss, grad, hess, gn, E, E1, E2, phys};
+  AngHessPlan p;
+  if (int rc = ang_hess_prepare(h, c, active_slots, p)) return rc;
+  return ang_hess_enqueue(h, c, p);
 }
 
 // Jacobian of the spectra and Gauss-Newton curvature (k_jacobian.inc): the deck's table kernels, then k_jac_sweep on persistent

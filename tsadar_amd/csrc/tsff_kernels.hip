@@ -120,6 +120,7 @@ constexpr int kFusedMaxIon = 2;  // k_spectrum_fused is instantiated for n_ion <
 #include "k_hessian.inc"
 #include "k_jacobian.inc"
 #include "k_ffjvp.inc"
+#include "k_ffhess.inc"
 #include "k_ff2d_jvp.inc"
 #include "k_adam.inc"
 #include "k_lbfgs.inc"

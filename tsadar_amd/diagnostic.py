@@ -41,6 +41,15 @@ class ThomsonScatteringDiagnostic:
                                              fe_mode=L.FE_PER_LINEOUT if angular else None)
         return self._engines[activate]
 
+    def dlm_engine(self, activate: bool) -> Engine:
+        """The engine of an angular DLM deck whose tables the library builds from the leaves (fe_mode DLM): the exact Hessian with
+        the DLM order m among the leaves needs the m-derivatives of the tables (LossFunction.angular_h_loss_wrt_params)."""
+        key = (activate, "dlm")
+        if key not in self._engines:
+            self._engines[key] = Engine(self.cfg, self.scattering_angles, activate=activate, irf_cutoff_sigmas=self.irf_cutoff_sigmas,
+                                        fe_mode=L.FE_DLM)
+        return self._engines[key]
+
     def __call__(self, ts_params: ThomsonParams, batch: Dict):
         """-> (ThryE, ThryI, lamAxisE, lamAxisI), each [B, 1024] float64 NumPy
         (thomson_diagnostic.py:109-142).  A feature that is not loaded comes back as zeros."""

@@ -683,6 +683,42 @@ class Engine:
         L.check(self.lib, self.h, rc)
         return terms, grad, hess
 
+    def angular_loss_hess(self, leaves, active_slots, e_data, noise_e, e_amps, wcol, method, fe=None, want_images=False):
+        """Exact Hessian of ``_loss_for_hess_fn_`` on an angular (ARTS) deck with a 1-D f_e (tsff_angular_loss_hess; ``ats_setup`` has
+        run): ``leaves`` [NP] the normalised row of the one plasma condition, ``active_slots`` in ravel order (the DLM order among
+        them on an FE_DLM engine), ``e_data`` / ``noise_e`` [rows, n_lam] (noise_e None: zero), ``e_amps`` [rows], ``wcol`` [n_lam] the
+        weight of every column, ``method`` the loss functional's name, ``fe`` [nvx] on an FE_PER_LINEOUT engine.  -> a dict of CUDA
+        tensors: ``loss`` [1], ``grad`` [n], ``hess`` [n, n] (symmetric), ``gn`` [n, n] (its Gauss-Newton part); with ``want_images``
+        also ``E`` [rows, n_lam], ``E1`` [n, rows, n_lam], ``E2`` [n (n + 1) / 2, rows, n_lam] (pairs a <= c, row-major over the upper
+        triangle) and ``phys`` [NP].  Nothing is synchronised."""
+        torch = self.torch
+        rows, nJ = self._ats_shape
+        x = self.dev(leaves).reshape(-1)
+        assert x.numel() == self.NP, f"expected {self.NP} leaves, got {x.numel()}"
+        act = np.ascontiguousarray(active_slots, dtype=np.int32)
+        n = int(act.size)
+        d = self.dev(e_data).reshape(rows, nJ)
+        nz = None if noise_e is None else self.dev(noise_e)
+        if nz is not None and nz.numel() != rows * nJ:
+            nz = nz.expand(rows, nJ).contiguous()
+        ea = self.dev(np.broadcast_to(np.asarray(e_amps, dtype=np.float64).reshape(-1), (rows,)).copy()
+                      if not torch.is_tensor(e_amps) else e_amps.reshape(-1))
+        assert ea.numel() == rows
+        wc = self.dev(wcol).reshape(-1)
+        assert wc.numel() == nJ
+        fe_d = self.dev(fe)
+        new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=self.device)
+        out = dict(loss=new(1), grad=new(n), hess=new(n, n), gn=new(n, n))
+        if want_images:
+            out.update(E=new(rows, nJ), E1=new(n, rows, nJ), E2=new(n * (n + 1) // 2, rows, nJ), phys=new(self.NP))
+        p = self._ptr
+        self._sync_stream()
+        rc = self.lib.tsff_angular_loss_hess(self.h, p(x), p(fe_d), act.ctypes.data_as(C.POINTER(C.c_int32)), n, p(d), p(nz), p(ea), p(wc),
+                                             int(L.LOSS_METHODS[method]), p(out["loss"]), p(out["grad"]), p(out["hess"]), p(out["gn"]),
+                                             p(out.get("E")), p(out.get("E1")), p(out.get("E2")), p(out.get("phys")))
+        L.check(self.lib, self.h, rc)
+        return out
+
     def spectrum_jacobian(self, params, e_amps, i_amps, active_slots, fe=None):
         """Jacobian of the model spectra (``forward`` without the noise) w.r.t. the normalised leaves of ``active_slots`` (ravel
         order): -> (JE, JI), CUDA tensors [B, P, 1024]; a feature that is not loaded returns ``None``.  Nothing is synchronised

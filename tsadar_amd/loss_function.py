@@ -186,6 +186,17 @@ class LossFunction:
             wcol *= 0.5
         return wcol
 
+    def _angular_sum_wcol(self, lamE) -> np.ndarray:
+        """The column weights of ``_loss_for_hess_fn_`` on the ARTS image (sum reduce): the blue / red masks on the resolution-unit axis,
+        halved when both are fitted -- ``_angular_wcol`` without the division by rows x mask count."""
+        ext, r = self.cfg["other"]["extraoptions"], self.cfg["data"]["fit_rng"]
+        c = 0.5 if (ext["fit_EPWb"] and ext["fit_EPWr"]) else 1.0
+        wcol = np.zeros(np.size(lamE))
+        for on, lo, hi in ((ext["fit_EPWb"], r["blue_min"], r["blue_max"]), (ext["fit_EPWr"], r["red_min"], r["red_max"])):
+            if on:
+                wcol += c * ((lamE > lo) & (lamE < hi))
+        return wcol
+
     def _angular_value_device(self, eng, ts_params: ThomsonParams, batch, want_E: bool):
         """_angular_value(want_bar=True) with the image, the data, the masks and the loss seed on the device (a handful of
         element-wise torch operations on [rows, n_lam]; one scalar comes back): -> (value, ThryE or None, Ebar device)."""
@@ -451,7 +462,7 @@ class LossFunction:
         if method == "exact":
             if getattr(self, "angular", False):
                 raise NotImplementedError("h_loss_wrt_params(method='exact') is not built for angular_full decks "
-                                          "(their Gauss-Newton curvature and sigmas: angular_gn_loss_wrt_params)")
+                                          "(their exact Hessian: angular_h_loss_wrt_params; Gauss-Newton curvature: angular_gn_loss_wrt_params)")
             if getattr(weights, "fval", None) is not None and (weights.slots.fval_active or weights.slots.fval2d_active):
                 raise NotImplementedError("h_loss_wrt_params(method='exact'): the Hessian over the free-form f_e values "
                                           "(nvx table leaves) is not built")
@@ -663,12 +674,7 @@ class LossFunction:
                                       "Gauss-Newton matrix is zero (use l2, log-cosh or poisson)")
         eng, names, J, E, lamE = self._angular_jacobian_device(weights, batch, chunk)
         torch = eng.torch
-        ext, r = self.cfg["other"]["extraoptions"], self.cfg["data"]["fit_rng"]
-        c = 0.5 if (ext["fit_EPWb"] and ext["fit_EPWr"]) else 1.0
-        wcol = np.zeros(lamE.size)
-        for on, lo, hi in ((ext["fit_EPWb"], r["blue_min"], r["blue_max"]), (ext["fit_EPWr"], r["red_min"], r["red_max"])):
-            if on:
-                wcol += c * ((lamE > lo) & (lamE < hi))
+        wcol = self._angular_sum_wcol(lamE)
         w = eng.dev(wcol)[None, :]
         d = eng.dev(np.ascontiguousarray(batch["e_data"], dtype=np.float64))
         t = E + eng.dev(np.array(np.atleast_1d(np.asarray(batch["noise_e"], dtype=np.float64))))
@@ -695,4 +701,62 @@ class LossFunction:
                 for b_, (sp2, k2) in enumerate(names):
                     hess.setdefault(sp1, {}).setdefault(k1, {}).setdefault(sp2, {})[k2] = out["H"][a:a + 1, b_:b_ + 1].copy()
             out["hess"] = hess
+        return out
+
+    def _refuse_angular_hessian(self, weights: ThomsonParams, what: str):
+        """What the exact angular Hessian is not built for, refused before any device work."""
+        if not getattr(self, "angular", False):
+            raise NotImplementedError(f"{what} is for angular_full decks (1-D decks: h_loss_wrt_params(method='exact'))")
+        if getattr(self, "multiplex_ang", False):
+            raise NotImplementedError(f"{what} is not built for multiplexed angular decks")
+        if self.distributed:
+            raise NotImplementedError(f"{what} is not built for distributed=True (one plasma condition: nothing to shard)")
+        if int(getattr(weights, "fe_dim", 1)) == 2:
+            raise NotImplementedError(f"{what}: a 2-D f_e at second order is not built (its Gauss-Newton curvature: "
+                                      "angular_gn_loss_wrt_params)")
+        sm = weights.slots
+        if getattr(weights, "fval", None) is not None and (sm.fval_active or getattr(sm, "fval2d_active", False)):
+            raise NotImplementedError(f"{what}: a fitted Arbitrary1V.fval would be nvx (nvx + 1) / 2 pairs of table directions; not built")
+
+    def angular_h_loss_wrt_params(self, weights: ThomsonParams, batch: Dict):
+        """Exact Hessian of the reference's Hessian loss (``_loss_for_hess_fn_``, loss_function.py:170-188: denominators
+        |e_data| + 1e-10 for l2 and l1, sum reduce, the blue and red masks on the resolution-unit axis, halved when both are fitted)
+        on the ARTS image t = ThryE + noise_e of an angular deck with a 1-D f_e, w.r.t. every fitted normalised scalar leaf and the
+        DLM order m -- what ``h_loss_wrt_params`` is to the reference's ``recalculate_with_chosen_weights`` after an angular fit
+        (postprocess.py:131-135) -- in one device call (Engine.angular_loss_hess, tsff_angular_loss_hess: second-order forward mode):
+        H = sum_j w_j (l''(d_j, t_j) t_a t_c + l'(d_j, t_j) t_ac).  -> ``{"H", "grad", "loss", "gn", "leaves", "sigmas", "hess"}``, the
+        layout of ``angular_gn_loss_wrt_params``: ``gn`` is the Gauss-Newton part sum_j w_j l'' t_a t_c of H on its own, sigmas =
+        sign(diag H^-1) sqrt|diag H^-1| (postprocess.get_sigmas: a negative sigma marks a direction in which the fit is no minimum,
+        which the positive semi-definite Gauss-Newton matrix can never show), ``hess`` the nested layout ``hess[sp][k][sp2][k2]`` with
+        1 x 1 blocks that get_sigmas(hess, 1) reads.  All four loss methods (l1: H = sum_j w_j l' t_ac, its Gauss-Newton part is zero).
+        Not built: a 2-D f_e, a fitted ``Arbitrary1V.fval``, multiplexed decks, ``distributed=True``."""
+        self._refuse_angular_hessian(weights, "angular_h_loss_wrt_params")
+        names_slots = [(name, s) for name, s in tree.get_filter_spec(None, weights)]
+        if not names_slots:
+            raise ValueError("angular_h_loss_wrt_params: the deck has no fitted leaf")
+        names = [nm for nm, _ in names_slots]
+        act = [int(s) for _, s in names_slots]
+        with_m = L.P_M in act
+        eng = self.ts_diag.dlm_engine(weights.activate) if with_m else self.ts_diag.engine(weights.activate)
+        lam_step = self.ts_diag._ats_prepare(eng, batch)
+        lamE = self.ts_diag._ats_lam_axis(eng, lam_step)
+        wcol = self._angular_sum_wcol(lamE)
+        rows = eng._ats_shape[0]
+        fe = None
+        if not with_m:
+            fe = np.ascontiguousarray(np.asarray(weights()["electron"]["fe"], dtype=np.float64).reshape(-1))
+        noise = np.asarray(batch["noise_e"], dtype=np.float64)
+        noise = None if (noise.size == 1 and float(noise.reshape(-1)[0]) == 0.0) else np.broadcast_to(noise, eng._ats_shape)
+        e_amps = np.broadcast_to(np.asarray(batch["e_amps"], dtype=np.float64).reshape(-1), (rows,)).copy()
+        method = self.cfg.get("optimizer", {}).get("loss_method", "l2")
+        res = eng.angular_loss_hess(weights.X[0], act, np.ascontiguousarray(batch["e_data"], dtype=np.float64), noise, e_amps, wcol, method, fe=fe)
+        out = {"H": res["hess"].cpu().numpy(), "grad": res["grad"].cpu().numpy(), "loss": float(res["loss"].cpu().numpy()[0]),
+               "gn": res["gn"].cpu().numpy(), "leaves": names}
+        inv = np.linalg.inv(out["H"])
+        out["sigmas"] = np.sign(np.diag(inv)) * np.sqrt(np.abs(np.diag(inv)))
+        hess = {}
+        for a, (sp1, k1) in enumerate(names):
+            for b_, (sp2, k2) in enumerate(names):
+                hess.setdefault(sp1, {}).setdefault(k1, {}).setdefault(sp2, {})[k2] = out["H"][a:a + 1, b_:b_ + 1].copy()
+        out["hess"] = hess
         return out
